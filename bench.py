@@ -7,11 +7,15 @@ metric : images/s (+ p50 latency) of the whole detection hot path -- letterbox p
 N > 1  : one process per GPU (torch.distributed, backend nccl = RCCL), every rank runs its own shard of 32
          frames (weak scaling) and the per-rank detection slabs are all-gathered over xGMI each step.
          `python bench.py --gpus N` without a launcher spawns the N ranks itself (the parent never touches the GPU).
-Prints ONE JSON line on rank 0.  `roofline` is measured live with HIP events (rfd_set_profiling / rfd_stats);
-`value_host_path` is the PCIe-inclusive rate of the same workload through rfd_submit_batch / rfd_collect_batch
-(page-locked host frames in, host detections out, two batches in flight) -- reported beside `value`, never as it;
-`cpu_baseline` times the restated CPU path (plain f32 torch-CPU forward + the C oracle) on a bounded sample on
-rank 0 at N = 1.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and reports the headline figure
+(`value`, `ms_per_step`, `config`); --dump-outputs DIR also writes the detections of the last timed step as .npy files
+(seeded synthetic inputs: identical from run to run, so that two builds can be compared output for output).
+--full adds everything beside the headline figure, each leg after the timed steps:  `sustained` (>= 3 s of the same
+step), `p50_ms`, `stage_ms`; `roofline`, measured live with HIP events (rfd_set_profiling / rfd_stats) and two child
+`rocprofv3 --pmc` runs for its traffic; `value_host_path`, the PCIe-inclusive rate of the same workload through
+rfd_submit_batch / rfd_collect_batch (page-locked host frames in, host detections out, two batches in flight) --
+reported beside `value`, never as it; `cpu_baseline`, the restated CPU path (plain f32 torch-CPU forward + the C
+oracle) timed on a bounded sample on rank 0 at N = 1.
 """
 import argparse
 import json
@@ -130,7 +134,7 @@ def measure_traffic_live():
         for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, ctr)
             r = subprocess.run([exe, "--pmc", ctr, "-d", out, "--", sys.executable, os.path.abspath(__file__), "--no-cpu-baseline",
-                                "--steps", "4", "--warmup", "1"], cwd="/tmp", env=env, stdout=subprocess.DEVNULL,
+                                "--full", "--steps", "4", "--warmup", "1"], cwd=tmp, env=env, stdout=subprocess.DEVNULL,
                                stderr=subprocess.DEVNULL, timeout=240)
             if r.returncode != 0:
                 return None
@@ -157,6 +161,38 @@ def measure_traffic_live():
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def timed_outputs(slab, gslabs, gathered, world):
+    """What a caller of the timed step receives: ([(det [K,5], kps [K,5,2]) per image], total [n]) -- the local slab at
+    N = 1, every rank's slab after the all-gather (rank-major, i.e. the global image order) at N > 1."""
+    from rfd_hip import parallel
+    if gslabs is not None:
+        return gslabs.unpack()
+    if world > 1:
+        g = gathered.view(world, slab.words)
+        return parallel.unpack_gathered(slab, g), np.concatenate([slab.total(g[r]).cpu().numpy() for r in range(world)])
+    return slab.unpack(), slab.total().cpu().numpy()
+
+
+def dump_outputs(dirname, dets, totals, limit=64 << 20):
+    """--dump-outputs: boxes [n, max_det, 5] and landmarks [n, max_det, 5, 2] as float32, rows past an image's count zeroed
+    (the slab leaves them unspecified); count, total and image_index [n] as float64.  Above `limit` bytes a fixed seeded
+    sample of the images is written, in ascending image order."""
+    idx = np.arange(len(dets))
+    per_image = MAX_DET * 15 * 4 + 3 * 8
+    if len(idx) * per_image > limit:
+        idx = np.sort(np.random.default_rng(0).choice(len(idx), limit // per_image, replace=False))
+    boxes = np.zeros((len(idx), MAX_DET, 5), np.float32)
+    lmk = np.zeros((len(idx), MAX_DET, 5, 2), np.float32)
+    count = np.zeros(len(idx))
+    for j, i in enumerate(idx):
+        d, k = dets[i]
+        boxes[j, :len(d)], lmk[j, :len(d)], count[j] = d, k, len(d)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in (("boxes", boxes), ("landmarks", lmk), ("count", count), ("total", np.asarray(totals, np.float64)[idx]),
+                    ("image_index", idx.astype(np.float64))):
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: start N fresh rank processes (RANK / LOCAL_RANK / WORLD_SIZE /
     MASTER_* set) BEFORE anything in this process touches the GPU, relay rank 0's JSON line, fail if any rank fails."""
@@ -170,6 +206,7 @@ def spawn_ranks(args):
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps),
                "--warmup", str(args.warmup)] + (["--no-cpu-baseline"] if args.no_cpu_baseline else [])
+        cmd += (["--full"] if args.full else []) + (["--dump-outputs", args.dump_outputs] if args.dump_outputs else [])
         procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE if r == 0 else subprocess.DEVNULL, text=True))
     out0 = procs[0].communicate()[0]
     codes = [procs[0].returncode] + [p.wait() for p in procs[1:]]
@@ -185,6 +222,11 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: sustained window, p50 latency, host path, "
+                         "roofline, live PMC traffic, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the detections of the last timed step to DIR/<name>.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -296,110 +338,116 @@ def main():
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed = float(elapsed.item())
 
-    # sustained rate: the same step for >= 3 s of wall time (the timed loop above is a ~0.1 s burst at the driver's default
-    # K; this window is long enough for clocks / power management to settle and for an SMI sampler to see the GPU busy)
-    sustained = None
-    if os.environ.get("RFD_BENCH_SUSTAIN", "1") != "0":
-        sus_s = float(os.environ.get("RFD_BENCH_SUSTAIN_S", "3.0"))
-        chunk = max(args.steps, 10)
-        fence()
-        # (the stop decision is collective -- parallel.run_for_at_least: every step() of a multi-rank job holds an all-gather)
-        sus_elapsed, ssteps = parallel.run_for_at_least(step, lambda: (det.sync(), torch.cuda.synchronize()), sus_s, chunk, world, dev)
-        if world > 1:
-            dist.barrier()
-        sus = torch.tensor([sus_elapsed, float(ssteps)], dtype=torch.float64, device=dev)
-        if world > 1:  # whole-job figure: all ranks' images over the slowest rank's window
-            t_max = sus[:1].clone(); dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
-            n_sum = sus[1:].clone(); dist.all_reduce(n_sum, op=dist.ReduceOp.SUM)
-            sus_t, sus_n = float(t_max.item()), float(n_sum.item())
-        else:
-            sus_t, sus_n = float(sus[0].item()), float(sus[1].item())
-        sustained = {"seconds": round(sus_t, 3), "steps": int(ssteps), "images_per_s": round(BATCH * sus_n / sus_t, 2),
-                     "ms_per_step": round(sus_t / ssteps * 1e3, 4),
-                     "note": "same step() as the timed loop, synchronised every %d steps" % chunk}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *timed_outputs(slab, gslabs, gathered, world))
 
-    # p50 latency of one synchronous step (batch of 32 end to end)
-    lat = []
-    for _ in range(min(args.steps, 20)):
-        fence()
-        a = time.perf_counter()
-        step()
-        det.sync()
-        torch.cuda.synchronize()
-        lat.append((time.perf_counter() - a) * 1e3)
-    p50 = float(np.median(lat))
-
-    counts = slab.count().cpu().numpy()
+    # rfd_stats of the last synchronous pass (in a plain run the set-up pass): same frames, same candidates as the timed steps
+    stats = det.stats()
     totals = slab.total().cpu().numpy()
 
-    # PCIe-inclusive rate of the same workload (H2D of u8 frames ... D2H of detections): page-locked host
-    # frames through rfd_submit_batch / rfd_collect_batch, two batches in flight.  Reported beside `value`, never as it.
-    host_path = None
-    if world == 1 and os.environ.get("RFD_BENCH_HOST_PATH", "1") != "0":
-        hsets = []
-        for k in range(2):
-            buf = det.host_frames(BATCH, SRC_H, SRC_W)
-            for i in range(BATCH):
-                buf[i] = frames_np[i]
-            hsets.append([buf[i] for i in range(BATCH)])
-        det.submit(hsets[0]); det.submit(hsets[1]); det.collect(); det.collect()
-        hsteps = max(args.steps, 8)
-        fence()
-        h0 = time.perf_counter()
-        det.submit(hsets[0])
-        for k in range(1, hsteps):
-            det.submit(hsets[k & 1])
+    # everything beside the headline figure: only with --full
+    if args.full:
+        # sustained rate: the same step for >= 3 s of wall time (the timed loop above is a ~0.1 s burst at the driver's default
+        # K; this window is long enough for clocks / power management to settle and for an SMI sampler to see the GPU busy)
+        sustained = None
+        if os.environ.get("RFD_BENCH_SUSTAIN", "1") != "0":
+            sus_s = float(os.environ.get("RFD_BENCH_SUSTAIN_S", "3.0"))
+            chunk = max(args.steps, 10)
+            fence()
+            # (the stop decision is collective -- parallel.run_for_at_least: every step() of a multi-rank job holds an all-gather)
+            sus_elapsed, ssteps = parallel.run_for_at_least(step, lambda: (det.sync(), torch.cuda.synchronize()), sus_s, chunk, world, dev)
+            if world > 1:
+                dist.barrier()
+            sus = torch.tensor([sus_elapsed, float(ssteps)], dtype=torch.float64, device=dev)
+            if world > 1:  # whole-job figure: all ranks' images over the slowest rank's window
+                t_max = sus[:1].clone(); dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
+                n_sum = sus[1:].clone(); dist.all_reduce(n_sum, op=dist.ReduceOp.SUM)
+                sus_t, sus_n = float(t_max.item()), float(n_sum.item())
+            else:
+                sus_t, sus_n = float(sus[0].item()), float(sus[1].item())
+            sustained = {"seconds": round(sus_t, 3), "steps": int(ssteps), "images_per_s": round(BATCH * sus_n / sus_t, 2),
+                         "ms_per_step": round(sus_t / ssteps * 1e3, 4),
+                         "note": "same step() as the timed loop, synchronised every %d steps" % chunk}
+
+        # p50 latency of one synchronous step (batch of 32 end to end)
+        lat = []
+        for _ in range(min(args.steps, 20)):
+            fence()
+            a = time.perf_counter()
+            step()
+            det.sync()
+            torch.cuda.synchronize()
+            lat.append((time.perf_counter() - a) * 1e3)
+        p50 = float(np.median(lat))
+
+        # PCIe-inclusive rate of the same workload (H2D of u8 frames ... D2H of detections): page-locked host
+        # frames through rfd_submit_batch / rfd_collect_batch, two batches in flight.  Reported beside `value`, never as it.
+        host_path = None
+        if world == 1 and os.environ.get("RFD_BENCH_HOST_PATH", "1") != "0":
+            hsets = []
+            for k in range(2):
+                buf = det.host_frames(BATCH, SRC_H, SRC_W)
+                for i in range(BATCH):
+                    buf[i] = frames_np[i]
+                hsets.append([buf[i] for i in range(BATCH)])
+            det.submit(hsets[0]); det.submit(hsets[1]); det.collect(); det.collect()
+            hsteps = max(args.steps, 8)
+            fence()
+            h0 = time.perf_counter()
+            det.submit(hsets[0])
+            for k in range(1, hsteps):
+                det.submit(hsets[k & 1])
+                det.collect()
             det.collect()
-        det.collect()
-        h1 = time.perf_counter()
-        host_path = {"value_host_path": round(BATCH * hsteps / (h1 - h0), 2), "ms_per_step_host_path": round((h1 - h0) / hsteps * 1e3, 4),
-                     "steps_host_path": hsteps}
+            h1 = time.perf_counter()
+            host_path = {"value_host_path": round(BATCH * hsteps / (h1 - h0), 2), "ms_per_step_host_path": round((h1 - h0) / hsteps * 1e3, 4),
+                         "steps_host_path": hsteps}
 
-    # roofline of the dominant kernel class (implicit-GEMM convs): HIP events around every launch
-    det.set_profiling(True)
-    conv_ms, conv_flops, launches = [], 0.0, 0
-    op_ms = np.zeros(graph.num_ops)
-    reps = 5
-    for _ in range(reps):
-        det.detect_device(fptrs, shapes, pb, pl, pc, pt, async_=False)
-        ms, fl, nl = det.conv_profile()
-        conv_ms.append(ms)
-        conv_flops, launches = fl, nl
-        op_ms += det.op_profile(graph.num_ops)
-    det.set_profiling(False)
-    stats = det.stats()
-    conv_ms_med = float(np.median(conv_ms))
-    serial_tflops = conv_flops / (conv_ms_med * 1e-3) / 1e12
-    op_ms /= reps
-    # In the timed configuration the network runs as two overlapped half-batch chains (+ side streams), so single
-    # launches cannot be timed in isolation; the class is timed as a whole: HIP events on the caller's stream at the
-    # fork and after the join of the network pass (rfd_stats.ms_network), all conv FLOPs of the pass over that time.
-    net_ms = []
-    for _ in range(10):
-        det.detect_device(fptrs, shapes, pb, pl, pc, pt, async_=False)
-        net_ms.append(det.stats()["ms_network"])
-    net_ms_med = float(np.median(net_ms))
-    net_flops = 2.0 * graph.macs * BATCH
-    achieved = net_flops / (net_ms_med * 1e-3) / 1e12
+        # roofline of the dominant kernel class (implicit-GEMM convs): HIP events around every launch
+        det.set_profiling(True)
+        conv_ms, conv_flops, launches = [], 0.0, 0
+        op_ms = np.zeros(graph.num_ops)
+        reps = 5
+        for _ in range(reps):
+            det.detect_device(fptrs, shapes, pb, pl, pc, pt, async_=False)
+            ms, fl, nl = det.conv_profile()
+            conv_ms.append(ms)
+            conv_flops, launches = fl, nl
+            op_ms += det.op_profile(graph.num_ops)
+        det.set_profiling(False)
+        stats = det.stats()
+        conv_ms_med = float(np.median(conv_ms))
+        serial_tflops = conv_flops / (conv_ms_med * 1e-3) / 1e12
+        op_ms /= reps
+        # In the timed configuration the network runs as two overlapped half-batch chains (+ side streams), so single
+        # launches cannot be timed in isolation; the class is timed as a whole: HIP events on the caller's stream at the
+        # fork and after the join of the network pass (rfd_stats.ms_network), all conv FLOPs of the pass over that time.
+        net_ms = []
+        for _ in range(10):
+            det.detect_device(fptrs, shapes, pb, pl, pc, pt, async_=False)
+            net_ms.append(det.stats()["ms_network"])
+        net_ms_med = float(np.median(net_ms))
+        net_flops = 2.0 * graph.macs * BATCH
+        achieved = net_flops / (net_ms_med * 1e-3) / 1e12
 
-    # HBM traffic of the network kernels per forward pass, from the PMC counters: FETCH_SIZE and WRITE_SIZE in SEPARATE rocprofv3
-    # passes (they do not fit one pass), FETCH_SIZE x2 on gfx950 (wide reads / LDS-DMA are tallied at half their bytes), KiB ->
-    # bytes -- MI355X_MICROARCH.md, HBM section; tools/rocpd_summary.py.  Counters cannot be read from inside the process, so
-    # rank 0 runs this same script twice as a CHILD under `rocprofv3 --pmc` (4 steps each, calls ordered on one stream: under PMC
-    # every dispatch runs alone anyway) and summarises the two databases: the figure belongs to THIS run on THIS box.  If the
-    # profiler is missing, fails or times out, the last committed summary is reported and labelled as such.
-    traffic, traffic_source = None, "none"
-    if rank == 0 and world == 1 and BATCH == 32 and os.environ.get("RFD_BENCH_TRAFFIC", "live") == "live":
-        traffic = measure_traffic_live()
-        if traffic is not None:
-            traffic_source = "measured in this run: child `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes of bench.py --steps 4"
-    tpath = os.path.join(ROOT, "profiles", "hbm_traffic_latest.json")
-    if traffic is None and BATCH == 32 and os.path.exists(tpath):
-        try:
-            traffic = float(json.load(open(tpath))["conv_igemm_hbm_bytes_per_pass"])
-            traffic_source = "committed summary profiles/hbm_traffic_latest.json (tools/profile_bench.sh), not this run"
-        except Exception:
-            traffic = None
+        # HBM traffic of the network kernels per forward pass, from the PMC counters: FETCH_SIZE and WRITE_SIZE in SEPARATE rocprofv3
+        # passes (they do not fit one pass), FETCH_SIZE x2 on gfx950 (wide reads / LDS-DMA are tallied at half their bytes), KiB ->
+        # bytes -- see tools/rocpd_summary.py.  Counters cannot be read from inside the process, so
+        # rank 0 runs this same script twice as a CHILD under `rocprofv3 --pmc` (4 steps each, calls ordered on one stream: under PMC
+        # every dispatch runs alone anyway) and summarises the two databases: the figure belongs to THIS run on THIS box.  If the
+        # profiler is missing, fails or times out, the last committed summary is reported and labelled as such.
+        traffic, traffic_source = None, "none"
+        if rank == 0 and world == 1 and BATCH == 32 and os.environ.get("RFD_BENCH_TRAFFIC", "live") == "live":
+            traffic = measure_traffic_live()
+            if traffic is not None:
+                traffic_source = "measured in this run: child `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes of bench.py --steps 4"
+        tpath = os.path.join(ROOT, "profiles", "hbm_traffic_latest.json")
+        if traffic is None and BATCH == 32 and os.path.exists(tpath):
+            try:
+                traffic = float(json.load(open(tpath))["conv_igemm_hbm_bytes_per_pass"])
+                traffic_source = "committed summary profiles/hbm_traffic_latest.json (tools/profile_bench.sh), not this run"
+            except Exception:
+                traffic = None
 
     out = None
     if rank == 0:
@@ -419,47 +467,50 @@ def main():
                        "parallelism": "image-parallel x%d, RCCL all-gather of detection slabs via %s" % (world, gather_impl) if world > 1 else "single GPU",
                        "candidates_per_image": round(float(stats["candidates"]) / BATCH, 1),
                        "detections_per_image": round(float(totals.mean()), 1)},
-            "p50_ms": round(p50, 4),
-            "p50_ms_per_image": round(p50 / BATCH, 5),
-            "stage_ms": dict({k: round(stats[k], 4) for k in ("ms_preprocess", "ms_decode", "ms_sort", "ms_nms")},
-                             ms_network=round(net_ms_med, 4)),
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": traffic,
-                         "traffic_unit": "HBM bytes per forward pass of the network conv kernels (PMC: FETCH_SIZE x2 + WRITE_SIZE)",
-                         "traffic_source": traffic_source,
-                         "hbm_frac_of_8TBps": round(traffic / (net_ms_med * 1e-3) / 8e12, 4) if traffic else None,
-                         "kernel": "network conv kernels of one forward pass (stem_persistent / conv_igemm / conv_ring / conv3x3_kx / conv3x3_halo / "
-                                   "conv3x3_c64 / pw_stream / pw_gemm / pw_wide / pw_b2b / pw_pair / conv_b2b_s1), timed as a class: the two "
-                                   "half-batch chains overlap",
-                         "flops_per_pass": net_flops, "ms_per_pass": round(net_ms_med, 4),
-                         "serialised": {"note": "same pass with every op on one stream, HIP events around each of the %d "
-                                                "implicit-GEMM launches (conv0/stem excluded)" % launches,
-                                        "flops_per_pass": conv_flops, "ms_per_pass": round(conv_ms_med, 4),
-                                        "tflops": round(serial_tflops, 2),
-                                        "avg_launch_us": round(conv_ms_med * 1e3 / max(launches, 1), 2)}},
         }
-        if sustained:
-            out["sustained"] = sustained
-            out["sustained_vs_value"] = round(sustained["images_per_s"] / value, 4)
-        if host_path:
-            out.update(host_path)
-            out["host_path_note"] = ("same workload with frames in page-locked HOST memory and detections returned to the host "
-                                     "(rfd_submit_batch / rfd_collect_batch, two batches in flight, per rank); `value` is the "
-                                     "HBM-resident rate")
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(frames_np, 0.7)
-        else:
-            out["cpu_baseline"] = None
-        if os.environ.get("RFD_BENCH_OPS"):
-            rows = []
-            for i, o in enumerate(graph.ops):
-                L = graph.layers[o.layer]
-                t = graph.tensors[o.out if o.out >= 0 else (o.out2 if o.out2 >= 0 else o.outf)]
-                fl = 2.0 * o.macs * BATCH
-                rows.append("%3d %-22s k%d s%d %4d->%4d @%3dx%-3d %8.1f us %7.1f TF" % (
-                    i, L.name.decode() if o.kind != 1 else "maxpool", L.kh, L.stride, L.cin, L.cout, t.height,
-                    t.width, op_ms[i] * 1e3, fl / (op_ms[i] * 1e-3) / 1e12 if op_ms[i] > 0 else 0))
-            sys.stderr.write("\n".join(rows) + "\n")
+        if args.full:
+            out.update({
+                "p50_ms": round(p50, 4),
+                "p50_ms_per_image": round(p50 / BATCH, 5),
+                "stage_ms": dict({k: round(stats[k], 4) for k in ("ms_preprocess", "ms_decode", "ms_sort", "ms_nms")},
+                                 ms_network=round(net_ms_med, 4)),
+                "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                             "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": traffic,
+                             "traffic_unit": "HBM bytes per forward pass of the network conv kernels (PMC: FETCH_SIZE x2 + WRITE_SIZE)",
+                             "traffic_source": traffic_source,
+                             "hbm_frac_of_8TBps": round(traffic / (net_ms_med * 1e-3) / 8e12, 4) if traffic else None,
+                             "kernel": "network conv kernels of one forward pass (stem_persistent / conv_igemm / conv_ring / conv3x3_kx / conv3x3_halo / "
+                                       "conv3x3_c64 / pw_stream / pw_gemm / pw_wide / pw_b2b / pw_pair / conv_b2b_s1), timed as a class: the two "
+                                       "half-batch chains overlap",
+                             "flops_per_pass": net_flops, "ms_per_pass": round(net_ms_med, 4),
+                             "serialised": {"note": "same pass with every op on one stream, HIP events around each of the %d "
+                                                    "implicit-GEMM launches (conv0/stem excluded)" % launches,
+                                            "flops_per_pass": conv_flops, "ms_per_pass": round(conv_ms_med, 4),
+                                            "tflops": round(serial_tflops, 2),
+                                            "avg_launch_us": round(conv_ms_med * 1e3 / max(launches, 1), 2)}},
+            })
+            if sustained:
+                out["sustained"] = sustained
+                out["sustained_vs_value"] = round(sustained["images_per_s"] / value, 4)
+            if host_path:
+                out.update(host_path)
+                out["host_path_note"] = ("same workload with frames in page-locked HOST memory and detections returned to the host "
+                                         "(rfd_submit_batch / rfd_collect_batch, two batches in flight, per rank); `value` is the "
+                                         "HBM-resident rate")
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(frames_np, 0.7)
+            else:
+                out["cpu_baseline"] = None
+            if os.environ.get("RFD_BENCH_OPS"):
+                rows = []
+                for i, o in enumerate(graph.ops):
+                    L = graph.layers[o.layer]
+                    t = graph.tensors[o.out if o.out >= 0 else (o.out2 if o.out2 >= 0 else o.outf)]
+                    fl = 2.0 * o.macs * BATCH
+                    rows.append("%3d %-22s k%d s%d %4d->%4d @%3dx%-3d %8.1f us %7.1f TF" % (
+                        i, L.name.decode() if o.kind != 1 else "maxpool", L.kh, L.stride, L.cin, L.cout, t.height,
+                        t.width, op_ms[i] * 1e3, fl / (op_ms[i] * 1e-3) / 1e12 if op_ms[i] > 0 else 0))
+                sys.stderr.write("\n".join(rows) + "\n")
     if gslabs is not None:
         det.comm_destroy()
     det.set_stream(None)

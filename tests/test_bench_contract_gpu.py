@@ -4,19 +4,35 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DUMPED = ("boxes", "landmarks", "count", "total", "image_index")
 
 
-def test_bench_json_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1"],
-                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+def _bench(*extra, steps=4, warmup=1):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+                        str(warmup)] + list(extra), capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.strip()]
     assert len(lines) == 1
-    d = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+def _load(d):
+    return {n: np.load(os.path.join(d, n + ".npy")) for n in DUMPED}
+
+
+@pytest.fixture(scope="module")
+def full_run(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("dump_full"))
+    return _bench("--full", "--dump-outputs", out), out
+
+
+def test_bench_json_contract(full_run):
+    d, _ = full_run
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -44,3 +60,25 @@ def test_bench_json_contract():
         assert k in cb, k
     assert cb["kind"] in ("reference", "port") and cb["cores"] >= 1 and cb["value"] > 0
     assert d["value"] > 100 * cb["value"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_timed_outputs(full_run, tmp_path):
+    """A plain run reports the headline figure only, for the --steps it was given, and --dump-outputs writes the detections
+    of the last timed step: the same arrays as the --full run's (seeded inputs, same timed path)."""
+    d = _bench("--dump-outputs", str(tmp_path), steps=7, warmup=2)
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["n_gpus"] == 1
+    assert d["unit"] == "images/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert d["metric"] == full_run[0]["metric"]
+    assert abs(d["value"] - 32 * 1000.0 / d["ms_per_step"]) < 0.01 * d["value"]
+    for k in ("roofline", "sustained", "cpu_baseline", "p50_ms", "value_host_path"):
+        assert k not in d, k
+    got, want = _load(str(tmp_path)), _load(full_run[1])
+    assert sum(os.path.getsize(os.path.join(str(tmp_path), n + ".npy")) for n in DUMPED) <= 64 << 20
+    assert got["boxes"].shape == (32, 1024, 5) and got["landmarks"].shape == (32, 1024, 5, 2)
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["count"].sum() > 0 and (got["count"] <= got["total"]).all()
+    np.testing.assert_array_equal(got["image_index"], np.arange(32))
+    for n in ("count", "total"):
+        np.testing.assert_array_equal(got[n], want[n], err_msg=n)
+    for n in ("boxes", "landmarks"):
+        np.testing.assert_allclose(got[n], want[n], rtol=0, atol=1e-4, err_msg=n)
