@@ -1,0 +1,368 @@
+"""Every conv-path kernel the launcher can pick, on every op, against the f64 reference of tests/exact_ref.py.
+
+plan() asks the library which kernel(s) each op would run under every force_tile value (nothing is launched) and keeps one
+case per distinct kernel list.  Each case runs once on two input sets:
+- dyadic: weights k 2^-6 (|k| <= 8), biases on 2^-10, power-of-two affine scales, shifts on 2^-4, activations j 2^-4, pixels
+  0..255.  Every f32 sum and epilogue step is then exact in any order, so every bf16 output must equal RNE(v64) bit for bit;
+- random: the synthetic weights and the ReLU'd-normal activations of test_network_gpu.py.  Every decided element must match,
+  every undecided one must lie in its interval, and the undecided share of an op stays <= 10 % (the bound is not vacuous).
+Outputs are poisoned with NaN before the launch: every element the op writes must be overwritten, every other byte kept.
+
+test_plan_covers_every_kernel_instantiation: every conv-path kernel the shipped objects hold is either checked here or listed
+in UNREACHABLE_IN_PROCESS with the environment knob that alone selects it."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import exact_ref
+import torch_ref
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BUILD = os.path.join(ROOT, "rs-face-detection_amd", "build")
+LLVM = "/opt/rocm/lib/llvm/bin"
+
+# (backbone, image w, image h, images per chain, ops: None = all; "large": the stem and the 1x1 convs on maps <= 40 rows, the
+#  layers whose kernel choice changes between 5 images and a production chain of 16)
+GEOMETRIES = [
+    ("r50", 640, 640, 1, None), ("r50", 640, 640, 2, None), ("r50", 768, 480, 3, None), ("r50", 480, 352, 5, None),
+    ("r50", 96, 64, 3, None), ("r50", 32, 32, 4, None),
+    ("r50", 640, 640, 4, None),     # 25 600-pixel stride-8 maps: pw_gemm's 128 x 256 items (N = 256, >= 150 of them)
+    ("r50", 640, 640, 16, "large"),  # >= 2048 stem tiles: the persistent stem kernel (alone and with conv1 fused); stage 3's 1x1s
+    ("mnet025", 640, 640, 1, None), ("mnet025", 640, 640, 2, None), ("mnet025", 768, 480, 3, None),
+    ("mnet025", 480, 352, 5, None), ("mnet025", 96, 64, 3, None), ("mnet025", 32, 32, 4, None),
+]
+TILES = range(20)  # every force_tile value launch_conv knows (0 = the production heuristic)
+
+# conv-path kernels no in-process setting reaches: (the environment knob, read once at library load, that selects it -- None:
+# nothing does -- and why)
+UNREACHABLE_IN_PROCESS = {}
+_HALF = "pair kernel on half workgroups (A/B form)"
+_PX2 = "pair kernel, 32 pixels per wave (A/B form)"
+for _t, _why in (("4, 1", _HALF), ("4, 2", _PX2)):
+    _knob = "RFD_PAIR_HALF" if _t == "4, 1" else "RFD_PAIR_PX2"
+    for _a in ("4, 2, false, 0", "2, 2, true, 0", "2, 1, false, 4"):
+        UNREACHABLE_IN_PROCESS["pw_pair_kernel<%s, 0, %s, false>" % (_a, _t)] = (_knob, _why)
+    for _a in ("2, 1, false, 0", "1, 1, true, 0"):   # the streaming pair forms themselves need RFD_PW_PAIR=1
+        UNREACHABLE_IN_PROCESS["pw_pair_kernel<%s, 0, %s, false>" % (_a, _t)] = (_knob + " + RFD_PW_PAIR=1", _why)
+    for _a in ("1, 1, false, 0", "1, 1, false, 1"):  # launch_pw_pair<..., HALF1 = true> instantiates its env branch, never takes it
+        UNREACHABLE_IN_PROCESS["pw_pair_kernel<%s, 0, %s, false>" % (_a, _t)] = (None, "dead instantiation: the stage-1 pair "
+                                                                              "form has no half / px2 variant")
+UNREACHABLE_IN_PROCESS.update({
+    "pw_pair_kernel<2, 1, false, 0, 0, 8, 1, false>": ("RFD_PW_PAIR=1", "pair kernel instead of pw_b2b for stage 2 (A/B)"),
+    "pw_pair_kernel<1, 1, true, 0, 0, 8, 1, false>": ("RFD_PW_PAIR=1", "streaming pair at the stage 1 -> 2 boundary (A/B)"),
+    "pw_b2b_kernel<1, true>": ("RFD_PW_PAIR=2", "streaming pw_b2b at the stage 1 -> 2 boundary (A/B)"),
+    "conv0_kernel": (None, "no graph emits OP_CONV0 since the fused stem (OP_STEM) replaced conv0 + pool"),
+    "maxpool_kernel": (None, "no graph emits OP_POOL since the fused stem (OP_STEM) replaced conv0 + pool"),
+    "conv_ring_kernel<false, true>": (None, "chunk-major K without merged kx: a halo-shape layer with W < 3, which has W >= 16"),
+})
+for _f in ("1, true, false", "1, true, true", "2, true, true", "4, true, true"):
+    UNREACHABLE_IN_PROCESS["pw_stream_kernel<%s>" % _f] = ("RFD_FUSE_ACT_STAGES / RFD_B2B_STAGES", "a conv3 that stores its raw "
+                                                        "sum outside a back-to-back op: the default graph has none of that shape")
+for _cfg in ("128, 64, 4, 1, 2", "128, 32, 4, 1, 2", "256, 64, 4, 1, 2", "128, 128, 2, 2, 3"):
+    # chunk-major K order is set only for halo-shape layers (3x3 s1, Cout % 128 == 0 or 192, W >= 16); launch_conv sends those to
+    # the halo / merged-kx kernels or to the force_tile 1 / 2 / 18 generic forms, never to these tiles
+    UNREACHABLE_IN_PROCESS["conv_igemm_kernel<%s, true>" % _cfg] = (None, "chunk-major form of a tile no halo-shape layer reaches")
+
+NAN_BF16 = 0x7FC0
+NAN_F32 = 0x7FC00000
+
+
+def _bb(rfd, name):
+    return rfd.BACKBONE_R50 if name == "r50" else rfd.BACKBONE_MNET025
+
+
+def plan(det, g, n, ops=None):
+    """[(op, kernel names, force_tile, last op of the run)]: one case per distinct kernel list of every op.  The stem and the
+    conv behind it run as ONE launch when the library fuses them (reported as "(fused into ...)" for the conv): that case runs
+    both ops and checks both outputs."""
+    cases = []
+    idx = range(len(g.ops)) if ops is None else [i for i, o in enumerate(g.ops) if o.kind == 3 or (
+        o.kind in (2, 6) and g.layers[o.layer].kh == 1 and g.tensors[o.in_].height <= 40)]
+    try:
+        for i in idx:
+            seen = set()
+            for tile in TILES:
+                det.debug_set_conv_tile(tile)
+                names = tuple(det.debug_op_kernels(n, i, co_running=False))
+                if names[0].startswith("(fused into") or names in seen:
+                    continue
+                seen.add(names)
+                last = i
+                if g.ops[i].kind == 3 and i + 1 < len(g.ops):
+                    if det.debug_op_kernels(n, i + 1, co_running=False)[0].startswith("(fused into"):
+                        last = i + 1
+                cases.append((i, names, tile, last))
+    finally:
+        det.debug_set_conv_tile(0)
+    return cases
+
+
+def _dyadic_weights(det, g, rng):
+    """Ops whose second conv reads the op's own stored output (the stem + fused conv1, the back-to-back pairs) keep that
+    operand on a coarse grid: the stem's bias on 2^-6, affine scales +-1 on the stored output, small second-conv weights.
+    ExactRef(exact=True) asserts that every sum stays exact in f32."""
+    feeds = {o.layer for o in g.ops if o.kind in (3, 6)}
+    second = {o.layer_b for o in g.ops if o.kind == 6}
+    for i, L in enumerate(g.layers):
+        w, b = det.get_layer(i, L)
+        k = 2 if i in second else 8
+        bias = rng.integers(-64, 65, size=b.shape) * 2.0 ** -6 if L.kind == 3 else rng.integers(-512, 513, size=b.shape) * 2.0 ** -10
+        det.set_layer(i, rng.integers(-k, k + 1, size=w.shape) * 2.0 ** -6, bias)
+        if L.has_affine:
+            s = rng.choice([1.0, -1.0] if i in feeds else [1.0, 0.5, 0.25, -0.5], size=L.cout)
+            det.set_affine(i, s, rng.integers(-16, 17, size=L.cout) * 2.0 ** -4)
+
+
+def _act(rng, n, td, signed, dyadic):
+    shape = (n, td.channels_logical, td.height, td.width)
+    if dyadic:
+        return torch.from_numpy(rng.integers(-15 if signed else 0, 16, size=shape) * 2.0 ** -4)
+    x = rng.normal(0, 1, size=shape).astype(np.float32)
+    if not signed:
+        x = np.maximum(x, 0)
+    return torch.from_numpy(x).to(torch.bfloat16).double()
+
+
+def _inputs(rng, g, o, n, dyadic):
+    L = g.layers[o.layer]
+    tin = g.tensors[o.in_]
+    tens = {}
+    if o.kind in (0, 3, 5):
+        x = rng.integers(0, 256, size=(n, 4, tin.height, tin.width)).astype(np.float64)
+        x[:, 3] = 0
+        tens[o.in_] = torch.from_numpy(x)
+    else:
+        tens[o.in_] = _act(rng, n, tin, o.in_affine >= 0, dyadic)
+    if o.in2 >= 0:
+        tens[o.in2] = _act(rng, n, g.tensors[o.in2], False, dyadic)
+    if o.res >= 0:
+        tens[o.res] = _act(rng, n, g.tensors[o.res], True, dyadic)
+    if o.out >= 0 and o.out != o.in_ and g.tensors[o.out].channels_logical != L.cout:
+        tens[o.out] = _act(rng, n, g.tensors[o.out], False, dyadic)   # SSH concat slice: the untouched channels keep these
+    return tens
+
+
+def _dev(t, td):
+    return torch_ref.nchw_to_dev(t.float(), channels=td.channels)
+
+
+def _to_f64(a, is_f32):
+    if is_f32:
+        return torch.from_numpy(a.astype(np.float64)).permute(0, 3, 1, 2)
+    return torch.from_numpy((a.astype(np.uint32) << 16).view(np.float32).astype(np.float64)).permute(0, 3, 1, 2)
+
+
+def _first_bad(bad):
+    pos = np.argwhere(bad.numpy())
+    return [tuple(int(v) for v in p) for p in pos[:3]]
+
+
+class Sweep:
+    def __init__(self, det, g, geo, n):
+        self.det, self.g, self.geo, self.n = det, g, geo, n
+        self.fail = []
+        self.cases = 0
+        self.names = set()
+        self.ties = [0, 0]
+        self.undecided = 0.0
+        self.ratio = 0.0
+        self._cache = {}
+
+    def run_set(self, cases, dyadic, seed):
+        det, g, n = self.det, self.g, self.n
+        ref = exact_ref.ExactRef(g, det)
+        ref.radius, ref.exact = not dyadic, dyadic
+        tag = "dyadic" if dyadic else "random"
+        rng = np.random.default_rng(seed)
+        by_op = {}
+        for c in cases:
+            by_op.setdefault(c[0], []).append(c)
+        for i, ocases in by_op.items():
+            o = g.ops[i]
+            tens = _inputs(rng, g, o, n, dyadic)
+            with torch.no_grad():
+                want = ref.run_op(i, tens)
+            if dyadic:
+                for t, w in want.items():
+                    if not w.is_f32:
+                        d, u = exact_ref.bf16_ties(w.v)
+                        self.ties[0] += d
+                        self.ties[1] += u
+            else:
+                und = [float((w.lo != w.hi).double().mean()) for w in want.values() if not w.is_f32]
+                if und:
+                    self.undecided = max(self.undecided, max(und))
+                    if max(und) > 0.10:
+                        self.fail.append("op %d: %.1f %% of the outputs undecided: the radius is too wide" % (i, 100 * max(und)))
+            self._cache.clear()
+            for (_, names, tile, last) in ocases:
+                self.cases += 1
+                self.names.update(names)
+                self._run_case(ref, i, tens, want, names, tile, last, tag)
+
+    def _run_case(self, ref, i, tens, want, names, tile, last, tag):
+        det, g, n = self.det, self.g, self.n
+        o = g.ops[i]
+        det.debug_set_conv_tile(tile)
+        for t, x in tens.items():
+            det.debug_write(t, _dev(x, g.tensors[t]))
+        outs = [(t, i) for t in (o.out, o.out2, o.outf, o.out_b) if t >= 0]
+        if last > i:
+            outs.append((g.ops[last].out, last))
+        prior = {}
+        for t, _ in outs:
+            td = g.tensors[t]
+            if t in tens:
+                a = _dev(tens[t], td).copy()
+            else:
+                a = np.zeros((n, td.height, td.width, td.channels), np.float32 if td.is_f32 else np.uint16)
+            written = want[t].dst if (t in want and want[t].dst is not None) else np.arange(td.channels_logical)
+            if t == o.in_:
+                assert not set(written) & set(range(o.x_coff, o.x_coff + g.layers[o.layer].cin)), "in-place op overwrites its input"
+            pa = a.view(np.uint32) if td.is_f32 else a
+            pa[..., written] = NAN_F32 if td.is_f32 else NAN_BF16
+            det.debug_write(t, a)
+            prior[t] = (a.copy(), written)
+        det.debug_run(n, i, last)
+        det.debug_set_conv_tile(0)
+        what = "op %d (%s, kind %d) kernel %s (tile %d) at %s n = %d, %s set" % (
+            i, g.layers[o.layer].name.decode(), o.kind, " + ".join(names), tile, self.geo, n, tag)
+        for t, oi in outs:
+            td = g.tensors[t]
+            got = det.debug_read(t, n, td)
+            a, written = prior[t]
+            keep = np.setdiff1d(np.arange(td.channels), written)
+            if not np.array_equal(np.ascontiguousarray(got[..., keep]).view(np.uint8), np.ascontiguousarray(a[..., keep]).view(np.uint8)):
+                self.fail.append("%s tensor %d: bytes outside the op's channels changed" % (what, t))
+            g64 = _to_f64(got[..., written], td.is_f32)
+            if t in want and oi == i:
+                w = want[t]
+            else:   # read from the device's own stored first output: out_b of a b2b op, or the conv fused into the stem kernel
+                src = o.out if (oi == i and o.out >= 0) else (o.out2 if oi == i else g.ops[oi].in_)
+                st = g.tensors[src]
+                raw = det.debug_read(src, n, st)
+                key = (t, raw.tobytes())
+                if key not in self._cache:
+                    first = _to_f64(raw[..., :st.channels_logical], False)
+                    with torch.no_grad():
+                        self._cache[key] = ref.b2b_second(i, first) if oi == i else ref.run_op(oi, {src: first})[t]
+                w = self._cache[key]
+            if td.is_f32:
+                bad, ratio = exact_ref.check_f32(g64, w)
+                self.ratio = max(self.ratio, ratio)
+            else:
+                bad, _ = exact_ref.check_bf16(g64, w)
+            if bool(bad.any()):
+                p = _first_bad(bad)
+                b0 = p[0]
+                ex = (g64[b0] - w.v[b0]).abs() / max(float(w.rad[b0]), 1e-300)
+                self.fail.append("%s tensor %d: %d / %d elements wrong, first at (n, c, y, x) %s: got %r, legal [%r, %r], v64 %r "
+                                 "(%.3g r from v64)" % (what, t, int(bad.sum()), bad.numel(), p, float(g64[b0]), float(w.lo[b0]),
+                                                        float(w.hi[b0]), float(w.v[b0]), float(ex)))
+
+
+@pytest.mark.parametrize("geom", GEOMETRIES, ids=["%s-%dx%d-n%d%s" % (b, w, h, n, "-" + o if o else "") for b, w, h, n, o in GEOMETRIES])
+def test_every_kernel_matches_the_f64_reference(rfd, geom):
+    bb, w, h, n, ops = geom
+    det = rfd.RetinaFaceDetection(image_size=(w, h), max_batch_size=n, max_det=16, backbone=_bb(rfd, bb))
+    try:
+        det.init_synthetic_weights(1234)
+        g = rfd.Graph(_bb(rfd, bb), w, h)
+        cases = plan(det, g, n, ops)
+        sw = Sweep(det, g, "%s %dx%d" % (bb, w, h), n)
+        sw.run_set(cases, dyadic=False, seed=11)
+        _dyadic_weights(det, g, np.random.default_rng(12))
+        sw.run_set(cases, dyadic=True, seed=13)
+        print("\nexact sweep %s %dx%d n=%d: %d cases, %d kernel names, %d failures, ties %d down / %d up, "
+              "max undecided %.2f %%, head |got - v64| / r max %.3f" % (bb, w, h, n, sw.cases // 2, len(sw.names), len(sw.fail),
+                                                                        sw.ties[0], sw.ties[1], 100 * sw.undecided, sw.ratio))
+        assert not sw.fail, "\n".join(sw.fail[:12]) + ("\n... %d more" % (len(sw.fail) - 12) if len(sw.fail) > 12 else "")
+        if ops is None:
+            assert min(sw.ties) >= 200 and sum(sw.ties) >= 2000, sw.ties   # the dyadic set must really exercise ties-to-even
+        if bb == "r50" and ops is None:
+            assert 0 < sw.ratio <= 1.0, sw.ratio
+    finally:
+        det.close()
+
+
+def _shipped_kernels(tmp):
+    names = set()
+    for f in ("kernels_conv", "kernels_ring"):
+        obj = os.path.join(BUILD, f + ".o")
+        fat, co = os.path.join(tmp, f + ".fat"), os.path.join(tmp, f + ".co")
+        subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", obj, fat], check=True)
+        subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
+                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], check=True)
+        txt = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True, text=True).stdout
+        mangled = re.findall(r"^\s+\.name:\s+(_Z\S+)", txt, re.M)
+        filt = os.path.join(LLVM, "llvm-cxxfilt")
+        filt = filt if os.path.exists(filt) else "c++filt"
+        out = subprocess.run([filt], input="\n".join(mangled), check=True, capture_output=True, text=True).stdout
+        for line in out.splitlines():
+            s = re.sub(r"^void ", "", line.strip()).replace("rfd::", "")
+            names.add(s[:s.rindex("(")] if s.endswith(")") else s)
+    names.discard("heads_to_nchw_kernel")   # post-network layout kernel, not a conv path
+    return names
+
+
+def test_plan_covers_every_kernel_instantiation(rfd, tmp_path):
+    shipped = _shipped_kernels(str(tmp_path))
+    assert len(shipped) >= 70, sorted(shipped)
+    reached = set()
+    for bb, w, h, n, ops in GEOMETRIES:
+        det = rfd.RetinaFaceDetection(image_size=(w, h), max_batch_size=n, max_det=16, backbone=_bb(rfd, bb))
+        try:
+            det.init_synthetic_weights(1234)
+            g = rfd.Graph(_bb(rfd, bb), w, h)
+            for _, names, _, _ in plan(det, g, n, ops):
+                reached.update(names)
+        finally:
+            det.close()
+    unknown = reached - shipped
+    assert not unknown, "plan() names kernels the objects do not hold (name format drift?): %s" % sorted(unknown)
+    missing = shipped - reached - set(UNREACHABLE_IN_PROCESS)
+    assert not missing, "kernels without an exact-reference check: %s" % sorted(missing)
+    stale = set(UNREACHABLE_IN_PROCESS) & reached
+    assert not stale, "UNREACHABLE_IN_PROCESS entries the plan does reach: %s" % sorted(stale)
+    gone = set(UNREACHABLE_IN_PROCESS) - shipped
+    assert not gone, "UNREACHABLE_IN_PROCESS entries the objects no longer hold: %s" % sorted(gone)
+    print("\ncoverage: %d shipped conv-path kernels, %d checked, %d env-only" % (len(shipped), len(reached), len(UNREACHABLE_IN_PROCESS)))
+
+
+BATCH_RUNS = {"r50": [(640, 640), (768, 480)], "mnet025": [(640, 640)]}
+
+
+@pytest.mark.parametrize("bb,w,h", [(b, w, h) for b, gs in BATCH_RUNS.items() for w, h in gs])
+def test_heads_do_not_depend_on_the_batch_size(rfd, bb, w, h):
+    """one K order per layer whatever kernel runs it, so a frame's 9 head tensors are bit-identical whether it
+    runs alone (B = 1), in small split batches, or inside a 32-frame batch (two 16-image chains, persistent kernels, stem+conv1
+    fusion)."""
+    det = rfd.RetinaFaceDetection(image_size=(w, h), max_batch_size=32, max_det=16, backbone=_bb(rfd, bb))
+    try:
+        det.init_synthetic_weights(1234)
+        rng = np.random.default_rng(21)
+        frames = rng.uniform(-1.0, 1.0, size=(32, 3, h, w)).astype(np.float32)
+        alone = [det.forward(frames[k:k + 1]) for k in range(6)]
+        runs = []
+        for bs in (2, 3, 8):
+            for s0 in range(0, 6, bs):
+                batch = frames[[(s0 + j) % 32 if s0 + j < 6 else 6 + j for j in range(bs)]]
+                heads = det.forward(batch)
+                runs += [("B=%d" % bs, s0 + j, [x[j:j + 1] for x in heads]) for j in range(bs) if s0 + j < 6]
+        big = frames.copy()
+        big[26:32] = frames[0:6]
+        heads = det.forward(big)
+        runs += [("B=32 pos %d" % j, j, [x[j:j + 1] for x in heads]) for j in range(6)]
+        runs += [("B=32 pos %d" % (26 + j), j, [x[26 + j:27 + j] for x in heads]) for j in range(6)]
+        for tag, k, hs in runs:
+            for lvl, (a, b) in enumerate(zip(hs, alone[k])):
+                assert np.array_equal(a, b), "%s %dx%d frame %d, %s: head tensor %d differs from the B = 1 run (%d elements)" % (
+                    bb, w, h, k, tag, lvl, int((a != b).sum()))
+    finally:
+        det.close()

@@ -57,6 +57,7 @@ def test_every_op_in_isolation(rfd, net, tile):
     rng = np.random.default_rng(99)
     n = 2
     exact = []
+    per_op = {}
     for i, o in enumerate(g.ops):
         if tile == 2 and (o.kind != 2 or g.layers[o.layer].cout % 128 or o.layer_n2 >= 0):  # (kind 6 has its own kernel)
             continue
@@ -88,8 +89,12 @@ def test_every_op_in_isolation(rfd, net, tile):
             td = g.tensors[t]
             got = torch_ref.dev_to_nchw(det.debug_read(t, n, td), bool(td.is_f32), td.channels_logical)
             exact.append(_check_close(got, tens[t], "op %d (%s) tensor %d" % (i, g.layers[o.layer].name.decode(), t)))
+            if not td.is_f32:   # f32 heads: torch's own f32 order differs in the last bits (checked against f64 in test_conv_exact_gpu)
+                per_op.setdefault(i, []).append(exact[-1])
     det.debug_set_conv_tile(0)
     assert np.mean(exact) > 0.97  # nearly every bf16 output is bit-identical to the torch result
+    worst = min(per_op, key=lambda i: min(per_op[i]))
+    assert min(per_op[worst]) > 0.97, "op %d: only %.4f of the bf16 outputs equal the torch result" % (worst, min(per_op[worst]))
 
 
 def test_batch_tail_rows(rfd, net):
@@ -163,8 +168,7 @@ def test_fused_pipeline_matches_oracle_on_same_heads(rfd, oracle, net):
         gdet, glmk = got[b]
         assert len(gdet) == len(odet) == det.last_total[b] and len(odet) >= 1
         assert np.array_equal(gdet[:, 4], odet[:, 4])                       # same anchors, same order
-        np.testing.assert_allclose(gdet[:, :4], odet[:, :4], rtol=0, atol=1e-4)
-        np.testing.assert_allclose(glmk, olmk, rtol=0, atol=1e-4)
+        assert np.array_equal(gdet, odet[:, :5]) and np.array_equal(glmk, olmk)  # the post-network path is bit-identical
     # the single-image entry point (`call`) returns the same rows as the batch
     d0, k0 = det.call(frames[0])
     assert np.array_equal(d0, got[0][0]) and np.array_equal(k0, got[0][1])

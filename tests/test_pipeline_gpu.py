@@ -90,8 +90,7 @@ def test_pipelined_matches_oracle(rfd, oracle, backbone, n):
         for i, ((gd, gk), (od, ok)) in enumerate(zip(g, w)):
             assert len(gd) == len(od), (bi, i)
             assert np.array_equal(gd[:, 4], od[:, 4]), (bi, i)
-            np.testing.assert_allclose(gd[:, :4], od[:, :4], rtol=0, atol=1e-4)
-            np.testing.assert_allclose(gk, ok, rtol=0, atol=1e-4)
+            assert np.array_equal(gd, od) and np.array_equal(gk, ok), (bi, i)
     det.close()
 
 
