@@ -188,9 +188,6 @@ struct B2BParams {
     int force_tile;            // as ConvParams::force_tile (6: persistent form forced, 7 / 1 / 2: never)
 };
 int launch_conv_b2b_s1(const B2BParams &p, hipStream_t s);
-// conv0: 7x7 stride 2 pad 3 on the NHWC4 input, fused bias + ReLU -> [B][H/2][W/2][64]
-int launch_conv0(const bf16_t *x4, const bf16_t *w, const float *bias, bf16_t *y, int B, int H,
-                 int W, hipStream_t s);
 // fused stem: conv0 (7x7/2 + bias + ReLU) -> 3x3/2 max pool -> affine + ReLU, NHWC4 in, [B][H/4][W/4][64] out
 // w1 / bias1 / t1 / fused (all or none): the first unit's conv1 (1x1, 64 -> 64, bias + ReLU) computed on the pooled tile and stored to
 // t1 when the persistent form runs; *fused tells the caller whether it was (then the conv's own op must not run)
@@ -202,10 +199,6 @@ int launch_first3x3(const bf16_t *x4, const bf16_t *w, const float *bias, bf16_t
                     hipStream_t s);
 int launch_dwconv3x3(const bf16_t *x, const bf16_t *w, const float *bias, bf16_t *y, int B, int H, int W, int C,
                      int stride, hipStream_t s);
-// 3x3 stride 2 pad 1 max pool, NHWC bf16
-// optional fused per-channel affine + ReLU on the pooled value (scale/shift may be null)
-int launch_maxpool3x3s2(const bf16_t *x, bf16_t *y, const float *scale, const float *shift, int B, int H,
-                        int W, int C, hipStream_t s);
 // head tensors [B][h][w][32] f32 (cls4 bbox8 lmk20) -> reference NCHW contract (rfd_forward)
 int launch_heads_to_nchw(const float *h32, float *cls, float *bbox, float *lmk, int B, int fh,
                          int fw, hipStream_t s);

@@ -799,19 +799,10 @@ extern "C" __attribute__((visibility("default"))) int rfd_debug_pair_prof(unsign
 #else
 #define RFD_STAMP(i) do { } while (0)
 #endif
-// NW (round 4): waves per workgroup.  8 = the form above (128-pixel tiles, one workgroup per CU, the weight stream a whole chunk
-// ahead in an S + 1 slot ring, one drain per chunk).  4 = HALF workgroups: 64-pixel tiles, a 2-slot weight ring with the next
-// step issued one step ahead and drained at the top of every step (conv_igemm's scheme: the L2-served 16-KiB step lands in
-// ~170 ns, tools/ring_fill_bench.hip), 45 KiB of LDS -- so TWO workgroups share a CU and run out of phase: one's chunk epilogue
-// (VALU, 27 % of a wave's lifetime with the matrix pipe idle) and barrier stalls fall under the other's MFMA steps.  Each wave
-// still owns 16 pixels with the same arithmetic in the same order: bit-identical.
-// PX (round 4): 16-pixel groups per wave.  2 = a wave owns 32 pixels: every weight fragment read from LDS feeds TWO MFMAs (the
-// 16-pixel forms read one fragment per MFMA -- 8 MiB of LDS reads per 128 pixels, as many LDS cycles as the tile has MFMA cycles);
-// 4 waves x 32 pixels, one wave per SIMD with up to 512 registers, the deep ring.
 // HALF1 (round 4): conv1 has 64 outputs (stage 1's units: 256 -> 64).  W1's 64 rows fill the first half of a slot (the other
 // half is never staged nor read), conv1 runs 4 row blocks per step instead of 8, t1's row pitch is 64.
-template <int NK, int N1B, bool ACT_OUT, int NK2 = 0, int NCR = 0, int NW = 8, int PX = 1, bool HALF1 = false>
-__global__ void __launch_bounds__(NW * 64, PX == 2 ? 1 : 2) pw_pair_kernel(const ConvParams p) // PX 1: 2 waves per SIMD (256 registers: two half workgroups fit a CU)
+template <int NK, int N1B, bool ACT_OUT, int NK2 = 0, int NCR = 0, bool HALF1 = false>
+__global__ void __launch_bounds__(512, 2) pw_pair_kernel(const ConvParams p) // 2 waves per SIMD
 {
     RFD_CLOCK(3);
 #ifdef RFD_PAIR_STAMPS
@@ -819,11 +810,9 @@ __global__ void __launch_bounds__(NW * 64, PX == 2 ? 1 : 2) pw_pair_kernel(const
     const unsigned long long tstart = tlast;
 #endif
     constexpr bool RESIDENT = NCR > 0;
-    constexpr bool SHORT = NW == 4 && PX == 1; // 2-slot ring, one step of lead, a drain per step
-    static_assert((NW == 8 && PX == 1) || (NW == 4 && !RESIDENT && (PX == 1 || PX == 2)), "8 waves x 16 px, 4 x 16 (short ring) or 4 x 32");
-    constexpr int BM = 16 * NW * PX, NT = 64 * NW, PQ = 16 / NW; // pixels per tile, threads, weight pieces per wave and step
-    static_assert(!HALF1 || (N1B == 1 && NW == 8), "64-output conv1: one (half) row block, 8 waves");
-    constexpr int NKT = NK + NK2, S = NKT + 2 * N1B, WSLOTS = RESIDENT ? NCR * S : (SHORT ? 2 : S + 1), N1 = HALF1 ? 64 : 128 * N1B;
+    constexpr int BM = 128, NT = 512, PQ = 2; // pixels per tile (8 waves x 16), threads, weight pieces per wave and step
+    static_assert(!HALF1 || N1B == 1, "64-output conv1: one (half) row block");
+    constexpr int NKT = NK + NK2, S = NKT + 2 * N1B, WSLOTS = RESIDENT ? NCR * S : S + 1, N1 = HALF1 ? 64 : 128 * N1B;
     constexpr int RB1 = HALF1 ? 4 : 8; // 16-row blocks of a W1 slot-step that hold filter rows
     constexpr bool HAS_RES = NK2 == 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -859,7 +848,7 @@ __global__ void __launch_bounds__(NW * 64, PX == 2 ? 1 : 2) pw_pair_kernel(const
     uint32_t woff[PQ], woff1[PQ];
 #pragma unroll
     for (int q = 0; q < PQ; ++q) {
-        const int rho = (wave + NW * q) * 8 + lr;
+        const int rho = (wave + 8 * q) * 8 + lr;
         const int rw_ = rho & 63, i_ = rw_ >> 4, fq_ = (rw_ >> 2) & 3, r_ = rw_ & 3;
         const int chn = (rho - rw_) + (i_ >> 1) * 32 + fq_ * 8 + (i_ & 1) * 4 + r_;
         woff[q] = (uint32_t)(((size_t)chn * KT + chunk * 8) * 2);
@@ -876,43 +865,36 @@ __global__ void __launch_bounds__(NW * 64, PX == 2 ? 1 : 2) pw_pair_kernel(const
                                : w1_delta + (uint32_t)((((size_t)r1 * 128) * N + (wi_nc << 7) + (k1 << 6)) * 2);
 #pragma unroll
         for (int q = 0; q < PQ; ++q) {
-            if (HALF1 && !w3 && q * NW >= 8) continue; // slot rows 64 .. 127 of a 64-row W1: nothing there (NW = 8: pieces q >= 1)
-            blds16(rw, w3 ? woff[q] : woff1[q], (uint32_t)__builtin_amdgcn_readfirstlane(so), dst + (wave + NW * q) * 512);
+            if (HALF1 && !w3 && q >= 1) continue; // slot rows 64 .. 127 of a 64-row W1: nothing there
+            blds16(rw, w3 ? woff[q] : woff1[q], (uint32_t)__builtin_amdgcn_readfirstlane(so), dst + (wave + 8 * q) * 512);
         }
         if (++wi_s == S) { wi_s = 0; if (++wi_nc == NC) wi_nc = 0; }
         wi_slot = wi_slot + 1 == WSLOTS ? 0 : wi_slot + 1;
     };
     // this lane: pixel row wave*16 + frow of the tile; per chunk its four 8-channel groups h*32 + fq*8 (h = 0..3)
-    // (pixel group g of the wave: tile rows (wave * PX + g) * 16 + frow)
-    auto issue_res = [&](u32x4 (&r)[PX][4], int mt, int nc) {
+    auto issue_res = [&](u32x4 (&r)[4], int mt, int nc) {
         if (!HAS_RES) return;
+        const int m = mt * BM + wave * 16 + frow;
+        const bool ok = mt < tiles_m && m < M;
 #pragma unroll
-        for (int g = 0; g < PX; ++g) {
-            const int m = mt * BM + (wave * PX + g) * 16 + frow;
-            const bool ok = mt < tiles_m && m < M;
-#pragma unroll
-            for (int h = 0; h < 4; ++h)
-                asm_buffer_load_b128(r[g][h], ok ? (uint32_t)(((size_t)m * N + (nc << 7) + h * 32 + fq * 8) * 2) : kOob, rres);
-        }
+        for (int h = 0; h < 4; ++h)
+            asm_buffer_load_b128(r[h], ok ? (uint32_t)(((size_t)m * N + (nc << 7) + h * 32 + fq * 8) * 2) : kOob, rres);
     };
-    u32x4 xq[PX][NKT * 2]; // the activation tile of this wave as B fragments: K slice q = channels q*32 + fq*8 .. +7 of pixel `frow`
+    u32x4 xq[NKT * 2]; // the activation tile of this wave as B fragments: K slice q = channels q*32 + fq*8 .. +7 of pixel `frow`
     auto issue_x = [&](int mt) {
+        const int m = mt * BM + wave * 16 + frow;
+        const bool ok = mt < tiles_m && m < M;
 #pragma unroll
-        for (int g = 0; g < PX; ++g) {
-            const int m = mt * BM + (wave * PX + g) * 16 + frow;
-            const bool ok = mt < tiles_m && m < M;
+        for (int q = 0; q < NK * 2; ++q) asm_buffer_load_b128(xq[q], ok ? (uint32_t)(((size_t)m * K + q * 32 + fq * 8) * 2) : kOob, rxs);
+        if (NK2) { // the shortcut's source pixel: (b, stride2 * ho, stride2 * wo) of x2
+            const int HoWo = p.Ho * p.Wo, mm = ok ? m : 0, b = mm / HoWo, rem = mm - b * HoWo, ho = rem / p.Wo, wo = rem - ho * p.Wo;
+            const uint32_t base = (uint32_t)(((((size_t)b * p.H2 + ho * p.stride2) * p.W2 + wo * p.stride2) * p.Cin2 + fq * 8) * 2);
 #pragma unroll
-            for (int q = 0; q < NK * 2; ++q) asm_buffer_load_b128(xq[g][q], ok ? (uint32_t)(((size_t)m * K + q * 32 + fq * 8) * 2) : kOob, rxs);
-            if (NK2) { // the shortcut's source pixel: (b, stride2 * ho, stride2 * wo) of x2
-                const int HoWo = p.Ho * p.Wo, mm = ok ? m : 0, b = mm / HoWo, rem = mm - b * HoWo, ho = rem / p.Wo, wo = rem - ho * p.Wo;
-                const uint32_t base = (uint32_t)(((((size_t)b * p.H2 + ho * p.stride2) * p.W2 + wo * p.stride2) * p.Cin2 + fq * 8) * 2);
-#pragma unroll
-                for (int q = 0; q < NK2 * 2; ++q) asm_buffer_load_b128(xq[g][NK * 2 + q], ok ? base + (uint32_t)(q * 64) : kOob, rxs2);
-            }
+            for (int q = 0; q < NK2 * 2; ++q) asm_buffer_load_b128(xq[NK * 2 + q], ok ? base + (uint32_t)(q * 64) : kOob, rxs2);
         }
     };
 
-    u32x4 resA[PX][4] = {}, resB[PX][4] = {};
+    u32x4 resA[4] = {}, resB[4] = {};
     if (RESIDENT) { // the whole of both filter banks, once: NCR chunks x S steps fill the NCR * S slots in consumption order
         for (int i = 0; i < WSLOTS; ++i) issue_w();
         wait_vmcnt<0>();
@@ -922,37 +904,30 @@ __global__ void __launch_bounds__(NW * 64, PX == 2 ? 1 : 2) pw_pair_kernel(const
     issue_res(resA, blockIdx.x, 0);
     if (!RESIDENT) {
 #pragma unroll
-        for (int i = 0; i < (SHORT ? 1 : S); ++i) issue_w(); // the first chunk's steps (SHORT: the first step)
+        for (int i = 0; i < S; ++i) issue_w(); // the first chunk's steps
     }
     int cslot = 0;
     const int arow = frow * 64; // A fragment of row block i: row i*16 + frow; 16-byte slot (kk*4 + fq) ^ (row & 7), row & 7 = frow & 7
 
     for (int mt = blockIdx.x; mt < tiles_m; mt += gridDim.x) {
-        f32x4 acc1[PX][8 * N1B];
+        f32x4 acc1[8 * N1B];
 #pragma unroll
-        for (int g = 0; g < PX; ++g)
-#pragma unroll
-            for (int i = 0; i < 8 * N1B; ++i) acc1[g][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < 8 * N1B; ++i) acc1[i] = f32x4{0.f, 0.f, 0.f, 0.f};
         // the tile's activation fragments (requested during the previous tile's last chunk, or before the loop) and everything older
         asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
         // ... and xq[] is only defined from here on: tied to the wait as cur[] is below, so that no copy of a fragment register
         // hipcc might make (a phi across the back edge, a spill-free re-allocation) can be taken before the loads have landed
         // (volatile asm statements keep their order; round-3 advisor finding)
 #pragma unroll
-        for (int g = 0; g < PX; ++g)
+        for (int q = 0; q < NKT * 2; ++q) asm volatile("" : "+v"(xq[q]));
+        auto do_chunk = [&](int nc, u32x4 (&cur)[4], u32x4 (&nxt)[4], bool last_chunk) __attribute__((always_inline)) {
+            f32x4 acc[8];
 #pragma unroll
-            for (int q = 0; q < NKT * 2; ++q) asm volatile("" : "+v"(xq[g][q]));
-        auto do_chunk = [&](int nc, u32x4 (&cur)[PX][4], u32x4 (&nxt)[PX][4], bool last_chunk) __attribute__((always_inline)) {
-            f32x4 acc[PX][8];
-#pragma unroll
-            for (int g = 0; g < PX; ++g)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) acc[g][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int i = 0; i < 8; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kt = 0; kt < NKT; ++kt) { // conv3 (+ shortcut) steps: all 128 rows of the slot against this wave's 16 pixels
                 RFD_STAMP(2);
                 if (!RESIDENT) {
-                    if (SHORT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this step's weights (issued one step ago) and everything older
                     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
                     RFD_STAMP(0);
                     issue_w();
@@ -966,9 +941,7 @@ __global__ void __launch_bounds__(NW * 64, PX == 2 ? 1 : 2) pw_pair_kernel(const
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
                         const bf16x8 a = *reinterpret_cast<const bf16x8 *>(ws + i * 1024 + so);
-#pragma unroll
-                        for (int g = 0; g < PX; ++g) // one fragment read, PX MFMAs
-                            acc[g][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(bf16x8, xq[g][kt * 2 + kk]), acc[g][i], 0, 0, 0);
+                        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(bf16x8, xq[kt * 2 + kk]), acc[i], 0, 0, 0);
                     }
                 }
             }
@@ -976,30 +949,26 @@ __global__ void __launch_bounds__(NW * 64, PX == 2 ? 1 : 2) pw_pair_kernel(const
             // the next tile's activation fragments may be requested as soon as this tile's last conv3 step has read them
             if (last_chunk) issue_x(mt + (int)gridDim.x);
             // ---- the one drain of the chunk: residual of this chunk, W1 steps of this chunk, stores of the previous one ----
-            if (HAS_RES) {
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(cur[0][0]), "+v"(cur[0][1]), "+v"(cur[0][2]), "+v"(cur[0][3]) : : "memory");
-                if (PX == 2) asm volatile("" : "+v"(cur[PX - 1][0]), "+v"(cur[PX - 1][1]), "+v"(cur[PX - 1][2]), "+v"(cur[PX - 1][3])); // behind the wait (volatile asm keeps its order)
-            } else asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
+            if (HAS_RES) asm volatile("s_waitcnt vmcnt(0)" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]), "+v"(cur[3]) : : "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
             __builtin_amdgcn_sched_barrier(0);
             RFD_STAMP(3);
             if (!last_chunk) issue_res(nxt, mt, nc + 1);
             else issue_res(nxt, mt + (int)gridDim.x, 0);
-            u32x4 actq[PX][4]; // conv1's B fragments: the activated chunk, K slice h = channels h*32 + fq*8 .. +7 of this pixel
+            u32x4 actq[4]; // conv1's B fragments: the activated chunk, K slice h = channels h*32 + fq*8 .. +7 of this pixel
 #pragma unroll
             for (int h = 0; h < 4; ++h) {
                 const int n = (nc << 7) + h * 32 + fq * 8;
                 float bias[8], sc[8], sh[8];
                 lds_table_read8x3(Tab + n, Tab + N + n, Tab + 2 * N + n, bias, sc, sh);
-#pragma unroll
-              for (int g = 0; g < PX; ++g) {
-                const int m = mt * BM + (wave * PX + g) * 16 + frow;
+                const int m = mt * BM + wave * 16 + frow;
                 const uint32_t off = m < M ? (uint32_t)(((size_t)m * N + n) * 2) : kOob;
-                const u32x4 rv = cur[g][h];
+                const u32x4 rv = cur[h];
                 float v[8];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    v[k] = acc[g][2 * h][k] + bias[k];
-                    v[4 + k] = acc[g][2 * h + 1][k] + bias[4 + k];
+                    v[k] = acc[2 * h][k] + bias[k];
+                    v[4 + k] = acc[2 * h + 1][k] + bias[4 + k];
                 }
                 if (HAS_RES) {
 #pragma unroll
@@ -1032,8 +1001,7 @@ __global__ void __launch_bounds__(NW * 64, PX == 2 ? 1 : 2) pw_pair_kernel(const
                     }
                     alo = pack_bf16x4(a[0], a[1], a[2], a[3]); ahi = pack_bf16x4(a[4], a[5], a[6], a[7]);
                 }
-                actq[g][h] = u32x4{alo.x, alo.y, ahi.x, ahi.y};
-              }
+                actq[h] = u32x4{alo.x, alo.y, ahi.x, ahi.y};
             }
 #pragma unroll
             for (int k1 = 0; k1 < 2; ++k1)       // conv1: the chunk's 64-channel half k1 ...
@@ -1041,7 +1009,6 @@ __global__ void __launch_bounds__(NW * 64, PX == 2 ? 1 : 2) pw_pair_kernel(const
                 for (int r1 = 0; r1 < N1B; ++r1) { // ... against the 128-row block r1 of W1 (one slot-step)
                     RFD_STAMP(k1 == 0 && r1 == 0 ? 4 : 7);
                     if (!RESIDENT) {
-                        if (SHORT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
                         RFD_STAMP(5);
                         issue_w();
@@ -1055,9 +1022,7 @@ __global__ void __launch_bounds__(NW * 64, PX == 2 ? 1 : 2) pw_pair_kernel(const
 #pragma unroll
                         for (int i = 0; i < RB1; ++i) {
                             const bf16x8 a = *reinterpret_cast<const bf16x8 *>(ws + i * 1024 + so);
-#pragma unroll
-                            for (int g = 0; g < PX; ++g)
-                                acc1[g][r1 * 8 + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(bf16x8, actq[g][k1 * 2 + kk]), acc1[g][r1 * 8 + i], 0, 0, 0);
+                            acc1[r1 * 8 + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(bf16x8, actq[k1 * 2 + kk]), acc1[r1 * 8 + i], 0, 0, 0);
                         }
                     }
                 }
@@ -1076,18 +1041,15 @@ __global__ void __launch_bounds__(NW * 64, PX == 2 ? 1 : 2) pw_pair_kernel(const
                 const int n = r1 * 128 + h * 32 + fq * 8;
                 float b1[8];
                 lds_table_read8(Tab + 3 * N + n, b1);
+                const int m = mt * BM + wave * 16 + frow;
+                float o[8];
 #pragma unroll
-                for (int g = 0; g < PX; ++g) {
-                    const int m = mt * BM + (wave * PX + g) * 16 + frow;
-                    float o[8];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        o[k] = fmaxf(acc1[g][r1 * 8 + 2 * h][k] + b1[k], 0.f);
-                        o[4 + k] = fmaxf(acc1[g][r1 * 8 + 2 * h + 1][k] + b1[4 + k], 0.f);
-                    }
-                    const uint2 lo = pack_bf16x4(o[0], o[1], o[2], o[3]), hi = pack_bf16x4(o[4], o[5], o[6], o[7]);
-                    __builtin_amdgcn_raw_buffer_store_b128(u32x4{lo.x, lo.y, hi.x, hi.y}, rt1, m < M ? (uint32_t)(((size_t)m * N1 + n) * 2) : kOob, 0, 0);
+                for (int k = 0; k < 4; ++k) {
+                    o[k] = fmaxf(acc1[r1 * 8 + 2 * h][k] + b1[k], 0.f);
+                    o[4 + k] = fmaxf(acc1[r1 * 8 + 2 * h + 1][k] + b1[4 + k], 0.f);
                 }
+                const uint2 lo = pack_bf16x4(o[0], o[1], o[2], o[3]), hi = pack_bf16x4(o[4], o[5], o[6], o[7]);
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{lo.x, lo.y, hi.x, hi.y}, rt1, m < M ? (uint32_t)(((size_t)m * N1 + n) * 2) : kOob, 0, 0);
             }
     }
 #ifdef RFD_PAIR_STAMPS
@@ -1117,23 +1079,11 @@ static int device_cus()
     return n;
 }
 
-// CUs a persistent kernel spreads over when another chain of the same pass runs beside it (RFD_PERSIST_CUS: A/B knob;
-// default: all of them)
-static int persistent_cus(int co_running, bool hbm_bound = false)
-{
-    static const int env = [] { const char *e = getenv("RFD_PERSIST_CUS"); return e ? atoi(e) : 0; }();
-    static const int env_hbm = [] { const char *e = getenv("RFD_PERSIST_CUS_HBM"); return e ? atoi(e) : 0; }(); // HBM-bound kernels only
-    const int ncu = device_cus();
-    if (co_running && hbm_bound && env_hbm > 0) return std::min(env_hbm, ncu);
-    return co_running && env > 0 ? std::min(env, ncu) : ncu;
-}
-
 // ---- the one launch path of every persistent kernel ----
 // A persistent workgroup must own its CU's LDS (rule 2): whatever the kernel needs, the launch asks for
 // the whole 160 KiB, so no workgroup of another kernel can ever share the CU.  kPersistentKernels is the list the CPU build test
 // walks (tests/test_build_cpu.py, through rfd_debug_persistent_kernel): every 8-wave LDS-DMA kernel of the code object is either
-// in it or named there as one-tile-per-workgroup.  RFD_PERSIST_LDS_EXACT=1 (diagnostic only, tools/split_diag.py) requests the
-// real need instead -- the configuration that gave nondeterministic images in round 2.
+// in it or named there as one-tile-per-workgroup.
 constexpr size_t kPersistentLds = 160 * 1024;
 static const char *const kPersistentKernels[] = {"pw_stream_kernel", "conv3x3_c64_kernel", "conv3x3_halo_kernel", "pw_gemm_kernel",
                                                  "pw_wide_kernel", "conv_b2b_s1_persistent_kernel", "conv_b2b_s1_persistent_k128_kernel",
@@ -1149,11 +1099,10 @@ int persistent_kernel_table(int i, const char **name, size_t *lds_bytes)
 template <auto Kern, typename... A> static int launch_persistent(int grid, size_t lds_need, hipStream_t s, A... args)
 {
     if (launch_note().dry) return RFD_OK; // the caller has recorded the kernel's name (note_launch)
-    static const bool exact = [] { const char *e = getenv("RFD_PERSIST_LDS_EXACT"); return e && atoi(e) != 0; }();
     if (lds_need > kPersistentLds) { set_error("persistent kernel: %zu bytes of LDS needed", lds_need); return RFD_ERR_CAPACITY; }
     static DynLdsOnce once;
     RFD_TRY(once.ensure(reinterpret_cast<const void *>(Kern), (int)kPersistentLds));
-    hipLaunchKernelGGL(Kern, dim3(grid), dim3(512), exact ? lds_need : kPersistentLds, s, args...);
+    hipLaunchKernelGGL(Kern, dim3(grid), dim3(512), kPersistentLds, s, args...);
     RFD_HIP(hipGetLastError());
     return RFD_OK;
 }
@@ -1162,7 +1111,7 @@ template <int NK, bool HAS_Y, bool HAS_Y2> static int launch_pw_stream(const Con
 {
     const int M = p.B * p.Ho * p.Wo;
     const int tiles_m = ceil_div(M, 128);
-    const int ncu = persistent_cus(p.co_running, true);
+    const int ncu = device_cus();
     // one persistent workgroup per CU; tiles are dealt round-robin, so an even share per workgroup means no tail
     const int per = ceil_div(tiles_m, ncu);
     const int grid = ceil_div(tiles_m, per);
@@ -1180,82 +1129,32 @@ template <int NK, bool ACT_OUT> static int launch_pw_b2b(const ConvParams &p, hi
 {
     const int M = p.B * p.Ho * p.Wo;
     const int tiles_m = ceil_div(M, 128);
-    const int ncu = persistent_cus(p.co_running, true);
+    const int ncu = device_cus();
     const int per = ceil_div(tiles_m, ncu);
     const int grid = ceil_div(tiles_m, per);
     const size_t lds_need = (size_t)(NK + 2 + NK + 3) * 128 * 64 * sizeof(bf16_t) + (size_t)(3 * p.Cout + 128) * sizeof(float);
     note_launch("pw_b2b_kernel<%d, %s>", NK, ACT_OUT ? "true" : "false");
     return launch_persistent<pw_b2b_kernel<NK, ACT_OUT>>(grid, lds_need, s, p);
 }
-// half-workgroup form of pw_pair_kernel (NW = 4): two workgroups per CU, 64-pixel tiles, short weight ring
-template <int NK, int N1B, bool ACT_OUT, int NK2 = 0> static int launch_pw_pair_half(const ConvParams &p, hipStream_t s)
-{
-    const int M = p.B * p.Ho * p.Wo;
-    const int tiles_m = ceil_div(M, 64);
-    const int slots = 2 * persistent_cus(p.co_running, true);
-    const int per = ceil_div(tiles_m, slots);
-    const int grid = ceil_div(tiles_m, per);
-    const size_t lds_need = (size_t)2 * 128 * 64 * sizeof(bf16_t) + (size_t)(3 * p.Cout + 128 * N1B) * sizeof(float);
-    // each workgroup asks for HALF the CU's LDS, so that exactly two co-reside (and nothing else beside them)
-    constexpr size_t kHalfLds = 80 * 1024;
-    if (lds_need > kHalfLds) { set_error("pw_pair (half workgroups): %zu bytes of LDS needed", lds_need); return RFD_ERR_CAPACITY; }
-    note_launch("pw_pair_kernel<%d, %d, %s, %d, 0, 4, 1, false>", NK, N1B, ACT_OUT ? "true" : "false", NK2); // the name rocprofv3 reports: every template argument
-    if (launch_note().dry) return RFD_OK;
-    auto kern = pw_pair_kernel<NK, N1B, ACT_OUT, NK2, 0, 4>;
-    static DynLdsOnce once;
-    RFD_TRY(once.ensure(reinterpret_cast<const void *>(kern), (int)kHalfLds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), kHalfLds, s, p);
-    RFD_HIP(hipGetLastError());
-    return RFD_OK;
-}
-// 32-pixel-per-wave form of pw_pair_kernel (NW = 4, PX = 2): 128-pixel tiles, one workgroup of 4 waves per CU, the deep ring
-template <int NK, int N1B, bool ACT_OUT, int NK2 = 0> static int launch_pw_pair_px2(const ConvParams &p, hipStream_t s)
-{
-    const int M = p.B * p.Ho * p.Wo;
-    const int tiles_m = ceil_div(M, 128);
-    const int ncu = persistent_cus(p.co_running, true);
-    const int per = ceil_div(tiles_m, ncu);
-    const int grid = ceil_div(tiles_m, per);
-    const size_t lds_need = (size_t)(NK + NK2 + 2 * N1B + 1) * 128 * 64 * sizeof(bf16_t) + (size_t)(3 * p.Cout + 128 * N1B) * sizeof(float);
-    if (lds_need > kPersistentLds) { set_error("pw_pair (32 px per wave): %zu bytes of LDS needed", lds_need); return RFD_ERR_CAPACITY; }
-    note_launch("pw_pair_kernel<%d, %d, %s, %d, 0, 4, 2, false>", NK, N1B, ACT_OUT ? "true" : "false", NK2);
-    if (launch_note().dry) return RFD_OK;
-    auto kern = pw_pair_kernel<NK, N1B, ACT_OUT, NK2, 0, 4, 2>;
-    static DynLdsOnce once;
-    RFD_TRY(once.ensure(reinterpret_cast<const void *>(kern), (int)kPersistentLds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), kPersistentLds, s, p);
-    RFD_HIP(hipGetLastError());
-    return RFD_OK;
-}
 template <int NK, int N1B, bool ACT_OUT, int NK2 = 0, int NCR = 0, bool HALF1 = false> static int launch_pw_pair(const ConvParams &p, hipStream_t s)
 {
-    // RFD_PAIR_HALF: which pairs run as half workgroups (bit mask: 1 stage 3's middle units <4,2>, 2 the 2 -> 3 boundary <2,2,true>,
-    // 4 stage 2's first unit <2,1,false,4>, 8 stage 2's middle units); A/B knob, bit-identical either way
-    static const int half_env = [] { const char *e = getenv("RFD_PAIR_HALF"); return e ? atoi(e) : 0; }();
-    if (NCR == 0 && !HALF1) {
-        const int bit = (NK == 4 && N1B == 2) ? 1 : (NK == 2 && N1B == 2) ? 2 : (NK == 2 && NK2 == 4) ? 4 : (NK == 2 && N1B == 1 && NK2 == 0) ? 8 : 0;
-        if (half_env & bit) return launch_pw_pair_half<NK, N1B, ACT_OUT, NK2>(p, s);
-        // RFD_PAIR_PX2: the same bit mask for the 32-pixel-per-wave form
-        static const int px2_env = [] { const char *e = getenv("RFD_PAIR_PX2"); return e ? atoi(e) : 0; }();
-        if (px2_env & bit) return launch_pw_pair_px2<NK, N1B, ACT_OUT, NK2>(p, s);
-    }
     const int M = p.B * p.Ho * p.Wo;
     const int tiles_m = ceil_div(M, 128);
-    const int ncu = persistent_cus(p.co_running, true);
+    const int ncu = device_cus();
     const int per = ceil_div(tiles_m, ncu);
     const int grid = ceil_div(tiles_m, per);
     const size_t slots = NCR ? (size_t)NCR * (NK + NK2 + 2 * N1B) : (size_t)(NK + NK2 + 2 * N1B + 1);
     const size_t lds_need = slots * 128 * 64 * sizeof(bf16_t) + (size_t)(3 * p.Cout + 128 * N1B) * sizeof(float);
     if (NCR && p.Cout != NCR * 128) { set_error("pw_pair: resident form instantiated for %d output channels", NCR * 128); return RFD_ERR_INVALID_ARG; }
     if (p.n1 != (HALF1 ? 64 : 128 * N1B)) { set_error("pw_pair: instantiated for n1 = %d, got %d", HALF1 ? 64 : 128 * N1B, p.n1); return RFD_ERR_INVALID_ARG; }
-    note_launch("pw_pair_kernel<%d, %d, %s, %d, %d, 8, 1, %s>", NK, N1B, ACT_OUT ? "true" : "false", NK2, NCR, HALF1 ? "true" : "false");
-    return launch_persistent<pw_pair_kernel<NK, N1B, ACT_OUT, NK2, NCR, 8, 1, HALF1>>(grid, lds_need, s, p);
+    note_launch("pw_pair_kernel<%d, %d, %s, %d, %d, %s>", NK, N1B, ACT_OUT ? "true" : "false", NK2, NCR, HALF1 ? "true" : "false");
+    return launch_persistent<pw_pair_kernel<NK, N1B, ACT_OUT, NK2, NCR, HALF1>>(grid, lds_need, s, p);
 }
+// the forms launch_conv's pw_ok admits: one output, raw (y) or activated (y2); K = 64 layers only the activated one
 template <int NK> static int launch_pw_stream_nk(const ConvParams &p, hipStream_t s)
 {
-
-    if (p.y && p.y2) return launch_pw_stream<NK, true, true>(p, s);
-    if (p.y) return launch_pw_stream<NK, true, false>(p, s);
+    if constexpr (NK > 1)
+        if (p.y) return launch_pw_stream<NK, true, false>(p, s);
     return launch_pw_stream<NK, false, true>(p, s);
 }
 
@@ -1426,9 +1325,6 @@ __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64, 2) conv3x3_kx_kernel(co
 // chunk swizzle keyed on hx & 7, so the XOR of a tap depends on kx only.  LDS: 72 KiB + 2 x 41 KiB = 154 KiB, 1 workgroup / CU.
 // ------------------------------------------------------------------------------------------------
 constexpr int kC64T = 16, kC64H = kC64T + 2, kC64HP = 41 /* pieces of 8 rows */;
-#ifndef RFD_C64_EXP
-#define RFD_C64_EXP 0 // timing experiments (tools/build_variant.sh; results are garbage): 1 no halo DMA after the first tile, 2 no output stores, 3 neither, 4 neither + no MFMAs
-#endif
 __global__ void __launch_bounds__(512) conv3x3_c64_kernel(const ConvParams p, int tiles_x, int tiles_y)
 {
     RFD_CLOCK(5);
@@ -1501,9 +1397,7 @@ __global__ void __launch_bounds__(512) conv3x3_c64_kernel(const ConvParams p, in
         // previous tile's stores were issued); the other buffer is free
         if (tile == (int)blockIdx.x) wait_vmcnt<0>();
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); /* no LDS read in flight at a barrier that frees a ring slot for DMA (tools/isa_check.py) */
-#if RFD_C64_EXP == 0 || RFD_C64_EXP == 2
         if (next < ntiles) stage_halo(next, buf ^ 1);
-#endif
         const bf16_t *xb = xbase + buf * (kC64HP * 512);
         f32x4 acc[2][4];
 #pragma unroll
@@ -1552,11 +1446,7 @@ __global__ void __launch_bounds__(512) conv3x3_c64_kernel(const ConvParams p, in
             const uint2 lo = pack_bf16x4(o[0], o[1], o[2], o[3]), hi = pack_bf16x4(o[4], o[5], o[6], o[7]);
             typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
             const uint32_t yoff = (uint32_t)(((((size_t)b * p.H + oy) * p.W + ox) * p.ldy + p.y_coff + wn * 32 + fq * 8) * 2);
-#if RFD_C64_EXP == 0 || RFD_C64_EXP == 1
             __builtin_amdgcn_raw_buffer_store_b128(u32x4{lo.x, lo.y, hi.x, hi.y}, ry, (oy < p.H && ox < p.W) ? yoff : kOob, 0, 0);
-#else
-            if (lo.x == 0x12345678u && tile < 0) __builtin_amdgcn_raw_buffer_store_b128(u32x4{lo.x, lo.y, hi.x, hi.y}, ry, yoff, 0, 0); // keeps the values live
-#endif
         }
         buf ^= 1;
     }
@@ -1566,7 +1456,7 @@ static int launch_conv3x3_c64(const ConvParams &p, hipStream_t s)
 {
     const int tiles_x = ceil_div(p.W, kC64T), tiles_y = ceil_div(p.H, kC64T);
     const int ntiles = p.B * tiles_x * tiles_y;
-    const int ncu = persistent_cus(p.co_running);
+    const int ncu = device_cus();
     const int per = ceil_div(ntiles, ncu);
     const int grid = ceil_div(ntiles, per); // even share per persistent workgroup: no tail
     // needs 154 KiB; launch_persistent asks for the whole CU's LDS so that no other kernel's workgroup can ever share the CU
@@ -1594,9 +1484,6 @@ static int launch_conv3x3_c64(const ConvParams &p, hipStream_t s)
 // Nine steps are unrolled ("superblock": one chunk at TN = 8, two chunks = 18 units at TN = 4, where step 4 straddles the
 // chunk boundary and the two halo buffers are bound to chunk parity).
 // ------------------------------------------------------------------------------------------------
-#ifndef RFD_HALO_EXP
-#define RFD_HALO_EXP 0 // timing experiments (tools/build_variant.sh; results are garbage): 1 no weight DMA, 2 no halo DMA, 3 neither, 4 neither + no barrier, 5 weight DMAs issued but never waited for
-#endif
 template <int TC, int TR, int TN>
 __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const ConvParams p, int tiles_x, int tiles_y, int n_items)
 {
@@ -1705,28 +1592,18 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const ConvParams p, i
 #pragma unroll
         for (int s = 0; s < 9; ++s) {
             // weights of this step were issued a step ago; a halo tile 4+ steps ago (the bias table, the first time, by plain stores)
-#if RFD_HALO_EXP == 5 // timing only: the weight waves never wait for their DMAs (is the step waiting for the weights to land?)
-            if (wn != 0 && (s == 0 || (U == 2 && s == 4))) wait_vmcnt<0>();
-#else
             if (wn == 0 || s == 0 || (U == 2 && s == 4)) wait_vmcnt<0>();
-#endif
-#if RFD_HALO_EXP != 4
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
-#if RFD_HALO_EXP == 0 || RFD_HALO_EXP == 2 || RFD_HALO_EXP == 5
             if (wn == 0) {
                 if (s < 8) issue_w(wslot ^ 1, item, c0, s + 1);
                 else if (has_next) issue_w(wslot ^ 1, nitem, nc0, 0);
             }
-#endif
-#if RFD_HALO_EXP == 0 || RFD_HALO_EXP == 1 || RFD_HALO_EXP == 5
             if (wn == 1 && U == 1) {
                 if (s == 0 && has_next) issue_halo(nitem, nc0, hbuf ^ 1);
             } else if (wn == 1) {
                 if (s == 0) issue_halo(item, c0 + 1, 1);
                 if (s == 5 && has_next) issue_halo(nitem, nc0, 0);
             }
-#endif
             // ---- the step's 64 (TN = 6: 48) MFMAs as four groups, software-pipelined: the fragments of group g + 1 are read
             //      from LDS while group g's MFMAs issue (the compiler's own order was read - wait - 4 MFMAs - read - wait ...).
             //      group -> (unit k, 32-wide K half kk, first A fragment ih): TN = 4: (g >> 1, g & 1, 0); else (0, g >> 1, (g & 1) NA);
@@ -1829,7 +1706,7 @@ template <int TC, int TR, int TN> static int launch_conv3x3_halo(const ConvParam
 {
     const int tiles_x = ceil_div(p.W, TC), tiles_y = ceil_div(p.H, TR);
     const int n_items = p.B * tiles_x * tiles_y * (p.Cout / (32 * TN));
-    const int ncu = persistent_cus(p.co_running);
+    const int ncu = device_cus();
     const int per = ceil_div(n_items, ncu);
     const int grid = ceil_div(n_items, per);
     constexpr int HP = ((TR + 2) * (TC + 2) + 7) / 8, U = TN == 4 ? 2 : 1;
@@ -1867,9 +1744,6 @@ static int launch_conv3x3_kx(const ConvParams &p, hipStream_t s)
 // epilogue's stores are simply queued behind the DMAs and retire with the next drain.  Same K order and MFMA sequence as
 // the generic kernel: bit-identical results.
 // ------------------------------------------------------------------------------------------------
-#ifndef RFD_PWG_EXP
-#define RFD_PWG_EXP 0 // timing experiments (tools/build_variant.sh; results are garbage)
-#endif
 // HAS_AFF: x' = relu(x * in_scale[c] + in_shift[c]) on the landed activation tile (the producer unit's BN + ReLU).
 // WIDE: items of 128 pixels x 256 channels (waves 2 pixel x 4 channel) instead of 256 x 128 (4 x 2) -- for N = 256 layers one
 // item then covers all output channels: the activation is read and, with HAS_AFF, transformed once instead of once per
@@ -1973,12 +1847,7 @@ __global__ void __launch_bounds__(512) pw_gemm_kernel(const ConvParams p, int ti
                     asm volatile("s_waitcnt vmcnt(0)" : "+v"(resv[0][0]), "+v"(resv[0][1]), "+v"(resv[0][2]), "+v"(resv[0][3])::"memory");
                     asm volatile("" : "+v"(resv[1][0]), "+v"(resv[1][1]), "+v"(resv[1][2]), "+v"(resv[1][3])::"memory");
                 } else {
-#if RFD_PWG_EXP == 1 // timing only: the weight waves never wait (is the step waiting for the weight tile to land?)
-                    if (!is_w) wait_vmcnt<0>();
-#elif RFD_PWG_EXP == 2 // timing only: nobody waits
-#else
                     wait_vmcnt<0>();
-#endif
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -2127,7 +1996,7 @@ static int launch_pw_gemm(const ConvParams &p, hipStream_t s)
     // 128-pixel x 256-channel items where they cover all channels of an N = 256 layer and still fill the GPU (force_tile 15: never)
     const bool wide = p.Cout == 256 && ceil_div(M, 128) >= 150 && p.force_tile != 15;
     const int tiles_m = ceil_div(M, wide ? 128 : 256), n_items = tiles_m * (p.Cout / (wide ? 256 : 128));
-    const int ncu = persistent_cus(p.co_running, true);
+    const int ncu = device_cus();
     const int per = ceil_div(n_items, ncu);
     const int grid = ceil_div(n_items, per);
     if (p.in_scale) return wide ? launch_pw_gemm_t<true, true>(p, s, tiles_m, n_items, grid) : launch_pw_gemm_t<true, false>(p, s, tiles_m, n_items, grid);
@@ -2145,9 +2014,6 @@ static int launch_pw_gemm(const ConvParams &p, hipStream_t s)
 // segment (the 1x1 stride-2 shortcut conv over x2: a per-lane pixel gather), residual, raw + activated outputs -- the
 // generic kernel's epilogue arithmetic in the same order, and the same K order: bit-identical results.
 // ------------------------------------------------------------------------------------------------
-#ifndef RFD_WIDE_EXP
-#define RFD_WIDE_EXP 0 // timing experiments (tools/build_variant.sh; results are garbage): 1 no operand DMA, 2 no DMA + no step barrier, 3 DMA issued but never waited for
-#endif
 __global__ void __launch_bounds__(512) pw_wide_kernel(const ConvParams p, int n_items)
 {
     RFD_CLOCK(8);
@@ -2238,17 +2104,11 @@ __global__ void __launch_bounds__(512) pw_wide_kernel(const ConvParams p, int n_
     while (true) {
         int nit = item, nk = k + 1;
         if (nk == KC) { nk = 0; nit = item + grid; }
-#if RFD_WIDE_EXP != 3
         wait_vmcnt<0>();
-#endif
-#if RFD_WIDE_EXP != 2
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
         // the next item's second-segment pixels: needed from its step KC1 on, so recomputed one step into the item
         if (p.Cin2 && k == 0 && item != item0) item_x2(item);
-#if RFD_WIDE_EXP == 0 || RFD_WIDE_EXP == 3
         if (nit < n_items) issue(sl ^ 1, nit, nk);
-#endif
         const bf16_t *xb = Xs + sl * XEL, *wb = Ws + sl * WEL;
         bf16x8 af[2][4], bfr[2][4];
         auto load_group = [&](int g) { // group g -> (kk = g >> 1, A fragments 4 (g & 1) ..); B fragments with the first of a kk
@@ -2353,7 +2213,7 @@ static int launch_pw_wide(const ConvParams &p, hipStream_t s)
 {
     const int M = p.B * p.Ho * p.Wo;
     const int n_items = ceil_div(M, 256) * (p.Cout / 256);
-    const int ncu = persistent_cus(p.co_running);
+    const int ncu = device_cus();
     const int per = ceil_div(n_items, ncu);
     const int grid = ceil_div(n_items, per);
     // 4 x 32 KiB + tables: the whole CU
@@ -2868,11 +2728,10 @@ int launch_conv_b2b_s1(const B2BParams &p, hipStream_t s)
     const int ntiles = ceil_div(M, 128);
     // Round 4: the weight-resident barrier-free pair kernel (pw_pair_kernel<.., NCR = 2, HALF1>, the form that runs the stage
     // 1 -> 2 boundary) takes stage 1's pairs too: W3 [256][64 or 128] + W1 [64][256] stay in LDS, every wave is an independent
-    // pipeline over its 16 pixels.  force_tile 16 forces it, 6 keeps the older persistent kernels below (RFD_S1_PAIR=0: always).
-    static const int s1_pair = [] { const char *e = getenv("RFD_S1_PAIR"); return e ? atoi(e) : 1; }();
+    // pipeline over its 16 pixels.  force_tile 16 forces it, 6 keeps the older persistent kernels below.
     const bool pair_ok = (const char *)p.w1 > (const char *)p.w3 && (size_t)((const char *)p.w1 - (const char *)p.w3) < (1u << 30) &&
                          (p.Cin2 == 0 ? p.res != nullptr : (!p.res && p.bias3b)) && (size_t)M * 256 * 2 < 0xfffffff0ull;
-    if (pair_ok && (p.force_tile == 16 || (p.force_tile == 0 && s1_pair && ntiles >= 512))) {
+    if (pair_ok && (p.force_tile == 16 || (p.force_tile == 0 && ntiles >= 512))) {
         ConvParams c;
         memset(&c, 0, sizeof c);
         c.x = p.x; c.w = p.w3; c.bias = p.bias3; c.x2 = p.x2; c.bias2 = p.bias3b; c.res = p.res;
@@ -2883,14 +2742,14 @@ int launch_conv_b2b_s1(const B2BParams &p, hipStream_t s)
     }
     // K1 = 64 and at least two tiles per CU: the persistent form (force_tile 7 opts out, 6 forces it whatever the size)
     if (p.Cin2 == 0 && p.force_tile != 7 && p.force_tile != 1 && p.force_tile != 2 && (ntiles >= 512 || p.force_tile == 6)) {
-        const int per = ceil_div(ntiles, persistent_cus(1, true));
+        const int per = ceil_div(ntiles, device_cus());
         const int grid = ceil_div(ntiles, per);
         note_launch("conv_b2b_s1_persistent_kernel");
         return launch_persistent<conv_b2b_s1_persistent_kernel>(grid, kPersistentLds, s, p, ntiles);
     }
     // K1 = 128 (fused shortcut, no residual): persistent 64-pixel tiles, both filter banks resident
     if (p.Cin2 == 64 && !p.res && p.force_tile != 7 && p.force_tile != 1 && p.force_tile != 2 && (M >= 64 * 1024 || p.force_tile == 6)) {
-        const int nt = ceil_div(M, 64), per = ceil_div(nt, persistent_cus(1, true));
+        const int nt = ceil_div(M, 64), per = ceil_div(nt, device_cus());
         note_launch("conv_b2b_s1_persistent_k128_kernel");
         return launch_persistent<conv_b2b_s1_persistent_k128_kernel>(ceil_div(nt, per), kPersistentLds, s, p, nt);
     }
@@ -2922,8 +2781,15 @@ static int launch_conv_cfg_order(const ConvParams &p, hipStream_t s)
 }
 template <int BM, int BN, int WAVES_M, int WAVES_N, int NSX> static int launch_conv_cfg(const ConvParams &p, hipStream_t s)
 {
-    return p.k_chunk_major ? launch_conv_cfg_order<BM, BN, WAVES_M, WAVES_N, NSX, true>(p, s)
-                           : launch_conv_cfg_order<BM, BN, WAVES_M, WAVES_N, NSX, false>(p, s);
+    // chunk-major K order is set for halo-shape layers only (launch_conv), and those reach the generic kernel on these tiles alone
+    constexpr bool kHaloTile = (BN == 128 && !(WAVES_M == 2 && NSX == 3)) || BN == 192;
+    if constexpr (kHaloTile) {
+        if (p.k_chunk_major) return launch_conv_cfg_order<BM, BN, WAVES_M, WAVES_N, NSX, true>(p, s);
+    } else if (p.k_chunk_major) {
+        set_error("conv: the %d x %d tile has no chunk-major form", BM, BN);
+        return RFD_ERR_INVALID_ARG;
+    }
+    return launch_conv_cfg_order<BM, BN, WAVES_M, WAVES_N, NSX, false>(p, s);
 }
 
 int launch_conv(const ConvParams &p, hipStream_t s)
@@ -2952,8 +2818,6 @@ int launch_conv(const ConvParams &p, hipStream_t s)
         const bool b23 = act_out && p.Cin == 128 && p.Cout == 512 && p.n1 == 256;                     // stage 2 -> 3 boundary: pw_pair_kernel only
         const bool shape = s3 || b23 || (act_out ? (p.Cin == 64 && p.Cout == 256 && p.n1 == 128) : (p.Cin == 128 && p.Cout == 512 && p.n1 == 128 && p.y && !p.y2 && p.ldy == p.Cout));
         const int N1 = p.n1;
-        // RFD_PW_PAIR=1: pw_pair_kernel for every pair (A/B against pw_b2b_kernel); default: stage 3 only
-        static const int pair_all = [] { const char *e = getenv("RFD_PW_PAIR"); return e ? atoi(e) : 0; }();
         // the first unit of stage 2: conv3 128 -> 512 with the 1x1 stride-2 shortcut 256 -> 512 as second K segment, no residual
         const bool u1 = !act_out && p.Cin == 128 && p.Cin2 == 256 && p.stride2 == 2 && p.Cout == 512 && p.n1 == 128 && !p.res && p.y && !p.y2 && p.ldy == p.Cout && p.bias2;
         const bool fuse = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && (u1 || (shape && p.Cin2 == 0 && p.res)) && !p.in_scale &&
@@ -2967,10 +2831,9 @@ int launch_conv(const ConvParams &p, hipStream_t s)
                 return launch_pw_pair<4, 2, false>(p, s);
             }
             if (b23) return launch_pw_pair<2, 2, true>(p, s);
-            // the stage 1 -> 2 boundary: both filter banks (96 KiB) resident in LDS, barrier-free (RFD_PW_PAIR=2: the streaming pw_b2b form)
-            if (act_out && pair_all != 2) return launch_pw_pair<1, 1, true, 0, 2>(p, s);
-            if (pair_all == 1) return act_out ? launch_pw_pair<1, 1, true>(p, s) : launch_pw_pair<2, 1, false>(p, s);
-            return act_out ? launch_pw_b2b<1, true>(p, s) : launch_pw_b2b<2, false>(p, s);
+            // the stage 1 -> 2 boundary: both filter banks (96 KiB) resident in LDS, barrier-free
+            if (act_out) return launch_pw_pair<1, 1, true, 0, 2>(p, s);
+            return launch_pw_b2b<2, false>(p, s); // stage 2's middle units
         }
         ConvParams a = p;
         a.w1 = nullptr; a.bias1 = nullptr; a.t1 = nullptr;
@@ -3024,15 +2887,17 @@ int launch_conv(const ConvParams &p, hipStream_t s)
         // 28.8 us per 16 images in isolation) and the stride-2 conv2 of stage 4's first unit (48.6 vs 52.7 us); end to end +1.1 %
         // in two alternating A/B pairs on one box (7 798 / 7 734 vs 7 716 / 7 650 img/s; profiles/r04_ab_ring_env.jsonl).  Every
         // other layer stays with the kernels above (the ring is slower there: DESIGN_AB_RECORD.md round 4).  Bit-identical either
-        // way (tests/test_ring_gpu.py).  RFD_CONV_RING=0 switches it off, =2 widens it to every generic-form layer with Cout = 512.
-        static const int ring_env = [] { const char *e = getenv("RFD_CONV_RING"); return e ? atoi(e) : 1; }();
+        // way (tests/test_ring_gpu.py).  RFD_CONV_RING=0 switches it off.
+        static const bool ring_on = [] { const char *e = getenv("RFD_CONV_RING"); return !e || atoi(e) >= 1; }();
         bool kx3 = false;
-        if (ring_env >= 1 && p.force_tile == 0 && conv_ring_supports(p, &kx3) && !kx3 && p.B * p.Ho * p.Wo <= 128 * 64 &&
-            p.KH * p.KW * p.Cin + p.Cin2 >= (ring_env >= 2 ? 512 : 2048) && p.Cout == 512)
+        if (ring_on && p.force_tile == 0 && conv_ring_supports(p, &kx3) && !kx3 && p.B * p.Ho * p.Wo <= 128 * 64 &&
+            p.KH * p.KW * p.Cin + p.Cin2 >= 2048 && p.Cout == 512)
             return launch_conv_ring(p, s);
     }
     // short-K, wide-N pointwise layers with a residual: persistent X-stationary streaming kernel (force_tile 1 / 2 / 5 opt out)
+    // (one output: the raw sum or, at the end of a stage, the activated one; K = 64 only the latter -- the forms instantiated)
     const bool pw_ok = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.Cin2 == 0 && !p.in_scale && !p.yf && p.res &&
+                       !(p.y && p.y2) && !(p.y && p.Cin == 64) &&
                        !p.res_up2 && !p.res_post && p.ldx == p.Cin && p.x_coff == 0 && p.Cout % 128 == 0 && p.Cout >= 4 * p.Cin &&
                        p.y_coff == 0 && p.y_split >= p.Cout && p.n_valid >= p.Cout && (!p.y || p.ldy == p.Cout) &&
                        (p.Cin == 64 || p.Cin == 128 || p.Cin == 256) && (p.force_tile == 0 || p.force_tile == 6 || p.force_tile == 8 ||
@@ -3090,8 +2955,7 @@ int launch_conv(const ConvParams &p, hipStream_t s)
     // and fragment-read latencies (1 725 cycles per 32-MFMA step).  Two waves per SIMD from the same workgroup: 53.8 -> 46.1 us
     // (stage-4 conv2, 16 images), 73 -> 65 us at 32 images where two four-wave workgroups already shared a CU, 30.5 -> 27.4 us
     // (SSH 80 x 80 context conv); same K order, bit-identical (force_tile 19: the four-wave form).
-    static const int tile_waves = [] { const char *e = getenv("RFD_TILE_WAVES"); return e ? atoi(e) : 8; }(); // 4: the older forms (A/B)
-    if (kx_ok && p.Cout % 128 == 0) return tile_waves == 4 ? launch_conv3x3_kx<128, 2, 2>(p, s) : launch_conv3x3_kx<128, 4, 2>(p, s);
+    if (kx_ok && p.Cout % 128 == 0) return launch_conv3x3_kx<128, 4, 2>(p, s);
     // (with BN = 64 the merged-kx kernel measured 7 % slower than the generic 128x64 tile at 3 workgroups / CU)
     // Per-layer tile choice for a chain that has the GPU to itself (unsplit passes, B < 16; tools/tile_sweep.py): the
     // 128x64 tile (3 workgroups per CU, twice the grid) wins by 5-28 % where the 128x128 grid cannot give every CU a
@@ -3112,103 +2976,18 @@ int launch_conv(const ConvParams &p, hipStream_t s)
         if (p.force_tile == 1 || p.in_scale) return launch_conv_cfg<128, 128, 2, 2, 2>(p, s);
         // eight waves on the 128 x 128 tile (round 4; as in the merged-kx kernel above): 46.5 vs 49.5 us and 39.2 vs 41.0 us on the
         // stride-2 3x3 layers, 24.8 vs 26.2 us on the 1024 -> 256 lateral; the K = 2048 lateral ties (26.5 vs 26.0) and keeps four
-        if (tile_waves != 4 && !(p.KH == 1 && p.Cin + p.Cin2 >= 2048)) return launch_conv_cfg<128, 128, 4, 2, 3>(p, s);
+        if (!(p.KH == 1 && p.Cin + p.Cin2 >= 2048)) return launch_conv_cfg<128, 128, 4, 2, 3>(p, s);
         return launch_conv_cfg<128, 128, 2, 2, 3>(p, s);
     }
     // fused SSH pair (conv1 + ctx1 along N): eight waves (32 x 96 wave tiles) since round 4 -- these layers have at most 50 tiles
     // below the halo kernel's threshold, one workgroup per CU, and the four-wave form needs 284 registers (one wave per SIMD)
-    if (p.Cout % 192 == 0 && p.Cout % 128 != 0) return (tile_waves == 4 || p.force_tile == 1 || p.force_tile == 19) ? launch_conv_cfg<128, 192, 2, 2, 2>(p, s) : launch_conv_cfg<128, 192, 4, 2, 2>(p, s);
+    if (p.Cout % 192 == 0 && p.Cout % 128 != 0) return (p.force_tile == 1 || p.force_tile == 19) ? launch_conv_cfg<128, 192, 2, 2, 2>(p, s) : launch_conv_cfg<128, 192, 4, 2, 2>(p, s);
     // 128x64: the 2-slot ring keeps 3 workgroups per CU, which measured faster than a deeper ring at 2
     if (p.Cout % 64 == 0) {
         if (p.force_tile == 3) return launch_conv_cfg<256, 64, 4, 1, 2>(p, s); // 64x64 wave tiles, 2 workgroups / CU
         return launch_conv_cfg<128, 64, 4, 1, 2>(p, s);
     }
     return launch_conv_cfg<128, 32, 4, 1, 2>(p, s);
-}
-
-// ------------------------------------------------------------------------------------------------
-// conv0: 7x7 stride 2 pad 3, Cin = 3 (+1 zero channel), Cout = 64, fused bias + ReLU.
-// K is laid out as 7 (ky) x 32 (8 kx x 4 channels; kx = 7 and channel 3 carry zero weights), so each
-// ky is exactly one 16x16x32 MFMA K step and a lane's 8-element B fragment is two adjacent input
-// pixels (16 contiguous bytes of the NHWC4 image).  Each wave keeps all 64x224 weights in registers
-// (28 A fragments) and streams 16-pixel output tiles.
-// ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) conv0_kernel(const bf16_t *__restrict__ x4,
-                                                    const bf16_t *__restrict__ w, // [64][7][32]
-                                                    const float *__restrict__ bias,
-                                                    bf16_t *__restrict__ y, int B, int H, int W)
-{
-    const int lane = threadIdx.x & 63, frow = lane & 15, fq = lane >> 4;
-    const int Ho = H >> 1, Wo = W >> 1;
-    const long long M = (long long)B * Ho * Wo;
-    const long long ntile = (M + 15) >> 4;
-    bf16x8 af[4][7];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int k = 0; k < 7; ++k)
-            af[i][k] = *reinterpret_cast<const bf16x8 *>(w + ((size_t)(i * 16 + frow) * 7 + k) * 32 + fq * 8);
-    float4 bv[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) bv[i] = *reinterpret_cast<const float4 *>(bias + i * 16 + fq * 4);
-
-    const long long wave_id = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const long long nwaves = (long long)gridDim.x * 4;
-    for (long long t = wave_id; t < ntile; t += nwaves) {
-        const long long m = t * 16 + frow;
-        const bool mok = m < M;
-        int b = 0, ho = 0, wo = 0;
-        if (mok) {
-            b = (int)(m / ((long long)Ho * Wo));
-            const int rem = (int)(m - (long long)b * Ho * Wo);
-            ho = rem / Wo;
-            wo = rem - ho * Wo;
-        }
-        const int wi = 2 * wo - 3 + 2 * fq; // first of this lane's two input pixels
-        const bool w0ok = mok && (unsigned)wi < (unsigned)W, w1ok = mok && (unsigned)(wi + 1) < (unsigned)W;
-        f32x4 acc[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        uint4 frag[7];
-#pragma unroll
-        for (int k = 0; k < 7; ++k) {
-            const int hi = 2 * ho - 3 + k;
-            const bool hok = (unsigned)hi < (unsigned)H;
-            const uint2 *px = reinterpret_cast<const uint2 *>(x4) + ((long long)b * H + hi) * W + wi;
-            const uint2 p0 = (hok && w0ok) ? px[0] : make_uint2(0, 0);
-            const uint2 p1 = (hok && w1ok) ? px[1] : make_uint2(0, 0);
-            frag[k] = make_uint4(p0.x, p0.y, p1.x, p1.y);
-        }
-#pragma unroll
-        for (int k = 0; k < 7; ++k) {
-            const bf16x8 bf = __builtin_bit_cast(bf16x8, frag[k]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][k], bf, acc[i], 0, 0, 0);
-        }
-        if (mok) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                *reinterpret_cast<uint2 *>(y + m * 64 + i * 16 + fq * 4) =
-                    pack_bf16x4(fmaxf(acc[i][0] + bv[i].x, 0.f), fmaxf(acc[i][1] + bv[i].y, 0.f),
-                                fmaxf(acc[i][2] + bv[i].z, 0.f), fmaxf(acc[i][3] + bv[i].w, 0.f));
-        }
-    }
-}
-
-int launch_conv0(const bf16_t *x4, const bf16_t *w, const float *bias, bf16_t *y, int B, int H, int W,
-                 hipStream_t s)
-{
-    if ((H | W) & 1) {
-        set_error("conv0: input %dx%d must be even", H, W);
-        return RFD_ERR_INVALID_ARG;
-    }
-    const long long ntile = ((long long)B * (H / 2) * (W / 2) + 15) / 16;
-    const int grid = (int)std::min<long long>((ntile + 3) / 4, 256 * 8);
-    if (note_launch("conv0_kernel")) return RFD_OK;
-    hipLaunchKernelGGL(conv0_kernel, dim3(grid), dim3(256), 0, s, x4, w, bias, y, B, H, W);
-    RFD_HIP(hipGetLastError());
-    return RFD_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3573,10 +3352,9 @@ int launch_stem(const bf16_t *x4, const bf16_t *w, const float *bias, const floa
     const int tiles_h = ceil_div(Hp, kStemPH), tiles_w = ceil_div(Wp, kStemPW);
     const int ntiles = B * tiles_h * tiles_w;
     // persistent form from 4 tiles per workgroup slot (2 workgroups per CU by LDS): weights stay in registers, the next patch is
-    // prefetched (RFD_STEM_PERSIST=0: the one-tile kernel, for A/B; bit-identical)
-    static const int persist_env = [] { const char *e = getenv("RFD_STEM_PERSIST"); return e ? atoi(e) : 1; }();
+    // prefetched
     const int slots = 2 * device_cus();
-    if (persist_env && ntiles >= 4 * slots) {
+    if (ntiles >= 4 * slots) {
         const int per = ceil_div(ntiles, slots), grid = ceil_div(ntiles, per);
         if (w1 && t1 && fused) { // the first unit's conv1 on the pooled tile (Network::run offers it when the next op is that conv)
             *fused = true;
@@ -3593,65 +3371,6 @@ int launch_stem(const bf16_t *x4, const bf16_t *w, const float *bias, const floa
     if (note_launch("stem_kernel")) return RFD_OK;
     hipLaunchKernelGGL(stem_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, x4, w, bias, scale, shift, y,
                        H, W, tiles_w, tiles_h);
-    RFD_HIP(hipGetLastError());
-    return RFD_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// 3x3 stride-2 pad-1 max pool (NHWC bf16), optional fused per-channel affine + ReLU on the output
-// (the BN1+ReLU that opens the first pre-activation unit).  8 channels (16 bytes) per thread.
-// ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) maxpool_kernel(const bf16_t *__restrict__ x, bf16_t *__restrict__ y,
-                                                      const float *__restrict__ scale,
-                                                      const float *__restrict__ shift, int B, int H, int W,
-                                                      int C, int Ho, int Wo)
-{
-    const int cg = C >> 3;
-    const long long total = (long long)B * Ho * Wo * cg;
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int c = (int)(i % cg) * 8;
-    long long pix = i / cg;
-    const int wo = (int)(pix % Wo);
-    pix /= Wo;
-    const int ho = (int)(pix % Ho);
-    const int b = (int)(pix / Ho);
-    float mx[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) mx[k] = -INFINITY;
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy) {
-        const int hi = 2 * ho - 1 + dy;
-        if ((unsigned)hi >= (unsigned)H) continue;
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {
-            const int wi = 2 * wo - 1 + dx;
-            if ((unsigned)wi >= (unsigned)W) continue;
-            const uint4 v = *reinterpret_cast<const uint4 *>(x + (((long long)b * H + hi) * W + wi) * C + c);
-            const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                mx[2 * k] = fmaxf(mx[2 * k], bf16_bits_to_f32(u[k] & 0xffffu));
-                mx[2 * k + 1] = fmaxf(mx[2 * k + 1], bf16_bits_to_f32(u[k] >> 16));
-            }
-        }
-    }
-    if (scale) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) mx[k] = fmaxf(mx[k] * scale[c + k] + shift[c + k], 0.f);
-    }
-    const uint2 lo = pack_bf16x4(mx[0], mx[1], mx[2], mx[3]), hi2 = pack_bf16x4(mx[4], mx[5], mx[6], mx[7]);
-    *reinterpret_cast<uint4 *>(y + i * 8) = make_uint4(lo.x, lo.y, hi2.x, hi2.y);
-}
-
-int launch_maxpool3x3s2(const bf16_t *x, bf16_t *y, const float *scale, const float *shift, int B, int H,
-                        int W, int C, hipStream_t s)
-{
-    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-    const long long total = (long long)B * Ho * Wo * (C / 8);
-    if (note_launch("maxpool_kernel")) return RFD_OK;
-    hipLaunchKernelGGL(maxpool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, y, scale,
-                       shift, B, H, W, C, Ho, Wo);
     RFD_HIP(hipGetLastError());
     return RFD_OK;
 }

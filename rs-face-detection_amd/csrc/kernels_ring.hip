@@ -37,11 +37,6 @@
 
 namespace rfd {
 
-#ifndef RFD_RING_EXP
-#define RFD_RING_EXP 0 // timing experiments (tools/build_variant.sh; results are garbage): 1 loaders ignore FREE, 2 consumers ignore
-#endif                 // FULL, 3 both, 4 loaders publish without waiting for the data, 5 polls without s_sleep; on top of 3 (no
-                       // handshake at all): 6 consumers skip the fragment reads, 7 consumers skip the MFMAs, 8 consumers do nothing
-#define RFD_RING_NOSYNC (RFD_RING_EXP == 3 || RFD_RING_EXP >= 6)
 #ifndef RFD_RING_ROLES
 #define RFD_RING_ROLES 0 // how roles are dealt to the 8 waves: 0 = waves 0-3 load, 4-7 compute; 1 = even waves load, odd waves compute
 #endif
@@ -71,7 +66,7 @@ __device__ __forceinline__ void ring_wait(uint32_t addr, uint32_t target, bool &
     if (dead) return;
     for (int it = 0; it < kRingSpinLimit; ++it) {
         if (ring_flag_read(addr) >= target) return;
-        if (RFD_RING_EXP != 5) __builtin_amdgcn_s_sleep(1);
+        __builtin_amdgcn_s_sleep(1);
     }
     dead = true;
     asm volatile("ds_write_b32 %0, %1" : : "v"(gave_up_word), "v"(1u) : "memory");
@@ -79,7 +74,6 @@ __device__ __forceinline__ void ring_wait(uint32_t addr, uint32_t target, bool &
 template <int N> __device__ __forceinline__ void ring_vmcnt()
 {
     static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
-    if (RFD_RING_EXP == 4 && N != 0) return;
     asm volatile("s_waitcnt vmcnt(%0)" : : "i"(N) : "memory");
 }
 
@@ -115,7 +109,7 @@ template <bool KX3> struct RingGeom {
 };
 
 // grid: tiles_m x tiles_n workgroups of 512 threads (waves 0-3 load, 4-7 compute); dynamic LDS: see launch_conv_ring
-template <bool KX3, bool CHUNK_MAJOR>
+template <bool KX3>
 __global__ void __launch_bounds__(512) conv_ring_kernel(const ConvParams p)
 {
     using R = RingGeom<KX3>;
@@ -198,7 +192,7 @@ __global__ void __launch_bounds__(512) conv_ring_kernel(const ConvParams p)
             auto step = [&](auto kx_c) __attribute__((always_inline)) {
                 constexpr int kx = decltype(kx_c)::value;
                 if (kx == 0) {
-                    if (xneed && !(RFD_RING_EXP == 1 || RFD_RING_NOSYNC)) ring_wait(freeX + 4 * xslot, xneed, dead, gave_up);
+                    if (xneed) ring_wait(freeX + 4 * xslot, xneed, dead, gave_up);
                     const uint32_t rowoff = (uint32_t)(ky * p.W * p.ldx * 2);
 #pragma unroll
                     for (int q = 0; q < XP; ++q) {
@@ -207,7 +201,7 @@ __global__ void __launch_bounds__(512) conv_ring_kernel(const ConvParams p)
                     }
                     if (++xslot == NSX) { xslot = 0; xneed += 4; }
                 }
-                if (wneed && !(RFD_RING_EXP == 1 || RFD_RING_NOSYNC)) ring_wait(freeW + 4 * wslot, wneed, dead, gave_up);
+                if (wneed) ring_wait(freeW + 4 * wslot, wneed, dead, gave_up);
                 const uint32_t col = (uint32_t)((((ky * 3 + kx) * p.Cin) + (kc << 6)) * 2);
 #pragma unroll
                 for (int q = 0; q < WP; ++q) blds16(rw, woff[q], col, Ws + wslot * BN * 64 + (wave + 4 * q) * 512);
@@ -260,11 +254,11 @@ __global__ void __launch_bounds__(512) conv_ring_kernel(const ConvParams p)
                 }
             }
             const int kc_n = p.Cin >> 6;
-            int ky = 0, kx = 0, kc = 0, wtap = 0, wkc = 0;
+            int ky = 0, kx = 0, kc = 0;
             int slot = 0, pslot = 0;
             uint32_t need = 0;
             for (int s = 0; s < nsteps; ++s) {
-                if (need && !(RFD_RING_EXP == 1 || RFD_RING_NOSYNC)) ring_wait(freeW + 4 * slot, need, dead, gave_up);
+                if (need) ring_wait(freeW + 4 * slot, need, dead, gave_up);
                 if (s < nk1) {
                     const uint32_t tap = (uint32_t)((ky * p.W + kx) * p.ldx * 2);
                     const uint32_t so = (uint32_t)__builtin_amdgcn_readfirstlane(kc << 7);
@@ -273,11 +267,9 @@ __global__ void __launch_bounds__(512) conv_ring_kernel(const ConvParams p)
                         const bool ok = (unsigned)(hi0[q] + ky) < (unsigned)p.H && (unsigned)(wi0[q] + kx) < (unsigned)p.W;
                         blds16(rx, ok ? xoff[q] + tap : kOob, so, Xs + slot * XR * 64 + (wave + 4 * q) * 512);
                     }
-                    // K order: (ky, kx, chunk) as the weight rows are laid out, or chunk-major (chunk, ky, kx) for the layer shapes
-                    // the halo-tile 3x3 kernels are bound to (launch_conv sets p.k_chunk_major): one K order per layer
-                    if (CHUNK_MAJOR) {
-                        if (++kx == p.KW) { kx = 0; if (++ky == p.KH) { ky = 0; ++kc; } }
-                    } else if (++kc == kc_n) {
+                    // K order: (ky, kx, chunk) as the weight rows are laid out (the layers that accumulate chunk-major -- launch_conv
+                    // sets p.k_chunk_major -- are 3x3 / stride 1 and take the KX3 form above)
+                    if (++kc == kc_n) {
                         kc = 0;
                         if (++kx == p.KW) { kx = 0; ++ky; }
                     }
@@ -285,13 +277,8 @@ __global__ void __launch_bounds__(512) conv_ring_kernel(const ConvParams p)
 #pragma unroll
                     for (int q = 0; q < XP; ++q) blds16(rx2, xoff2[q], (uint32_t)((s - nk1) << 7), Xs + slot * XR * 64 + (wave + 4 * q) * 512);
                 }
-                {
-                    const uint32_t col = CHUNK_MAJOR ? (uint32_t)__builtin_amdgcn_readfirstlane(s < nk1 ? (wtap * p.Cin + (wkc << 6)) * 2 : s << 7)
-                                                     : (uint32_t)(s << 7);
 #pragma unroll
-                    for (int q = 0; q < WP; ++q) blds16(rw, woff[q], col, Ws + slot * BN * 64 + (wave + 4 * q) * 512);
-                    if (CHUNK_MAJOR && ++wtap == p.KH * p.KW) { wtap = 0; ++wkc; }
-                }
+                for (int q = 0; q < WP; ++q) blds16(rw, woff[q], (uint32_t)(s << 7), Ws + slot * BN * 64 + (wave + 4 * q) * 512);
                 if (++slot == NSW) { slot = 0; need += 4; }
                 if (s >= D) {
                     ring_vmcnt<R::later(0)>();
@@ -335,12 +322,10 @@ __global__ void __launch_bounds__(512) conv_ring_kernel(const ConvParams p)
     int wslot = 0, xslot = 0, kx = 0;
     uint32_t wwant = 4, xwant = 4;
     auto wait_step = [&]() { // for the step the cursors point at
-        if (RFD_RING_EXP == 2 || RFD_RING_NOSYNC) return;
         if (KX3 ? kx == 0 : false) ring_wait(fullX + 4 * xslot, xwant, dead, gave_up);
         ring_wait(fullW + 4 * wslot, wwant, dead, gave_up);
     };
     auto read_half = [&](int kk, bf16x8 (&A)[TN], bf16x8 (&B)[TM]) {
-        if (RFD_RING_EXP == 6 || RFD_RING_EXP == 8) return;
         const bf16_t *ws = Ws + wslot * BN * 64 + (wn * WN) * 64;
         const bf16_t *xs = Xs + xslot * XR * 64 + (wm * WM + (KX3 ? kx : 0)) * 64;
         const int ch = kk * 4 + fq;
@@ -390,11 +375,6 @@ __global__ void __launch_bounds__(512) conv_ring_kernel(const ConvParams p)
                 B[j] = v;
             }
         }
-        if (RFD_RING_EXP == 7 || RFD_RING_EXP == 8) {
-#pragma unroll
-            for (int i = 0; i < TN; ++i) asm volatile("" : : "v"(A[i]), "v"(B[i])); // keep the reads
-            return;
-        }
 #pragma unroll
         for (int i = 0; i < TN; ++i)
 #pragma unroll
@@ -403,11 +383,7 @@ __global__ void __launch_bounds__(512) conv_ring_kernel(const ConvParams p)
 
     // software pipeline over half steps (32 of the 64 K columns): the reads of the next half are issued before the MFMAs of
     // the current one, into the register set the previous half has just left
-#if RFD_RING_EXP >= 6
-    bf16x8 A0[TN] = {}, B0[TM] = {}, A1[TN] = {}, B1[TM] = {};
-#else
     bf16x8 A0[TN], B0[TM], A1[TN], B1[TM];
-#endif
     wait_step();
     read_half(0, A0, B0);
     for (int s = 0; s < nsteps; ++s) {
@@ -447,18 +423,13 @@ int launch_conv_ring(const ConvParams &p, hipStream_t s)
     // the workgroup owns its CU: one ring per CU is the point (rule 4 for the persistent kernels)
     constexpr size_t lds = 160 * 1024;
     static_assert(RingGeom<true>::kSlotBytes + 128 <= lds && RingGeom<false>::kSlotBytes + 128 + 16 * 1024 <= lds, "LDS budget");
-#define RFD_RING_LAUNCH(KX, CM)                                                              \
-    do {                                                                                     \
-        auto kern = conv_ring_kernel<KX, CM>;                                                \
-        static DynLdsOnce once;                                                              \
-        if (note_launch("conv_ring_kernel<%s, %s>", KX ? "true" : "false", CM ? "true" : "false")) return RFD_OK; \
-        RFD_TRY(once.ensure(reinterpret_cast<const void *>(kern), (int)lds));                \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, p);                          \
-    } while (0)
-    if (kx3) RFD_RING_LAUNCH(true, true);
-    else if (p.k_chunk_major) RFD_RING_LAUNCH(false, true);
-    else RFD_RING_LAUNCH(false, false);
-#undef RFD_RING_LAUNCH
+    // the merged-kx form accumulates chunk-major, the generic form in weight-row order: a chunk-major layer is a 3x3 / stride-1 one
+    if (!kx3 && p.k_chunk_major) { set_error("conv_ring: the generic form has no chunk-major K order"); return RFD_ERR_INVALID_ARG; }
+    auto kern = kx3 ? conv_ring_kernel<true> : conv_ring_kernel<false>;
+    static DynLdsOnce once[2];
+    if (note_launch("conv_ring_kernel<%s>", kx3 ? "true" : "false")) return RFD_OK;
+    RFD_TRY(once[kx3].ensure(reinterpret_cast<const void *>(kern), (int)lds));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, p);
     RFD_HIP(hipGetLastError());
     return RFD_OK;
 }

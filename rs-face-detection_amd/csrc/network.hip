@@ -80,9 +80,6 @@ void Graph::build_r50()
         ops.push_back(o);
     }
     static const int units[4] = {3, 4, 6, 3};
-    // number of leading stages whose middle units hand over only the raw sum (see fuse_act below); RFD_FUSE_ACT_STAGES: A/B knob
-    int fuse_act_stages = 3;
-    if (const char *e = getenv("RFD_FUSE_ACT_STAGES")) fuse_act_stages = atoi(e);
     static const int mids[4] = {64, 128, 256, 512};
     int x_act = t_p, x_raw = -1, cin = 64, h = H / 4, w = W / 4;
     int prev_l3 = -1; // conv3 layer of the previous unit when its BN+ReLU output was NOT materialised
@@ -124,15 +121,12 @@ void Graph::build_r50()
             // conv1 applies the affine to its operand fragments.  (Round 1 measured that as a loss for stage 3 with the generic
             // kernel; with the HBM-bound streaming kernels of round 2 -- pw_stream without the second output, pw_gemm<true> --
             // it is +1-2 % end to end: 7.24 k vs 7.09-7.19 k img/s on one box.  Stage 4 too: 7.13-7.18 k, so it keeps both.)
-            const bool fuse_act = s < fuse_act_stages;
+            const bool fuse_act = s < 3;
             const int t_raw = last ? -1 : add_tensor(cout, ho, wo);
             const int t_act = (last || !fuse_act) ? add_tensor(cout, ho, wo) : -1;
             const int o3 = add_conv(l3, t2, t_raw, 0, dim_match ? x_raw : -1, t_act);
             if (!dim_match) { ops[o3].in2 = x_act; ops[o3].layer2 = ls; }
-            // stage 2 (round 3): the same pairing for the dim-match units -- pw_b2b_kernel, or two launches where it does not pay
-            // (RFD_B2B_STAGES=1 keeps it to stage 1: A/B knob)
-            static const int b2b_stages = [] { const char *e = getenv("RFD_B2B_STAGES"); return e ? atoi(e) : 6; }(); // 1: stage 1 only; 2: + stage 2's middle units; 3: + stage 1 -> 2; 4: + stage 3's middle units; 5: + stage 2 -> 3; 6: + stage 2's first unit
-            if ((s == 0 && last && b2b_stages >= 3) || (s == 1 && last && b2b_stages >= 5)) {
+            if (s <= 1 && last) {
                 // the last unit of stage 1 with stage 2's first conv1 (256 -> 128 at 160 x 160, on the stage output): pw_b2b_kernel;
                 // the last unit of stage 2 with stage 3's first conv1 (512 -> 256 at 80 x 80): pw_pair_kernel
                 snprintf(nm, sizeof nm, "stage%d_unit%d_conv1", s + 2, 1);
@@ -140,10 +134,10 @@ void Graph::build_r50()
                 b2b_t1 = add_tensor(mids[s + 1], ho, wo);
                 ops[o3].kind = OP_B2B; ops[o3].layer_b = l1n; ops[o3].out_b = b2b_t1;
             }
-            if ((s == 0 || (s == 1 && b2b_stages >= 2 && dim_match && fuse_act) || (s == 2 && b2b_stages >= 4 && dim_match && fuse_act) ||
-                 (s == 1 && b2b_stages >= 6 && !dim_match && fuse_act)) && !last) {
+            if ((s <= 1 || (s == 2 && dim_match)) && !last) {
                 // stage 1: conv3 of this unit and conv1 of the NEXT unit run back to back in one kernel; the
-                // activated 256-channel tile stays in LDS (conv_b2b_s1_kernel)
+                // activated 256-channel tile stays in LDS (conv_b2b_s1_kernel).  Stages 2 (every unit) and 3 (the dim-match units):
+                // the same pairing -- pw_b2b_kernel / pw_pair_kernel, or two launches where it does not pay
                 snprintf(nm, sizeof nm, "stage%d_unit%d_conv1", s + 1, u + 2);
                 const int l1n = add_layer(nm, cout, mid, 1, 1, 0, 1.0f, 0);
                 b2b_t1 = add_tensor(mid, ho, wo);
@@ -384,7 +378,6 @@ int Graph::build(int backbone_, int w, int h)
 double Graph::layer_macs(int i) const
 {
     const Op &o = ops[i];
-    if (o.kind == OP_POOL) return 0.0;
     const Layer &L = layers[o.layer];
     if (o.kind == OP_STEM) return (double)(net_h / 2) * (net_w / 2) * L.cout * L.kh * L.kw * L.cin;
     if (o.kind == OP_DW) return (double)tensors[o.out].H * tensors[o.out].W * L.cout * 9;
@@ -413,7 +406,7 @@ int Network::create(int backbone, int net_w, int net_h, int max_batch_, int prec
     precision = precision_;
     if (precision != 0) {
         for (const Op &o : g.ops)
-            if (o.kind == OP_DW || o.kind == OP_FIRST || o.kind == OP_CONV0) { set_error("f32 parity mode: this backbone has no f32 kernels (RetinaFace-R50 only)"); return RFD_ERR_INVALID_ARG; }
+            if (o.kind == OP_DW || o.kind == OP_FIRST) { set_error("f32 parity mode: this backbone has no f32 kernels (RetinaFace-R50 only)"); return RFD_ERR_INVALID_ARG; }
         use_graph = false;
         RFD_HIP(hipMalloc((void **)&d_w32, g.w_total * sizeof(float)));
         RFD_HIP(hipMemset(d_w32, 0, g.w_total * sizeof(float)));
@@ -437,9 +430,6 @@ int Network::create(int backbone, int net_w, int net_h, int max_batch_, int prec
         RFD_HIP(hipEventCreateWithFlags(&ev_part_join[hh], hipEventDisableTiming));
     }
     RFD_HIP(hipEventCreateWithFlags(&ev_part_fork, hipEventDisableTiming));
-    RFD_HIP(hipEventCreateWithFlags(&ev_shift, hipEventDisableTiming));
-
-    if (getenv("RFD_CHAIN_SHIFT")) chain_shift_op = atoi(getenv("RFD_CHAIN_SHIFT"));
     RFD_HIP(hipMalloc((void **)&d_zero, 256));
     RFD_HIP(hipMemset(d_zero, 0, 256));
     d_buffers.assign(g.buffer_bytes_per_image.size(), nullptr);
@@ -488,9 +478,6 @@ void Network::destroy()
     }
     if (ev_part_fork) (void)hipEventDestroy(ev_part_fork);
     ev_part_fork = nullptr;
-    if (ev_shift) (void)hipEventDestroy(ev_shift);
-    ev_shift = nullptr;
-
 
     for (hipEvent_t e : ev) (void)hipEventDestroy(e);
     for (hipGraphExec_t ge : graph_exec)
@@ -758,10 +745,7 @@ int Network::run(int B, hipStream_t s, int first_op, int last_op, int batch_off,
             s = side[part][bidx];
         }
         if (profiling) RFD_HIP(hipEventRecord(ev[2 * i], s));
-        if (o.kind == OP_CONV0) {
-            RFD_TRY(launch_conv0((const bf16_t *)tensor_ptr(o.in, batch_off), d_w + L.w_off, d_b + L.b_off,
-                                 (bf16_t *)tensor_ptr(o.out, batch_off), B, tin.H, tin.W, s));
-        } else if (o.kind == OP_FIRST) {
+        if (o.kind == OP_FIRST) {
             RFD_TRY(launch_first3x3((const bf16_t *)tensor_ptr(o.in, batch_off), d_w + L.w_off, d_b + L.b_off, (bf16_t *)tensor_ptr(o.out, batch_off), B,
                                     tin.H, tin.W, g.tensors[o.out].C, s));
         } else if (o.kind == OP_DW) {
@@ -770,10 +754,9 @@ int Network::run(int B, hipStream_t s, int first_op, int last_op, int batch_off,
         } else if (o.kind == OP_STEM) {
             // Peephole (round 4): when the next op of the range is the first unit's conv1 -- a plain 1x1 64 -> 64 conv + bias + ReLU
             // on the stem's output -- the persistent stem kernel computes it on the pooled tile (launch_stem decides whether that
-            // form runs); the conv's own op is then skipped.  Bit-identical (tests/test_persistent_gpu.py); RFD_STEM_FUSE=0: never.
-            static const int fuse_env = [] { const char *e = getenv("RFD_STEM_FUSE"); return e ? atoi(e) : 1; }();
+            // form runs); the conv's own op is then skipped.  Bit-identical (tests/test_persistent_gpu.py).
             const bf16_t *w1 = nullptr; const float *b1 = nullptr; bf16_t *t1 = nullptr;
-            if (fuse_env && !profiling && force_tile == 0 && i + 1 <= last_op && skip_ops.empty()) {
+            if (!profiling && force_tile == 0 && i + 1 <= last_op && skip_ops.empty()) {
                 const Op &n = g.ops[i + 1];
                 const Layer &Ln = g.layers[n.layer];
                 const bool plain = n.kind == OP_CONV && n.in == o.out && Ln.kh == 1 && Ln.kw == 1 && Ln.stride == 1 && Ln.cin_d == 64 &&
@@ -810,10 +793,6 @@ int Network::run(int B, hipStream_t s, int first_op, int last_op, int batch_off,
             bp.B = B; bp.H = tin.H; bp.W = tin.W; bp.Cin = L.cin_d;
             bp.force_tile = force_tile;
             RFD_TRY(launch_conv_b2b_s1(bp, s));
-        } else if (o.kind == OP_POOL) {
-            RFD_TRY(launch_maxpool3x3s2((const bf16_t *)tensor_ptr(o.in, batch_off), (bf16_t *)tensor_ptr(o.out, batch_off),
-                                        d_b + g.b_total + L.a_off, d_b + g.b_total + L.a_off + L.cout_d, B, tin.H, tin.W,
-                                        tin.C, s));
         } else {
             const int tout = o.out >= 0 ? o.out : (o.out2 >= 0 ? o.out2 : o.outf);
             ConvParams p;
@@ -862,7 +841,6 @@ int Network::run(int B, hipStream_t s, int first_op, int last_op, int batch_off,
             RFD_TRY(launch_conv(p, s));
         }
         if (profiling) RFD_HIP(hipEventRecord(ev[2 * i + 1], s));
-        if (co_running && part == 0 && i == chain_shift_op) RFD_HIP(hipEventRecord(ev_shift, main_stream));
     }
     for (int bidx = 0; bidx < 2; ++bidx)
         if (forked[bidx]) { // join
@@ -891,11 +869,6 @@ int Network::run_f32(int B, hipStream_t s, int first_op, int last_op, int batch_
             RFD_TRY(launch_conv0_f32((const bf16_t *)tensor_ptr(o.in, batch_off), d_w32 + L.w_off, d_b + L.b_off, c0, B, tin.H, tin.W, s));
             RFD_TRY(launch_maxpool_f32(c0, (float *)tensor_ptr32(o.out, batch_off), aff + L.a_off, aff + L.a_off + L.cout_d, B, tin.H / 2,
                                        tin.W / 2, 64, s));
-            continue;
-        }
-        if (o.kind == OP_POOL) {
-            RFD_TRY(launch_maxpool_f32((const float *)tensor_ptr32(o.in, batch_off), (float *)tensor_ptr32(o.out, batch_off), aff + L.a_off,
-                                       aff + L.a_off + L.cout_d, B, tin.H, tin.W, tin.C, s));
             continue;
         }
         if (o.kind != OP_CONV && o.kind != OP_B2B) { set_error("f32 parity mode: op kind %d has no f32 kernel", o.kind); return RFD_ERR_INVALID_ARG; }
@@ -1007,9 +980,6 @@ int Network::split_body(int B, int P, hipStream_t s)
     for (int p = 0; p < P && st == RFD_OK; ++p) {
         const int Bp = B / P + (p < B % P ? 1 : 0);
         RFD_HIP(hipStreamWaitEvent(part_stream[p], ev_part_fork, 0));
-        // (A/B knob RFD_CHAIN_SHIFT.  ev_shift is recorded by part 0 in run(); part 0 is enqueued before this wait, so the
-        // event this waits for is this pass's.  Split passes are never captured into a graph -- run_graphed -- so no capture guard.)
-        if (p == 1 && P == 2 && chain_shift_op >= 0 && chain_shift_op < (int)g.ops.size()) RFD_HIP(hipStreamWaitEvent(part_stream[1], ev_shift, 0));
         st = run(Bp, part_stream[p], 0, -1, off, p);
         if (st == RFD_OK) RFD_HIP(hipEventRecord(ev_part_join[p], part_stream[p]));
         off += Bp;

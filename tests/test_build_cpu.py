@@ -123,7 +123,7 @@ def test_counted_vmcnt_publishes_only_from_waves_without_stores(disasm):
                 ring += 1
             else:
                 assert n == 0, "%s: a counted vmcnt publishes LDS-DMA data outside the ring kernels (every other kernel drains)" % name
-    assert ring == 3
+    assert ring == 2   # conv_ring_kernel<false> (generic) and <true> (merged kx)
 
 
 @_needs_llvm
@@ -181,3 +181,26 @@ def test_every_persistent_kernel_requests_the_whole_cu(disasm, tmp_path):
         else:
             assert any(("%d%s" % (len(t), t)) in name for t in one_tile_per_workgroup), "%s: 8-wave LDS-DMA kernel outside the persistent launch path" % name
     assert seen == set(table), "listed but not in the code object: %s" % (set(table) - seen)
+
+
+ENV_NAMES = {"RFD_RCCL_LIB", "RFD_NMS_CHUNKED", "RFD_CONV_RING", "RFD_STREAM_TUNE", "RFD_STREAM_TUNE_VERBOSE", "GPU_MAX_HW_QUEUES"}
+
+
+def test_the_library_reads_only_the_documented_environment_variables():
+    """The shipped library holds no A/B knob: which kernel runs depends on the layer, the batch and debug_set_conv_tile, never
+    on a variable that happens to be in the environment.  Every string of librfd_hip.so that looks like one of its variables
+    (what `strings` prints, whole line RFD_* or GPU_MAX*) is one of the six DESIGN.md documents; and no preprocessor line of
+    the sources selects a timing-only *_EXP variant (builds that switched waits off)."""
+    lib = os.path.join(ROOT, "rs-face-detection_amd", "librfd_hip.so")
+    assert os.path.exists(lib), "run rs-face-detection_amd/build.sh (or __graft_entry__.build()) first"
+    with open(lib, "rb") as f:
+        data = f.read()
+    names = {m.decode() for m in re.findall(rb"[\x20-\x7e]{4,}", data) if re.fullmatch(rb"(RFD_|GPU_MAX)[A-Z0-9_]+", m)}
+    assert names == ENV_NAMES, "unexpected: %s, missing: %s" % (sorted(names - ENV_NAMES), sorted(ENV_NAMES - names))
+    csrc = os.path.join(ROOT, "rs-face-detection_amd", "csrc")
+    files = sorted(os.listdir(csrc))
+    assert len(files) >= 10, files
+    for fn in files:
+        with open(os.path.join(csrc, fn)) as f:
+            for no, line in enumerate(f, 1):
+                assert not (line.lstrip().startswith("#") and "_EXP" in line), "%s:%d: %s" % (fn, no, line.strip())

@@ -8,8 +8,8 @@ case per distinct kernel list.  Each case runs once on two input sets:
   every undecided one must lie in its interval, and the undecided share of an op stays <= 10 % (the bound is not vacuous).
 Outputs are poisoned with NaN before the launch: every element the op writes must be overwritten, every other byte kept.
 
-test_plan_covers_every_kernel_instantiation: every conv-path kernel the shipped objects hold is either checked here or listed
-in UNREACHABLE_IN_PROCESS with the environment knob that alone selects it."""
+test_plan_covers_every_kernel_instantiation: a conv-path kernel is in the shipped code objects if and only if this sweep runs it
+(no exceptions list: a kernel that only an environment variable, or nothing, could select does not ship)."""
 import os
 import re
 import subprocess
@@ -38,36 +38,6 @@ GEOMETRIES = [
     ("mnet025", 480, 352, 5, None), ("mnet025", 96, 64, 3, None), ("mnet025", 32, 32, 4, None),
 ]
 TILES = range(20)  # every force_tile value launch_conv knows (0 = the production heuristic)
-
-# conv-path kernels no in-process setting reaches: (the environment knob, read once at library load, that selects it -- None:
-# nothing does -- and why)
-UNREACHABLE_IN_PROCESS = {}
-_HALF = "pair kernel on half workgroups (A/B form)"
-_PX2 = "pair kernel, 32 pixels per wave (A/B form)"
-for _t, _why in (("4, 1", _HALF), ("4, 2", _PX2)):
-    _knob = "RFD_PAIR_HALF" if _t == "4, 1" else "RFD_PAIR_PX2"
-    for _a in ("4, 2, false, 0", "2, 2, true, 0", "2, 1, false, 4"):
-        UNREACHABLE_IN_PROCESS["pw_pair_kernel<%s, 0, %s, false>" % (_a, _t)] = (_knob, _why)
-    for _a in ("2, 1, false, 0", "1, 1, true, 0"):   # the streaming pair forms themselves need RFD_PW_PAIR=1
-        UNREACHABLE_IN_PROCESS["pw_pair_kernel<%s, 0, %s, false>" % (_a, _t)] = (_knob + " + RFD_PW_PAIR=1", _why)
-    for _a in ("1, 1, false, 0", "1, 1, false, 1"):  # launch_pw_pair<..., HALF1 = true> instantiates its env branch, never takes it
-        UNREACHABLE_IN_PROCESS["pw_pair_kernel<%s, 0, %s, false>" % (_a, _t)] = (None, "dead instantiation: the stage-1 pair "
-                                                                              "form has no half / px2 variant")
-UNREACHABLE_IN_PROCESS.update({
-    "pw_pair_kernel<2, 1, false, 0, 0, 8, 1, false>": ("RFD_PW_PAIR=1", "pair kernel instead of pw_b2b for stage 2 (A/B)"),
-    "pw_pair_kernel<1, 1, true, 0, 0, 8, 1, false>": ("RFD_PW_PAIR=1", "streaming pair at the stage 1 -> 2 boundary (A/B)"),
-    "pw_b2b_kernel<1, true>": ("RFD_PW_PAIR=2", "streaming pw_b2b at the stage 1 -> 2 boundary (A/B)"),
-    "conv0_kernel": (None, "no graph emits OP_CONV0 since the fused stem (OP_STEM) replaced conv0 + pool"),
-    "maxpool_kernel": (None, "no graph emits OP_POOL since the fused stem (OP_STEM) replaced conv0 + pool"),
-    "conv_ring_kernel<false, true>": (None, "chunk-major K without merged kx: a halo-shape layer with W < 3, which has W >= 16"),
-})
-for _f in ("1, true, false", "1, true, true", "2, true, true", "4, true, true"):
-    UNREACHABLE_IN_PROCESS["pw_stream_kernel<%s>" % _f] = ("RFD_FUSE_ACT_STAGES / RFD_B2B_STAGES", "a conv3 that stores its raw "
-                                                        "sum outside a back-to-back op: the default graph has none of that shape")
-for _cfg in ("128, 64, 4, 1, 2", "128, 32, 4, 1, 2", "256, 64, 4, 1, 2", "128, 128, 2, 2, 3"):
-    # chunk-major K order is set only for halo-shape layers (3x3 s1, Cout % 128 == 0 or 192, W >= 16); launch_conv sends those to
-    # the halo / merged-kx kernels or to the force_tile 1 / 2 / 18 generic forms, never to these tiles
-    UNREACHABLE_IN_PROCESS["conv_igemm_kernel<%s, true>" % _cfg] = (None, "chunk-major form of a tile no halo-shape layer reaches")
 
 NAN_BF16 = 0x7FC0
 NAN_F32 = 0x7FC00000
@@ -313,7 +283,7 @@ def _shipped_kernels(tmp):
 
 def test_plan_covers_every_kernel_instantiation(rfd, tmp_path):
     shipped = _shipped_kernels(str(tmp_path))
-    assert len(shipped) >= 70, sorted(shipped)
+    assert len(shipped) == 49, sorted(shipped)   # guards the name extraction: 47 in kernels_conv.o, 2 in kernels_ring.o
     reached = set()
     for bb, w, h, n, ops in GEOMETRIES:
         det = rfd.RetinaFaceDetection(image_size=(w, h), max_batch_size=n, max_det=16, backbone=_bb(rfd, bb))
@@ -324,15 +294,9 @@ def test_plan_covers_every_kernel_instantiation(rfd, tmp_path):
                 reached.update(names)
         finally:
             det.close()
-    unknown = reached - shipped
-    assert not unknown, "plan() names kernels the objects do not hold (name format drift?): %s" % sorted(unknown)
-    missing = shipped - reached - set(UNREACHABLE_IN_PROCESS)
-    assert not missing, "kernels without an exact-reference check: %s" % sorted(missing)
-    stale = set(UNREACHABLE_IN_PROCESS) & reached
-    assert not stale, "UNREACHABLE_IN_PROCESS entries the plan does reach: %s" % sorted(stale)
-    gone = set(UNREACHABLE_IN_PROCESS) - shipped
-    assert not gone, "UNREACHABLE_IN_PROCESS entries the objects no longer hold: %s" % sorted(gone)
-    print("\ncoverage: %d shipped conv-path kernels, %d checked, %d env-only" % (len(shipped), len(reached), len(UNREACHABLE_IN_PROCESS)))
+    print("\ncoverage: %d shipped conv-path kernels, %d reached by the sweep" % (len(shipped), len(reached)))
+    assert shipped == reached, "reached but not shipped (name format drift?): %s; shipped without an exact-reference check: %s" % (
+        sorted(reached - shipped), sorted(shipped - reached))
 
 
 BATCH_RUNS = {"r50": [(640, 640), (768, 480)], "mnet025": [(640, 640)]}

@@ -1,7 +1,7 @@
 #!/bin/bash
-# Diagnostic build of the library with extra macros on ONE translation unit (timing experiments; never shipped):
-#   tools/build_variant.sh exp1 -DRFD_HALO_EXP=1            ->  tools/bin/librfd_hip_exp1.so   (load with RFD_HIP_LIB=...)
-#   UNIT=kernels_ring tools/build_variant.sh r1 -DRFD_RING_EXP=1   (UNIT: the csrc/*.hip file rebuilt; default kernels_conv)
+# Diagnostic build of the library with extra macros on ONE translation unit (instrumentation; never shipped):
+#   tools/build_variant.sh stamps -DRFD_CLOCK_STAMPS        ->  tools/bin/librfd_hip_stamps.so   (load with RFD_HIP_LIB=...)
+#   UNIT=network tools/build_variant.sh diag -DRFD_DIAG     (UNIT: the csrc/*.hip file rebuilt; default kernels_conv)
 set -e
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 NAME="$1"; shift

@@ -6,7 +6,7 @@
 // Variants: A = the body as shipped, waves free-running; B = + the step barrier (s_waitcnt lgkmcnt(0); s_barrier);
 // C = one wave per SIMD (4 waves, twice the steps); D = no LDS reads in the loop (fragments read once): the MFMA issue alone;
 // E = A with 32 KiB of LDS-DMA per step issued by nobody but with 16 extra ds_write_b128 per wave and step (the LDS write
-// bandwidth a step's incoming operands take) -- not built: the DMA's own cost is measured in the kernels (RFD_WIDE_EXP).
+// bandwidth a step's incoming operands take) -- not built.
 // Prints cycles per step (median over workgroups, s_memtime), the clock held (s_memtime / s_memrealtime) and the PF/s implied.
 // The ideal is 64 MFMAs x 16 cycles x 2 waves per SIMD = 2 048 cycles per step.
 //
