@@ -59,6 +59,9 @@ typedef enum rfd_backbone {
  * capacity and output capacity are new.
  */
 typedef enum rfd_precision { RFD_PRECISION_BF16 = 0, RFD_PRECISION_F32 = 1 } rfd_precision;
+typedef enum rfd_schedule { RFD_SCHEDULE_THROUGHPUT = 0, RFD_SCHEDULE_LATENCY = 1 } rfd_schedule;
+/* Largest pass (images) a latency context runs with the split-K kernels. */
+#define RFD_LATENCY_MAX_BATCH 2
 
 typedef struct rfd_config {
     int image_w;                /* config.rs:26 image_size.0, default 640 */
@@ -77,7 +80,15 @@ typedef struct rfd_config {
                                  * FP32 tensor contract (face_detection.rs:261), reproducible to the bit by any evaluation that
                                  * sums the same products exactly.  A correctness mode: plain FMA kernels, one stream, ~60x slower
                                  * than the bf16 path. */
-    int reserved[5];
+    int schedule;               /* rfd_schedule: 0 = the throughput schedule (every context before this field existed); 1 = the
+                                 * latency schedule (bf16 path only): a pass of n <= RFD_LATENCY_MAX_BATCH images runs the
+                                 * long-K, few-tile convolutions as K segments over several workgroups (split-K); a larger pass
+                                 * runs exactly the throughput kernels.  Contract: results are deterministic; a frame's nine head
+                                 * tensors are bit-identical for every n <= RFD_LATENCY_MAX_BATCH and every position in the
+                                 * batch; they are NOT promised to equal the throughput schedule's bits (a segmented f32 sum
+                                 * rounds differently) -- both schedules meet the same per-op bound against the exact f64
+                                 * result (tests/test_conv_exact_gpu.py, tests/test_latency_gpu.py). */
+    int reserved[4];
 } rfd_config;
 
 /* A decoded source frame: HxWx3 u8, BGR, row stride in bytes (an OpenCV Mat CV_8UC3,

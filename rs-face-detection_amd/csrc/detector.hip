@@ -250,7 +250,7 @@ struct rfd_ctx {
     int ensure_network()
     {
         if (net_created) return RFD_OK;
-        RFD_TRY(net.create(cfg.backbone, cfg.image_w, cfg.image_h, cfg.max_batch_size, cfg.precision));
+        RFD_TRY(net.create(cfg.backbone, cfg.image_w, cfg.image_h, cfg.max_batch_size, cfg.precision, cfg.schedule));
         // the ring convolutions' bounded spins report into the same device word as the chunked NMS (check_nms_flag)
         net.d_fail = (int *)nms_state.p + (size_t)cfg.max_batch_size * kNmsChunks * 2;
         net_created = true;
@@ -405,7 +405,7 @@ int check_nms_flag(rfd_ctx *c)
     RFD_HIP(hipMemsetAsync(flag, 0, sizeof(int), c->stream));
     RFD_HIP(hipStreamSynchronize(c->stream));
     set_error("a device-side bounded wait gave up (chunked NMS: a workgroup waiting for its predecessor chunk; ring convolution: a "
-              "wave waiting for a ring slot); the detections of the batches since the last synchronisation are invalid "
+              "wave waiting for a ring slot; split-K convolution: an arrival counter left dirty by an earlier fault); the detections of the batches since the last synchronisation are invalid "
               "(re-submit them; RFD_NMS_CHUNKED=0 selects the one-workgroup-per-image NMS kernel, RFD_CONV_RING=0 the barrier-per-step convolutions)");
     return RFD_ERR_HIP;
 }
@@ -618,6 +618,8 @@ int rfd_create(const rfd_config *cfg, rfd_ctx **out)
     RFD_CHECK_ARG(cfg->max_det >= 1, "max_det < 1");
     RFD_CHECK_ARG(cfg->precision == RFD_PRECISION_BF16 || cfg->precision == RFD_PRECISION_F32, "precision must be RFD_PRECISION_BF16 or RFD_PRECISION_F32");
     RFD_CHECK_ARG(cfg->precision == RFD_PRECISION_BF16 || cfg->backbone == RFD_BACKBONE_R50, "the f32 parity mode exists for RetinaFace-R50 only");
+    RFD_CHECK_ARG(cfg->schedule == RFD_SCHEDULE_THROUGHPUT || cfg->schedule == RFD_SCHEDULE_LATENCY, "schedule must be RFD_SCHEDULE_THROUGHPUT or RFD_SCHEDULE_LATENCY");
+    RFD_CHECK_ARG(cfg->schedule == RFD_SCHEDULE_THROUGHPUT || cfg->precision == RFD_PRECISION_BF16, "the latency schedule exists for the bf16 path only (not the f32 parity mode)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         set_error("no HIP device is available: librfd_hip has no CPU fallback");

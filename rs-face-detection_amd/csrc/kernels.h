@@ -149,8 +149,26 @@ struct ConvParams {
     bf16_t *t1;
     int n1;               // conv1's output channels (128 or 256)
     int *fail;            // device word a kernel with bounded spin waits (kernels_ring.hip) sets when a wave gives up, or null
+    // latency schedule (kernels_splitk.hip): set by Network::run for a pass of <= RFD_LATENCY_MAX_BATCH images of a latency context
+    int latency;          // the layers conv_splitk_wants() accepts run as K segments over several workgroups
+    float *sk_ws;         // f32 partial tiles [tile][segment][BM * BN] of this op's stream
+    unsigned *sk_cnt;     // this op's arrival counters [tile]: zero between launches
+    size_t sk_ws_bytes;   // capacities, checked on the host before every launch
+    int sk_cnt_n;
 };
 int launch_conv(const ConvParams &p, hipStream_t s);
+// split-K form of the generic implicit-GEMM tile (kernels_splitk.hip; the latency schedule).  The plan is a pure function of the
+// layer (K, Cout), the pixels of one image and -- for the grid and the workspace only -- the batch.
+constexpr int kSplitKMaxSegments = 8;
+struct SplitKPlan {
+    int S, bm, bn;    // K segments, tile
+    int tiles;        // output tiles = arrival counters
+    size_t ws_bytes;  // tiles * S * bm * bn f32
+};
+int conv_splitk_segments(int nk);
+bool conv_splitk_plan(int K, int Cout, int HoWo, int B, SplitKPlan *pl);
+bool conv_splitk_wants(const ConvParams &p, SplitKPlan *pl); // false: the throughput kernels run the layer
+int launch_conv_splitk(const ConvParams &p, hipStream_t s);
 // wave-specialised loader / consumer ring form of the 128 x 128 implicit-GEMM tile (kernels_ring.hip)
 bool conv_ring_supports(const ConvParams &p, bool *kx3);
 int launch_conv_ring(const ConvParams &p, hipStream_t s);

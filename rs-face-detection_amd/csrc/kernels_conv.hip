@@ -2824,7 +2824,25 @@ int launch_conv(const ConvParams &p, hipStream_t s)
                           !p.res_up2 && !p.res_post && !p.relu && !p.yf && p.ldx == p.Cin && p.x_coff == 0 &&
                           p.y_coff == 0 && p.y_split >= p.Cout && p.n_valid >= p.Cout &&
                           (p.force_tile == 6 || p.force_tile == 16 || (p.force_tile == 0 && M1 >= 128 * 128));
-        if (fuse && (const char *)p.w1 > (const char *)p.w && (size_t)((const char *)p.w1 - (const char *)p.w) < (1u << 30)) {
+        // the pair as its two convolutions, as the small-batch rule above already runs it
+        ConvParams a = p;
+        a.w1 = nullptr; a.bias1 = nullptr; a.t1 = nullptr;
+        ConvParams q;
+        memset(&q, 0, sizeof q);
+        q.x = act_out ? p.y2 : p.y; q.w = p.w1; q.bias = p.bias1; q.zero = p.zero;
+        if (!act_out) { q.in_scale = p.scale2; q.in_shift = p.shift2; }
+        q.y = p.t1;
+        q.B = p.B; q.H = q.Ho = p.Ho; q.W = q.Wo = p.Wo; q.Cin = p.Cout; q.Cout = N1;
+        q.KH = q.KW = 1; q.stride = 1; q.pad = 0;
+        q.ldx = p.Cout; q.ldy = N1; q.y_split = 1 << 30; q.n_valid = 1 << 30; q.relu = 1;
+        q.force_tile = p.force_tile == 16 ? 0 : p.force_tile; q.co_running = p.co_running;
+        if (p.latency) q.fail = p.fail;
+        q.latency = p.latency; q.sk_ws = p.sk_ws; q.sk_cnt = p.sk_cnt; q.sk_ws_bytes = p.sk_ws_bytes; q.sk_cnt_n = p.sk_cnt_n; // one after the other on one stream: shared
+        // latency schedule: a pair one of whose convolutions is split never runs fused, whatever the batch (the fused kernel sums in
+        // the throughput order; a frame's bits must not depend on the size of the latency pass)
+        SplitKPlan skp;
+        const bool split_pair = conv_splitk_wants(a, &skp) || conv_splitk_wants(q, &skp);
+        if (fuse && !split_pair && (const char *)p.w1 > (const char *)p.w && (size_t)((const char *)p.w1 - (const char *)p.w) < (1u << 30)) {
             if (u1) return launch_pw_pair<2, 1, false, 4>(p, s);
             if (s3) {
                 if (p.n1 != 256) { set_error("conv pair: stage-3 form instantiated for n1 = 256, got %d", p.n1); return RFD_ERR_INVALID_ARG; }
@@ -2835,18 +2853,7 @@ int launch_conv(const ConvParams &p, hipStream_t s)
             if (act_out) return launch_pw_pair<1, 1, true, 0, 2>(p, s);
             return launch_pw_b2b<2, false>(p, s); // stage 2's middle units
         }
-        ConvParams a = p;
-        a.w1 = nullptr; a.bias1 = nullptr; a.t1 = nullptr;
         RFD_TRY(launch_conv(a, s));
-        ConvParams q;
-        memset(&q, 0, sizeof q);
-        q.x = act_out ? p.y2 : p.y; q.w = p.w1; q.bias = p.bias1; q.zero = p.zero;
-        if (!act_out) { q.in_scale = p.scale2; q.in_shift = p.shift2; }
-        q.y = p.t1;
-        q.B = p.B; q.H = q.Ho = p.Ho; q.W = q.Wo = p.Wo; q.Cin = p.Cout; q.Cout = N1;
-        q.KH = q.KW = 1; q.stride = 1; q.pad = 0;
-        q.ldx = p.Cout; q.ldy = N1; q.y_split = 1 << 30; q.n_valid = 1 << 30; q.relu = 1;
-        q.force_tile = p.force_tile == 16 ? 0 : p.force_tile; q.co_running = p.co_running;
         return launch_conv(q, s);
     }
     if (p.Cin % 64 != 0 || p.Cin2 % 64 != 0 || p.Cout % 32 != 0) {
@@ -2861,6 +2868,10 @@ int launch_conv(const ConvParams &p, hipStream_t s)
         set_error("conv: an input tensor of %zu bytes exceeds the 4 GiB buffer-addressing limit; lower max_batch_size",
                   (size_t)p.B * p.H * p.W * p.Cin * 2);
         return RFD_ERR_CAPACITY;
+    }
+    {   // latency schedule (rfd_config.schedule; a forced tile wins): the K range as segments over several workgroups
+        SplitKPlan skp;
+        if (conv_splitk_wants(p, &skp)) return launch_conv_splitk(p, s);
     }
     const int M = p.B * p.Ho * p.Wo;
     const int nk = (p.KH * p.KW * p.Cin + p.Cin2) / 64;

@@ -106,7 +106,17 @@ struct Network {
         return (char *)d_buffers32[bi] + (size_t)batch_off * g.buffer_bytes_per_image[bi] * 2;
     }
     int run_f32(int B, hipStream_t s, int first_op, int last_op, int batch_off);
-    int create(int backbone, int net_w, int net_h, int max_batch, int precision = 0);
+    // latency schedule (rfd_config.schedule = RFD_SCHEDULE_LATENCY; kernels_splitk.hip): a pass of <= RFD_LATENCY_MAX_BATCH images runs
+    // the layers conv_splitk_plan() accepts as K segments over several workgroups.  One f32 workspace per stream of a pass (the main
+    // chain and the two side chains run concurrently), one range of arrival counters per op; allocated for latency contexts only
+    // and zeroed once (every launch leaves its counters at zero).
+    int schedule = 0;
+    float *d_sk_ws[3] = {nullptr, nullptr, nullptr};
+    size_t sk_ws_bytes[3] = {0, 0, 0};
+    unsigned *d_sk_cnt = nullptr;
+    std::vector<int> sk_cnt_off, sk_cnt_n; // per op
+    bool latency_pass(int B) const { return schedule == RFD_SCHEDULE_LATENCY && precision == 0 && B >= 1 && B <= RFD_LATENCY_MAX_BATCH; }
+    int create(int backbone, int net_w, int net_h, int max_batch, int precision = 0, int schedule = 0);
     void destroy();
     int init_synthetic(uint64_t seed, hipStream_t s);
     int get_layer(int idx, float *w, float *bias, hipStream_t s);
@@ -161,7 +171,7 @@ struct Network {
     int split_max_parts = 2; // parts = clamp(B / split_min_part, 1, split_max_parts)
     int num_parts(int B) const
     {
-        if (profiling || split_min_part < 1 || precision != 0) return 1;
+        if (profiling || split_min_part < 1 || precision != 0 || latency_pass(B)) return 1;
         return std::max(1, std::min(std::min(split_max_parts, kMaxParts), B / split_min_part));
     }
     int collect_profile(); // after the stream has drained

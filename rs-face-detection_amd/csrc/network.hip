@@ -399,11 +399,44 @@ double Graph::macs_per_image() const
 // ------------------------------------------------------------------------------------------------
 // Network
 // ------------------------------------------------------------------------------------------------
-int Network::create(int backbone, int net_w, int net_h, int max_batch_, int precision_)
+int Network::create(int backbone, int net_w, int net_h, int max_batch_, int precision_, int schedule_)
 {
     RFD_TRY(g.build(backbone, net_w, net_h));
     max_batch = max_batch_;
     precision = precision_;
+    schedule = schedule_;
+    if (schedule == RFD_SCHEDULE_LATENCY) {
+        // the same plan launch_conv_splitk() makes, at the largest latency pass: workspace per stream, counters per op
+        const int Bl = std::min(max_batch, (int)RFD_LATENCY_MAX_BATCH);
+        sk_cnt_off.assign(g.ops.size(), 0);
+        sk_cnt_n.assign(g.ops.size(), 0);
+        int cnt_total = 0;
+        for (size_t i = 0; i < g.ops.size(); ++i) {
+            const Op &o = g.ops[i];
+            if (o.kind != OP_CONV && o.kind != OP_B2B) continue;
+            const Layer &L = g.layers[o.layer];
+            const int tout = o.out >= 0 ? o.out : (o.out2 >= 0 ? o.out2 : o.outf);
+            const int HoWo = g.tensors[tout].H * g.tensors[tout].W;
+            const int cout = L.cout_d + (o.layer_n2 >= 0 ? g.layers[o.layer_n2].cout_d : 0);
+            const int K = L.kh * L.kw * L.cin_d + (o.layer2 >= 0 ? g.layers[o.layer2].cin_d : 0);
+            SplitKPlan pl;
+            const int br = std::min(std::max(o.branch, 0), 2);
+            if (L.cin_d % 64 == 0 && conv_splitk_plan(K, cout, HoWo, Bl, &pl)) {
+                sk_ws_bytes[br] = std::max(sk_ws_bytes[br], pl.ws_bytes);
+                sk_cnt_n[i] = std::max(sk_cnt_n[i], pl.tiles);
+            }
+            if (o.kind == OP_B2B && conv_splitk_plan(cout, g.layers[o.layer_b].cout_d, HoWo, Bl, &pl)) { // the pair's conv1: 1x1 on this op's output
+                sk_ws_bytes[br] = std::max(sk_ws_bytes[br], pl.ws_bytes);
+                sk_cnt_n[i] = std::max(sk_cnt_n[i], pl.tiles);
+            }
+            sk_cnt_off[i] = cnt_total;
+            cnt_total += sk_cnt_n[i];
+        }
+        for (int b = 0; b < 3; ++b)
+            if (sk_ws_bytes[b]) RFD_HIP(hipMalloc((void **)&d_sk_ws[b], sk_ws_bytes[b]));
+        RFD_HIP(hipMalloc((void **)&d_sk_cnt, (size_t)std::max(cnt_total, 1) * sizeof(unsigned)));
+        RFD_HIP(hipMemset(d_sk_cnt, 0, (size_t)std::max(cnt_total, 1) * sizeof(unsigned))); // (the synchronize below orders it)
+    }
     if (precision != 0) {
         for (const Op &o : g.ops)
             if (o.kind == OP_DW || o.kind == OP_FIRST) { set_error("f32 parity mode: this backbone has no f32 kernels (RetinaFace-R50 only)"); return RFD_ERR_INVALID_ARG; }
@@ -453,6 +486,12 @@ void Network::destroy()
     d_zero = nullptr;
     if (d_w32) (void)hipFree(d_w32);
     d_w32 = nullptr;
+    for (int b = 0; b < 3; ++b) {
+        if (d_sk_ws[b]) (void)hipFree(d_sk_ws[b]);
+        d_sk_ws[b] = nullptr; sk_ws_bytes[b] = 0;
+    }
+    if (d_sk_cnt) (void)hipFree(d_sk_cnt);
+    d_sk_cnt = nullptr;
     if (d_stem32) (void)hipFree(d_stem32);
     d_stem32 = nullptr;
     for (void *p : d_buffers32)
@@ -804,6 +843,12 @@ int Network::run(int B, hipStream_t s, int first_op, int last_op, int batch_off,
             p.force_tile = force_tile;
             p.co_running = co_running;
             p.fail = d_fail;
+            if (latency_pass(B) && !co_running && batch_off == 0 && part == 0 && !sk_cnt_n.empty()) {
+                const int br = std::min(std::max(o.branch, 0), 2);
+                p.latency = 1;
+                p.sk_ws = d_sk_ws[br]; p.sk_ws_bytes = sk_ws_bytes[br];
+                p.sk_cnt = d_sk_cnt + sk_cnt_off[i]; p.sk_cnt_n = sk_cnt_n[i];
+            }
             p.res = o.res >= 0 ? (const bf16_t *)tensor_ptr(o.res, batch_off) : nullptr;
             if (o.layer2 >= 0) {
                 const Layer &L2 = g.layers[o.layer2];

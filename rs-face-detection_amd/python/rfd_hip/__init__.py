@@ -16,6 +16,8 @@ RFD_OK = 0
 RFD_ERR_INVALID_ARG = -1
 RFD_ERR_NO_DEVICE = -2
 PRECISION_BF16, PRECISION_F32 = 0, 1
+SCHEDULE_THROUGHPUT, SCHEDULE_LATENCY = 0, 1
+LATENCY_MAX_BATCH = 2   # RFD_LATENCY_MAX_BATCH: the largest pass a latency context runs with the split-K kernels
 RFD_ERR_HIP = -3
 RFD_ERR_CAPACITY = -4
 RFD_ERR_STATE = -5
@@ -40,7 +42,8 @@ class rfd_config(C.Structure):
     _fields_ = [("image_w", C.c_int), ("image_h", C.c_int), ("max_batch_size", C.c_int),
                 ("confidence_threshold", C.c_float), ("iou_threshold", C.c_float),
                 ("device_id", C.c_int), ("max_det", C.c_int), ("max_src_w", C.c_int),
-                ("max_src_h", C.c_int), ("backbone", C.c_int), ("precision", C.c_int), ("reserved", C.c_int * 5)]
+                ("max_src_h", C.c_int), ("backbone", C.c_int), ("precision", C.c_int), ("schedule", C.c_int),
+                ("reserved", C.c_int * 4)]
 
 
 class rfd_image(C.Structure):
@@ -259,7 +262,7 @@ class RetinaFaceDetection:
     """
 
     def __init__(self, image_size=(640, 640), max_batch_size=1, confidence_threshold=0.7,
-                 iou_threshold=0.45, device_id=0, max_det=1024, backbone=BACKBONE_R50, precision=0):
+                 iou_threshold=0.45, device_id=0, max_det=1024, backbone=BACKBONE_R50, precision=0, schedule=0):
         self._L = load_library()
         cfg = rfd_config()
         self._L.rfd_config_default(C.byref(cfg))
@@ -268,6 +271,7 @@ class RetinaFaceDetection:
         cfg.confidence_threshold = float(confidence_threshold)
         cfg.iou_threshold = float(iou_threshold)
         cfg.precision = int(precision)   # 0 = bf16 product path, 1 = PRECISION_F32 parity mode (R50 only)
+        cfg.schedule = int(schedule)     # 0 = throughput, 1 = SCHEDULE_LATENCY: split-K convolutions for passes of <= LATENCY_MAX_BATCH images
         cfg.device_id = int(device_id)
         cfg.max_det = int(max_det)
         cfg.backbone = int(backbone)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Times single network ops (HIP events around the launch, median of --reps runs) under forced conv tile configurations
 (rfd_debug_set_conv_tile) and batch sizes, interleaved in ONE process (A/B rule: never compare across processes).
-usage: python tools/op_bench.py --ops 13,25 --tiles 0,7 --batches 32,16 [--reps 20] [--rounds 3]"""
+usage: python tools/op_bench.py --ops 13,25 --tiles 0,7 --batches 32,16 [--reps 20] [--rounds 3] [--schedule {throughput,latency}]
+(--schedule latency: a latency context; its split-K kernels run at tile 0 in batches <= LATENCY_MAX_BATCH, a forced tile wins)"""
 import argparse
 import os
 import sys
@@ -18,10 +19,12 @@ ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--batches", default="32")
 ap.add_argument("--tiles", default="0")
+ap.add_argument("--schedule", choices=("throughput", "latency"), default="throughput")
 a = ap.parse_args()
 batches = [int(x) for x in a.batches.split(",")]
 tiles = [int(x) for x in a.tiles.split(",")]
-det = rfd_hip.RetinaFaceDetection(max_batch_size=max(batches), max_det=16)
+det = rfd_hip.RetinaFaceDetection(max_batch_size=max(batches), max_det=16,
+                                  schedule=rfd_hip.SCHEDULE_LATENCY if a.schedule == "latency" else rfd_hip.SCHEDULE_THROUGHPUT)
 det.init_synthetic_weights(1234)
 g = rfd_hip.Graph()
 rng = np.random.default_rng(0)
@@ -68,7 +71,7 @@ for rnd in range(a.rounds):
                     ts.append(float(det.op_profile(g.num_ops)[op]) * 1e3)
                 res.setdefault((B, tile, op), []).append(float(np.median(ts)))
 for B in batches:
-    print("batch %d: us per launch (median over %d rounds of medians of %d), tiles %s" % (B, a.rounds, a.reps, tiles))
+    print("batch %d, %s schedule: us per launch (median over %d rounds of medians of %d), tiles %s" % (B, a.schedule, a.rounds, a.reps, tiles))
     tot = {t: 0.0 for t in tiles}
     for op in ops:
         o = g.ops[op]
@@ -78,5 +81,6 @@ for B in batches:
             tot[t] += v
         fl = 2.0 * o.macs * B
         print("%3d %-22s k%d %4d->%4d  " % (op, L.name.decode(), L.kh, L.cin, L.cout) +
-              "  ".join(("%7.1f us %6.0f TF" % (v, fl / v / 1e6)) if v > 0 else "    (fused into the stem)" for v in row))
+              "  ".join(("%7.1f us %6.0f TF" % (v, fl / v / 1e6)) if v > 0 else "    (fused into the stem)" for v in row) +
+              "  " + " + ".join(det.debug_op_kernels(B, op, co_running=False)))
     print("    totals", {t: round(v, 1) for t, v in tot.items()})
