@@ -357,6 +357,16 @@ RFD_API int rfd_get_op_profile(rfd_ctx *ctx, float *ms, int cap);
  *      op list [first_op, last_op] (last_op < 0: to the end), so every op can be checked in isolation. */
 RFD_API int rfd_debug_tensor_io(rfd_ctx *ctx, int tensor_id, int n, void *host, int write);
 RFD_API int rfd_debug_run_ops(rfd_ctx *ctx, int n, int first_op, int last_op);
+/* rfd_debug_run_ops as a chain of a split pass runs the range: on images [batch_off, batch_off + n) of the workspace
+ * (batch_off + n <= max_batch_size), with the kernel choice of a chain that runs beside another one when co_running != 0. */
+RFD_API int rfd_debug_run_chain(rfd_ctx *ctx, int n, int first_op, int last_op, int batch_off, int co_running);
+/* the chains a pass of n images runs as: returns their number (1: the pass is not split) and fills sizes[0 .. that number);
+ * chain p holds the images from the sum of the sizes before it.  The rule the pass itself uses; launches nothing. */
+RFD_API int rfd_debug_pass_chains(rfd_ctx *ctx, int n, int *sizes, int cap);
+/* raw access to the WHOLE workspace buffer that holds a tensor: max_batch_size * *image_pitch bytes.  The images of a chain at
+ * batch_off start at byte batch_off * *image_pitch and follow each other at the tensor's own C*H*W size (tensors that share a
+ * buffer differ in size, so the pitch belongs to the buffer).  host == NULL only reports the pitch. */
+RFD_API int rfd_debug_buffer_io(rfd_ctx *ctx, int tensor_id, void *host, size_t bytes, int write, size_t *image_pitch);
 /* force the conv tile configuration: 0 = heuristic, 1 = 128-row four-wave tiles, 2 = 256x128 tiles where legal, 16 = the
  * weight-resident pair kernel for stage 1's pairs, 17 = the wave-specialised ring form wherever the layer shape allows, 18 = the
  * eight-wave 128x128 generic tile, 19 = the four-wave merged-kx 3x3 kernel (the full list: launch_conv in csrc/kernels_conv.hip) */

@@ -500,11 +500,13 @@ int detect_overlapped(rfd_ctx *c, const rfd_image *imgs, int n, rfd_dets *out, h
     RFD_HIP(hipStreamWaitEvent(st[1], c->ov_desc, 0));
     net.head_parity = par;
     net.co_running = 1;
-    const int B0 = (n + 1) / 2;
+    int chain[Network::kMaxParts];
+    if (net.pass_chains(n, chain) != 2) { set_error("overlapped calls run as two chains"); return RFD_ERR_STATE; }
+    const int B0 = chain[0];
     const size_t in_px = (size_t)c->cfg.image_h * c->cfg.image_w * 4;
     int status = RFD_OK;
     for (int p = 0; p < 2 && status == RFD_OK; ++p) {
-        const int off = p ? B0 : 0, Bp = p ? n - B0 : B0;
+        const int off = p ? B0 : 0, Bp = chain[p];
         PreParams pp;
         memset(&pp, 0, sizeof pp);
         pp.imgs = (const PreImage *)c->ov_imgs[par].p + off;
@@ -909,6 +911,52 @@ int rfd_debug_run_ops(rfd_ctx *c, int n, int first_op, int last_op)
     RFD_HIP(hipStreamSynchronize(c->stream));
     if (c->net.profiling) RFD_TRY(c->net.collect_profile());
     return check_nms_flag(c);
+}
+
+int rfd_debug_run_chain(rfd_ctx *c, int n, int first_op, int last_op, int batch_off, int co_running)
+{
+    RFD_CHECK_ARG(c, "ctx is null");
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    RFD_TRY(c->ensure_network());
+    RFD_CHECK_ARG(n >= 1 && batch_off >= 0 && batch_off + n <= c->cfg.max_batch_size, "chain [batch_off, batch_off + n) out of range");
+    c->ov_last_n = -1;
+    const int saved = c->net.co_running;
+    c->net.co_running = co_running != 0;
+    const int st = c->net.run(n, c->stream, first_op, last_op, batch_off, 0);
+    c->net.co_running = saved;
+    RFD_TRY(st);
+    RFD_HIP(hipMemcpyAsync(c->h_nms_flag, c->net.d_fail, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    if (c->net.profiling) RFD_TRY(c->net.collect_profile());
+    return check_nms_flag(c);
+}
+int rfd_debug_pass_chains(rfd_ctx *c, int n, int *sizes, int cap)
+{
+    RFD_CHECK_ARG(c && sizes, "null argument");
+    RFD_TRY(c->ensure_network());
+    RFD_CHECK_ARG(n >= 1 && n <= c->cfg.max_batch_size, "batch out of range");
+    int chain[Network::kMaxParts];
+    const int P = c->net.pass_chains(n, chain);
+    RFD_CHECK_ARG(cap >= P, "sizes holds fewer entries than the pass has chains");
+    for (int p = 0; p < P; ++p) sizes[p] = chain[p];
+    return P;
+}
+int rfd_debug_buffer_io(rfd_ctx *c, int tensor_id, void *host, size_t bytes, int write, size_t *image_pitch)
+{
+    RFD_CHECK_ARG(c, "ctx is null");
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    RFD_TRY(c->ensure_network());
+    RFD_CHECK_ARG(tensor_id >= 0 && tensor_id < (int)c->net.g.tensors.size(), "tensor id out of range");
+    if (c->net.precision != 0) { set_error("f32 parity mode keeps its own workspace"); return RFD_ERR_STATE; }
+    const size_t pitch = c->net.g.buffer_bytes_per_image[c->net.g.tensors[tensor_id].buffer];
+    if (image_pitch) *image_pitch = pitch;
+    if (!host) return RFD_OK;
+    RFD_CHECK_ARG(bytes == pitch * (size_t)c->cfg.max_batch_size, "bytes is not the size of the buffer (max_batch_size * image pitch)");
+    c->ov_last_n = -1;
+    if (write) RFD_HIP(hipMemcpyAsync(c->net.tensor_ptr(tensor_id), host, bytes, hipMemcpyHostToDevice, c->stream));
+    else RFD_HIP(hipMemcpyAsync(host, c->net.tensor_ptr(tensor_id), bytes, hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    return RFD_OK;
 }
 
 int rfd_debug_op_kernels(rfd_ctx *c, int n, int op, int co_running, char *names, int cap)

@@ -139,7 +139,7 @@ struct Network {
     int ensure_alt_heads();
     int run(int B, hipStream_t s, int first_op = 0, int last_op = -1, int batch_off = 0, int part = 0);
     int run_split(int B, hipStream_t s); // whole pass; splits the batch over several streams when it pays
-    int split_body(int B, int P, hipStream_t s);
+    int split_body(int B, hipStream_t s);
     int tune_streams(int B, int P, hipStream_t s);
     void assign_streams(int a, int b, int c);
     static constexpr int kPool = 8;
@@ -173,6 +173,14 @@ struct Network {
     {
         if (profiling || split_min_part < 1 || precision != 0 || latency_pass(B)) return 1;
         return std::max(1, std::min(std::min(split_max_parts, kMaxParts), B / split_min_part));
+    }
+    // the chains of a pass of B images: their number, and into sizes[0 .. kMaxParts) the images of each (chain p starts at the sum of
+    // the sizes before it).  The ONE statement of the split rule: split_body() enqueues exactly these, the test hook reports them.
+    int pass_chains(int B, int *sizes) const
+    {
+        const int P = num_parts(B);
+        for (int p = 0; p < P; ++p) sizes[p] = B / P + (p < B % P ? 1 : 0);
+        return P;
     }
     int collect_profile(); // after the stream has drained
 };

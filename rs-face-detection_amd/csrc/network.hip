@@ -1017,13 +1017,15 @@ void Network::assign_streams(int a, int b, int c)
 // joined range also picks kernels by its own batch size, which for two layers means another f32 summation order, i.e. heads
 // that differ in the last bf16 bit from the split pass (tests/test_concurrency_gpu.py fails with it).  Removed.
 
-int Network::split_body(int B, int P, hipStream_t s)
+int Network::split_body(int B, hipStream_t s)
 {
+    int sizes[kMaxParts];
+    const int P = pass_chains(B, sizes);
     RFD_HIP(hipEventRecord(ev_part_fork, s));
     co_running = 1;
     int off = 0, st = RFD_OK;
     for (int p = 0; p < P && st == RFD_OK; ++p) {
-        const int Bp = B / P + (p < B % P ? 1 : 0);
+        const int Bp = sizes[p];
         RFD_HIP(hipStreamWaitEvent(part_stream[p], ev_part_fork, 0));
         st = run(Bp, part_stream[p], 0, -1, off, p);
         if (st == RFD_OK) RFD_HIP(hipEventRecord(ev_part_join[p], part_stream[p]));
@@ -1051,7 +1053,7 @@ int Network::tune_streams(int B, int P, hipStream_t s)
         std::vector<float> ts;
         for (int rep = 0; rep <= reps && st == RFD_OK; ++rep) {
             if (hipEventRecord(e0, s) != hipSuccess) st = RFD_ERR_HIP;
-            if (st == RFD_OK) st = split_body(B, P, s);
+            if (st == RFD_OK) st = split_body(B, s);
             if (st == RFD_OK && (hipEventRecord(e1, s) != hipSuccess || hipEventSynchronize(e1) != hipSuccess)) st = RFD_ERR_HIP;
             float ms = 0.f;
             if (st == RFD_OK && hipEventElapsedTime(&ms, e0, e1) == hipSuccess && rep > 0) ts.push_back(ms);
@@ -1104,10 +1106,10 @@ int Network::run_split(int B, hipStream_t s)
     if (P <= 1) return run(B, s);
     if (!tuned && tune && (P == 2 || P == 3)) {
         tuned = true;
-        if (getenv("RFD_STREAM_TUNE") && atoi(getenv("RFD_STREAM_TUNE")) == 0) return split_body(B, P, s);
+        if (getenv("RFD_STREAM_TUNE") && atoi(getenv("RFD_STREAM_TUNE")) == 0) return split_body(B, s);
         RFD_TRY(tune_streams(B, P, s));
     }
-    return split_body(B, P, s);
+    return split_body(B, s);
 }
 
 int Network::run_graphed(int B, hipStream_t s)

@@ -102,7 +102,8 @@ API_SYMBOLS = [
     "rfd_set_layer_weights", "rfd_get_layer_affine", "rfd_set_layer_affine", "rfd_detect_batch",
     "rfd_detect_batch_device", "rfd_sync", "rfd_set_stream", "rfd_preprocess", "rfd_forward", "rfd_decode_nms",
     "rfd_nms_sorted", "_nms", "rfd_get_stats", "rfd_get_config", "rfd_set_thresholds", "rfd_set_profiling",
-    "rfd_get_conv_profile", "rfd_get_op_profile", "rfd_debug_tensor_io", "rfd_debug_run_ops", "rfd_debug_set_conv_tile", "rfd_debug_op_kernels", "rfd_debug_set_concurrency", "rfd_debug_persistent_kernel", "rfd_debug_poke_nms_flag", "rfd_selection_config_default",
+    "rfd_get_conv_profile", "rfd_get_op_profile", "rfd_debug_tensor_io", "rfd_debug_run_ops", "rfd_debug_run_chain", "rfd_debug_pass_chains", "rfd_debug_buffer_io",
+    "rfd_debug_set_conv_tile", "rfd_debug_op_kernels", "rfd_debug_set_concurrency", "rfd_debug_persistent_kernel", "rfd_debug_poke_nms_flag", "rfd_selection_config_default",
     "rfd_select_faces", "rfd_detect_select_batch", "rfd_save_weights", "rfd_load_weights",
     "rfd_alignment_config_default", "rfd_align_faces", "rfd_detect_select_align_batch",
     "rfd_host_alloc", "rfd_host_free", "rfd_submit_batch", "rfd_collect_batch",
@@ -164,6 +165,9 @@ def load_library(path=None):
     L.rfd_get_op_profile.argtypes = [vp, vp, ci]
     L.rfd_debug_tensor_io.argtypes = [vp, ci, ci, vp, ci]
     L.rfd_debug_run_ops.argtypes = [vp, ci, ci, ci]
+    L.rfd_debug_run_chain.argtypes = [vp, ci, ci, ci, ci, ci]
+    L.rfd_debug_pass_chains.argtypes = [vp, ci, C.POINTER(ci), ci]
+    L.rfd_debug_buffer_io.argtypes = [vp, ci, vp, C.c_size_t, ci, C.POINTER(C.c_size_t)]
     L.rfd_debug_set_conv_tile.argtypes = [vp, ci]
     L.rfd_debug_set_concurrency.argtypes = [vp, ci, ci, ci, ci]
     L.rfd_debug_op_kernels.argtypes = [vp, ci, ci, ci, C.c_char_p, ci]
@@ -598,8 +602,33 @@ class RetinaFaceDetection:
         _check(self._L.rfd_debug_set_concurrency(self._ctx, int(multi_stream), int(split_min_part), int(split_max_parts),
                                                  int(use_graph)))
 
-    def debug_run(self, n, first_op, last_op):
-        _check(self._L.rfd_debug_run_ops(self._ctx, n, first_op, last_op))
+    def debug_run(self, n, first_op, last_op, batch_off=0, co_running=False):
+        """ops [first_op, last_op] on images [batch_off, batch_off + n); co_running: with the kernel choice of a chain of a split pass"""
+        if batch_off == 0 and not co_running:
+            _check(self._L.rfd_debug_run_ops(self._ctx, n, first_op, last_op))
+        else:
+            _check(self._L.rfd_debug_run_chain(self._ctx, n, first_op, last_op, batch_off, 1 if co_running else 0))
+
+    def debug_pass_chains(self, n):
+        """sizes of the chains a pass of n images runs as (one entry: the pass is not split); nothing is launched"""
+        sizes = (C.c_int * 8)()
+        return list(sizes[:_check(self._L.rfd_debug_pass_chains(self._ctx, n, sizes, 8))])
+
+    def debug_buffer_pitch(self, tensor_id):
+        """bytes between the first images of two chains in the workspace buffer that holds the tensor"""
+        pitch = C.c_size_t()
+        _check(self._L.rfd_debug_buffer_io(self._ctx, tensor_id, None, 0, 0, C.byref(pitch)))
+        return pitch.value
+
+    def debug_buffer_read(self, tensor_id):
+        """the whole workspace buffer that holds the tensor: max_batch_size * pitch bytes"""
+        a = np.zeros(self.cfg.max_batch_size * self.debug_buffer_pitch(tensor_id), np.uint8)
+        _check(self._L.rfd_debug_buffer_io(self._ctx, tensor_id, a.ctypes.data, a.nbytes, 0, None))
+        return a
+
+    def debug_buffer_write(self, tensor_id, arr):
+        a = np.ascontiguousarray(arr).reshape(-1).view(np.uint8)
+        _check(self._L.rfd_debug_buffer_io(self._ctx, tensor_id, a.ctypes.data, a.nbytes, 1, None))
 
     # ---- introspection ----
     def stats(self):

@@ -54,6 +54,12 @@ class Out:
         self.lo, self.hi, self.v, self.rad, self.is_f32, self.dst, self.softmax = lo, hi, v, rad, is_f32, dst, softmax
 
 
+def _cat(outs):
+    """the Outs of consecutive image chunks of one tensor, as one Out"""
+    a = outs[0]
+    return Out(*(torch.cat([getattr(o, k) for o in outs]) for k in ("lo", "hi", "v", "rad")), is_f32=a.is_f32, dst=a.dst, softmax=a.softmax)
+
+
 class ExactRef:
     def __init__(self, graph, det):
         self.g = graph
@@ -119,9 +125,18 @@ class ExactRef:
         return rne_bf16(v), hi - lo
 
     # ---- ops ----
-    def run_op(self, i, tens):
+    def run_op(self, i, tens, chunk=0):
         """tens: dict tensor id -> NCHW f64 tensor (bf16 values; logical channels).  Returns {tensor id: Out} for every
-        output of op i except out_b of a back-to-back op (b2b_second: it reads the device's own stored first output)."""
+        output of op i except out_b of a back-to-back op (b2b_second: it reads the device's own stored first output).
+        chunk > 0: evaluated `chunk` images at a time (every op treats the images of a batch independently) and concatenated,
+        so the f64 intermediates of a 16-image chain on the 160 x 160 maps never exist all at once."""
+        n = next(iter(tens.values())).shape[0]
+        if chunk <= 0 or chunk >= n:
+            return self._run_op(i, tens)
+        parts = [self._run_op(i, {t: x[k:k + chunk] for t, x in tens.items()}) for k in range(0, n, chunk)]
+        return {t: _cat([p[t] for p in parts]) for t in parts[0]}
+
+    def _run_op(self, i, tens):
         g = self.g
         o = g.ops[i]
         L = g.layers[o.layer]
@@ -200,9 +215,14 @@ class ExactRef:
             res[o.outf] = Out(lo, hi, v, torch.maximum(v - lo, hi - v), is_f32=True, softmax=bool(o.head_softmax))
         return res
 
-    def b2b_second(self, i, first):
+    def b2b_second(self, i, first, chunk=0):
         """out_b of back-to-back op i: relu(conv1x1(a) + bias), a = bf16(relu(affine(raw))) of the device's stored raw output
-        (or its stored activated output when the op has no raw one).  first: NCHW f64 of that stored tensor."""
+        (or its stored activated output when the op has no raw one).  first: NCHW f64 of that stored tensor.  chunk: as run_op."""
+        if chunk <= 0 or chunk >= first.shape[0]:
+            return self._b2b_second(i, first)
+        return _cat([self._b2b_second(i, first[k:k + chunk]) for k in range(0, first.shape[0], chunk)])
+
+    def _b2b_second(self, i, first):
         o = self.g.ops[i]
         if o.out >= 0:
             a, dx = self._operand(first, *self.aff[o.layer])

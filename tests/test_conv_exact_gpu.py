@@ -134,8 +134,19 @@ def _first_bad(bad):
 
 
 class Sweep:
-    def __init__(self, det, g, geo, n):
+    """batch_off / co_running: the cases run as a chain of a split pass does (tests/test_production_plan_gpu.py), on images
+    [batch_off, batch_off + n) of a workspace of max_batch images, with the kernel choice of a co-running chain.  Every tensor
+    then goes to the device as its WHOLE workspace buffer, NaN outside the chain's images, and every byte outside them must come
+    back unchanged.  chunk: images per evaluation of the f64 reference (0: all at once)."""
+
+    def __init__(self, det, g, geo, n, batch_off=0, co_running=False, max_batch=None, chunk=0):
         self.det, self.g, self.geo, self.n = det, g, geo, n
+        self.batch_off, self.co_running, self.chunk = batch_off, co_running, chunk
+        self.chain = max_batch is not None
+        assert self.chain or (batch_off == 0 and not co_running)
+        assert not self.chain or batch_off + n <= max_batch
+        self.pairs = set()
+        self._sent, self._poison = {}, {}
         self.fail = []
         self.cases = 0
         self.names = set()
@@ -157,7 +168,7 @@ class Sweep:
             o = g.ops[i]
             tens = _inputs(rng, g, o, n, dyadic)
             with torch.no_grad():
-                want = ref.run_op(i, tens)
+                want = ref.run_op(i, tens, self.chunk)
             if dyadic:
                 for t, w in want.items():
                     if not w.is_f32:
@@ -174,14 +185,19 @@ class Sweep:
             for (_, names, tile, last) in ocases:
                 self.cases += 1
                 self.names.update(names)
+                self.pairs.add((i, tuple(names)))
                 self._run_case(ref, i, tens, want, names, tile, last, tag)
 
     def _run_case(self, ref, i, tens, want, names, tile, last, tag):
         det, g, n = self.det, self.g, self.n
         o = g.ops[i]
         det.debug_set_conv_tile(tile)
+        what = "op %d (%s, kind %d) kernel %s (tile %d) at %s n = %d%s, %s set" % (
+            i, g.layers[o.layer].name.decode(), o.kind, " + ".join(names), tile, self.geo, n,
+            " at image %d%s" % (self.batch_off, ", co-running" if self.co_running else "") if self.chain else "", tag)
+        self._sent.clear()
         for t, x in tens.items():
-            det.debug_write(t, _dev(x, g.tensors[t]))
+            self._write(t, _dev(x, g.tensors[t]))
         outs = [(t, i) for t in (o.out, o.out2, o.outf, o.out_b) if t >= 0]
         if last > i:
             outs.append((g.ops[last].out, last))
@@ -197,15 +213,18 @@ class Sweep:
                 assert not set(written) & set(range(o.x_coff, o.x_coff + g.layers[o.layer].cin)), "in-place op overwrites its input"
             pa = a.view(np.uint32) if td.is_f32 else a
             pa[..., written] = NAN_F32 if td.is_f32 else NAN_BF16
-            det.debug_write(t, a)
+            self._write(t, a)
             prior[t] = (a.copy(), written)
-        det.debug_run(n, i, last)
+        det.debug_run(n, i, last, self.batch_off, self.co_running)
         det.debug_set_conv_tile(0)
-        what = "op %d (%s, kind %d) kernel %s (tile %d) at %s n = %d, %s set" % (
-            i, g.layers[o.layer].name.decode(), o.kind, " + ".join(names), tile, self.geo, n, tag)
+        for t in tens if self.chain else ():
+            if t not in prior:   # an operand the op only reads
+                a = _dev(tens[t], g.tensors[t])
+                if not np.array_equal(self._read(t, what).view(np.uint8), a.view(np.uint8)):
+                    self.fail.append("%s tensor %d: the op changed an operand it only reads" % (what, t))
         for t, oi in outs:
             td = g.tensors[t]
-            got = det.debug_read(t, n, td)
+            got = self._read(t, what)
             a, written = prior[t]
             keep = np.setdiff1d(np.arange(td.channels), written)
             if not np.array_equal(np.ascontiguousarray(got[..., keep]).view(np.uint8), np.ascontiguousarray(a[..., keep]).view(np.uint8)):
@@ -216,12 +235,15 @@ class Sweep:
             else:   # read from the device's own stored first output: out_b of a b2b op, or the conv fused into the stem kernel
                 src = o.out if (oi == i and o.out >= 0) else (o.out2 if oi == i else g.ops[oi].in_)
                 st = g.tensors[src]
-                raw = det.debug_read(src, n, st)
+                raw = self._read(src, what)
+                first = _to_f64(raw[..., :st.channels_logical], False)
+                if bool(torch.isnan(first).any()):   # reported with tensor src itself; the reference cannot start from NaN
+                    self.fail.append("%s tensor %d: not checked, the stored tensor %d it is computed from holds NaN" % (what, t, src))
+                    continue
                 key = (t, raw.tobytes())
                 if key not in self._cache:
-                    first = _to_f64(raw[..., :st.channels_logical], False)
                     with torch.no_grad():
-                        self._cache[key] = ref.b2b_second(i, first) if oi == i else ref.run_op(oi, {src: first})[t]
+                        self._cache[key] = ref.b2b_second(i, first, self.chunk) if oi == i else ref.run_op(oi, {src: first}, self.chunk)[t]
                 w = self._cache[key]
             if td.is_f32:
                 bad, ratio = exact_ref.check_f32(g64, w)
@@ -235,6 +257,43 @@ class Sweep:
                 self.fail.append("%s tensor %d: %d / %d elements wrong, first at (n, c, y, x) %s: got %r, legal [%r, %r], v64 %r "
                                  "(%.3g r from v64)" % (what, t, int(bad.sum()), bad.numel(), p, float(g64[b0]), float(w.lo[b0]),
                                                         float(w.hi[b0]), float(w.v[b0]), float(ex)))
+
+    def _write(self, t, a):
+        """the n images of tensor t; in chain mode inside its whole buffer, NaN bits everywhere else"""
+        if not self.chain:
+            self.det.debug_write(t, a)
+            return
+        td = self.g.tensors[t]
+        pitch = self.det.debug_buffer_pitch(t)
+        assert pitch % 4 == 0 and a.nbytes <= self.n * pitch
+        nan, u = (NAN_F32, np.uint32) if td.is_f32 else (NAN_BF16, np.uint16)
+        key = (self.det.cfg.max_batch_size * pitch, u)
+        if key not in self._poison:
+            self._poison[key] = np.full(key[0] // np.dtype(u).itemsize, nan, u)
+        buf = self._poison[key].view(np.uint8)
+        lo = self.batch_off * pitch
+        a = np.ascontiguousarray(a)
+        buf[lo:lo + a.nbytes] = a.reshape(-1).view(np.uint8)
+        self.det.debug_buffer_write(t, buf)
+        buf[lo:lo + a.nbytes].view(u)[:] = nan
+        self._sent[t] = (lo, a.shape, a.dtype)
+
+    def _read(self, t, what):
+        """the n images of tensor t; in chain mode every byte of its buffer outside them must still hold the NaN bits"""
+        td = self.g.tensors[t]
+        if not self.chain:
+            return self.det.debug_read(t, self.n, td)
+        buf = self.det.debug_buffer_read(t)
+        lo, shape, dt = self._sent[t]
+        hi = lo + int(np.prod(shape)) * np.dtype(dt).itemsize
+        nan, u = (NAN_F32, np.uint32) if td.is_f32 else (NAN_BF16, np.uint16)
+        for name, part in (("before", buf[:lo]), ("behind", buf[hi:])):
+            ok = part.view(u) == nan
+            if not bool(ok.all()):
+                first = int(np.argmin(ok)) * np.dtype(u).itemsize + (0 if name == "before" else hi)
+                self.fail.append("%s tensor %d: %d elements %s the chain's images changed, first at byte %d of the buffer (image pitch %d; "
+                                 "the chain holds bytes [%d, %d))" % (what, t, int((~ok).sum()), name, first, len(buf) // self.det.cfg.max_batch_size, lo, hi))
+        return buf[lo:hi].view(dt).reshape(shape).copy()
 
 
 @pytest.mark.parametrize("geom", GEOMETRIES, ids=["%s-%dx%d-n%d%s" % (b, w, h, n, "-" + o if o else "") for b, w, h, n, o in GEOMETRIES])
@@ -306,21 +365,26 @@ BATCH_RUNS = {"r50": [(640, 640), (768, 480)], "mnet025": [(640, 640)]}
 def test_heads_do_not_depend_on_the_batch_size(rfd, bb, w, h):
     """one K order per layer whatever kernel runs it, so a frame's 9 head tensors are bit-identical whether it
     runs alone (B = 1), in small split batches, or inside a 32-frame batch (two 16-image chains, persistent kernels, stem+conv1
-    fusion)."""
+    fusion).  Every position of the passes of 32 (chains of 16 + 16), 17 (9 + 8) and 8 (4 + 4) images is compared with the B = 1
+    run of its frame: the positions in the middle of a chain and on both sides of the cut between the chains included."""
     det = rfd.RetinaFaceDetection(image_size=(w, h), max_batch_size=32, max_det=16, backbone=_bb(rfd, bb))
     try:
         det.init_synthetic_weights(1234)
         rng = np.random.default_rng(21)
         frames = rng.uniform(-1.0, 1.0, size=(32, 3, h, w)).astype(np.float32)
-        alone = [det.forward(frames[k:k + 1]) for k in range(6)]
+        big = frames.copy()
+        big[26:32] = frames[0:6]
+        alone_big = [det.forward(big[k:k + 1]) for k in range(32)]   # positions 26..31 repeat frames 0..5: runs of their own
+        alone = alone_big[:6]
+        for j in range(6):
+            for lvl, (a, b) in enumerate(zip(alone_big[26 + j], alone[j])):
+                assert np.array_equal(a, b), "%s %dx%d frame %d: two B = 1 runs differ in head tensor %d" % (bb, w, h, j, lvl)
         runs = []
         for bs in (2, 3, 8):
             for s0 in range(0, 6, bs):
                 batch = frames[[(s0 + j) % 32 if s0 + j < 6 else 6 + j for j in range(bs)]]
                 heads = det.forward(batch)
                 runs += [("B=%d" % bs, s0 + j, [x[j:j + 1] for x in heads]) for j in range(bs) if s0 + j < 6]
-        big = frames.copy()
-        big[26:32] = frames[0:6]
         heads = det.forward(big)
         runs += [("B=32 pos %d" % j, j, [x[j:j + 1] for x in heads]) for j in range(6)]
         runs += [("B=32 pos %d" % (26 + j), j, [x[26 + j:27 + j] for x in heads]) for j in range(6)]
@@ -328,5 +392,11 @@ def test_heads_do_not_depend_on_the_batch_size(rfd, bb, w, h):
             for lvl, (a, b) in enumerate(zip(hs, alone[k])):
                 assert np.array_equal(a, b), "%s %dx%d frame %d, %s: head tensor %d differs from the B = 1 run (%d elements)" % (
                     bb, w, h, k, tag, lvl, int((a != b).sum()))
+        for B, hs in ((32, heads), (17, det.forward(big[:17])), (8, det.forward(big[:8]))):
+            assert len(det.debug_pass_chains(B)) == 2, "a pass of %d images is expected to run as two chains" % B
+            for j in range(B):
+                for lvl, (a, b) in enumerate(zip(hs, alone_big[j])):
+                    assert np.array_equal(a[j:j + 1], b), "%s %dx%d B=%d (chains %s) position %d: head tensor %d differs from the B = 1 " \
+                        "run of that frame (%d elements)" % (bb, w, h, B, det.debug_pass_chains(B), j, lvl, int((a[j:j + 1] != b).sum()))
     finally:
         det.close()

@@ -175,3 +175,32 @@ def test_dyadic_set_is_exact_in_f32(graph):
                 ties[0] += d
                 ties[1] += u
     assert min(ties) >= 100, ties
+
+
+@pytest.mark.parametrize("dyadic", [False, True])
+def test_chunked_reference_equals_the_unchunked_one(graph, dyadic):
+    """run_op / b2b_second evaluated 2 images (then 1 image: a ragged last chunk) at a time return, bit for bit, what one
+    evaluation of all 5 images returns: every field of every output, on both input sets."""
+    g = graph
+    rng = np.random.default_rng(5)
+    ref = exact_ref.ExactRef(g, _Weights(g, rng, dyadic))
+    ref.radius, ref.exact = not dyadic, dyadic
+    n = 5
+    compared = 0
+    for i, o in enumerate(g.ops):
+        tens = {t: x.double() for t, x in _inputs(rng, g, o, n, dyadic).items()}
+        whole = ref.run_op(i, tens)
+        pairs = [(whole, ref.run_op(i, tens, chunk=2)), (whole, ref.run_op(i, tens, chunk=n)), (whole, ref.run_op(i, tens, chunk=64))]
+        if o.out_b >= 0:
+            first = exact_ref.rne_bf16(whole[o.out if o.out >= 0 else o.out2].v)   # what a device would have stored
+            pairs.append(({0: ref.b2b_second(i, first)}, {0: ref.b2b_second(i, first, chunk=2)}))
+        for a, b in pairs:
+            assert a.keys() == b.keys()
+            for t in a:
+                assert (a[t].is_f32, a[t].softmax) == (b[t].is_f32, b[t].softmax)
+                assert (a[t].dst is None) == (b[t].dst is None) and (a[t].dst is None or np.array_equal(a[t].dst, b[t].dst))
+                for k in ("lo", "hi", "v", "rad"):
+                    x, y = getattr(a[t], k), getattr(b[t], k)
+                    assert x.shape == y.shape and x.shape[0] == n and torch.equal(x, y), "op %d tensor %d field %s" % (i, t, k)
+                    compared += 1
+    assert compared >= 4 * len(g.ops)
