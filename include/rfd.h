@@ -369,12 +369,19 @@ RFD_API int rfd_debug_pass_chains(rfd_ctx *ctx, int n, int *sizes, int cap);
 RFD_API int rfd_debug_buffer_io(rfd_ctx *ctx, int tensor_id, void *host, size_t bytes, int write, size_t *image_pitch);
 /* force the conv tile configuration: 0 = heuristic, 1 = 128-row four-wave tiles, 2 = 256x128 tiles where legal, 16 = the
  * weight-resident pair kernel for stage 1's pairs, 17 = the wave-specialised ring form wherever the layer shape allows, 18 = the
- * eight-wave 128x128 generic tile, 19 = the four-wave merged-kx 3x3 kernel (the full list: launch_conv in csrc/kernels_conv.hip) */
+ * eight-wave 128x128 generic tile, 19 = the four-wave merged-kx 3x3 kernel (all twenty, by name: enum ConvTile in csrc/kernels.h;
+ * rfd_hip exports the same names) */
 RFD_API int rfd_debug_set_conv_tile(rfd_ctx *ctx, int tile);
 /* which kernel(s) op `op` of the network would be run by at `n` images per chain (co_running != 0: as one of the two chains of a
  * split pass) -- the names rocprofv3 reports without the rfd:: prefix, " + "-separated when an op takes two launches.  Nothing is
  * launched.  tools/traffic_model.py and tools/roof_gap.py attribute bytes and time to kernels through this call. */
 RFD_API int rfd_debug_op_kernels(rfd_ctx *ctx, int n, int op, int co_running, char *names, int cap);
+/* The same answer without a context or a GPU: the chooser (csrc/conv_select.hip) asked with the parameters a context of this
+ * backbone and image size would build for op `op` of a chain of n images -- weight offsets from the layer table, split-K
+ * capacities from the graph -- under forced tile `tile` (0 in production), schedule RFD_SCHEDULE_*, on a GPU of `cus` compute
+ * units.  tests/test_kernel_choice_cpu.py replays the pinned choice table tests/golden/kernel_choice.json through it. */
+RFD_API int rfd_debug_op_kernels_static(int backbone, int net_w, int net_h, int n, int op, int co_running, int tile, int schedule,
+                                        int cus, char *names, int cap);
 /* execution structure of the network pass: side streams for independent chains on/off; batch split into
  * clamp(n / split_min_part, 1, split_max_parts) contiguous parts that run as independent chains on their own streams
  * (split_max_parts <= 1 = never; at most 4); hipGraph replay of unsplit passes on/off.  Every structure gives

@@ -14,24 +14,6 @@
 namespace rfd {
 
 static thread_local char g_err[512] = "";
-LaunchNote &launch_note()
-{
-    static thread_local LaunchNote n;
-    return n;
-}
-bool note_launch(const char *fmt, ...)
-{
-    LaunchNote &n = launch_note();
-    if (!n.dry) return false;
-    char buf[160];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (!n.names.empty()) n.names += " + ";
-    n.names += buf;
-    return true;
-}
 
 void set_error(const char *fmt, ...)
 {
@@ -966,29 +948,39 @@ int rfd_debug_op_kernels(rfd_ctx *c, int n, int op, int co_running, char *names,
     RFD_TRY(c->ensure_network());
     RFD_CHECK_ARG(n >= 1 && n <= c->cfg.max_batch_size && op >= 0 && op < (int)c->net.g.ops.size(), "batch or op out of range");
     if (c->net.precision != 0) { set_error("kernel-choice introspection covers the bf16 path"); return RFD_ERR_STATE; }
-    LaunchNote &note = launch_note();
-    note.names.clear();
-    note.dry = true;                       // every launch path records its kernel and returns without launching
+    if (!c->net.weights_ready) { set_error("network weights are not initialised (rfd_init_synthetic_weights / rfd_set_layer_weights)"); return RFD_ERR_STATE; }
     const int saved = c->net.co_running;
-    const bool prof = c->net.profiling;
     c->net.co_running = co_running != 0;   // as for a chain of a split pass (batches >= 16 run as two chains of n / 2 images)
-    c->net.profiling = false;
-    // the stem and the conv behind it may run as ONE launch when a pass runs them back to back (Network::run's peephole): ask for the
-    // pair, and report the conv as fused when the pair took a single launch
-    const auto &ops = c->net.g.ops;
-    const bool is_stem = ops[op].kind == OP_STEM && op + 1 < (int)ops.size(), after_stem = op > 0 && ops[op - 1].kind == OP_STEM;
-    const int st = c->net.run(n, c->stream, after_stem ? op - 1 : op, is_stem ? op + 1 : op);
+    std::string out;
+    const int st = c->net.op_kernel_names(n, op, device_cus(), &out);
     c->net.co_running = saved;
-    c->net.profiling = prof;
-    note.dry = false;
     RFD_TRY(st);
-    std::string out = note.names;
-    if (is_stem || after_stem) {
-        const size_t cut = out.find(" + ");
-        const bool fused = cut == std::string::npos; // one launch for the two ops
-        if (is_stem) out = fused ? out : out.substr(0, cut);
-        else out = fused ? "(fused into " + out + ")" : out.substr(cut + 3);
-    }
+    snprintf(names, (size_t)cap, "%s", out.c_str());
+    return RFD_OK;
+}
+
+int rfd_debug_op_kernels_static(int backbone, int net_w, int net_h, int n, int op, int co_running, int tile, int schedule, int cus, char *names, int cap)
+{
+    RFD_CHECK_ARG(names && cap > 0 && n >= 1 && cus >= 1 && tile >= 0 && tile <= 31, "bad argument");
+    Network net; // never created: no device, no allocation
+    RFD_TRY(net.g.build(backbone, net_w, net_h));
+    RFD_CHECK_ARG(op >= 0 && op < (int)net.g.ops.size(), "op out of range");
+    net.max_batch = n;
+    net.schedule = schedule;
+    net.force_tile = tile;
+    net.co_running = co_running != 0;
+    if (schedule == RFD_SCHEDULE_LATENCY) (void)net.plan_splitk();
+    // Operands "present" for the chooser: addresses at the offsets of the layer table and the workspace plan from a made-up base.
+    // Nothing reads through them; the relation of two filter banks is one of their offsets, as on a device.
+    char *const base = reinterpret_cast<char *>((uintptr_t)1 << 32);
+    net.d_w = reinterpret_cast<bf16_t *>(base);
+    net.d_b = reinterpret_cast<float *>(base);
+    net.d_zero = reinterpret_cast<bf16_t *>(base);
+    net.d_buffers.assign(net.g.buffer_bytes_per_image.size(), base);
+    for (int b = 0; b < 3; ++b) net.d_sk_ws[b] = reinterpret_cast<float *>(base);
+    net.d_sk_cnt = reinterpret_cast<unsigned *>(base);
+    std::string out;
+    RFD_TRY(net.op_kernel_names(n, op, cus, &out));
     snprintf(names, (size_t)cap, "%s", out.c_str());
     return RFD_OK;
 }

@@ -136,14 +136,14 @@ struct ConvParams {
     int relu;             // relu on the primary output
     int res_up2;          // residual is half resolution: read at (ho/2, wo/2) (FPN nearest 2x)
     int res_post;         // add the residual AFTER the ReLU (FPN: relu(lateral) + upsampled)
-    int force_tile;       // 0 = heuristic, 1 = 128-row tiles, 2 = 256x128 tile (tuning / tests)
+    int force_tile;       // ConvTile: TILE_HEURISTIC in production, a forced choice in tuning / tests
     int co_running;       // another chain of the same pass runs concurrently (batch split): affects the tile heuristic
     int head_softmax;     // heads: channels [0,4) are cls logits -> 2-class softmax pairs (a, A+a)
-    int k_chunk_major;    // set by launch_conv: K order (chunk, ky, kx) instead of (ky, kx, chunk) (see conv_igemm_kernel)
+    int k_chunk_major;    // set by choose_conv: K order (chunk, ky, kx) instead of (ky, kx, chunk) (see conv_igemm_kernel)
     // back-to-back pair (OP_B2B beyond stage 1): after this 1x1 conv3 (+ residual -> y = the raw sum), the NEXT unit's conv1 on
     // relu(y * scale2 + shift2) -- or, for the last unit of a stage (y null), on its activated output y2 --:
     // t1 = relu(W1 . act + bias1), [B][H][W][N1], N1 = the next unit's bottleneck width (this Cin; 128 for the stage 1 -> 2 boundary).
-    // launch_conv runs the pair in one kernel (pw_b2b_kernel) where that pays and as two launches otherwise: same bits.
+    // choose_conv runs the pair in one kernel (pw_b2b_kernel, pw_pair_kernel) where that pays and as two launches otherwise: same bits.
     const bf16_t *w1;     // [n1][Cout] (row pitch Cout), or null: no pair
     const float *bias1;
     bf16_t *t1;
@@ -156,7 +156,110 @@ struct ConvParams {
     size_t sk_ws_bytes;   // capacities, checked on the host before every launch
     int sk_cnt_n;
 };
-int launch_conv(const ConvParams &p, hipStream_t s);
+// ---- kernel choice (conv_select.hip): pure host functions; the launchers below execute what they return ----
+// ConvParams::force_tile / rfd_debug_set_conv_tile.  "Persistent kernels": pw_stream, pw_wide, pw_gemm, conv3x3_c64, conv3x3_halo,
+// the pair kernels and stage 1's persistent back-to-back forms; each runs a layer only from a size threshold in production.
+enum ConvTile : int {
+    TILE_HEURISTIC = 0,        // production: every rule by its measured size threshold
+    TILE_128 = 1,              // generic 128 x 128 tile, four waves, 2 slots (128 x 192: four waves); no persistent, merged-kx or pair kernel,
+                               // stage 1's pairs in the one-tile kernel
+    TILE_256x128 = 2,          // generic 256 x 128 tile; otherwise as TILE_128
+    TILE_256x64 = 3,           // 256 x 64 instead of 128 x 64 on the layers the generic rules give a 64-wide tile
+    TILE_NO_128 = 4,           // never a 128-wide generic tile: 128 x 64 / 128 x 32
+    TILE_NO_PW_STREAM = 5,     // none of the persistent convolution or pair kernels (stage 1's back-to-back forms keep their size rule, as
+                               // under every tile that does not name them); the merged-kx 3x3 kernel stays
+    TILE_PERSISTENT = 6,       // every persistent kernel wherever its shape rule holds, whatever the size
+    TILE_GENERIC = 7,          // as TILE_NO_PW_STREAM, and stage 1's pairs in the one-tile kernel
+    TILE_PW_STREAM = 8,        // of the persistent kernels only pw_stream, by its size rule
+    TILE_C64 = 9,              // of the persistent kernels only conv3x3_c64, by its size rule
+    TILE_PW_STREAM_K128 = 10,  // as TILE_PW_STREAM for the K = 128 layers alone
+    TILE_PW_STREAM_K256 = 11,  // as TILE_PW_STREAM for the K = 256 layers alone
+    TILE_PW_WIDE = 12,         // pw_wide wherever its shape rule holds, whatever the size
+    TILE_HALO_SMALL = 13,      // conv3x3_halo with its smallest work item, whatever the size
+    TILE_HALO_LARGE = 14,      // conv3x3_halo with its largest work item, whatever the size
+    TILE_PW_GEMM = 15,         // pw_gemm with 256 x 128 items (never the wide item), whatever the size
+    TILE_PAIR = 16,            // the fused pair kernels whatever the size (stage 1: pw_pair); a pair run as two convolutions: heuristic
+    TILE_RING = 17,            // the loader / consumer ring wherever its shape rule holds
+    TILE_128_EIGHT_WAVES = 18, // generic 128 x 128 tile with eight waves on every Cout % 128 == 0 layer without input affine
+    TILE_KX_FOUR_WAVES = 19,   // the merged-kx 3x3 kernel (and the 128 x 192 tile) in the four-wave form
+    TILE_COUNT = 20
+};
+
+// every shipped conv-path instantiation: id, display name (the string rocprofv3 reports, without the rfd:: prefix)
+#define RFD_CONV_KERNELS(X)                                                                           \
+    X(K_STEM, "stem_kernel")                                                                          \
+    X(K_STEM_PERSISTENT, "stem_persistent_kernel<false>")                                             \
+    X(K_STEM_PERSISTENT_CONV1, "stem_persistent_kernel<true>")                                        \
+    X(K_FIRST3X3, "first3x3_kernel")                                                                  \
+    X(K_DWCONV3X3, "dwconv3x3_kernel")                                                                \
+    X(K_B2B_S1, "conv_b2b_s1_kernel")                                                                 \
+    X(K_B2B_S1_PERSISTENT, "conv_b2b_s1_persistent_kernel")                                           \
+    X(K_B2B_S1_PERSISTENT_K128, "conv_b2b_s1_persistent_k128_kernel")                                 \
+    X(K_IGEMM_256_128_4_2_3, "conv_igemm_kernel<256, 128, 4, 2, 3, false>")                           \
+    X(K_IGEMM_256_128_4_2_3_CM, "conv_igemm_kernel<256, 128, 4, 2, 3, true>")                         \
+    X(K_IGEMM_128_128_2_2_2, "conv_igemm_kernel<128, 128, 2, 2, 2, false>")                           \
+    X(K_IGEMM_128_128_2_2_2_CM, "conv_igemm_kernel<128, 128, 2, 2, 2, true>")                         \
+    X(K_IGEMM_128_128_4_2_3, "conv_igemm_kernel<128, 128, 4, 2, 3, false>")                           \
+    X(K_IGEMM_128_128_4_2_3_CM, "conv_igemm_kernel<128, 128, 4, 2, 3, true>")                         \
+    X(K_IGEMM_128_128_2_2_3, "conv_igemm_kernel<128, 128, 2, 2, 3, false>")                           \
+    X(K_IGEMM_128_192_2_2_2, "conv_igemm_kernel<128, 192, 2, 2, 2, false>")                           \
+    X(K_IGEMM_128_192_2_2_2_CM, "conv_igemm_kernel<128, 192, 2, 2, 2, true>")                         \
+    X(K_IGEMM_128_192_4_2_2, "conv_igemm_kernel<128, 192, 4, 2, 2, false>")                           \
+    X(K_IGEMM_128_192_4_2_2_CM, "conv_igemm_kernel<128, 192, 4, 2, 2, true>")                         \
+    X(K_IGEMM_256_64_4_1_2, "conv_igemm_kernel<256, 64, 4, 1, 2, false>")                             \
+    X(K_IGEMM_128_64_4_1_2, "conv_igemm_kernel<128, 64, 4, 1, 2, false>")                             \
+    X(K_IGEMM_128_32_4_1_2, "conv_igemm_kernel<128, 32, 4, 1, 2, false>")                             \
+    X(K_CONV3X3_KX_128_2_2, "conv3x3_kx_kernel<128, 2, 2>")                                           \
+    X(K_CONV3X3_KX_128_4_2, "conv3x3_kx_kernel<128, 4, 2>")                                           \
+    X(K_CONV3X3_C64, "conv3x3_c64_kernel")                                                            \
+    X(K_HALO_40_6_6, "conv3x3_halo_kernel<40, 6, 6>")                                                 \
+    X(K_HALO_16_16_6, "conv3x3_halo_kernel<16, 16, 6>")                                               \
+    X(K_HALO_16_16_8, "conv3x3_halo_kernel<16, 16, 8>")                                               \
+    X(K_HALO_40_6_4, "conv3x3_halo_kernel<40, 6, 4>")                                                 \
+    X(K_HALO_16_16_4, "conv3x3_halo_kernel<16, 16, 4>")                                               \
+    X(K_PW_STREAM_1_Y2, "pw_stream_kernel<1, false, true>")                                           \
+    X(K_PW_STREAM_2_Y, "pw_stream_kernel<2, true, false>")                                            \
+    X(K_PW_STREAM_2_Y2, "pw_stream_kernel<2, false, true>")                                           \
+    X(K_PW_STREAM_4_Y, "pw_stream_kernel<4, true, false>")                                            \
+    X(K_PW_STREAM_4_Y2, "pw_stream_kernel<4, false, true>")                                           \
+    X(K_PW_B2B_2, "pw_b2b_kernel<2, false>")                                                          \
+    X(K_PW_PAIR_2_1_RAW_4, "pw_pair_kernel<2, 1, false, 4, 0, false>")                                \
+    X(K_PW_PAIR_4_2_RAW, "pw_pair_kernel<4, 2, false, 0, 0, false>")                                  \
+    X(K_PW_PAIR_2_2_ACT, "pw_pair_kernel<2, 2, true, 0, 0, false>")                                   \
+    X(K_PW_PAIR_1_1_ACT_0_2, "pw_pair_kernel<1, 1, true, 0, 2, false>")                               \
+    X(K_PW_PAIR_1_1_RAW_1_2_HALF, "pw_pair_kernel<1, 1, false, 1, 2, true>")                          \
+    X(K_PW_PAIR_1_1_RAW_0_2_HALF, "pw_pair_kernel<1, 1, false, 0, 2, true>")                          \
+    X(K_PW_GEMM, "pw_gemm_kernel<false, false>")                                                      \
+    X(K_PW_GEMM_WIDE, "pw_gemm_kernel<false, true>")                                                  \
+    X(K_PW_GEMM_AFF, "pw_gemm_kernel<true, false>")                                                   \
+    X(K_PW_GEMM_AFF_WIDE, "pw_gemm_kernel<true, true>")                                               \
+    X(K_PW_WIDE, "pw_wide_kernel")                                                                    \
+    X(K_RING, "conv_ring_kernel<false>")                                                              \
+    X(K_RING_KX3, "conv_ring_kernel<true>")                                                           \
+    X(K_SPLITK_64_64_2_2, "conv_splitk_kernel<64, 64, 2, 2>")
+enum ConvKernel : int {
+    K_NONE = 0,
+#define RFD_ID(id, name) id,
+    RFD_CONV_KERNELS(RFD_ID)
+#undef RFD_ID
+};
+const char *conv_kernel_name(ConvKernel k);
+
+struct ConvStep {
+    ConvKernel kernel;
+    ConvParams p; // what the kernel runs with: k_chunk_major set, the two convolutions of an unfused pair derived
+};
+struct ConvPlan {
+    int steps; // 1, or 2: a pair run as its two convolutions
+    ConvStep step[2];
+};
+// The pair kernels address both filter banks through ONE 32-bit buffer descriptor based at the first: the second must lie behind
+// it, within 1 GiB.  A relation of the banks' offsets into the weight buffer, wherever that buffer is.
+static inline bool bank_behind(const bf16_t *w, const bf16_t *w1) { return (uintptr_t)w1 > (uintptr_t)w && (uintptr_t)w1 - (uintptr_t)w < (1u << 30); }
+// validates p (launch_conv's errors, in its order) and fills the plan
+int choose_conv(const ConvParams &p, bool w1_behind_w, ConvPlan *plan);
+int launch_conv(const ConvParams &p, hipStream_t s); // validate, choose, execute
+
 // split-K form of the generic implicit-GEMM tile (kernels_splitk.hip; the latency schedule).  The plan is a pure function of the
 // layer (K, Cout), the pixels of one image and -- for the grid and the workspace only -- the batch.
 constexpr int kSplitKMaxSegments = 8;
@@ -172,6 +275,7 @@ int launch_conv_splitk(const ConvParams &p, hipStream_t s);
 // wave-specialised loader / consumer ring form of the 128 x 128 implicit-GEMM tile (kernels_ring.hip)
 bool conv_ring_supports(const ConvParams &p, bool *kx3);
 int launch_conv_ring(const ConvParams &p, hipStream_t s);
+int device_cus(); // CU count of the current device (cached per device)
 // entry i of the list of persistent kernels (name prefix, dynamic LDS every launch of it requests); returns the list length
 int persistent_kernel_table(int i, const char **name, size_t *lds_bytes);
 // ---- f32 parity mode (kernels_f32.hip): ConvParams with f32 tensors and weights; same field meanings ----
@@ -203,15 +307,19 @@ struct B2BParams {
     const float *bias1;
     bf16_t *t1;                // [M][64]
     int B, H, W, Cin, Cin2;
-    int force_tile;            // as ConvParams::force_tile (6: persistent form forced, 7 / 1 / 2: never)
+    int force_tile;            // as ConvParams::force_tile
 };
+// st->kernel: one of stage 1's three kernels (they run with p itself), or a pw_pair form with its parameters in st->p
+void choose_b2b_s1(const B2BParams &p, bool w1_behind_w3, ConvStep *st);
 int launch_conv_b2b_s1(const B2BParams &p, hipStream_t s);
 // fused stem: conv0 (7x7/2 + bias + ReLU) -> 3x3/2 max pool -> affine + ReLU, NHWC4 in, [B][H/4][W/4][64] out
 // w1 / bias1 / t1 / fused (all or none): the first unit's conv1 (1x1, 64 -> 64, bias + ReLU) computed on the pooled tile and stored to
 // t1 when the persistent form runs; *fused tells the caller whether it was (then the conv's own op must not run)
+constexpr int kStemPH = 4, kStemPW = 16; // pooled tile of a stem workgroup
+ConvKernel choose_stem(int B, int H, int W, bool conv1_offered, int force_tile, int cus); // K_STEM, K_STEM_PERSISTENT or K_STEM_PERSISTENT_CONV1
 int launch_stem(const bf16_t *x4, const bf16_t *w, const float *bias, const float *scale, const float *shift,
-                bf16_t *y, int B, int H, int W, hipStream_t s, const bf16_t *w1 = nullptr, const float *bias1 = nullptr,
-                bf16_t *t1 = nullptr, bool *fused = nullptr);
+                bf16_t *y, int B, int H, int W, hipStream_t s, int force_tile = 0, const bf16_t *w1 = nullptr,
+                const float *bias1 = nullptr, bf16_t *t1 = nullptr, bool *fused = nullptr);
 // MobileNet-0.25 helpers: first 3x3/2 conv (3 -> 8 real channels, output padded to Cd) and depthwise 3x3
 int launch_first3x3(const bf16_t *x4, const bf16_t *w, const float *bias, bf16_t *y, int B, int H, int W, int Cd,
                     hipStream_t s);

@@ -1066,7 +1066,7 @@ __global__ void __launch_bounds__(512, 2) pw_pair_kernel(const ConvParams p) // 
 
 // CU count of the current device, queried once per device (every persistent launcher sizes its "even share, no tail" grid
 // with it; a partitioned or smaller device simply gets a smaller grid)
-static int device_cus()
+int device_cus()
 {
     static std::atomic<int> cached[DynLdsOnce::kMaxDevices] = {};
     int dev = 0;
@@ -1098,7 +1098,6 @@ int persistent_kernel_table(int i, const char **name, size_t *lds_bytes)
 }
 template <auto Kern, typename... A> static int launch_persistent(int grid, size_t lds_need, hipStream_t s, A... args)
 {
-    if (launch_note().dry) return RFD_OK; // the caller has recorded the kernel's name (note_launch)
     if (lds_need > kPersistentLds) { set_error("persistent kernel: %zu bytes of LDS needed", lds_need); return RFD_ERR_CAPACITY; }
     static DynLdsOnce once;
     RFD_TRY(once.ensure(reinterpret_cast<const void *>(Kern), (int)kPersistentLds));
@@ -1122,7 +1121,6 @@ template <int NK, bool HAS_Y, bool HAS_Y2> static int launch_pw_stream(const Con
     // write-after-read race on the weight ring in this kernel's ISA (bare s_barrier with ds_reads in flight, now
     // `s_waitcnt lgkmcnt(0)` + barrier) that the padding may only have masked; the padding stays as the rule either way.
     const size_t lds_need = (size_t)(NK * 128 + (NK + 1) * 128) * 64 * sizeof(bf16_t) + (size_t)3 * p.Cout * sizeof(float);
-    note_launch("pw_stream_kernel<%d, %s, %s>", NK, HAS_Y ? "true" : "false", HAS_Y2 ? "true" : "false");
     return launch_persistent<pw_stream_kernel<NK, HAS_Y, HAS_Y2>>(grid, lds_need, s, p);
 }
 template <int NK, bool ACT_OUT> static int launch_pw_b2b(const ConvParams &p, hipStream_t s)
@@ -1133,7 +1131,6 @@ template <int NK, bool ACT_OUT> static int launch_pw_b2b(const ConvParams &p, hi
     const int per = ceil_div(tiles_m, ncu);
     const int grid = ceil_div(tiles_m, per);
     const size_t lds_need = (size_t)(NK + 2 + NK + 3) * 128 * 64 * sizeof(bf16_t) + (size_t)(3 * p.Cout + 128) * sizeof(float);
-    note_launch("pw_b2b_kernel<%d, %s>", NK, ACT_OUT ? "true" : "false");
     return launch_persistent<pw_b2b_kernel<NK, ACT_OUT>>(grid, lds_need, s, p);
 }
 template <int NK, int N1B, bool ACT_OUT, int NK2 = 0, int NCR = 0, bool HALF1 = false> static int launch_pw_pair(const ConvParams &p, hipStream_t s)
@@ -1147,17 +1144,8 @@ template <int NK, int N1B, bool ACT_OUT, int NK2 = 0, int NCR = 0, bool HALF1 = 
     const size_t lds_need = slots * 128 * 64 * sizeof(bf16_t) + (size_t)(3 * p.Cout + 128 * N1B) * sizeof(float);
     if (NCR && p.Cout != NCR * 128) { set_error("pw_pair: resident form instantiated for %d output channels", NCR * 128); return RFD_ERR_INVALID_ARG; }
     if (p.n1 != (HALF1 ? 64 : 128 * N1B)) { set_error("pw_pair: instantiated for n1 = %d, got %d", HALF1 ? 64 : 128 * N1B, p.n1); return RFD_ERR_INVALID_ARG; }
-    note_launch("pw_pair_kernel<%d, %d, %s, %d, %d, %s>", NK, N1B, ACT_OUT ? "true" : "false", NK2, NCR, HALF1 ? "true" : "false");
     return launch_persistent<pw_pair_kernel<NK, N1B, ACT_OUT, NK2, NCR, HALF1>>(grid, lds_need, s, p);
 }
-// the forms launch_conv's pw_ok admits: one output, raw (y) or activated (y2); K = 64 layers only the activated one
-template <int NK> static int launch_pw_stream_nk(const ConvParams &p, hipStream_t s)
-{
-    if constexpr (NK > 1)
-        if (p.y) return launch_pw_stream<NK, true, false>(p, s);
-    return launch_pw_stream<NK, false, true>(p, s);
-}
-
 // ------------------------------------------------------------------------------------------------
 // 3x3 / stride 1 / pad 1 convolutions with the three kx taps sharing ONE staged activation tile.
 //
@@ -1462,7 +1450,6 @@ static int launch_conv3x3_c64(const ConvParams &p, hipStream_t s)
     // needs 154 KiB; launch_persistent asks for the whole CU's LDS so that no other kernel's workgroup can ever share the CU
     constexpr size_t lds_need = (size_t)(9 * 64 * 64 + 2 * kC64HP * 512) * sizeof(bf16_t);
     static_assert(lds_need <= kPersistentLds, "LDS");
-    note_launch("conv3x3_c64_kernel");
     return launch_persistent<conv3x3_c64_kernel>(grid, lds_need, s, p, tiles_x, tiles_y);
 }
 
@@ -1711,7 +1698,6 @@ template <int TC, int TR, int TN> static int launch_conv3x3_halo(const ConvParam
     const int grid = ceil_div(n_items, per);
     constexpr int HP = ((TR + 2) * (TC + 2) + 7) / 8, U = TN == 4 ? 2 : 1;
     constexpr size_t lds_need = (size_t)(2 * HP * 512 + 2 * U * 32 * TN * 64) * 2 + 2048; // two halo buffers, two weight slots, tables
-    note_launch("conv3x3_halo_kernel<%d, %d, %d>", TC, TR, TN);
     return launch_persistent<conv3x3_halo_kernel<TC, TR, TN>>(grid, lds_need, s, p, tiles_x, tiles_y, n_items);
 }
 
@@ -1724,7 +1710,6 @@ static int launch_conv3x3_kx(const ConvParams &p, hipStream_t s)
     auto kern = conv3x3_kx_kernel<BN, WAVES_M, WAVES_N>;
     static DynLdsOnce once;
     RFD_TRY(once.ensure(reinterpret_cast<const void *>(kern), (int)lds));
-    if (note_launch("conv3x3_kx_kernel<%d, %d, %d>", BN, WAVES_M, WAVES_N)) return RFD_OK;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES_M * WAVES_N * 64), lds, s, p);
     RFD_HIP(hipGetLastError());
     return RFD_OK;
@@ -1983,24 +1968,16 @@ __global__ void __launch_bounds__(512) pw_gemm_kernel(const ConvParams p, int ti
     wait_vmcnt<0>();
 }
 
-template <bool AFF, bool WIDE> static int launch_pw_gemm_t(const ConvParams &p, hipStream_t s, int tiles_m, int n_items, int grid)
-{
-    // 3 activation + 2 weight slots + tables: the whole CU
-    note_launch("pw_gemm_kernel<%s, %s>", AFF ? "true" : "false", WIDE ? "true" : "false");
-    return launch_persistent<pw_gemm_kernel<AFF, WIDE>>(grid, kPersistentLds, s, p, tiles_m, n_items);
-}
-
-static int launch_pw_gemm(const ConvParams &p, hipStream_t s)
+// WIDE: 128-pixel x 256-channel items (choose_conv: where they cover all channels of an N = 256 layer and still fill the GPU)
+template <bool AFF, bool WIDE> static int launch_pw_gemm(const ConvParams &p, hipStream_t s)
 {
     const int M = p.B * p.H * p.W;
-    // 128-pixel x 256-channel items where they cover all channels of an N = 256 layer and still fill the GPU (force_tile 15: never)
-    const bool wide = p.Cout == 256 && ceil_div(M, 128) >= 150 && p.force_tile != 15;
-    const int tiles_m = ceil_div(M, wide ? 128 : 256), n_items = tiles_m * (p.Cout / (wide ? 256 : 128));
+    const int tiles_m = ceil_div(M, WIDE ? 128 : 256), n_items = tiles_m * (p.Cout / (WIDE ? 256 : 128));
     const int ncu = device_cus();
     const int per = ceil_div(n_items, ncu);
     const int grid = ceil_div(n_items, per);
-    if (p.in_scale) return wide ? launch_pw_gemm_t<true, true>(p, s, tiles_m, n_items, grid) : launch_pw_gemm_t<true, false>(p, s, tiles_m, n_items, grid);
-    return wide ? launch_pw_gemm_t<false, true>(p, s, tiles_m, n_items, grid) : launch_pw_gemm_t<false, false>(p, s, tiles_m, n_items, grid);
+    // 3 activation + 2 weight slots + tables: the whole CU
+    return launch_persistent<pw_gemm_kernel<AFF, WIDE>>(grid, kPersistentLds, s, p, tiles_m, n_items);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2217,7 +2194,6 @@ static int launch_pw_wide(const ConvParams &p, hipStream_t s)
     const int per = ceil_div(n_items, ncu);
     const int grid = ceil_div(n_items, per);
     // 4 x 32 KiB + tables: the whole CU
-    note_launch("pw_wide_kernel");
     return launch_persistent<pw_wide_kernel>(grid, kPersistentLds, s, p, n_items);
 }
 
@@ -2717,50 +2693,6 @@ __global__ void __launch_bounds__(512) conv_b2b_s1_persistent_k128_kernel(const 
     }
 }
 
-int launch_conv_b2b_s1(const B2BParams &p, hipStream_t s)
-{
-    if (p.Cin != 64 || (p.Cin2 != 0 && p.Cin2 != 64)) {
-        set_error("b2b: unsupported shape Cin=%d Cin2=%d", p.Cin, p.Cin2);
-        return RFD_ERR_INVALID_ARG;
-    }
-    const int M = p.B * p.H * p.W;
-    const size_t lds = (size_t)(128 * 64 + 256 * 64 + 4 * 128 * 64 + 4 * 64 * 64) * sizeof(bf16_t); // 144 KiB
-    const int ntiles = ceil_div(M, 128);
-    // Round 4: the weight-resident barrier-free pair kernel (pw_pair_kernel<.., NCR = 2, HALF1>, the form that runs the stage
-    // 1 -> 2 boundary) takes stage 1's pairs too: W3 [256][64 or 128] + W1 [64][256] stay in LDS, every wave is an independent
-    // pipeline over its 16 pixels.  force_tile 16 forces it, 6 keeps the older persistent kernels below.
-    const bool pair_ok = (const char *)p.w1 > (const char *)p.w3 && (size_t)((const char *)p.w1 - (const char *)p.w3) < (1u << 30) &&
-                         (p.Cin2 == 0 ? p.res != nullptr : (!p.res && p.bias3b)) && (size_t)M * 256 * 2 < 0xfffffff0ull;
-    if (pair_ok && (p.force_tile == 16 || (p.force_tile == 0 && ntiles >= 512))) {
-        ConvParams c;
-        memset(&c, 0, sizeof c);
-        c.x = p.x; c.w = p.w3; c.bias = p.bias3; c.x2 = p.x2; c.bias2 = p.bias3b; c.res = p.res;
-        c.scale2 = p.scale; c.shift2 = p.shift; c.y = p.raw; c.w1 = p.w1; c.bias1 = p.bias1; c.t1 = p.t1; c.n1 = 64;
-        c.B = p.B; c.H = c.Ho = c.H2 = p.H; c.W = c.Wo = c.W2 = p.W; c.Cin = p.Cin; c.Cin2 = p.Cin2; c.stride2 = 1; c.Cout = 256;
-        c.KH = c.KW = 1; c.stride = 1; c.ldx = p.Cin; c.ldy = 256; c.y_split = c.n_valid = 1 << 30; c.co_running = 1;
-        return p.Cin2 ? launch_pw_pair<1, 1, false, 1, 2, true>(c, s) : launch_pw_pair<1, 1, false, 0, 2, true>(c, s);
-    }
-    // K1 = 64 and at least two tiles per CU: the persistent form (force_tile 7 opts out, 6 forces it whatever the size)
-    if (p.Cin2 == 0 && p.force_tile != 7 && p.force_tile != 1 && p.force_tile != 2 && (ntiles >= 512 || p.force_tile == 6)) {
-        const int per = ceil_div(ntiles, device_cus());
-        const int grid = ceil_div(ntiles, per);
-        note_launch("conv_b2b_s1_persistent_kernel");
-        return launch_persistent<conv_b2b_s1_persistent_kernel>(grid, kPersistentLds, s, p, ntiles);
-    }
-    // K1 = 128 (fused shortcut, no residual): persistent 64-pixel tiles, both filter banks resident
-    if (p.Cin2 == 64 && !p.res && p.force_tile != 7 && p.force_tile != 1 && p.force_tile != 2 && (M >= 64 * 1024 || p.force_tile == 6)) {
-        const int nt = ceil_div(M, 64), per = ceil_div(nt, device_cus());
-        note_launch("conv_b2b_s1_persistent_k128_kernel");
-        return launch_persistent<conv_b2b_s1_persistent_k128_kernel>(ceil_div(nt, per), kPersistentLds, s, p, nt);
-    }
-    static DynLdsOnce once;
-    RFD_TRY(once.ensure(reinterpret_cast<const void *>(conv_b2b_s1_kernel), (int)lds));
-    if (note_launch("conv_b2b_s1_kernel")) return RFD_OK;
-    hipLaunchKernelGGL(conv_b2b_s1_kernel, dim3(ceil_div(M, 128)), dim3(512), lds, s, p);
-    RFD_HIP(hipGetLastError());
-    return RFD_OK;
-}
-
 template <int BM, int BN, int WAVES_M, int WAVES_N, int NSX, bool CHUNK_MAJOR>
 static int launch_conv_cfg_order(const ConvParams &p, hipStream_t s)
 {
@@ -2774,231 +2706,93 @@ static int launch_conv_cfg_order(const ConvParams &p, hipStream_t s)
     auto kern = conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, NSX, CHUNK_MAJOR>;
     static DynLdsOnce once;
     RFD_TRY(once.ensure(reinterpret_cast<const void *>(kern), (int)(full + 16384)));
-    if (note_launch("conv_igemm_kernel<%d, %d, %d, %d, %d, %s>", BM, BN, WAVES_M, WAVES_N, NSX, CHUNK_MAJOR ? "true" : "false")) return RFD_OK;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES_M * WAVES_N * 64), lds, s, p);
     RFD_HIP(hipGetLastError());
     return RFD_OK;
 }
-template <int BM, int BN, int WAVES_M, int WAVES_N, int NSX> static int launch_conv_cfg(const ConvParams &p, hipStream_t s)
+// the launcher of every ConvParams kernel id (choose_conv, choose_b2b_s1)
+static int run_conv_step(const ConvStep &st, hipStream_t s)
 {
-    // chunk-major K order is set for halo-shape layers only (launch_conv), and those reach the generic kernel on these tiles alone
-    constexpr bool kHaloTile = (BN == 128 && !(WAVES_M == 2 && NSX == 3)) || BN == 192;
-    if constexpr (kHaloTile) {
-        if (p.k_chunk_major) return launch_conv_cfg_order<BM, BN, WAVES_M, WAVES_N, NSX, true>(p, s);
-    } else if (p.k_chunk_major) {
-        set_error("conv: the %d x %d tile has no chunk-major form", BM, BN);
+    const ConvParams &p = st.p;
+    switch (st.kernel) {
+    case K_IGEMM_256_128_4_2_3: return launch_conv_cfg_order<256, 128, 4, 2, 3, false>(p, s);
+    case K_IGEMM_256_128_4_2_3_CM: return launch_conv_cfg_order<256, 128, 4, 2, 3, true>(p, s);
+    case K_IGEMM_128_128_2_2_2: return launch_conv_cfg_order<128, 128, 2, 2, 2, false>(p, s);
+    case K_IGEMM_128_128_2_2_2_CM: return launch_conv_cfg_order<128, 128, 2, 2, 2, true>(p, s);
+    case K_IGEMM_128_128_4_2_3: return launch_conv_cfg_order<128, 128, 4, 2, 3, false>(p, s);
+    case K_IGEMM_128_128_4_2_3_CM: return launch_conv_cfg_order<128, 128, 4, 2, 3, true>(p, s);
+    case K_IGEMM_128_128_2_2_3: return launch_conv_cfg_order<128, 128, 2, 2, 3, false>(p, s);
+    case K_IGEMM_128_192_2_2_2: return launch_conv_cfg_order<128, 192, 2, 2, 2, false>(p, s);
+    case K_IGEMM_128_192_2_2_2_CM: return launch_conv_cfg_order<128, 192, 2, 2, 2, true>(p, s);
+    case K_IGEMM_128_192_4_2_2: return launch_conv_cfg_order<128, 192, 4, 2, 2, false>(p, s);
+    case K_IGEMM_128_192_4_2_2_CM: return launch_conv_cfg_order<128, 192, 4, 2, 2, true>(p, s);
+    case K_IGEMM_256_64_4_1_2: return launch_conv_cfg_order<256, 64, 4, 1, 2, false>(p, s);
+    case K_IGEMM_128_64_4_1_2: return launch_conv_cfg_order<128, 64, 4, 1, 2, false>(p, s);
+    case K_IGEMM_128_32_4_1_2: return launch_conv_cfg_order<128, 32, 4, 1, 2, false>(p, s);
+    case K_CONV3X3_KX_128_2_2: return launch_conv3x3_kx<128, 2, 2>(p, s);
+    case K_CONV3X3_KX_128_4_2: return launch_conv3x3_kx<128, 4, 2>(p, s);
+    case K_CONV3X3_C64: return launch_conv3x3_c64(p, s);
+    case K_HALO_40_6_6: return launch_conv3x3_halo<40, 6, 6>(p, s);
+    case K_HALO_16_16_6: return launch_conv3x3_halo<16, 16, 6>(p, s);
+    case K_HALO_16_16_8: return launch_conv3x3_halo<16, 16, 8>(p, s);
+    case K_HALO_40_6_4: return launch_conv3x3_halo<40, 6, 4>(p, s);
+    case K_HALO_16_16_4: return launch_conv3x3_halo<16, 16, 4>(p, s);
+    case K_PW_STREAM_1_Y2: return launch_pw_stream<1, false, true>(p, s);
+    case K_PW_STREAM_2_Y: return launch_pw_stream<2, true, false>(p, s);
+    case K_PW_STREAM_2_Y2: return launch_pw_stream<2, false, true>(p, s);
+    case K_PW_STREAM_4_Y: return launch_pw_stream<4, true, false>(p, s);
+    case K_PW_STREAM_4_Y2: return launch_pw_stream<4, false, true>(p, s);
+    case K_PW_B2B_2: return launch_pw_b2b<2, false>(p, s);
+    case K_PW_PAIR_2_1_RAW_4: return launch_pw_pair<2, 1, false, 4>(p, s);
+    case K_PW_PAIR_4_2_RAW: return launch_pw_pair<4, 2, false>(p, s);
+    case K_PW_PAIR_2_2_ACT: return launch_pw_pair<2, 2, true>(p, s);
+    case K_PW_PAIR_1_1_ACT_0_2: return launch_pw_pair<1, 1, true, 0, 2>(p, s);
+    case K_PW_PAIR_1_1_RAW_1_2_HALF: return launch_pw_pair<1, 1, false, 1, 2, true>(p, s);
+    case K_PW_PAIR_1_1_RAW_0_2_HALF: return launch_pw_pair<1, 1, false, 0, 2, true>(p, s);
+    case K_PW_GEMM: return launch_pw_gemm<false, false>(p, s);
+    case K_PW_GEMM_WIDE: return launch_pw_gemm<false, true>(p, s);
+    case K_PW_GEMM_AFF: return launch_pw_gemm<true, false>(p, s);
+    case K_PW_GEMM_AFF_WIDE: return launch_pw_gemm<true, true>(p, s);
+    case K_PW_WIDE: return launch_pw_wide(p, s);
+    case K_RING:
+    case K_RING_KX3: return launch_conv_ring(p, s);
+    case K_SPLITK_64_64_2_2: return launch_conv_splitk(p, s);
+    default: set_error("conv: kernel id %d does not run with ConvParams", (int)st.kernel); return RFD_ERR_INVALID_ARG;
+    }
+}
+
+int launch_conv_b2b_s1(const B2BParams &p, hipStream_t s)
+{
+    if (p.Cin != 64 || (p.Cin2 != 0 && p.Cin2 != 64)) {
+        set_error("b2b: unsupported shape Cin=%d Cin2=%d", p.Cin, p.Cin2);
         return RFD_ERR_INVALID_ARG;
     }
-    return launch_conv_cfg_order<BM, BN, WAVES_M, WAVES_N, NSX, false>(p, s);
+    ConvStep st;
+    choose_b2b_s1(p, bank_behind(p.w3, p.w1), &st);
+    const int M = p.B * p.H * p.W;
+    if (st.kernel == K_B2B_S1_PERSISTENT) {
+        const int ntiles = ceil_div(M, 128), per = ceil_div(ntiles, device_cus());
+        return launch_persistent<conv_b2b_s1_persistent_kernel>(ceil_div(ntiles, per), kPersistentLds, s, p, ntiles);
+    }
+    if (st.kernel == K_B2B_S1_PERSISTENT_K128) {
+        const int nt = ceil_div(M, 64), per = ceil_div(nt, device_cus());
+        return launch_persistent<conv_b2b_s1_persistent_k128_kernel>(ceil_div(nt, per), kPersistentLds, s, p, nt);
+    }
+    if (st.kernel != K_B2B_S1) return run_conv_step(st, s); // a pw_pair form
+    const size_t lds = (size_t)(128 * 64 + 256 * 64 + 4 * 128 * 64 + 4 * 64 * 64) * sizeof(bf16_t); // 144 KiB
+    static DynLdsOnce once;
+    RFD_TRY(once.ensure(reinterpret_cast<const void *>(conv_b2b_s1_kernel), (int)lds));
+    hipLaunchKernelGGL(conv_b2b_s1_kernel, dim3(ceil_div(M, 128)), dim3(512), lds, s, p);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
 }
 
 int launch_conv(const ConvParams &p, hipStream_t s)
 {
-    // every kernel addresses its tensors through 32-bit buffer descriptors and offsets: inputs, outputs (M x Cout, M x ldy) and,
-    // for a back-to-back pair, conv1's output (M x n1) must each stay below 4 GiB -- checked before ANY path is chosen
-    // (round-3 advisor finding: the pair branch used to return before the guard; B >= 328 at the stage 1 -> 2 boundary wrapped)
-    {
-        const size_t Mo = (size_t)p.B * p.Ho * p.Wo, lim = 0xfffffff0ull;
-        const size_t in1 = (size_t)p.B * p.H * p.W * (p.ldx ? p.ldx : p.Cin) * 2, in2 = (size_t)p.B * p.H2 * p.W2 * p.Cin2 * 2;
-        const size_t out = Mo * (size_t)std::max(p.Cout, p.ldy) * (p.yf ? 4 : 2), out1 = p.w1 ? Mo * (size_t)p.n1 * 2 : 0;
-        if (in1 >= lim || in2 >= lim || out >= lim || out1 >= lim) {
-            set_error("conv: a tensor of %zu bytes exceeds the 4 GiB buffer-addressing limit; lower max_batch_size",
-                      std::max(std::max(in1, in2), std::max(out, out1)));
-            return RFD_ERR_CAPACITY;
-        }
-    }
-    if (p.w1) {
-        // conv3 of a dim-match unit + the next unit's conv1 (OP_B2B beyond stage 1).  One persistent kernel where pw_stream
-        // itself would run (force_tile 7 / 1 / 2 and small batches: two launches; bit-identical either way).
-        const int M1 = p.B * p.Ho * p.Wo;
-        // two shapes: (i) a middle unit of stage 2: 128 -> 512, raw sum out, conv1 512 -> 128 on relu(BN(raw));
-        //             (ii) the last unit of stage 1: 64 -> 256, activated output only, conv1 256 -> 128 of stage 2's first unit on it
-        const bool act_out = !p.y && p.y2;
-        const bool s3 = !act_out && p.Cin == 256 && p.Cout == 1024 && p.y && !p.y2 && p.ldy == p.Cout; // stage 3's middle units: pw_pair_kernel only
-        const bool b23 = act_out && p.Cin == 128 && p.Cout == 512 && p.n1 == 256;                     // stage 2 -> 3 boundary: pw_pair_kernel only
-        const bool shape = s3 || b23 || (act_out ? (p.Cin == 64 && p.Cout == 256 && p.n1 == 128) : (p.Cin == 128 && p.Cout == 512 && p.n1 == 128 && p.y && !p.y2 && p.ldy == p.Cout));
-        const int N1 = p.n1;
-        // the first unit of stage 2: conv3 128 -> 512 with the 1x1 stride-2 shortcut 256 -> 512 as second K segment, no residual
-        const bool u1 = !act_out && p.Cin == 128 && p.Cin2 == 256 && p.stride2 == 2 && p.Cout == 512 && p.n1 == 128 && !p.res && p.y && !p.y2 && p.ldy == p.Cout && p.bias2;
-        const bool fuse = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && (u1 || (shape && p.Cin2 == 0 && p.res)) && !p.in_scale &&
-                          !p.res_up2 && !p.res_post && !p.relu && !p.yf && p.ldx == p.Cin && p.x_coff == 0 &&
-                          p.y_coff == 0 && p.y_split >= p.Cout && p.n_valid >= p.Cout &&
-                          (p.force_tile == 6 || p.force_tile == 16 || (p.force_tile == 0 && M1 >= 128 * 128));
-        // the pair as its two convolutions, as the small-batch rule above already runs it
-        ConvParams a = p;
-        a.w1 = nullptr; a.bias1 = nullptr; a.t1 = nullptr;
-        ConvParams q;
-        memset(&q, 0, sizeof q);
-        q.x = act_out ? p.y2 : p.y; q.w = p.w1; q.bias = p.bias1; q.zero = p.zero;
-        if (!act_out) { q.in_scale = p.scale2; q.in_shift = p.shift2; }
-        q.y = p.t1;
-        q.B = p.B; q.H = q.Ho = p.Ho; q.W = q.Wo = p.Wo; q.Cin = p.Cout; q.Cout = N1;
-        q.KH = q.KW = 1; q.stride = 1; q.pad = 0;
-        q.ldx = p.Cout; q.ldy = N1; q.y_split = 1 << 30; q.n_valid = 1 << 30; q.relu = 1;
-        q.force_tile = p.force_tile == 16 ? 0 : p.force_tile; q.co_running = p.co_running;
-        if (p.latency) q.fail = p.fail;
-        q.latency = p.latency; q.sk_ws = p.sk_ws; q.sk_cnt = p.sk_cnt; q.sk_ws_bytes = p.sk_ws_bytes; q.sk_cnt_n = p.sk_cnt_n; // one after the other on one stream: shared
-        // latency schedule: a pair one of whose convolutions is split never runs fused, whatever the batch (the fused kernel sums in
-        // the throughput order; a frame's bits must not depend on the size of the latency pass)
-        SplitKPlan skp;
-        const bool split_pair = conv_splitk_wants(a, &skp) || conv_splitk_wants(q, &skp);
-        if (fuse && !split_pair && (const char *)p.w1 > (const char *)p.w && (size_t)((const char *)p.w1 - (const char *)p.w) < (1u << 30)) {
-            if (u1) return launch_pw_pair<2, 1, false, 4>(p, s);
-            if (s3) {
-                if (p.n1 != 256) { set_error("conv pair: stage-3 form instantiated for n1 = 256, got %d", p.n1); return RFD_ERR_INVALID_ARG; }
-                return launch_pw_pair<4, 2, false>(p, s);
-            }
-            if (b23) return launch_pw_pair<2, 2, true>(p, s);
-            // the stage 1 -> 2 boundary: both filter banks (96 KiB) resident in LDS, barrier-free
-            if (act_out) return launch_pw_pair<1, 1, true, 0, 2>(p, s);
-            return launch_pw_b2b<2, false>(p, s); // stage 2's middle units
-        }
-        RFD_TRY(launch_conv(a, s));
-        return launch_conv(q, s);
-    }
-    if (p.Cin % 64 != 0 || p.Cin2 % 64 != 0 || p.Cout % 32 != 0) {
-        set_error("conv: Cin=%d must be a multiple of 64 and Cout=%d of 32", p.Cin, p.Cout);
-        return RFD_ERR_INVALID_ARG;
-    }
-    if (p.in_scale && (p.KH != 1 || p.KW != 1 || p.pad != 0 || p.Cin > 2048)) {
-        set_error("conv: the input affine is only defined for un-padded 1x1 convs with Cin <= 2048");
-        return RFD_ERR_INVALID_ARG;
-    }
-    if ((size_t)p.B * p.H * p.W * p.ldx * 2 >= 0xfffffff0ull || (size_t)p.B * p.H2 * p.W2 * p.Cin2 * 2 >= 0xfffffff0ull) {
-        set_error("conv: an input tensor of %zu bytes exceeds the 4 GiB buffer-addressing limit; lower max_batch_size",
-                  (size_t)p.B * p.H * p.W * p.Cin * 2);
-        return RFD_ERR_CAPACITY;
-    }
-    {   // latency schedule (rfd_config.schedule; a forced tile wins): the K range as segments over several workgroups
-        SplitKPlan skp;
-        if (conv_splitk_wants(p, &skp)) return launch_conv_splitk(p, s);
-    }
-    const int M = p.B * p.Ho * p.Wo;
-    const int nk = (p.KH * p.KW * p.Cin + p.Cin2) / 64;
-    // layer shapes conv3x3_halo_kernel accepts (any size, any force_tile): all their kernels accumulate chunk-major
-    const bool halo_shape = p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && p.Cin2 == 0 && !p.in_scale && !p.res && !p.y2 &&
-                            !p.yf && p.y && p.Ho == p.H && p.Wo == p.W && p.n_valid >= p.Cout && p.Cin % 128 == 0 &&
-                            (p.Cout % 128 == 0 || p.Cout == 192) && p.Cout <= 512 && (p.y_split >= p.Cout || p.y_split % 8 == 0) &&
-                            (p.W % 16 == 0 || p.W == 40);
-    if (halo_shape && !p.k_chunk_major) {
-        ConvParams q = p;
-        q.k_chunk_major = 1;
-        return launch_conv(q, s);
-    }
-    // force_tile 18: the generic 128 x 128 tile with EIGHT waves (32 x 64 wave tiles, two waves per SIMD from one workgroup): for
-    // the small-M layers whose grid gives a CU a single workgroup (A/B; bit-identical, same K order)
-    if (p.force_tile == 18 && p.Cout % 128 == 0 && !p.in_scale) return launch_conv_cfg<128, 128, 4, 2, 3>(p, s);
-    // force_tile 19: the merged-kx 3x3 kernel in its older four-wave form (64 x 64 wave tiles)
-    if (p.force_tile == 19 && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && p.Cin2 == 0 && !p.in_scale && p.Ho == p.H && p.Wo == p.W &&
-        p.W >= 3 && p.Cout % 128 == 0)
-        return launch_conv3x3_kx<128, 2, 2>(p, s);
-    // wave-specialised loader / consumer ring (kernels_ring.hip): force_tile 17 = wherever the shape allows (tests, A/B)
-    if (p.force_tile == 17 && conv_ring_supports(p, nullptr)) return launch_conv_ring(p, s);
-    {   // The ring runs the small-M, long-K layers it measured faster on, in its generic form: stage-4 conv1 (2048 -> 512: 27.3 vs
-        // 28.8 us per 16 images in isolation) and the stride-2 conv2 of stage 4's first unit (48.6 vs 52.7 us); end to end +1.1 %
-        // in two alternating A/B pairs on one box (7 798 / 7 734 vs 7 716 / 7 650 img/s; profiles/r04_ab_ring_env.jsonl).  Every
-        // other layer stays with the kernels above (the ring is slower there: DESIGN_AB_RECORD.md round 4).  Bit-identical either
-        // way (tests/test_ring_gpu.py).  RFD_CONV_RING=0 switches it off.
-        static const bool ring_on = [] { const char *e = getenv("RFD_CONV_RING"); return !e || atoi(e) >= 1; }();
-        bool kx3 = false;
-        if (ring_on && p.force_tile == 0 && conv_ring_supports(p, &kx3) && !kx3 && p.B * p.Ho * p.Wo <= 128 * 64 &&
-            p.KH * p.KW * p.Cin + p.Cin2 >= 2048 && p.Cout == 512)
-            return launch_conv_ring(p, s);
-    }
-    // short-K, wide-N pointwise layers with a residual: persistent X-stationary streaming kernel (force_tile 1 / 2 / 5 opt out)
-    // (one output: the raw sum or, at the end of a stage, the activated one; K = 64 only the latter -- the forms instantiated)
-    const bool pw_ok = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.Cin2 == 0 && !p.in_scale && !p.yf && p.res &&
-                       !(p.y && p.y2) && !(p.y && p.Cin == 64) &&
-                       !p.res_up2 && !p.res_post && p.ldx == p.Cin && p.x_coff == 0 && p.Cout % 128 == 0 && p.Cout >= 4 * p.Cin &&
-                       p.y_coff == 0 && p.y_split >= p.Cout && p.n_valid >= p.Cout && (!p.y || p.ldy == p.Cout) &&
-                       (p.Cin == 64 || p.Cin == 128 || p.Cin == 256) && (p.force_tile == 0 || p.force_tile == 6 || p.force_tile == 8 ||
-                        (p.force_tile == 10 && p.Cin == 128) || (p.force_tile == 11 && p.Cin == 256));
-    // a persistent workgroup walks all N / 128 chunks of its tiles one after the other: below ~half a GPU of tiles (small
-    // batches; B = 1: 13 tiles at 40 x 40) the generic kernel's tiles_m x N / 128 independent workgroups are faster
-    if (pw_ok && (p.y || p.y2) && ((p.Cout >> 7) & 1) == 0 && p.Cout <= 1024 && (M >= 128 * 128 || p.force_tile == 6)) return p.Cin == 64 ? launch_pw_stream_nk<1>(p, s) : (p.Cin == 128 ? launch_pw_stream_nk<2>(p, s) : launch_pw_stream_nk<4>(p, s));
-    // wide pointwise GEMMs that pw_stream does not take (conv3 + fused shortcut of the down-sampling units, stage-4 conv3, and
-    // N >= 512 conv1s, where the 256 x 256 tile measured faster than pw_gemm's 256 x 128: 32.8 vs 39.3 us for 1024 -> 512 at
-    // 40 x 40 x 16): persistent 256 x 256 tiles (force_tile 12: whatever the size; 1 / 2 / 7 opt out)
-    const bool pww_ok = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && !p.in_scale && !p.yf && (p.y || p.y2) &&
-                        (!p.res || (!p.res_up2 && !p.res_post)) && p.Cin2 % 64 == 0 && p.Cin + p.Cin2 >= 384 && p.Cout % 256 == 0 &&
-                        p.Cout >= 512 && p.Cout <= 2048 && p.y_split >= p.Cout && p.n_valid >= p.Cout && M % 8 == 0 &&
-                        (p.force_tile == 0 || p.force_tile == 6 || p.force_tile == 12);
-    if (pww_ok && (p.force_tile != 0 || ceil_div(M, 256) * (p.Cout / 256) >= 150)) return launch_pw_wide(p, s);
-    // long-K pointwise layers without a residual (conv1 of the units): persistent activation-streaming kernel
-    // (force_tile 15: whatever the size; 1 / 2 / 7 opt out)
-    const bool pwg_ok = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.Cin2 == 0 && !p.y2 && !p.yf && p.Ho == p.H && p.Wo == p.W &&
-                        p.y && p.Cin % 128 == 0 && p.Cin >= 256 && p.Cin <= 2048 && p.Cout % 128 == 0 && p.Cout <= 1024 && p.y_split >= p.Cout &&
-                        p.n_valid >= p.Cout && M % 8 == 0 && (p.force_tile == 0 || p.force_tile == 6 || p.force_tile == 15);
-    // (with a residual -- the FPN laterals -- only from 400 items: 52 vs 57 us for 512 -> 256 at 80 x 80 x 16, but 27 vs 25 us for the
-    //  200 items of 1024 -> 256 at 40 x 40)
-    if (pwg_ok && (p.force_tile != 0 || ceil_div(M, 256) * (p.Cout / 128) >= (p.res ? 400 : 150))) return launch_pw_gemm(p, s);
-    // 64 -> 64 3x3: filter bank resident in LDS, halo tile staged once for all nine taps (force_tile 1 / 2 / 7 opt out)
-    const bool c64_ok = p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && p.Cin == 64 && p.Cout == 64 && p.Cin2 == 0 && !p.in_scale &&
-                        !p.res && !p.y2 && !p.yf && p.y && p.Ho == p.H && p.Wo == p.W && p.y_split >= 64 && p.n_valid >= 64 &&
-                        (p.force_tile == 0 || p.force_tile == 6 || p.force_tile == 9);
-    if (c64_ok && (M >= 96 * 256 || p.force_tile == 6)) return launch_conv3x3_c64(p, s); // >= 96 tiles of 16 x 16 pixels
-    // Cin >= 128 3x3: persistent halo-tile kernel; work items of 128 / 192 / 256 output channels (TN = 4 / 6 / 8).  Every 3x3
-    // kernel accumulates in the same order, so the choice changes no bit of the result.
-    // force_tile 13: smallest item, 14: largest item, whatever the size; 1 / 2 / 7 opt out
-    const bool halo_ok = halo_shape && (p.force_tile == 0 || p.force_tile == 6 || p.force_tile == 13 || p.force_tile == 14);
-    if (halo_ok) {
-        const int tiles = p.W == 40 ? p.B * ceil_div(p.H, 6) : p.B * (p.W / 16) * ceil_div(p.H, 16);
-        const bool forced = p.force_tile != 0;
-        if (p.Cout == 192) {
-            if (forced || tiles >= 100) return p.W == 40 ? launch_conv3x3_halo<40, 6, 6>(p, s) : launch_conv3x3_halo<16, 16, 6>(p, s);
-        } else {
-            // (the 256-channel item is not instantiated for the 40-wide row tile: its per-pixel address registers next to 128
-            //  accumulators spill to scratch, and scratch reloads share the DMA counters; 128-channel items measured 5 % slower
-            //  there at B = 32 and are what the size rule picks at B = 16 anyway)
-            const int items8 = p.Cout % 256 == 0 && p.W != 40 ? tiles * (p.Cout / 256) : 0, items4 = tiles * (p.Cout / 128);
-            // 256-channel items read the halo half as often, 128-channel items fill the last round of workgroups better:
-            // 256 unless its share of busy CU-rounds is clearly lower (B = 32, 80 x 80: 800 items = 3.1 rounds vs 1600 = 6.25)
-            auto fill = [](int n) { return (double)n / (ceil_div(n, 256) * 256); };
-            const bool use8 = p.force_tile == 14 ? items8 > 0 : (p.force_tile == 13 ? false : items8 >= 200 && fill(items8) >= fill(items4) - 0.05);
-            if (use8) return launch_conv3x3_halo<16, 16, 8>(p, s);
-            if (forced || items4 >= 200) return p.W == 40 ? launch_conv3x3_halo<40, 6, 4>(p, s) : launch_conv3x3_halo<16, 16, 4>(p, s);
-        }
-    }
-    const bool kx_ok = p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && p.Cin2 == 0 && !p.in_scale && p.Ho == p.H &&
-                       p.Wo == p.W && p.W >= 3 && p.force_tile != 1 && p.force_tile != 2;
-    // Eight waves (32 x 64 wave tiles) since round 4: the layers that come here have small grids (stage-4 conv2: 200 tiles on 256
-    // CUs), so a CU mostly holds ONE workgroup, and with four waves that is one wave per SIMD -- nothing covers its barrier, drain
-    // and fragment-read latencies (1 725 cycles per 32-MFMA step).  Two waves per SIMD from the same workgroup: 53.8 -> 46.1 us
-    // (stage-4 conv2, 16 images), 73 -> 65 us at 32 images where two four-wave workgroups already shared a CU, 30.5 -> 27.4 us
-    // (SSH 80 x 80 context conv); same K order, bit-identical (force_tile 19: the four-wave form).
-    if (kx_ok && p.Cout % 128 == 0) return launch_conv3x3_kx<128, 4, 2>(p, s);
-    // (with BN = 64 the merged-kx kernel measured 7 % slower than the generic 128x64 tile at 3 workgroups / CU)
-    // Per-layer tile choice for a chain that has the GPU to itself (unsplit passes, B < 16; tools/tile_sweep.py): the
-    // 128x64 tile (3 workgroups per CU, twice the grid) wins by 5-28 % where the 128x128 grid cannot give every CU a
-    // workgroup, and by 5-11 % on the 1x1 layers whose FLOPs per byte of activation traffic are far below the machine
-    // balance (more loads in flight per CU).  With a second chain co-running (batch split) the other chain already
-    // fills those gaps and the same choice measured 2.5 % SLOWER end to end, so it is not applied there.
-    const long long n128 = (long long)ceil_div(M, 128) * (p.Cout / 128);
-    const double act_bytes = 2.0 * ((double)(p.KH * p.KW * p.Cin + p.Cin2) / (p.stride * p.stride) +
-                                    (double)p.Cout * (1 + (p.res ? 1 : 0) + (p.y && p.y2 ? 1 : 0)));
-    const double flop_per_byte = 2.0 * (p.KH * p.KW * p.Cin + p.Cin2) * p.Cout / act_bytes;
-    const bool prefer_small = p.force_tile == 0 && !p.co_running && (n128 <= 256 || (p.KH == 1 && flop_per_byte < 110.0));
-    if (p.Cout % 128 == 0 && p.force_tile != 4 && !prefer_small) {
-        // The 8-wave 256x128 tile with a 3-slot ring (1 workgroup per CU) measured 5-13 % SLOWER than two
-        // co-resident 128x128 workgroups on every layer of this network (profiles/): opt-in only.
-        (void)M; (void)nk;
-        if (p.force_tile == 2) return launch_conv_cfg<256, 128, 4, 2, 3>(p, s);
-        // the 80 KiB ring leaves no room for the input-affine table next to a second workgroup
-        if (p.force_tile == 1 || p.in_scale) return launch_conv_cfg<128, 128, 2, 2, 2>(p, s);
-        // eight waves on the 128 x 128 tile (round 4; as in the merged-kx kernel above): 46.5 vs 49.5 us and 39.2 vs 41.0 us on the
-        // stride-2 3x3 layers, 24.8 vs 26.2 us on the 1024 -> 256 lateral; the K = 2048 lateral ties (26.5 vs 26.0) and keeps four
-        if (!(p.KH == 1 && p.Cin + p.Cin2 >= 2048)) return launch_conv_cfg<128, 128, 4, 2, 3>(p, s);
-        return launch_conv_cfg<128, 128, 2, 2, 3>(p, s);
-    }
-    // fused SSH pair (conv1 + ctx1 along N): eight waves (32 x 96 wave tiles) since round 4 -- these layers have at most 50 tiles
-    // below the halo kernel's threshold, one workgroup per CU, and the four-wave form needs 284 registers (one wave per SIMD)
-    if (p.Cout % 192 == 0 && p.Cout % 128 != 0) return (p.force_tile == 1 || p.force_tile == 19) ? launch_conv_cfg<128, 192, 2, 2, 2>(p, s) : launch_conv_cfg<128, 192, 4, 2, 2>(p, s);
-    // 128x64: the 2-slot ring keeps 3 workgroups per CU, which measured faster than a deeper ring at 2
-    if (p.Cout % 64 == 0) {
-        if (p.force_tile == 3) return launch_conv_cfg<256, 64, 4, 1, 2>(p, s); // 64x64 wave tiles, 2 workgroups / CU
-        return launch_conv_cfg<128, 64, 4, 1, 2>(p, s);
-    }
-    return launch_conv_cfg<128, 32, 4, 1, 2>(p, s);
+    ConvPlan plan;
+    RFD_TRY(choose_conv(p, bank_behind(p.w, p.w1), &plan));
+    for (int i = 0; i < plan.steps; ++i) RFD_TRY(run_conv_step(plan.step[i], s));
+    return RFD_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3010,7 +2804,7 @@ int launch_conv(const ConvParams &p, hipStream_t s)
 // reaches HBM (840 MB per 32-image batch saved: one write, one read).
 // Out-of-image conv pixels (pool padding) are stored as 0: exact, because every real value is >= 0 (ReLU).
 // ------------------------------------------------------------------------------------------------
-constexpr int kStemPH = 4, kStemPW = 16;                       // pooled tile
+// (kStemPH x kStemPW = 4 x 16: the pooled tile, kernels.h)
 constexpr int kStemCR = 2 * kStemPH + 1, kStemCC = 2 * kStemPW + 1; // conv pixels: 9 x 33
 constexpr int kStemIR = 2 * kStemCR + 5, kStemIC = 2 * kStemCC + 5; // input patch: 23 x 71
 constexpr int kStemIP = 72;                                    // input row pitch in pixels (8 B each)
@@ -3352,7 +3146,7 @@ __global__ void __launch_bounds__(256) stem_persistent_kernel(const bf16_t *__re
 
 
 int launch_stem(const bf16_t *x4, const bf16_t *w, const float *bias, const float *scale, const float *shift,
-                bf16_t *y, int B, int H, int W, hipStream_t s, const bf16_t *w1, const float *bias1, bf16_t *t1, bool *fused)
+                bf16_t *y, int B, int H, int W, hipStream_t s, int force_tile, const bf16_t *w1, const float *bias1, bf16_t *t1, bool *fused)
 {
     if (fused) *fused = false;
     if ((H | W) & 3) {
@@ -3362,26 +3156,20 @@ int launch_stem(const bf16_t *x4, const bf16_t *w, const float *bias, const floa
     const int Hp = H / 4, Wp = W / 4;
     const int tiles_h = ceil_div(Hp, kStemPH), tiles_w = ceil_div(Wp, kStemPW);
     const int ntiles = B * tiles_h * tiles_w;
-    // persistent form from 4 tiles per workgroup slot (2 workgroups per CU by LDS): weights stay in registers, the next patch is
-    // prefetched
-    const int slots = 2 * device_cus();
-    if (ntiles >= 4 * slots) {
-        const int per = ceil_div(ntiles, slots), grid = ceil_div(ntiles, per);
-        if (w1 && t1 && fused) { // the first unit's conv1 on the pooled tile (Network::run offers it when the next op is that conv)
-            *fused = true;
-            if (note_launch("stem_persistent_kernel<true>")) return RFD_OK;
-            hipLaunchKernelGGL(stem_persistent_kernel<true>, dim3((unsigned)grid), dim3(256), 0, s, x4, w, bias, scale, shift, y, H, W, tiles_w, tiles_h, ntiles, per, w1, bias1, t1);
-            RFD_HIP(hipGetLastError());
-            return RFD_OK;
-        }
-        if (note_launch("stem_persistent_kernel<false>")) return RFD_OK;
+    const int slots = 2 * device_cus(); // 2 workgroups per CU by LDS
+    const int per = ceil_div(ntiles, slots), grid = ceil_div(ntiles, per);
+    switch (choose_stem(B, H, W, w1 && t1 && fused, force_tile, device_cus())) {
+    case K_STEM_PERSISTENT_CONV1:
+        *fused = true;
+        hipLaunchKernelGGL(stem_persistent_kernel<true>, dim3((unsigned)grid), dim3(256), 0, s, x4, w, bias, scale, shift, y, H, W, tiles_w, tiles_h, ntiles, per, w1, bias1, t1);
+        break;
+    case K_STEM_PERSISTENT:
         hipLaunchKernelGGL(stem_persistent_kernel<false>, dim3((unsigned)grid), dim3(256), 0, s, x4, w, bias, scale, shift, y, H, W, tiles_w, tiles_h, ntiles, per, nullptr, nullptr, nullptr);
-        RFD_HIP(hipGetLastError());
-        return RFD_OK;
+        break;
+    default:
+        hipLaunchKernelGGL(stem_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, x4, w, bias, scale, shift, y,
+                           H, W, tiles_w, tiles_h);
     }
-    if (note_launch("stem_kernel")) return RFD_OK;
-    hipLaunchKernelGGL(stem_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, x4, w, bias, scale, shift, y,
-                       H, W, tiles_w, tiles_h);
     RFD_HIP(hipGetLastError());
     return RFD_OK;
 }
@@ -3439,7 +3227,6 @@ int launch_first3x3(const bf16_t *x4, const bf16_t *w, const float *bias, bf16_t
 {
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     const long long total = (long long)B * Ho * Wo;
-    if (note_launch("first3x3_kernel")) return RFD_OK;
     hipLaunchKernelGGL(first3x3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x4,
                        reinterpret_cast<const uint32_t *>(w), bias, y, B, H, W, Ho, Wo, Cd);
     RFD_HIP(hipGetLastError());
@@ -3493,7 +3280,6 @@ int launch_dwconv3x3(const bf16_t *x, const bf16_t *w, const float *bias, bf16_t
 {
     const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
     const long long total = (long long)B * Ho * Wo * (C / 8);
-    if (note_launch("dwconv3x3_kernel")) return RFD_OK;
     hipLaunchKernelGGL(dwconv3x3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, w, bias, y, B, H, W,
                        C, Ho, Wo, stride);
     RFD_HIP(hipGetLastError());

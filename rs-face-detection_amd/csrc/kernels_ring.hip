@@ -403,17 +403,6 @@ __global__ void __launch_bounds__(512) conv_ring_kernel(const ConvParams p)
     __builtin_amdgcn_endpgm(); // (as the loader path: keeps the two roles disjoint in the emitted control-flow graph)
 }
 
-// shapes the ring kernel accepts (launch_conv asks before routing a layer here)
-bool conv_ring_supports(const ConvParams &p, bool *kx3)
-{
-    if (p.Cout % 128 != 0 || p.Cin % 64 != 0 || p.Cin2 % 64 != 0 || p.w1) return false;
-    const bool k3 = p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && p.Cin2 == 0 && !p.in_scale && p.Ho == p.H && p.Wo == p.W &&
-                    p.W >= 3; // launch_conv's kx_ok: these layers accumulate chunk-major in every kernel that runs them
-    if (kx3) *kx3 = k3;
-    if (p.in_scale && (p.Cin2 || (size_t)2 * p.KH * p.KW * p.Cin * sizeof(float) > 16 * 1024)) return false;
-    return true;
-}
-
 int launch_conv_ring(const ConvParams &p, hipStream_t s)
 {
     bool kx3 = false;
@@ -427,7 +416,6 @@ int launch_conv_ring(const ConvParams &p, hipStream_t s)
     if (!kx3 && p.k_chunk_major) { set_error("conv_ring: the generic form has no chunk-major K order"); return RFD_ERR_INVALID_ARG; }
     auto kern = kx3 ? conv_ring_kernel<true> : conv_ring_kernel<false>;
     static DynLdsOnce once[2];
-    if (note_launch("conv_ring_kernel<%s>", kx3 ? "true" : "false")) return RFD_OK;
     RFD_TRY(once[kx3].ensure(reinterpret_cast<const void *>(kern), (int)lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, p);
     RFD_HIP(hipGetLastError());

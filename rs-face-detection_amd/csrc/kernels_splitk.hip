@@ -27,42 +27,7 @@
 
 namespace rfd {
 
-// ---- selection: pure functions of the layer shape and the pixels of one image ----
-// Split when the throughput schedule's 128 x 128 tiling of ONE image would give at most kSplitKMaxTiles128 workgroups (an eighth
-// of the 256 CUs) and K has at least kSplitKMinSteps steps of 64.  Both limits come from the per-op table at one image
-// (profiles/latency_schedule_per_op_b1.txt): with 4 <= nk < 16 (heads, stage-4 conv3, the 64 -> 64 SSH
-// context convs) or 50-64 tiles (the 80 x 80 level, stage 2, stage-4 conv3 and the first stage-4 conv1) the slab round trip costs
-// more than the idle CUs give back -- those layers measured slower split and keep their throughput kernels.
-constexpr int kSplitKMaxTiles128 = 32;
-constexpr int kSplitKMinSteps = 16;
-
-int conv_splitk_segments(int nk)
-{
-    if (nk < kSplitKMinSteps) return 1;
-    return std::min(nk / 8, kSplitKMaxSegments); // segments of 8+ K steps: 2 .. 8
-}
-
-bool conv_splitk_plan(int K, int Cout, int HoWo, int B, SplitKPlan *pl)
-{
-    if (K % 64 != 0 || Cout % 64 != 0 || HoWo < 1 || B < 1) return false; // 64 x 64 tiles
-    const int nk = K / 64;
-    const long long tiles128 = (long long)ceil_div(HoWo, 128) * ceil_div(Cout, 128);
-    if (nk < kSplitKMinSteps || tiles128 > kSplitKMaxTiles128) return false;
-    pl->S = conv_splitk_segments(nk);
-    pl->bm = 64;
-    pl->bn = 64;
-    pl->tiles = ceil_div(B * HoWo, pl->bm) * (Cout / pl->bn);
-    pl->ws_bytes = (size_t)pl->tiles * pl->S * pl->bm * pl->bn * sizeof(float);
-    return true;
-}
-
-bool conv_splitk_wants(const ConvParams &p, SplitKPlan *pl)
-{
-    if (!p.latency || p.force_tile != 0 || p.co_running || p.w1) return false;
-    if (p.Cin % 64 != 0 || p.Cin2 % 64 != 0) return false;
-    return conv_splitk_plan(p.KH * p.KW * p.Cin + p.Cin2, p.Cout, p.Ho * p.Wo, p.B, pl);
-}
-
+// Selection (conv_splitk_plan, conv_splitk_wants): conv_select.hip.
 template <int BM, int BN, int WAVES_M, int WAVES_N>
 __global__ void __launch_bounds__(WAVES_M *WAVES_N * 64) conv_splitk_kernel(const ConvParams p, const int S)
 {
@@ -308,7 +273,6 @@ template <int BM, int BN, int WAVES_M, int WAVES_N> static int launch_splitk_cfg
     auto kern = conv_splitk_kernel<BM, BN, WAVES_M, WAVES_N>;
     static DynLdsOnce once;
     RFD_TRY(once.ensure(reinterpret_cast<const void *>(kern), (int)((size_t)(3 * BM + 2 * BN) * 64 * sizeof(bf16_t) + 16384)));
-    if (note_launch("conv_splitk_kernel<%d, %d, %d, %d>", BM, BN, WAVES_M, WAVES_N)) return RFD_OK;
     hipLaunchKernelGGL(kern, dim3(pl.tiles * pl.S), dim3(WAVES_M * WAVES_N * 64), lds, s, p, pl.S);
     RFD_HIP(hipGetLastError());
     return RFD_OK;
@@ -323,7 +287,7 @@ int launch_conv_splitk(const ConvParams &p, hipStream_t s)
         return RFD_ERR_INVALID_ARG;
     }
     // the workspace and the counters are sized at context creation from the same plan: a mismatch is a bug, never an out-of-range write
-    if (!launch_note().dry && (!p.sk_ws || !p.sk_cnt || pl.ws_bytes > p.sk_ws_bytes || pl.tiles > p.sk_cnt_n)) {
+    if (!p.sk_ws || !p.sk_cnt || pl.ws_bytes > p.sk_ws_bytes || pl.tiles > p.sk_cnt_n) {
         set_error("split-K conv: workspace of %zu bytes / %d counters, the layer needs %zu / %d", p.sk_ws_bytes, p.sk_cnt_n, pl.ws_bytes, pl.tiles);
         return RFD_ERR_CAPACITY;
     }

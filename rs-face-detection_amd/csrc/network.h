@@ -76,6 +76,25 @@ struct Graph {
     void plan();
 };
 
+// What one op of a pass launches with (Network::op_launch): parameters only.  Which kernel runs them is conv_select.hip's choice.
+struct OpLaunch {
+    int kind;         // OpKind
+    int force_tile;
+    bool b2b_s1;      // OP_B2B of stage 1: b2b; every other OP_B2B and OP_CONV: conv
+    ConvParams conv;
+    B2BParams b2b;
+    // OP_STEM, OP_FIRST, OP_DW
+    const bf16_t *x, *w;
+    const float *bias, *scale, *shift;
+    bf16_t *y;
+    int B, H, W, C, stride;
+    const bf16_t *w1; // OP_STEM: the conv behind it, offered for fusion into the stem kernel, or null
+    const float *bias1;
+    bf16_t *t1;
+};
+int launch_op(const OpLaunch &l, hipStream_t s, bool *fused); // *fused: the stem kernel ran the offered conv too
+int op_kernels(const OpLaunch &l, int cus, std::string *names, bool *fused);
+
 struct Network {
     Graph g;
     int max_batch = 0;
@@ -86,7 +105,7 @@ struct Network {
     int *d_fail = nullptr;    // device fault word of the owning context (bounded spins of the ring convolutions), or null
     std::vector<void *> d_buffers;
     bool profiling = false;
-    int force_tile = 0; // test hook: 0 heuristic, 1 = 128-row tiles only, 2 = 256x128 wherever Cout % 128 == 0
+    int force_tile = 0; // test hook: ConvTile (kernels.h)
     std::vector<hipEvent_t> ev; // 2 per op when profiling
     std::vector<float> op_ms;   // last profiled run
     int prof_first = 0, prof_last = -1; // op range of the last run
@@ -137,6 +156,9 @@ struct Network {
     std::vector<void *> d_alt;
     int head_parity = 0;
     int ensure_alt_heads();
+    void op_launch(int i, int B, int batch_off, int part, bool offer_conv1, OpLaunch *out) const;
+    int op_kernel_names(int n, int op, int cus, std::string *out) const; // nothing is launched
+    int plan_splitk();
     int run(int B, hipStream_t s, int first_op = 0, int last_op = -1, int batch_off = 0, int part = 0);
     int run_split(int B, hipStream_t s); // whole pass; splits the batch over several streams when it pays
     int split_body(int B, hipStream_t s);

@@ -399,6 +399,39 @@ double Graph::macs_per_image() const
 // ------------------------------------------------------------------------------------------------
 // Network
 // ------------------------------------------------------------------------------------------------
+// latency schedule: the split-K workspace per stream and the arrival counters per op, from the graph alone; returns the counters of
+// all ops together
+int Network::plan_splitk()
+{
+    // the same plan launch_conv_splitk() makes, at the largest latency pass: workspace per stream, counters per op
+    const int Bl = std::min(max_batch, (int)RFD_LATENCY_MAX_BATCH);
+    sk_cnt_off.assign(g.ops.size(), 0);
+    sk_cnt_n.assign(g.ops.size(), 0);
+    int cnt_total = 0;
+    for (size_t i = 0; i < g.ops.size(); ++i) {
+        const Op &o = g.ops[i];
+        if (o.kind != OP_CONV && o.kind != OP_B2B) continue;
+        const Layer &L = g.layers[o.layer];
+        const int tout = o.out >= 0 ? o.out : (o.out2 >= 0 ? o.out2 : o.outf);
+        const int HoWo = g.tensors[tout].H * g.tensors[tout].W;
+        const int cout = L.cout_d + (o.layer_n2 >= 0 ? g.layers[o.layer_n2].cout_d : 0);
+        const int K = L.kh * L.kw * L.cin_d + (o.layer2 >= 0 ? g.layers[o.layer2].cin_d : 0);
+        SplitKPlan pl;
+        const int br = std::min(std::max(o.branch, 0), 2);
+        if (L.cin_d % 64 == 0 && conv_splitk_plan(K, cout, HoWo, Bl, &pl)) {
+            sk_ws_bytes[br] = std::max(sk_ws_bytes[br], pl.ws_bytes);
+            sk_cnt_n[i] = std::max(sk_cnt_n[i], pl.tiles);
+        }
+        if (o.kind == OP_B2B && conv_splitk_plan(cout, g.layers[o.layer_b].cout_d, HoWo, Bl, &pl)) { // the pair's conv1: 1x1 on this op's output
+            sk_ws_bytes[br] = std::max(sk_ws_bytes[br], pl.ws_bytes);
+            sk_cnt_n[i] = std::max(sk_cnt_n[i], pl.tiles);
+        }
+        sk_cnt_off[i] = cnt_total;
+        cnt_total += sk_cnt_n[i];
+    }
+    return cnt_total;
+}
+
 int Network::create(int backbone, int net_w, int net_h, int max_batch_, int precision_, int schedule_)
 {
     RFD_TRY(g.build(backbone, net_w, net_h));
@@ -406,32 +439,7 @@ int Network::create(int backbone, int net_w, int net_h, int max_batch_, int prec
     precision = precision_;
     schedule = schedule_;
     if (schedule == RFD_SCHEDULE_LATENCY) {
-        // the same plan launch_conv_splitk() makes, at the largest latency pass: workspace per stream, counters per op
-        const int Bl = std::min(max_batch, (int)RFD_LATENCY_MAX_BATCH);
-        sk_cnt_off.assign(g.ops.size(), 0);
-        sk_cnt_n.assign(g.ops.size(), 0);
-        int cnt_total = 0;
-        for (size_t i = 0; i < g.ops.size(); ++i) {
-            const Op &o = g.ops[i];
-            if (o.kind != OP_CONV && o.kind != OP_B2B) continue;
-            const Layer &L = g.layers[o.layer];
-            const int tout = o.out >= 0 ? o.out : (o.out2 >= 0 ? o.out2 : o.outf);
-            const int HoWo = g.tensors[tout].H * g.tensors[tout].W;
-            const int cout = L.cout_d + (o.layer_n2 >= 0 ? g.layers[o.layer_n2].cout_d : 0);
-            const int K = L.kh * L.kw * L.cin_d + (o.layer2 >= 0 ? g.layers[o.layer2].cin_d : 0);
-            SplitKPlan pl;
-            const int br = std::min(std::max(o.branch, 0), 2);
-            if (L.cin_d % 64 == 0 && conv_splitk_plan(K, cout, HoWo, Bl, &pl)) {
-                sk_ws_bytes[br] = std::max(sk_ws_bytes[br], pl.ws_bytes);
-                sk_cnt_n[i] = std::max(sk_cnt_n[i], pl.tiles);
-            }
-            if (o.kind == OP_B2B && conv_splitk_plan(cout, g.layers[o.layer_b].cout_d, HoWo, Bl, &pl)) { // the pair's conv1: 1x1 on this op's output
-                sk_ws_bytes[br] = std::max(sk_ws_bytes[br], pl.ws_bytes);
-                sk_cnt_n[i] = std::max(sk_cnt_n[i], pl.tiles);
-            }
-            sk_cnt_off[i] = cnt_total;
-            cnt_total += sk_cnt_n[i];
-        }
+        const int cnt_total = plan_splitk();
         for (int b = 0; b < 3; ++b)
             if (sk_ws_bytes[b]) RFD_HIP(hipMalloc((void **)&d_sk_ws[b], sk_ws_bytes[b]));
         RFD_HIP(hipMalloc((void **)&d_sk_cnt, (size_t)std::max(cnt_total, 1) * sizeof(unsigned)));
@@ -735,6 +743,168 @@ int Network::get_affine(int idx, float *scale, float *shift, hipStream_t s)
     return RFD_OK;
 }
 
+// The parameters op i of a chain of B images at image batch_off launches with -- nothing is launched and no kernel chosen here
+// (launch_op runs them; op_kernels asks conv_select.hip which kernels that takes).
+void Network::op_launch(int i, int B, int batch_off, int part, bool offer_conv1, OpLaunch *out) const
+{
+    const Op &o = g.ops[i];
+    const Layer &L = g.layers[o.layer];
+    const TensorDesc &tin = g.tensors[o.in];
+    OpLaunch &l = *out;
+    memset(&l, 0, sizeof l);
+    l.kind = o.kind;
+    l.force_tile = force_tile;
+    if (o.kind == OP_FIRST || o.kind == OP_DW || o.kind == OP_STEM) {
+        l.x = (const bf16_t *)tensor_ptr(o.in, batch_off);
+        l.w = d_w + L.w_off;
+        l.bias = d_b + L.b_off;
+        l.y = (bf16_t *)tensor_ptr(o.out, batch_off);
+        l.B = B; l.H = tin.H; l.W = tin.W;
+        l.C = o.kind == OP_FIRST ? g.tensors[o.out].C : tin.C;
+        l.stride = L.stride;
+    }
+    if (o.kind == OP_STEM) {
+        l.scale = d_b + g.b_total + L.a_off;
+        l.shift = d_b + g.b_total + L.a_off + L.cout_d;
+        // Peephole (round 4): when the next op of the range is the first unit's conv1 -- a plain 1x1 64 -> 64 conv + bias + ReLU
+        // on the stem's output -- the persistent stem kernel computes it on the pooled tile (choose_stem decides whether that
+        // form runs); the conv's own op is then skipped.  Bit-identical (tests/test_persistent_gpu.py).
+        if (offer_conv1 && i + 1 < (int)g.ops.size()) {
+            const Op &n = g.ops[i + 1];
+            const Layer &Ln = g.layers[n.layer];
+            const bool plain = n.kind == OP_CONV && n.in == o.out && Ln.kh == 1 && Ln.kw == 1 && Ln.stride == 1 && Ln.cin_d == 64 &&
+                               Ln.cout_d == 64 && n.relu && n.in_affine < 0 && n.res < 0 && n.layer2 < 0 && n.layer_n2 < 0 && n.out2 < 0 &&
+                               n.outf < 0 && n.out >= 0 && n.x_coff == 0 && n.y_coff == 0 && n.branch == o.branch &&
+                               g.tensors[n.out].C == 64 && n.n_valid >= 64 && n.y_split >= 64;
+            if (plain) { l.w1 = d_w + Ln.w_off; l.bias1 = d_b + Ln.b_off; l.t1 = (bf16_t *)tensor_ptr(n.out, batch_off); }
+        }
+    } else if (o.kind == OP_B2B && L.cin_d == 64 && g.layers[o.layer_b].cout_d == 64) {
+        l.b2b_s1 = true;
+        B2BParams &bp = l.b2b;
+        const Layer &Lb = g.layers[o.layer_b];
+        bp.x = (const bf16_t *)tensor_ptr(o.in, batch_off);
+        bp.w3 = d_w + L.w_off;
+        bp.bias3 = d_b + L.b_off;
+        if (o.layer2 >= 0) {
+            const Layer &L2 = g.layers[o.layer2];
+            bp.x2 = (const bf16_t *)tensor_ptr(o.in2, batch_off);
+            bp.bias3b = d_b + L2.b_off;
+            bp.Cin2 = L2.cin_d;
+        }
+        bp.res = o.res >= 0 ? (const bf16_t *)tensor_ptr(o.res, batch_off) : nullptr;
+        bp.scale = d_b + g.b_total + L.a_off;
+        bp.shift = d_b + g.b_total + L.a_off + L.cout_d;
+        bp.raw = (bf16_t *)tensor_ptr(o.out, batch_off);
+        bp.w1 = d_w + Lb.w_off;
+        bp.bias1 = d_b + Lb.b_off;
+        bp.t1 = (bf16_t *)tensor_ptr(o.out_b, batch_off);
+        bp.B = B; bp.H = tin.H; bp.W = tin.W; bp.Cin = L.cin_d;
+        bp.force_tile = force_tile;
+    } else if (o.kind == OP_CONV || o.kind == OP_B2B) {
+        const int tout = o.out >= 0 ? o.out : (o.out2 >= 0 ? o.out2 : o.outf);
+        ConvParams &p = l.conv;
+        p.x = (const bf16_t *)tensor_ptr(o.in, batch_off);
+        p.w = d_w + L.w_off;
+        p.bias = d_b + L.b_off;
+        p.zero = d_zero;
+        p.force_tile = force_tile;
+        p.co_running = co_running;
+        p.fail = d_fail;
+        if (latency_pass(B) && !co_running && batch_off == 0 && part == 0 && !sk_cnt_n.empty()) {
+            const int br = std::min(std::max(o.branch, 0), 2);
+            p.latency = 1;
+            p.sk_ws = d_sk_ws[br]; p.sk_ws_bytes = sk_ws_bytes[br];
+            p.sk_cnt = d_sk_cnt + sk_cnt_off[i]; p.sk_cnt_n = sk_cnt_n[i];
+        }
+        p.res = o.res >= 0 ? (const bf16_t *)tensor_ptr(o.res, batch_off) : nullptr;
+        if (o.layer2 >= 0) {
+            const Layer &L2 = g.layers[o.layer2];
+            const TensorDesc &t2 = g.tensors[o.in2];
+            p.x2 = (const bf16_t *)tensor_ptr(o.in2, batch_off);
+            p.bias2 = d_b + L2.b_off;
+            p.H2 = t2.H; p.W2 = t2.W; p.Cin2 = L2.cin_d; p.stride2 = L2.stride;
+        }
+        if (o.in_affine >= 0) {
+            const Layer &La = g.layers[o.in_affine];
+            p.in_scale = d_b + g.b_total + La.a_off;
+            p.in_shift = d_b + g.b_total + La.a_off + La.cout_d;
+        }
+        p.scale2 = d_b + g.b_total + L.a_off;
+        p.shift2 = d_b + g.b_total + L.a_off + L.cout_d;
+        p.y = o.out >= 0 ? (bf16_t *)tensor_ptr(o.out, batch_off) : nullptr;
+        p.y2 = o.out2 >= 0 ? (bf16_t *)tensor_ptr(o.out2, batch_off) : nullptr;
+        p.yf = o.outf >= 0 ? (float *)tensor_ptr(o.outf, batch_off) : nullptr;
+        p.B = B; p.H = tin.H; p.W = tin.W; p.Cin = L.cin_d;
+        p.Cout = L.cout_d + (o.layer_n2 >= 0 ? g.layers[o.layer_n2].cout_d : 0); // N-fused sibling: its rows follow
+        p.n_valid = o.n_valid;
+        p.ldx = tin.C; p.x_coff = o.x_coff; p.y_split = o.y_split; p.y_split_add = o.y_split_add;
+        p.KH = L.kh; p.KW = L.kw; p.stride = L.stride; p.pad = L.pad;
+        p.Ho = g.tensors[tout].H; p.Wo = g.tensors[tout].W;
+        p.ldy = o.out >= 0 ? g.tensors[o.out].C : p.Cout;
+        p.y_coff = o.y_coff;
+        p.relu = o.relu; p.res_up2 = o.res_up2; p.res_post = o.res_post; p.head_softmax = o.head_softmax;
+        if (o.kind == OP_B2B) { // beyond stage 1: the pair runs through launch_conv (a fused pair kernel, or two launches)
+            const Layer &Lb = g.layers[o.layer_b];
+            p.w1 = d_w + Lb.w_off;
+            p.bias1 = d_b + Lb.b_off;
+            p.t1 = (bf16_t *)tensor_ptr(o.out_b, batch_off);
+            p.n1 = Lb.cout_d;
+        }
+    }
+}
+
+int launch_op(const OpLaunch &l, hipStream_t s, bool *fused)
+{
+    *fused = false;
+    switch (l.kind) {
+    case OP_FIRST: return launch_first3x3(l.x, l.w, l.bias, l.y, l.B, l.H, l.W, l.C, s);
+    case OP_DW: return launch_dwconv3x3(l.x, l.w, l.bias, l.y, l.B, l.H, l.W, l.C, l.stride, s);
+    case OP_STEM: return launch_stem(l.x, l.w, l.bias, l.scale, l.shift, l.y, l.B, l.H, l.W, s, l.force_tile, l.w1, l.bias1, l.t1, l.w1 ? fused : nullptr);
+    default: return l.b2b_s1 ? launch_conv_b2b_s1(l.b2b, s) : launch_conv(l.conv, s);
+    }
+}
+
+// the kernels launch_op(l) runs, " + "-separated (display names, conv_kernel_name); *fused as launch_op reports it
+int op_kernels(const OpLaunch &l, int cus, std::string *names, bool *fused)
+{
+    *fused = false;
+    ConvPlan plan;
+    plan.steps = 1;
+    switch (l.kind) {
+    case OP_FIRST: plan.step[0].kernel = K_FIRST3X3; break;
+    case OP_DW: plan.step[0].kernel = K_DWCONV3X3; break;
+    case OP_STEM:
+        plan.step[0].kernel = choose_stem(l.B, l.H, l.W, l.w1 && l.t1, l.force_tile, cus);
+        *fused = plan.step[0].kernel == K_STEM_PERSISTENT_CONV1;
+        break;
+    default:
+        if (l.b2b_s1) choose_b2b_s1(l.b2b, bank_behind(l.b2b.w3, l.b2b.w1), &plan.step[0]);
+        else RFD_TRY(choose_conv(l.conv, bank_behind(l.conv.w, l.conv.w1), &plan));
+    }
+    names->clear();
+    for (int i = 0; i < plan.steps; ++i) {
+        if (i) *names += " + ";
+        *names += conv_kernel_name(plan.step[i].kernel);
+    }
+    return RFD_OK;
+}
+
+// rfd_debug_op_kernels' answer for op `op` of a chain of n images.  The stem and the conv behind it may run as ONE launch when a
+// pass runs them back to back: the stem is asked with the conv on offer, and the conv reports "(fused into ...)" when it was taken.
+int Network::op_kernel_names(int n, int op, int cus, std::string *out) const
+{
+    OpLaunch l;
+    bool fused = false;
+    if (op > 0 && g.ops[op - 1].kind == OP_STEM) {
+        std::string stem;
+        op_launch(op - 1, n, 0, 0, true, &l);
+        RFD_TRY(op_kernels(l, cus, &stem, &fused));
+        if (fused) { *out = "(fused into " + stem + ")"; return RFD_OK; }
+    }
+    op_launch(op, n, 0, 0, g.ops[op].kind == OP_STEM, &l);
+    return op_kernels(l, cus, out, &fused);
+}
+
 int Network::run(int B, hipStream_t s, int first_op, int last_op, int batch_off, int part)
 {
     if (!weights_ready) { set_error("network weights are not initialised (rfd_init_synthetic_weights / rfd_set_layer_weights)"); return RFD_ERR_STATE; }
@@ -767,8 +937,6 @@ int Network::run(int B, hipStream_t s, int first_op, int last_op, int batch_off,
 #endif
     for (int i = std::max(first_op, 0); i <= last_op; ++i) {
         const Op &o = g.ops[i];
-        const Layer &L = g.layers[o.layer];
-        const TensorDesc &tin = g.tensors[o.in];
         s = main_stream;
         if (!skip_ops.empty() && std::find(skip_ops.begin(), skip_ops.end(), i) != skip_ops.end()) {
             if (profiling) { RFD_HIP(hipEventRecord(ev[2 * i], s)); RFD_HIP(hipEventRecord(ev[2 * i + 1], s)); }
@@ -784,108 +952,13 @@ int Network::run(int B, hipStream_t s, int first_op, int last_op, int batch_off,
             s = side[part][bidx];
         }
         if (profiling) RFD_HIP(hipEventRecord(ev[2 * i], s));
-        if (o.kind == OP_FIRST) {
-            RFD_TRY(launch_first3x3((const bf16_t *)tensor_ptr(o.in, batch_off), d_w + L.w_off, d_b + L.b_off, (bf16_t *)tensor_ptr(o.out, batch_off), B,
-                                    tin.H, tin.W, g.tensors[o.out].C, s));
-        } else if (o.kind == OP_DW) {
-            RFD_TRY(launch_dwconv3x3((const bf16_t *)tensor_ptr(o.in, batch_off), d_w + L.w_off, d_b + L.b_off, (bf16_t *)tensor_ptr(o.out, batch_off), B,
-                                     tin.H, tin.W, tin.C, L.stride, s));
-        } else if (o.kind == OP_STEM) {
-            // Peephole (round 4): when the next op of the range is the first unit's conv1 -- a plain 1x1 64 -> 64 conv + bias + ReLU
-            // on the stem's output -- the persistent stem kernel computes it on the pooled tile (launch_stem decides whether that
-            // form runs); the conv's own op is then skipped.  Bit-identical (tests/test_persistent_gpu.py).
-            const bf16_t *w1 = nullptr; const float *b1 = nullptr; bf16_t *t1 = nullptr;
-            if (!profiling && force_tile == 0 && i + 1 <= last_op && skip_ops.empty()) {
-                const Op &n = g.ops[i + 1];
-                const Layer &Ln = g.layers[n.layer];
-                const bool plain = n.kind == OP_CONV && n.in == o.out && Ln.kh == 1 && Ln.kw == 1 && Ln.stride == 1 && Ln.cin_d == 64 &&
-                                   Ln.cout_d == 64 && n.relu && n.in_affine < 0 && n.res < 0 && n.layer2 < 0 && n.layer_n2 < 0 && n.out2 < 0 &&
-                                   n.outf < 0 && n.out >= 0 && n.x_coff == 0 && n.y_coff == 0 && n.branch == o.branch &&
-                                   g.tensors[n.out].C == 64 && n.n_valid >= 64 && n.y_split >= 64;
-                if (plain) { w1 = d_w + Ln.w_off; b1 = d_b + Ln.b_off; t1 = (bf16_t *)tensor_ptr(n.out, batch_off); }
-            }
-            bool fused = false;
-            RFD_TRY(launch_stem((const bf16_t *)tensor_ptr(o.in, batch_off), d_w + L.w_off, d_b + L.b_off, d_b + g.b_total + L.a_off,
-                                d_b + g.b_total + L.a_off + L.cout_d, (bf16_t *)tensor_ptr(o.out, batch_off), B, tin.H, tin.W, s, w1, b1, t1,
-                                w1 ? &fused : nullptr));
-            if (fused) ++i; // the conv ran inside the stem kernel
-        } else if (o.kind == OP_B2B && L.cin_d == 64 && g.layers[o.layer_b].cout_d == 64) {
-            const Layer &Lb = g.layers[o.layer_b];
-            B2BParams bp;
-            memset(&bp, 0, sizeof bp);
-            bp.x = (const bf16_t *)tensor_ptr(o.in, batch_off);
-            bp.w3 = d_w + L.w_off;
-            bp.bias3 = d_b + L.b_off;
-            if (o.layer2 >= 0) {
-                const Layer &L2 = g.layers[o.layer2];
-                bp.x2 = (const bf16_t *)tensor_ptr(o.in2, batch_off);
-                bp.bias3b = d_b + L2.b_off;
-                bp.Cin2 = L2.cin_d;
-            }
-            bp.res = o.res >= 0 ? (const bf16_t *)tensor_ptr(o.res, batch_off) : nullptr;
-            bp.scale = d_b + g.b_total + L.a_off;
-            bp.shift = d_b + g.b_total + L.a_off + L.cout_d;
-            bp.raw = (bf16_t *)tensor_ptr(o.out, batch_off);
-            bp.w1 = d_w + Lb.w_off;
-            bp.bias1 = d_b + Lb.b_off;
-            bp.t1 = (bf16_t *)tensor_ptr(o.out_b, batch_off);
-            bp.B = B; bp.H = tin.H; bp.W = tin.W; bp.Cin = L.cin_d;
-            bp.force_tile = force_tile;
-            RFD_TRY(launch_conv_b2b_s1(bp, s));
-        } else {
-            const int tout = o.out >= 0 ? o.out : (o.out2 >= 0 ? o.out2 : o.outf);
-            ConvParams p;
-            memset(&p, 0, sizeof p);
-            p.x = (const bf16_t *)tensor_ptr(o.in, batch_off);
-            p.w = d_w + L.w_off;
-            p.bias = d_b + L.b_off;
-            p.zero = d_zero;
-            p.force_tile = force_tile;
-            p.co_running = co_running;
-            p.fail = d_fail;
-            if (latency_pass(B) && !co_running && batch_off == 0 && part == 0 && !sk_cnt_n.empty()) {
-                const int br = std::min(std::max(o.branch, 0), 2);
-                p.latency = 1;
-                p.sk_ws = d_sk_ws[br]; p.sk_ws_bytes = sk_ws_bytes[br];
-                p.sk_cnt = d_sk_cnt + sk_cnt_off[i]; p.sk_cnt_n = sk_cnt_n[i];
-            }
-            p.res = o.res >= 0 ? (const bf16_t *)tensor_ptr(o.res, batch_off) : nullptr;
-            if (o.layer2 >= 0) {
-                const Layer &L2 = g.layers[o.layer2];
-                const TensorDesc &t2 = g.tensors[o.in2];
-                p.x2 = (const bf16_t *)tensor_ptr(o.in2, batch_off);
-                p.bias2 = d_b + L2.b_off;
-                p.H2 = t2.H; p.W2 = t2.W; p.Cin2 = L2.cin_d; p.stride2 = L2.stride;
-            }
-            if (o.in_affine >= 0) {
-                const Layer &La = g.layers[o.in_affine];
-                p.in_scale = d_b + g.b_total + La.a_off;
-                p.in_shift = d_b + g.b_total + La.a_off + La.cout_d;
-            }
-            p.scale2 = d_b + g.b_total + L.a_off;
-            p.shift2 = d_b + g.b_total + L.a_off + L.cout_d;
-            p.y = o.out >= 0 ? (bf16_t *)tensor_ptr(o.out, batch_off) : nullptr;
-            p.y2 = o.out2 >= 0 ? (bf16_t *)tensor_ptr(o.out2, batch_off) : nullptr;
-            p.yf = o.outf >= 0 ? (float *)tensor_ptr(o.outf, batch_off) : nullptr;
-            p.B = B; p.H = tin.H; p.W = tin.W; p.Cin = L.cin_d;
-            p.Cout = L.cout_d + (o.layer_n2 >= 0 ? g.layers[o.layer_n2].cout_d : 0); // N-fused sibling: its rows follow
-            p.n_valid = o.n_valid;
-            p.ldx = tin.C; p.x_coff = o.x_coff; p.y_split = o.y_split; p.y_split_add = o.y_split_add;
-            p.KH = L.kh; p.KW = L.kw; p.stride = L.stride; p.pad = L.pad;
-            p.Ho = g.tensors[tout].H; p.Wo = g.tensors[tout].W;
-            p.ldy = o.out >= 0 ? g.tensors[o.out].C : p.Cout;
-            p.y_coff = o.y_coff;
-            p.relu = o.relu; p.res_up2 = o.res_up2; p.res_post = o.res_post; p.head_softmax = o.head_softmax;
-            if (o.kind == OP_B2B) { // beyond stage 1: the pair runs through launch_conv (pw_b2b_kernel, or two launches)
-                const Layer &Lb = g.layers[o.layer_b];
-                p.w1 = d_w + Lb.w_off;
-                p.bias1 = d_b + Lb.b_off;
-                p.t1 = (bf16_t *)tensor_ptr(o.out_b, batch_off);
-                p.n1 = Lb.cout_d;
-            }
-            RFD_TRY(launch_conv(p, s));
-        }
+        // the stem is offered the conv behind it when that conv is the next op of the range (op_launch)
+        OpLaunch L;
+        op_launch(i, B, batch_off, part, !profiling && i + 1 <= last_op && skip_ops.empty(), &L);
+        bool fused = false;
+        RFD_TRY(launch_op(L, s, &fused));
         if (profiling) RFD_HIP(hipEventRecord(ev[2 * i + 1], s));
+        if (fused) ++i; // the conv ran inside the stem kernel
     }
     for (int bidx = 0; bidx < 2; ++bidx)
         if (forked[bidx]) { // join

@@ -25,6 +25,10 @@ RFD_ERR_IO = -6
 RFD_ERR_COMM = -7
 COMM_ID_BYTES = 128
 
+# debug_set_conv_tile / op_kernels_static: the forced tiles, enum ConvTile of csrc/kernels.h (each value's meaning is there)
+(TILE_HEURISTIC, TILE_128, TILE_256x128, TILE_256x64, TILE_NO_128, TILE_NO_PW_STREAM, TILE_PERSISTENT, TILE_GENERIC, TILE_PW_STREAM,
+ TILE_C64, TILE_PW_STREAM_K128, TILE_PW_STREAM_K256, TILE_PW_WIDE, TILE_HALO_SMALL, TILE_HALO_LARGE, TILE_PW_GEMM, TILE_PAIR, TILE_RING,
+ TILE_128_EIGHT_WAVES, TILE_KX_FOUR_WAVES) = range(20)
 BACKBONE_R50 = 0
 BACKBONE_MNET025 = 1
 
@@ -103,7 +107,7 @@ API_SYMBOLS = [
     "rfd_detect_batch_device", "rfd_sync", "rfd_set_stream", "rfd_preprocess", "rfd_forward", "rfd_decode_nms",
     "rfd_nms_sorted", "_nms", "rfd_get_stats", "rfd_get_config", "rfd_set_thresholds", "rfd_set_profiling",
     "rfd_get_conv_profile", "rfd_get_op_profile", "rfd_debug_tensor_io", "rfd_debug_run_ops", "rfd_debug_run_chain", "rfd_debug_pass_chains", "rfd_debug_buffer_io",
-    "rfd_debug_set_conv_tile", "rfd_debug_op_kernels", "rfd_debug_set_concurrency", "rfd_debug_persistent_kernel", "rfd_debug_poke_nms_flag", "rfd_selection_config_default",
+    "rfd_debug_set_conv_tile", "rfd_debug_op_kernels", "rfd_debug_op_kernels_static", "rfd_debug_set_concurrency", "rfd_debug_persistent_kernel", "rfd_debug_poke_nms_flag", "rfd_selection_config_default",
     "rfd_select_faces", "rfd_detect_select_batch", "rfd_save_weights", "rfd_load_weights",
     "rfd_alignment_config_default", "rfd_align_faces", "rfd_detect_select_align_batch",
     "rfd_host_alloc", "rfd_host_free", "rfd_submit_batch", "rfd_collect_batch",
@@ -171,6 +175,7 @@ def load_library(path=None):
     L.rfd_debug_set_conv_tile.argtypes = [vp, ci]
     L.rfd_debug_set_concurrency.argtypes = [vp, ci, ci, ci, ci]
     L.rfd_debug_op_kernels.argtypes = [vp, ci, ci, ci, C.c_char_p, ci]
+    L.rfd_debug_op_kernels_static.argtypes = [ci] * 9 + [C.c_char_p, ci]
     L.rfd_debug_poke_nms_flag.argtypes = [vp, ci]
     L.rfd_debug_persistent_kernel.argtypes = [ci, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t)]
     L.rfd_save_weights.argtypes = [vp, C.c_char_p]
@@ -201,6 +206,14 @@ def _check(status):
     if status < 0:
         raise RfdError(status, load_library().rfd_last_error().decode("utf-8", "replace"))
     return status
+
+
+def op_kernels_static(backbone, image_w, image_h, n, op, co_running=True, tile=0, schedule=SCHEDULE_THROUGHPUT, cus=256):
+    """debug_op_kernels without a context or a GPU: the kernel(s) a context of this backbone and image size would run op `op` of a
+    chain of n images with, under forced tile `tile`, on a GPU of `cus` compute units"""
+    buf = C.create_string_buffer(512)
+    _check(load_library().rfd_debug_op_kernels_static(backbone, image_w, image_h, n, op, 1 if co_running else 0, tile, schedule, cus, buf, 512))
+    return buf.value.decode().split(" + ")
 
 
 def head_shapes(n, net_h, net_w):

@@ -18,13 +18,19 @@ shipped kernel, but through one chain at image 0 with co_running off, and mostly
 - test_every_production_choice_is_checked: every production pair is planned by the exact sweep for the same (backbone, w, h) or
   run by the chain sweep.  The chain sweep derives its cases from production_pairs(), so a change of launch_conv's heuristics that
   picks a kernel nobody checked on that layer is run against the reference from then on (and shows in the printed count of pairs
-  new to the sweep); the audit is what fails should a pair ever be left out of both."""
+  new to the sweep); the audit is what fails should a pair ever be left out of both;
+- test_context_and_device_free_choices_agree: over the enumeration tests/golden/kernel_choice.json pins (the exact sweep's geometries
+  x every forced tile, these geometries x 1 .. 32 images, the latency schedule at 1 and 2 images; co_running off and on) the
+  context's answer (debug_op_kernels) and the device-free entry's (op_kernels_static, asked with this device's CU count) are the
+  same strings -- so what tests/test_kernel_choice_cpu.py replays without a GPU is what a context on the GPU picks."""
 import time
 
 import numpy as np
 import pytest
 
-from test_conv_exact_gpu import GEOMETRIES, Sweep, _bb, _dyadic_weights, plan
+import torch
+
+from test_conv_exact_gpu import GEOMETRIES, TILES, Sweep, _bb, _dyadic_weights, plan
 
 pytestmark = pytest.mark.gpu
 
@@ -156,3 +162,34 @@ def test_every_production_choice_is_checked(rfd, bb, w, h):
         assert not unchecked, "production picks kernels no test checks on that layer:\n" + "\n".join(unchecked)
     finally:
         det.close()
+
+
+def test_context_and_device_free_choices_agree(rfd):
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    sweeps = [(bb, w, h, 0, [(n, t) for t in TILES], ops) for bb, w, h, n, ops in GEOMETRIES]
+    sweeps += [(bb, w, h, 0, [(n, 0) for n in range(1, MAX_BATCH + 1)], None) for bb, w, h in GEOS]
+    sweeps += [(bb, 640, 640, rfd.SCHEDULE_LATENCY, [(1, 0), (2, 0)], None) for bb in ("r50", "mnet025")]
+    count, bad = 0, []
+    for bb, w, h, schedule, points, ops in sweeps:
+        det = rfd.RetinaFaceDetection(image_size=(w, h), max_batch_size=max(n for n, _ in points), max_det=16, backbone=_bb(rfd, bb), schedule=schedule)
+        try:
+            det.init_synthetic_weights(1234)
+            g = rfd.Graph(_bb(rfd, bb), w, h)
+            idx = range(len(g.ops)) if ops is None else [i for i, o in enumerate(g.ops) if o.kind == 3 or (
+                o.kind in (2, 6) and g.layers[o.layer].kh == 1 and g.tensors[o.in_].height <= 40)]
+            for n, tile in points:
+                det.debug_set_conv_tile(tile)
+                for co in (False, True):
+                    for i in idx:
+                        ctx = det.debug_op_kernels(n, i, co_running=co)
+                        free = rfd.op_kernels_static(_bb(rfd, bb), w, h, n, i, co_running=co, tile=tile, schedule=schedule, cus=cus)
+                        count += 1
+                        if ctx != free:
+                            bad.append("%s %dx%d schedule %d n=%d op %d co_running %d tile %d: context %s, device-free %s" % (
+                                bb, w, h, schedule, n, i, co, tile, ctx, free))
+        finally:
+            det.debug_set_conv_tile(0)
+            det.close()
+    print("\nkernel choice: %d (geometry, n, op, co_running, tile) points, context vs device-free entry at %d CUs: %d differ" % (count, cus, len(bad)))
+    assert count >= 29600
+    assert not bad, "\n".join(bad[:20]) + ("\n... %d more" % (len(bad) - 20) if len(bad) > 20 else "")

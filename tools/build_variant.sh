@@ -11,7 +11,8 @@ mkdir -p "$ROOT/tools/bin"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fvisibility=hidden -Wno-unused-function "$@" \
     -c "${SRC:-$PKG/csrc/$UNIT.hip}" -o "$ROOT/tools/bin/${UNIT}_$NAME.o"
 OBJS=""
-for f in kernels_pre kernels_post kernels_conv kernels_ring kernels_f32 network detector; do
+for src in "$PKG"/csrc/*.hip; do
+  f="$(basename "$src" .hip)"
   if [ "$f" = "$UNIT" ]; then OBJS="$OBJS $ROOT/tools/bin/${UNIT}_$NAME.o"; else OBJS="$OBJS $PKG/build/$f.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$ROOT/tools/bin/librfd_hip_$NAME.so" $OBJS -ldl

@@ -12,6 +12,7 @@ The checks work on `llvm-objdump -d` text of the device code object embedded in 
   returned wrong data next to another kernel's MFMA waves (rule (i)).
 * lds_dma_kernels / has_instr -- helpers for the per-object rules (no ds_read_b128 at all in the pre / post kernels).
 """
+import glob
 import os
 import re
 import subprocess
@@ -325,7 +326,13 @@ def counted_vmcnt_waits(ins):
     return out
 
 
-def report(objs=("kernels_pre", "kernels_post", "kernels_conv", "kernels_ring", "kernels_f32")):
+def kernel_units(build=BUILD):
+    """the translation units of csrc/ that hold kernels, by their objects in the build directory"""
+    return sorted(os.path.basename(f)[:-2] for f in glob.glob(os.path.join(build, "kernels_*.o")))
+
+
+def report(objs=None):
+    objs = objs or kernel_units()
     rows = []
     with tempfile.TemporaryDirectory() as tmp:
         for f in objs:
