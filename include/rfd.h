@@ -338,6 +338,73 @@ RFD_API int rfd_detect_select_align_batch(rfd_ctx *ctx, const rfd_image *imgs, i
                                           const rfd_alignment_config *align_cfg, float *out_box, float *out_kps,
                                           int32_t *found, uint8_t *out_crops, int32_t *status);
 
+/* ---- the model inputs of the two stages after alignment, and what follows their models: FaceQuality::call
+ *      (src/pipeline/module/face_quality.rs:40-186) and FaceExtraction::call (face_extraction.rs:30-150) -- the rest of
+ *      FacePipeline::extract (pipeline.rs:218-249).  The two models themselves are remote and not part of this library.
+ *      Before each model the reference runs, per face, cv::resize(INTER_LINEAR) to the model's image_size, COLOR_BGR2RGB,
+ *      (p - mean) * scale per pixel and the NHWC -> NCHW permute (face_quality.rs:43-44,56-101, face_extraction.rs:38-77);
+ *      here one launch does it for every face and every model.  The resize is the same restated cv::resize as the
+ *      detector's letterbox (its exact-2x case is the 2x2 mean; equal sizes are a copy).  Byte-exact against the oracle's
+ *      restatement; parity against a running OpenCV unpinned, like alignment. ---- */
+#define RFD_MAX_FACE_TENSORS 4
+typedef struct rfd_face_tensor_config {
+    int32_t out_w, out_h;   /* the model's image_size (w, h) */
+    float   mean[3];        /* per OUTPUT channel (R, G, B) */
+    float   scale[3];       /* value = (float(p) - mean[c]) * scale[c]: two roundings, in this order */
+    int32_t reserved[4];
+} rfd_face_tensor_config;
+RFD_API void rfd_face_tensor_config_quality(rfd_face_tensor_config *cfg);    /* 112x112; mean 123.675, 116.28, 103.53; scale 0.01712475, 0.017507, 0.01742919 (face_quality.rs:43-44) */
+RFD_API void rfd_face_tensor_config_extraction(rfd_face_tensor_config *cfg); /* 112x112; mean 127.5 x3; scale 0.0078125 x3 (face_extraction.rs:38-39) */
+/* Stage-level: crops [n][crop_h][crop_w][3] u8 BGR -> tensors[j] [n][3][cfgs[j].out_h][cfgs[j].out_w] f32, R,G,B planes,
+ * 1 <= k <= RFD_MAX_FACE_TENSORS (more: RFD_ERR_CAPACITY), n <= max_batch_size.  Host pointers. */
+RFD_API int rfd_face_tensors(rfd_ctx *ctx, const uint8_t *crops, int n, int crop_w, int crop_h,
+                             const rfd_face_tensor_config *cfgs, int k, float *const *tensors);
+/* rfd_detect_select_align_batch plus the k model inputs of every aligned face (k may be 0): tensors[j] as above, host.
+ * out_crops may be NULL (the u8 crops are then not returned; with configs of the crop's own size they are never stored at
+ * all).  A face with a negative alignment status gets all-zero tensors (0.0f in every plane, NOT (0 - mean) * scale), as its
+ * crop is zero-filled. */
+RFD_API int rfd_detect_select_align_tensors_batch(rfd_ctx *ctx, const rfd_image *imgs, int n,
+                                                  const rfd_selection_config *sel_cfg, int is_enroll,
+                                                  const rfd_alignment_config *align_cfg, float *out_box, float *out_kps,
+                                                  int32_t *found, uint8_t *out_crops, int32_t *status,
+                                                  const rfd_face_tensor_config *cfgs, int k, float *const *tensors);
+/* Stage-level: rfd_align_faces plus the k model inputs of every face (the same kernels as the fused entry, on caller-supplied
+ * selection results).  Host pointers; out_crops may be NULL. */
+RFD_API int rfd_align_faces_tensors(rfd_ctx *ctx, const rfd_image *imgs, int n, const float *boxes, const float *kps,
+                                    const int32_t *found, const rfd_alignment_config *cfg, uint8_t *out_crops,
+                                    int32_t *status, const rfd_face_tensor_config *cfgs, int k, float *const *tensors);
+/* The device-resident form (conventions of rfd_detect_batch_device): every imgs[i].data and every pointer of `out` is
+ * DEVICE memory -- box [n][5], kps [n][10], found [n], crops [n][out_h][out_w][3] (may be NULL), status [n], tensors[j < k].
+ * The whole call -- detection, selection, alignment, tensors -- is enqueued on the context's stream; async = 0 returns after
+ * the stream has drained, any other value returns at once with no host synchronisation (call rfd_sync before reading the
+ * results or reusing the buffers; the cross-call overlap of rfd_detect_batch_device's async = 2 is not offered here). */
+typedef struct rfd_faces {
+    float *box;
+    float *kps;
+    int32_t *found;
+    uint8_t *crops; /* may be NULL */
+    int32_t *status;
+    float *tensors[RFD_MAX_FACE_TENSORS];
+} rfd_faces;
+RFD_API int rfd_detect_faces_device(rfd_ctx *ctx, const rfd_image *imgs, int n, const rfd_selection_config *sel_cfg,
+                                    int is_enroll, const rfd_alignment_config *align_cfg,
+                                    const rfd_face_tensor_config *cfgs, int k, rfd_faces *out, int async);
+/* The quality decision rule (face_quality.rs:159-168) on the quality model's logits [n][classes]: klass[i] = the index of the
+ * row's maximum -- on equal values the LAST such index, as Rust's max_by returns; klass 1 with logits[1] < threshold becomes
+ * klass 0 (`<` is strict); score[i] = the logit of the final class.  Host pointers.
+ * Divergence: a NaN logit makes the reference panic (partial_cmp(..).unwrap()); here the call returns RFD_ERR_INVALID_ARG for
+ * the whole frame set and rfd_last_error() names the first such frame.  The device form cannot report without waiting for the
+ * stream: it marks such a row with klass = -1 and score = NaN. */
+RFD_API int rfd_quality_decide(rfd_ctx *ctx, const float *logits, int n, int classes, float threshold, float *score,
+                               int32_t *klass);
+/* normalize_outputs (src/utils/utils.rs:148-154) on the ID model's embeddings [n][dim]: out = emb / sqrt(sum emb^2) per row,
+ * f32, deterministic (fixed summation order).  An all-zero row gives NaN, as the reference's division does.  Host pointers. */
+RFD_API int rfd_normalize_embeddings(rfd_ctx *ctx, const float *emb, int n, int dim, float *out);
+/* Both with DEVICE pointers, enqueued on the context's stream (no synchronisation; out may equal emb). */
+RFD_API int rfd_quality_decide_device(rfd_ctx *ctx, const float *logits, int n, int classes, float threshold, float *score,
+                                      int32_t *klass);
+RFD_API int rfd_normalize_embeddings_device(rfd_ctx *ctx, const float *emb, int n, int dim, float *out);
+
 /* ---- introspection ---- */
 RFD_API int rfd_get_stats(rfd_ctx *ctx, rfd_stats *stats);
 RFD_API int rfd_get_config(const rfd_ctx *ctx, rfd_config *cfg);

@@ -197,5 +197,42 @@ class FaceAlignment {
     rfd_alignment_config cfg_;
 };
 
+// The inputs of the two models after alignment and what follows them: FaceQuality::call (face_quality.rs:40-186) and
+// FaceExtraction::call (face_extraction.rs:30-150) minus the remote models themselves.
+struct FaceTensorConfig : rfd_face_tensor_config {
+    static FaceTensorConfig quality() { FaceTensorConfig c; rfd_face_tensor_config_quality(&c); return c; }       // face_quality.rs:43-44
+    static FaceTensorConfig extraction() { FaceTensorConfig c; rfd_face_tensor_config_extraction(&c); return c; } // face_extraction.rs:38-39
+};
+// crops [n][crop_h][crop_w][3] u8 BGR -> one [n][3][out_h][out_w] f32 tensor (R, G, B planes) per config
+inline std::vector<std::vector<float>> face_tensors(RetinaFaceDetection &det, const uint8_t *crops, int n, int crop_w, int crop_h,
+                                                    const std::vector<FaceTensorConfig> &cfgs)
+{
+    std::vector<rfd_face_tensor_config> c(cfgs.begin(), cfgs.end());
+    std::vector<std::vector<float>> out(cfgs.size());
+    std::vector<float *> ptrs(cfgs.size());
+    for (std::size_t j = 0; j < cfgs.size(); ++j) {
+        out[j].resize((std::size_t)n * 3 * (cfgs[j].out_w > 0 ? cfgs[j].out_w : 0) * (cfgs[j].out_h > 0 ? cfgs[j].out_h : 0));
+        ptrs[j] = out[j].data();
+    }
+    check(rfd_face_tensors(det.raw(), crops, n, crop_w, crop_h, c.data(), (int)c.size(), ptrs.data()));
+    return out;
+}
+// face_quality.rs:159-168 on logits [n][classes] -> (scores, classes); throws where the reference panics (a NaN logit)
+inline std::pair<std::vector<float>, std::vector<int32_t>> quality_decide(RetinaFaceDetection &det, const std::vector<float> &logits,
+                                                                           int n, int classes, float threshold)
+{
+    std::vector<float> score(n);
+    std::vector<int32_t> klass(n);
+    check(rfd_quality_decide(det.raw(), logits.data(), n, classes, threshold, score.data(), klass.data()));
+    return {score, klass};
+}
+// normalize_outputs (utils.rs:148-154): every row of emb [n][dim] divided by its L2 norm
+inline std::vector<float> normalize_embeddings(RetinaFaceDetection &det, const std::vector<float> &emb, int n, int dim)
+{
+    std::vector<float> out(emb.size());
+    check(rfd_normalize_embeddings(det.raw(), emb.data(), n, dim, out.data()));
+    return out;
+}
+
 } // namespace rfd
 #endif

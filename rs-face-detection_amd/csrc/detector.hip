@@ -190,12 +190,19 @@ struct rfd_ctx {
     DevBuf scratch[12];
     DevBuf sel_dims, sel_out;
     DevBuf align_faces, align_out, align_status;
+    // model inputs of the quality / ID stages: staged crops and per-config planes of the host entries; in / out staging of the
+    // host forms of the decision rule and the normalisation
+    DevBuf face_in, face_tensors[kMaxFaceTensors], face_io[2];
     // pinned host ring for per-call descriptors, so enqueueing never blocks on the previous call
     static constexpr int kRing = 4;
     PreImage *pin_imgs[kRing] = {};
     float *pin_scales[kRing] = {};
     hipEvent_t pin_done[kRing] = {};
     int pin_next = 0;
+    // frame sizes of the selection epilogue: page-locked like pin_imgs, so that the copy may still be pending when the call returns
+    int *pin_dims[kRing] = {};
+    hipEvent_t pin_dims_done[kRing] = {};
+    int pin_dims_next = 0;
     // pipelined host entry (rfd_submit_batch / rfd_collect_batch): two slots, H2D on its own stream
     struct PipeSlot {
         DevBuf frames, imgs, scale, ob, ol, oc, ot;
@@ -638,7 +645,9 @@ int rfd_create(const rfd_config *cfg, rfd_ctx **out)
     for (int i = 0; i < rfd_ctx::kRing && st == RFD_OK; ++i) {
         if (hipHostMalloc((void **)&c->pin_imgs[i], cfg->max_batch_size * sizeof(PreImage)) != hipSuccess ||
             hipHostMalloc((void **)&c->pin_scales[i], cfg->max_batch_size * sizeof(float)) != hipSuccess ||
-            hipEventCreate(&c->pin_done[i]) != hipSuccess)
+            hipEventCreate(&c->pin_done[i]) != hipSuccess ||
+            hipHostMalloc((void **)&c->pin_dims[i], (size_t)cfg->max_batch_size * 2 * sizeof(int)) != hipSuccess ||
+            hipEventCreateWithFlags(&c->pin_dims_done[i], hipEventDisableTiming) != hipSuccess)
             st = RFD_ERR_HIP;
     }
     if (st == RFD_OK && hipHostMalloc((void **)&c->h_nms_flag, sizeof(int)) != hipSuccess) st = RFD_ERR_HIP;
@@ -667,12 +676,16 @@ void rfd_destroy(rfd_ctx *c)
     for (DevBuf &b : c->scratch) b.release();
     c->sel_dims.release(); c->sel_out.release();
     c->align_faces.release(); c->align_out.release(); c->align_status.release();
+    c->face_in.release(); c->face_io[0].release(); c->face_io[1].release();
+    for (DevBuf &b : c->face_tensors) b.release();
     for (int i = 0; i < 10; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     for (int i = 0; i < rfd_ctx::kRing; ++i) {
         if (c->pin_imgs[i]) (void)hipHostFree(c->pin_imgs[i]);
         if (c->pin_scales[i]) (void)hipHostFree(c->pin_scales[i]);
         if (c->pin_done[i]) (void)hipEventDestroy(c->pin_done[i]);
+        if (c->pin_dims[i]) (void)hipHostFree(c->pin_dims[i]);
+        if (c->pin_dims_done[i]) (void)hipEventDestroy(c->pin_dims_done[i]);
     }
     if (c->h_nms_flag) (void)hipHostFree(c->h_nms_flag);
     for (rfd_ctx::PipeSlot &ps : c->pipe) {
@@ -1458,19 +1471,24 @@ void rfd_selection_config_default(rfd_selection_config *cfg)
     cfg->minimum_face_ratio = 0.0075f;     // config.rs:113
 }
 
-// selection over device-resident detection slabs; results copied to the host pointers
-static int select_impl(rfd_ctx *c, const float *d_boxes, const float *d_lmk, const int *d_count, const int *img_h,
-                       const int *img_w, int n, const rfd_selection_config *cfg, int is_enroll, float *out_box,
-                       float *out_kps, int32_t *found)
+// selection over device-resident detection slabs into device arrays d_box [n][5], d_kps [n][10], d_found [n]; enqueued only.
+// The frame sizes go through a ring of page-locked arrays (as the frame descriptors do, stage_frames), so nothing here
+// needs the host to wait for the stream.
+static int select_enqueue(rfd_ctx *c, const float *d_boxes, const float *d_lmk, const int *d_count, const int *img_h,
+                          const int *img_w, int n, const rfd_selection_config *cfg, int is_enroll, float *d_box,
+                          float *d_kps, int32_t *d_found)
 {
     rfd_selection_config def;
     rfd_selection_config_default(&def);
     if (!cfg) cfg = &def;
     RFD_TRY(c->sel_dims.reserve((size_t)2 * n * sizeof(int)));
-    RFD_TRY(c->sel_out.reserve((size_t)n * 16 * sizeof(float)));
-    std::vector<int> dims(2 * n);
+    const int slot = c->pin_dims_next;
+    c->pin_dims_next = (c->pin_dims_next + 1) % rfd_ctx::kRing;
+    RFD_HIP(hipEventSynchronize(c->pin_dims_done[slot])); // the copy that last used this slot has run
+    int *dims = c->pin_dims[slot];
     for (int i = 0; i < n; ++i) { dims[i] = img_h[i]; dims[n + i] = img_w[i]; }
-    RFD_HIP(hipMemcpyAsync(c->sel_dims.p, dims.data(), 2 * n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    RFD_HIP(hipMemcpyAsync(c->sel_dims.p, dims, 2 * n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    RFD_HIP(hipEventRecord(c->pin_dims_done[slot], c->stream));
     SelectParams sp;
     memset(&sp, 0, sizeof sp);
     sp.boxes = d_boxes; sp.lmk = d_lmk; sp.count = d_count;
@@ -1480,13 +1498,24 @@ static int select_impl(rfd_ctx *c, const float *d_boxes, const float *d_lmk, con
     sp.margin_center_right_ratio = cfg->margin_center_right_ratio;
     sp.margin_edge_ratio = cfg->margin_edge_ratio;
     sp.minimum_face_ratio = cfg->minimum_face_ratio;
+    sp.out_box = d_box; sp.out_kps = d_kps; sp.out_found = d_found;
+    return launch_face_select(sp, c->stream);
+}
+
+// the same into c->sel_out, then copied to the host pointers
+static int select_impl(rfd_ctx *c, const float *d_boxes, const float *d_lmk, const int *d_count, const int *img_h,
+                       const int *img_w, int n, const rfd_selection_config *cfg, int is_enroll, float *out_box,
+                       float *out_kps, int32_t *found)
+{
+    RFD_TRY(c->sel_out.reserve((size_t)n * 16 * sizeof(float)));
     float *o = (float *)c->sel_out.p;
-    sp.out_box = o; sp.out_kps = o + (size_t)n * 5; sp.out_found = (int *)(o + (size_t)n * 15);
-    RFD_TRY(launch_face_select(sp, c->stream));
-    RFD_HIP(hipMemcpyAsync(out_box, sp.out_box, (size_t)n * 5 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipMemcpyAsync(out_kps, sp.out_kps, (size_t)n * 10 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipMemcpyAsync(found, sp.out_found, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipStreamSynchronize(c->stream)); // dims is a host temporary
+    float *d_box = o, *d_kps = o + (size_t)n * 5;
+    int32_t *d_found = (int32_t *)(o + (size_t)n * 15);
+    RFD_TRY(select_enqueue(c, d_boxes, d_lmk, d_count, img_h, img_w, n, cfg, is_enroll, d_box, d_kps, d_found));
+    RFD_HIP(hipMemcpyAsync(out_box, d_box, (size_t)n * 5 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipMemcpyAsync(out_kps, d_kps, (size_t)n * 10 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipMemcpyAsync(found, d_found, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipStreamSynchronize(c->stream)); // the results are read by the caller
     return check_nms_flag(c);
 }
 
@@ -1583,6 +1612,265 @@ int rfd_detect_select_align_batch(rfd_ctx *c, const rfd_image *imgs, int n, cons
     RFD_TRY(rfd_detect_select_batch(c, imgs, n, sel_cfg, is_enroll, out_box, out_kps, found));
     const float *o = (const float *)c->sel_out.p;
     return align_impl(c, n, o, o + (size_t)n * 5, (const int *)(o + (size_t)n * 15), align_cfg, out_crops, status);
+}
+
+// ---- model inputs of the quality and ID stages (face_quality.rs:43-44,56-101, face_extraction.rs:38-77) ----
+void rfd_face_tensor_config_quality(rfd_face_tensor_config *cfg)
+{
+    if (!cfg) return;
+    memset(cfg, 0, sizeof *cfg);
+    cfg->out_w = 112; cfg->out_h = 112;
+    static const float mean[3] = {123.675f, 116.28f, 103.53f};          // face_quality.rs:43
+    static const float scale[3] = {0.01712475f, 0.017507f, 0.01742919f}; // :44 (named `std`, applied as a factor :93)
+    memcpy(cfg->mean, mean, sizeof mean);
+    memcpy(cfg->scale, scale, sizeof scale);
+}
+
+void rfd_face_tensor_config_extraction(rfd_face_tensor_config *cfg)
+{
+    if (!cfg) return;
+    memset(cfg, 0, sizeof *cfg);
+    cfg->out_w = 112; cfg->out_h = 112;
+    for (int i = 0; i < 3; ++i) { cfg->mean[i] = 127.5f; cfg->scale[i] = 0.0078125f; } // face_extraction.rs:38-39
+}
+
+static int check_face_tensor_args(const rfd_face_tensor_config *cfgs, int k, float *const *tensors, int k_min)
+{
+    if (k > RFD_MAX_FACE_TENSORS) { set_error("%d tensor configs exceed RFD_MAX_FACE_TENSORS (%d)", k, RFD_MAX_FACE_TENSORS); return RFD_ERR_CAPACITY; }
+    RFD_CHECK_ARG(k >= k_min, "too few tensor configs");
+    RFD_CHECK_ARG(k == 0 || (cfgs && tensors), "tensor configs / tensor pointers are null");
+    for (int j = 0; j < k; ++j) {
+        if (cfgs[j].out_w < 1 || cfgs[j].out_h < 1 || cfgs[j].out_w > 4096 || cfgs[j].out_h > 4096) {
+            set_error("tensor config %d: size %dx%d out of range", j, cfgs[j].out_w, cfgs[j].out_h);
+            return RFD_ERR_INVALID_ARG;
+        }
+        if (!tensors[j]) { set_error("tensor pointer %d is null", j); return RFD_ERR_INVALID_ARG; }
+    }
+    return RFD_OK;
+}
+
+// cv::resize's scale bookkeeping for a crop_w x crop_h crop (as letterbox() does for a frame)
+static void fill_face_tensor_cfg(FaceTensorCfg &d, const rfd_face_tensor_config &s, float *out, int crop_w, int crop_h)
+{
+    d.out = out; d.out_w = s.out_w; d.out_h = s.out_h;
+    memcpy(d.mean, s.mean, sizeof d.mean);
+    memcpy(d.scale, s.scale, sizeof d.scale);
+    d.same = s.out_w == crop_w && s.out_h == crop_h;
+    const double inv_x = (double)s.out_w / crop_w, inv_y = (double)s.out_h / crop_h;
+    d.scale_x = 1.0 / inv_x;
+    d.scale_y = 1.0 / inv_y;
+    const int ix = (int)lrint(d.scale_x), iy = (int)lrint(d.scale_y);
+    d.area_fast = fabs(d.scale_x - ix) < 2.220446049250313e-16 && fabs(d.scale_y - iy) < 2.220446049250313e-16 && ix == 2 && iy == 2;
+}
+
+int rfd_face_tensors(rfd_ctx *c, const uint8_t *crops, int n, int crop_w, int crop_h, const rfd_face_tensor_config *cfgs, int k,
+                     float *const *tensors)
+{
+    RFD_CHECK_ARG(c && crops, "null argument");
+    RFD_TRY(check_face_tensor_args(cfgs, k, tensors, 1));
+    RFD_CHECK_ARG(crop_w >= 1 && crop_h >= 1 && crop_w <= 4096 && crop_h <= 4096, "crop size out of range");
+    if (n < 1 || n > c->cfg.max_batch_size) { set_error("batch %d exceeds max_batch_size %d", n, c->cfg.max_batch_size); return RFD_ERR_CAPACITY; }
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    const size_t crop = (size_t)crop_w * crop_h * 3;
+    RFD_TRY(c->face_in.reserve((size_t)n * crop));
+    RFD_HIP(hipMemcpyAsync(c->face_in.p, crops, (size_t)n * crop, hipMemcpyHostToDevice, c->stream));
+    FaceTensorParams tp;
+    memset(&tp, 0, sizeof tp);
+    tp.crops = (const uint8_t *)c->face_in.p;
+    tp.n = n; tp.crop_w = crop_w; tp.crop_h = crop_h; tp.k = k;
+    for (int j = 0; j < k; ++j) {
+        RFD_TRY(c->face_tensors[j].reserve((size_t)n * 3 * cfgs[j].out_w * cfgs[j].out_h * sizeof(float)));
+        fill_face_tensor_cfg(tp.cfg[j], cfgs[j], (float *)c->face_tensors[j].p, crop_w, crop_h);
+    }
+    RFD_TRY(launch_face_tensors(tp, c->stream));
+    for (int j = 0; j < k; ++j)
+        RFD_HIP(hipMemcpyAsync(tensors[j], tp.cfg[j].out, (size_t)n * 3 * cfgs[j].out_w * cfgs[j].out_h * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    return RFD_OK;
+}
+
+// Alignment of the frames whose descriptors sit in c->imgs plus the k model inputs of every face, into DEVICE arrays; enqueued
+// only.  Configs of the crop's own size are written by the warp itself, from the registers that hold the pixel; the others are
+// resized from the crop in HBM (d_crops, or the context's own buffer when the caller wants no crop).
+static int align_tensors_enqueue(rfd_ctx *c, int n, const float *d_box, const float *d_kps, const int *d_found,
+                                 const rfd_alignment_config *cfg, const rfd_face_tensor_config *cfgs, int k,
+                                 float *const *d_tensors, uint8_t *d_crops, int32_t *d_status)
+{
+    rfd_alignment_config def;
+    rfd_alignment_config_default(&def);
+    if (!cfg) cfg = &def;
+    if (cfg->out_w < 1 || cfg->out_h < 1 || cfg->out_w > 4096 || cfg->out_h > 4096) {
+        set_error("alignment output size %dx%d out of range", cfg->out_w, cfg->out_h);
+        return RFD_ERR_INVALID_ARG;
+    }
+    FaceTensorParams fused, rest;
+    memset(&fused, 0, sizeof fused);
+    memset(&rest, 0, sizeof rest);
+    for (int j = 0; j < k; ++j) {
+        FaceTensorParams &t = (cfgs[j].out_w == cfg->out_w && cfgs[j].out_h == cfg->out_h) ? fused : rest;
+        fill_face_tensor_cfg(t.cfg[t.k++], cfgs[j], d_tensors[j], cfg->out_w, cfg->out_h);
+    }
+    if (!d_crops && rest.k) {
+        RFD_TRY(c->align_out.reserve((size_t)n * cfg->out_w * cfg->out_h * 3));
+        d_crops = (uint8_t *)c->align_out.p;
+    }
+    RFD_TRY(c->align_faces.reserve((size_t)n * sizeof(AlignFace)));
+    AlignParams ap;
+    memset(&ap, 0, sizeof ap);
+    ap.imgs = (const PreImage *)c->imgs.p;
+    ap.box = d_box; ap.kps = d_kps; ap.found = d_found;
+    memcpy(ap.std_lmk, cfg->standard_landmarks, sizeof ap.std_lmk);
+    ap.out_w = cfg->out_w; ap.out_h = cfg->out_h; ap.n = n;
+    ap.faces = (AlignFace *)c->align_faces.p;
+    ap.status = d_status;
+    ap.out = d_crops;
+    fused.n = rest.n = n;
+    fused.crop_w = rest.crop_w = cfg->out_w;
+    fused.crop_h = rest.crop_h = cfg->out_h;
+    rest.crops = d_crops;
+    rest.status = d_status;
+    RFD_TRY(launch_face_align_tensors(ap, fused, c->stream));
+    return launch_face_tensors(rest, c->stream);
+}
+
+// align_tensors_enqueue on the selection results in c->sel_out, into the context's own buffers, then copied to the host pointers
+static int align_tensors_to_host(rfd_ctx *c, int n, const rfd_alignment_config *align_cfg, uint8_t *out_crops, int32_t *status,
+                                 const rfd_face_tensor_config *cfgs, int k, float *const *tensors)
+{
+    const size_t crop = (size_t)align_cfg->out_w * align_cfg->out_h * 3;
+    RFD_TRY(c->align_status.reserve((size_t)n * sizeof(int)));
+    if (out_crops) RFD_TRY(c->align_out.reserve((size_t)n * crop));
+    float *d_tensors[kMaxFaceTensors] = {};
+    for (int j = 0; j < k; ++j) {
+        RFD_TRY(c->face_tensors[j].reserve((size_t)n * 3 * cfgs[j].out_w * cfgs[j].out_h * sizeof(float)));
+        d_tensors[j] = (float *)c->face_tensors[j].p;
+    }
+    const float *o = (const float *)c->sel_out.p;
+    RFD_TRY(align_tensors_enqueue(c, n, o, o + (size_t)n * 5, (const int *)(o + (size_t)n * 15), align_cfg, cfgs, k, d_tensors,
+                                  out_crops ? (uint8_t *)c->align_out.p : nullptr, (int32_t *)c->align_status.p));
+    if (out_crops) RFD_HIP(hipMemcpyAsync(out_crops, c->align_out.p, (size_t)n * crop, hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipMemcpyAsync(status, c->align_status.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    for (int j = 0; j < k; ++j)
+        RFD_HIP(hipMemcpyAsync(tensors[j], d_tensors[j], (size_t)n * 3 * cfgs[j].out_w * cfgs[j].out_h * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    return check_nms_flag(c);
+}
+
+int rfd_align_faces_tensors(rfd_ctx *c, const rfd_image *imgs, int n, const float *boxes, const float *kps, const int32_t *found,
+                            const rfd_alignment_config *cfg, uint8_t *out_crops, int32_t *status,
+                            const rfd_face_tensor_config *cfgs, int k, float *const *tensors)
+{
+    RFD_CHECK_ARG(c && boxes && kps && found && status, "null argument");
+    RFD_TRY(check_face_tensor_args(cfgs, k, tensors, 0));
+    rfd_alignment_config def;
+    rfd_alignment_config_default(&def);
+    if (!cfg) cfg = &def;
+    if (cfg->out_w < 1 || cfg->out_h < 1 || cfg->out_w > 4096 || cfg->out_h > 4096) {
+        set_error("alignment output size %dx%d out of range", cfg->out_w, cfg->out_h);
+        return RFD_ERR_INVALID_ARG;
+    }
+    RFD_TRY(check_images(c, imgs, n));
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    std::vector<float> scales;
+    RFD_TRY(stage_frames(c, imgs, n, false, scales));
+    RFD_TRY(c->sel_out.reserve((size_t)n * 16 * sizeof(float)));
+    float *o = (float *)c->sel_out.p;
+    RFD_HIP(hipMemcpyAsync(o, boxes, (size_t)n * 5 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    RFD_HIP(hipMemcpyAsync(o + (size_t)n * 5, kps, (size_t)n * 10 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    RFD_HIP(hipMemcpyAsync(o + (size_t)n * 15, found, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    return align_tensors_to_host(c, n, cfg, out_crops, status, cfgs, k, tensors);
+}
+
+int rfd_detect_select_align_tensors_batch(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_selection_config *sel_cfg,
+                                          int is_enroll, const rfd_alignment_config *align_cfg, float *out_box, float *out_kps,
+                                          int32_t *found, uint8_t *out_crops, int32_t *status,
+                                          const rfd_face_tensor_config *cfgs, int k, float *const *tensors)
+{
+    RFD_CHECK_ARG(c && status, "null argument");
+    RFD_TRY(check_face_tensor_args(cfgs, k, tensors, 0));
+    rfd_alignment_config def;
+    rfd_alignment_config_default(&def);
+    if (!align_cfg) align_cfg = &def;
+    if (align_cfg->out_w < 1 || align_cfg->out_h < 1 || align_cfg->out_w > 4096 || align_cfg->out_h > 4096) {
+        set_error("alignment output size %dx%d out of range", align_cfg->out_w, align_cfg->out_h);
+        return RFD_ERR_INVALID_ARG;
+    }
+    RFD_TRY(rfd_detect_select_batch(c, imgs, n, sel_cfg, is_enroll, out_box, out_kps, found));
+    return align_tensors_to_host(c, n, align_cfg, out_crops, status, cfgs, k, tensors);
+}
+
+int rfd_detect_faces_device(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_selection_config *sel_cfg, int is_enroll,
+                            const rfd_alignment_config *align_cfg, const rfd_face_tensor_config *cfgs, int k, rfd_faces *out,
+                            int async)
+{
+    RFD_CHECK_ARG(c && out && out->box && out->kps && out->found && out->status, "null argument");
+    RFD_TRY(check_face_tensor_args(cfgs, k, out->tensors, 0));
+    RFD_TRY(check_images(c, imgs, n));
+    rfd_dets dev = {(float *)c->out_boxes.p, (float *)c->out_lmk.p, (int32_t *)c->out_count.p, (int32_t *)c->out_total.p};
+    RFD_TRY(detect_impl(c, imgs, n, &dev, /*outputs stay on the device*/ true, /*async*/ 1, /*frames on device*/ true));
+    std::vector<int> hh(n), ww(n);
+    for (int i = 0; i < n; ++i) { hh[i] = imgs[i].height; ww[i] = imgs[i].width; }
+    RFD_TRY(select_enqueue(c, dev.boxes, dev.landmarks, dev.count, hh.data(), ww.data(), n, sel_cfg, is_enroll, out->box, out->kps,
+                           out->found));
+    RFD_TRY(align_tensors_enqueue(c, n, out->box, out->kps, out->found, align_cfg, cfgs, k, out->tensors, out->crops, out->status));
+    if (async) return RFD_OK;
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    return check_nms_flag(c);
+}
+
+// ---- after the two models: quality decision rule (face_quality.rs:159-168), embedding normalisation (utils.rs:148-154) ----
+int rfd_quality_decide_device(rfd_ctx *c, const float *logits, int n, int classes, float threshold, float *score, int32_t *klass)
+{
+    RFD_CHECK_ARG(c && logits && score && klass, "null argument");
+    RFD_CHECK_ARG(n >= 1 && classes >= 1, "n < 1 or classes < 1");
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    return launch_quality_decide(logits, n, classes, threshold, score, klass, c->stream);
+}
+
+int rfd_quality_decide(rfd_ctx *c, const float *logits, int n, int classes, float threshold, float *score, int32_t *klass)
+{
+    RFD_CHECK_ARG(c && logits && score && klass, "null argument");
+    RFD_CHECK_ARG(n >= 1 && classes >= 1, "n < 1 or classes < 1");
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    const size_t in_bytes = (size_t)n * classes * sizeof(float);
+    RFD_TRY(c->face_io[0].reserve(in_bytes));
+    RFD_TRY(c->face_io[1].reserve((size_t)n * (sizeof(float) + sizeof(int32_t))));
+    float *d_score = (float *)c->face_io[1].p;
+    int32_t *d_klass = (int32_t *)(d_score + n);
+    RFD_HIP(hipMemcpyAsync(c->face_io[0].p, logits, in_bytes, hipMemcpyHostToDevice, c->stream));
+    RFD_TRY(rfd_quality_decide_device(c, (const float *)c->face_io[0].p, n, classes, threshold, d_score, d_klass));
+    RFD_HIP(hipMemcpyAsync(score, d_score, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipMemcpyAsync(klass, d_klass, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < n; ++i)
+        if (klass[i] < 0) { // the reference panics here (partial_cmp(..).unwrap(), face_quality.rs:160)
+            set_error("invalid argument: the logits of frame %d hold a NaN", i);
+            return RFD_ERR_INVALID_ARG;
+        }
+    return RFD_OK;
+}
+
+int rfd_normalize_embeddings_device(rfd_ctx *c, const float *emb, int n, int dim, float *out)
+{
+    RFD_CHECK_ARG(c && emb && out, "null argument");
+    RFD_CHECK_ARG(n >= 1 && dim >= 1, "n < 1 or dim < 1");
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    return launch_l2_normalize(emb, n, dim, out, c->stream);
+}
+
+int rfd_normalize_embeddings(rfd_ctx *c, const float *emb, int n, int dim, float *out)
+{
+    RFD_CHECK_ARG(c && emb && out, "null argument");
+    RFD_CHECK_ARG(n >= 1 && dim >= 1, "n < 1 or dim < 1");
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    const size_t bytes = (size_t)n * dim * sizeof(float);
+    RFD_TRY(c->face_io[0].reserve(bytes));
+    RFD_TRY(c->face_io[1].reserve(bytes));
+    RFD_HIP(hipMemcpyAsync(c->face_io[0].p, emb, bytes, hipMemcpyHostToDevice, c->stream));
+    RFD_TRY(rfd_normalize_embeddings_device(c, (const float *)c->face_io[0].p, n, dim, (float *)c->face_io[1].p));
+    RFD_HIP(hipMemcpyAsync(out, c->face_io[1].p, bytes, hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    return RFD_OK;
 }
 
 int rfd_nms_sorted(rfd_ctx *c, int32_t *keep, int *num_out, const float *boxes, int boxes_num, int boxes_dim,

@@ -110,6 +110,35 @@ struct AlignParams {
 };
 int launch_face_align(const AlignParams &p, hipStream_t s);
 
+// The model inputs of FaceQuality::call / FaceExtraction::call (face_quality.rs:43-44,56-101, face_extraction.rs:38-77):
+// cv::resize(INTER_LINEAR) of the aligned crop to the model's image_size, COLOR_BGR2RGB, (p - mean) * scale, NHWC -> NCHW.
+constexpr int kMaxFaceTensors = 4; // = RFD_MAX_FACE_TENSORS
+struct FaceTensorCfg {
+    float *out;              // [n][3][out_h][out_w] f32, R,G,B planes
+    int out_w, out_h;
+    float mean[3], scale[3]; // per OUTPUT channel: value = (float(p) - mean[c]) * scale[c], two roundings
+    double scale_x, scale_y; // 1 / (out_w / crop_w), 1 / (out_h / crop_h) in f64, as cv::resize computes them
+    int area_fast;           // both exactly 2: the 2x2 mean
+    int same;                // out size == crop size: a copy
+};
+struct FaceTensorParams {
+    const uint8_t *crops;    // [n][crop_h][crop_w][3] u8 BGR (face_tensor_kernel only)
+    const int *status;       // [n] alignment status or null: a face with a negative status gets all-zero tensors
+    int n, crop_w, crop_h, k;
+    FaceTensorCfg cfg[kMaxFaceTensors];
+};
+// every config of p from crops in HBM: one launch for all k configs and n faces
+int launch_face_tensors(const FaceTensorParams &p, hipStream_t s);
+// launch_face_align whose warp also writes the planes of every config of t (all of the crop's own size, t.k may be 0) from the
+// registers that hold the pixel; a.out may be null (no u8 crop wanted)
+int launch_face_align_tensors(const AlignParams &a, const FaceTensorParams &t, hipStream_t s);
+
+// quality decision rule (face_quality.rs:159-168): klass = LAST index of the maximum, class 1 below the threshold -> class 0,
+// score = the logit of the final class; a row that holds a NaN gets klass = -1, score = NaN.  One thread per row.
+int launch_quality_decide(const float *logits, int n, int classes, float threshold, float *score, int *klass, hipStream_t s);
+// out = emb / sqrt(sum emb^2) per row (utils.rs:148-154), one wave64 per row, deterministic
+int launch_l2_normalize(const float *emb, int n, int dim, float *out, hipStream_t s);
+
 // ---------------------------------------------------------------- convolution engine (kernels_conv.hip)
 // Activations: NHWC bf16.  Weights: [Cout][KH][KW][Cin] bf16 (K contiguous).  f32 accumulate on MFMA.
 struct ConvParams {

@@ -309,17 +309,9 @@ __global__ void align_setup_kernel(AlignParams p)
     p.status[b] = f.mode;
 }
 
-__global__ void __launch_bounds__(256) align_warp_kernel(AlignParams p)
+// one pixel of the aligned crop of a face with mode >= 0: v = B,G,R.  The arithmetic of both warp kernels.
+__device__ __forceinline__ void align_warp_px(const AlignFace &f, const PreImage &im, int x, int y, int v[3])
 {
-    const int b = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= p.out_w * p.out_h) return;
-    const int y = i / p.out_w, x = i - y * p.out_w;
-    const AlignFace &f = p.faces[b];
-    uint8_t *d = p.out + ((size_t)b * p.out_h * p.out_w + i) * 3;
-    if (f.mode < 0) { d[0] = d[1] = d[2] = 0; return; }
-    const PreImage im = p.imgs[b];
-    int v[3];
     if (f.mode == 1) {
         resize_linear_px(im.src + (long long)f.y0 * im.stride + f.x0 * 3, im.stride, f.rh, f.rw, f.scale_x, f.scale_y,
                          f.area_fast, x, y, v);
@@ -346,6 +338,20 @@ __global__ void __launch_bounds__(256) align_warp_kernel(AlignParams p)
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[c] = (acc[c] + (1 << 14)) >> 15;
     }
+}
+
+__global__ void __launch_bounds__(256) align_warp_kernel(AlignParams p)
+{
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.out_w * p.out_h) return;
+    const int y = i / p.out_w, x = i - y * p.out_w;
+    const AlignFace &f = p.faces[b];
+    uint8_t *d = p.out + ((size_t)b * p.out_h * p.out_w + i) * 3;
+    if (f.mode < 0) { d[0] = d[1] = d[2] = 0; return; }
+    const PreImage im = p.imgs[b];
+    int v[3];
+    align_warp_px(f, im, x, y, v);
     d[0] = (uint8_t)v[0]; d[1] = (uint8_t)v[1]; d[2] = (uint8_t)v[2];
 }
 
@@ -354,6 +360,137 @@ int launch_face_align(const AlignParams &p, hipStream_t s)
     hipLaunchKernelGGL(align_setup_kernel, dim3(ceil_div(p.n, 64)), dim3(64), 0, s, p);
     RFD_HIP(hipGetLastError());
     hipLaunchKernelGGL(align_warp_kernel, dim3(ceil_div(p.out_w * p.out_h, 256), p.n), dim3(256), 0, s, p);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The model inputs of the two stages after alignment (face_quality.rs:43-44,56-101, face_extraction.rs:38-77): resize to the
+// model's image_size, BGR -> RGB, (p - mean) * scale, NHWC -> NCHW.  Byte work + two f32 roundings per value, pinned with
+// __fsub_rn / __fmul_rn so that no contraction can merge them.  Plane stores: lane i writes float i of a row-major plane.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void face_tensor_store(const FaceTensorCfg &c, int b, int i, const int v[3], bool zero)
+{
+    const size_t plane = (size_t)c.out_w * c.out_h;
+    float *t = c.out + (size_t)b * 3 * plane + i;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) // output channel R,G,B = crop channel 2,1,0
+        t[ch * plane] = zero ? 0.0f : __fmul_rn(__fsub_rn((float)v[2 - ch], c.mean[ch]), c.scale[ch]);
+}
+
+// align_warp_kernel + the planes of every config of the crop's own size, from the registers that hold the pixel
+__global__ void __launch_bounds__(256) align_warp_tensor_kernel(AlignParams p, FaceTensorParams t)
+{
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.out_w * p.out_h) return;
+    const int y = i / p.out_w, x = i - y * p.out_w;
+    const AlignFace &f = p.faces[b];
+    const bool zero = f.mode < 0;
+    int v[3] = {0, 0, 0};
+    if (!zero) {
+        const PreImage im = p.imgs[b];
+        align_warp_px(f, im, x, y, v);
+    }
+    if (p.out) {
+        uint8_t *d = p.out + ((size_t)b * p.out_h * p.out_w + i) * 3;
+        d[0] = (uint8_t)v[0]; d[1] = (uint8_t)v[1]; d[2] = (uint8_t)v[2];
+    }
+#pragma unroll
+    for (int j = 0; j < kMaxFaceTensors; ++j)
+        if (j < t.k) face_tensor_store(t.cfg[j], b, i, v, zero);
+}
+
+int launch_face_align_tensors(const AlignParams &a, const FaceTensorParams &t, hipStream_t s)
+{
+    hipLaunchKernelGGL(align_setup_kernel, dim3(ceil_div(a.n, 64)), dim3(64), 0, s, a);
+    RFD_HIP(hipGetLastError());
+    hipLaunchKernelGGL(align_warp_tensor_kernel, dim3(ceil_div(a.out_w * a.out_h, 256), a.n), dim3(256), 0, s, a, t);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+// crops in HBM -> the planes of config blockIdx.z of face blockIdx.y: resize (or copy), swap, normalise
+__global__ void __launch_bounds__(256) face_tensor_kernel(FaceTensorParams p)
+{
+    const FaceTensorCfg &c = p.cfg[blockIdx.z];
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= c.out_w * c.out_h) return;
+    const bool zero = p.status && p.status[b] < 0;
+    int v[3] = {0, 0, 0};
+    if (!zero) {
+        const long long stride = (long long)p.crop_w * 3;
+        const uint8_t *src = p.crops + (size_t)b * p.crop_h * stride;
+        if (c.same) {
+            const uint8_t *s = src + (size_t)i * 3;
+            v[0] = s[0]; v[1] = s[1]; v[2] = s[2];
+        } else {
+            const int y = i / c.out_w, x = i - y * c.out_w;
+            resize_linear_px(src, stride, p.crop_h, p.crop_w, c.scale_x, c.scale_y, c.area_fast, x, y, v);
+        }
+    }
+    face_tensor_store(c, b, i, v, zero);
+}
+
+int launch_face_tensors(const FaceTensorParams &p, hipStream_t s)
+{
+    if (p.k < 1) return RFD_OK;
+    int px = 0;
+    for (int j = 0; j < p.k; ++j) px = max(px, p.cfg[j].out_w * p.cfg[j].out_h);
+    hipLaunchKernelGGL(face_tensor_kernel, dim3(ceil_div(px, 256), p.n, p.k), dim3(256), 0, s, p);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+// quality decision rule, face_quality.rs:159-168.  `max_by(|a, b| a.partial_cmp(b).unwrap())` keeps the LAST of equal maxima
+// and panics on a NaN: such a row is marked klass = -1 / score = NaN here (the host entry turns it into an error).
+__global__ void __launch_bounds__(64) quality_decide_kernel(const float *__restrict__ logits, int n, int classes, float threshold,
+                                                           float *__restrict__ score, int *__restrict__ klass)
+{
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= n) return;
+    const float *l = logits + (size_t)b * classes;
+    int best = 0;
+    float m = l[0];
+    bool nan = m != m;
+    for (int i = 1; i < classes; ++i) {
+        const float x = l[i];
+        nan |= x != x;
+        if (x >= m) { m = x; best = i; }
+    }
+    if (best == 1 && m < threshold) { best = 0; m = l[0]; } // :163-166
+    score[b] = nan ? __int_as_float(0x7fc00000) : m;
+    klass[b] = nan ? -1 : best;
+}
+
+int launch_quality_decide(const float *logits, int n, int classes, float threshold, float *score, int *klass, hipStream_t s)
+{
+    hipLaunchKernelGGL(quality_decide_kernel, dim3(ceil_div(n, 64)), dim3(64), 0, s, logits, n, classes, threshold, score, klass);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+// normalize_outputs, utils.rs:148-154: array / array.norm_l2().  One wave64 per row: lane l sums the squares of elements l,
+// l + 64, ... in ascending order, the 64 partial sums meet in a fixed xor butterfly (every lane ends with the same bits: IEEE
+// addition commutes), then one correctly rounded square root and one correctly rounded division per element.
+__global__ void __launch_bounds__(256) l2_normalize_kernel(const float *emb, int n, int dim, float *out) // out may be emb
+{
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= n) return; // whole waves leave together: every shuffle below runs with all 64 lanes
+    const float *x = emb + (size_t)row * dim;
+    float s = 0.0f;
+    for (int i = lane; i < dim; i += 64) s = __fadd_rn(s, __fmul_rn(x[i], x[i]));
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s = __fadd_rn(s, __shfl_xor(s, off, 64));
+    const float norm = __fsqrt_rn(s);
+    float *o = out + (size_t)row * dim;
+    for (int i = lane; i < dim; i += 64) o[i] = __fdiv_rn(x[i], norm);
+}
+
+int launch_l2_normalize(const float *emb, int n, int dim, float *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(l2_normalize_kernel, dim3(ceil_div(n, 4)), dim3(256), 0, s, emb, n, dim, out);
     RFD_HIP(hipGetLastError());
     return RFD_OK;
 }

@@ -24,6 +24,7 @@ RFD_ERR_STATE = -5
 RFD_ERR_IO = -6
 RFD_ERR_COMM = -7
 COMM_ID_BYTES = 128
+MAX_FACE_TENSORS = 4   # RFD_MAX_FACE_TENSORS
 
 # debug_set_conv_tile / op_kernels_static: the forced tiles, enum ConvTile of csrc/kernels.h (each value's meaning is there)
 (TILE_HEURISTIC, TILE_128, TILE_256x128, TILE_256x64, TILE_NO_128, TILE_NO_PW_STREAM, TILE_PERSISTENT, TILE_GENERIC, TILE_PW_STREAM,
@@ -91,6 +92,16 @@ class rfd_alignment_config(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+class rfd_face_tensor_config(C.Structure):
+    _fields_ = [("out_w", C.c_int32), ("out_h", C.c_int32), ("mean", C.c_float * 3), ("scale", C.c_float * 3),
+                ("reserved", C.c_int32 * 4)]
+
+
+class rfd_faces(C.Structure):
+    _fields_ = [("box", C.c_void_p), ("kps", C.c_void_p), ("found", C.c_void_p), ("crops", C.c_void_p),
+                ("status", C.c_void_p), ("tensors", C.c_void_p * MAX_FACE_TENSORS)]
+
+
 class rfd_tensor_desc(C.Structure):
     _fields_ = [("channels", C.c_int), ("height", C.c_int), ("width", C.c_int),
                 ("is_f32", C.c_int), ("buffer", C.c_int), ("is_input", C.c_int),
@@ -112,6 +123,9 @@ API_SYMBOLS = [
     "rfd_alignment_config_default", "rfd_align_faces", "rfd_detect_select_align_batch",
     "rfd_host_alloc", "rfd_host_free", "rfd_submit_batch", "rfd_collect_batch",
     "rfd_comm_get_unique_id", "rfd_comm_init", "rfd_comm_info", "rfd_gather_detections", "rfd_comm_destroy",
+    "rfd_face_tensor_config_quality", "rfd_face_tensor_config_extraction", "rfd_face_tensors",
+    "rfd_align_faces_tensors", "rfd_detect_select_align_tensors_batch", "rfd_detect_faces_device", "rfd_quality_decide", "rfd_normalize_embeddings",
+    "rfd_quality_decide_device", "rfd_normalize_embeddings_device",
 ]
 
 _lib = None
@@ -197,6 +211,17 @@ def load_library(path=None):
     L.rfd_alignment_config_default.restype = None
     L.rfd_align_faces.argtypes = [vp, C.POINTER(rfd_image), ci, vp, vp, vp, vp, vp, vp]
     L.rfd_detect_select_align_batch.argtypes = [vp, C.POINTER(rfd_image), ci, vp, ci, vp, vp, vp, vp, vp, vp]
+    for f in (L.rfd_face_tensor_config_quality, L.rfd_face_tensor_config_extraction):
+        f.argtypes = [C.POINTER(rfd_face_tensor_config)]
+        f.restype = None
+    L.rfd_face_tensors.argtypes = [vp, vp, ci, ci, ci, vp, ci, C.POINTER(vp)]
+    L.rfd_detect_select_align_tensors_batch.argtypes = [vp, C.POINTER(rfd_image), ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, C.POINTER(vp)]
+    L.rfd_align_faces_tensors.argtypes = [vp, C.POINTER(rfd_image), ci, vp, vp, vp, vp, vp, vp, vp, ci, C.POINTER(vp)]
+    L.rfd_detect_faces_device.argtypes = [vp, C.POINTER(rfd_image), ci, vp, ci, vp, vp, ci, C.POINTER(rfd_faces), ci]
+    L.rfd_quality_decide.argtypes = [vp, vp, ci, ci, C.c_float, vp, vp]
+    L.rfd_quality_decide_device.argtypes = [vp, vp, ci, ci, C.c_float, vp, vp]
+    L.rfd_normalize_embeddings.argtypes = [vp, vp, ci, ci, vp]
+    L.rfd_normalize_embeddings_device.argtypes = [vp, vp, ci, ci, vp]
     if path is None:
         _lib = L
     return L
@@ -206,6 +231,38 @@ def _check(status):
     if status < 0:
         raise RfdError(status, load_library().rfd_last_error().decode("utf-8", "replace"))
     return status
+
+
+def face_tensor_config(image_size, mean, scale):
+    """rfd_face_tensor_config of a model: image_size (w, h); mean, scale per output channel R, G, B"""
+    c = rfd_face_tensor_config()
+    c.out_w, c.out_h = int(image_size[0]), int(image_size[1])
+    for i in range(3):
+        c.mean[i], c.scale[i] = mean[i], scale[i]
+    return c
+
+
+def face_tensor_config_quality():
+    """the input of the quality model (face_quality.rs:43-44): 112 x 112, ImageNet mean / reciprocal std"""
+    c = rfd_face_tensor_config()
+    load_library().rfd_face_tensor_config_quality(C.byref(c))
+    return c
+
+
+def face_tensor_config_extraction():
+    """the input of the ID model (face_extraction.rs:38-39): 112 x 112, (p - 127.5) / 128"""
+    c = rfd_face_tensor_config()
+    load_library().rfd_face_tensor_config_extraction(C.byref(c))
+    return c
+
+
+def _face_tensor_args(cfgs, n):
+    """(config array, output arrays, pointer array) of n faces; sizes the library would refuse get a 1-element stand-in"""
+    k = len(cfgs)
+    arr = (rfd_face_tensor_config * max(k, 1))(*cfgs)
+    outs = [np.zeros((n, 3, max(c.out_h, 1), max(c.out_w, 1)), np.float32) for c in cfgs]
+    ptrs = (C.c_void_p * max(k, 1))(*[o.ctypes.data for o in outs])
+    return arr, outs, ptrs
 
 
 def op_kernels_static(backbone, image_w, image_h, n, op, co_running=True, tile=0, schedule=SCHEDULE_THROUGHPUT, cus=256):
@@ -537,6 +594,88 @@ class RetinaFaceDetection:
                                                      C.addressof(c), ob.ctypes.data, ok.ctypes.data, fd.ctypes.data,
                                                      crops.ctypes.data, status.ctypes.data))
         return self._sel_out(ob, ok, fd), crops, status
+
+    # ---- the model inputs of the quality / ID stages and what follows their models (rfd.h) ----
+    def face_tensors(self, crops, cfgs):
+        """crops [n, h, w, 3] u8 BGR -> one [n, 3, out_h, out_w] f32 array (R, G, B planes) per config"""
+        crops = np.ascontiguousarray(crops, np.uint8)
+        assert crops.ndim == 4 and crops.shape[3] == 3
+        n, h, w = crops.shape[:3]
+        arr, outs, ptrs = _face_tensor_args(cfgs, n)
+        _check(self._L.rfd_face_tensors(self._ctx, crops.ctypes.data, n, w, h, C.addressof(arr), len(cfgs), ptrs))
+        return outs
+
+    def align_faces_tensors(self, frames, selected, cfgs, image_size=None, standard_landmarks=None, want_crops=True):
+        """align_faces plus the model inputs of every face -> (crops or None, status, tensors)"""
+        arr, keep = self._images(frames)
+        n = len(frames)
+        ob, ok, fd = np.zeros((n, 5), np.float32), np.zeros((n, 10), np.float32), np.zeros(n, np.int32)
+        for i, (b, k) in enumerate(selected):
+            if b is not None:
+                ob[i] = b
+                fd[i] |= 1
+            if k is not None:
+                ok[i] = np.asarray(k, np.float32).reshape(10)
+                fd[i] |= 2
+        c = self._align_cfg(image_size, standard_landmarks)
+        crops = np.zeros((n, c.out_h, c.out_w, 3), np.uint8) if want_crops else None
+        status = np.zeros(n, np.int32)
+        tc, outs, ptrs = _face_tensor_args(cfgs, n)
+        _check(self._L.rfd_align_faces_tensors(self._ctx, arr, n, ob.ctypes.data, ok.ctypes.data, fd.ctypes.data, C.addressof(c),
+                                               crops.ctypes.data if want_crops else None, status.ctypes.data,
+                                               C.addressof(tc), len(cfgs), ptrs))
+        return crops, status, outs
+
+    def detect_select_align_tensors(self, frames, cfgs, is_enroll=False, sel_cfg=None, image_size=None, standard_landmarks=None,
+                                    want_crops=True):
+        """detect_select_align plus the model inputs of every face -> (selected list, crops or None, status, tensors)"""
+        arr, keep = self._images(frames)
+        n = len(frames)
+        ob, ok, fd = np.zeros((n, 5), np.float32), np.zeros((n, 10), np.float32), np.zeros(n, np.int32)
+        sc = self._sel_cfg(sel_cfg)
+        c = self._align_cfg(image_size, standard_landmarks)
+        crops = np.zeros((n, c.out_h, c.out_w, 3), np.uint8) if want_crops else None
+        status = np.zeros(n, np.int32)
+        tc, outs, ptrs = _face_tensor_args(cfgs, n)
+        _check(self._L.rfd_detect_select_align_tensors_batch(self._ctx, arr, n, C.addressof(sc), 1 if is_enroll else 0,
+                                                             C.addressof(c), ob.ctypes.data, ok.ctypes.data, fd.ctypes.data,
+                                                             crops.ctypes.data if want_crops else None, status.ctypes.data,
+                                                             C.addressof(tc), len(cfgs), ptrs))
+        return self._sel_out(ob, ok, fd), crops, status, outs
+
+    def detect_faces_device(self, frame_ptrs, shapes, cfgs, box_ptr, kps_ptr, found_ptr, crops_ptr, status_ptr, tensor_ptrs,
+                            is_enroll=False, sel_cfg=None, image_size=None, standard_landmarks=None, async_=False):
+        """Frames and every output already in device memory (raw device addresses; crops_ptr may be None); enqueued on the
+        context's stream, with no host synchronisation when async_ is set (then sync() before reading)."""
+        n = len(frame_ptrs)
+        arr = (rfd_image * n)()
+        for i, (p, (h, w)) in enumerate(zip(frame_ptrs, shapes)):
+            arr[i].data, arr[i].height, arr[i].width, arr[i].stride = p, h, w, w * 3
+        sc = self._sel_cfg(sel_cfg)
+        c = self._align_cfg(image_size, standard_landmarks)
+        tc = (rfd_face_tensor_config * max(len(cfgs), 1))(*cfgs)
+        out = rfd_faces(box_ptr, kps_ptr, found_ptr, crops_ptr, status_ptr)
+        for j, p in enumerate(tensor_ptrs):
+            out.tensors[j] = p
+        _check(self._L.rfd_detect_faces_device(self._ctx, arr, n, C.addressof(sc), 1 if is_enroll else 0, C.addressof(c),
+                                               C.addressof(tc), len(cfgs), C.byref(out), int(async_)))
+
+    def quality_decide(self, logits, threshold):
+        """logits [n, classes] of the quality model -> (score [n] f32, klass [n] i32), face_quality.rs:159-168"""
+        x = np.ascontiguousarray(logits, np.float32)
+        assert x.ndim == 2
+        score, klass = np.zeros(x.shape[0], np.float32), np.zeros(x.shape[0], np.int32)
+        _check(self._L.rfd_quality_decide(self._ctx, x.ctypes.data, x.shape[0], x.shape[1], float(threshold), score.ctypes.data,
+                                          klass.ctypes.data))
+        return score, klass
+
+    def normalize_embeddings(self, emb):
+        """emb [n, dim] of the ID model -> emb / its L2 norm per row, utils.rs:148-154"""
+        x = np.ascontiguousarray(emb, np.float32)
+        assert x.ndim == 2
+        out = np.zeros_like(x)
+        _check(self._L.rfd_normalize_embeddings(self._ctx, x.ctypes.data, x.shape[0], x.shape[1], out.ctypes.data))
+        return out
 
     # ---- stage-level entry points ----
     def preprocess(self, frames):
