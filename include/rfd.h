@@ -404,6 +404,69 @@ RFD_API int rfd_normalize_embeddings(rfd_ctx *ctx, const float *emb, int n, int 
 RFD_API int rfd_quality_decide_device(rfd_ctx *ctx, const float *logits, int n, int classes, float threshold, float *score,
                                       int32_t *klass);
 RFD_API int rfd_normalize_embeddings_device(rfd_ctx *ctx, const float *emb, int n, int dim, float *out);
+/* The FaceQualityAssessment preset (src/pipeline/module/face_quality_assessment.rs:50-76): resize to the caller's w x h (the
+ * reference reads it from its config), BGR -> RGB, (p - 127.5) * 0.00784313725 (the f32 value of that literal).  The existing
+ * face-tensor entry points run it.  Its decision (:150-155) is `logit[0] > threshold ? 1 : 0` on the model's single logit: a
+ * comparison the caller writes; it has no entry point here. */
+RFD_API void rfd_face_tensor_config_quality_assessment(rfd_face_tensor_config *cfg, int w, int h);
+
+/* ---- liveness: FaceAntiSpoofing::call (src/pipeline/module/face_antispoofing.rs), the other consumer of the selected box.
+ *      The k miniFAS models are remote, like the quality and the ID model; this is what the reference runs on the CPU around
+ *      them.  Before the models, per face (_get_scale_image :245-295): a crop box 0.94 x the box height wide around the box
+ *      centre, then per model j (_get_new_box :342-385) that box scaled by min(scale[j], what the frame allows), shifted back
+ *      into the frame, truncated to integer corners; Mat::roi + cv::resize(INTER_LINEAR) to out_w[j] x out_h[j] :323-337;
+ *      planes of raw 0..255 floats in the frame's own channel order -- B, G, R for the library's BGR frames, where the
+ *      detector's tensor is R, G, B (_preprocess :180-217: its cvt_color and its `2 - i` store cancel).  All f32 arithmetic
+ *      is done in the reference's order with one rounding per operation; `as i32` truncates, saturates and maps NaN to 0;
+ *      the i32 sums wrap (a release build).  Byte-exact against the oracle's restated cv::resize, parity against a running
+ *      OpenCV unpinned, like alignment.  weights[i][j] = used scale / scale[j] (1 unless the frame capped the scale).
+ *      After the models (_postprocess :219-243): the weighted mean of column 1 of the k outputs, live iff it exceeds a
+ *      threshold.
+ *      Divergences, both on purpose: (1) `call` :58-81 inserts one-image lists at index i for every image, so a
+ *      call with more than one image does not pair images with weights; the stage is defined PER FACE here, each face equal
+ *      to a single-image call, and the batch is not zero-padded to a multiple of batch_size.  (2) `_postprocess` zips the k
+ *      outputs with a list of ONE weight, so as written only the first model counts (o0 * w0 / w0); rfd_liveness_decide
+ *      computes the weighted mean over all k models that the function's structure and its computed weights are for.  The
+ *      reference-as-written result is the k = 1 call on the first model's logits.  The reference compares with the literal
+ *      0.55 (its `threshold` field is never read); here the threshold is an argument. ---- */
+typedef struct rfd_liveness_config {
+    int32_t k;                            /* models, 1 .. RFD_MAX_FACE_TENSORS */
+    float   scale[RFD_MAX_FACE_TENSORS];  /* scales[j]: finite, > 0 */
+    int32_t out_w[RFD_MAX_FACE_TENSORS];  /* image_sizes[j].0 */
+    int32_t out_h[RFD_MAX_FACE_TENSORS];  /* image_sizes[j].1 */
+    int32_t reserved[4];
+} rfd_liveness_config;
+/* The four models the reference names (:448-485): scale 4.0 -> 80x80, 2.7 -> 80x80, 2.0 -> 256x256, 1.0 -> 128x128. */
+RFD_API void rfd_liveness_config_default(rfd_liveness_config *cfg);
+/* Stage-level, host pointers: frames, boxes [n][5] and found [n] as rfd_select_faces / rfd_detect_select_batch return them
+ * (only x1, y1, x2, y2 and bit 0 of found are read), cfg (NULL: the default) -> tensors[j] [n][3][out_h[j]][out_w[j]] f32,
+ * weights [n][k], rois [n][k][4] = ltx, lty, rbx, rby of every model's ROI (may be NULL), status [n]: 0 ok, -2 no face (bit 0
+ * of found[i] clear), -3 some model's ROI is not inside the frame or is empty (the reference's Mat::roi / cv::resize return
+ * Err for the whole face).  A face with a negative status gets all-zero tensors and weights 0; its rois hold what was
+ * computed (-3) or 0 (-2).  n <= max_batch_size; k > RFD_MAX_FACE_TENSORS: RFD_ERR_CAPACITY; a non-positive size or a scale
+ * that is not finite and positive: RFD_ERR_INVALID_ARG.  The staging memory of this stage is allocated by its first call. */
+RFD_API int rfd_liveness_tensors(rfd_ctx *ctx, const rfd_image *imgs, int n, const float *boxes, const int32_t *found,
+                                 const rfd_liveness_config *cfg, float *const *tensors, float *weights, int32_t *rois,
+                                 int32_t *status);
+/* The device-resident form (conventions of rfd_detect_faces_device): every imgs[i].data and every other pointer is DEVICE
+ * memory (imgs[], cfg and the tensors[] array itself are host memory).  Enqueued on the context's stream; async = 0 returns
+ * after the stream has drained, any other value at once.  boxes / found may be the box / found arrays rfd_detect_faces_device
+ * has just been asked to fill on the same stream: detection, selection, alignment, the ID / quality tensors and the liveness
+ * tensors then run back to back with no host synchronisation in between. */
+RFD_API int rfd_liveness_tensors_device(rfd_ctx *ctx, const rfd_image *imgs, int n, const float *boxes, const int32_t *found,
+                                        const rfd_liveness_config *cfg, float *const *tensors, float *weights, int32_t *rois,
+                                        int32_t *status, int async);
+/* The decision rule on the outputs of k models (any k >= 1), logits[j] = [n][classes] f32 with classes >= 2, weights [n][k] as
+ * the tensor call returned them: score[i] = (((0 + l0*w0) + l1*w1) + ...) / ((0 + w0) + w1 + ...) with l_j = logits[j][i][1],
+ * every operation one f32 rounding in this order; live[i] = score[i] > threshold (strict; the reference's literal is 0.55).
+ * Weights that sum to 0 -- every face with a negative status -- give score NaN and live 0, as the reference's division would.
+ * Host pointers.  No output may overlap an input, except that score may be weights when k = 1. */
+RFD_API int rfd_liveness_decide(rfd_ctx *ctx, const float *const *logits, int k, int n, int classes, const float *weights,
+                                float threshold, float *score, int32_t *live);
+/* The same with DEVICE pointers (the logits[] array itself is host memory), enqueued on the context's stream (no
+ * synchronisation). */
+RFD_API int rfd_liveness_decide_device(rfd_ctx *ctx, const float *const *logits, int k, int n, int classes,
+                                       const float *weights, float threshold, float *score, int32_t *live);
 
 /* ---- introspection ---- */
 RFD_API int rfd_get_stats(rfd_ctx *ctx, rfd_stats *stats);

@@ -234,5 +234,47 @@ inline std::vector<float> normalize_embeddings(RetinaFaceDetection &det, const s
     return out;
 }
 
+// FaceAntiSpoofing (face_antispoofing.rs) minus the remote miniFAS models: FAS config, the model inputs, the decision rule.
+// Defined per face (rfd.h: the reference's two bugs are not copied).
+struct LivenessConfig : rfd_liveness_config {
+    LivenessConfig() { rfd_liveness_config_default(this); }   // the four models the reference names (:448-485)
+};
+struct LivenessInputs {
+    std::vector<std::vector<float>> tensors;   // per model: [n][3][out_h][out_w], B, G, R planes, raw 0..255
+    std::vector<float> weights;                // [n][k]
+    std::vector<int32_t> rois;                 // [n][k][4] ltx, lty, rbx, rby
+    std::vector<int32_t> status;               // [n]: 0 ok, -2 no face, -3 a ROI outside the frame (the reference returns Err)
+};
+// _get_scale_image + _preprocess for n frames and their selected boxes [n][5] / flags [n]
+inline LivenessInputs liveness_tensors(RetinaFaceDetection &det, const std::vector<rfd_image> &imgs, const float *boxes,
+                                       const int32_t *found, const LivenessConfig &cfg = LivenessConfig())
+{
+    const std::size_t n = imgs.size(), k = cfg.k > 0 && cfg.k <= RFD_MAX_FACE_TENSORS ? (std::size_t)cfg.k : 0;
+    LivenessInputs r;
+    r.tensors.resize(k);
+    std::vector<float *> ptrs(k ? k : 1, nullptr);
+    for (std::size_t j = 0; j < k; ++j) {
+        r.tensors[j].resize(n * 3 * (cfg.out_w[j] > 0 ? cfg.out_w[j] : 0) * (cfg.out_h[j] > 0 ? cfg.out_h[j] : 0));
+        ptrs[j] = r.tensors[j].data();
+    }
+    r.weights.resize(n * k); r.rois.resize(n * k * 4); r.status.resize(n);
+    check(rfd_liveness_tensors(det.raw(), imgs.data(), (int)n, boxes, found, &cfg, ptrs.data(), r.weights.data(), r.rois.data(),
+                               r.status.data()));
+    return r;
+}
+// _postprocess on logits[j] = [n][classes] of every model -> (scores, live flags); the reference's literal threshold is 0.55
+inline std::pair<std::vector<float>, std::vector<int32_t>> liveness_decide(RetinaFaceDetection &det,
+                                                                            const std::vector<std::vector<float>> &logits, int n,
+                                                                            int classes, const std::vector<float> &weights,
+                                                                            float threshold = 0.55f)
+{
+    std::vector<const float *> ptrs;
+    for (const std::vector<float> &l : logits) ptrs.push_back(l.data());
+    std::vector<float> score(n);
+    std::vector<int32_t> live(n);
+    check(rfd_liveness_decide(det.raw(), ptrs.data(), (int)ptrs.size(), n, classes, weights.data(), threshold, score.data(), live.data()));
+    return {score, live};
+}
+
 } // namespace rfd
 #endif

@@ -203,6 +203,12 @@ struct rfd_ctx {
     int *pin_dims[kRing] = {};
     hipEvent_t pin_dims_done[kRing] = {};
     int pin_dims_next = 0;
+    // liveness stage, all allocated by its first call: frame descriptors (through a page-locked ring, like pin_imgs), the
+    // per-(face, model) geometry, the in / out staging of the host forms, the running sums of a decide call of many models
+    DevBuf live_imgs, live_geo, live_io, live_acc;
+    LiveImage *pin_live[kRing] = {};
+    hipEvent_t pin_live_done[kRing] = {};
+    int pin_live_next = 0;
     // pipelined host entry (rfd_submit_batch / rfd_collect_batch): two slots, H2D on its own stream
     struct PipeSlot {
         DevBuf frames, imgs, scale, ob, ol, oc, ot;
@@ -678,6 +684,11 @@ void rfd_destroy(rfd_ctx *c)
     c->align_faces.release(); c->align_out.release(); c->align_status.release();
     c->face_in.release(); c->face_io[0].release(); c->face_io[1].release();
     for (DevBuf &b : c->face_tensors) b.release();
+    c->live_imgs.release(); c->live_geo.release(); c->live_io.release(); c->live_acc.release();
+    for (int i = 0; i < rfd_ctx::kRing; ++i) {
+        if (c->pin_live[i]) (void)hipHostFree(c->pin_live[i]);
+        if (c->pin_live_done[i]) (void)hipEventDestroy(c->pin_live_done[i]);
+    }
     for (int i = 0; i < 10; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     for (int i = 0; i < rfd_ctx::kRing; ++i) {
@@ -1869,6 +1880,195 @@ int rfd_normalize_embeddings(rfd_ctx *c, const float *emb, int n, int dim, float
     RFD_HIP(hipMemcpyAsync(c->face_io[0].p, emb, bytes, hipMemcpyHostToDevice, c->stream));
     RFD_TRY(rfd_normalize_embeddings_device(c, (const float *)c->face_io[0].p, n, dim, (float *)c->face_io[1].p));
     RFD_HIP(hipMemcpyAsync(out, c->face_io[1].p, bytes, hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    return RFD_OK;
+}
+
+// ---- liveness (face_antispoofing.rs): the inputs of the miniFAS models from the frame and the selected box, and the rule
+//      on their outputs.  The models themselves are remote, like the quality and the ID model. ----
+void rfd_face_tensor_config_quality_assessment(rfd_face_tensor_config *cfg, int w, int h)
+{
+    if (!cfg) return;
+    memset(cfg, 0, sizeof *cfg);
+    cfg->out_w = w; cfg->out_h = h;
+    for (int i = 0; i < 3; ++i) { cfg->mean[i] = 127.5f; cfg->scale[i] = 0.00784313725f; } // face_quality_assessment.rs:76
+}
+
+void rfd_liveness_config_default(rfd_liveness_config *cfg)
+{
+    if (!cfg) return;
+    memset(cfg, 0, sizeof *cfg);
+    // face_antispoofing.rs:448-485, the only place that names the models: miniFAS_4, miniFAS_2_7, miniFAS_2, miniFAS_1
+    static const float scale[4] = {4.0f, 2.7f, 2.0f, 1.0f};
+    static const int32_t size[4] = {80, 80, 256, 128};
+    cfg->k = 4;
+    for (int j = 0; j < 4; ++j) { cfg->scale[j] = scale[j]; cfg->out_w[j] = cfg->out_h[j] = size[j]; }
+}
+
+static int check_liveness_cfg(const rfd_liveness_config *cfg)
+{
+    if (cfg->k > RFD_MAX_FACE_TENSORS) { set_error("liveness config: k = %d exceeds RFD_MAX_FACE_TENSORS (%d)", cfg->k, RFD_MAX_FACE_TENSORS); return RFD_ERR_CAPACITY; }
+    if (cfg->k < 1) { set_error("invalid argument: liveness config: k = %d, at least one model is needed", cfg->k); return RFD_ERR_INVALID_ARG; }
+    for (int j = 0; j < cfg->k; ++j) {
+        if (cfg->out_w[j] < 1 || cfg->out_w[j] > 4096) { set_error("invalid argument: liveness config: out_w[%d] = %d out of range", j, cfg->out_w[j]); return RFD_ERR_INVALID_ARG; }
+        if (cfg->out_h[j] < 1 || cfg->out_h[j] > 4096) { set_error("invalid argument: liveness config: out_h[%d] = %d out of range", j, cfg->out_h[j]); return RFD_ERR_INVALID_ARG; }
+        if (!(cfg->scale[j] > 0.0f && cfg->scale[j] <= 3.402823466e38f)) { set_error("invalid argument: liveness config: scale[%d] = %g is not finite and positive", j, (double)cfg->scale[j]); return RFD_ERR_INVALID_ARG; }
+    }
+    return RFD_OK;
+}
+
+// Both kernels of the tensor call on DEVICE boxes / flags into DEVICE outputs; enqueued only.  The frame descriptors go
+// through a ring of page-locked arrays, so nothing here waits for the stream; host frames are staged first.
+static int liveness_enqueue(rfd_ctx *c, const rfd_image *imgs, int n, bool frames_on_device, const float *d_box, const int *d_found,
+                            const rfd_liveness_config *cfg, float *const *d_tensors, float *d_weights, int32_t *d_rois,
+                            int32_t *d_status)
+{
+    const size_t B = (size_t)c->cfg.max_batch_size;
+    for (int i = 0; i < rfd_ctx::kRing; ++i) { // first call on this context
+        if (!c->pin_live[i]) RFD_HIP(hipHostMalloc((void **)&c->pin_live[i], B * sizeof(LiveImage)));
+        if (!c->pin_live_done[i]) RFD_HIP(hipEventCreateWithFlags(&c->pin_live_done[i], hipEventDisableTiming));
+    }
+    RFD_TRY(c->live_imgs.reserve(B * sizeof(LiveImage)));
+    RFD_TRY(c->live_geo.reserve(B * kMaxFaceTensors * sizeof(LiveRoi)));
+    const int slot = c->pin_live_next;
+    c->pin_live_next = (c->pin_live_next + 1) % rfd_ctx::kRing;
+    RFD_HIP(hipEventSynchronize(c->pin_live_done[slot])); // the copy that last used this slot has run
+    LiveImage *li = c->pin_live[slot];
+    if (!frames_on_device) {
+        size_t total = 0;
+        for (int i = 0; i < n; ++i) total += (size_t)imgs[i].height * imgs[i].width * 3;
+        RFD_TRY(c->staging.reserve(total));
+    }
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        li[i].h = imgs[i].height; li[i].w = imgs[i].width;
+        if (frames_on_device) {
+            li[i].src = imgs[i].data;
+            li[i].stride = (long long)imgs[i].stride;
+        } else {
+            uint8_t *dst = (uint8_t *)c->staging.p + off;
+            const size_t row = (size_t)imgs[i].width * 3;
+            RFD_HIP(hipMemcpy2DAsync(dst, row, imgs[i].data, (size_t)imgs[i].stride, row, imgs[i].height, hipMemcpyHostToDevice, c->stream));
+            li[i].src = dst;
+            li[i].stride = (long long)row;
+            off += row * imgs[i].height;
+        }
+    }
+    RFD_HIP(hipMemcpyAsync(c->live_imgs.p, li, n * sizeof(LiveImage), hipMemcpyHostToDevice, c->stream));
+    RFD_HIP(hipEventRecord(c->pin_live_done[slot], c->stream));
+    LiveParams p;
+    memset(&p, 0, sizeof p);
+    p.imgs = (const LiveImage *)c->live_imgs.p;
+    p.box = d_box; p.found = d_found;
+    p.n = n; p.k = cfg->k;
+    for (int j = 0; j < cfg->k; ++j) {
+        p.cfg[j].out = d_tensors[j]; p.cfg[j].scale = cfg->scale[j];
+        p.cfg[j].out_w = cfg->out_w[j]; p.cfg[j].out_h = cfg->out_h[j];
+        p.cfg[j].tile0 = p.tiles;
+        p.tiles += ceil_div(cfg->out_w[j] * cfg->out_h[j], 256);
+    }
+    p.geo = (LiveRoi *)c->live_geo.p;
+    p.weights = d_weights; p.rois = d_rois; p.status = d_status;
+    return launch_liveness_tensors(p, c->stream);
+}
+
+static int check_liveness_args(rfd_ctx *c, const rfd_image *imgs, int n, const float *boxes, const int32_t *found,
+                               const rfd_liveness_config **cfg, rfd_liveness_config *def, float *const *tensors,
+                               const float *weights, const int32_t *status)
+{
+    RFD_CHECK_ARG(c && boxes && found && tensors && weights && status, "null argument");
+    if (!*cfg) { rfd_liveness_config_default(def); *cfg = def; }
+    RFD_TRY(check_liveness_cfg(*cfg));
+    for (int j = 0; j < (*cfg)->k; ++j)
+        if (!tensors[j]) { set_error("invalid argument: tensor pointer %d is null", j); return RFD_ERR_INVALID_ARG; }
+    return check_images(c, imgs, n);
+}
+
+int rfd_liveness_tensors_device(rfd_ctx *c, const rfd_image *imgs, int n, const float *boxes, const int32_t *found,
+                                const rfd_liveness_config *cfg, float *const *tensors, float *weights, int32_t *rois,
+                                int32_t *status, int async)
+{
+    rfd_liveness_config def;
+    RFD_TRY(check_liveness_args(c, imgs, n, boxes, found, &cfg, &def, tensors, weights, status));
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    RFD_TRY(liveness_enqueue(c, imgs, n, true, boxes, found, cfg, tensors, weights, rois, status));
+    if (async) return RFD_OK;
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    return check_nms_flag(c);
+}
+
+int rfd_liveness_tensors(rfd_ctx *c, const rfd_image *imgs, int n, const float *boxes, const int32_t *found,
+                         const rfd_liveness_config *cfg, float *const *tensors, float *weights, int32_t *rois, int32_t *status)
+{
+    rfd_liveness_config def;
+    RFD_TRY(check_liveness_args(c, imgs, n, boxes, found, &cfg, &def, tensors, weights, status));
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    const int k = cfg->k;
+    // box [n][5] | found [n] | weights [n][k] | rois [n][k][4] | status [n]: all 4-byte words
+    RFD_TRY(c->live_io.reserve((size_t)n * (5 + 1 + k + 4 * k + 1) * 4));
+    float *d_box = (float *)c->live_io.p;
+    int32_t *d_found = (int32_t *)(d_box + (size_t)n * 5);
+    float *d_weights = (float *)(d_found + n);
+    int32_t *d_rois = (int32_t *)(d_weights + (size_t)n * k), *d_status = d_rois + (size_t)n * k * 4;
+    float *d_tensors[kMaxFaceTensors] = {};
+    size_t bytes[kMaxFaceTensors] = {};
+    for (int j = 0; j < k; ++j) {
+        bytes[j] = (size_t)n * 3 * cfg->out_w[j] * cfg->out_h[j] * sizeof(float);
+        RFD_TRY(c->face_tensors[j].reserve(bytes[j]));
+        d_tensors[j] = (float *)c->face_tensors[j].p;
+    }
+    RFD_HIP(hipMemcpyAsync(d_box, boxes, (size_t)n * 5 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    RFD_HIP(hipMemcpyAsync(d_found, found, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    RFD_TRY(liveness_enqueue(c, imgs, n, false, d_box, d_found, cfg, d_tensors, d_weights, d_rois, d_status));
+    for (int j = 0; j < k; ++j) RFD_HIP(hipMemcpyAsync(tensors[j], d_tensors[j], bytes[j], hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipMemcpyAsync(weights, d_weights, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (rois) RFD_HIP(hipMemcpyAsync(rois, d_rois, (size_t)n * k * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipMemcpyAsync(status, d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    return check_nms_flag(c);
+}
+
+int rfd_liveness_decide_device(rfd_ctx *c, const float *const *logits, int k, int n, int classes, const float *weights,
+                               float threshold, float *score, int32_t *live)
+{
+    RFD_CHECK_ARG(c && logits && weights && score && live, "null argument");
+    RFD_CHECK_ARG(k >= 1 && n >= 1 && classes >= 2, "k < 1, n < 1 or classes < 2");
+    for (int j = 0; j < k; ++j)
+        if (!logits[j]) { set_error("invalid argument: logits pointer %d is null", j); return RFD_ERR_INVALID_ARG; }
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    if (k > kLiveDecideChunk) RFD_TRY(c->live_acc.reserve((size_t)n * 2 * sizeof(float)));
+    for (int j0 = 0; j0 < k; j0 += kLiveDecideChunk) {
+        LiveLogits l;
+        memset(&l, 0, sizeof l);
+        const int kc = std::min(kLiveDecideChunk, k - j0);
+        for (int q = 0; q < kc; ++q) l.p[q] = logits[j0 + q];
+        RFD_TRY(launch_liveness_decide(l, kc, k, j0, n, classes, weights, threshold, (float *)c->live_acc.p, score, live, c->stream));
+    }
+    return RFD_OK;
+}
+
+int rfd_liveness_decide(rfd_ctx *c, const float *const *logits, int k, int n, int classes, const float *weights, float threshold,
+                        float *score, int32_t *live)
+{
+    RFD_CHECK_ARG(c && logits && weights && score && live, "null argument");
+    RFD_CHECK_ARG(k >= 1 && n >= 1 && classes >= 2, "k < 1, n < 1 or classes < 2");
+    for (int j = 0; j < k; ++j)
+        if (!logits[j]) { set_error("invalid argument: logits pointer %d is null", j); return RFD_ERR_INVALID_ARG; }
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    const size_t one = (size_t)n * classes;
+    // logits [k][n][classes] | weights [n][k] | score [n] | live [n]
+    RFD_TRY(c->live_io.reserve(((size_t)k * one + (size_t)n * k + 2 * (size_t)n) * 4));
+    float *d_logits = (float *)c->live_io.p, *d_weights = d_logits + (size_t)k * one, *d_score = d_weights + (size_t)n * k;
+    int32_t *d_live = (int32_t *)(d_score + n);
+    std::vector<const float *> ptrs(k);
+    for (int j = 0; j < k; ++j) {
+        ptrs[j] = d_logits + (size_t)j * one;
+        RFD_HIP(hipMemcpyAsync(d_logits + (size_t)j * one, logits[j], one * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    }
+    RFD_HIP(hipMemcpyAsync(d_weights, weights, (size_t)n * k * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    RFD_TRY(rfd_liveness_decide_device(c, ptrs.data(), k, n, classes, d_weights, threshold, d_score, d_live));
+    RFD_HIP(hipMemcpyAsync(score, d_score, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipMemcpyAsync(live, d_live, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     RFD_HIP(hipStreamSynchronize(c->stream));
     return RFD_OK;
 }

@@ -139,6 +139,46 @@ int launch_quality_decide(const float *logits, int n, int classes, float thresho
 // out = emb / sqrt(sum emb^2) per row (utils.rs:148-154), one wave64 per row, deterministic
 int launch_l2_normalize(const float *emb, int n, int dim, float *out, hipStream_t s);
 
+// FaceAntiSpoofing (face_antispoofing.rs): the inputs of the miniFAS models from the source frame and the selected box --
+// _get_scale_image :245-295, _get_new_box :342-385, Mat::roi + cv::resize(INTER_LINEAR) :323-337, _preprocess :180-217 --
+// and the rule on their outputs, _postprocess :219-243.
+struct LiveImage {
+    const uint8_t *src; // device, HxWx3 u8 BGR
+    long long stride;   // bytes per source row
+    int h, w;
+};
+struct LiveRoi {             // per (face, model), filled by the geometry kernel
+    double scale_x, scale_y; // 1 / (out_w / rw), 1 / (out_h / rh) in f64, as cv::resize computes them
+    int x0, y0, rw, rh;      // the ROI inside the frame
+    int area_fast;           // both exactly 2: the 2x2 mean
+    int ok;                  // the FACE's status is 0 (every model's ROI is valid)
+};
+struct LiveCfg {
+    float *out;       // [n][3][out_h][out_w] f32, planes in source channel order (B, G, R), raw 0..255
+    float scale;      // scales[j]
+    int out_w, out_h; // image_sizes[j]
+    int tile0;        // first 256-pixel tile of this model in the flat tile table of the crop kernel
+};
+struct LiveParams {
+    const LiveImage *imgs; // [n]
+    const float *box;      // [n][5] selected detection (x1, y1, x2, y2, score)
+    const int *found;      // [n] selection flags: bit 0 = a box
+    int n, k, tiles;       // tiles = all 256-pixel tiles of one face's k outputs
+    LiveCfg cfg[kMaxFaceTensors];
+    LiveRoi *geo;          // [n][k] scratch
+    float *weights;        // [n][k]: scale / scales[j]; 0 for a face with a negative status
+    int *rois;             // [n][k][4] ltx, lty, rbx, rby, or null
+    int *status;           // [n]: 0 ok, -2 no face, -3 some model's ROI is not inside the frame or is empty
+};
+// geometry (one thread per face and model) + crop, resize, tensorise (one launch for all n * k outputs)
+int launch_liveness_tensors(const LiveParams &p, hipStream_t s);
+// _postprocess: score = sum_j logits[j][b][1] * w[b][j] / sum_j w[b][j] in the reference's f32 order, live = score > threshold.
+// Models [j0, j0 + kc) of k per launch (kc <= kLiveDecideChunk); the sums of a call of more models travel through acc [n][2].
+constexpr int kLiveDecideChunk = 8;
+struct LiveLogits { const float *p[kLiveDecideChunk]; };
+int launch_liveness_decide(const LiveLogits &l, int kc, int k, int j0, int n, int classes, const float *weights, float threshold,
+                           float *acc, float *score, int *live, hipStream_t s);
+
 // ---------------------------------------------------------------- convolution engine (kernels_conv.hip)
 // Activations: NHWC bf16.  Weights: [Cout][KH][KW][Cin] bf16 (K contiguous).  f32 accumulate on MFMA.
 struct ConvParams {

@@ -495,4 +495,170 @@ int launch_l2_normalize(const float *emb, int n, int dim, float *out, hipStream_
     return RFD_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// FaceAntiSpoofing (face_antispoofing.rs): the inputs of the k miniFAS models of a face, from the source frame and the
+// selected box, and the rule on their outputs.
+// Geometry: one thread per (face, model) restates _get_scale_image :245-295 and _get_new_box :342-385.  Every f32 operation
+// is a single pinned rounding (__fsub_rn ...) in the reference's order, because each result is truncated to an integer pixel
+// coordinate: a contraction or a reassociation could move a crop by a pixel.  Rust's `as i32` truncates toward zero,
+// saturates and maps NaN to 0; its i32 `+` / `-` wrap (a release build).  Mat::roi (:324) accepts a rectangle iff
+// 0 <= x, 0 <= w, x + w <= cols (same in y); cv::resize (:332) rejects an empty one: either makes the reference return Err
+// for the whole face, so the k validity bits of a face are reduced to one status.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int rust_f32_as_i32(float f)
+{
+    if (f != f) return 0;
+    if (f >= 2147483648.0f) return 2147483647;
+    if (f <= -2147483648.0f) return -2147483647 - 1;
+    return (int)f;
+}
+
+__device__ __forceinline__ float rust_f32_min(float a, float b) // f32::min: a NaN operand yields the other one
+{
+    if (a != a) return b;
+    if (b != b) return a;
+    return a < b ? a : b;
+}
+
+__device__ __forceinline__ int wrap_span(int hi, int lo) // hi - lo + 1 in wrapping i32 arithmetic
+{
+    return (int)((unsigned)hi - (unsigned)lo + 1u);
+}
+
+constexpr int kLiveGeoFaces = 64 / kMaxFaceTensors; // faces per workgroup of the geometry kernel
+
+__global__ void __launch_bounds__(64) liveness_geometry_kernel(LiveParams p)
+{
+    __shared__ int bad[kLiveGeoFaces];
+    const int fl = threadIdx.x / kMaxFaceTensors, j = threadIdx.x % kMaxFaceTensors;
+    const int b = blockIdx.x * kLiveGeoFaces + fl;
+    if (threadIdx.x < kLiveGeoFaces) bad[threadIdx.x] = 0;
+    __syncthreads();
+    const bool active = b < p.n && j < p.k;
+    const bool found = active && (p.found[b] & 1);
+    LiveRoi g;
+    memset(&g, 0, sizeof g);
+    float weight = 0.0f;
+    int ltx = 0, lty = 0, rbx = 0, rby = 0;
+    if (found) {
+        const float *det = p.box + (size_t)b * 5;
+        const LiveImage im = p.imgs[b];
+        const float scale_ori = p.cfg[j].scale;
+        // _get_scale_image :249-262
+        const float xmin = det[0], ymin = det[1], xmax = det[2], ymax = det[3];
+        const float det_height = __fsub_rn(ymax, ymin);
+        const float c_x = __fdiv_rn(__fadd_rn(xmin, xmax), 2.0f);
+        const float half = __fmul_rn(0.47f, det_height);
+        const int left = rust_f32_as_i32(__fsub_rn(c_x, half)), right = rust_f32_as_i32(__fadd_rn(c_x, half));
+        const int bx = left, by = rust_f32_as_i32(ymin);
+        const int bw = wrap_span(right, left), bh = rust_f32_as_i32(__fadd_rn(__fsub_rn(ymax, ymin), 1.0f));
+        // _get_new_box :347-384
+        const float w1 = __fsub_rn((float)im.w, 1.0f), h1 = __fsub_rn((float)im.h, 1.0f);
+        const float scale = rust_f32_min(__fdiv_rn(h1, (float)bh), rust_f32_min(__fdiv_rn(w1, (float)bw), scale_ori));
+        const float new_w = __fmul_rn((float)bw, scale), new_h = __fmul_rn((float)bh, scale);
+        const float cx = __fadd_rn(__fdiv_rn((float)bw, 2.0f), (float)bx), cy = __fadd_rn(__fdiv_rn((float)bh, 2.0f), (float)by);
+        float fx0 = __fsub_rn(cx, __fdiv_rn(new_w, 2.0f)), fy0 = __fsub_rn(cy, __fdiv_rn(new_h, 2.0f));
+        float fx1 = __fadd_rn(cx, __fdiv_rn(new_w, 2.0f)), fy1 = __fadd_rn(cy, __fdiv_rn(new_h, 2.0f));
+        if (fx0 < 0.0f) { fx1 = __fsub_rn(fx1, fx0); fx0 = 0.0f; }
+        if (fy0 < 0.0f) { fy1 = __fsub_rn(fy1, fy0); fy0 = 0.0f; }
+        if (fx1 > w1) { fx0 = __fsub_rn(fx0, __fadd_rn(__fsub_rn(fx1, (float)im.w), 1.0f)); fx1 = w1; }
+        if (fy1 > h1) { fy0 = __fsub_rn(fy0, __fadd_rn(__fsub_rn(fy1, (float)im.h), 1.0f)); fy1 = h1; }
+        ltx = rust_f32_as_i32(fx0); lty = rust_f32_as_i32(fy0); rbx = rust_f32_as_i32(fx1); rby = rust_f32_as_i32(fy1);
+        weight = __fdiv_rn(scale, scale_ori);
+        // Mat::roi(Rect(ltx, lty, rbx - ltx + 1, rby - lty + 1)) :323-324, then cv::resize :332
+        g.x0 = ltx; g.y0 = lty; g.rw = wrap_span(rbx, ltx); g.rh = wrap_span(rby, lty);
+        const bool valid = g.x0 >= 0 && g.y0 >= 0 && g.rw > 0 && g.rh > 0 && (long long)g.x0 + g.rw <= im.w &&
+                           (long long)g.y0 + g.rh <= im.h;
+        if (valid) { // cv::resize's scale bookkeeping for this ROI (as align_setup_kernel's fallback branch)
+            g.scale_x = 1.0 / ((double)p.cfg[j].out_w / g.rw);
+            g.scale_y = 1.0 / ((double)p.cfg[j].out_h / g.rh);
+            const int ix = cv_round_sat(g.scale_x), iy = cv_round_sat(g.scale_y);
+            g.area_fast = fabs(g.scale_x - ix) < 2.220446049250313e-16 && fabs(g.scale_y - iy) < 2.220446049250313e-16 &&
+                          ix == 2 && iy == 2;
+        } else {
+            bad[fl] = 1; // every writer stores the same value
+        }
+    }
+    __syncthreads();
+    if (!active) return;
+    const int st = !found ? -2 : (bad[fl] ? -3 : 0);
+    g.ok = st == 0;
+    const size_t o = (size_t)b * p.k + j;
+    p.geo[o] = g;
+    p.weights[o] = st == 0 ? weight : 0.0f;
+    if (p.rois) { int *r = p.rois + o * 4; r[0] = ltx; r[1] = lty; r[2] = rbx; r[3] = rby; }
+    if (j == 0) p.status[b] = st;
+}
+
+// Crop, resize, tensorise: workgroup blockIdx.x of face blockIdx.y is one 256-pixel tile of the flat tile table -- the tiles
+// of model 0, then of model 1, ... (cfg[j].tile0) -- so that outputs of different sizes share one launch and no workgroup is
+// idle.  The ROI is resized as a frame of its own: resize_linear_px gets the ROI's first pixel, the frame's stride and the
+// ROI's height and width, so its wide-load guard ends at the ROI's last pixel, inside the frame.  _preprocess :188-213:
+// cvt_color(RGB2BGR) and the store to channel 2 - i cancel, plane c = byte channel c of the frame, raw 0..255.
+__global__ void __launch_bounds__(256) liveness_tensor_kernel(LiveParams p)
+{
+    const int t = blockIdx.x, b = blockIdx.y;
+    int j = 0;
+#pragma unroll
+    for (int q = 1; q < kMaxFaceTensors; ++q)
+        if (q < p.k && t >= p.cfg[q].tile0) j = q;
+    const LiveCfg &c = p.cfg[j];
+    const int i = (t - c.tile0) * 256 + threadIdx.x;
+    if (i >= c.out_w * c.out_h) return;
+    const LiveRoi &g = p.geo[(size_t)b * p.k + j];
+    int v[3] = {0, 0, 0};
+    if (g.ok) {
+        const LiveImage im = p.imgs[b];
+        const int y = i / c.out_w, x = i - y * c.out_w;
+        resize_linear_px(im.src + (long long)g.y0 * im.stride + (long long)g.x0 * 3, im.stride, g.rh, g.rw, g.scale_x, g.scale_y,
+                         g.area_fast, x, y, v);
+    }
+    const size_t plane = (size_t)c.out_w * c.out_h;
+    float *o = c.out + (size_t)b * 3 * plane + i;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) o[ch * plane] = (float)v[ch]; // a face with a negative status: 0.0f
+}
+
+int launch_liveness_tensors(const LiveParams &p, hipStream_t s)
+{
+    static_assert(64 % kMaxFaceTensors == 0, "a face's models share a wave of the geometry kernel");
+    hipLaunchKernelGGL(liveness_geometry_kernel, dim3(ceil_div(p.n, kLiveGeoFaces)), dim3(64), 0, s, p);
+    RFD_HIP(hipGetLastError());
+    hipLaunchKernelGGL(liveness_tensor_kernel, dim3(p.tiles, p.n), dim3(256), 0, s, p);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+// _postprocess :228-238 for one face per thread: live_score = live_score + column(1) * w and total_weight += w in model
+// order, one division, score > threshold.  Everything is read before anything is written (score may be weights when k = 1).
+__global__ void __launch_bounds__(64) liveness_decide_kernel(LiveLogits l, int kc, int k, int j0, int n, int classes,
+                                                            const float *weights, float threshold, float *acc, float *score,
+                                                            int *live)
+{
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= n) return;
+    float s = 0.0f, w = 0.0f;
+    if (j0 > 0) { s = acc[2 * b]; w = acc[2 * b + 1]; }
+#pragma unroll
+    for (int q = 0; q < kLiveDecideChunk; ++q)
+        if (q < kc) {
+            const float wq = weights[(size_t)b * k + j0 + q];
+            s = __fadd_rn(s, __fmul_rn(l.p[q][(size_t)b * classes + 1], wq));
+            w = __fadd_rn(w, wq);
+        }
+    if (j0 + kc < k) { acc[2 * b] = s; acc[2 * b + 1] = w; return; }
+    const float r = __fdiv_rn(s, w);
+    score[b] = r;
+    live[b] = r > threshold ? 1 : 0;
+}
+
+int launch_liveness_decide(const LiveLogits &l, int kc, int k, int j0, int n, int classes, const float *weights, float threshold,
+                           float *acc, float *score, int *live, hipStream_t s)
+{
+    hipLaunchKernelGGL(liveness_decide_kernel, dim3(ceil_div(n, 64)), dim3(64), 0, s, l, kc, k, j0, n, classes, weights, threshold,
+                       acc, score, live);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
 } // namespace rfd

@@ -102,6 +102,11 @@ class rfd_faces(C.Structure):
                 ("status", C.c_void_p), ("tensors", C.c_void_p * MAX_FACE_TENSORS)]
 
 
+class rfd_liveness_config(C.Structure):
+    _fields_ = [("k", C.c_int32), ("scale", C.c_float * MAX_FACE_TENSORS), ("out_w", C.c_int32 * MAX_FACE_TENSORS),
+                ("out_h", C.c_int32 * MAX_FACE_TENSORS), ("reserved", C.c_int32 * 4)]
+
+
 class rfd_tensor_desc(C.Structure):
     _fields_ = [("channels", C.c_int), ("height", C.c_int), ("width", C.c_int),
                 ("is_f32", C.c_int), ("buffer", C.c_int), ("is_input", C.c_int),
@@ -126,6 +131,8 @@ API_SYMBOLS = [
     "rfd_face_tensor_config_quality", "rfd_face_tensor_config_extraction", "rfd_face_tensors",
     "rfd_align_faces_tensors", "rfd_detect_select_align_tensors_batch", "rfd_detect_faces_device", "rfd_quality_decide", "rfd_normalize_embeddings",
     "rfd_quality_decide_device", "rfd_normalize_embeddings_device",
+    "rfd_face_tensor_config_quality_assessment", "rfd_liveness_config_default", "rfd_liveness_tensors",
+    "rfd_liveness_tensors_device", "rfd_liveness_decide", "rfd_liveness_decide_device",
 ]
 
 _lib = None
@@ -222,6 +229,14 @@ def load_library(path=None):
     L.rfd_quality_decide_device.argtypes = [vp, vp, ci, ci, C.c_float, vp, vp]
     L.rfd_normalize_embeddings.argtypes = [vp, vp, ci, ci, vp]
     L.rfd_normalize_embeddings_device.argtypes = [vp, vp, ci, ci, vp]
+    L.rfd_face_tensor_config_quality_assessment.argtypes = [C.POINTER(rfd_face_tensor_config), ci, ci]
+    L.rfd_face_tensor_config_quality_assessment.restype = None
+    L.rfd_liveness_config_default.argtypes = [C.POINTER(rfd_liveness_config)]
+    L.rfd_liveness_config_default.restype = None
+    L.rfd_liveness_tensors.argtypes = [vp, C.POINTER(rfd_image), ci, vp, vp, vp, C.POINTER(vp), vp, vp, vp]
+    L.rfd_liveness_tensors_device.argtypes = [vp, C.POINTER(rfd_image), ci, vp, vp, vp, C.POINTER(vp), vp, vp, vp, ci]
+    L.rfd_liveness_decide.argtypes = [vp, C.POINTER(vp), ci, ci, ci, vp, C.c_float, vp, vp]
+    L.rfd_liveness_decide_device.argtypes = [vp, C.POINTER(vp), ci, ci, ci, vp, C.c_float, vp, vp]
     if path is None:
         _lib = L
     return L
@@ -253,6 +268,27 @@ def face_tensor_config_extraction():
     """the input of the ID model (face_extraction.rs:38-39): 112 x 112, (p - 127.5) / 128"""
     c = rfd_face_tensor_config()
     load_library().rfd_face_tensor_config_extraction(C.byref(c))
+    return c
+
+
+def face_tensor_config_quality_assessment(image_size):
+    """the input of the quality-assessment model (face_quality_assessment.rs:50-76): image_size (w, h), (p - 127.5) * 0.00784313725;
+    its decision is logit[0] > threshold on the model's one logit"""
+    c = rfd_face_tensor_config()
+    load_library().rfd_face_tensor_config_quality_assessment(C.byref(c), int(image_size[0]), int(image_size[1]))
+    return c
+
+
+def liveness_config(scales=None, image_sizes=None):
+    """rfd_liveness_config: the four miniFAS models the reference names (face_antispoofing.rs:448-485), or one model per
+    entry of scales / image_sizes [(w, h)] (more than MAX_FACE_TENSORS: the library refuses the call)"""
+    c = rfd_liveness_config()
+    load_library().rfd_liveness_config_default(C.byref(c))
+    if scales is not None:
+        c.k = len(scales)
+        for j in range(min(c.k, MAX_FACE_TENSORS)):
+            c.scale[j] = scales[j]
+            c.out_w[j], c.out_h[j] = int(image_sizes[j][0]), int(image_sizes[j][1])
     return c
 
 
@@ -676,6 +712,57 @@ class RetinaFaceDetection:
         out = np.zeros_like(x)
         _check(self._L.rfd_normalize_embeddings(self._ctx, x.ctypes.data, x.shape[0], x.shape[1], out.ctypes.data))
         return out
+
+    # ---- liveness: the inputs of the miniFAS models and the rule on their outputs (face_antispoofing.rs; rfd.h) ----
+    def liveness_tensors(self, frames, boxes, found=None, cfg=None):
+        """frames: list of HxWx3 u8 BGR; boxes [n, >= 4] (x1, y1, x2, y2[, score]); found [n] (default: every face has a box)
+        -> (tensors: one [n, 3, out_h, out_w] f32 array per model, B, G, R planes; weights [n, k]; rois [n, k, 4]; status [n])"""
+        arr, keep = self._images(frames)
+        n = len(frames)
+        cfg = liveness_config() if cfg is None else cfg
+        k = max(min(cfg.k, MAX_FACE_TENSORS), 0)
+        b = np.zeros((n, 5), np.float32)
+        bx = np.asarray(boxes, np.float32).reshape(n, -1)
+        b[:, :min(bx.shape[1], 5)] = bx[:, :5]
+        fd = np.ones(n, np.int32) if found is None else np.ascontiguousarray(found, np.int32)
+        outs = [np.zeros((n, 3, max(cfg.out_h[j], 1), max(cfg.out_w[j], 1)), np.float32) for j in range(k)]
+        ptrs = (C.c_void_p * max(k, 1))(*[o.ctypes.data for o in outs])
+        weights, rois, status = np.zeros((n, k), np.float32), np.zeros((n, k, 4), np.int32), np.zeros(n, np.int32)
+        _check(self._L.rfd_liveness_tensors(self._ctx, arr, n, b.ctypes.data, fd.ctypes.data, C.addressof(cfg), ptrs,
+                                            weights.ctypes.data, rois.ctypes.data, status.ctypes.data))
+        return outs, weights, rois, status
+
+    def liveness_tensors_device(self, frame_ptrs, shapes, box_ptr, found_ptr, tensor_ptrs, weights_ptr, rois_ptr, status_ptr,
+                                cfg=None, strides=None, async_=False):
+        """Frames, boxes, flags and every output already in device memory (raw device addresses; rois_ptr may be None); enqueued on
+        the context's stream, with no host synchronisation when async_ is set (then sync() before reading)."""
+        n = len(frame_ptrs)
+        arr = (rfd_image * n)()
+        for i, (p, (h, w)) in enumerate(zip(frame_ptrs, shapes)):
+            arr[i].data, arr[i].height, arr[i].width, arr[i].stride = p, h, w, (w * 3 if strides is None else strides[i])
+        cfg = liveness_config() if cfg is None else cfg
+        ptrs = (C.c_void_p * max(len(tensor_ptrs), 1))(*tensor_ptrs)
+        _check(self._L.rfd_liveness_tensors_device(self._ctx, arr, n, box_ptr, found_ptr, C.addressof(cfg), ptrs, weights_ptr,
+                                                   rois_ptr, status_ptr, int(async_)))
+
+    def liveness_decide(self, logits, weights, threshold=0.55):
+        """logits: one [n, classes] array per model; weights [n, k] of liveness_tensors -> (score [n] f32, live [n] i32):
+        the weighted mean of column 1 over the models, live = score > threshold (face_antispoofing.rs:219-243)"""
+        xs = [np.ascontiguousarray(x, np.float32) for x in logits]
+        k, (n, classes) = len(xs), xs[0].shape
+        assert all(x.shape == (n, classes) for x in xs)
+        w = np.ascontiguousarray(weights, np.float32).reshape(n, k)
+        ptrs = (C.c_void_p * k)(*[x.ctypes.data for x in xs])
+        score, live = np.zeros(n, np.float32), np.zeros(n, np.int32)
+        _check(self._L.rfd_liveness_decide(self._ctx, ptrs, k, n, classes, w.ctypes.data, float(threshold), score.ctypes.data,
+                                           live.ctypes.data))
+        return score, live
+
+    def liveness_decide_device(self, logit_ptrs, n, classes, weights_ptr, score_ptr, live_ptr, threshold=0.55):
+        """the same on raw device addresses, enqueued on the context's stream (no synchronisation)"""
+        k = len(logit_ptrs)
+        ptrs = (C.c_void_p * k)(*logit_ptrs)
+        _check(self._L.rfd_liveness_decide_device(self._ctx, ptrs, k, n, classes, weights_ptr, float(threshold), score_ptr, live_ptr))
 
     # ---- stage-level entry points ----
     def preprocess(self, frames):
