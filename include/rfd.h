@@ -468,6 +468,57 @@ RFD_API int rfd_liveness_decide(rfd_ctx *ctx, const float *const *logits, int k,
 RFD_API int rfd_liveness_decide_device(rfd_ctx *ctx, const float *const *logits, int k, int n, int classes,
                                        const float *weights, float threshold, float *score, int32_t *live);
 
+/* ---- the face gallery: what FacePipeline::extract's `facial_feature` (pipeline.rs:188-249) is for.  With is_enroll the
+ *      L2-normalised embedding is stored, otherwise it is compared with the stored ones; the reference leaves both to its caller.
+ *      Here the stored set lives in HBM and one pass over it scores a batch of queries and returns the k best rows of each, so
+ *      rfd_normalize_embeddings_device -> rfd_gallery_search_device runs back to back and only n * k pairs cross PCIe.
+ *      A gallery belongs to ONE context (its device, its stream; same thread rule) and is destroyed BEFORE it.  It holds up to
+ *      `capacity` rows of `dim` values, both fixed at creation, so no device pointer moves under enqueued work.  A row's index is
+ *      its insertion order; the caller keeps the table from rows to identities.  Rows are never deleted (rfd_gallery_clear
+ *      empties the gallery).
+ *      Storage: every added f32 value is stored as bf16, rounded to nearest-even.  Rows are expected to be unit vectors (the
+ *      output of rfd_normalize_embeddings); they are not normalised again.  The layout is private (MFMA-fragment-major).
+ *      Score: score[i][r] = the f32 MFMA-accumulated dot product of bf16(query i) and stored row r over dim, 32 elements per
+ *      v_mfma_f32_16x16x32_bf16, K ascending, one accumulator.  The bits of a (query, row) score depend on nothing else: not on
+ *      n, k, the gallery's size, the workgroup that scored the row or the query's place in the batch.
+ *      Order: a query's results are the k best rows under the total order (score descending, row ascending), in that order:
+ *      equal scores resolve to the lower row, and the result does not depend on how the rows are spread over workgroups.  A
+ *      gallery of fewer than k rows leaves the tail at row = -1, score = -inf.
+ *      Accuracy against the f32 inputs' exact dot product: RNE to bf16 moves a value by at most 2^-9 of itself, so
+ *      bf16(q) bf16(g) = q g (1 + a)(1 + b) with |a|, |b| <= 2^-9, i.e. |bf16(q) bf16(g) - q g| <= (2 * 2^-9 + 2^-18) |q g|, and
+ *          |score - sum_d q_d g_d| <= (2 * 2^-9 + 2^-18) * sum_d |q_d g_d| + the f32 accumulation error
+ *      (a few 2^-24 sum_d |q_d g_d|: bf16 products are exact in f32).  By Cauchy-Schwarz sum_d |q_d g_d| <= |q| |g| = 1 for unit
+ *      vectors: at most about 2^-8.
+ *      Non-finite values: the host forms reject a NaN or an infinity in a row or a query with RFD_ERR_INVALID_ARG, nothing is
+ *      added or searched, and rfd_last_error() names the first offender (row / query and element).  The device forms cannot
+ *      look at the data: a NaN score compares false with everything and is never selected (nor is a score of -inf).
+ *      Errors: an add beyond capacity returns RFD_ERR_CAPACITY and adds nothing; k < 1 RFD_ERR_INVALID_ARG; k >
+ *      RFD_GALLERY_MAX_K RFD_ERR_CAPACITY; a dim that is not a multiple of 32 in 32..1024 RFD_ERR_INVALID_ARG; n = 0 is a no-op;
+ *      searching an empty gallery returns all -1 / -inf.  Device pointers must be 16-byte aligned. ---- */
+#define RFD_GALLERY_MAX_K 32
+typedef struct rfd_gallery rfd_gallery;
+RFD_API int rfd_gallery_create(rfd_ctx *ctx, int dim /* multiple of 32, 32..1024 */, int capacity, rfd_gallery **out);
+RFD_API void rfd_gallery_destroy(rfd_gallery *g);
+RFD_API int rfd_gallery_size(const rfd_gallery *g, int *rows, int *capacity, int *dim); /* any pointer may be NULL */
+RFD_API int rfd_gallery_clear(rfd_gallery *g);
+/* emb: host [n][dim]; *first_row (may be NULL) = the row the first one got.  Synchronous; staged through page-locked memory
+ * that the first host call of a gallery allocates. */
+RFD_API int rfd_gallery_add(rfd_gallery *g, const float *emb, int n, int *first_row);
+/* emb: device; enqueued on the context's stream, no synchronisation.  The rows count at once (rfd_gallery_size, a following
+ * search on the same stream). */
+RFD_API int rfd_gallery_add_device(rfd_gallery *g, const float *emb, int n, int *first_row);
+/* out: host [n][dim], the stored bf16 values of rows [row0, row0 + n) as f32 */
+RFD_API int rfd_gallery_get_rows(rfd_gallery *g, int row0, int n, float *out);
+/* queries: host [n][dim], any n: processed in groups of at most 32, one pass over the gallery per group.
+ * scores [n][k] f32, rows [n][k] i32, host. */
+RFD_API int rfd_gallery_search(rfd_gallery *g, const float *queries, int n, int k, float *scores, int32_t *rows);
+/* The same with DEVICE pointers, by the conventions of rfd_detect_faces_device: enqueued on the context's stream; async = 0
+ * returns after the stream has drained, any other value at once (rfd_sync before reading the results). */
+RFD_API int rfd_gallery_search_device(rfd_gallery *g, const float *queries, int n, int k, float *scores, int32_t *rows, int async);
+/* host only, no GPU: element offset of (row, d) in the private storage layout (-1: dim or an index out of range); the add
+ * kernel scatters by this function and tests pin that it is a bijection and that an MFMA operand fetch is one 1 KiB span */
+RFD_API int64_t rfd_debug_gallery_offset(int dim, int row, int d);
+
 /* ---- introspection ---- */
 RFD_API int rfd_get_stats(rfd_ctx *ctx, rfd_stats *stats);
 RFD_API int rfd_get_config(const rfd_ctx *ctx, rfd_config *cfg);

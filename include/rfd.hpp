@@ -276,5 +276,58 @@ inline std::pair<std::vector<float>, std::vector<int32_t>> liveness_decide(Retin
     return {score, live};
 }
 
+// The face gallery (rfd.h, "gallery"): what FacePipeline::extract's facial_feature is enrolled into and compared with.  Owns the
+// rfd_gallery; destroy it before the detector it was made from.
+class Gallery {
+  public:
+    struct Matches {
+        int n = 0, k = 0;
+        std::vector<float> scores;  // [n][k], descending; -inf where the gallery has fewer than k rows
+        std::vector<int32_t> rows;  // [n][k], equal scores by ascending row; -1 in that tail
+    };
+    Gallery(RetinaFaceDetection &det, int dim, int capacity) : dim_(dim) { check(rfd_gallery_create(det.raw(), dim, capacity, &g_)); }
+    Gallery(const Gallery &) = delete;
+    Gallery &operator=(const Gallery &) = delete;
+    ~Gallery() { rfd_gallery_destroy(g_); }
+    rfd_gallery *raw() { return g_; }
+    int dim() const { return dim_; }
+    int size() const
+    {
+        int rows = 0;
+        check(rfd_gallery_size(g_, &rows, nullptr, nullptr));
+        return rows;
+    }
+    void clear() { check(rfd_gallery_clear(g_)); }
+    // emb [n][dim], unit vectors -> the row the first one got
+    int add(const std::vector<float> &emb)
+    {
+        int first = 0;
+        check(rfd_gallery_add(g_, emb.data(), (int)(emb.size() / (std::size_t)dim_), &first));
+        return first;
+    }
+    // the stored (bf16) values of rows [row0, row0 + n)
+    std::vector<float> rows(int row0, int n)
+    {
+        std::vector<float> out((std::size_t)(n > 0 ? n : 0) * (std::size_t)dim_);
+        check(rfd_gallery_get_rows(g_, row0, n, out.data()));
+        return out;
+    }
+    // queries [n][dim] -> the k best rows of each
+    Matches search(const std::vector<float> &queries, int k)
+    {
+        Matches m;
+        m.n = (int)(queries.size() / (std::size_t)dim_);
+        m.k = k;
+        m.scores.resize((std::size_t)m.n * (std::size_t)(k > 0 ? k : 0));
+        m.rows.resize(m.scores.size());
+        check(rfd_gallery_search(g_, queries.data(), m.n, k, m.scores.data(), m.rows.data()));
+        return m;
+    }
+
+  private:
+    rfd_gallery *g_ = nullptr;
+    int dim_;
+};
+
 } // namespace rfd
 #endif

@@ -253,6 +253,20 @@ struct rfd_ctx {
     }
 };
 
+// A face gallery: the enrolled embeddings of one context in HBM (rfd.h, "gallery").  Next to the context, which lends it its
+// device and stream; the caller destroys it first.
+struct rfd_gallery {
+    rfd_ctx *ctx = nullptr;
+    int dim = 0, capacity = 0, rows = 0;
+    int groups_max = 0; // workgroups of a search, from the CU count: the workspace holds their lists
+    DevBuf store;       // ceil(capacity / 16) blocks of 16 rows, bf16, fragment-major (gallery_offset)
+    DevBuf ws;          // [groups_max][32][RFD_GALLERY_MAX_K] keys
+    // host forms, allocated by the first of them: a page-locked buffer and its device twin
+    static constexpr size_t kStageBytes = 4u << 20;
+    DevBuf stage;
+    void *pin = nullptr;
+};
+
 namespace {
 
 int ctx_alloc(rfd_ctx *c)
@@ -2121,6 +2135,200 @@ void _nms(int32_t *keep, int *num_out, float *boxes, int boxes_num, int boxes_di
         if (rfd_create(&cfg, &g_nms_ctx[device_id]) != RFD_OK) { g_nms_ctx[device_id] = nullptr; return; }
     }
     if (rfd_nms_sorted(g_nms_ctx[device_id], keep, num_out, boxes, boxes_num, boxes_dim, thresh) != RFD_OK) *num_out = -1;
+}
+
+// ---- face gallery: enrol embeddings, search the k best rows (rfd.h; kernels_gallery.hip) ----
+static int gallery_host_stage(rfd_gallery *g)
+{
+    if (g->pin) return RFD_OK;
+    RFD_TRY(g->stage.reserve(rfd_gallery::kStageBytes));
+    RFD_HIP(hipHostMalloc(&g->pin, rfd_gallery::kStageBytes, hipHostMallocDefault));
+    return RFD_OK;
+}
+
+// first non-finite value of x [n][dim], named in the error message (`what` = "row" / "query")
+static int gallery_check_finite(const float *x, int n, int dim, const char *what)
+{
+    for (int i = 0; i < n; ++i)
+        for (int d = 0; d < dim; ++d) {
+            uint32_t u;
+            memcpy(&u, &x[(size_t)i * dim + d], 4);
+            if ((u & 0x7f800000u) == 0x7f800000u) {
+                set_error("invalid argument: %s %d holds a non-finite value (%g) at element %d", what, i, (double)x[(size_t)i * dim + d], d);
+                return RFD_ERR_INVALID_ARG;
+            }
+        }
+    return RFD_OK;
+}
+
+static int gallery_check_k(int k)
+{
+    RFD_CHECK_ARG(k >= 1, "k < 1");
+    if (k > RFD_GALLERY_MAX_K) { set_error("k = %d exceeds RFD_GALLERY_MAX_K (%d)", k, RFD_GALLERY_MAX_K); return RFD_ERR_CAPACITY; }
+    return RFD_OK;
+}
+
+static int gallery_check_room(const rfd_gallery *g, int n)
+{
+    if (n > g->capacity - g->rows) {
+        set_error("the gallery holds %d of %d rows: %d more do not fit", g->rows, g->capacity, n);
+        return RFD_ERR_CAPACITY;
+    }
+    return RFD_OK;
+}
+
+int64_t rfd_debug_gallery_offset(int dim, int row, int d)
+{
+    if (dim < 32 || dim > 1024 || dim % 32 != 0 || row < 0 || d < 0 || d >= dim) return -1;
+    return (int64_t)gallery_offset(dim, row, d);
+}
+
+int rfd_gallery_create(rfd_ctx *c, int dim, int capacity, rfd_gallery **out)
+{
+    RFD_CHECK_ARG(c && out, "null argument");
+    *out = nullptr;
+    RFD_CHECK_ARG(dim >= 32 && dim <= 1024 && dim % 32 == 0, "dim must be a multiple of 32 in 32..1024");
+    RFD_CHECK_ARG(capacity >= 1 && capacity <= (1 << 30), "capacity out of range");
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    rfd_gallery *g = new rfd_gallery();
+    g->ctx = c; g->dim = dim; g->capacity = capacity;
+    g->groups_max = 2 * device_cus(); // two workgroups of four waves per CU: what the scan's registers admit
+    const size_t bytes = (size_t)ceil_div(capacity, 16) * 16 * dim * sizeof(bf16_t);
+    int st = g->store.reserve(bytes);
+    if (st == RFD_OK) st = g->ws.reserve((size_t)g->groups_max * kGalleryMaxQueries * RFD_GALLERY_MAX_K * sizeof(uint2));
+    // rows that were never added read as zeros (the tail of the last block is scored, then masked by its row index)
+    if (st == RFD_OK && hipMemsetAsync(g->store.p, 0, bytes, c->stream) != hipSuccess) { set_error("hipMemsetAsync of the gallery failed"); st = RFD_ERR_HIP; }
+    if (st != RFD_OK) { rfd_gallery_destroy(g); return st; }
+    *out = g;
+    return RFD_OK;
+}
+
+void rfd_gallery_destroy(rfd_gallery *g)
+{
+    if (!g) return;
+    (void)hipSetDevice(g->ctx->cfg.device_id);
+    (void)hipStreamSynchronize(g->ctx->stream);
+    g->store.release(); g->ws.release(); g->stage.release();
+    if (g->pin) (void)hipHostFree(g->pin);
+    delete g;
+}
+
+int rfd_gallery_size(const rfd_gallery *g, int *rows, int *capacity, int *dim)
+{
+    RFD_CHECK_ARG(g, "gallery is null");
+    if (rows) *rows = g->rows;
+    if (capacity) *capacity = g->capacity;
+    if (dim) *dim = g->dim;
+    return RFD_OK;
+}
+
+int rfd_gallery_clear(rfd_gallery *g)
+{
+    RFD_CHECK_ARG(g, "gallery is null");
+    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
+    if (g->rows > 0) RFD_HIP(hipMemsetAsync(g->store.p, 0, (size_t)ceil_div(g->rows, 16) * 16 * g->dim * sizeof(bf16_t), g->ctx->stream));
+    g->rows = 0;
+    return RFD_OK;
+}
+
+int rfd_gallery_add_device(rfd_gallery *g, const float *emb, int n, int *first_row)
+{
+    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
+    if (first_row) *first_row = g->rows;
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(emb && (uintptr_t)emb % 16 == 0, "emb is null or not 16-byte aligned");
+    RFD_TRY(gallery_check_room(g, n));
+    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
+    RFD_TRY(launch_gallery_add(emb, n, g->dim, g->rows, (bf16_t *)g->store.p, g->ctx->stream));
+    g->rows += n;
+    return RFD_OK;
+}
+
+int rfd_gallery_add(rfd_gallery *g, const float *emb, int n, int *first_row)
+{
+    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
+    if (first_row) *first_row = g->rows;
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(emb, "emb is null");
+    RFD_TRY(gallery_check_room(g, n));
+    RFD_TRY(gallery_check_finite(emb, n, g->dim, "row"));
+    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
+    RFD_TRY(gallery_host_stage(g));
+    const int chunk = (int)(rfd_gallery::kStageBytes / ((size_t)g->dim * sizeof(float)));
+    for (int i = 0; i < n; i += chunk) { // one staging buffer: a chunk has left it before the next one is copied in
+        const int m = std::min(chunk, n - i);
+        const size_t bytes = (size_t)m * g->dim * sizeof(float);
+        memcpy(g->pin, emb + (size_t)i * g->dim, bytes);
+        RFD_HIP(hipMemcpyAsync(g->stage.p, g->pin, bytes, hipMemcpyHostToDevice, g->ctx->stream));
+        RFD_TRY(launch_gallery_add((const float *)g->stage.p, m, g->dim, g->rows + i, (bf16_t *)g->store.p, g->ctx->stream));
+        RFD_HIP(hipStreamSynchronize(g->ctx->stream));
+    }
+    g->rows += n;
+    return RFD_OK;
+}
+
+int rfd_gallery_get_rows(rfd_gallery *g, int row0, int n, float *out)
+{
+    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(out, "out is null");
+    RFD_CHECK_ARG(row0 >= 0 && n <= g->rows - row0, "rows [row0, row0 + n) are not all in the gallery");
+    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
+    RFD_TRY(gallery_host_stage(g));
+    const int chunk = (int)(rfd_gallery::kStageBytes / ((size_t)g->dim * sizeof(float)));
+    for (int i = 0; i < n; i += chunk) {
+        const int m = std::min(chunk, n - i);
+        const size_t bytes = (size_t)m * g->dim * sizeof(float);
+        RFD_TRY(launch_gallery_get((const bf16_t *)g->store.p, row0 + i, m, g->dim, (float *)g->stage.p, g->ctx->stream));
+        RFD_HIP(hipMemcpyAsync(g->pin, g->stage.p, bytes, hipMemcpyDeviceToHost, g->ctx->stream));
+        RFD_HIP(hipStreamSynchronize(g->ctx->stream));
+        memcpy(out + (size_t)i * g->dim, g->pin, bytes);
+    }
+    return RFD_OK;
+}
+
+int rfd_gallery_search_device(rfd_gallery *g, const float *queries, int n, int k, float *scores, int32_t *rows, int async)
+{
+    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
+    RFD_TRY(gallery_check_k(k));
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(queries && scores && rows, "null argument");
+    RFD_CHECK_ARG((uintptr_t)queries % 16 == 0, "queries are not 16-byte aligned");
+    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
+    for (int i = 0; i < n; i += kGalleryMaxQueries) // one pass over the gallery per group of queries; the passes share the workspace in stream order
+        RFD_TRY(launch_gallery_search((const bf16_t *)g->store.p, g->rows, g->dim, queries + (size_t)i * g->dim, std::min(kGalleryMaxQueries, n - i), k,
+                                      (uint2 *)g->ws.p, g->groups_max, scores + (size_t)i * k, rows + (size_t)i * k, g->ctx->stream));
+    if (!async) RFD_HIP(hipStreamSynchronize(g->ctx->stream));
+    return RFD_OK;
+}
+
+int rfd_gallery_search(rfd_gallery *g, const float *queries, int n, int k, float *scores, int32_t *rows)
+{
+    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
+    RFD_TRY(gallery_check_k(k));
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(queries && scores && rows, "null argument");
+    RFD_TRY(gallery_check_finite(queries, n, g->dim, "query"));
+    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
+    RFD_TRY(gallery_host_stage(g));
+    // the staging buffer holds one group: its queries, then its scores and rows
+    const size_t qcap = (size_t)kGalleryMaxQueries * g->dim * sizeof(float), rcap = (size_t)kGalleryMaxQueries * RFD_GALLERY_MAX_K * sizeof(float);
+    float *d_q = (float *)g->stage.p, *d_s = (float *)((char *)g->stage.p + qcap);
+    int32_t *d_r = (int32_t *)((char *)g->stage.p + qcap + rcap);
+    char *h = (char *)g->pin;
+    for (int i = 0; i < n; i += kGalleryMaxQueries) {
+        const int m = std::min(kGalleryMaxQueries, n - i);
+        const size_t qbytes = (size_t)m * g->dim * sizeof(float), rbytes = (size_t)m * k * sizeof(float);
+        memcpy(h, queries + (size_t)i * g->dim, qbytes);
+        RFD_HIP(hipMemcpyAsync(d_q, h, qbytes, hipMemcpyHostToDevice, g->ctx->stream));
+        RFD_TRY(launch_gallery_search((const bf16_t *)g->store.p, g->rows, g->dim, d_q, m, k, (uint2 *)g->ws.p, g->groups_max, d_s, d_r, g->ctx->stream));
+        RFD_HIP(hipMemcpyAsync(h + qcap, d_s, rbytes, hipMemcpyDeviceToHost, g->ctx->stream));
+        RFD_HIP(hipMemcpyAsync(h + qcap + rcap, d_r, rbytes, hipMemcpyDeviceToHost, g->ctx->stream));
+        RFD_HIP(hipStreamSynchronize(g->ctx->stream));
+        memcpy(scores + (size_t)i * k, h + qcap, rbytes);
+        memcpy(rows + (size_t)i * k, h + qcap + rcap, rbytes);
+    }
+    return RFD_OK;
 }
 
 } // extern "C"

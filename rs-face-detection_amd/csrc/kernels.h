@@ -179,6 +179,26 @@ struct LiveLogits { const float *p[kLiveDecideChunk]; };
 int launch_liveness_decide(const LiveLogits &l, int kc, int k, int j0, int n, int classes, const float *weights, float threshold,
                            float *acc, float *score, int *live, hipStream_t s);
 
+// ---------------------------------------------------------------- face gallery (kernels_gallery.hip)
+// Element offset of (row, d) in a gallery's storage, the one statement of the layout (rfd_debug_gallery_offset returns it):
+// rows in blocks of 16; a block holds dim / 32 K steps of 512 elements; inside a K step lane (row & 15) + 16 * ((d & 31) >> 3) of
+// v_mfma_f32_16x16x32_bf16's B operand owns 8 consecutive elements.
+__host__ __device__ static inline size_t gallery_offset(int dim, int row, int d)
+{
+    return ((size_t)(row >> 4) * (dim >> 5) + (d >> 5)) * 512 + (size_t)(((row & 15) + 16 * ((d & 31) >> 3)) * 8 + (d & 7));
+}
+constexpr int kGalleryMaxQueries = 32; // queries of one pass over the gallery (two 16-row M-tiles)
+// emb [n][dim] f32 (device, 16-byte aligned) -> rows [row0, row0 + n) of store, bf16 RNE
+int launch_gallery_add(const float *emb, int n, int dim, int row0, bf16_t *store, hipStream_t s);
+// the stored values of rows [row0, row0 + n) -> out [n][dim] f32 (device)
+int launch_gallery_get(const bf16_t *store, int row0, int n, int dim, float *out, hipStream_t s);
+// workgroups a search over `rows` rows runs with, <= groups_max; ws must hold that many x n x k keys of 8 bytes
+int gallery_search_groups(int rows, int groups_max);
+// one pass: queries [n <= kGalleryMaxQueries][dim] f32 (device, 16-byte aligned) against rows [0, rows) -> scores / out_rows
+// [n][k] under (score descending, row ascending); two launches (scan, merge of the workgroups' lists), no synchronisation
+int launch_gallery_search(const bf16_t *store, int rows, int dim, const float *queries, int n, int k, uint2 *ws, int groups_max,
+                          float *scores, int32_t *out_rows, hipStream_t s);
+
 // ---------------------------------------------------------------- convolution engine (kernels_conv.hip)
 // Activations: NHWC bf16.  Weights: [Cout][KH][KW][Cin] bf16 (K contiguous).  f32 accumulate on MFMA.
 struct ConvParams {

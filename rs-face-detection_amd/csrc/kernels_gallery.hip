@@ -1,0 +1,281 @@
+// kernels_gallery.hip -- the on-device face gallery (include/rfd.h, "gallery"): enrol L2-normalised embeddings as bf16, score a
+// batch of queries against every enrolled row on the matrix cores, keep the k best rows per query.
+//
+// Storage (gallery_offset, kernels.h): MFMA-fragment-major.  Rows in blocks of 16; inside a block, for each 32-wide K step, the 64
+// lanes' 16-byte B operands of v_mfma_f32_16x16x32_bf16 lie contiguously (lane l: row l & 15, elements 8 * (l >> 4) .. + 7), so a
+// wave reads one (block, K step) with ONE coalesced 1 KiB global_load_dwordx4 and the gallery never passes through LDS.
+//
+// Search: one pass over the gallery for up to 32 queries.  The queries are rounded to bf16 once per workgroup and kept in LDS as A
+// fragments (two 8-byte halves per lane, so every LDS read is 64 bits and conflict-free).  Each wave walks row blocks at a grid
+// stride with kGalleryPrefetch K steps (1 KiB each) of loads in flight; per block it issues dim / 32 MFMAs per M-tile into one
+// accumulator, K ascending -- a (query, row) score therefore has the same bits wherever the row and the query sit.  C mapping:
+// lane & 15 = gallery row of the block, 4 * (lane >> 4) + reg = query of the M-tile.
+// Selection: every wave keeps, per query, a list of its k best (score, row) keys in LDS, sorted by (score descending, row
+// ascending); the list's last key is the filter, one compare rejects nearly every score, and what passes is inserted by the whole
+// wave (one lane per list entry).  No wave touches another wave's list, so the scan needs no barrier, no atomic and no wait.  At
+// the end one barrier, the four lists of a query are merged, and the workgroup writes k keys per query to the workspace
+// [groups][n][k]; gallery_merge_kernel reduces the groups' lists per query with the same two routines.  The order is total (rows
+// are unique), so the result does not depend on which wave or workgroup scored a row.
+#include "conv_device.h"
+
+namespace rfd {
+
+namespace {
+
+constexpr int kGalleryWaves = 4;     // waves per workgroup (search and merge)
+constexpr int kGalleryPrefetch = 8;  // K steps of gallery loads a wave keeps in flight: 8 KiB per wave, 64 KiB per CU at two workgroups
+
+__device__ __forceinline__ uint2 gallery_sentinel() { return make_uint2(0xff800000u, 0xffffffffu); } // score -inf, row -1
+
+// the total order of the results: score descending, then row ascending.  False whenever a score is NaN.
+__device__ __forceinline__ bool key_better(float s, int r, float s2, int r2) { return s > s2 || (s == s2 && r < r2); }
+
+// Inserts the wave-uniform key (cs, crow) into the sorted list of k <= 64 keys; the whole wave calls it, lane i owns entry i.
+// LDS operations of one wave execute in order, so every lane's reads are done before any lane's write.
+__device__ __forceinline__ void list_insert(uint2 *list, int k, float cs, int crow, int lane)
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    const bool in = lane < k;
+    uint2 e = gallery_sentinel(), ep = e;
+    if (in) {
+        e = list[lane];
+        if (lane > 0) ep = list[lane - 1];
+    }
+    const bool ahead = in && key_better(__uint_as_float(e.x), (int)e.y, cs, crow);
+    const int pos = __popcll(__ballot(ahead)); // the list is sorted: the keys ahead of the new one are its first `pos`
+    if (in && lane >= pos) list[lane] = lane == pos ? make_uint2(__float_as_uint(cs), (uint32_t)crow) : ep;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+
+// Offers every lane's key (s, row) to list `li` of the wave's lists (k keys each); `valid` masks lanes without a key.  The last key
+// of a list is its filter; a key that passes is inserted by the whole wave, lowest lane first.  Called with all 64 lanes.
+__device__ __forceinline__ void list_offer(uint2 *lists, int li, int k, float s, int row, bool valid, int lane)
+{
+    bool pass = false;
+    if (valid) {
+        const uint2 t = lists[li * k + k - 1];
+        pass = key_better(s, row, __uint_as_float(t.x), (int)t.y);
+    }
+    unsigned long long m = __ballot(pass);
+    while (m) {
+        const int l = __ffsll(m) - 1;
+        m &= m - 1;
+        list_insert(lists + __builtin_amdgcn_readlane(li, l) * k, k, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), l)),
+                    __builtin_amdgcn_readlane(row, l), lane);
+    }
+}
+
+// k best keys of the kGalleryWaves sorted lists at lists + w * wave_pitch, in order, handed to out(j, key); one thread.
+template <class Out>
+__device__ __forceinline__ void merge_wave_lists(const uint2 *lists, int wave_pitch, int k, Out out)
+{
+    int h0 = 0, h1 = 0, h2 = 0, h3 = 0;
+    for (int j = 0; j < k; ++j) {
+        // a list has k keys and j < k heads have been taken in all, so every head index is < k
+        const uint2 e0 = lists[h0], e1 = lists[wave_pitch + h1], e2 = lists[2 * wave_pitch + h2], e3 = lists[3 * wave_pitch + h3];
+        uint2 b = e0;
+        int bi = 0;
+        if (key_better(__uint_as_float(e1.x), (int)e1.y, __uint_as_float(b.x), (int)b.y)) { b = e1; bi = 1; }
+        if (key_better(__uint_as_float(e2.x), (int)e2.y, __uint_as_float(b.x), (int)b.y)) { b = e2; bi = 2; }
+        if (key_better(__uint_as_float(e3.x), (int)e3.y, __uint_as_float(b.x), (int)b.y)) { b = e3; bi = 3; }
+        out(j, b);
+        h0 += bi == 0; h1 += bi == 1; h2 += bi == 2; h3 += bi == 3;
+    }
+}
+
+} // namespace
+
+// ---- add: f32 -> bf16 (RNE), scattered into the fragment-major layout.  One thread per 16-byte operand. ----
+__global__ void __launch_bounds__(256) gallery_add_kernel(const float *__restrict__ emb, int n, int dim, int row0, bf16_t *__restrict__ store)
+{
+    const int per_row = dim >> 3;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)n * per_row) return;
+    const int r = (int)(i / per_row), d = (int)(i - (size_t)r * per_row) * 8;
+    const float4 a = *reinterpret_cast<const float4 *>(emb + (size_t)r * dim + d), b = *reinterpret_cast<const float4 *>(emb + (size_t)r * dim + d + 4);
+    const uint2 lo = pack_bf16x4(a.x, a.y, a.z, a.w), hi = pack_bf16x4(b.x, b.y, b.z, b.w);
+    *reinterpret_cast<uint4 *>(store + gallery_offset(dim, row0 + r, d)) = make_uint4(lo.x, lo.y, hi.x, hi.y);
+}
+
+int launch_gallery_add(const float *emb, int n, int dim, int row0, bf16_t *store, hipStream_t s)
+{
+    const size_t items = (size_t)n * (dim >> 3);
+    hipLaunchKernelGGL(gallery_add_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, emb, n, dim, row0, store);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+// ---- get: the stored bf16 values of rows [row0, row0 + n) as f32 [n][dim] ----
+__global__ void __launch_bounds__(256) gallery_get_kernel(const bf16_t *__restrict__ store, int row0, int n, int dim, float *__restrict__ out)
+{
+    const int per_row = dim >> 3;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)n * per_row) return;
+    const int r = (int)(i / per_row), d = (int)(i - (size_t)r * per_row) * 8;
+    const uint4 v = *reinterpret_cast<const uint4 *>(store + gallery_offset(dim, row0 + r, d));
+    float4 *o = reinterpret_cast<float4 *>(out + (size_t)r * dim + d);
+    o[0] = make_float4(bf16_bits_to_f32(v.x & 0xffffu), bf16_bits_to_f32(v.x >> 16), bf16_bits_to_f32(v.y & 0xffffu), bf16_bits_to_f32(v.y >> 16));
+    o[1] = make_float4(bf16_bits_to_f32(v.z & 0xffffu), bf16_bits_to_f32(v.z >> 16), bf16_bits_to_f32(v.w & 0xffffu), bf16_bits_to_f32(v.w >> 16));
+}
+
+int launch_gallery_get(const bf16_t *store, int row0, int n, int dim, float *out, hipStream_t s)
+{
+    const size_t items = (size_t)n * (dim >> 3);
+    hipLaunchKernelGGL(gallery_get_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, store, row0, n, dim, out);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+// ---- search: n <= 16 * NMT queries against rows [0, rows); writes ws[blockIdx.x][n][k] ----
+template <int NMT>
+__global__ void __launch_bounds__(kGalleryWaves * 64) gallery_search_kernel(const bf16_t *__restrict__ store, int rows, int ksteps,
+                                                                             const float *__restrict__ queries, int n, int k,
+                                                                             uint2 *__restrict__ ws)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char gallery_smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6); // scalar: the walk below is wave-uniform
+    const int dim = ksteps * 32, quads = dim >> 2;
+    uint2 *afrag = reinterpret_cast<uint2 *>(gallery_smem);  // [NMT][ksteps][2 halves][64 lanes] x 4 bf16
+    uint2 *lists = afrag + NMT * ksteps * 128;               // [waves][NMT * 16 queries][k]
+    uint2 *mine = lists + wave * (NMT * 16 * k);
+
+    // queries -> bf16 A fragments: lane (q & 15) + 16 * ((d & 31) >> 3) of K step d >> 5 holds elements d & ~7 .. + 7 of query q
+    for (int i = tid; i < NMT * 16 * quads; i += kGalleryWaves * 64) {
+        const int q = i / quads, d = (i - q * quads) * 4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (q < n) v = *reinterpret_cast<const float4 *>(queries + (size_t)q * dim + d);
+        afrag[(((q >> 4) * ksteps + (d >> 5)) * 2 + ((d & 7) >> 2)) * 64 + (q & 15) + 16 * ((d & 31) >> 3)] = pack_bf16x4(v.x, v.y, v.z, v.w);
+    }
+    for (int i = lane; i < NMT * 16 * k; i += 64) mine[i] = gallery_sentinel();
+    __syncthreads();
+
+    const int nblocks = (rows + 15) >> 4;
+    const int stride = gridDim.x * kGalleryWaves;
+    int blk = blockIdx.x * kGalleryWaves + wave, ks = 0; // the step the MFMAs are at
+    if (blk < nblocks) {                                 // wave-uniform
+        int pblk = blk, pks = 0;                         // the step the loads are at
+        const uint4 *src = reinterpret_cast<const uint4 *>(store) + lane;
+        uint4 buf[kGalleryPrefetch];
+        // Loads beyond the wave's last block re-read its last in-range block (never out of bounds); their MFMAs run and are dropped.
+        auto issue = [&](uint4 &dst) {
+            const int b = pblk < nblocks ? pblk : nblocks - 1;
+            dst = src[((size_t)b * ksteps + pks) * 64];
+            if (++pks == ksteps) { pks = 0; pblk += stride; }
+        };
+#pragma unroll
+        for (int i = 0; i < kGalleryPrefetch; ++i) {
+            issue(buf[i]);
+            __builtin_amdgcn_sched_barrier(0); // keep the issue order: the loop waits for buf[0] with the other loads still in flight
+        }
+        f32x4 acc[NMT];
+#pragma unroll
+        for (int mt = 0; mt < NMT; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        while (blk < nblocks) {
+#pragma unroll
+            for (int i = 0; i < kGalleryPrefetch; ++i) {
+                const bf16x8 b = __builtin_bit_cast(bf16x8, buf[i]);
+#pragma unroll
+                for (int mt = 0; mt < NMT; ++mt) {
+                    const uint2 lo = afrag[((mt * ksteps + ks) * 2 + 0) * 64 + lane], hi = afrag[((mt * ksteps + ks) * 2 + 1) * 64 + lane];
+                    acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y)), b, acc[mt], 0, 0, 0);
+                }
+                issue(buf[i]);
+                if (++ks == ksteps) {
+                    if (blk < nblocks) {
+                        const int row = blk * 16 + (lane & 15);
+                        // the common case, no score of the block passes its list's filter, costs the compares and one branch
+                        bool any = false;
+#pragma unroll
+                        for (int mt = 0; mt < NMT; ++mt)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const int q = mt * 16 + 4 * (lane >> 4) + r;
+                                if (row < rows && q < n) {
+                                    const uint2 t = mine[q * k + k - 1];
+                                    any |= key_better(acc[mt][r], row, __uint_as_float(t.x), (int)t.y);
+                                }
+                            }
+                        if (__ballot(any)) {
+#pragma unroll
+                            for (int mt = 0; mt < NMT; ++mt)
+#pragma unroll
+                                for (int r = 0; r < 4; ++r) {
+                                    const int q = mt * 16 + 4 * (lane >> 4) + r;
+                                    list_offer(mine, q, k, acc[mt][r], row, row < rows && q < n, lane);
+                                }
+                        }
+                    }
+#pragma unroll
+                    for (int mt = 0; mt < NMT; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    ks = 0;
+                    blk += stride;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < n) {
+        uint2 *dst = ws + ((size_t)blockIdx.x * n + tid) * k;
+        merge_wave_lists(lists + tid * k, NMT * 16 * k, k, [&](int j, uint2 key) { dst[j] = key; });
+    }
+}
+
+// ---- merge: one workgroup per query reduces the groups' lists ws[groups][n][k] to scores / rows [n][k] ----
+__global__ void __launch_bounds__(kGalleryWaves * 64) gallery_merge_kernel(const uint2 *__restrict__ ws, int groups, int n, int k,
+                                                                            float *__restrict__ scores, int32_t *__restrict__ out_rows)
+{
+    __shared__ uint2 lists[kGalleryWaves * 32];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), q = blockIdx.x;
+    uint2 *mine = lists + wave * k;
+    if (lane < k) mine[lane] = gallery_sentinel();
+    const int total = groups * k;
+    for (int base = wave * 64; base < total; base += kGalleryWaves * 64) { // wave-uniform bounds: list_offer runs with all lanes
+        const int idx = base + lane;
+        uint2 c = gallery_sentinel();
+        if (idx < total) {
+            const int g = idx / k, j = idx - g * k;
+            c = ws[((size_t)g * n + q) * k + j];
+        }
+        list_offer(mine, 0, k, __uint_as_float(c.x), (int)c.y, (int)c.y >= 0, lane);
+    }
+    __syncthreads();
+    if (tid == 0)
+        merge_wave_lists(lists, k, k, [&](int j, uint2 key) {
+            scores[(size_t)q * k + j] = __uint_as_float(key.x);
+            out_rows[(size_t)q * k + j] = (int32_t)key.y;
+        });
+}
+
+int gallery_search_groups(int rows, int groups_max)
+{
+    // at least two row blocks per wave before another workgroup (and its conversion of the queries) is worth starting
+    const int nblocks = (rows + 15) / 16;
+    return std::max(1, std::min(groups_max, ceil_div(nblocks, kGalleryWaves * 2)));
+}
+
+int launch_gallery_search(const bf16_t *store, int rows, int dim, const float *queries, int n, int k, uint2 *ws, int groups_max,
+                          float *scores, int32_t *out_rows, hipStream_t s)
+{
+    if (n < 1 || n > kGalleryMaxQueries || k < 1 || k > RFD_GALLERY_MAX_K || dim % 32 != 0 || rows < 0 || groups_max < 1) {
+        set_error("launch_gallery_search: n %d, k %d, dim %d, rows %d out of range", n, k, dim, rows);
+        return RFD_ERR_INVALID_ARG;
+    }
+    const int groups = gallery_search_groups(rows, groups_max), ksteps = dim / 32, nmt = n > 16 ? 2 : 1;
+    const size_t lds = (size_t)nmt * 16 * dim * sizeof(bf16_t) + (size_t)kGalleryWaves * nmt * 16 * k * sizeof(uint2);
+    constexpr int kLdsMax = 2 * 16 * 1024 * 2 + kGalleryWaves * 32 * RFD_GALLERY_MAX_K * 8; // dim 1024, 32 queries, k 32: 96 KiB
+    if (nmt == 2) {
+        static DynLdsOnce once;
+        RFD_TRY(once.ensure((const void *)gallery_search_kernel<2>, kLdsMax));
+        hipLaunchKernelGGL(gallery_search_kernel<2>, dim3(groups), dim3(kGalleryWaves * 64), lds, s, store, rows, ksteps, queries, n, k, ws);
+    } else {
+        static DynLdsOnce once;
+        RFD_TRY(once.ensure((const void *)gallery_search_kernel<1>, kLdsMax));
+        hipLaunchKernelGGL(gallery_search_kernel<1>, dim3(groups), dim3(kGalleryWaves * 64), lds, s, store, rows, ksteps, queries, n, k, ws);
+    }
+    RFD_HIP(hipGetLastError());
+    hipLaunchKernelGGL(gallery_merge_kernel, dim3(n), dim3(kGalleryWaves * 64), 0, s, ws, groups, n, k, scores, out_rows);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+} // namespace rfd

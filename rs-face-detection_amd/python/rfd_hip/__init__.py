@@ -25,6 +25,7 @@ RFD_ERR_IO = -6
 RFD_ERR_COMM = -7
 COMM_ID_BYTES = 128
 MAX_FACE_TENSORS = 4   # RFD_MAX_FACE_TENSORS
+GALLERY_MAX_K = 32     # RFD_GALLERY_MAX_K
 
 # debug_set_conv_tile / op_kernels_static: the forced tiles, enum ConvTile of csrc/kernels.h (each value's meaning is there)
 (TILE_HEURISTIC, TILE_128, TILE_256x128, TILE_256x64, TILE_NO_128, TILE_NO_PW_STREAM, TILE_PERSISTENT, TILE_GENERIC, TILE_PW_STREAM,
@@ -133,6 +134,8 @@ API_SYMBOLS = [
     "rfd_quality_decide_device", "rfd_normalize_embeddings_device",
     "rfd_face_tensor_config_quality_assessment", "rfd_liveness_config_default", "rfd_liveness_tensors",
     "rfd_liveness_tensors_device", "rfd_liveness_decide", "rfd_liveness_decide_device",
+    "rfd_gallery_create", "rfd_gallery_destroy", "rfd_gallery_size", "rfd_gallery_clear", "rfd_gallery_add", "rfd_gallery_add_device",
+    "rfd_gallery_get_rows", "rfd_gallery_search", "rfd_gallery_search_device", "rfd_debug_gallery_offset",
 ]
 
 _lib = None
@@ -237,6 +240,18 @@ def load_library(path=None):
     L.rfd_liveness_tensors_device.argtypes = [vp, C.POINTER(rfd_image), ci, vp, vp, vp, C.POINTER(vp), vp, vp, vp, ci]
     L.rfd_liveness_decide.argtypes = [vp, C.POINTER(vp), ci, ci, ci, vp, C.c_float, vp, vp]
     L.rfd_liveness_decide_device.argtypes = [vp, C.POINTER(vp), ci, ci, ci, vp, C.c_float, vp, vp]
+    L.rfd_gallery_create.argtypes = [vp, ci, ci, C.POINTER(vp)]
+    L.rfd_gallery_destroy.argtypes = [vp]
+    L.rfd_gallery_destroy.restype = None
+    L.rfd_gallery_size.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+    L.rfd_gallery_clear.argtypes = [vp]
+    L.rfd_gallery_add.argtypes = [vp, vp, ci, C.POINTER(ci)]
+    L.rfd_gallery_add_device.argtypes = [vp, vp, ci, C.POINTER(ci)]
+    L.rfd_gallery_get_rows.argtypes = [vp, ci, ci, vp]
+    L.rfd_gallery_search.argtypes = [vp, vp, ci, ci, vp, vp]
+    L.rfd_gallery_search_device.argtypes = [vp, vp, ci, ci, vp, vp, ci]
+    L.rfd_debug_gallery_offset.argtypes = [ci, ci, ci]
+    L.rfd_debug_gallery_offset.restype = C.c_int64
     if path is None:
         _lib = L
     return L
@@ -301,6 +316,11 @@ def _face_tensor_args(cfgs, n):
     return arr, outs, ptrs
 
 
+def gallery_offset(dim, row, d):
+    """element offset of (row, d) in a gallery's private storage layout (rfd_debug_gallery_offset; host only, -1: out of range)"""
+    return int(load_library().rfd_debug_gallery_offset(int(dim), int(row), int(d)))
+
+
 def op_kernels_static(backbone, image_w, image_h, n, op, co_running=True, tile=0, schedule=SCHEDULE_THROUGHPUT, cus=256):
     """debug_op_kernels without a context or a GPU: the kernel(s) a context of this backbone and image size would run op `op` of a
     chain of n images with, under forced tile `tile`, on a GPU of `cus` compute units"""
@@ -363,6 +383,70 @@ class FaceDetectionConfig:
         self.timeout = 20
 
 
+class Gallery:
+    """The enrolled embeddings of one detector in HBM (rfd.h, "gallery"): rows of `dim` values stored as bf16, searched by one
+    pass per 32 queries.  Obtained from RetinaFaceDetection.gallery(); close it before the detector."""
+
+    def __init__(self, det, dim, capacity):
+        self._L, self._det, self._g = det._L, det, C.c_void_p()
+        _check(self._L.rfd_gallery_create(det._ctx, int(dim), int(capacity), C.byref(self._g)))
+        self.dim, self.capacity = int(dim), int(capacity)
+
+    def close(self):
+        if getattr(self, "_g", None) and getattr(self._det, "_ctx", None):
+            self._L.rfd_gallery_destroy(self._g)
+        self._g = None
+
+    def __del__(self):
+        self.close()
+
+    def size(self):
+        """rows enrolled so far"""
+        rows = C.c_int()
+        _check(self._L.rfd_gallery_size(self._g, C.byref(rows), None, None))
+        return rows.value
+
+    def clear(self):
+        _check(self._L.rfd_gallery_clear(self._g))
+
+    def _rows2d(self, x):
+        x = np.ascontiguousarray(x, np.float32)
+        assert x.ndim == 2 and x.shape[1] == self.dim, "expected [n, %d], got %s" % (self.dim, x.shape)
+        return x
+
+    def add(self, emb):
+        """emb [n, dim] f32 (unit vectors) -> the row the first one got; the others follow it"""
+        x, first = self._rows2d(emb), C.c_int()
+        _check(self._L.rfd_gallery_add(self._g, x.ctypes.data, x.shape[0], C.byref(first)))
+        return first.value
+
+    def add_device(self, emb_ptr, n):
+        """the same from a raw device address ([n, dim] f32, 16-byte aligned); enqueued on the detector's stream, no synchronisation"""
+        first = C.c_int()
+        _check(self._L.rfd_gallery_add_device(self._g, emb_ptr, int(n), C.byref(first)))
+        return first.value
+
+    def rows(self, row0, n):
+        """the stored (bf16) values of rows [row0, row0 + n) as f32 [n, dim]"""
+        out = np.zeros((int(n), self.dim), np.float32)
+        _check(self._L.rfd_gallery_get_rows(self._g, int(row0), int(n), out.ctypes.data))
+        return out
+
+    def search(self, queries, k):
+        """queries [n, dim] f32 -> (scores [n, k] f32, rows [n, k] i32): the k best rows of every query, score descending, equal
+        scores by ascending row; (-inf, -1) where the gallery has fewer than k rows"""
+        x = self._rows2d(queries)
+        shape = (x.shape[0], max(int(k), 0))
+        scores, rows = np.zeros(shape, np.float32), np.zeros(shape, np.int32)
+        _check(self._L.rfd_gallery_search(self._g, x.ctypes.data, x.shape[0], int(k), scores.ctypes.data, rows.ctypes.data))
+        return scores, rows
+
+    def search_device(self, queries_ptr, n, k, scores_ptr, rows_ptr, async_=False):
+        """the same on raw device addresses (torch tensors' data_ptr()); enqueued on the detector's stream, with no host
+        synchronisation when async_ is set (then det.sync() before reading)"""
+        _check(self._L.rfd_gallery_search_device(self._g, queries_ptr, int(n), int(k), scores_ptr, rows_ptr, int(async_)))
+
+
 class RetinaFaceDetection:
     """Host mirror of the reference's RetinaFaceDetection (face_detection.rs:19-513).
 
@@ -391,7 +475,16 @@ class RetinaFaceDetection:
         self.image_size = (cfg.image_w, cfg.image_h)
         self.max_det = cfg.max_det
 
+    def gallery(self, dim=512, capacity=1 << 20):
+        """a face gallery on this detector's device and stream (rfd_gallery_create); it is closed with the detector at the latest"""
+        g = Gallery(self, dim, capacity)
+        self._galleries = getattr(self, "_galleries", []) + [g]
+        return g
+
     def close(self):
+        for g in getattr(self, "_galleries", []):
+            g.close()
+        self._galleries = []
         for p in getattr(self, "_pinned", []):
             self._L.rfd_host_free(p)
         self._pinned = []
