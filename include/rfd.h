@@ -474,8 +474,9 @@ RFD_API int rfd_liveness_decide_device(rfd_ctx *ctx, const float *const *logits,
  *      rfd_normalize_embeddings_device -> rfd_gallery_search_device runs back to back and only n * k pairs cross PCIe.
  *      A gallery belongs to ONE context (its device, its stream; same thread rule) and is destroyed BEFORE it.  It holds up to
  *      `capacity` rows of `dim` values, both fixed at creation, so no device pointer moves under enqueued work.  A row's index is
- *      its insertion order; the caller keeps the table from rows to identities.  Rows are never deleted (rfd_gallery_clear
- *      empties the gallery).
+ *      its insertion order; the caller keeps the table from rows to identities.  rfd_gallery_clear empties the gallery; single
+ *      rows leave and change through rfd_gallery_remove / _replace, and a gallery outlives its process through
+ *      rfd_gallery_save / _load (both below).
  *      Storage: every added f32 value is stored as bf16, rounded to nearest-even.  Rows are expected to be unit vectors (the
  *      output of rfd_normalize_embeddings); they are not normalised again.  The layout is private (MFMA-fragment-major).
  *      Score: score[i][r] = the f32 MFMA-accumulated dot product of bf16(query i) and stored row r over dim, 32 elements per
@@ -515,6 +516,52 @@ RFD_API int rfd_gallery_search(rfd_gallery *g, const float *queries, int n, int 
 /* The same with DEVICE pointers, by the conventions of rfd_detect_faces_device: enqueued on the context's stream; async = 0
  * returns after the stream has drained, any other value at once (rfd_sync before reading the results). */
 RFD_API int rfd_gallery_search_device(rfd_gallery *g, const float *queries, int n, int k, float *scores, int32_t *rows, int async);
+/* ---- remove and replace.  A row is LIVE from the add that made it until it is removed; a removed row keeps its number (add
+ *      never reuses it: rfd_gallery_size's rows stay the number of slots handed out), is never returned by a search again, and
+ *      its stored values are erased: rfd_gallery_get_rows reads +0.0 for it, nothing of the embedding stays in HBM.  Replace
+ *      writes new values into a row's slot and makes it live, whether it was live or removed: the way to correct an enrolment
+ *      and to reuse a hole.  rfd_gallery_clear also forgets every removal.
+ *      Search with removed rows: the same scan with one more term in its predicate.  Liveness lives in HBM as one 16-bit word
+ *      per block of 16 rows (bit i: row 16 b + i is live); the host keeps a copy, which answers _live and _removed.  Scores
+ *      keep their bits (a score depends on its two vectors only) and the order stays total, so a gallery with removed rows
+ *      returns what a gallery of its live rows alone would, under the map between the row numbers.  While no row is removed,
+ *      a search launches exactly the kernels it launched before these calls existed.
+ *      Stream order: remove and replace_device are enqueued on the context's stream in call order with no synchronisation
+ *      (row lists travel through page-locked memory of the gallery), so add_device -> remove -> replace_device ->
+ *      search_device(async) -> rfd_sync is one sequence without a host wait.  The host form of replace is synchronous.
+ *      Errors: a row outside [0, rows) returns RFD_ERR_INVALID_ARG, rfd_last_error() names the first such row and nothing is
+ *      changed; n = 0 is a no-op.  remove accepts duplicates and rows that are already removed (no-ops).  replace refuses a
+ *      row listed twice (two writers of one slot have no defined order) and, in the host form, non-finite values (naming the
+ *      row by its index in the call, as add does, and the element); the device form cannot look, as with add. ---- */
+RFD_API int rfd_gallery_remove(rfd_gallery *g, const int32_t *rows /* host [n] */, int n);
+/* rows: host [n], distinct; emb: host [n][dim].  Row rows[i] takes bf16(emb[i]) (RNE) and is live afterwards. */
+RFD_API int rfd_gallery_replace(rfd_gallery *g, const int32_t *rows, const float *emb, int n);
+/* The same with emb in DEVICE memory (16-byte aligned); the row list stays on the host. */
+RFD_API int rfd_gallery_replace_device(rfd_gallery *g, const int32_t *rows, const float *emb, int n);
+/* the number of live rows (rows - removed rows) */
+RFD_API int rfd_gallery_live(const rfd_gallery *g, int *live_rows);
+/* the removed rows in ascending order: at most cap of them into out (may be NULL when cap is 0); *count = how many there are,
+ * also when that exceeds cap */
+RFD_API int rfd_gallery_removed(const rfd_gallery *g, int32_t *out, int cap, int *count);
+
+/* ---- gallery file "RFDG", version 1, little-endian, in logical row order (not the private storage layout):
+ *          bytes 0..19  "RFDG", u32 version = 1, u32 dim, u32 rows, u32 reserved = 0
+ *          then         ceil(rows / 8) bytes of liveness, bit (r & 7) of byte r >> 3 set while row r is live, bits past rows 0
+ *          then         rows x dim bf16 values, row-major; a removed row is present, as zeros
+ *      Row numbers survive a round trip: after load, every rfd_gallery_get_rows and every search returns the bits it returned
+ *      before save, and _live / _removed answer the same.
+ *      save synchronises the context's stream, writes path + ".tmp" and renames it over path; a failure to open, write or
+ *      rename returns RFD_ERR_IO and leaves path as it was.
+ *      load validates the whole file before it allocates anything, then creates a gallery of `capacity` rows (0: the file's
+ *      rows, at least 1; fewer than the file's rows: RFD_ERR_CAPACITY) on ctx, synchronously.
+ *      Validation (all of it also in rfd_gallery_file_info, which needs no context and no device): a path that cannot be
+ *      opened or read returns RFD_ERR_IO; a wrong magic or version, a dim that is not a multiple of 32 in 32..1024, a non-zero
+ *      reserved field, a file length other than the header implies, liveness bits set beyond rows, or a non-finite bf16 value
+ *      (row and element are named) returns RFD_ERR_INVALID_ARG, and rfd_last_error() names the cause.  Values of a removed
+ *      row, which a file of this library holds as zeros, are loaded as zeros whatever the file holds. ---- */
+RFD_API int rfd_gallery_save(rfd_gallery *g, const char *path);
+RFD_API int rfd_gallery_load(rfd_ctx *ctx, const char *path, int capacity, rfd_gallery **out);
+RFD_API int rfd_gallery_file_info(const char *path, int *dim, int *rows, int *live); /* any of the three may be NULL */
 /* host only, no GPU: element offset of (row, d) in the private storage layout (-1: dim or an index out of range); the add
  * kernel scatters by this function and tests pin that it is a bijection and that an MFMA operand fetch is one 1 KiB span */
 RFD_API int64_t rfd_debug_gallery_offset(int dim, int row, int d);

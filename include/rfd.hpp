@@ -286,6 +286,12 @@ class Gallery {
         std::vector<int32_t> rows;  // [n][k], equal scores by ascending row; -1 in that tail
     };
     Gallery(RetinaFaceDetection &det, int dim, int capacity) : dim_(dim) { check(rfd_gallery_create(det.raw(), dim, capacity, &g_)); }
+    // a gallery read from a file that save() wrote; capacity 0 = the file's rows
+    Gallery(RetinaFaceDetection &det, const std::string &path, int capacity = 0)
+    {
+        check(rfd_gallery_load(det.raw(), path.c_str(), capacity, &g_));
+        check(rfd_gallery_size(g_, nullptr, nullptr, &dim_));
+    }
     Gallery(const Gallery &) = delete;
     Gallery &operator=(const Gallery &) = delete;
     ~Gallery() { rfd_gallery_destroy(g_); }
@@ -305,7 +311,34 @@ class Gallery {
         check(rfd_gallery_add(g_, emb.data(), (int)(emb.size() / (std::size_t)dim_), &first));
         return first;
     }
-    // the stored (bf16) values of rows [row0, row0 + n)
+    // rows (duplicates allowed) are erased and never found again; add does not reuse their numbers
+    void remove(const std::vector<int32_t> &rows) { check(rfd_gallery_remove(g_, rows.data(), (int)rows.size())); }
+    // row rows[i] takes emb[i] and is live afterwards, whether it was live or removed; rows must be distinct
+    void replace(const std::vector<int32_t> &rows, const std::vector<float> &emb)
+    {
+        if (emb.size() != rows.size() * (std::size_t)dim_) throw Error(RFD_ERR_INVALID_ARG, "replace: one embedding per row");
+        check(rfd_gallery_replace(g_, rows.data(), emb.data(), (int)rows.size()));
+    }
+    // the same with emb [rows.size()][dim] in device memory (16-byte aligned); enqueued, no synchronisation
+    void replace_device(const std::vector<int32_t> &rows, const float *emb) { check(rfd_gallery_replace_device(g_, rows.data(), emb, (int)rows.size())); }
+    int live() const
+    {
+        int n = 0;
+        check(rfd_gallery_live(g_, &n));
+        return n;
+    }
+    // the removed rows, ascending
+    std::vector<int32_t> removed() const
+    {
+        int n = 0;
+        check(rfd_gallery_removed(g_, nullptr, 0, &n));
+        std::vector<int32_t> out((std::size_t)n);
+        check(rfd_gallery_removed(g_, out.data(), n, &n));
+        return out;
+    }
+    // writes path + ".tmp", then renames it over path
+    void save(const std::string &path) { check(rfd_gallery_save(g_, path.c_str())); }
+    // the stored (bf16) values of rows [row0, row0 + n); a removed row reads as zeros
     std::vector<float> rows(int row0, int n)
     {
         std::vector<float> out((std::size_t)(n > 0 ? n : 0) * (std::size_t)dim_);

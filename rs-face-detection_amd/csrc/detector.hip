@@ -9,6 +9,7 @@
 #include <mutex>
 #include <vector>
 
+#include "gallery_file.h"
 #include "network.h"
 
 namespace rfd {
@@ -265,6 +266,20 @@ struct rfd_gallery {
     static constexpr size_t kStageBytes = 4u << 20;
     DevBuf stage;
     void *pin = nullptr;
+    // Liveness (rfd.h, "remove and replace").  The host's words are the truth: one per block of 16 rows enrolled so far, bit i =
+    // row 16 b + i is live.  Their device twin is read by the masked scan only, which runs while removed > 0, so it is brought
+    // up to date lazily: it is right for rows [0, live_synced), the rows added since are all live, and gallery_live_sync sets
+    // their bits before the twin is next written or read.  A gallery that never removes a row never touches it.
+    std::vector<uint16_t> live_words;
+    int removed = 0, live_synced = 0;
+    DevBuf live; // ceil(capacity / 16) words, zero beyond live_synced
+    // row lists of remove / replace travel through a ring of page-locked slots (like the context's frame descriptors), so the
+    // calls enqueue without waiting for the stream; allocated by the first such call.  A slot: rows | blocks | their new words.
+    static constexpr int kRing = 4, kEditRows = 1024;
+    int32_t *pin_edit[kRing] = {};
+    hipEvent_t pin_edit_done[kRing] = {};
+    int pin_edit_next = 0;
+    DevBuf edit;
 };
 
 namespace {
@@ -2177,6 +2192,96 @@ static int gallery_check_room(const rfd_gallery *g, int n)
     return RFD_OK;
 }
 
+// the host's live words: rows [row0, row1) become live (an add; the words grow with the rows)
+static void gallery_mark_live(rfd_gallery *g, int row0, int row1)
+{
+    g->live_words.resize((size_t)ceil_div(row1, 16), 0);
+    for (int r = row0; r < row1;) {
+        const int b = r >> 4, end = std::min(row1, (b + 1) * 16);
+        g->live_words[b] |= (uint16_t)((0xffffu >> (16 - (end - b * 16))) & (0xffffu << (r & 15)));
+        r = end;
+    }
+}
+
+// brings the device's live words up to the rows added since they were last written or read
+static int gallery_live_sync(rfd_gallery *g)
+{
+    if (g->live_synced < g->rows) RFD_TRY(launch_gallery_live_range((uint16_t *)g->live.p, g->live_synced, g->rows, g->ctx->stream));
+    g->live_synced = g->rows;
+    return RFD_OK;
+}
+
+// what a search passes for `live`: null while no row is removed (the scan without the mask), else the device's words
+static int gallery_search_mask(rfd_gallery *g, const uint16_t **live)
+{
+    *live = nullptr;
+    if (g->removed == 0) return RFD_OK;
+    RFD_TRY(gallery_live_sync(g));
+    *live = (const uint16_t *)g->live.p;
+    return RFD_OK;
+}
+
+static int gallery_check_rows(const rfd_gallery *g, const int32_t *rows, int n)
+{
+    for (int i = 0; i < n; ++i)
+        if (rows[i] < 0 || rows[i] >= g->rows) {
+            set_error("invalid argument: rows[%d] = %d is not in [0, %d)", i, rows[i], g->rows);
+            return RFD_ERR_INVALID_ARG;
+        }
+    return RFD_OK;
+}
+
+// Rows `rows` (host, checked) take bf16(emb[i]) and become live (emb: device [n][dim]), or are erased and become removed (emb
+// null).  Enqueued in chunks of kEditRows, each through the next ring slot; no synchronisation with the stream.
+static int gallery_edit(rfd_gallery *g, const int32_t *rows, const float *emb, int n)
+{
+    constexpr int kEdit = rfd_gallery::kEditRows;
+    for (int i = 0; i < rfd_gallery::kRing; ++i) { // first call on this gallery
+        if (!g->pin_edit[i]) RFD_HIP(hipHostMalloc((void **)&g->pin_edit[i], (size_t)3 * kEdit * sizeof(int32_t), hipHostMallocDefault));
+        if (!g->pin_edit_done[i]) RFD_HIP(hipEventCreateWithFlags(&g->pin_edit_done[i], hipEventDisableTiming));
+    }
+    RFD_TRY(g->edit.reserve((size_t)3 * kEdit * sizeof(int32_t)));
+    RFD_TRY(gallery_live_sync(g));
+    for (int at = 0; at < n; at += kEdit) {
+        const int m = std::min(kEdit, n - at);
+        const int slot = g->pin_edit_next;
+        g->pin_edit_next = (g->pin_edit_next + 1) % rfd_gallery::kRing;
+        RFD_HIP(hipEventSynchronize(g->pin_edit_done[slot])); // the copy that last used this slot has run
+        int32_t *list = g->pin_edit[slot], *blk = list + m;
+        for (int i = 0; i < m; ++i) {
+            const int r = rows[at + i];
+            list[i] = r;
+            blk[i] = r >> 4;
+            uint16_t &w = g->live_words[r >> 4];
+            const uint16_t bit = (uint16_t)(1u << (r & 15));
+            if (emb && !(w & bit)) { w |= bit; --g->removed; }
+            if (!emb && (w & bit)) { w &= (uint16_t)~bit; ++g->removed; }
+        }
+        std::sort(blk, blk + m);
+        const int nb = (int)(std::unique(blk, blk + m) - blk);
+        int32_t *word = blk + nb;
+        for (int j = 0; j < nb; ++j) word[j] = g->live_words[blk[j]];
+        RFD_HIP(hipMemcpyAsync(g->edit.p, list, (size_t)(m + 2 * nb) * sizeof(int32_t), hipMemcpyHostToDevice, g->ctx->stream));
+        RFD_HIP(hipEventRecord(g->pin_edit_done[slot], g->ctx->stream));
+        const int32_t *d = (const int32_t *)g->edit.p;
+        RFD_TRY(launch_gallery_put(emb ? emb + (size_t)at * g->dim : nullptr, d, m, g->dim, (bf16_t *)g->store.p, d + m, d + m + nb, nb, (uint16_t *)g->live.p,
+                                   g->ctx->stream));
+    }
+    return RFD_OK;
+}
+
+static int gallery_check_distinct(const int32_t *rows, int n)
+{
+    std::vector<int32_t> sorted(rows, rows + n);
+    std::sort(sorted.begin(), sorted.end());
+    for (int i = 1; i < n; ++i)
+        if (sorted[i] == sorted[i - 1]) {
+            set_error("invalid argument: row %d is listed more than once", sorted[i]);
+            return RFD_ERR_INVALID_ARG;
+        }
+    return RFD_OK;
+}
+
 int64_t rfd_debug_gallery_offset(int dim, int row, int d)
 {
     if (dim < 32 || dim > 1024 || dim % 32 != 0 || row < 0 || d < 0 || d >= dim) return -1;
@@ -2196,8 +2301,13 @@ int rfd_gallery_create(rfd_ctx *c, int dim, int capacity, rfd_gallery **out)
     const size_t bytes = (size_t)ceil_div(capacity, 16) * 16 * dim * sizeof(bf16_t);
     int st = g->store.reserve(bytes);
     if (st == RFD_OK) st = g->ws.reserve((size_t)g->groups_max * kGalleryMaxQueries * RFD_GALLERY_MAX_K * sizeof(uint2));
+    const size_t live_bytes = (size_t)ceil_div(ceil_div(capacity, 16), 2) * 2 * sizeof(uint16_t); // the masked scan loads aligned pairs of words
+    if (st == RFD_OK) st = g->live.reserve(live_bytes);
     // rows that were never added read as zeros (the tail of the last block is scored, then masked by its row index)
-    if (st == RFD_OK && hipMemsetAsync(g->store.p, 0, bytes, c->stream) != hipSuccess) { set_error("hipMemsetAsync of the gallery failed"); st = RFD_ERR_HIP; }
+    if (st == RFD_OK && (hipMemsetAsync(g->store.p, 0, bytes, c->stream) != hipSuccess || hipMemsetAsync(g->live.p, 0, live_bytes, c->stream) != hipSuccess)) {
+        set_error("hipMemsetAsync of the gallery failed");
+        st = RFD_ERR_HIP;
+    }
     if (st != RFD_OK) { rfd_gallery_destroy(g); return st; }
     *out = g;
     return RFD_OK;
@@ -2208,8 +2318,12 @@ void rfd_gallery_destroy(rfd_gallery *g)
     if (!g) return;
     (void)hipSetDevice(g->ctx->cfg.device_id);
     (void)hipStreamSynchronize(g->ctx->stream);
-    g->store.release(); g->ws.release(); g->stage.release();
+    g->store.release(); g->ws.release(); g->stage.release(); g->live.release(); g->edit.release();
     if (g->pin) (void)hipHostFree(g->pin);
+    for (int i = 0; i < rfd_gallery::kRing; ++i) {
+        if (g->pin_edit[i]) (void)hipHostFree(g->pin_edit[i]);
+        if (g->pin_edit_done[i]) (void)hipEventDestroy(g->pin_edit_done[i]);
+    }
     delete g;
 }
 
@@ -2227,7 +2341,9 @@ int rfd_gallery_clear(rfd_gallery *g)
     RFD_CHECK_ARG(g, "gallery is null");
     RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
     if (g->rows > 0) RFD_HIP(hipMemsetAsync(g->store.p, 0, (size_t)ceil_div(g->rows, 16) * 16 * g->dim * sizeof(bf16_t), g->ctx->stream));
-    g->rows = 0;
+    if (g->live_synced > 0) RFD_HIP(hipMemsetAsync(g->live.p, 0, (size_t)ceil_div(g->live_synced, 16) * sizeof(uint16_t), g->ctx->stream));
+    g->rows = g->removed = g->live_synced = 0;
+    g->live_words.clear();
     return RFD_OK;
 }
 
@@ -2240,6 +2356,7 @@ int rfd_gallery_add_device(rfd_gallery *g, const float *emb, int n, int *first_r
     RFD_TRY(gallery_check_room(g, n));
     RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
     RFD_TRY(launch_gallery_add(emb, n, g->dim, g->rows, (bf16_t *)g->store.p, g->ctx->stream));
+    gallery_mark_live(g, g->rows, g->rows + n);
     g->rows += n;
     return RFD_OK;
 }
@@ -2263,6 +2380,7 @@ int rfd_gallery_add(rfd_gallery *g, const float *emb, int n, int *first_row)
         RFD_TRY(launch_gallery_add((const float *)g->stage.p, m, g->dim, g->rows + i, (bf16_t *)g->store.p, g->ctx->stream));
         RFD_HIP(hipStreamSynchronize(g->ctx->stream));
     }
+    gallery_mark_live(g, g->rows, g->rows + n);
     g->rows += n;
     return RFD_OK;
 }
@@ -2295,8 +2413,10 @@ int rfd_gallery_search_device(rfd_gallery *g, const float *queries, int n, int k
     RFD_CHECK_ARG(queries && scores && rows, "null argument");
     RFD_CHECK_ARG((uintptr_t)queries % 16 == 0, "queries are not 16-byte aligned");
     RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
+    const uint16_t *live = nullptr;
+    RFD_TRY(gallery_search_mask(g, &live));
     for (int i = 0; i < n; i += kGalleryMaxQueries) // one pass over the gallery per group of queries; the passes share the workspace in stream order
-        RFD_TRY(launch_gallery_search((const bf16_t *)g->store.p, g->rows, g->dim, queries + (size_t)i * g->dim, std::min(kGalleryMaxQueries, n - i), k,
+        RFD_TRY(launch_gallery_search((const bf16_t *)g->store.p, live, g->rows, g->dim, queries + (size_t)i * g->dim, std::min(kGalleryMaxQueries, n - i), k,
                                       (uint2 *)g->ws.p, g->groups_max, scores + (size_t)i * k, rows + (size_t)i * k, g->ctx->stream));
     if (!async) RFD_HIP(hipStreamSynchronize(g->ctx->stream));
     return RFD_OK;
@@ -2311,6 +2431,8 @@ int rfd_gallery_search(rfd_gallery *g, const float *queries, int n, int k, float
     RFD_TRY(gallery_check_finite(queries, n, g->dim, "query"));
     RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
     RFD_TRY(gallery_host_stage(g));
+    const uint16_t *live = nullptr;
+    RFD_TRY(gallery_search_mask(g, &live));
     // the staging buffer holds one group: its queries, then its scores and rows
     const size_t qcap = (size_t)kGalleryMaxQueries * g->dim * sizeof(float), rcap = (size_t)kGalleryMaxQueries * RFD_GALLERY_MAX_K * sizeof(float);
     float *d_q = (float *)g->stage.p, *d_s = (float *)((char *)g->stage.p + qcap);
@@ -2321,13 +2443,160 @@ int rfd_gallery_search(rfd_gallery *g, const float *queries, int n, int k, float
         const size_t qbytes = (size_t)m * g->dim * sizeof(float), rbytes = (size_t)m * k * sizeof(float);
         memcpy(h, queries + (size_t)i * g->dim, qbytes);
         RFD_HIP(hipMemcpyAsync(d_q, h, qbytes, hipMemcpyHostToDevice, g->ctx->stream));
-        RFD_TRY(launch_gallery_search((const bf16_t *)g->store.p, g->rows, g->dim, d_q, m, k, (uint2 *)g->ws.p, g->groups_max, d_s, d_r, g->ctx->stream));
+        RFD_TRY(launch_gallery_search((const bf16_t *)g->store.p, live, g->rows, g->dim, d_q, m, k, (uint2 *)g->ws.p, g->groups_max, d_s, d_r, g->ctx->stream));
         RFD_HIP(hipMemcpyAsync(h + qcap, d_s, rbytes, hipMemcpyDeviceToHost, g->ctx->stream));
         RFD_HIP(hipMemcpyAsync(h + qcap + rcap, d_r, rbytes, hipMemcpyDeviceToHost, g->ctx->stream));
         RFD_HIP(hipStreamSynchronize(g->ctx->stream));
         memcpy(scores + (size_t)i * k, h + qcap, rbytes);
         memcpy(rows + (size_t)i * k, h + qcap + rcap, rbytes);
     }
+    return RFD_OK;
+}
+
+int rfd_gallery_remove(rfd_gallery *g, const int32_t *rows, int n)
+{
+    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(rows, "rows is null");
+    RFD_TRY(gallery_check_rows(g, rows, n));
+    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
+    return gallery_edit(g, rows, nullptr, n);
+}
+
+int rfd_gallery_replace_device(rfd_gallery *g, const int32_t *rows, const float *emb, int n)
+{
+    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(rows, "rows is null");
+    RFD_CHECK_ARG(emb && (uintptr_t)emb % 16 == 0, "emb is null or not 16-byte aligned");
+    RFD_TRY(gallery_check_rows(g, rows, n));
+    RFD_TRY(gallery_check_distinct(rows, n));
+    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
+    return gallery_edit(g, rows, emb, n);
+}
+
+int rfd_gallery_replace(rfd_gallery *g, const int32_t *rows, const float *emb, int n)
+{
+    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(rows && emb, "rows or emb is null");
+    RFD_TRY(gallery_check_rows(g, rows, n));
+    RFD_TRY(gallery_check_distinct(rows, n));
+    RFD_TRY(gallery_check_finite(emb, n, g->dim, "row"));
+    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
+    RFD_TRY(gallery_host_stage(g));
+    const int chunk = (int)(rfd_gallery::kStageBytes / ((size_t)g->dim * sizeof(float)));
+    for (int i = 0; i < n; i += chunk) { // one staging buffer: a chunk has left it before the next one is copied in
+        const int m = std::min(chunk, n - i);
+        const size_t bytes = (size_t)m * g->dim * sizeof(float);
+        memcpy(g->pin, emb + (size_t)i * g->dim, bytes);
+        RFD_HIP(hipMemcpyAsync(g->stage.p, g->pin, bytes, hipMemcpyHostToDevice, g->ctx->stream));
+        RFD_TRY(gallery_edit(g, rows + i, (const float *)g->stage.p, m));
+        RFD_HIP(hipStreamSynchronize(g->ctx->stream));
+    }
+    return RFD_OK;
+}
+
+int rfd_gallery_live(const rfd_gallery *g, int *live_rows)
+{
+    RFD_CHECK_ARG(g && live_rows, "null argument");
+    *live_rows = g->rows - g->removed;
+    return RFD_OK;
+}
+
+int rfd_gallery_removed(const rfd_gallery *g, int32_t *out, int cap, int *count)
+{
+    RFD_CHECK_ARG(g && count && cap >= 0 && (out || cap == 0), "null argument or cap < 0");
+    *count = g->removed;
+    int at = 0;
+    for (int r = 0; r < g->rows && at < cap && at < g->removed; ++r)
+        if (!((g->live_words[r >> 4] >> (r & 15)) & 1)) out[at++] = r;
+    return RFD_OK;
+}
+
+int rfd_gallery_file_info(const char *path, int *dim, int *rows, int *live)
+{
+    RFD_CHECK_ARG(path, "path is null");
+    char msg[256];
+    const int st = gallery_file_info(path, dim, rows, live, msg, sizeof msg);
+    if (st != RFD_OK) set_error("%s", msg);
+    return st;
+}
+
+int rfd_gallery_save(rfd_gallery *g, const char *path)
+{
+    RFD_CHECK_ARG(g && path, "null argument");
+    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
+    RFD_TRY(gallery_host_stage(g));
+    RFD_HIP(hipStreamSynchronize(g->ctx->stream));
+    const std::string tmp = std::string(path) + ".tmp";
+    FILE *f = fopen(tmp.c_str(), "wb");
+    if (!f) { set_error("cannot open %s for writing", tmp.c_str()); return RFD_ERR_IO; }
+    std::vector<unsigned char> bits((size_t)ceil_div(g->rows, 8), 0);
+    for (size_t i = 0; i < bits.size(); ++i) bits[i] = (unsigned char)(g->live_words[i >> 1] >> (8 * (i & 1)));
+    bool ok = gallery_file_write_head(f, g->dim, g->rows, bits.data());
+    int st = RFD_OK;
+    const int chunk = (int)(rfd_gallery::kStageBytes / ((size_t)g->dim * sizeof(bf16_t)));
+    for (int i = 0; ok && st == RFD_OK && i < g->rows; i += chunk) {
+        const int m = std::min(chunk, g->rows - i);
+        const size_t bytes = (size_t)m * g->dim * sizeof(bf16_t);
+        st = launch_gallery_export((const bf16_t *)g->store.p, i, m, g->dim, (bf16_t *)g->stage.p, g->ctx->stream);
+        if (st == RFD_OK && (hipMemcpyAsync(g->pin, g->stage.p, bytes, hipMemcpyDeviceToHost, g->ctx->stream) != hipSuccess ||
+                             hipStreamSynchronize(g->ctx->stream) != hipSuccess)) {
+            set_error("copying rows %d..%d of the gallery to the host failed", i, i + m - 1);
+            st = RFD_ERR_HIP;
+        }
+        if (st == RFD_OK) ok = gallery_file_write_values(f, (const uint16_t *)g->pin, (size_t)m * g->dim);
+    }
+    ok = (fclose(f) == 0) && ok;
+    if (st == RFD_OK && !ok) { set_error("short write to %s", tmp.c_str()); st = RFD_ERR_IO; }
+    if (st == RFD_OK && rename(tmp.c_str(), path) != 0) { set_error("cannot rename %s to %s", tmp.c_str(), path); st = RFD_ERR_IO; }
+    if (st != RFD_OK) (void)remove(tmp.c_str());
+    return st;
+}
+
+int rfd_gallery_load(rfd_ctx *c, const char *path, int capacity, rfd_gallery **out)
+{
+    RFD_CHECK_ARG(c && path && out && capacity >= 0, "null argument or capacity < 0");
+    *out = nullptr;
+    RFD_TRY(rfd_gallery_file_info(path, nullptr, nullptr, nullptr)); // the whole validation, before anything is allocated
+    GalleryFileReader r;
+    if (int st = r.open(path)) { set_error("%s", r.msg); return st; }
+    if (capacity == 0) capacity = std::max(r.rows, 1);
+    if (capacity < r.rows) { set_error("%s holds %d rows: a capacity of %d does not fit them", path, r.rows, capacity); return RFD_ERR_CAPACITY; }
+    rfd_gallery *g = nullptr;
+    RFD_TRY(rfd_gallery_create(c, r.dim, capacity, &g));
+    int st = gallery_host_stage(g);
+    const int chunk = (int)(rfd_gallery::kStageBytes / ((size_t)r.dim * sizeof(bf16_t)));
+    uint16_t *h = (uint16_t *)g->pin;
+    for (int i = 0; st == RFD_OK && i < r.rows; i += chunk) {
+        const int m = std::min(chunk, r.rows - i);
+        const size_t bytes = (size_t)m * r.dim * sizeof(bf16_t);
+        st = r.read_rows(m, h);
+        if (st != RFD_OK) { set_error("%s", r.msg); break; }
+        for (int j = 0; j < m; ++j) // a removed row is erased whatever the file holds for it
+            if (!r.is_live(i + j)) memset(h + (size_t)j * r.dim, 0, (size_t)r.dim * sizeof(uint16_t));
+        if (hipMemcpyAsync(g->stage.p, h, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) { set_error("copying rows of %s to the device failed", path); st = RFD_ERR_HIP; }
+        if (st == RFD_OK) st = launch_gallery_import((const bf16_t *)g->stage.p, m, r.dim, i, (bf16_t *)g->store.p, c->stream);
+        if (st == RFD_OK && hipStreamSynchronize(c->stream) != hipSuccess) { set_error("loading rows of %s failed", path); st = RFD_ERR_HIP; }
+    }
+    if (st == RFD_OK && r.rows > 0) {
+        g->rows = g->live_synced = r.rows;
+        g->removed = r.rows - r.live;
+        g->live_words.assign((size_t)ceil_div(r.rows, 16), 0);
+        for (size_t i = 0; i < r.bits.size(); ++i) g->live_words[i >> 1] |= (uint16_t)(r.bits[i] << (8 * (i & 1)));
+        const size_t bytes = g->live_words.size() * sizeof(uint16_t); // <= ceil(2^30 / 16) * 2 = 128 MiB: in pieces
+        for (size_t at = 0; st == RFD_OK && at < bytes; at += rfd_gallery::kStageBytes) {
+            const size_t m = std::min(rfd_gallery::kStageBytes, bytes - at);
+            memcpy(g->pin, (const char *)g->live_words.data() + at, m);
+            if (hipMemcpyAsync((char *)g->live.p + at, g->pin, m, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+                set_error("copying the live words of %s to the device failed", path);
+                st = RFD_ERR_HIP;
+            }
+        }
+    }
+    if (st != RFD_OK) { rfd_gallery_destroy(g); return st; }
+    *out = g;
     return RFD_OK;
 }
 

@@ -195,9 +195,19 @@ int launch_gallery_get(const bf16_t *store, int row0, int n, int dim, float *out
 // workgroups a search over `rows` rows runs with, <= groups_max; ws must hold that many x n x k keys of 8 bytes
 int gallery_search_groups(int rows, int groups_max);
 // one pass: queries [n <= kGalleryMaxQueries][dim] f32 (device, 16-byte aligned) against rows [0, rows) -> scores / out_rows
-// [n][k] under (score descending, row ascending); two launches (scan, merge of the workgroups' lists), no synchronisation
-int launch_gallery_search(const bf16_t *store, int rows, int dim, const float *queries, int n, int k, uint2 *ws, int groups_max,
+// [n][k] under (score descending, row ascending); two launches (scan, merge of the workgroups' lists), no synchronisation.
+// live: null (every row counts: the scan without the mask), or one 16-bit word per block of 16 rows, bit i = row 16 b + i counts
+int launch_gallery_search(const bf16_t *store, const uint16_t *live, int rows, int dim, const float *queries, int n, int k, uint2 *ws, int groups_max,
                           float *scores, int32_t *out_rows, hipStream_t s);
+// rows[i] (device list, distinct unless emb is null) of store takes bf16(emb[i]), or zeros where emb is null; then live[blk[j]] =
+// word[j] for j < nwords <= n (device lists, blk distinct)
+int launch_gallery_put(const float *emb, const int32_t *rows, int n, int dim, bf16_t *store, const int32_t *blk, const int32_t *word, int nwords,
+                       uint16_t *live, hipStream_t s);
+// sets the live bits of rows [row0, row1), row0 < row1
+int launch_gallery_live_range(uint16_t *live, int row0, int row1, hipStream_t s);
+// bf16 values [n][dim] in row-major order (device, 16-byte aligned) <-> rows [row0, row0 + n) of store, bit for bit
+int launch_gallery_import(const bf16_t *src, int n, int dim, int row0, bf16_t *store, hipStream_t s);
+int launch_gallery_export(const bf16_t *store, int row0, int n, int dim, bf16_t *out, hipStream_t s);
 
 // ---------------------------------------------------------------- convolution engine (kernels_conv.hip)
 // Activations: NHWC bf16.  Weights: [Cout][KH][KW][Cin] bf16 (K contiguous).  f32 accumulate on MFMA.

@@ -127,11 +127,21 @@ int launch_gallery_get(const bf16_t *store, int row0, int n, int dim, float *out
 }
 
 // ---- search: n <= 16 * NMT queries against rows [0, rows); writes ws[blockIdx.x][n][k] ----
-template <int NMT>
+// MASKED: rows whose bit in `live` (one 16-bit word per row block; an even number of words is allocated) is clear are scored and
+// then never offered to a list.  Every K step loads the aligned 32 bits that hold its block's word right behind its operand,
+// kGalleryPrefetch steps ahead, into a register that travels with the operand; the step reads it back into a scalar register
+// before it issues the next loads, and a block's last step takes the row's bit from it.  Forms that made the compiler wait for
+// every load in flight (vmcnt(0)) inside the loop, which this one does not: loading with the last K step alone (the word becomes
+// a value merged from two paths, and all words are copied at every step); loading 16 bits (the words are zero-extended, or packed
+// in pairs, at the loop's back edge); using the word after the next loads were issued (old and new value live side by side and
+// are copied at the back edge).  The words' address is the one member of the pack `Live` of a MASKED instantiation; without
+// MASKED the pack is empty, so that instantiation has the arguments and the code of the scan as it was.
+template <int NMT, bool MASKED, class... Live>
 __global__ void __launch_bounds__(kGalleryWaves * 64) gallery_search_kernel(const bf16_t *__restrict__ store, int rows, int ksteps,
                                                                              const float *__restrict__ queries, int n, int k,
-                                                                             uint2 *__restrict__ ws)
+                                                                             uint2 *__restrict__ ws, Live... live)
 {
+    static_assert(sizeof...(Live) == (MASKED ? 1 : 0), "a masked scan takes the live words, the other nothing");
     extern __shared__ __attribute__((aligned(16))) unsigned char gallery_smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6); // scalar: the walk below is wave-uniform
     const int dim = ksteps * 32, quads = dim >> 2;
@@ -156,15 +166,22 @@ __global__ void __launch_bounds__(kGalleryWaves * 64) gallery_search_kernel(cons
         int pblk = blk, pks = 0;                         // the step the loads are at
         const uint4 *src = reinterpret_cast<const uint4 *>(store) + lane;
         uint4 buf[kGalleryPrefetch];
+        // MASKED: a zero the compiler takes for a per-lane value.  With it in the address the words are fetched by vector loads,
+        // which return in order behind the operand loads and are waited for by count (vmcnt) at their use; the scalar load that a
+        // wave-uniform address gets instead is waited for by the lgkmcnt(0) in front of the very next LDS read.
+        int lane_zero = 0;
+        if constexpr (MASKED) asm("v_mov_b32 %0, 0" : "=v"(lane_zero));
+        uint32_t lw[kGalleryPrefetch] = {}; // MASKED: lw[i] = the live words of the block whose K step is in buf[i] and of its neighbour
         // Loads beyond the wave's last block re-read its last in-range block (never out of bounds); their MFMAs run and are dropped.
-        auto issue = [&](uint4 &dst) {
+        auto issue = [&](uint4 &dst, uint32_t &words) {
             const int b = pblk < nblocks ? pblk : nblocks - 1;
             dst = src[((size_t)b * ksteps + pks) * 64];
+            if constexpr (MASKED) words = reinterpret_cast<const uint32_t *>((live, ...))[(b >> 1) + lane_zero];
             if (++pks == ksteps) { pks = 0; pblk += stride; }
         };
 #pragma unroll
         for (int i = 0; i < kGalleryPrefetch; ++i) {
-            issue(buf[i]);
+            issue(buf[i], lw[i]);
             __builtin_amdgcn_sched_barrier(0); // keep the issue order: the loop waits for buf[0] with the other loads still in flight
         }
         f32x4 acc[NMT];
@@ -174,15 +191,20 @@ __global__ void __launch_bounds__(kGalleryWaves * 64) gallery_search_kernel(cons
 #pragma unroll
             for (int i = 0; i < kGalleryPrefetch; ++i) {
                 const bf16x8 b = __builtin_bit_cast(bf16x8, buf[i]);
+                // before issue() loads lw[i] anew; their load was issued right behind buf[i]'s, which the MFMAs below wait for
+                uint32_t words = 0;
+                if constexpr (MASKED) words = __builtin_amdgcn_readfirstlane(lw[i]);
 #pragma unroll
                 for (int mt = 0; mt < NMT; ++mt) {
                     const uint2 lo = afrag[((mt * ksteps + ks) * 2 + 0) * 64 + lane], hi = afrag[((mt * ksteps + ks) * 2 + 1) * 64 + lane];
                     acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y)), b, acc[mt], 0, 0, 0);
                 }
-                issue(buf[i]);
+                issue(buf[i], lw[i]);
                 if (++ks == ksteps) {
                     if (blk < nblocks) {
                         const int row = blk * 16 + (lane & 15);
+                        bool row_ok = row < rows;
+                        if constexpr (MASKED) row_ok = row_ok && ((words >> (16 * (blk & 1) + (lane & 15))) & 1u);
                         // the common case, no score of the block passes its list's filter, costs the compares and one branch
                         bool any = false;
 #pragma unroll
@@ -190,7 +212,7 @@ __global__ void __launch_bounds__(kGalleryWaves * 64) gallery_search_kernel(cons
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
                                 const int q = mt * 16 + 4 * (lane >> 4) + r;
-                                if (row < rows && q < n) {
+                                if (row_ok && q < n) {
                                     const uint2 t = mine[q * k + k - 1];
                                     any |= key_better(acc[mt][r], row, __uint_as_float(t.x), (int)t.y);
                                 }
@@ -201,7 +223,7 @@ __global__ void __launch_bounds__(kGalleryWaves * 64) gallery_search_kernel(cons
 #pragma unroll
                                 for (int r = 0; r < 4; ++r) {
                                     const int q = mt * 16 + 4 * (lane >> 4) + r;
-                                    list_offer(mine, q, k, acc[mt][r], row, row < rows && q < n, lane);
+                                    list_offer(mine, q, k, acc[mt][r], row, row_ok && q < n, lane);
                                 }
                         }
                     }
@@ -253,7 +275,27 @@ int gallery_search_groups(int rows, int groups_max)
     return std::max(1, std::min(groups_max, ceil_div(nblocks, kGalleryWaves * 2)));
 }
 
-int launch_gallery_search(const bf16_t *store, int rows, int dim, const float *queries, int n, int k, uint2 *ws, int groups_max,
+using GalleryLiveWords = const uint16_t *__restrict__;
+
+template <int NMT, bool MASKED>
+static int launch_gallery_scan(int groups, size_t lds, hipStream_t s, const bf16_t *store, int rows, int ksteps, const float *queries, int n, int k,
+                               uint2 *ws, const uint16_t *live)
+{
+    constexpr int kLdsMax = 2 * 16 * 1024 * 2 + kGalleryWaves * 32 * RFD_GALLERY_MAX_K * 8; // dim 1024, 32 queries, k 32: 96 KiB
+    static DynLdsOnce once;
+    const void *kernel = nullptr;
+    if constexpr (MASKED) kernel = (const void *)gallery_search_kernel<NMT, true, GalleryLiveWords>;
+    else kernel = (const void *)gallery_search_kernel<NMT, false>;
+    RFD_TRY(once.ensure(kernel, kLdsMax));
+    if constexpr (MASKED)
+        hipLaunchKernelGGL((gallery_search_kernel<NMT, true, GalleryLiveWords>), dim3(groups), dim3(kGalleryWaves * 64), lds, s, store, rows, ksteps, queries, n, k, ws, live);
+    else
+        hipLaunchKernelGGL((gallery_search_kernel<NMT, false>), dim3(groups), dim3(kGalleryWaves * 64), lds, s, store, rows, ksteps, queries, n, k, ws);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+int launch_gallery_search(const bf16_t *store, const uint16_t *live, int rows, int dim, const float *queries, int n, int k, uint2 *ws, int groups_max,
                           float *scores, int32_t *out_rows, hipStream_t s)
 {
     if (n < 1 || n > kGalleryMaxQueries || k < 1 || k > RFD_GALLERY_MAX_K || dim % 32 != 0 || rows < 0 || groups_max < 1) {
@@ -262,18 +304,93 @@ int launch_gallery_search(const bf16_t *store, int rows, int dim, const float *q
     }
     const int groups = gallery_search_groups(rows, groups_max), ksteps = dim / 32, nmt = n > 16 ? 2 : 1;
     const size_t lds = (size_t)nmt * 16 * dim * sizeof(bf16_t) + (size_t)kGalleryWaves * nmt * 16 * k * sizeof(uint2);
-    constexpr int kLdsMax = 2 * 16 * 1024 * 2 + kGalleryWaves * 32 * RFD_GALLERY_MAX_K * 8; // dim 1024, 32 queries, k 32: 96 KiB
-    if (nmt == 2) {
-        static DynLdsOnce once;
-        RFD_TRY(once.ensure((const void *)gallery_search_kernel<2>, kLdsMax));
-        hipLaunchKernelGGL(gallery_search_kernel<2>, dim3(groups), dim3(kGalleryWaves * 64), lds, s, store, rows, ksteps, queries, n, k, ws);
-    } else {
-        static DynLdsOnce once;
-        RFD_TRY(once.ensure((const void *)gallery_search_kernel<1>, kLdsMax));
-        hipLaunchKernelGGL(gallery_search_kernel<1>, dim3(groups), dim3(kGalleryWaves * 64), lds, s, store, rows, ksteps, queries, n, k, ws);
-    }
-    RFD_HIP(hipGetLastError());
+    auto *scan = live ? (nmt == 2 ? launch_gallery_scan<2, true> : launch_gallery_scan<1, true>) : (nmt == 2 ? launch_gallery_scan<2, false> : launch_gallery_scan<1, false>);
+    RFD_TRY(scan(groups, lds, s, store, rows, ksteps, queries, n, k, ws, live));
     hipLaunchKernelGGL(gallery_merge_kernel, dim3(n), dim3(kGalleryWaves * 64), 0, s, ws, groups, n, k, scores, out_rows);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+// ---- remove / replace: rows[i] of the store takes bf16(emb[i]) (RNE), or zeros where emb is null.  One thread per 16-byte
+//      operand; the first `nwords` threads also store the new live words of the blocks the call touches (blk ascending and
+//      distinct, so every word has one writer).  rows / blk / word: device copies of the host's lists. ----
+__global__ void __launch_bounds__(256) gallery_put_kernel(const float *__restrict__ emb, const int32_t *__restrict__ rows, int n, int dim,
+                                                          bf16_t *__restrict__ store, const int32_t *__restrict__ blk,
+                                                          const int32_t *__restrict__ word, int nwords, uint16_t *__restrict__ live)
+{
+    const int per_row = dim >> 3;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < (size_t)nwords) live[blk[i]] = (uint16_t)word[i];
+    if (i >= (size_t)n * per_row) return;
+    const int r = (int)(i / per_row), d = (int)(i - (size_t)r * per_row) * 8;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (emb) {
+        const float4 a = *reinterpret_cast<const float4 *>(emb + (size_t)r * dim + d), b = *reinterpret_cast<const float4 *>(emb + (size_t)r * dim + d + 4);
+        const uint2 lo = pack_bf16x4(a.x, a.y, a.z, a.w), hi = pack_bf16x4(b.x, b.y, b.z, b.w);
+        v = make_uint4(lo.x, lo.y, hi.x, hi.y);
+    }
+    *reinterpret_cast<uint4 *>(store + gallery_offset(dim, rows[r], d)) = v;
+}
+
+int launch_gallery_put(const float *emb, const int32_t *rows, int n, int dim, bf16_t *store, const int32_t *blk, const int32_t *word, int nwords,
+                       uint16_t *live, hipStream_t s)
+{
+    const size_t items = (size_t)n * (dim >> 3); // nwords <= n <= items
+    hipLaunchKernelGGL(gallery_put_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, emb, rows, n, dim, store, blk, word, nwords, live);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+// ---- live words of rows [row0, row1), row0 < row1: their bits are set, the other bits of the two end blocks stay.  One thread per
+//      block, so every word has one writer. ----
+__global__ void __launch_bounds__(256) gallery_live_range_kernel(uint16_t *__restrict__ live, int row0, int row1)
+{
+    const int b0 = row0 >> 4, b = b0 + (int)(blockIdx.x * 256 + threadIdx.x);
+    if (b > ((row1 - 1) >> 4)) return;
+    const int lo = std::max(row0 - b * 16, 0), hi = std::min(row1 - b * 16, 16); // bits [lo, hi) of word b
+    const uint32_t mask = (0xffffu >> (16 - hi)) & (0xffffu << lo) & 0xffffu;
+    live[b] = (uint16_t)(mask == 0xffffu ? mask : (live[b] | mask));
+}
+
+int launch_gallery_live_range(uint16_t *live, int row0, int row1, hipStream_t s)
+{
+    const int nb = ((row1 - 1) >> 4) - (row0 >> 4) + 1;
+    hipLaunchKernelGGL(gallery_live_range_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, live, row0, row1);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+// ---- file forms: bf16 values in row-major order <-> the fragment-major store, no conversion.  One thread per 16-byte operand. ----
+__global__ void __launch_bounds__(256) gallery_import_kernel(const bf16_t *__restrict__ src, int n, int dim, int row0, bf16_t *__restrict__ store)
+{
+    const int per_row = dim >> 3;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)n * per_row) return;
+    const int r = (int)(i / per_row), d = (int)(i - (size_t)r * per_row) * 8;
+    *reinterpret_cast<uint4 *>(store + gallery_offset(dim, row0 + r, d)) = *reinterpret_cast<const uint4 *>(src + (size_t)r * dim + d);
+}
+
+__global__ void __launch_bounds__(256) gallery_export_kernel(const bf16_t *__restrict__ store, int row0, int n, int dim, bf16_t *__restrict__ out)
+{
+    const int per_row = dim >> 3;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)n * per_row) return;
+    const int r = (int)(i / per_row), d = (int)(i - (size_t)r * per_row) * 8;
+    *reinterpret_cast<uint4 *>(out + (size_t)r * dim + d) = *reinterpret_cast<const uint4 *>(store + gallery_offset(dim, row0 + r, d));
+}
+
+int launch_gallery_import(const bf16_t *src, int n, int dim, int row0, bf16_t *store, hipStream_t s)
+{
+    const size_t items = (size_t)n * (dim >> 3);
+    hipLaunchKernelGGL(gallery_import_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, src, n, dim, row0, store);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+int launch_gallery_export(const bf16_t *store, int row0, int n, int dim, bf16_t *out, hipStream_t s)
+{
+    const size_t items = (size_t)n * (dim >> 3);
+    hipLaunchKernelGGL(gallery_export_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, store, row0, n, dim, out);
     RFD_HIP(hipGetLastError());
     return RFD_OK;
 }

@@ -136,6 +136,8 @@ API_SYMBOLS = [
     "rfd_liveness_tensors_device", "rfd_liveness_decide", "rfd_liveness_decide_device",
     "rfd_gallery_create", "rfd_gallery_destroy", "rfd_gallery_size", "rfd_gallery_clear", "rfd_gallery_add", "rfd_gallery_add_device",
     "rfd_gallery_get_rows", "rfd_gallery_search", "rfd_gallery_search_device", "rfd_debug_gallery_offset",
+    "rfd_gallery_remove", "rfd_gallery_replace", "rfd_gallery_replace_device", "rfd_gallery_live", "rfd_gallery_removed",
+    "rfd_gallery_save", "rfd_gallery_load", "rfd_gallery_file_info",
 ]
 
 _lib = None
@@ -252,6 +254,14 @@ def load_library(path=None):
     L.rfd_gallery_search_device.argtypes = [vp, vp, ci, ci, vp, vp, ci]
     L.rfd_debug_gallery_offset.argtypes = [ci, ci, ci]
     L.rfd_debug_gallery_offset.restype = C.c_int64
+    L.rfd_gallery_remove.argtypes = [vp, vp, ci]
+    L.rfd_gallery_replace.argtypes = [vp, vp, vp, ci]
+    L.rfd_gallery_replace_device.argtypes = [vp, vp, vp, ci]
+    L.rfd_gallery_live.argtypes = [vp, C.POINTER(ci)]
+    L.rfd_gallery_removed.argtypes = [vp, vp, ci, C.POINTER(ci)]
+    L.rfd_gallery_save.argtypes = [vp, C.c_char_p]
+    L.rfd_gallery_load.argtypes = [vp, C.c_char_p, ci, C.POINTER(vp)]
+    L.rfd_gallery_file_info.argtypes = [C.c_char_p, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
     if path is None:
         _lib = L
     return L
@@ -321,6 +331,48 @@ def gallery_offset(dim, row, d):
     return int(load_library().rfd_debug_gallery_offset(int(dim), int(row), int(d)))
 
 
+GALLERY_FILE_MAGIC, GALLERY_FILE_VERSION = b"RFDG", 1
+
+
+def _bf16_bits(values):
+    """f32 array of values that are exact in bf16 -> their 16 bits (the upper half of the f32 bits)"""
+    bits = np.ascontiguousarray(values, np.float32).view(np.uint32)
+    assert not np.any(bits & 0xffff), "values are not exact in bf16"
+    return (bits >> 16).astype("<u2")
+
+
+def gallery_file_write(path, values_bf16_as_f32, live):
+    """Writes a gallery file (rfd.h, "gallery file") from values [rows, dim] that are exact in bf16 (what Gallery.rows returns)
+    and a boolean mask [rows] of the live rows.  Pure numpy: the format stated a second time, apart from the library's code."""
+    v = np.ascontiguousarray(values_bf16_as_f32, np.float32)
+    live = np.asarray(live, bool).reshape(-1)
+    assert v.ndim == 2 and live.shape[0] == v.shape[0]
+    with open(path, "wb") as f:
+        f.write(GALLERY_FILE_MAGIC + np.array([GALLERY_FILE_VERSION, v.shape[1], v.shape[0], 0], "<u4").tobytes())
+        f.write(np.packbits(live, bitorder="little").tobytes())
+        f.write(_bf16_bits(v).tobytes())
+
+
+def gallery_file_read(path):
+    """-> (values [rows, dim] f32, live [rows] bool) of a gallery file; pure numpy, checks nothing but the magic and the length"""
+    with open(path, "rb") as f:
+        data = f.read()
+    assert data[:4] == GALLERY_FILE_MAGIC, "not a gallery file"
+    version, dim, rows, _ = (int(x) for x in np.frombuffer(data, "<u4", 4, 4))
+    nbits = (rows + 7) // 8
+    assert version == GALLERY_FILE_VERSION and len(data) == 20 + nbits + rows * dim * 2
+    live = np.unpackbits(np.frombuffer(data, np.uint8, nbits, 20), bitorder="little")[:rows].astype(bool)
+    bits = np.frombuffer(data, "<u2", rows * dim, 20 + nbits).astype(np.uint32) << 16
+    return bits.view(np.float32).reshape(rows, dim), live
+
+
+def gallery_file_info(path):
+    """(dim, rows, live rows) of a gallery file after the library's whole validation (rfd_gallery_file_info; host only, no GPU)"""
+    dim, rows, live = C.c_int(), C.c_int(), C.c_int()
+    _check(load_library().rfd_gallery_file_info(os.fsencode(path), C.byref(dim), C.byref(rows), C.byref(live)))
+    return dim.value, rows.value, live.value
+
+
 def op_kernels_static(backbone, image_w, image_h, n, op, co_running=True, tile=0, schedule=SCHEDULE_THROUGHPUT, cus=256):
     """debug_op_kernels without a context or a GPU: the kernel(s) a context of this backbone and image size would run op `op` of a
     chain of n images with, under forced tile `tile`, on a GPU of `cus` compute units"""
@@ -387,9 +439,15 @@ class Gallery:
     """The enrolled embeddings of one detector in HBM (rfd.h, "gallery"): rows of `dim` values stored as bf16, searched by one
     pass per 32 queries.  Obtained from RetinaFaceDetection.gallery(); close it before the detector."""
 
-    def __init__(self, det, dim, capacity):
+    def __init__(self, det, dim, capacity, _load=None):
         self._L, self._det, self._g = det._L, det, C.c_void_p()
-        _check(self._L.rfd_gallery_create(det._ctx, int(dim), int(capacity), C.byref(self._g)))
+        if _load is None:
+            _check(self._L.rfd_gallery_create(det._ctx, int(dim), int(capacity), C.byref(self._g)))
+        else:   # RetinaFaceDetection.load_gallery
+            _check(self._L.rfd_gallery_load(det._ctx, os.fsencode(_load), int(capacity), C.byref(self._g)))
+            cap, d = C.c_int(), C.c_int()
+            _check(self._L.rfd_gallery_size(self._g, None, C.byref(cap), C.byref(d)))
+            dim, capacity = d.value, cap.value
         self.dim, self.capacity = int(dim), int(capacity)
 
     def close(self):
@@ -426,8 +484,47 @@ class Gallery:
         _check(self._L.rfd_gallery_add_device(self._g, emb_ptr, int(n), C.byref(first)))
         return first.value
 
+    @staticmethod
+    def _row_list(rows):
+        return np.ascontiguousarray(np.asarray(rows, np.int64).reshape(-1), np.int32)
+
+    def remove(self, rows):
+        """rows (a list, duplicates allowed) are erased and never found again; their numbers are not reused by add"""
+        r = self._row_list(rows)
+        _check(self._L.rfd_gallery_remove(self._g, r.ctypes.data, r.shape[0]))
+
+    def replace(self, rows, emb):
+        """row rows[i] takes emb[i] ([n, dim] f32) and is live afterwards, whether it was live or removed; rows must be distinct"""
+        r, x = self._row_list(rows), self._rows2d(emb)
+        assert r.shape[0] == x.shape[0], "one row number per embedding"
+        _check(self._L.rfd_gallery_replace(self._g, r.ctypes.data, x.ctypes.data, r.shape[0]))
+
+    def replace_device(self, rows, emb_ptr):
+        """the same with emb at a raw device address ([len(rows), dim] f32, 16-byte aligned); the row list stays on the host;
+        enqueued on the detector's stream, no synchronisation"""
+        r = self._row_list(rows)
+        _check(self._L.rfd_gallery_replace_device(self._g, r.ctypes.data, emb_ptr, r.shape[0]))
+
+    def live(self):
+        """rows enrolled and not removed"""
+        n = C.c_int()
+        _check(self._L.rfd_gallery_live(self._g, C.byref(n)))
+        return n.value
+
+    def removed(self):
+        """the removed rows, ascending (i32 array)"""
+        n = C.c_int()
+        _check(self._L.rfd_gallery_removed(self._g, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.int32)
+        _check(self._L.rfd_gallery_removed(self._g, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def save(self, path):
+        """writes the gallery to `path` (rfd_gallery_save: synchronises, writes path + ".tmp", renames)"""
+        _check(self._L.rfd_gallery_save(self._g, os.fsencode(path)))
+
     def rows(self, row0, n):
-        """the stored (bf16) values of rows [row0, row0 + n) as f32 [n, dim]"""
+        """the stored (bf16) values of rows [row0, row0 + n) as f32 [n, dim]; a removed row reads as zeros"""
         out = np.zeros((int(n), self.dim), np.float32)
         _check(self._L.rfd_gallery_get_rows(self._g, int(row0), int(n), out.ctypes.data))
         return out
@@ -478,6 +575,12 @@ class RetinaFaceDetection:
     def gallery(self, dim=512, capacity=1 << 20):
         """a face gallery on this detector's device and stream (rfd_gallery_create); it is closed with the detector at the latest"""
         g = Gallery(self, dim, capacity)
+        self._galleries = getattr(self, "_galleries", []) + [g]
+        return g
+
+    def load_gallery(self, path, capacity=0):
+        """a gallery read from a file that Gallery.save wrote (rfd_gallery_load); capacity 0 = the file's rows"""
+        g = Gallery(self, 0, capacity, _load=path)
         self._galleries = getattr(self, "_galleries", []) + [g]
         return g
 

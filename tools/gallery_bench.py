@@ -8,6 +8,12 @@ Per size: the gallery is filled from device memory (rfd_gallery_add_device, seed
 read once per search); the floor is those bytes / 6.2 TB/s, the rate a streaming global_load_dwordx4 kernel reaches on the
 MI355X.  The yardstick is torch.topk(q @ G.T, k) on bf16 copies of the same rows and queries, timed the same way; its product is
 rounded to bf16 before the top-k, so its rows are compared with the library's only as a fraction of equal best rows.
+
+--removed FRACTION measures the scan that skips removed rows against the plain one on the same gallery in the same process:
+--repeats windows of --steps plain searches (their spread is the yardstick), then that share of the rows, drawn at random, is
+removed (rfd_gallery_remove) and the same windows are timed on the masked scan, then the rows are put back
+(rfd_gallery_replace_device with their own embeddings) and the plain windows are timed again, so a drift of the machine shows
+as a difference between the two plain series.  The masked scan reads 2 more bytes per block of 16 rows.
 Prints one JSON line per size."""
 import argparse
 import json
@@ -28,7 +34,10 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--rows", type=int, nargs="*", default=[100_000, 1_000_000])
+    ap.add_argument("--removed", type=float, default=0.0, help="share of the rows to remove at random before timing the masked scan")
+    ap.add_argument("--repeats", type=int, default=5, help="timed windows per series of a --removed run")
     args = ap.parse_args()
+    assert 0.0 <= args.removed < 1.0
     import torch
     import rfd_hip
     det = rfd_hip.RetinaFaceDetection(image_size=(640, 640), max_batch_size=1, max_det=16)
@@ -37,12 +46,15 @@ def main():
     for rows in args.rows:
         gal = det.gallery(DIM, rows)
         g16 = torch.empty(rows, DIM, dtype=torch.bfloat16, device=dev)
+        g32 = torch.empty(rows, DIM, device=dev) if args.removed > 0 else None   # the embeddings, to put removed rows back
         gen.manual_seed(rows)
         for at in range(0, rows, CHUNK):
             m = min(CHUNK, rows - at)
             x = torch.randn(m, DIM, device=dev, generator=gen)
             x = x / x.norm(dim=1, keepdim=True)
             g16[at:at + m] = x.to(torch.bfloat16)
+            if g32 is not None:
+                g32[at:at + m] = x
             torch.cuda.synchronize()
             gal.add_device(x.data_ptr(), m)
             det.sync()
@@ -66,10 +78,37 @@ def main():
             torch.cuda.synchronize()
             return out
 
+        def window():
+            t0 = time.perf_counter()
+            ours(args.steps)
+            return (time.perf_counter() - t0) * 1e3 / args.steps
+
         ours(args.warmup)
-        t0 = time.perf_counter()
-        ours(args.steps)
-        ms = (time.perf_counter() - t0) * 1e3 / args.steps
+        ms = window()
+        masked = {}
+        if args.removed > 0:
+            import numpy as np
+            series = lambda: [round(window(), 4) for _ in range(args.repeats)]
+            stats = lambda w: {"windows_ms": w, "median_ms": round(float(np.median(w)), 4), "min_ms": min(w), "max_ms": max(w)}
+            plain = series()
+            gone = np.sort(np.random.default_rng(rows).choice(rows, max(1, int(rows * args.removed)), replace=False)).astype(np.int32)
+            gal.remove(gone)
+            assert gal.live() == rows - len(gone)
+            ours(args.warmup)                      # the masked instantiation's first launches
+            with_mask = series()
+            assert not bool(torch.isin(d_r.cpu(), torch.from_numpy(gone)).any())
+            back = g32[torch.from_numpy(gone).to(dev).long()].contiguous()
+            torch.cuda.synchronize()
+            gal.replace_device(gone, back.data_ptr())
+            det.sync()
+            assert gal.live() == rows
+            ours(args.warmup)
+            plain_again = series()
+            spread = max(plain + plain_again) - min(plain + plain_again)
+            masked = {"removed_rows": int(len(gone)), "repeats": args.repeats, "plain": stats(plain), "masked": stats(with_mask),
+                      "plain_again": stats(plain_again), "plain_spread_ms": round(spread, 4),
+                      "masked_minus_plain_median_ms": round(float(np.median(with_mask) - np.median(plain + plain_again)), 4),
+                      "masked_extra_bytes": (rows + 15) // 16 * 2}
         theirs(args.warmup)
         t0 = time.perf_counter()
         ref = theirs(args.steps)
@@ -82,9 +121,9 @@ def main():
                           "search_ms": round(ms, 4), "bytes_streamed": streamed, "streamed_TB_per_s": round(streamed / ms / 1e9, 3),
                           "floor_ms_at_6.2_TB_per_s": round(floor_ms, 4), "fraction_of_floor_rate": round(floor_ms / ms, 3),
                           "torch_matmul_topk_ms": round(ms_torch, 4), "best_row_equals_torch": same_best,
-                          "query_finds_its_row": found_self}), flush=True)
+                          "query_finds_its_row": found_self, **masked}), flush=True)
         gal.close()
-        del g16
+        del g16, g32
     det.close()
 
 
