@@ -6,7 +6,7 @@ import pytest
 import gallery_ref as R
 
 
-@pytest.mark.parametrize("dim", [32, 128, 512])
+@pytest.mark.parametrize("dim", [32, 96, 128, 160, 352, 512, 1024])
 def test_offset_is_a_bijection_for_every_multiple_of_16_rows(rfd, dim):
     """[0, rows) x [0, dim) -> [0, rows * dim) one to one, for every row count that is a multiple of 16: the first `rows` rows
     occupy exactly the first rows * dim elements, so a gallery of any capacity is a prefix of a larger one."""
@@ -17,7 +17,7 @@ def test_offset_is_a_bijection_for_every_multiple_of_16_rows(rfd, dim):
         assert np.array_equal(part, np.arange(16 * b * dim)), "rows %d" % (16 * b)
 
 
-@pytest.mark.parametrize("dim", [32, 128, 512])
+@pytest.mark.parametrize("dim", [32, 96, 128, 160, 352, 512, 1024])
 def test_an_mfma_operand_fetch_is_one_contiguous_kib(rfd, dim):
     """The 64 lanes' B operands of one (block, K step) -- lane l: row l & 15, elements 8 * (l >> 4) .. + 7 -- lie in lane order in
     one 1 KiB span (512 bf16), 16 bytes per lane: one coalesced global_load_dwordx4 per wave."""
