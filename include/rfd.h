@@ -44,7 +44,8 @@ typedef enum rfd_status {
     RFD_ERR_CAPACITY = -4,    /* batch / frame / detections exceed the configured capacity */
     RFD_ERR_STATE = -5,       /* weights not initialised (reference: empty model config, face_detection.rs:239) */
     RFD_ERR_IO = -6,          /* weight file could not be read / written */
-    RFD_ERR_COMM = -7         /* librccl missing, or an RCCL call failed (multi-GPU gather) */
+    RFD_ERR_COMM = -7,        /* librccl missing, or an RCCL call failed (multi-GPU gather) */
+    RFD_ERR_UNSUPPORTED = -8  /* a well-formed JPEG file of a kind the decoder does not do (progressive, 12-bit, ...): "JPEG decode" below */
 } rfd_status;
 
 typedef enum rfd_backbone {
@@ -565,6 +566,75 @@ RFD_API int rfd_gallery_file_info(const char *path, int *dim, int *rows, int *li
 /* host only, no GPU: element offset of (row, d) in the private storage layout (-1: dim or an index out of range); the add
  * kernel scatters by this function and tests pin that it is a bijection and that an MFMA operand fetch is one 1 KiB span */
 RFD_API int64_t rfd_debug_gallery_offset(int dim, int row, int d);
+
+/* ---- JPEG decode: the first line of FacePipeline::extract (pipeline.rs:188-249), byte_data_to_opencv (src/utils/utils.rs:8-52),
+ *      an imdecode of the file's bytes.  File bytes in, BGR frames in HBM out: the frames rfd_detect_batch_device and
+ *      rfd_detect_faces_device read, with no JPEG library in the caller, no decoded frame on PCIe.
+ *      Two halves.  The serial one -- marker parsing and Huffman decoding -- runs on host threads inside the call, one frame per
+ *      task, on threads that never touch HIP (rfd_set_decode_threads: 1..16, default 4; never derived from the machine's CPU
+ *      count).  It writes each block's QUANTISED coefficients, in zigzag order and only up to the last non-zero one, with one
+ *      32-bit (offset, count) word per block, straight into page-locked memory of the context (allocated by the first decode
+ *      call, sized by max_src_w, max_src_h and max_batch_size; the layout is private: DESIGN.md section 5).  The parallel half is
+ *      two kernels per BATCH, whatever the number, sizes and samplings of its frames: dequantisation + libjpeg's accurate integer
+ *      inverse DCT (jidctint.c: 13-bit constants, a column pass that keeps 2 extra bits, a row pass that descales by 18 and adds
+ *      128, clamped to 0..255) into u8 component planes padded to whole MCUs; then libjpeg's fancy (triangle) chroma upsampling
+ *      and its fixed-point YCbCr -> RGB tables, cropped to the image and stored as [H][W][3] u8 BGR at the caller's stride.
+ *      Contract: the pixels equal libjpeg-turbo's defaults (JDCT_ISLOW, fancy upsampling) -- what cv::imdecode and Pillow return
+ *      -- byte for byte (tests/test_jpeg_cpu.py pins the arithmetic against Pillow, tests/test_jpeg_gpu.py the kernels).  Edges
+ *      are part of it: horizontally the filter runs over the component's own ceil(W h / hmax) samples, vertically the first and
+ *      the last real sample row stand in for the rows beyond them, and a chroma plane of one or two samples per row is
+ *      replicated, not filtered (libjpeg's own rule).  Outside the contract: coefficients that no 8-bit image produces (IDCT
+ *      results far outside 0..255) decode without a fault to pixels that are not pinned -- libjpeg's own C and SIMD paths differ
+ *      there; the arithmetic here wraps modulo 2^32 and clamps.
+ *      Supported: baseline and extended sequential Huffman files (SOF0, SOF1) with 8-bit samples and ONE interleaved scan of one
+ *      component (grey) or of three with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1; 8- and 16-bit quantisation tables;
+ *      restart intervals; APPn and COM segments are skipped, fill bytes and 0xFF00 stuffing understood.
+ *      RFD_ERR_UNSUPPORTED: progressive (SOF2), lossless, hierarchical and arithmetic-coded files, 12-bit samples, four (or two)
+ *      components, other sampling factors, files of more than one scan.  RFD_ERR_INVALID_ARG: a truncated or malformed file -- a
+ *      length field that points past the end, a Huffman code that is not in its table, a coefficient index above 63, a table
+ *      that was never defined, zero dimensions, a restart marker out of sequence, data that ends before the last MCU.  In both
+ *      cases rfd_last_error() names the cause and the byte offset (and, in a batch, the frame), and NOTHING is enqueued for any
+ *      frame of the call: every file is parsed and entropy-decoded before the first copy or kernel.  A file may end without EOI
+ *      once its last MCU is complete (libjpeg warns and accepts).
+ *      Divergence: a grey file gives B = G = R = Y in a 3-channel frame.  The reference decodes with IMREAD_UNCHANGED, which
+ *      keeps such a file at one channel, and its detector then fails on it (at_2d::<Vec3b>, face_detection.rs:226). ---- */
+typedef enum rfd_jpeg_sampling { RFD_JPEG_GRAY = 0, RFD_JPEG_444 = 1, RFD_JPEG_422 = 2, RFD_JPEG_420 = 3 } rfd_jpeg_sampling;
+struct rfd_jpeg_info {
+    int32_t width, height;
+    int32_t components;       /* 1 or 3 */
+    int32_t sampling;         /* rfd_jpeg_sampling */
+    int32_t restart_interval; /* MCUs between restart markers, 0: none */
+    int32_t reserved[3];      /* 0 */
+};
+/* Host only, no context, no device: everything from SOI to the end of the SOS header is parsed and validated, with the statuses
+ * and messages the decode would give (the entropy-coded data itself is looked at by the decode only).  A refused file leaves
+ * *out untouched.  (The struct shares its name with the function, so C and C++ both spell the type `struct rfd_jpeg_info`.) */
+RFD_API int rfd_jpeg_info(const uint8_t *bytes, size_t len, struct rfd_jpeg_info *out);
+/* Decodes n files into n caller-allocated DEVICE frames: out[i].data is device memory of out[i].height rows of out[i].stride
+ * bytes; width and height must equal the file's (else RFD_ERR_INVALID_ARG) and stride must be >= 3 * width; bytes of a row
+ * beyond 3 * width are not touched.  rfd_image declares data const because every other entry point reads frames; this one
+ * WRITES through it (the library casts the const away).  The same array is then valid input to rfd_detect_batch_device,
+ * rfd_detect_faces_device and rfd_liveness_tensors_device on the same stream, with no synchronisation in between.
+ * bytes[] / len[] and the files are host memory and may be freed when the call returns.  Entropy decoding happens inside the
+ * call; the copies and the two kernels go on the context's stream.  async as in rfd_gallery_search_device: 0 returns after the
+ * stream has drained, any other value at once (rfd_sync before reading the frames from another stream).
+ * n > max_batch_size, or a file wider than max_src_w or higher than max_src_h: RFD_ERR_CAPACITY.  n = 0 is a no-op.
+ * Staging reuse: there is ONE page-locked staging area, guarded by an event -- a call waits, before its threads write into it,
+ * until the copies the previous call enqueued from it have run (its kernels need not have: they read the device copy, which
+ * the next call's copies follow in stream order).  So two asynchronous calls back to back are safe; the second one's entropy
+ * decoding does not overlap the first one's PCIe copy. */
+RFD_API int rfd_decode_jpeg_batch_device(rfd_ctx *ctx, const uint8_t *const *bytes, const size_t *len, int n, const rfd_image *out, int async);
+/* The same into HOST frames (out[i].data is host memory, written through the same const cast); synchronous. */
+RFD_API int rfd_decode_jpeg_batch(rfd_ctx *ctx, const uint8_t *const *bytes, const size_t *len, int n, const rfd_image *out);
+/* Worker threads of the entropy decoder: 1 <= threads <= 16 (else RFD_ERR_INVALID_ARG); a batch uses min(threads, n) of them.
+ * The pixels do not depend on it. */
+RFD_API int rfd_set_decode_threads(rfd_ctx *ctx, int threads);
+/* Test hook, host only, no context: the DEQUANTISED coefficients of every block, [blocks][64] i16 in natural (row-major) order,
+ * blocks component-major, each component's plane padded to whole MCUs and walked row by row -- the input of the inverse DCT, so
+ * the host half can be tested without a GPU (tests/jpeg_ref.py continues from here).  A product outside i16 (hostile files
+ * only) saturates.  *blocks = the file's block count, also when it exceeds cap_blocks (then RFD_ERR_CAPACITY, nothing written);
+ * out may be NULL when cap_blocks is 0. */
+RFD_API int rfd_debug_jpeg_coefficients(const uint8_t *bytes, size_t len, int16_t *out, size_t cap_blocks, size_t *blocks);
 
 /* ---- introspection ---- */
 RFD_API int rfd_get_stats(rfd_ctx *ctx, rfd_stats *stats);

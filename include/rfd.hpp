@@ -9,6 +9,7 @@
 //                                        -> (Array2<f32> [K,5], Option<Array3<f32>> [K,5,2])
 //   rfd::FaceSelection::call          <- FaceSelection::call                 src/pipeline/module/face_selection.rs:72-189
 //   rfd::FaceAlignment::call          <- FaceAlignment::call                 src/pipeline/module/face_alignment.rs:27-141
+//   rfd::decode_jpeg / _device        <- byte_data_to_opencv (imdecode)      src/utils/utils.rs:8-52
 //   rfd::Error                        <- anyhow::Error: every failing entry point throws it (status + message)
 // What changed against the reference constructor: the Triton client / model config / model name arguments are gone
 // (the network runs in-process); device_id, max_det and the backbone are new.
@@ -29,7 +30,8 @@ namespace rfd {
 
 struct Error : std::runtime_error {
     int status;
-    Error(int st, const std::string &what) : std::runtime_error("rfd status " + std::to_string(st) + ": " + what), status(st) {}
+    std::string message; // the library's text alone
+    Error(int st, const std::string &what) : std::runtime_error("rfd status " + std::to_string(st) + ": " + what), status(st), message(what) {}
 };
 inline void check(int status)
 {
@@ -361,6 +363,63 @@ class Gallery {
     rfd_gallery *g_ = nullptr;
     int dim_;
 };
+
+// JPEG decode on the device (rfd.h, "JPEG decode"): byte_data_to_opencv (utils.rs:8-52), the first line of FacePipeline::extract.
+struct JpegInfo {
+    int width = 0, height = 0, components = 0;
+    int sampling = RFD_JPEG_GRAY; // rfd_jpeg_sampling
+    int restart_interval = 0;
+};
+// host only: the whole marker validation; throws with RFD_ERR_UNSUPPORTED / RFD_ERR_INVALID_ARG and the cause
+inline JpegInfo jpeg_info(const std::vector<uint8_t> &file)
+{
+    struct rfd_jpeg_info i;
+    check(rfd_jpeg_info(file.data(), file.size(), &i));
+    JpegInfo r;
+    r.width = i.width; r.height = i.height; r.components = i.components; r.sampling = i.sampling; r.restart_interval = i.restart_interval;
+    return r;
+}
+// a decoded frame that owns its pixels: rows x cols x 3 u8 BGR (a grey file: B = G = R)
+struct DecodedImage {
+    std::vector<uint8_t> pixels;
+    int rows = 0, cols = 0;
+    Mat mat() const { return Mat(pixels.data(), rows, cols); }
+};
+inline void set_decode_threads(RetinaFaceDetection &det, int threads) { check(rfd_set_decode_threads(det.raw(), threads)); }
+// files -> host frames, decoded on the device; throws where the reference's imdecode fails
+inline std::vector<DecodedImage> decode_jpeg(RetinaFaceDetection &det, const std::vector<std::vector<uint8_t>> &files)
+{
+    const std::size_t n = files.size();
+    std::vector<DecodedImage> out(n);
+    std::vector<const uint8_t *> ptrs(n);
+    std::vector<std::size_t> lens(n);
+    std::vector<rfd_image> im(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        JpegInfo info;
+        try {
+            info = jpeg_info(files[i]);
+        } catch (const Error &e) { // name the file, as the batch call itself does
+            throw Error(e.status, "file " + std::to_string(i) + ": " + e.message);
+        }
+        out[i].rows = info.height; out[i].cols = info.width;
+        out[i].pixels.resize((std::size_t)info.height * (std::size_t)info.width * 3);
+        ptrs[i] = files[i].data(); lens[i] = files[i].size();
+        im[i] = rfd_image{out[i].pixels.data(), info.height, info.width, (std::ptrdiff_t)info.width * 3};
+    }
+    check(rfd_decode_jpeg_batch(det.raw(), ptrs.data(), lens.data(), (int)n, im.data()));
+    return out;
+}
+// files -> caller-allocated DEVICE frames (frames[i].data is device memory the library writes); the same array then feeds
+// rfd_detect_batch_device / rfd_detect_faces_device.  async: no host synchronisation (rfd_sync before reading).
+inline void decode_jpeg_device(RetinaFaceDetection &det, const std::vector<std::vector<uint8_t>> &files, const std::vector<rfd_image> &frames,
+                               bool async = false)
+{
+    if (files.size() != frames.size()) throw Error(RFD_ERR_INVALID_ARG, "decode_jpeg_device: one frame per file");
+    std::vector<const uint8_t *> ptrs(files.size());
+    std::vector<std::size_t> lens(files.size());
+    for (std::size_t i = 0; i < files.size(); ++i) { ptrs[i] = files[i].data(); lens[i] = files[i].size(); }
+    check(rfd_decode_jpeg_batch_device(det.raw(), ptrs.data(), lens.data(), (int)files.size(), frames.data(), async ? 1 : 0));
+}
 
 } // namespace rfd
 #endif

@@ -6,10 +6,14 @@
 #include <stdarg.h>
 #include <stdlib.h>
 
+#include <atomic>
+#include <memory>
 #include <mutex>
+#include <thread>
 #include <vector>
 
 #include "gallery_file.h"
+#include "jpeg_parse.h"
 #include "network.h"
 
 namespace rfd {
@@ -210,6 +214,14 @@ struct rfd_ctx {
     LiveImage *pin_live[kRing] = {};
     hipEvent_t pin_live_done[kRing] = {};
     int pin_live_next = 0;
+    // JPEG decode (rfd.h, "JPEG decode"), all allocated by its first call.  jpeg_pin is the page-locked staging the decode threads
+    // write and jpeg_dev its device twin, both laid out as: JpegFrame [B] | block records u32 [B * jpeg_blocks_max] | coefficients
+    // i16 [B * jpeg_blocks_max * 64], B = max_batch_size.  jpeg_pin_done: the copies out of jpeg_pin that the last call enqueued.
+    int decode_threads = 4;
+    size_t jpeg_blocks_max = 0; // blocks of the largest frame (max_src_w x max_src_h) in its most expensive sampling
+    void *jpeg_pin = nullptr;
+    hipEvent_t jpeg_pin_done = nullptr;
+    DevBuf jpeg_dev, jpeg_planes, jpeg_out; // jpeg_out: the device frames of the host-output form
     // pipelined host entry (rfd_submit_batch / rfd_collect_batch): two slots, H2D on its own stream
     struct PipeSlot {
         DevBuf frames, imgs, scale, ob, ol, oc, ot;
@@ -718,6 +730,9 @@ void rfd_destroy(rfd_ctx *c)
         if (c->pin_live[i]) (void)hipHostFree(c->pin_live[i]);
         if (c->pin_live_done[i]) (void)hipEventDestroy(c->pin_live_done[i]);
     }
+    c->jpeg_dev.release(); c->jpeg_planes.release(); c->jpeg_out.release();
+    if (c->jpeg_pin) (void)hipHostFree(c->jpeg_pin);
+    if (c->jpeg_pin_done) (void)hipEventDestroy(c->jpeg_pin_done);
     for (int i = 0; i < 10; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     for (int i = 0; i < rfd_ctx::kRing; ++i) {
@@ -2598,6 +2613,189 @@ int rfd_gallery_load(rfd_ctx *c, const char *path, int capacity, rfd_gallery **o
     if (st != RFD_OK) { rfd_gallery_destroy(g); return st; }
     *out = g;
     return RFD_OK;
+}
+
+// ---- JPEG decode (rfd.h, "JPEG decode"): csrc/jpeg_parse.h on host threads, then csrc/kernels_jpeg.hip ----
+int rfd_jpeg_info(const uint8_t *bytes, size_t len, struct rfd_jpeg_info *out)
+{
+    char msg[256] = "";
+    const int st = jpeg_info(bytes, len, out, msg, sizeof msg);
+    if (st != RFD_OK) set_error("%s", msg);
+    return st;
+}
+
+int rfd_debug_jpeg_coefficients(const uint8_t *bytes, size_t len, int16_t *out, size_t cap_blocks, size_t *blocks)
+{
+    RFD_CHECK_ARG(out || cap_blocks == 0, "out is null");
+    char msg[256] = "";
+    const int st = jpeg_debug_coefficients(bytes, len, out, cap_blocks, blocks, msg, sizeof msg);
+    if (st != RFD_OK) set_error("%s", msg);
+    return st;
+}
+
+int rfd_set_decode_threads(rfd_ctx *c, int threads)
+{
+    RFD_CHECK_ARG(c, "ctx is null");
+    if (threads < 1 || threads > 16) { set_error("invalid argument: %d decode threads (1..16)", threads); return RFD_ERR_INVALID_ARG; }
+    c->decode_threads = threads;
+    return RFD_OK;
+}
+
+// blocks of a w x h frame in the sampling that needs most: 4:4:4, 4:2:2 or 4:2:0, each padded to its own MCU
+static size_t jpeg_blocks_bound(int w, int h)
+{
+    const size_t a8 = (size_t)ceil_div(w, 8), b8 = (size_t)ceil_div(h, 8), a16 = (size_t)ceil_div(w, 16), b16 = (size_t)ceil_div(h, 16);
+    return std::max(3 * a8 * b8, std::max(4 * a16 * b8, 6 * a16 * b16));
+}
+
+// first decode call of a context: the page-locked staging, its device twin, the plane pool
+static int jpeg_stage_alloc(rfd_ctx *c)
+{
+    if (c->jpeg_pin) return RFD_OK;
+    RFD_CHECK_ARG(c->cfg.max_src_w >= 1 && c->cfg.max_src_h >= 1, "max_src_w / max_src_h < 1");
+    const size_t B = (size_t)c->cfg.max_batch_size, blocks = jpeg_blocks_bound(c->cfg.max_src_w, c->cfg.max_src_h);
+    if (blocks * 64 > kJpegMaxCoefs) {
+        set_error("max_src %d x %d exceeds the JPEG decoder's %u coefficient slots per frame", c->cfg.max_src_w, c->cfg.max_src_h, kJpegMaxCoefs);
+        return RFD_ERR_CAPACITY;
+    }
+    const size_t bytes = B * sizeof(JpegFrame) + B * blocks * (sizeof(uint32_t) + 64 * sizeof(int16_t));
+    if (!c->jpeg_pin_done) RFD_HIP(hipEventCreateWithFlags(&c->jpeg_pin_done, hipEventDisableTiming));
+    RFD_TRY(c->jpeg_dev.reserve(bytes));
+    RFD_TRY(c->jpeg_planes.reserve(B * blocks * 64));
+    RFD_HIP(hipHostMalloc(&c->jpeg_pin, bytes, hipHostMallocDefault));
+    c->jpeg_blocks_max = blocks;
+    return RFD_OK;
+}
+
+// Both forms.  Everything that can refuse the call -- arguments, headers, entropy data -- is settled before the first copy or
+// kernel is enqueued.
+static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_t *len, int n, const rfd_image *out, bool out_on_device, int async)
+{
+    RFD_CHECK_ARG(c, "ctx is null");
+    RFD_CHECK_ARG(n >= 0, "n < 0");
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(bytes && len && out, "null argument");
+    if (n > c->cfg.max_batch_size) {
+        set_error("batch of %d files exceeds max_batch_size %d", n, c->cfg.max_batch_size);
+        return RFD_ERR_CAPACITY;
+    }
+    std::unique_ptr<JpegHeader[]> hdr(new JpegHeader[(size_t)n]);
+    for (int i = 0; i < n; ++i) {
+        const int st = jpeg_parse_header(bytes[i], len[i], hdr[i]);
+        if (st != RFD_OK) { set_error("file %d: %s", i, hdr[i].msg); return st; }
+        const JpegHeader &h = hdr[i];
+        if (h.width > c->cfg.max_src_w || h.height > c->cfg.max_src_h) {
+            set_error("file %d: %d x %d exceeds max_src %d x %d", i, h.width, h.height, c->cfg.max_src_w, c->cfg.max_src_h);
+            return RFD_ERR_CAPACITY;
+        }
+        if (!out[i].data) { set_error("invalid argument: output frame %d has no data pointer", i); return RFD_ERR_INVALID_ARG; }
+        if (out[i].width != h.width || out[i].height != h.height) {
+            set_error("invalid argument: output frame %d is %d x %d, file %d is %d x %d", i, out[i].width, out[i].height, i, h.width, h.height);
+            return RFD_ERR_INVALID_ARG;
+        }
+        if (out[i].stride < (ptrdiff_t)h.width * 3) { set_error("invalid argument: output frame %d has stride %td < 3 * width", i, out[i].stride); return RFD_ERR_INVALID_ARG; }
+    }
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    RFD_TRY(jpeg_stage_alloc(c));
+    const size_t B = (size_t)c->cfg.max_batch_size;
+    JpegFrame *fr = (JpegFrame *)c->jpeg_pin;
+    uint32_t *rec = (uint32_t *)(fr + B);
+    int16_t *coef = (int16_t *)(rec + B * c->jpeg_blocks_max);
+    RFD_HIP(hipEventSynchronize(c->jpeg_pin_done)); // the previous call's copies out of the staging have run
+    std::vector<size_t> rec0((size_t)n);
+    std::vector<uint32_t> used((size_t)n, 0);
+    std::vector<int> status((size_t)n, RFD_OK);
+    size_t blocks = 0, out_bytes = 0;
+    for (int i = 0; i < n; ++i) { rec0[(size_t)i] = blocks; blocks += (size_t)hdr[i].nblocks; out_bytes += (size_t)hdr[i].width * 3 * hdr[i].height; }
+    {
+        // one frame per task; the workers touch nothing but their frame's bytes, header and slice of the staging
+        std::atomic<int> next{0};
+        auto work = [&]() {
+            for (int i; (i = next.fetch_add(1)) < n;)
+                status[(size_t)i] = jpeg_decode_scan(bytes[i], len[i], hdr[i], rec + rec0[(size_t)i], coef + rec0[(size_t)i] * 64, &used[(size_t)i]);
+        };
+        std::vector<std::thread> pool;
+        const int T = std::min(c->decode_threads, n);
+        try {
+            for (int t = 0; t < T; ++t) pool.emplace_back(work);
+        } catch (...) {
+        }
+        for (std::thread &t : pool) t.join();
+        if (pool.empty()) { set_error("cannot start a JPEG decode thread"); return RFD_ERR_STATE; }
+    }
+    for (int i = 0; i < n; ++i)
+        if (status[(size_t)i] != RFD_OK) { set_error("file %d: %s", i, hdr[i].msg); return status[(size_t)i]; }
+    if (!out_on_device) RFD_TRY(c->jpeg_out.reserve(out_bytes));
+    JpegParams p;
+    memset(&p, 0, sizeof p);
+    size_t out_at = 0;
+    for (int i = 0; i < n; ++i) {
+        const JpegHeader &h = hdr[i];
+        JpegFrame &f = fr[i];
+        memset(&f, 0, sizeof f);
+        if (out_on_device) {
+            f.out = const_cast<uint8_t *>(out[i].data); // the one entry point that writes a frame (rfd.h)
+            f.stride = (long long)out[i].stride;
+        } else {
+            f.out = (uint8_t *)c->jpeg_out.p + out_at;
+            f.stride = (long long)h.width * 3;
+            out_at += (size_t)h.width * 3 * h.height;
+        }
+        f.rec0 = rec0[(size_t)i]; f.coef0 = rec0[(size_t)i] * 64; f.plane0 = rec0[(size_t)i] * 64;
+        f.width = h.width; f.height = h.height;
+        f.ncomp = h.ncomp; f.hmax = h.hmax; f.vmax = h.vmax;
+        f.nblocks = h.nblocks;
+        f.group0 = p.groups; f.tile0 = p.tiles;
+        p.groups += ceil_div(h.nblocks, kJpegGroupBlocks);
+        p.tiles += (int)(((size_t)ceil_div(h.width, 4) * h.height + 255) / 256);
+        for (int k = 0; k < h.ncomp; ++k) {
+            f.bw[k] = h.comp[k].bw; f.bh[k] = h.comp[k].bh; f.blk0[k] = h.comp[k].blk0;
+            for (int z = 0; z < 64; ++z) f.quant[k][kJpegNatural[z]] = h.quant[h.comp[k].tq][z];
+        }
+    }
+    char *dev = (char *)c->jpeg_dev.p;
+    const size_t rec_off = B * sizeof(JpegFrame), coef_off = rec_off + B * c->jpeg_blocks_max * sizeof(uint32_t);
+    auto copies = [&]() -> int {
+        RFD_HIP(hipMemcpyAsync(dev, fr, rec_off + blocks * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        for (int i = 0; i < n; ++i)
+            if (used[(size_t)i])
+                RFD_HIP(hipMemcpyAsync(dev + coef_off + rec0[(size_t)i] * 64 * sizeof(int16_t), coef + rec0[(size_t)i] * 64, (size_t)used[(size_t)i] * sizeof(int16_t),
+                                       hipMemcpyHostToDevice, c->stream));
+        return RFD_OK;
+    };
+    const int copied = copies();
+    // also where a copy failed after others were enqueued: the next call must wait for those before it writes the staging
+    const hipError_t recorded = hipEventRecord(c->jpeg_pin_done, c->stream);
+    RFD_TRY(copied);
+    RFD_HIP(recorded);
+    p.frames = (const JpegFrame *)dev;
+    p.n = n;
+    p.rec = (const uint32_t *)(dev + rec_off);
+    p.coef = (const int16_t *)(dev + coef_off);
+    p.planes = (uint8_t *)c->jpeg_planes.p;
+    RFD_TRY(launch_jpeg_decode(p, c->stream));
+    if (!out_on_device) {
+        out_at = 0;
+        for (int i = 0; i < n; ++i) {
+            const size_t row = (size_t)hdr[i].width * 3;
+            RFD_HIP(hipMemcpy2DAsync(const_cast<uint8_t *>(out[i].data), (size_t)out[i].stride, (const uint8_t *)c->jpeg_out.p + out_at, row, row, (size_t)hdr[i].height,
+                                     hipMemcpyDeviceToHost, c->stream));
+            out_at += row * hdr[i].height;
+        }
+    }
+    if (async && out_on_device) return RFD_OK;
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    return check_nms_flag(c);
+}
+
+int rfd_decode_jpeg_batch_device(rfd_ctx *c, const uint8_t *const *bytes, const size_t *len, int n, const rfd_image *out, int async)
+{
+    return jpeg_decode_impl(c, bytes, len, n, out, true, async);
+}
+
+int rfd_decode_jpeg_batch(rfd_ctx *c, const uint8_t *const *bytes, const size_t *len, int n, const rfd_image *out)
+{
+    return jpeg_decode_impl(c, bytes, len, n, out, false, 0);
 }
 
 } // extern "C"

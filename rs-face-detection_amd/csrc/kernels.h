@@ -209,6 +209,36 @@ int launch_gallery_live_range(uint16_t *live, int row0, int row1, hipStream_t s)
 int launch_gallery_import(const bf16_t *src, int n, int dim, int row0, bf16_t *store, hipStream_t s);
 int launch_gallery_export(const bf16_t *store, int row0, int n, int dim, bf16_t *out, hipStream_t s);
 
+// ---------------------------------------------------------------- JPEG decode (kernels_jpeg.hip)
+// The parallel half of the baseline JPEG decoder (rfd.h, "JPEG decode"); the serial half is csrc/jpeg_parse.h on the host.
+// One frame of a batch.  The frames of a batch share three pools: block records, coefficients, component planes.
+struct JpegFrame {
+    uint8_t *out;              // device [height][stride] u8 BGR
+    long long stride;          // bytes per output row, >= 3 * width
+    unsigned long long rec0;   // the frame's first block record in the record pool
+    unsigned long long coef0;  // the frame's first value in the coefficient pool; a record's offset counts from here
+    unsigned long long plane0; // the frame's first byte in the plane pool: 64 per block, components in order, each plane row-major
+    int width, height;
+    int ncomp, hmax, vmax;     // 1 or 3 components; luma sampling 1x1, 2x1 or 2x2 (chroma is 1x1)
+    int nblocks;
+    int group0;                // the frame's first workgroup (32 blocks each) in the inverse-DCT launch
+    int tile0;                 // the frame's first workgroup (256 x 4 pixels each) in the colour launch
+    int bw[3], bh[3], blk0[3]; // per component: blocks per row / per column (whole MCUs), first block
+    uint16_t quant[3][64];     // per component, in NATURAL order
+};
+struct JpegParams {
+    const JpegFrame *frames; // device [n]
+    int n;
+    int groups, tiles;       // workgroups of the two launches: the sum over the frames
+    const uint32_t *rec;     // offset << 7 | count per block (jpeg_parse.h)
+    const int16_t *coef;     // quantised coefficients, zigzag order, `count` per block
+    uint8_t *planes;
+};
+constexpr int kJpegGroupBlocks = 32;  // 8 lanes per block
+constexpr int kJpegTilePixels = 1024; // one thread per 4 pixels of a row
+// kernel 1: zigzag run -> dequantise -> libjpeg's accurate integer IDCT -> u8 planes; kernel 2: fancy upsampling + YCbCr -> BGR
+int launch_jpeg_decode(const JpegParams &p, hipStream_t s);
+
 // ---------------------------------------------------------------- convolution engine (kernels_conv.hip)
 // Activations: NHWC bf16.  Weights: [Cout][KH][KW][Cin] bf16 (K contiguous).  f32 accumulate on MFMA.
 struct ConvParams {

@@ -1,0 +1,196 @@
+// kernels_jpeg.hip -- the parallel half of the baseline JPEG decoder (rfd.h, "JPEG decode"), gfx950.
+//
+// Two launches per batch, whatever the number, sizes and samplings of its frames: every workgroup finds its frame in the
+// descriptor table (JpegFrame, kernels.h) by its own index, as the liveness crops do.
+//   jpeg_idct_kernel   8 lanes per 8x8 block, 32 blocks per workgroup.  Lane j gathers column j of the block from the block's
+//                      truncated zigzag run (positions past the run are zero), dequantises, runs the column pass of
+//                      jidctint.c, hands the result over through LDS, runs the row pass on row j and stores its 8 samples as
+//                      one 8-byte word.  A wave's eight blocks are neighbours in a plane, so it writes 8 rows of 64 bytes.
+//   jpeg_color_kernel  one thread per 4 pixels of an output row: h2v1 / h2v2 fancy upsampling (jdsample.c) of the two chroma
+//                      planes, jdcolor.c's fixed-point YCbCr -> RGB, three 4-byte stores of B,G,R bytes (single bytes where the
+//                      row is not 4-byte aligned or the image ends inside the quad).
+// All arithmetic is 32-bit integer.  The IDCT computes in unsigned words, so that coefficients no 8-bit image produces wrap
+// instead of overflowing a signed type; nothing indexes memory with a data-dependent value except the zigzag run, whose
+// length is masked to 64 and whose extent the host sized.
+#include "kernels.h"
+
+namespace rfd {
+
+namespace {
+
+// zigzag position of natural (row-major) index n
+__device__ const unsigned char kZigzagOf[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30,
+                                                41, 43, 9,  11, 18, 24, 31, 40, 44, 53, 10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38,
+                                                46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
+
+typedef unsigned int U;
+
+__device__ inline int descale(U v, int n) { return (int)(v + (1u << (n - 1))) >> n; }
+
+// jidctint.c jpeg_idct_islow, one dimension: x = frequencies 0..7 -> o = the eight sums scaled by 2^13, before the descale
+__device__ __forceinline__ void idct_1d(const U (&x)[8], U (&o)[8])
+{
+    U z2 = x[2], z3 = x[6];
+    U z1 = (z2 + z3) * 4433u;                 // FIX(0.541196100)
+    U tmp2 = z1 - z3 * 15137u;                // FIX(1.847759065)
+    U tmp3 = z1 + z2 * 6270u;                 // FIX(0.765366865)
+    U tmp0 = (x[0] + x[4]) << 13, tmp1 = (x[0] - x[4]) << 13;
+    const U tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    tmp0 = x[7]; tmp1 = x[5]; tmp2 = x[3]; tmp3 = x[1];
+    z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2;
+    U z4 = tmp1 + tmp3;
+    const U z5 = (z3 + z4) * 9633u;           // FIX(1.175875602)
+    tmp0 *= 2446u;                            // FIX(0.298631336)
+    tmp1 *= 16819u;                           // FIX(2.053119869)
+    tmp2 *= 25172u;                           // FIX(3.072711026)
+    tmp3 *= 12299u;                           // FIX(1.501321110)
+    z1 = 0u - z1 * 7373u;                     // FIX(0.899976223)
+    z2 = 0u - z2 * 20995u;                    // FIX(2.562915447)
+    z3 = z5 - z3 * 16069u;                    // FIX(1.961570560)
+    z4 = z5 - z4 * 3196u;                     // FIX(0.390180644)
+    tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
+    o[0] = tmp10 + tmp3; o[7] = tmp10 - tmp3;
+    o[1] = tmp11 + tmp2; o[6] = tmp11 - tmp2;
+    o[2] = tmp12 + tmp1; o[5] = tmp12 - tmp1;
+    o[3] = tmp13 + tmp0; o[4] = tmp13 - tmp0;
+}
+
+// the frame whose first workgroup is the last one <= g (first[] ascends strictly: every frame has at least one workgroup)
+template <int JpegFrame::*First> __device__ inline const JpegFrame &frame_of(const JpegParams &p, int g)
+{
+    int lo = 0, hi = p.n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (p.frames[mid].*First <= g) lo = mid; else hi = mid - 1;
+    }
+    return p.frames[lo];
+}
+
+constexpr int kWsBlock = 72, kWsRow = 9; // LDS pitch of a block and of a row in it, in words: both passes touch 32 distinct banks
+
+__global__ __launch_bounds__(256) void jpeg_idct_kernel(JpegParams p)
+{
+    __shared__ U ws[kJpegGroupBlocks * kWsBlock];
+    const int g = blockIdx.x;
+    const JpegFrame &f = frame_of<&JpegFrame::group0>(p, g);
+    const int lb = threadIdx.x >> 3, j = threadIdx.x & 7;
+    const int blk = (g - f.group0) * kJpegGroupBlocks + lb;
+    const bool valid = blk < f.nblocks;
+    const int c = (f.ncomp == 3 && blk >= f.blk0[1]) ? (blk >= f.blk0[2] ? 2 : 1) : 0;
+    U x[8], o[8];
+    {
+        uint32_t rec = valid ? p.rec[f.rec0 + (unsigned)blk] : 0u;
+        const int count = min((int)(rec & 127u), 64);
+        const int16_t *run = p.coef + f.coef0 + (rec >> 7);
+        const uint16_t *q = f.quant[c];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int nat = r * 8 + j, z = kZigzagOf[nat];
+            x[r] = z < count ? (U)((int)run[z] * (int)q[nat]) : 0u;
+        }
+    }
+    idct_1d(x, o); // column j
+    U *w = ws + lb * kWsBlock;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) w[r * kWsRow + j] = (U)descale(o[r], 13 - 2);
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 8; ++k) x[k] = w[j * kWsRow + k];
+    idct_1d(x, o); // row j
+    if (!valid) return;
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        lo |= (uint32_t)min(max(descale(o[k], 13 + 2 + 3) + 128, 0), 255) << (8 * k);
+        hi |= (uint32_t)min(max(descale(o[k + 4], 13 + 2 + 3) + 128, 0), 255) << (8 * k);
+    }
+    const int b = blk - f.blk0[c], by = b / f.bw[c], bx = b - by * f.bw[c];
+    uint8_t *plane = p.planes + f.plane0 + (size_t)f.blk0[c] * 64;
+    *reinterpret_cast<uint2 *>(plane + ((size_t)by * 8 + j) * ((size_t)f.bw[c] * 8) + (size_t)bx * 8) = make_uint2(lo, hi);
+}
+
+__device__ inline int clamp255(int v) { return min(max(v, 0), 255); }
+
+struct Quad { int a, b, c, d; };
+
+// the four upsampled samples of one chroma plane under pixels x0 .. x0 + 3 of row y (pw: the plane's row pitch)
+__device__ __forceinline__ Quad chroma_quad(const uint8_t *pl, int pw, int hmax, int vmax, int dw, int dh, int x0, int y)
+{
+    if (hmax == 1) { // 4:4:4
+        const uint8_t *r = pl + (size_t)y * pw + x0;
+        return Quad{r[0], r[1], r[2], r[3]};
+    }
+    const int i0 = x0 >> 1, rn = vmax == 2 ? y >> 1 : y;
+    const uint8_t *near = pl + (size_t)rn * pw;
+    if (dw <= 2) { // libjpeg filters only planes of more than two samples per row; these are replicated
+        const int a = near[min(i0, dw - 1)], b = near[min(i0 + 1, dw - 1)];
+        return Quad{a, a, b, b};
+    }
+    // samples i0 - 1 .. i0 + 2, clamped into the row: a clamped one is only read where the edge rule ignores it
+    const int k0 = max(i0 - 1, 0), k1 = i0, k2 = min(i0 + 1, dw - 1), k3 = min(i0 + 2, dw - 1);
+    if (vmax == 1) { // h2v1_fancy_upsample
+        const int s0 = near[k0], s1 = near[k1], s2 = near[k2], s3 = near[k3];
+        return Quad{i0 == 0 ? s1 : (3 * s1 + s0 + 1) >> 2, i0 == dw - 1 ? s1 : (3 * s1 + s2 + 2) >> 2, (3 * s2 + s1 + 1) >> 2,
+                    i0 + 1 >= dw - 1 ? s2 : (3 * s2 + s3 + 2) >> 2};
+    }
+    // h2v2_fancy_upsample: column sums of the nearer row (3/4) and the farther one (1/4), which at the edges is the row itself
+    const uint8_t *far = pl + (size_t)((y & 1) ? min(rn + 1, dh - 1) : max(rn - 1, 0)) * pw;
+    const int s0 = 3 * near[k0] + far[k0], s1 = 3 * near[k1] + far[k1], s2 = 3 * near[k2] + far[k2], s3 = 3 * near[k3] + far[k3];
+    return Quad{i0 == 0 ? (4 * s1 + 8) >> 4 : (3 * s1 + s0 + 8) >> 4, i0 == dw - 1 ? (4 * s1 + 7) >> 4 : (3 * s1 + s2 + 7) >> 4, (3 * s2 + s1 + 8) >> 4,
+                i0 + 1 >= dw - 1 ? (4 * s2 + 7) >> 4 : (3 * s2 + s3 + 7) >> 4};
+}
+
+__device__ __forceinline__ uint32_t bgr_of(int Y, int cb, int cr) // jdcolor.c build_ycc_rgb_table, written out -> B | G << 8 | R << 16
+{
+    const int u = cb - 128, v = cr - 128;
+    return (uint32_t)clamp255(Y + ((116130 * u + 32768) >> 16)) | (uint32_t)clamp255(Y + ((-22554 * u - 46802 * v + 32768) >> 16)) << 8 |
+           (uint32_t)clamp255(Y + ((91881 * v + 32768) >> 16)) << 16;
+}
+
+__global__ __launch_bounds__(256) void jpeg_color_kernel(JpegParams p)
+{
+    const int t = blockIdx.x;
+    const JpegFrame &f = frame_of<&JpegFrame::tile0>(p, t);
+    const int W = f.width, H = f.height, qw = (W + 3) >> 2;
+    const int q = (t - f.tile0) * 256 + (int)threadIdx.x;
+    const int y = q / qw, x0 = (q - y * qw) * 4;
+    if (y >= H) return;
+    const uint8_t *base = p.planes + f.plane0;
+    const uint8_t *yr = base + (size_t)y * (f.bw[0] * 8) + x0; // x0 + 3 stays inside the row: the plane is padded to whole blocks
+    const int Y0 = yr[0], Y1 = yr[1], Y2 = yr[2], Y3 = yr[3];
+    uint32_t p0, p1, p2, p3; // B | G << 8 | R << 16 per pixel
+    if (f.ncomp == 1) {
+        p0 = (uint32_t)Y0 * 0x010101u; p1 = (uint32_t)Y1 * 0x010101u; p2 = (uint32_t)Y2 * 0x010101u; p3 = (uint32_t)Y3 * 0x010101u;
+    } else {
+        const int hmax = f.hmax, vmax = f.vmax, dw = (W + hmax - 1) / hmax, dh = (H + vmax - 1) / vmax, pwc = f.bw[1] * 8;
+        const Quad cb = chroma_quad(base + (size_t)f.blk0[1] * 64, pwc, hmax, vmax, dw, dh, x0, y);
+        const Quad cr = chroma_quad(base + (size_t)f.blk0[2] * 64, pwc, hmax, vmax, dw, dh, x0, y);
+        p0 = bgr_of(Y0, cb.a, cr.a); p1 = bgr_of(Y1, cb.b, cr.b); p2 = bgr_of(Y2, cb.c, cr.c); p3 = bgr_of(Y3, cb.d, cr.d);
+    }
+    uint8_t *dst = f.out + (long long)y * f.stride + (long long)x0 * 3;
+    if (x0 + 3 < W && (reinterpret_cast<uintptr_t>(dst) & 3) == 0) {
+        uint32_t *d4 = reinterpret_cast<uint32_t *>(dst); // B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3
+        d4[0] = p0 | p1 << 24;
+        d4[1] = p1 >> 8 | p2 << 16;
+        d4[2] = p2 >> 16 | p3 << 8;
+    } else {
+        const uint32_t px[4] = {p0, p1, p2, p3};
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (x0 + i < W) { dst[3 * i] = (uint8_t)px[i]; dst[3 * i + 1] = (uint8_t)(px[i] >> 8); dst[3 * i + 2] = (uint8_t)(px[i] >> 16); }
+    }
+}
+
+} // namespace
+
+int launch_jpeg_decode(const JpegParams &p, hipStream_t s)
+{
+    if (p.n < 1) return RFD_OK;
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)p.groups), dim3(256), 0, s, p);
+    RFD_HIP(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)p.tiles), dim3(256), 0, s, p);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+} // namespace rfd

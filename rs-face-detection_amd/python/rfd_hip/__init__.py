@@ -23,6 +23,8 @@ RFD_ERR_CAPACITY = -4
 RFD_ERR_STATE = -5
 RFD_ERR_IO = -6
 RFD_ERR_COMM = -7
+RFD_ERR_UNSUPPORTED = -8
+JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = 0, 1, 2, 3   # rfd_jpeg_sampling
 COMM_ID_BYTES = 128
 MAX_FACE_TENSORS = 4   # RFD_MAX_FACE_TENSORS
 GALLERY_MAX_K = 32     # RFD_GALLERY_MAX_K
@@ -42,6 +44,7 @@ class RfdError(RuntimeError):
     def __init__(self, status, message):
         super().__init__("rfd status %d: %s" % (status, message))
         self.status = status
+        self.message = message   # the library's text alone
 
 
 class rfd_config(C.Structure):
@@ -108,6 +111,11 @@ class rfd_liveness_config(C.Structure):
                 ("out_h", C.c_int32 * MAX_FACE_TENSORS), ("reserved", C.c_int32 * 4)]
 
 
+class rfd_jpeg_info(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("sampling", C.c_int32),
+                ("restart_interval", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class rfd_tensor_desc(C.Structure):
     _fields_ = [("channels", C.c_int), ("height", C.c_int), ("width", C.c_int),
                 ("is_f32", C.c_int), ("buffer", C.c_int), ("is_input", C.c_int),
@@ -138,6 +146,7 @@ API_SYMBOLS = [
     "rfd_gallery_get_rows", "rfd_gallery_search", "rfd_gallery_search_device", "rfd_debug_gallery_offset",
     "rfd_gallery_remove", "rfd_gallery_replace", "rfd_gallery_replace_device", "rfd_gallery_live", "rfd_gallery_removed",
     "rfd_gallery_save", "rfd_gallery_load", "rfd_gallery_file_info",
+    "rfd_jpeg_info", "rfd_decode_jpeg_batch_device", "rfd_decode_jpeg_batch", "rfd_set_decode_threads", "rfd_debug_jpeg_coefficients",
 ]
 
 _lib = None
@@ -262,6 +271,11 @@ def load_library(path=None):
     L.rfd_gallery_save.argtypes = [vp, C.c_char_p]
     L.rfd_gallery_load.argtypes = [vp, C.c_char_p, ci, C.POINTER(vp)]
     L.rfd_gallery_file_info.argtypes = [C.c_char_p, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+    L.rfd_jpeg_info.argtypes = [vp, C.c_size_t, C.POINTER(rfd_jpeg_info)]
+    L.rfd_decode_jpeg_batch_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), ci, C.POINTER(rfd_image), ci]
+    L.rfd_decode_jpeg_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), ci, C.POINTER(rfd_image)]
+    L.rfd_set_decode_threads.argtypes = [vp, ci]
+    L.rfd_debug_jpeg_coefficients.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     if path is None:
         _lib = L
     return L
@@ -371,6 +385,36 @@ def gallery_file_info(path):
     dim, rows, live = C.c_int(), C.c_int(), C.c_int()
     _check(load_library().rfd_gallery_file_info(os.fsencode(path), C.byref(dim), C.byref(rows), C.byref(live)))
     return dim.value, rows.value, live.value
+
+
+def _byte_buffer(data):
+    """bytes-like -> (object that keeps the memory alive, address, length)"""
+    b = np.frombuffer(bytes(data) if not isinstance(data, (bytes, bytearray, np.ndarray)) else data, np.uint8)
+    return b, (b.ctypes.data if b.size else None), int(b.size)
+
+
+def jpeg_info(data):
+    """the header of a JPEG file (bytes) after the library's whole marker validation (rfd_jpeg_info; host only, no GPU) ->
+    dict(width, height, components, sampling = JPEG_GRAY / _444 / _422 / _420, restart_interval).  A file the decoder would
+    refuse raises RfdError with RFD_ERR_UNSUPPORTED or RFD_ERR_INVALID_ARG and the cause."""
+    keep, addr, n = _byte_buffer(data)
+    info = rfd_jpeg_info()
+    _check(load_library().rfd_jpeg_info(addr, n, C.byref(info)))
+    return dict(width=info.width, height=info.height, components=info.components, sampling=info.sampling,
+                restart_interval=info.restart_interval)
+
+
+def jpeg_coefficients(data):
+    """the dequantised coefficients of every block of a JPEG file, [blocks, 64] i16 in natural order, blocks component-major
+    over planes padded to whole MCUs (rfd_debug_jpeg_coefficients; host only, no GPU): the input of the inverse DCT"""
+    keep, addr, n = _byte_buffer(data)
+    L, blocks = load_library(), C.c_size_t(0)
+    st = L.rfd_debug_jpeg_coefficients(addr, n, None, 0, C.byref(blocks))
+    if st != RFD_ERR_CAPACITY:
+        _check(st)
+    out = np.zeros((blocks.value, 64), np.int16)
+    _check(L.rfd_debug_jpeg_coefficients(addr, n, out.ctypes.data, blocks.value, C.byref(blocks)))
+    return out
 
 
 def op_kernels_static(backbone, image_w, image_h, n, op, co_running=True, tile=0, schedule=SCHEDULE_THROUGHPUT, cus=256):
@@ -553,7 +597,7 @@ class RetinaFaceDetection:
     """
 
     def __init__(self, image_size=(640, 640), max_batch_size=1, confidence_threshold=0.7,
-                 iou_threshold=0.45, device_id=0, max_det=1024, backbone=BACKBONE_R50, precision=0, schedule=0):
+                 iou_threshold=0.45, device_id=0, max_det=1024, backbone=BACKBONE_R50, precision=0, schedule=0, max_src=None):
         self._L = load_library()
         cfg = rfd_config()
         self._L.rfd_config_default(C.byref(cfg))
@@ -566,6 +610,8 @@ class RetinaFaceDetection:
         cfg.device_id = int(device_id)
         cfg.max_det = int(max_det)
         cfg.backbone = int(backbone)
+        if max_src is not None:          # (w, h) of the largest source frame: sizes the JPEG decoder's staging (default 3840 x 2160)
+            cfg.max_src_w, cfg.max_src_h = int(max_src[0]), int(max_src[1])
         self.cfg = cfg
         self._ctx = C.c_void_p()
         _check(self._L.rfd_create(C.byref(cfg), C.byref(self._ctx)))
@@ -709,6 +755,47 @@ class RetinaFaceDetection:
 
     def sync(self):
         _check(self._L.rfd_sync(self._ctx))
+
+    # ---- JPEG decode on the device (rfd.h, "JPEG decode"): byte_data_to_opencv, utils.rs:8-52 ----
+    def set_decode_threads(self, threads):
+        """host threads of the entropy decoder, 1..16 (default 4); the pixels do not depend on it"""
+        _check(self._L.rfd_set_decode_threads(self._ctx, int(threads)))
+
+    @staticmethod
+    def _jpeg_files(files):
+        bufs = [_byte_buffer(f) for f in files]
+        n = len(bufs)
+        ptrs = (C.c_void_p * max(n, 1))(*[b[1] for b in bufs])
+        lens = (C.c_size_t * max(n, 1))(*[b[2] for b in bufs])
+        return bufs, ptrs, lens
+
+    def decode_jpeg(self, files):
+        """list of JPEG files (bytes) -> list of [H, W, 3] u8 BGR host arrays, decoded on the device (a grey file: B = G = R)"""
+        bufs, ptrs, lens = self._jpeg_files(files)
+        outs = []
+        for k, f in enumerate(files):
+            try:
+                i = jpeg_info(f)
+            except RfdError as e:   # name the file, as the batch call itself does
+                raise RfdError(e.status, "file %d: %s" % (k, e.message)) from None
+            outs.append(np.zeros((i["height"], i["width"], 3), np.uint8))
+        arr, keep = self._images(outs) if outs else ((rfd_image * 1)(), [])
+        _check(self._L.rfd_decode_jpeg_batch(self._ctx, ptrs, lens, len(files), arr))
+        return outs
+
+    def decode_jpeg_device(self, files, frame_ptrs, shapes, strides=None, async_=False):
+        """the same into caller-allocated DEVICE frames: frame_ptrs[i] a raw device address of shapes[i] = (h, w) rows of
+        strides[i] bytes (default 3 * w).  Returns the rfd_image array, which is valid input to the device-resident
+        detect calls; enqueued on the detector's stream, with no host synchronisation when async_ is set."""
+        bufs, ptrs, lens = self._jpeg_files(files)
+        n = len(files)
+        arr = (rfd_image * max(n, 1))()
+        for i in range(n):
+            h, w = shapes[i]
+            arr[i].data, arr[i].height, arr[i].width = frame_ptrs[i], int(h), int(w)
+            arr[i].stride = int(strides[i]) if strides is not None else int(w) * 3
+        _check(self._L.rfd_decode_jpeg_batch_device(self._ctx, ptrs, lens, n, arr, int(async_)))
+        return arr
 
     # ---- multi-GPU: RCCL all-gather of the detection slabs behind the C ABI (SURVEY.md section 8(e)) ----
     @staticmethod

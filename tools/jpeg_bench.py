@@ -1,0 +1,194 @@
+#!/usr/bin/env python3
+"""JPEG decode (rfd.h, "JPEG decode") on 32 files of 1920x1080, 4:2:0, quality 90.  Each figure from its own source:
+  (a) host: wall time of an ASYNCHRONOUS rfd_decode_jpeg_batch_device call, which returns when the entropy decoding is done and
+      the copies and kernels are enqueued, per batch and per frame at 1, 4 and 16 decode threads; and the wall time of the
+      synchronous call (host clock around work that ends in a stream synchronise) as the end-to-end figure;
+  (b) device: the two kernels' time from a CHILD run of this script under `rocprofv3 --kernel-trace --memory-copy-trace --stats`
+      (a run of its own: tracing slows the host, so nothing else is timed there), jpeg_idct_kernel and jpeg_color_kernel read
+      from the kernel statistics, against the HBM floor (<= 19 MB per frame over the streaming rate); the host-to-device copies
+      of the same run as their own line against the PCIe link (63 GB/s), never against the HBM floor;
+  (c) bytes that cross PCIe per frame (records + coefficients up to each block's last non-zero one), counted from the
+      coefficients, against the 6.2 MB of a decoded frame;
+  (d) Pillow's full decode time on the same host, where Pillow is installed, as the yardstick.
+Files: generated with Pillow where it is installed, or every *.jpg of a directory given as the argument.
+
+    python tools/jpeg_bench.py [directory] [--files 32] [--reps 5] [--no-trace]
+Record the output in profiles/jpeg_decode.txt."""
+import argparse
+import glob
+import io
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "rs-face-detection_amd", "python"))
+STREAM_TBS = 6.3   # float4 copy rate of the chip, TB/s
+
+
+def make_files(n):
+    from PIL import Image
+    out = []
+    for i in range(n):
+        rng = np.random.default_rng(i)
+        y, x = np.mgrid[0:1080, 0:1920]
+        img = np.stack([(x * 255 // 1919), (y * 255 // 1079), ((x + y) * 255 // 2998)], -1).astype(np.float64)
+        for _ in range(40):   # blobs and a noisy band: a photograph-like mix of smooth and busy blocks
+            cx, cy, r = rng.integers(0, 1920), rng.integers(0, 1080), rng.integers(20, 200)
+            img[(x - cx) ** 2 + (y - cy) ** 2 < r * r] = rng.integers(0, 256, 3)
+        img[:, 1400:] += rng.normal(0, 12, (1080, 520, 3))
+        buf = io.BytesIO()
+        Image.fromarray(np.clip(img, 0, 255).astype(np.uint8)).save(buf, "JPEG", quality=90, subsampling=2)
+        out.append(buf.getvalue())
+    return out
+
+
+def load_files(a):
+    if a.directory:
+        return [open(f, "rb").read() for f in sorted(glob.glob(os.path.join(a.directory, "*.jpg")))[:a.files]]
+    return make_files(a.files)
+
+
+def open_detector(R, files):
+    import torch
+    infos = [R.jpeg_info(f) for f in files]
+    det = R.RetinaFaceDetection(max_batch_size=len(files), max_src=(max(i["width"] for i in infos), max(i["height"] for i in infos)))
+    dev = torch.device("cuda", 0)
+    bufs = [torch.zeros((i["height"], i["width"] * 3), dtype=torch.uint8, device=dev) for i in infos]
+    torch.cuda.synchronize()
+    return det, infos, bufs, [b.data_ptr() for b in bufs], [(i["height"], i["width"]) for i in infos]
+
+
+def traced_child(a):
+    """what runs under the profiler: one warm-up call, then --reps synchronous calls; prints how many calls it made"""
+    import torch  # noqa: F401  (first: librfd_hip.so then binds to the HIP runtime torch ships)
+    import rfd_hip as R
+    files = load_files(a)
+    det, infos, bufs, ptrs, shapes = open_detector(R, files)
+    for _ in range(1 + a.reps):
+        det.decode_jpeg_device(files, ptrs, shapes)
+    print("traced calls %d frames %d" % (1 + a.reps, len(files)))
+    det.close()
+
+
+def read_stats(directory, suffix):
+    """rows of the first *<suffix> under directory as dicts, or None"""
+    import csv
+    for d, _, fs in os.walk(directory):
+        for f in sorted(fs):
+            if f.endswith(suffix):
+                with open(os.path.join(d, f), newline="") as fh:
+                    return list(csv.DictReader(fh))
+    return None
+
+
+def kernel_pass(files, a, h2d_bytes_per_call):
+    """(b): a child of this script under rocprofv3, a process of its own started with subprocess; prints the figures"""
+    import shutil
+    import subprocess
+    import tempfile
+    exe = shutil.which("rocprofv3")
+    if exe is None:
+        print("(b) rocprofv3 is not installed here: kernel time not measured")
+        return
+    tmp = tempfile.mkdtemp(prefix="rfd_jpeg_")
+    try:
+        for i, f in enumerate(files):
+            with open(os.path.join(tmp, "%03d.jpg" % i), "wb") as fh:
+                fh.write(f)
+        out = os.path.join(tmp, "trace")
+        r = subprocess.run([exe, "--kernel-trace", "--memory-copy-trace", "--stats", "--output-format", "csv", "-d", out, "--", sys.executable,
+                            os.path.abspath(__file__), tmp, "--files", str(len(files)), "--reps", str(a.reps), "--child"],
+                           capture_output=True, text=True, timeout=600)
+        if r.returncode != 0 or "traced calls" not in r.stdout:
+            print("(b) the traced child failed (exit %d): kernel time not measured\n%s" % (r.returncode, (r.stdout + r.stderr)[-600:]))
+            return
+        calls, n = 1 + a.reps, len(files)
+        rows = read_stats(out, "kernel_stats.csv")
+        if not rows:
+            print("(b) no kernel statistics were written: kernel time not measured")
+            return
+        floor_us = 19e6 / (STREAM_TBS * 1e12) * 1e6
+        total = 0.0
+        for name in ("jpeg_idct_kernel", "jpeg_color_kernel"):
+            hit = [x for x in rows if name in x["Name"]]
+            if not hit:
+                print("(b) %s is not in the kernel statistics" % name)
+                continue
+            us = float(hit[0]["AverageNs"]) / 1e3
+            total += us
+            print("(b) %s: %d launches, %.1f us per launch = %.2f us per frame (min %.1f, max %.1f us per launch)" %
+                  (name, int(hit[0]["Calls"]), us, us / n, float(hit[0]["MinNs"]) / 1e3, float(hit[0]["MaxNs"]) / 1e3))
+        print("(b) both kernels: %.2f us per frame against the HBM floor of %.1f us per frame (19 MB at %.1f TB/s): %.0f %% of the floor's rate" %
+              (total / n, floor_us, STREAM_TBS, 100 * floor_us / (total / n) if total else 0))
+        copies = read_stats(out, "memory_copy_stats.csv")
+        h2d = [x for x in copies or [] if "HOST_TO_DEVICE" in x["Name"].upper() or "H2D" in x["Name"].upper()]
+        if h2d:
+            ns = sum(float(x["TotalDurationNs"]) for x in h2d) / calls
+            print("(b) host-to-device copies: %.1f us per call for %.2f MB = %.1f GB/s against the 63 GB/s of the PCIe link" %
+                  (ns / 1e3, h2d_bytes_per_call / 1e6, h2d_bytes_per_call / ns))
+        else:
+            print("(b) no host-to-device copy statistics were written: copy time not measured")
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("directory", nargs="?")
+    ap.add_argument("--files", type=int, default=32)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--no-trace", action="store_true", help="skip (b), the child run under rocprofv3")
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child:
+        return traced_child(a)
+    import torch  # noqa: F401  (first: librfd_hip.so then binds to the HIP runtime torch ships)
+    import rfd_hip as R
+    files = load_files(a)
+    n = len(files)
+    infos = [R.jpeg_info(f) for f in files]
+    print("%d files, %.0f KB each on average, first %dx%d sampling %d" % (n, sum(map(len, files)) / n / 1e3, infos[0]["width"], infos[0]["height"], infos[0]["sampling"]))
+    # (c) transport bytes: 4 per block + 2 per coefficient up to the last non-zero one of its block (in zigzag order)
+    zz = np.argsort(np.array([0, 1, 5, 6, 14, 15, 27, 28, 2, 4, 7, 13, 16, 26, 29, 42, 3, 8, 12, 17, 25, 30, 41, 43, 9, 11, 18, 24, 31, 40, 44, 53, 10, 19, 23, 32,
+                              39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63]))
+    h2d = []
+    for f in files:
+        nz = R.jpeg_coefficients(f)[:, zz] != 0
+        h2d.append(nz.shape[0] * 4 + 2 * int(np.where(nz.any(1), 64 - np.argmax(nz[:, ::-1], 1), 0).sum()))
+    decoded = [i["width"] * i["height"] * 3 for i in infos]
+    print("(c) H2D bytes per frame: %.2f MB (records + truncated runs) against %.2f MB decoded = %.1f %%" %
+          (np.mean(h2d) / 1e6, np.mean(decoded) / 1e6, 100 * np.sum(h2d) / np.sum(decoded)))
+    det, infos, bufs, ptrs, shapes = open_detector(R, files)
+    det.decode_jpeg_device(files, ptrs, shapes)   # allocates the staging, loads the code objects
+    for threads in (1, 4, 16):
+        det.set_decode_threads(threads)
+        enq, whole = [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            det.decode_jpeg_device(files, ptrs, shapes, async_=True)
+            enq.append(time.perf_counter() - t0)
+            det.sync()
+            t0 = time.perf_counter()
+            det.decode_jpeg_device(files, ptrs, shapes)
+            whole.append(time.perf_counter() - t0)
+        e, w = float(np.median(enq)) * 1e3, float(np.median(whole)) * 1e3
+        print("(a) %2d threads: entropy decode + enqueue %.2f ms per batch of %d = %.3f ms per frame (min %.2f, max %.2f ms); synchronous call %.2f ms = %.0f frames/s" %
+              (threads, e, n, e / n, min(enq) * 1e3, max(enq) * 1e3, w, n / w * 1e3))
+    det.close()
+    try:
+        from PIL import Image
+        t0 = time.perf_counter()
+        for f in files:
+            Image.open(io.BytesIO(f)).load()
+        print("(d) Pillow full decode, one thread: %.2f ms per frame" % ((time.perf_counter() - t0) / n * 1e3))
+    except ImportError:
+        print("(d) Pillow is not installed here")
+    if not a.no_trace:
+        kernel_pass(files, a, float(np.sum(h2d)) + n * 496)
+
+
+if __name__ == "__main__":
+    main()
