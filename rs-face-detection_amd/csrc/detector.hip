@@ -7,12 +7,14 @@
 #include <stdlib.h>
 
 #include <atomic>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
 
 #include "gallery_file.h"
+#include "host_resources.h"
 #include "jpeg_parse.h"
 #include "network.h"
 
@@ -152,21 +154,6 @@ static int rccl_load()
         }                                                                                                   \
     } while (0)
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t bytes)
-    {
-        if (bytes <= cap) return RFD_OK;
-        if (p) RFD_HIP(hipFree(p));
-        p = nullptr; cap = 0;
-        RFD_HIP(hipMalloc(&p, bytes));
-        cap = bytes;
-        return RFD_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
 } // namespace rfd
 
 using namespace rfd;
@@ -175,22 +162,30 @@ using namespace rfd;
 // Triton client/model config, plus device state.
 struct rfd_ctx {
     rfd_config cfg;
+    // The streams come first, so that they are destroyed last: after every event recorded on them and every buffer their
+    // commands use.  `stream` is the caller's (rfd_set_stream) or own_stream.
+    Stream own_stream, copy_stream, d2h_stream;
     hipStream_t stream = nullptr;
-    hipStream_t own_stream = nullptr;
-    hipEvent_t ev[10] = {};
+    Event ev[10];
     float base_anchor[kNumLevels][kA][4];
     int fh[kNumLevels], fw[kNumLevels], level_off[kNumLevels], total_anchors = 0;
     Network net;
     bool net_created = false;
     // device state sized for max_batch_size
     DevBuf staging, imgs, in4, rows, keys, sorted_keys, sorted_boxes, count, det_scale;
-    DevBuf nms_kept, nms_state; // chunked NMS (dense crowds): kept-box lists, per-chunk {count, epoch} + the spin_fail word
+    // chunked NMS (dense crowds): kept-box lists, and nms_state, in ints:
+    //   {count, epoch} of every chunk [max_batch_size][kNmsChunks] | the fault word | pad | the two chunk-ticket counters (8-byte aligned)
+    // The fault word is the one sticky word every bounded device-side wait reports into (check_nms_flag).
+    DevBuf nms_kept, nms_state;
+    size_t fault_word_index() const { return (size_t)cfg.max_batch_size * kNmsChunks * 2; }
+    size_t nms_state_ints() const { return fault_word_index() + 4; }
+    int *fault_word() const { return (int *)nms_state.p + fault_word_index(); }
     int nms_epoch = 0;
     int nms_ticket_sel = 0;  // which of the two chunk-ticket counters the next chunked NMS launch draws from
     bool nms_chunked = true; // RFD_NMS_CHUNKED=0: one workgroup per image always (A/B and fallback)
-    // host mirror (page-locked) of the chunked NMS's spin_fail word: copied stream-ordered behind every NMS launch, looked at
-    // wherever the host synchronises with the stream (check_nms_flag)
-    int *h_nms_flag = nullptr;
+    // host mirror (page-locked) of the fault word: copied stream-ordered behind every NMS launch, looked at wherever the host
+    // synchronises with the stream (check_nms_flag)
+    Pinned<int> h_nms_flag;
     DevBuf out_boxes, out_lmk, out_count, out_total, out_gidx;
     DevBuf scratch[12];
     DevBuf sel_dims, sel_out;
@@ -198,55 +193,45 @@ struct rfd_ctx {
     // model inputs of the quality / ID stages: staged crops and per-config planes of the host entries; in / out staging of the
     // host forms of the decision rule and the normalisation
     DevBuf face_in, face_tensors[kMaxFaceTensors], face_io[2];
-    // pinned host ring for per-call descriptors, so enqueueing never blocks on the previous call
+    // Per-call descriptors travel through rings of page-locked slots, so enqueueing never blocks on the previous call.
     static constexpr int kRing = 4;
-    PreImage *pin_imgs[kRing] = {};
-    float *pin_scales[kRing] = {};
-    hipEvent_t pin_done[kRing] = {};
-    int pin_next = 0;
-    // frame sizes of the selection epilogue: page-locked like pin_imgs, so that the copy may still be pending when the call returns
-    int *pin_dims[kRing] = {};
-    hipEvent_t pin_dims_done[kRing] = {};
-    int pin_dims_next = 0;
-    // liveness stage, all allocated by its first call: frame descriptors (through a page-locked ring, like pin_imgs), the
-    // per-(face, model) geometry, the in / out staging of the host forms, the running sums of a decide call of many models
+    PinnedRing<kRing> frame_ring; // PreImage [B] | det_scale f32 [B]; its events can be timed
+    PinnedRing<kRing> dims_ring;  // frame sizes of the selection epilogue: h i32 [n] | w i32 [n]
+    PinnedRing<kRing> live_ring;  // LiveImage [B]; allocated by the first liveness call
+    // liveness stage, all allocated by its first call: frame descriptors, the per-(face, model) geometry, the in / out staging of
+    // the host forms, the running sums of a decide call of many models
     DevBuf live_imgs, live_geo, live_io, live_acc;
-    LiveImage *pin_live[kRing] = {};
-    hipEvent_t pin_live_done[kRing] = {};
-    int pin_live_next = 0;
     // JPEG decode (rfd.h, "JPEG decode"), all allocated by its first call.  jpeg_pin is the page-locked staging the decode threads
     // write and jpeg_dev its device twin, both laid out as: JpegFrame [B] | block records u32 [B * jpeg_blocks_max] | coefficients
     // i16 [B * jpeg_blocks_max * 64], B = max_batch_size.  jpeg_pin_done: the copies out of jpeg_pin that the last call enqueued.
     int decode_threads = 4;
     size_t jpeg_blocks_max = 0; // blocks of the largest frame (max_src_w x max_src_h) in its most expensive sampling
-    void *jpeg_pin = nullptr;
-    hipEvent_t jpeg_pin_done = nullptr;
+    Pinned<char> jpeg_pin;
+    Event jpeg_pin_done;
     DevBuf jpeg_dev, jpeg_planes, jpeg_out; // jpeg_out: the device frames of the host-output form
     // pipelined host entry (rfd_submit_batch / rfd_collect_batch): two slots, H2D on its own stream
     struct PipeSlot {
         DevBuf frames, imgs, scale, ob, ol, oc, ot;
-        PreImage *pin_imgs = nullptr;
-        float *pin_scale = nullptr;
-        float *h_ob = nullptr, *h_ol = nullptr;
-        int *h_oc = nullptr, *h_ot = nullptr;
-        hipEvent_t h2d = nullptr, done = nullptr, post = nullptr;
+        Pinned<PreImage> pin_imgs;
+        Pinned<float> pin_scale, h_ob, h_ol;
+        Pinned<int> h_oc, h_ot;
+        Event h2d, done, post;
         int n = 0;
     };
     static constexpr int kPipe = 2;
     static constexpr int kPipeRows = 128; // rows per image the pipelined entry copies back unconditionally
     PipeSlot pipe[kPipe];
-    hipStream_t copy_stream = nullptr, d2h_stream = nullptr;
     int pipe_head = 0, pipe_tail = 0, pipe_inflight = 0;
     // cross-call overlap (rfd_detect_batch_device, async = 2): per-parity descriptors and events
     DevBuf ov_imgs[2], ov_scale[2];
-    hipEvent_t ov_chain_done[2][2] = {}, ov_post_done[2] = {}, ov_desc = nullptr;
+    Event ov_chain_done[2][2], ov_post_done[2], ov_desc;
     bool ov_post_valid[2] = {false, false};
     int ov_parity = 0;
     // batch size of the previous call if it ran in the overlap mode, else -1: the part boundary (n+1)/2 and with it the
     // workspace / input slices of the two chains depend on n, and every other entry point runs the network on the
     // caller's stream, so a chain may start under the previous call only when that call had the same shape
     int ov_last_n = -1;
-    hipEvent_t ov_resync = nullptr;
+    Event ov_resync;
     // multi-GPU: RCCL communicator of this rank (rfd_comm_init)
     Rccl::Comm comm = nullptr;
     int comm_rank = 0, comm_world = 0;
@@ -259,8 +244,7 @@ struct rfd_ctx {
     {
         if (net_created) return RFD_OK;
         RFD_TRY(net.create(cfg.backbone, cfg.image_w, cfg.image_h, cfg.max_batch_size, cfg.precision, cfg.schedule));
-        // the ring convolutions' bounded spins report into the same device word as the chunked NMS (check_nms_flag)
-        net.d_fail = (int *)nms_state.p + (size_t)cfg.max_batch_size * kNmsChunks * 2;
+        net.d_fail = fault_word(); // the ring convolutions' bounded spins report into the same device word as the chunked NMS
         net_created = true;
         return RFD_OK;
     }
@@ -277,7 +261,7 @@ struct rfd_gallery {
     // host forms, allocated by the first of them: a page-locked buffer and its device twin
     static constexpr size_t kStageBytes = 4u << 20;
     DevBuf stage;
-    void *pin = nullptr;
+    Pinned<char> pin;
     // Liveness (rfd.h, "remove and replace").  The host's words are the truth: one per block of 16 rows enrolled so far, bit i =
     // row 16 b + i is live.  Their device twin is read by the masked scan only, which runs while removed > 0, so it is brought
     // up to date lazily: it is right for rows [0, live_synced), the rows added since are all live, and gallery_live_sync sets
@@ -288,9 +272,7 @@ struct rfd_gallery {
     // row lists of remove / replace travel through a ring of page-locked slots (like the context's frame descriptors), so the
     // calls enqueue without waiting for the stream; allocated by the first such call.  A slot: rows | blocks | their new words.
     static constexpr int kRing = 4, kEditRows = 1024;
-    int32_t *pin_edit[kRing] = {};
-    hipEvent_t pin_edit_done[kRing] = {};
-    int pin_edit_next = 0;
+    PinnedRing<kRing> edit_ring;
     DevBuf edit;
 };
 
@@ -305,9 +287,8 @@ int ctx_alloc(rfd_ctx *c)
     RFD_TRY(c->sorted_keys.reserve(B * NA * sizeof(uint64_t)));
     RFD_TRY(c->sorted_boxes.reserve(B * NA * sizeof(float4)));
     RFD_TRY(c->nms_kept.reserve(B * NA * sizeof(float4)));
-    // per-chunk progress words | fault word (+ pad) | the chunk-ticket word (8-byte aligned)
-    RFD_TRY(c->nms_state.reserve((B * kNmsChunks * 2 + 4) * sizeof(int)));
-    RFD_HIP(hipMemset(c->nms_state.p, 0, (B * kNmsChunks * 2 + 4) * sizeof(int)));
+    RFD_TRY(c->nms_state.reserve(c->nms_state_ints() * sizeof(int)));
+    RFD_HIP(hipMemset(c->nms_state.p, 0, c->nms_state_ints() * sizeof(int)));
     RFD_HIP(hipDeviceSynchronize()); // the fill runs on the NULL stream, which the context's non-blocking stream is not ordered with
     RFD_TRY(c->count.reserve(B * sizeof(int)));
     RFD_TRY(c->det_scale.reserve(B * sizeof(float)));
@@ -319,13 +300,20 @@ int ctx_alloc(rfd_ctx *c)
     return RFD_OK;
 }
 
+// n images fit the context; the error names them as "<what> n<unit>"
+int check_batch(const rfd_ctx *c, int n, const char *what, const char *unit = "")
+{
+    if (n < 1 || n > c->cfg.max_batch_size) {
+        set_error("%s %d%s exceeds max_batch_size %d", what, n, unit, c->cfg.max_batch_size);
+        return RFD_ERR_CAPACITY;
+    }
+    return RFD_OK;
+}
+
 int check_images(const rfd_ctx *c, const rfd_image *imgs, int n)
 {
     RFD_CHECK_ARG(imgs != nullptr, "imgs is null");
-    if (n < 1 || n > c->cfg.max_batch_size) {
-        set_error("batch of %d frames exceeds max_batch_size %d", n, c->cfg.max_batch_size);
-        return RFD_ERR_CAPACITY;
-    }
+    RFD_TRY(check_batch(c, n, "batch of", " frames"));
     for (int i = 0; i < n; ++i) {
         RFD_CHECK_ARG(imgs[i].data != nullptr, "frame data is null");
         RFD_CHECK_ARG(imgs[i].height > 0 && imgs[i].width > 0, "frame has a non-positive size");
@@ -334,47 +322,86 @@ int check_images(const rfd_ctx *c, const rfd_image *imgs, int n)
     return RFD_OK;
 }
 
-// Stage the frames (host or device resident) and their letterbox geometry on the device.
-int stage_frames(rfd_ctx *c, const rfd_image *imgs, int n, bool frames_on_device, std::vector<float> &scales)
+size_t frames_bytes(const rfd_image *imgs, int n) // packed back to back with tight rows
 {
-    const int slot = c->pin_next;
-    c->pin_next = (c->pin_next + 1) % rfd_ctx::kRing;
-    RFD_HIP(hipEventSynchronize(c->pin_done[slot])); // the copy that last used this slot has run
-    PreImage *pis = c->pin_imgs[slot];
-    scales.resize(n);
     size_t total = 0;
     for (int i = 0; i < n; ++i) total += (size_t)imgs[i].height * imgs[i].width * 3;
-    if (!frames_on_device) RFD_TRY(c->staging.reserve(total));
+    return total;
+}
+
+// Where the kernels read frame i: desc[i].src / .stride (PreImage, LiveImage).  Device frames are read where they lie; host
+// frames are packed into c->staging on the context's stream, one 2-D copy each.
+template <class Desc> int place_frames(rfd_ctx *c, const rfd_image *imgs, int n, bool frames_on_device, Desc *desc)
+{
+    if (!frames_on_device) RFD_TRY(c->staging.reserve(frames_bytes(imgs, n)));
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
-        letterbox(imgs[i].height, imgs[i].width, c->cfg.image_w, c->cfg.image_h, &pis[i], &scales[i]);
-        if (pis[i].new_w <= 0 || pis[i].new_h <= 0) { // the reference's cv::resize errors out on an empty dsize (face_detection.rs:156-159)
-            set_error("invalid argument: frame %d (%dx%d) letterboxes to an empty %dx%d image", i, imgs[i].width,
-                      imgs[i].height, pis[i].new_w, pis[i].new_h);
-            return RFD_ERR_INVALID_ARG;
-        }
         if (frames_on_device) {
-            pis[i].src = imgs[i].data;
-            pis[i].stride = (long long)imgs[i].stride;
+            desc[i].src = imgs[i].data;
+            desc[i].stride = (long long)imgs[i].stride;
         } else {
             uint8_t *dst = (uint8_t *)c->staging.p + off;
             const size_t row = (size_t)imgs[i].width * 3;
             RFD_HIP(hipMemcpy2DAsync(dst, row, imgs[i].data, (size_t)imgs[i].stride, row, imgs[i].height,
                                      hipMemcpyHostToDevice, c->stream));
-            pis[i].src = dst;
-            pis[i].stride = (long long)row;
+            desc[i].src = dst;
+            desc[i].stride = (long long)row;
             off += row * imgs[i].height;
         }
     }
-    memcpy(c->pin_scales[slot], scales.data(), n * sizeof(float));
-    RFD_HIP(hipMemcpyAsync(c->imgs.p, pis, n * sizeof(PreImage), hipMemcpyHostToDevice, c->stream));
-    RFD_HIP(hipMemcpyAsync(c->det_scale.p, c->pin_scales[slot], n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    RFD_HIP(hipEventRecord(c->pin_done[slot], c->stream));
     return RFD_OK;
 }
 
-void fill_decode_params(const rfd_ctx *c, DecodeParams &p)
+// The letterbox geometry of frame i (all of *pi but src / stride) and its det_scale.
+int fill_pre_image(const rfd_ctx *c, const rfd_image &im, int i, PreImage *pi, float *det_scale)
 {
+    letterbox(im.height, im.width, c->cfg.image_w, c->cfg.image_h, pi, det_scale);
+    if (pi->new_w <= 0 || pi->new_h <= 0) { // the reference's cv::resize errors out on an empty dsize (face_detection.rs:156-159)
+        set_error("invalid argument: frame %d (%dx%d) letterboxes to an empty %dx%d image", i, im.width, im.height, pi->new_w, pi->new_h);
+        return RFD_ERR_INVALID_ARG;
+    }
+    return RFD_OK;
+}
+
+// The next slot of the frame ring: descriptors and det_scales of up to max_batch_size frames, one event for both.
+int acquire_frame_slot(rfd_ctx *c, PreImage **pis, float **scales)
+{
+    RFD_TRY(c->frame_ring.acquire(pis));
+    *scales = (float *)(*pis + c->cfg.max_batch_size);
+    return RFD_OK;
+}
+
+// Stage the frames (host or device resident) and their letterbox geometry on the device.  A frame that cannot be letterboxed
+// refuses the call before anything is enqueued.
+int stage_frames(rfd_ctx *c, const rfd_image *imgs, int n, bool frames_on_device, const float **det_scales = nullptr)
+{
+    PreImage *pis;
+    float *pin_scales;
+    RFD_TRY(acquire_frame_slot(c, &pis, &pin_scales));
+    for (int i = 0; i < n; ++i) RFD_TRY(fill_pre_image(c, imgs[i], i, &pis[i], &pin_scales[i]));
+    if (det_scales) *det_scales = pin_scales; // the slot: good until kRing - 1 more calls have taken theirs
+    RFD_TRY(place_frames(c, imgs, n, frames_on_device, pis));
+    RFD_HIP(hipMemcpyAsync(c->imgs.p, pis, n * sizeof(PreImage), hipMemcpyHostToDevice, c->stream));
+    RFD_HIP(hipMemcpyAsync(c->det_scale.p, pin_scales, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return c->frame_ring.record(c->stream);
+}
+
+// preprocess parameters for the frames whose descriptors start at `imgs` (device); into the network's input from image `net_off`
+// on, or (net_off < 0) with no output chosen yet
+PreParams pre_params(const rfd_ctx *c, const void *imgs, int net_off)
+{
+    PreParams pp;
+    memset(&pp, 0, sizeof pp);
+    pp.imgs = (const PreImage *)imgs;
+    pp.net_h = c->cfg.image_h; pp.net_w = c->cfg.image_w;
+    if (net_off >= 0) pp.out_nhwc4 = (bf16_t *)c->net.tensor_ptr(c->net.g.input) + (size_t)net_off * c->cfg.image_h * c->cfg.image_w * 4;
+    return pp;
+}
+
+// decode parameters; net_heads: with the heads of the network's own pass (of the current head parity) filled in
+DecodeParams decode_params(const rfd_ctx *c, bool net_heads)
+{
+    DecodeParams p;
     memset(&p, 0, sizeof p);
     for (int l = 0; l < kNumLevels; ++l) {
         p.fh[l] = c->fh[l]; p.fw[l] = c->fw[l]; p.stride[l] = kStrides[l]; p.level_off[l] = c->level_off[l];
@@ -386,6 +413,25 @@ void fill_decode_params(const rfd_ctx *c, DecodeParams &p)
     p.rows = (float *)c->rows.p;
     p.keys = (uint64_t *)c->keys.p;
     p.count = (int *)c->count.p;
+    for (int l = 0; net_heads && l < kNumLevels; ++l) p.cls[l] = (const float *)c->net.tensor_ptr(c->net.g.heads[l]);
+    return p;
+}
+
+// the context's own detection slabs
+rfd_dets own_slabs(const rfd_ctx *c)
+{
+    return rfd_dets{(float *)c->out_boxes.p, (float *)c->out_lmk.p, (int32_t *)c->out_count.p, (int32_t *)c->out_total.p};
+}
+
+// detection slabs of n images between host and device, on the context's stream; `total` travels if dst has one
+int copy_slabs(rfd_ctx *c, const rfd_dets &dst, const rfd_dets &src, int n, hipMemcpyKind kind)
+{
+    const size_t MD = (size_t)c->cfg.max_det;
+    RFD_HIP(hipMemcpyAsync(dst.boxes, src.boxes, n * MD * 5 * sizeof(float), kind, c->stream));
+    RFD_HIP(hipMemcpyAsync(dst.landmarks, src.landmarks, n * MD * 10 * sizeof(float), kind, c->stream));
+    RFD_HIP(hipMemcpyAsync(dst.count, src.count, n * sizeof(int), kind, c->stream));
+    if (dst.total) RFD_HIP(hipMemcpyAsync(dst.total, src.total, n * sizeof(int), kind, c->stream));
+    return RFD_OK;
 }
 
 // decode -> sort -> NMS on device-resident heads; outputs to device slabs `o*`.
@@ -413,7 +459,7 @@ int post_network(rfd_ctx *c, DecodeParams &dp, bool nchw, int n, float *oboxes, 
     if (c->nms_chunked) { // kNmsChunks workgroups per image; images with few candidates are done by the first alone
         np.kept_boxes = (float4 *)c->nms_kept.p;
         np.chunk_state = (int *)c->nms_state.p;
-        np.spin_fail = (int *)c->nms_state.p + (size_t)c->cfg.max_batch_size * kNmsChunks * 2;
+        np.spin_fail = c->fault_word();
         np.ticket = (unsigned *)(np.spin_fail + 2);
         np.ticket_sel = c->nms_ticket_sel;
         c->nms_epoch = c->nms_epoch == 0x7fffffff ? 1 : c->nms_epoch + 1;
@@ -425,7 +471,7 @@ int post_network(rfd_ctx *c, DecodeParams &dp, bool nchw, int n, float *oboxes, 
     RFD_HIP(hipEventRecord(c->ev[6], c->stream));
     // the device word is sticky (the kernel only ever sets it), so a later call's copy cannot hide an earlier give-up
     // (copied whether or not the chunked kernel ran: the ring convolutions of the network pass report into the same word)
-    RFD_HIP(hipMemcpyAsync(c->h_nms_flag, (int *)c->nms_state.p + (size_t)c->cfg.max_batch_size * kNmsChunks * 2, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipMemcpyAsync(c->h_nms_flag, c->fault_word(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
     return RFD_OK;
 }
 
@@ -437,8 +483,7 @@ int check_nms_flag(rfd_ctx *c)
 {
     if (!c->h_nms_flag || *c->h_nms_flag == 0) return RFD_OK;
     *c->h_nms_flag = 0;
-    int *flag = (int *)c->nms_state.p + (size_t)c->cfg.max_batch_size * kNmsChunks * 2;
-    RFD_HIP(hipMemsetAsync(flag, 0, sizeof(int), c->stream));
+    RFD_HIP(hipMemsetAsync(c->fault_word(), 0, sizeof(int), c->stream));
     RFD_HIP(hipStreamSynchronize(c->stream));
     set_error("a device-side bounded wait gave up (chunked NMS: a workgroup waiting for its predecessor chunk; ring convolution: a "
               "wave waiting for a ring slot; split-K convolution: an arrival counter left dirty by an earlier fault); the detections of the batches since the last synchronisation are invalid "
@@ -489,29 +534,21 @@ int detect_overlapped(rfd_ctx *c, const rfd_image *imgs, int n, rfd_dets *out, h
     RFD_TRY(net.ensure_alt_heads());
     const size_t B = (size_t)c->cfg.max_batch_size;
     if (!c->ov_desc) {
-        RFD_HIP(hipEventCreateWithFlags(&c->ov_desc, hipEventDisableTiming));
-        RFD_HIP(hipEventCreateWithFlags(&c->ov_resync, hipEventDisableTiming));
+        RFD_TRY(c->ov_desc.create());
+        RFD_TRY(c->ov_resync.create());
         for (int a = 0; a < 2; ++a) {
-            RFD_HIP(hipEventCreateWithFlags(&c->ov_post_done[a], hipEventDisableTiming));
-            for (int b = 0; b < 2; ++b) RFD_HIP(hipEventCreateWithFlags(&c->ov_chain_done[a][b], hipEventDisableTiming));
+            RFD_TRY(c->ov_post_done[a].create());
+            for (int b = 0; b < 2; ++b) RFD_TRY(c->ov_chain_done[a][b].create());
             RFD_TRY(c->ov_imgs[a].reserve(B * sizeof(PreImage)));
             RFD_TRY(c->ov_scale[a].reserve(B * sizeof(float)));
         }
     }
     const int par = (c->ov_parity ^= 1);
-    const int slot = c->pin_next;
-    c->pin_next = (c->pin_next + 1) % rfd_ctx::kRing;
-    RFD_HIP(hipEventSynchronize(c->pin_done[slot]));
-    PreImage *pis = c->pin_imgs[slot];
-    for (int i = 0; i < n; ++i) {
-        letterbox(imgs[i].height, imgs[i].width, c->cfg.image_w, c->cfg.image_h, &pis[i], &c->pin_scales[slot][i]);
-        if (pis[i].new_w <= 0 || pis[i].new_h <= 0) {
-            set_error("invalid argument: frame %d (%dx%d) letterboxes to an empty image", i, imgs[i].width, imgs[i].height);
-            return RFD_ERR_INVALID_ARG;
-        }
-        pis[i].src = imgs[i].data;
-        pis[i].stride = (long long)imgs[i].stride;
-    }
+    PreImage *pis;
+    float *pin_scales;
+    RFD_TRY(acquire_frame_slot(c, &pis, &pin_scales));
+    for (int i = 0; i < n; ++i) RFD_TRY(fill_pre_image(c, imgs[i], i, &pis[i], &pin_scales[i]));
+    RFD_TRY(place_frames(c, imgs, n, true, pis));
     hipStream_t st[2] = {net.part_stream[0], net.part_stream[1]};
     if (c->ov_last_n != n) {
         // Different slices than the previous call's chains (another batch size), or the previous call ran on the caller's
@@ -530,8 +567,8 @@ int detect_overlapped(rfd_ctx *c, const rfd_image *imgs, int n, rfd_dets *out, h
     if (c->ov_post_valid[par])
         for (int p = 0; p < 2; ++p) RFD_HIP(hipStreamWaitEvent(st[p], c->ov_post_done[par], 0));
     RFD_HIP(hipMemcpyAsync(c->ov_imgs[par].p, pis, n * sizeof(PreImage), hipMemcpyHostToDevice, st[0]));
-    RFD_HIP(hipMemcpyAsync(c->ov_scale[par].p, c->pin_scales[slot], n * sizeof(float), hipMemcpyHostToDevice, st[0]));
-    RFD_HIP(hipEventRecord(c->pin_done[slot], st[0]));
+    RFD_HIP(hipMemcpyAsync(c->ov_scale[par].p, pin_scales, n * sizeof(float), hipMemcpyHostToDevice, st[0]));
+    RFD_TRY(c->frame_ring.record(st[0]));
     RFD_HIP(hipEventRecord(c->ov_desc, st[0]));
     RFD_HIP(hipStreamWaitEvent(st[1], c->ov_desc, 0));
     net.head_parity = par;
@@ -539,25 +576,17 @@ int detect_overlapped(rfd_ctx *c, const rfd_image *imgs, int n, rfd_dets *out, h
     int chain[Network::kMaxParts];
     if (net.pass_chains(n, chain) != 2) { set_error("overlapped calls run as two chains"); return RFD_ERR_STATE; }
     const int B0 = chain[0];
-    const size_t in_px = (size_t)c->cfg.image_h * c->cfg.image_w * 4;
     int status = RFD_OK;
     for (int p = 0; p < 2 && status == RFD_OK; ++p) {
         const int off = p ? B0 : 0, Bp = chain[p];
-        PreParams pp;
-        memset(&pp, 0, sizeof pp);
-        pp.imgs = (const PreImage *)c->ov_imgs[par].p + off;
-        pp.net_h = c->cfg.image_h; pp.net_w = c->cfg.image_w;
-        pp.out_nhwc4 = (bf16_t *)net.tensor_ptr(net.g.input) + (size_t)off * in_px;
-        status = launch_preprocess(pp, Bp, st[p]);
+        status = launch_preprocess(pre_params(c, (const PreImage *)c->ov_imgs[par].p + off, off), Bp, st[p]);
         if (status == RFD_OK) status = net.run(Bp, st[p], 0, -1, off, p);
         if (status == RFD_OK && hipEventRecord(c->ov_chain_done[par][p], st[p]) != hipSuccess) status = RFD_ERR_HIP;
     }
     net.co_running = 0;
     if (status != RFD_OK) { net.head_parity = 0; c->ov_last_n = -1; return status; }
     for (int p = 0; p < 2; ++p) RFD_HIP(hipStreamWaitEvent(c->stream, c->ov_chain_done[par][p], 0));
-    DecodeParams dp;
-    fill_decode_params(c, dp);
-    for (int l = 0; l < kNumLevels; ++l) dp.cls[l] = (const float *)net.tensor_ptr(net.g.heads[l]);
+    DecodeParams dp = decode_params(c, true);
     net.head_parity = 0;
     RFD_TRY(post_network(c, dp, false, n, out->boxes, out->landmarks, out->count, out->total, nullptr,
                          (const float *)c->ov_scale[par].p));
@@ -579,34 +608,17 @@ int detect_impl(rfd_ctx *c, const rfd_image *imgs, int n, rfd_dets *out, bool on
     }
     RFD_HIP(hipSetDevice(c->cfg.device_id));
     c->ov_last_n = -1;
-    std::vector<float> scales;
     RFD_HIP(hipEventRecord(c->ev[0], c->stream));
-    RFD_TRY(stage_frames(c, imgs, n, frames_on_device, scales));
+    RFD_TRY(stage_frames(c, imgs, n, frames_on_device));
     RFD_HIP(hipEventRecord(c->ev[1], c->stream));
-    PreParams pp;
-    memset(&pp, 0, sizeof pp);
-    pp.imgs = (const PreImage *)c->imgs.p;
-    pp.net_h = c->cfg.image_h; pp.net_w = c->cfg.image_w;
-    pp.out_nhwc4 = (bf16_t *)c->net.tensor_ptr(c->net.g.input);
-    RFD_TRY(launch_preprocess(pp, n, c->stream));
+    RFD_TRY(launch_preprocess(pre_params(c, c->imgs.p, 0), n, c->stream));
     RFD_HIP(hipEventRecord(c->ev[2], c->stream));
     RFD_TRY(c->net.run_graphed(n, c->stream));
     RFD_HIP(hipEventRecord(c->ev[3], c->stream));
-    DecodeParams dp;
-    fill_decode_params(c, dp);
-    for (int l = 0; l < kNumLevels; ++l) dp.cls[l] = (const float *)c->net.tensor_ptr(c->net.g.heads[l]);
-    float *ob = on_device ? out->boxes : (float *)c->out_boxes.p;
-    float *ol = on_device ? out->landmarks : (float *)c->out_lmk.p;
-    int *oc = on_device ? out->count : (int *)c->out_count.p;
-    int *ot = on_device ? out->total : (int *)c->out_total.p;
-    RFD_TRY(post_network(c, dp, false, n, ob, ol, oc, ot, nullptr));
-    if (!on_device) {
-        const size_t MD = (size_t)c->cfg.max_det;
-        RFD_HIP(hipMemcpyAsync(out->boxes, ob, n * MD * 5 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        RFD_HIP(hipMemcpyAsync(out->landmarks, ol, n * MD * 10 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        RFD_HIP(hipMemcpyAsync(out->count, oc, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        if (out->total) RFD_HIP(hipMemcpyAsync(out->total, ot, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    }
+    DecodeParams dp = decode_params(c, true);
+    const rfd_dets dev = on_device ? *out : own_slabs(c);
+    RFD_TRY(post_network(c, dp, false, n, dev.boxes, dev.landmarks, dev.count, dev.total, nullptr));
+    if (!on_device) RFD_TRY(copy_slabs(c, *out, dev, n, hipMemcpyDeviceToHost));
     RFD_HIP(hipEventRecord(c->ev[7], c->stream));
     if (async && on_device) return RFD_OK;
     RFD_HIP(hipStreamSynchronize(c->stream));
@@ -671,7 +683,7 @@ int rfd_create(const rfd_config *cfg, rfd_ctx **out)
         set_error("hipSetDevice(%d) failed", cfg->device_id);
         return RFD_ERR_NO_DEVICE;
     }
-    rfd_ctx *c = new rfd_ctx();
+    std::unique_ptr<rfd_ctx> c(new rfd_ctx()); // an early return frees whatever was built so far
     c->cfg = *cfg;
     if (const char *e = getenv("RFD_NMS_CHUNKED")) c->nms_chunked = atoi(e) != 0;
     make_base_anchors(c->base_anchor);
@@ -684,28 +696,16 @@ int rfd_create(const rfd_config *cfg, rfd_ctx **out)
     }
     c->total_anchors = off;
     memset(&c->stats, 0, sizeof c->stats);
-    int st = RFD_OK;
-    if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) st = RFD_ERR_HIP;
+    const size_t B = (size_t)cfg->max_batch_size;
+    RFD_TRY(c->own_stream.create());
     c->stream = c->own_stream;
-    for (int i = 0; i < 10 && st == RFD_OK; ++i)
-        if (hipEventCreate(&c->ev[i]) != hipSuccess) st = RFD_ERR_HIP;
-    for (int i = 0; i < rfd_ctx::kRing && st == RFD_OK; ++i) {
-        if (hipHostMalloc((void **)&c->pin_imgs[i], cfg->max_batch_size * sizeof(PreImage)) != hipSuccess ||
-            hipHostMalloc((void **)&c->pin_scales[i], cfg->max_batch_size * sizeof(float)) != hipSuccess ||
-            hipEventCreate(&c->pin_done[i]) != hipSuccess ||
-            hipHostMalloc((void **)&c->pin_dims[i], (size_t)cfg->max_batch_size * 2 * sizeof(int)) != hipSuccess ||
-            hipEventCreateWithFlags(&c->pin_dims_done[i], hipEventDisableTiming) != hipSuccess)
-            st = RFD_ERR_HIP;
-    }
-    if (st == RFD_OK && hipHostMalloc((void **)&c->h_nms_flag, sizeof(int)) != hipSuccess) st = RFD_ERR_HIP;
-    if (st == RFD_OK) *c->h_nms_flag = 0;
-    if (st == RFD_OK) st = ctx_alloc(c);
-    if (st != RFD_OK) {
-        if (st == RFD_ERR_HIP && !*get_error()) set_error("HIP stream/event creation failed");
-        rfd_destroy(c);
-        return st;
-    }
-    *out = c;
+    for (Event &e : c->ev) RFD_TRY(e.create(hipEventDefault));
+    RFD_TRY(c->frame_ring.ensure(B * (sizeof(PreImage) + sizeof(float)), hipEventDefault));
+    RFD_TRY(c->dims_ring.ensure(B * 2 * sizeof(int)));
+    RFD_TRY(c->h_nms_flag.alloc(1));
+    *c->h_nms_flag = 0;
+    RFD_TRY(ctx_alloc(c.get()));
+    *out = c.release();
     return RFD_OK;
 }
 
@@ -716,54 +716,6 @@ void rfd_destroy(rfd_ctx *c)
     (void)hipDeviceSynchronize(); // part / side / copy streams included
     if (c->comm) { (void)g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
     if (c->net_created) c->net.destroy();
-    DevBuf *bufs[] = {&c->staging, &c->imgs, &c->in4, &c->rows, &c->keys, &c->sorted_keys, &c->sorted_boxes,
-                      &c->count, &c->det_scale, &c->out_boxes, &c->out_lmk, &c->out_count, &c->out_total,
-                      &c->out_gidx, &c->nms_kept, &c->nms_state};
-    for (DevBuf *b : bufs) b->release();
-    for (DevBuf &b : c->scratch) b.release();
-    c->sel_dims.release(); c->sel_out.release();
-    c->align_faces.release(); c->align_out.release(); c->align_status.release();
-    c->face_in.release(); c->face_io[0].release(); c->face_io[1].release();
-    for (DevBuf &b : c->face_tensors) b.release();
-    c->live_imgs.release(); c->live_geo.release(); c->live_io.release(); c->live_acc.release();
-    for (int i = 0; i < rfd_ctx::kRing; ++i) {
-        if (c->pin_live[i]) (void)hipHostFree(c->pin_live[i]);
-        if (c->pin_live_done[i]) (void)hipEventDestroy(c->pin_live_done[i]);
-    }
-    c->jpeg_dev.release(); c->jpeg_planes.release(); c->jpeg_out.release();
-    if (c->jpeg_pin) (void)hipHostFree(c->jpeg_pin);
-    if (c->jpeg_pin_done) (void)hipEventDestroy(c->jpeg_pin_done);
-    for (int i = 0; i < 10; ++i)
-        if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-    for (int i = 0; i < rfd_ctx::kRing; ++i) {
-        if (c->pin_imgs[i]) (void)hipHostFree(c->pin_imgs[i]);
-        if (c->pin_scales[i]) (void)hipHostFree(c->pin_scales[i]);
-        if (c->pin_done[i]) (void)hipEventDestroy(c->pin_done[i]);
-        if (c->pin_dims[i]) (void)hipHostFree(c->pin_dims[i]);
-        if (c->pin_dims_done[i]) (void)hipEventDestroy(c->pin_dims_done[i]);
-    }
-    if (c->h_nms_flag) (void)hipHostFree(c->h_nms_flag);
-    for (rfd_ctx::PipeSlot &ps : c->pipe) {
-        DevBuf *pb[] = {&ps.frames, &ps.imgs, &ps.scale, &ps.ob, &ps.ol, &ps.oc, &ps.ot};
-        for (DevBuf *b : pb) b->release();
-        void *hp[] = {ps.pin_imgs, ps.pin_scale, ps.h_ob, ps.h_ol, ps.h_oc, ps.h_ot};
-        for (void *h : hp)
-            if (h) (void)hipHostFree(h);
-        if (ps.h2d) (void)hipEventDestroy(ps.h2d);
-        if (ps.done) (void)hipEventDestroy(ps.done);
-        if (ps.post) (void)hipEventDestroy(ps.post);
-    }
-    for (int a = 0; a < 2; ++a) {
-        c->ov_imgs[a].release(); c->ov_scale[a].release();
-        if (c->ov_post_done[a]) (void)hipEventDestroy(c->ov_post_done[a]);
-        for (int b = 0; b < 2; ++b)
-            if (c->ov_chain_done[a][b]) (void)hipEventDestroy(c->ov_chain_done[a][b]);
-    }
-    if (c->ov_desc) (void)hipEventDestroy(c->ov_desc);
-    if (c->ov_resync) (void)hipEventDestroy(c->ov_resync);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->d2h_stream) (void)hipStreamDestroy(c->d2h_stream);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
 
@@ -785,7 +737,7 @@ int rfd_set_stream(rfd_ctx *c, void *hip_stream)
 {
     RFD_CHECK_ARG(c, "ctx is null");
     RFD_HIP(hipStreamSynchronize(c->stream));
-    c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
+    c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream.s;
     return RFD_OK;
 }
 
@@ -944,8 +896,7 @@ int rfd_debug_poke_nms_flag(rfd_ctx *c, int value)
 {
     RFD_CHECK_ARG(c, "ctx is null");
     RFD_HIP(hipSetDevice(c->cfg.device_id));
-    int *flag = (int *)c->nms_state.p + (size_t)c->cfg.max_batch_size * kNmsChunks * 2;
-    RFD_HIP(hipMemcpyAsync(flag, &value, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    RFD_HIP(hipMemcpyAsync(c->fault_word(), &value, sizeof(int), hipMemcpyHostToDevice, c->stream));
     RFD_HIP(hipStreamSynchronize(c->stream));
     return RFD_OK;
 }
@@ -1233,7 +1184,7 @@ int rfd_gather_detections(rfd_ctx *c, const rfd_dets *local, int n_local, rfd_de
                   "slab pointers are null");
     RFD_CHECK_ARG((local->total != nullptr) == (all->total != nullptr), "total must be given in both slabs or in neither");
     if (!c->comm) { set_error("no communicator: call rfd_comm_init first"); return RFD_ERR_STATE; }
-    if (n_local < 1 || n_local > c->cfg.max_batch_size) { set_error("n_local %d exceeds max_batch_size %d", n_local, c->cfg.max_batch_size); return RFD_ERR_CAPACITY; }
+    RFD_TRY(check_batch(c, n_local, "n_local"));
     RFD_HIP(hipSetDevice(c->cfg.device_id));
     const size_t MD = (size_t)c->cfg.max_det, n = (size_t)n_local;
     // four arrays, one fused collective; everything moves as 32-bit words (floats are not interpreted)
@@ -1286,16 +1237,16 @@ int rfd_submit_batch(rfd_ctx *c, const rfd_image *imgs, int n)
     RFD_TRY(c->ensure_network());
     const size_t B = (size_t)c->cfg.max_batch_size, MD = (size_t)c->cfg.max_det;
     rfd_ctx::PipeSlot &ps = c->pipe[c->pipe_head];
-    if (!c->copy_stream) RFD_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    RFD_TRY(c->copy_stream.create());
     if (!ps.done) { // first use of this slot
-        RFD_HIP(hipEventCreateWithFlags(&ps.h2d, hipEventDisableTiming));
-        RFD_HIP(hipEventCreateWithFlags(&ps.done, hipEventDisableTiming));
-        RFD_HIP(hipHostMalloc((void **)&ps.pin_imgs, B * sizeof(PreImage), hipHostMallocDefault));
-        RFD_HIP(hipHostMalloc((void **)&ps.pin_scale, B * sizeof(float), hipHostMallocDefault));
-        RFD_HIP(hipHostMalloc((void **)&ps.h_ob, B * MD * 5 * sizeof(float), hipHostMallocDefault));
-        RFD_HIP(hipHostMalloc((void **)&ps.h_ol, B * MD * 10 * sizeof(float), hipHostMallocDefault));
-        RFD_HIP(hipHostMalloc((void **)&ps.h_oc, B * sizeof(int), hipHostMallocDefault));
-        RFD_HIP(hipHostMalloc((void **)&ps.h_ot, B * sizeof(int), hipHostMallocDefault));
+        RFD_TRY(ps.h2d.create());
+        RFD_TRY(ps.done.create());
+        RFD_TRY(ps.pin_imgs.alloc(B));
+        RFD_TRY(ps.pin_scale.alloc(B));
+        RFD_TRY(ps.h_ob.alloc(B * MD * 5));
+        RFD_TRY(ps.h_ol.alloc(B * MD * 10));
+        RFD_TRY(ps.h_oc.alloc(B));
+        RFD_TRY(ps.h_ot.alloc(B));
         RFD_TRY(ps.imgs.reserve(B * sizeof(PreImage)));
         RFD_TRY(ps.scale.reserve(B * sizeof(float)));
         RFD_TRY(ps.ob.reserve(B * MD * 5 * sizeof(float)));
@@ -1303,19 +1254,14 @@ int rfd_submit_batch(rfd_ctx *c, const rfd_image *imgs, int n)
         RFD_TRY(ps.oc.reserve(B * sizeof(int)));
         RFD_TRY(ps.ot.reserve(B * sizeof(int)));
     }
-    size_t total = 0;
-    for (int i = 0; i < n; ++i) total += (size_t)imgs[i].height * imgs[i].width * 3;
+    const size_t total = frames_bytes(imgs, n);
     if (total > ps.frames.cap) { // growing the frame buffer frees the old one: nothing of this slot is in flight (it was collected)
         RFD_TRY(ps.frames.reserve(total + total / 4));
     }
     // copy stream: frames + descriptors of THIS batch while the main stream still computes the previous one
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
-        letterbox(imgs[i].height, imgs[i].width, c->cfg.image_w, c->cfg.image_h, &ps.pin_imgs[i], &ps.pin_scale[i]);
-        if (ps.pin_imgs[i].new_w <= 0 || ps.pin_imgs[i].new_h <= 0) {
-            set_error("invalid argument: frame %d (%dx%d) letterboxes to an empty image", i, imgs[i].width, imgs[i].height);
-            return RFD_ERR_INVALID_ARG;
-        }
+        RFD_TRY(fill_pre_image(c, imgs[i], i, &ps.pin_imgs[i], &ps.pin_scale[i]));
         ps.pin_imgs[i].src = (uint8_t *)ps.frames.p + off;
         ps.pin_imgs[i].stride = (long long)imgs[i].width * 3;
         off += (size_t)imgs[i].width * 3 * imgs[i].height;
@@ -1359,23 +1305,16 @@ int rfd_submit_batch(rfd_ctx *c, const rfd_image *imgs, int n)
         // main stream: the whole hot path of this batch, behind the previous batch
         c->ov_last_n = -1;
         RFD_HIP(hipStreamWaitEvent(c->stream, ps.h2d, 0));
-        PreParams pp;
-        memset(&pp, 0, sizeof pp);
-        pp.imgs = (const PreImage *)ps.imgs.p;
-        pp.net_h = c->cfg.image_h; pp.net_w = c->cfg.image_w;
-        pp.out_nhwc4 = (bf16_t *)c->net.tensor_ptr(c->net.g.input);
-        RFD_TRY(launch_preprocess(pp, n, c->stream));
+        RFD_TRY(launch_preprocess(pre_params(c, ps.imgs.p, 0), n, c->stream));
         RFD_TRY(c->net.run_graphed(n, c->stream));
-        DecodeParams dp;
-        fill_decode_params(c, dp);
-        for (int l = 0; l < kNumLevels; ++l) dp.cls[l] = (const float *)c->net.tensor_ptr(c->net.g.heads[l]);
+        DecodeParams dp = decode_params(c, true);
         RFD_TRY(post_network(c, dp, false, n, (float *)ps.ob.p, (float *)ps.ol.p, (int *)ps.oc.p, (int *)ps.ot.p, nullptr,
                              (const float *)ps.scale.p));
     }
     // detections go back on their own stream: neither the next batch's compute (caller's stream) nor its frames (copy stream,
     // enqueued earlier than this batch's NMS finishes) queue behind them
-    if (!c->d2h_stream) RFD_HIP(hipStreamCreateWithFlags(&c->d2h_stream, hipStreamNonBlocking));
-    if (!ps.post) RFD_HIP(hipEventCreateWithFlags(&ps.post, hipEventDisableTiming));
+    RFD_TRY(c->d2h_stream.create());
+    RFD_TRY(ps.post.create());
     RFD_HIP(hipEventRecord(ps.post, c->stream));
     RFD_HIP(hipStreamWaitEvent(c->d2h_stream, ps.post, 0));
     // the first kPipeRows rows of every image now (two strided copies); an image that kept more has the rest fetched by
@@ -1432,20 +1371,17 @@ int rfd_preprocess(rfd_ctx *c, const rfd_image *imgs, int n, uint8_t *det_img, f
     RFD_CHECK_ARG(c != nullptr, "ctx is null");
     RFD_TRY(check_images(c, imgs, n));
     RFD_HIP(hipSetDevice(c->cfg.device_id));
-    std::vector<float> scales;
-    RFD_TRY(stage_frames(c, imgs, n, false, scales));
+    const float *scales;
+    RFD_TRY(stage_frames(c, imgs, n, false, &scales));
     const size_t npix = (size_t)n * c->cfg.image_h * c->cfg.image_w;
-    PreParams pp;
-    memset(&pp, 0, sizeof pp);
-    pp.imgs = (const PreImage *)c->imgs.p;
-    pp.net_h = c->cfg.image_h; pp.net_w = c->cfg.image_w;
+    PreParams pp = pre_params(c, c->imgs.p, -1);
     if (det_img) { RFD_TRY(c->scratch[0].reserve(npix * 3)); pp.out_det_img = (uint8_t *)c->scratch[0].p; }
     if (tensor) { RFD_TRY(c->scratch[1].reserve(npix * 3 * sizeof(float))); pp.out_tensor = (float *)c->scratch[1].p; }
     RFD_TRY(launch_preprocess(pp, n, c->stream));
     if (det_img) RFD_HIP(hipMemcpyAsync(det_img, pp.out_det_img, npix * 3, hipMemcpyDeviceToHost, c->stream));
     if (tensor) RFD_HIP(hipMemcpyAsync(tensor, pp.out_tensor, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     RFD_HIP(hipStreamSynchronize(c->stream));
-    if (det_scale) memcpy(det_scale, scales.data(), n * sizeof(float));
+    if (det_scale) memcpy(det_scale, scales, n * sizeof(float));
     return RFD_OK;
 }
 
@@ -1453,7 +1389,7 @@ int rfd_forward(rfd_ctx *c, const float *tensor, int n, float *const heads[9])
 {
     RFD_CHECK_ARG(c && tensor && heads, "null argument");
     for (int i = 0; i < 9; ++i) RFD_CHECK_ARG(heads[i] != nullptr, "head pointer is null");
-    if (n < 1 || n > c->cfg.max_batch_size) { set_error("batch %d exceeds max_batch_size %d", n, c->cfg.max_batch_size); return RFD_ERR_CAPACITY; }
+    RFD_TRY(check_batch(c, n, "batch"));
     RFD_HIP(hipSetDevice(c->cfg.device_id));
     RFD_TRY(c->ensure_network());
     c->ov_last_n = -1;
@@ -1486,11 +1422,10 @@ int rfd_decode_nms(rfd_ctx *c, const float *const heads[9], int n, const float *
     RFD_CHECK_ARG(c && heads && det_scale, "null argument");
     RFD_CHECK_ARG(out && out->boxes && out->landmarks && out->count, "output buffers are null");
     for (int i = 0; i < 9; ++i) RFD_CHECK_ARG(heads[i] != nullptr, "head pointer is null");
-    if (n < 1 || n > c->cfg.max_batch_size) { set_error("batch %d exceeds max_batch_size %d", n, c->cfg.max_batch_size); return RFD_ERR_CAPACITY; }
+    RFD_TRY(check_batch(c, n, "batch"));
     RFD_HIP(hipSetDevice(c->cfg.device_id));
     static const int chans[3] = {2 * kA, 4 * kA, 10 * kA};
-    DecodeParams dp;
-    fill_decode_params(c, dp);
+    DecodeParams dp = decode_params(c, false);
     for (int l = 0; l < kNumLevels; ++l)
         for (int k = 0; k < 3; ++k) {
             const size_t bytes = (size_t)n * chans[k] * c->fh[l] * c->fw[l] * sizeof(float);
@@ -1501,14 +1436,10 @@ int rfd_decode_nms(rfd_ctx *c, const float *const heads[9], int n, const float *
         }
     RFD_HIP(hipMemcpyAsync(c->det_scale.p, det_scale, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     RFD_HIP(hipEventRecord(c->ev[3], c->stream));
-    RFD_TRY(post_network(c, dp, true, n, (float *)c->out_boxes.p, (float *)c->out_lmk.p, (int *)c->out_count.p,
-                         (int *)c->out_total.p, gidx ? (int *)c->out_gidx.p : nullptr));
-    const size_t MD = (size_t)c->cfg.max_det;
-    RFD_HIP(hipMemcpyAsync(out->boxes, c->out_boxes.p, n * MD * 5 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipMemcpyAsync(out->landmarks, c->out_lmk.p, n * MD * 10 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipMemcpyAsync(out->count, c->out_count.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if (out->total) RFD_HIP(hipMemcpyAsync(out->total, c->out_total.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if (gidx) RFD_HIP(hipMemcpyAsync(gidx, c->out_gidx.p, n * MD * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    const rfd_dets dev = own_slabs(c);
+    RFD_TRY(post_network(c, dp, true, n, dev.boxes, dev.landmarks, dev.count, dev.total, gidx ? (int *)c->out_gidx.p : nullptr));
+    RFD_TRY(copy_slabs(c, *out, dev, n, hipMemcpyDeviceToHost));
+    if (gidx) RFD_HIP(hipMemcpyAsync(gidx, c->out_gidx.p, (size_t)n * c->cfg.max_det * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     RFD_HIP(hipEventRecord(c->ev[7], c->stream));
     RFD_HIP(hipStreamSynchronize(c->stream));
     RFD_TRY(check_nms_flag(c));
@@ -1537,13 +1468,11 @@ static int select_enqueue(rfd_ctx *c, const float *d_boxes, const float *d_lmk, 
     rfd_selection_config_default(&def);
     if (!cfg) cfg = &def;
     RFD_TRY(c->sel_dims.reserve((size_t)2 * n * sizeof(int)));
-    const int slot = c->pin_dims_next;
-    c->pin_dims_next = (c->pin_dims_next + 1) % rfd_ctx::kRing;
-    RFD_HIP(hipEventSynchronize(c->pin_dims_done[slot])); // the copy that last used this slot has run
-    int *dims = c->pin_dims[slot];
+    int *dims;
+    RFD_TRY(c->dims_ring.acquire(&dims));
     for (int i = 0; i < n; ++i) { dims[i] = img_h[i]; dims[n + i] = img_w[i]; }
     RFD_HIP(hipMemcpyAsync(c->sel_dims.p, dims, 2 * n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    RFD_HIP(hipEventRecord(c->pin_dims_done[slot], c->stream));
+    RFD_TRY(c->dims_ring.record(c->stream));
     SelectParams sp;
     memset(&sp, 0, sizeof sp);
     sp.boxes = d_boxes; sp.lmk = d_lmk; sp.count = d_count;
@@ -1557,19 +1486,37 @@ static int select_enqueue(rfd_ctx *c, const float *d_boxes, const float *d_lmk, 
     return launch_face_select(sp, c->stream);
 }
 
-// the same into c->sel_out, then copied to the host pointers
+// c->sel_out holds the selection of n frames as box [n][5] | kps [n][10] | found [n]
+struct SelView { float *box, *kps; int32_t *found; };
+static SelView sel_view(const rfd_ctx *c, int n)
+{
+    float *o = (float *)c->sel_out.p;
+    return SelView{o, o + (size_t)n * 5, (int32_t *)(o + (size_t)n * 15)};
+}
+static int sel_reserve(rfd_ctx *c, int n) { return c->sel_out.reserve((size_t)n * 16 * sizeof(float)); }
+
+// a selection the caller holds on the host, into c->sel_out
+static int sel_upload(rfd_ctx *c, int n, const float *boxes, const float *kps, const int32_t *found)
+{
+    RFD_TRY(sel_reserve(c, n));
+    const SelView v = sel_view(c, n);
+    RFD_HIP(hipMemcpyAsync(v.box, boxes, (size_t)n * 5 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    RFD_HIP(hipMemcpyAsync(v.kps, kps, (size_t)n * 10 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    RFD_HIP(hipMemcpyAsync(v.found, found, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    return RFD_OK;
+}
+
+// select_enqueue into c->sel_out, then copied to the host pointers
 static int select_impl(rfd_ctx *c, const float *d_boxes, const float *d_lmk, const int *d_count, const int *img_h,
                        const int *img_w, int n, const rfd_selection_config *cfg, int is_enroll, float *out_box,
                        float *out_kps, int32_t *found)
 {
-    RFD_TRY(c->sel_out.reserve((size_t)n * 16 * sizeof(float)));
-    float *o = (float *)c->sel_out.p;
-    float *d_box = o, *d_kps = o + (size_t)n * 5;
-    int32_t *d_found = (int32_t *)(o + (size_t)n * 15);
-    RFD_TRY(select_enqueue(c, d_boxes, d_lmk, d_count, img_h, img_w, n, cfg, is_enroll, d_box, d_kps, d_found));
-    RFD_HIP(hipMemcpyAsync(out_box, d_box, (size_t)n * 5 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipMemcpyAsync(out_kps, d_kps, (size_t)n * 10 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipMemcpyAsync(found, d_found, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    RFD_TRY(sel_reserve(c, n));
+    const SelView v = sel_view(c, n);
+    RFD_TRY(select_enqueue(c, d_boxes, d_lmk, d_count, img_h, img_w, n, cfg, is_enroll, v.box, v.kps, v.found));
+    RFD_HIP(hipMemcpyAsync(out_box, v.box, (size_t)n * 5 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipMemcpyAsync(out_kps, v.kps, (size_t)n * 10 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipMemcpyAsync(found, v.found, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     RFD_HIP(hipStreamSynchronize(c->stream)); // the results are read by the caller
     return check_nms_flag(c);
 }
@@ -1579,14 +1526,12 @@ int rfd_select_faces(rfd_ctx *c, const rfd_dets *dets, const int *img_h, const i
 {
     RFD_CHECK_ARG(c && dets && dets->boxes && dets->landmarks && dets->count && img_h && img_w && out_box && out_kps && found,
                   "null argument");
-    if (n < 1 || n > c->cfg.max_batch_size) { set_error("batch %d exceeds max_batch_size %d", n, c->cfg.max_batch_size); return RFD_ERR_CAPACITY; }
+    RFD_TRY(check_batch(c, n, "batch"));
     RFD_HIP(hipSetDevice(c->cfg.device_id));
-    const size_t MD = (size_t)c->cfg.max_det;
-    RFD_HIP(hipMemcpyAsync(c->out_boxes.p, dets->boxes, n * MD * 5 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    RFD_HIP(hipMemcpyAsync(c->out_lmk.p, dets->landmarks, n * MD * 10 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    RFD_HIP(hipMemcpyAsync(c->out_count.p, dets->count, n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    return select_impl(c, (const float *)c->out_boxes.p, (const float *)c->out_lmk.p, (const int *)c->out_count.p, img_h, img_w,
-                       n, cfg, is_enroll, out_box, out_kps, found);
+    rfd_dets dev = own_slabs(c);
+    dev.total = nullptr; // the selection does not read it
+    RFD_TRY(copy_slabs(c, dev, *dets, n, hipMemcpyHostToDevice));
+    return select_impl(c, dev.boxes, dev.landmarks, dev.count, img_h, img_w, n, cfg, is_enroll, out_box, out_kps, found);
 }
 
 int rfd_detect_select_batch(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_selection_config *cfg, int is_enroll,
@@ -1594,7 +1539,7 @@ int rfd_detect_select_batch(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_
 {
     RFD_CHECK_ARG(c && out_box && out_kps && found, "null argument");
     RFD_TRY(check_images(c, imgs, n));
-    rfd_dets dev = {(float *)c->out_boxes.p, (float *)c->out_lmk.p, (int32_t *)c->out_count.p, (int32_t *)c->out_total.p};
+    rfd_dets dev = own_slabs(c);
     RFD_TRY(detect_impl(c, imgs, n, &dev, /*outputs stay on the device*/ true, /*async*/ 1, /*frames on host*/ false));
     std::vector<int> hh(n), ww(n);
     for (int i = 0; i < n; ++i) { hh[i] = imgs[i].height; ww[i] = imgs[i].width; }
@@ -1610,18 +1555,24 @@ void rfd_alignment_config_default(rfd_alignment_config *cfg)
     memcpy(cfg->standard_landmarks, tmpl, sizeof tmpl);
 }
 
+// the caller's alignment config or, for null, the reference's (into *def); refused if its output size is out of range
+static int resolve_align_cfg(const rfd_alignment_config **cfg, rfd_alignment_config *def)
+{
+    if (!*cfg) { rfd_alignment_config_default(def); *cfg = def; }
+    if ((*cfg)->out_w < 1 || (*cfg)->out_h < 1 || (*cfg)->out_w > 4096 || (*cfg)->out_h > 4096) {
+        set_error("alignment output size %dx%d out of range", (*cfg)->out_w, (*cfg)->out_h);
+        return RFD_ERR_INVALID_ARG;
+    }
+    return RFD_OK;
+}
+
 // alignment of the frames whose descriptors sit in c->imgs (the last staged batch); selection results are device
 // arrays; crops and status are copied to the host pointers
 static int align_impl(rfd_ctx *c, int n, const float *d_box, const float *d_kps, const int *d_found,
                       const rfd_alignment_config *cfg, uint8_t *out_crops, int32_t *status)
 {
     rfd_alignment_config def;
-    rfd_alignment_config_default(&def);
-    if (!cfg) cfg = &def;
-    if (cfg->out_w < 1 || cfg->out_h < 1 || cfg->out_w > 4096 || cfg->out_h > 4096) {
-        set_error("alignment output size %dx%d out of range", cfg->out_w, cfg->out_h);
-        return RFD_ERR_INVALID_ARG;
-    }
+    RFD_TRY(resolve_align_cfg(&cfg, &def));
     const size_t crop = (size_t)cfg->out_w * cfg->out_h * 3;
     RFD_TRY(c->align_faces.reserve((size_t)n * sizeof(AlignFace)));
     RFD_TRY(c->align_out.reserve((size_t)n * crop));
@@ -1648,14 +1599,10 @@ int rfd_align_faces(rfd_ctx *c, const rfd_image *imgs, int n, const float *boxes
     RFD_CHECK_ARG(c && boxes && kps && found && out_crops && status, "null argument");
     RFD_TRY(check_images(c, imgs, n));
     RFD_HIP(hipSetDevice(c->cfg.device_id));
-    std::vector<float> scales;
-    RFD_TRY(stage_frames(c, imgs, n, false, scales));
-    RFD_TRY(c->sel_out.reserve((size_t)n * 16 * sizeof(float)));
-    float *o = (float *)c->sel_out.p;
-    RFD_HIP(hipMemcpyAsync(o, boxes, (size_t)n * 5 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    RFD_HIP(hipMemcpyAsync(o + (size_t)n * 5, kps, (size_t)n * 10 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    RFD_HIP(hipMemcpyAsync(o + (size_t)n * 15, found, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    return align_impl(c, n, o, o + (size_t)n * 5, (const int *)(o + (size_t)n * 15), cfg, out_crops, status);
+    RFD_TRY(stage_frames(c, imgs, n, false));
+    RFD_TRY(sel_upload(c, n, boxes, kps, found));
+    const SelView v = sel_view(c, n);
+    return align_impl(c, n, v.box, v.kps, v.found, cfg, out_crops, status);
 }
 
 int rfd_detect_select_align_batch(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_selection_config *sel_cfg, int is_enroll,
@@ -1665,8 +1612,8 @@ int rfd_detect_select_align_batch(rfd_ctx *c, const rfd_image *imgs, int n, cons
     RFD_CHECK_ARG(c && out_crops && status, "null argument");
     // the staged frames and their descriptors (c->staging / c->imgs) stay valid until the next call on this context
     RFD_TRY(rfd_detect_select_batch(c, imgs, n, sel_cfg, is_enroll, out_box, out_kps, found));
-    const float *o = (const float *)c->sel_out.p;
-    return align_impl(c, n, o, o + (size_t)n * 5, (const int *)(o + (size_t)n * 15), align_cfg, out_crops, status);
+    const SelView v = sel_view(c, n);
+    return align_impl(c, n, v.box, v.kps, v.found, align_cfg, out_crops, status);
 }
 
 // ---- model inputs of the quality and ID stages (face_quality.rs:43-44,56-101, face_extraction.rs:38-77) ----
@@ -1724,7 +1671,7 @@ int rfd_face_tensors(rfd_ctx *c, const uint8_t *crops, int n, int crop_w, int cr
     RFD_CHECK_ARG(c && crops, "null argument");
     RFD_TRY(check_face_tensor_args(cfgs, k, tensors, 1));
     RFD_CHECK_ARG(crop_w >= 1 && crop_h >= 1 && crop_w <= 4096 && crop_h <= 4096, "crop size out of range");
-    if (n < 1 || n > c->cfg.max_batch_size) { set_error("batch %d exceeds max_batch_size %d", n, c->cfg.max_batch_size); return RFD_ERR_CAPACITY; }
+    RFD_TRY(check_batch(c, n, "batch"));
     RFD_HIP(hipSetDevice(c->cfg.device_id));
     const size_t crop = (size_t)crop_w * crop_h * 3;
     RFD_TRY(c->face_in.reserve((size_t)n * crop));
@@ -1752,12 +1699,7 @@ static int align_tensors_enqueue(rfd_ctx *c, int n, const float *d_box, const fl
                                  float *const *d_tensors, uint8_t *d_crops, int32_t *d_status)
 {
     rfd_alignment_config def;
-    rfd_alignment_config_default(&def);
-    if (!cfg) cfg = &def;
-    if (cfg->out_w < 1 || cfg->out_h < 1 || cfg->out_w > 4096 || cfg->out_h > 4096) {
-        set_error("alignment output size %dx%d out of range", cfg->out_w, cfg->out_h);
-        return RFD_ERR_INVALID_ARG;
-    }
+    RFD_TRY(resolve_align_cfg(&cfg, &def));
     FaceTensorParams fused, rest;
     memset(&fused, 0, sizeof fused);
     memset(&rest, 0, sizeof rest);
@@ -1800,8 +1742,8 @@ static int align_tensors_to_host(rfd_ctx *c, int n, const rfd_alignment_config *
         RFD_TRY(c->face_tensors[j].reserve((size_t)n * 3 * cfgs[j].out_w * cfgs[j].out_h * sizeof(float)));
         d_tensors[j] = (float *)c->face_tensors[j].p;
     }
-    const float *o = (const float *)c->sel_out.p;
-    RFD_TRY(align_tensors_enqueue(c, n, o, o + (size_t)n * 5, (const int *)(o + (size_t)n * 15), align_cfg, cfgs, k, d_tensors,
+    const SelView v = sel_view(c, n);
+    RFD_TRY(align_tensors_enqueue(c, n, v.box, v.kps, v.found, align_cfg, cfgs, k, d_tensors,
                                   out_crops ? (uint8_t *)c->align_out.p : nullptr, (int32_t *)c->align_status.p));
     if (out_crops) RFD_HIP(hipMemcpyAsync(out_crops, c->align_out.p, (size_t)n * crop, hipMemcpyDeviceToHost, c->stream));
     RFD_HIP(hipMemcpyAsync(status, c->align_status.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1818,21 +1760,11 @@ int rfd_align_faces_tensors(rfd_ctx *c, const rfd_image *imgs, int n, const floa
     RFD_CHECK_ARG(c && boxes && kps && found && status, "null argument");
     RFD_TRY(check_face_tensor_args(cfgs, k, tensors, 0));
     rfd_alignment_config def;
-    rfd_alignment_config_default(&def);
-    if (!cfg) cfg = &def;
-    if (cfg->out_w < 1 || cfg->out_h < 1 || cfg->out_w > 4096 || cfg->out_h > 4096) {
-        set_error("alignment output size %dx%d out of range", cfg->out_w, cfg->out_h);
-        return RFD_ERR_INVALID_ARG;
-    }
+    RFD_TRY(resolve_align_cfg(&cfg, &def));
     RFD_TRY(check_images(c, imgs, n));
     RFD_HIP(hipSetDevice(c->cfg.device_id));
-    std::vector<float> scales;
-    RFD_TRY(stage_frames(c, imgs, n, false, scales));
-    RFD_TRY(c->sel_out.reserve((size_t)n * 16 * sizeof(float)));
-    float *o = (float *)c->sel_out.p;
-    RFD_HIP(hipMemcpyAsync(o, boxes, (size_t)n * 5 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    RFD_HIP(hipMemcpyAsync(o + (size_t)n * 5, kps, (size_t)n * 10 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    RFD_HIP(hipMemcpyAsync(o + (size_t)n * 15, found, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    RFD_TRY(stage_frames(c, imgs, n, false));
+    RFD_TRY(sel_upload(c, n, boxes, kps, found));
     return align_tensors_to_host(c, n, cfg, out_crops, status, cfgs, k, tensors);
 }
 
@@ -1844,12 +1776,7 @@ int rfd_detect_select_align_tensors_batch(rfd_ctx *c, const rfd_image *imgs, int
     RFD_CHECK_ARG(c && status, "null argument");
     RFD_TRY(check_face_tensor_args(cfgs, k, tensors, 0));
     rfd_alignment_config def;
-    rfd_alignment_config_default(&def);
-    if (!align_cfg) align_cfg = &def;
-    if (align_cfg->out_w < 1 || align_cfg->out_h < 1 || align_cfg->out_w > 4096 || align_cfg->out_h > 4096) {
-        set_error("alignment output size %dx%d out of range", align_cfg->out_w, align_cfg->out_h);
-        return RFD_ERR_INVALID_ARG;
-    }
+    RFD_TRY(resolve_align_cfg(&align_cfg, &def));
     RFD_TRY(rfd_detect_select_batch(c, imgs, n, sel_cfg, is_enroll, out_box, out_kps, found));
     return align_tensors_to_host(c, n, align_cfg, out_crops, status, cfgs, k, tensors);
 }
@@ -1861,7 +1788,7 @@ int rfd_detect_faces_device(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_
     RFD_CHECK_ARG(c && out && out->box && out->kps && out->found && out->status, "null argument");
     RFD_TRY(check_face_tensor_args(cfgs, k, out->tensors, 0));
     RFD_TRY(check_images(c, imgs, n));
-    rfd_dets dev = {(float *)c->out_boxes.p, (float *)c->out_lmk.p, (int32_t *)c->out_count.p, (int32_t *)c->out_total.p};
+    rfd_dets dev = own_slabs(c);
     RFD_TRY(detect_impl(c, imgs, n, &dev, /*outputs stay on the device*/ true, /*async*/ 1, /*frames on device*/ true));
     std::vector<int> hh(n), ww(n);
     for (int i = 0; i < n; ++i) { hh[i] = imgs[i].height; ww[i] = imgs[i].width; }
@@ -1874,18 +1801,23 @@ int rfd_detect_faces_device(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_
 }
 
 // ---- after the two models: quality decision rule (face_quality.rs:159-168), embedding normalisation (utils.rs:148-154) ----
-int rfd_quality_decide_device(rfd_ctx *c, const float *logits, int n, int classes, float threshold, float *score, int32_t *klass)
+static int check_quality_args(const rfd_ctx *c, const float *logits, int n, int classes, const float *score, const int32_t *klass)
 {
     RFD_CHECK_ARG(c && logits && score && klass, "null argument");
     RFD_CHECK_ARG(n >= 1 && classes >= 1, "n < 1 or classes < 1");
+    return RFD_OK;
+}
+
+int rfd_quality_decide_device(rfd_ctx *c, const float *logits, int n, int classes, float threshold, float *score, int32_t *klass)
+{
+    RFD_TRY(check_quality_args(c, logits, n, classes, score, klass));
     RFD_HIP(hipSetDevice(c->cfg.device_id));
     return launch_quality_decide(logits, n, classes, threshold, score, klass, c->stream);
 }
 
 int rfd_quality_decide(rfd_ctx *c, const float *logits, int n, int classes, float threshold, float *score, int32_t *klass)
 {
-    RFD_CHECK_ARG(c && logits && score && klass, "null argument");
-    RFD_CHECK_ARG(n >= 1 && classes >= 1, "n < 1 or classes < 1");
+    RFD_TRY(check_quality_args(c, logits, n, classes, score, klass));
     RFD_HIP(hipSetDevice(c->cfg.device_id));
     const size_t in_bytes = (size_t)n * classes * sizeof(float);
     RFD_TRY(c->face_io[0].reserve(in_bytes));
@@ -1905,18 +1837,23 @@ int rfd_quality_decide(rfd_ctx *c, const float *logits, int n, int classes, floa
     return RFD_OK;
 }
 
-int rfd_normalize_embeddings_device(rfd_ctx *c, const float *emb, int n, int dim, float *out)
+static int check_normalize_args(const rfd_ctx *c, const float *emb, int n, int dim, const float *out)
 {
     RFD_CHECK_ARG(c && emb && out, "null argument");
     RFD_CHECK_ARG(n >= 1 && dim >= 1, "n < 1 or dim < 1");
+    return RFD_OK;
+}
+
+int rfd_normalize_embeddings_device(rfd_ctx *c, const float *emb, int n, int dim, float *out)
+{
+    RFD_TRY(check_normalize_args(c, emb, n, dim, out));
     RFD_HIP(hipSetDevice(c->cfg.device_id));
     return launch_l2_normalize(emb, n, dim, out, c->stream);
 }
 
 int rfd_normalize_embeddings(rfd_ctx *c, const float *emb, int n, int dim, float *out)
 {
-    RFD_CHECK_ARG(c && emb && out, "null argument");
-    RFD_CHECK_ARG(n >= 1 && dim >= 1, "n < 1 or dim < 1");
+    RFD_TRY(check_normalize_args(c, emb, n, dim, out));
     RFD_HIP(hipSetDevice(c->cfg.device_id));
     const size_t bytes = (size_t)n * dim * sizeof(float);
     RFD_TRY(c->face_io[0].reserve(bytes));
@@ -1968,38 +1905,15 @@ static int liveness_enqueue(rfd_ctx *c, const rfd_image *imgs, int n, bool frame
                             int32_t *d_status)
 {
     const size_t B = (size_t)c->cfg.max_batch_size;
-    for (int i = 0; i < rfd_ctx::kRing; ++i) { // first call on this context
-        if (!c->pin_live[i]) RFD_HIP(hipHostMalloc((void **)&c->pin_live[i], B * sizeof(LiveImage)));
-        if (!c->pin_live_done[i]) RFD_HIP(hipEventCreateWithFlags(&c->pin_live_done[i], hipEventDisableTiming));
-    }
+    RFD_TRY(c->live_ring.ensure(B * sizeof(LiveImage))); // first call on this context
     RFD_TRY(c->live_imgs.reserve(B * sizeof(LiveImage)));
     RFD_TRY(c->live_geo.reserve(B * kMaxFaceTensors * sizeof(LiveRoi)));
-    const int slot = c->pin_live_next;
-    c->pin_live_next = (c->pin_live_next + 1) % rfd_ctx::kRing;
-    RFD_HIP(hipEventSynchronize(c->pin_live_done[slot])); // the copy that last used this slot has run
-    LiveImage *li = c->pin_live[slot];
-    if (!frames_on_device) {
-        size_t total = 0;
-        for (int i = 0; i < n; ++i) total += (size_t)imgs[i].height * imgs[i].width * 3;
-        RFD_TRY(c->staging.reserve(total));
-    }
-    size_t off = 0;
-    for (int i = 0; i < n; ++i) {
-        li[i].h = imgs[i].height; li[i].w = imgs[i].width;
-        if (frames_on_device) {
-            li[i].src = imgs[i].data;
-            li[i].stride = (long long)imgs[i].stride;
-        } else {
-            uint8_t *dst = (uint8_t *)c->staging.p + off;
-            const size_t row = (size_t)imgs[i].width * 3;
-            RFD_HIP(hipMemcpy2DAsync(dst, row, imgs[i].data, (size_t)imgs[i].stride, row, imgs[i].height, hipMemcpyHostToDevice, c->stream));
-            li[i].src = dst;
-            li[i].stride = (long long)row;
-            off += row * imgs[i].height;
-        }
-    }
+    LiveImage *li;
+    RFD_TRY(c->live_ring.acquire(&li));
+    for (int i = 0; i < n; ++i) { li[i].h = imgs[i].height; li[i].w = imgs[i].width; }
+    RFD_TRY(place_frames(c, imgs, n, frames_on_device, li));
     RFD_HIP(hipMemcpyAsync(c->live_imgs.p, li, n * sizeof(LiveImage), hipMemcpyHostToDevice, c->stream));
-    RFD_HIP(hipEventRecord(c->pin_live_done[slot], c->stream));
+    RFD_TRY(c->live_ring.record(c->stream));
     LiveParams p;
     memset(&p, 0, sizeof p);
     p.imgs = (const LiveImage *)c->live_imgs.p;
@@ -2072,13 +1986,20 @@ int rfd_liveness_tensors(rfd_ctx *c, const rfd_image *imgs, int n, const float *
     return check_nms_flag(c);
 }
 
-int rfd_liveness_decide_device(rfd_ctx *c, const float *const *logits, int k, int n, int classes, const float *weights,
-                               float threshold, float *score, int32_t *live)
+static int check_liveness_decide_args(const rfd_ctx *c, const float *const *logits, int k, int n, int classes, const float *weights,
+                                      const float *score, const int32_t *live)
 {
     RFD_CHECK_ARG(c && logits && weights && score && live, "null argument");
     RFD_CHECK_ARG(k >= 1 && n >= 1 && classes >= 2, "k < 1, n < 1 or classes < 2");
     for (int j = 0; j < k; ++j)
         if (!logits[j]) { set_error("invalid argument: logits pointer %d is null", j); return RFD_ERR_INVALID_ARG; }
+    return RFD_OK;
+}
+
+int rfd_liveness_decide_device(rfd_ctx *c, const float *const *logits, int k, int n, int classes, const float *weights,
+                               float threshold, float *score, int32_t *live)
+{
+    RFD_TRY(check_liveness_decide_args(c, logits, k, n, classes, weights, score, live));
     RFD_HIP(hipSetDevice(c->cfg.device_id));
     if (k > kLiveDecideChunk) RFD_TRY(c->live_acc.reserve((size_t)n * 2 * sizeof(float)));
     for (int j0 = 0; j0 < k; j0 += kLiveDecideChunk) {
@@ -2094,10 +2015,7 @@ int rfd_liveness_decide_device(rfd_ctx *c, const float *const *logits, int k, in
 int rfd_liveness_decide(rfd_ctx *c, const float *const *logits, int k, int n, int classes, const float *weights, float threshold,
                         float *score, int32_t *live)
 {
-    RFD_CHECK_ARG(c && logits && weights && score && live, "null argument");
-    RFD_CHECK_ARG(k >= 1 && n >= 1 && classes >= 2, "k < 1, n < 1 or classes < 2");
-    for (int j = 0; j < k; ++j)
-        if (!logits[j]) { set_error("invalid argument: logits pointer %d is null", j); return RFD_ERR_INVALID_ARG; }
+    RFD_TRY(check_liveness_decide_args(c, logits, k, n, classes, weights, score, live));
     RFD_HIP(hipSetDevice(c->cfg.device_id));
     const size_t one = (size_t)n * classes;
     // logits [k][n][classes] | weights [n][k] | score [n] | live [n]
@@ -2172,7 +2090,28 @@ static int gallery_host_stage(rfd_gallery *g)
 {
     if (g->pin) return RFD_OK;
     RFD_TRY(g->stage.reserve(rfd_gallery::kStageBytes));
-    RFD_HIP(hipHostMalloc(&g->pin, rfd_gallery::kStageBytes, hipHostMallocDefault));
+    return g->pin.alloc(rfd_gallery::kStageBytes);
+}
+
+// The host forms move rows of `dim` floats through the one staging buffer, in chunks that fit it; a chunk has left the buffer
+// (the stream is drained) before the next one enters.  With `src`, rows [first, first + count) of it are copied in before
+// `op(first, count)` is enqueued; with `dst`, op fills the device buffer and the rows are copied out behind it.
+static int gallery_staged(rfd_gallery *g, const float *src, float *dst, int n, const std::function<int(int, int)> &op)
+{
+    RFD_TRY(gallery_host_stage(g));
+    const int chunk = (int)(rfd_gallery::kStageBytes / ((size_t)g->dim * sizeof(float)));
+    for (int i = 0; i < n; i += chunk) {
+        const int m = std::min(chunk, n - i);
+        const size_t bytes = (size_t)m * g->dim * sizeof(float);
+        if (src) {
+            memcpy(g->pin, src + (size_t)i * g->dim, bytes);
+            RFD_HIP(hipMemcpyAsync(g->stage.p, g->pin, bytes, hipMemcpyHostToDevice, g->ctx->stream));
+        }
+        RFD_TRY(op(i, m));
+        if (dst) RFD_HIP(hipMemcpyAsync(g->pin, g->stage.p, bytes, hipMemcpyDeviceToHost, g->ctx->stream));
+        RFD_HIP(hipStreamSynchronize(g->ctx->stream));
+        if (dst) memcpy(dst + (size_t)i * g->dim, g->pin, bytes);
+    }
     return RFD_OK;
 }
 
@@ -2251,18 +2190,14 @@ static int gallery_check_rows(const rfd_gallery *g, const int32_t *rows, int n)
 static int gallery_edit(rfd_gallery *g, const int32_t *rows, const float *emb, int n)
 {
     constexpr int kEdit = rfd_gallery::kEditRows;
-    for (int i = 0; i < rfd_gallery::kRing; ++i) { // first call on this gallery
-        if (!g->pin_edit[i]) RFD_HIP(hipHostMalloc((void **)&g->pin_edit[i], (size_t)3 * kEdit * sizeof(int32_t), hipHostMallocDefault));
-        if (!g->pin_edit_done[i]) RFD_HIP(hipEventCreateWithFlags(&g->pin_edit_done[i], hipEventDisableTiming));
-    }
+    RFD_TRY(g->edit_ring.ensure((size_t)3 * kEdit * sizeof(int32_t))); // first call on this gallery
     RFD_TRY(g->edit.reserve((size_t)3 * kEdit * sizeof(int32_t)));
     RFD_TRY(gallery_live_sync(g));
     for (int at = 0; at < n; at += kEdit) {
         const int m = std::min(kEdit, n - at);
-        const int slot = g->pin_edit_next;
-        g->pin_edit_next = (g->pin_edit_next + 1) % rfd_gallery::kRing;
-        RFD_HIP(hipEventSynchronize(g->pin_edit_done[slot])); // the copy that last used this slot has run
-        int32_t *list = g->pin_edit[slot], *blk = list + m;
+        int32_t *list;
+        RFD_TRY(g->edit_ring.acquire(&list));
+        int32_t *blk = list + m;
         for (int i = 0; i < m; ++i) {
             const int r = rows[at + i];
             list[i] = r;
@@ -2277,7 +2212,7 @@ static int gallery_edit(rfd_gallery *g, const int32_t *rows, const float *emb, i
         int32_t *word = blk + nb;
         for (int j = 0; j < nb; ++j) word[j] = g->live_words[blk[j]];
         RFD_HIP(hipMemcpyAsync(g->edit.p, list, (size_t)(m + 2 * nb) * sizeof(int32_t), hipMemcpyHostToDevice, g->ctx->stream));
-        RFD_HIP(hipEventRecord(g->pin_edit_done[slot], g->ctx->stream));
+        RFD_TRY(g->edit_ring.record(g->ctx->stream));
         const int32_t *d = (const int32_t *)g->edit.p;
         RFD_TRY(launch_gallery_put(emb ? emb + (size_t)at * g->dim : nullptr, d, m, g->dim, (bf16_t *)g->store.p, d + m, d + m + nb, nb, (uint16_t *)g->live.p,
                                    g->ctx->stream));
@@ -2310,21 +2245,21 @@ int rfd_gallery_create(rfd_ctx *c, int dim, int capacity, rfd_gallery **out)
     RFD_CHECK_ARG(dim >= 32 && dim <= 1024 && dim % 32 == 0, "dim must be a multiple of 32 in 32..1024");
     RFD_CHECK_ARG(capacity >= 1 && capacity <= (1 << 30), "capacity out of range");
     RFD_HIP(hipSetDevice(c->cfg.device_id));
-    rfd_gallery *g = new rfd_gallery();
+    std::unique_ptr<rfd_gallery> g(new rfd_gallery()); // an early return frees whatever was built so far
     g->ctx = c; g->dim = dim; g->capacity = capacity;
     g->groups_max = 2 * device_cus(); // two workgroups of four waves per CU: what the scan's registers admit
     const size_t bytes = (size_t)ceil_div(capacity, 16) * 16 * dim * sizeof(bf16_t);
-    int st = g->store.reserve(bytes);
-    if (st == RFD_OK) st = g->ws.reserve((size_t)g->groups_max * kGalleryMaxQueries * RFD_GALLERY_MAX_K * sizeof(uint2));
+    RFD_TRY(g->store.reserve(bytes));
+    RFD_TRY(g->ws.reserve((size_t)g->groups_max * kGalleryMaxQueries * RFD_GALLERY_MAX_K * sizeof(uint2)));
     const size_t live_bytes = (size_t)ceil_div(ceil_div(capacity, 16), 2) * 2 * sizeof(uint16_t); // the masked scan loads aligned pairs of words
-    if (st == RFD_OK) st = g->live.reserve(live_bytes);
+    RFD_TRY(g->live.reserve(live_bytes));
     // rows that were never added read as zeros (the tail of the last block is scored, then masked by its row index)
-    if (st == RFD_OK && (hipMemsetAsync(g->store.p, 0, bytes, c->stream) != hipSuccess || hipMemsetAsync(g->live.p, 0, live_bytes, c->stream) != hipSuccess)) {
+    if (hipMemsetAsync(g->store.p, 0, bytes, c->stream) != hipSuccess || hipMemsetAsync(g->live.p, 0, live_bytes, c->stream) != hipSuccess) {
         set_error("hipMemsetAsync of the gallery failed");
-        st = RFD_ERR_HIP;
+        (void)hipStreamSynchronize(c->stream); // a fill that was enqueued has run before its buffer is freed
+        return RFD_ERR_HIP;
     }
-    if (st != RFD_OK) { rfd_gallery_destroy(g); return st; }
-    *out = g;
+    *out = g.release();
     return RFD_OK;
 }
 
@@ -2333,12 +2268,6 @@ void rfd_gallery_destroy(rfd_gallery *g)
     if (!g) return;
     (void)hipSetDevice(g->ctx->cfg.device_id);
     (void)hipStreamSynchronize(g->ctx->stream);
-    g->store.release(); g->ws.release(); g->stage.release(); g->live.release(); g->edit.release();
-    if (g->pin) (void)hipHostFree(g->pin);
-    for (int i = 0; i < rfd_gallery::kRing; ++i) {
-        if (g->pin_edit[i]) (void)hipHostFree(g->pin_edit[i]);
-        if (g->pin_edit_done[i]) (void)hipEventDestroy(g->pin_edit_done[i]);
-    }
     delete g;
 }
 
@@ -2385,16 +2314,9 @@ int rfd_gallery_add(rfd_gallery *g, const float *emb, int n, int *first_row)
     RFD_TRY(gallery_check_room(g, n));
     RFD_TRY(gallery_check_finite(emb, n, g->dim, "row"));
     RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
-    RFD_TRY(gallery_host_stage(g));
-    const int chunk = (int)(rfd_gallery::kStageBytes / ((size_t)g->dim * sizeof(float)));
-    for (int i = 0; i < n; i += chunk) { // one staging buffer: a chunk has left it before the next one is copied in
-        const int m = std::min(chunk, n - i);
-        const size_t bytes = (size_t)m * g->dim * sizeof(float);
-        memcpy(g->pin, emb + (size_t)i * g->dim, bytes);
-        RFD_HIP(hipMemcpyAsync(g->stage.p, g->pin, bytes, hipMemcpyHostToDevice, g->ctx->stream));
-        RFD_TRY(launch_gallery_add((const float *)g->stage.p, m, g->dim, g->rows + i, (bf16_t *)g->store.p, g->ctx->stream));
-        RFD_HIP(hipStreamSynchronize(g->ctx->stream));
-    }
+    RFD_TRY(gallery_staged(g, emb, nullptr, n, [&](int i, int m) {
+        return launch_gallery_add((const float *)g->stage.p, m, g->dim, g->rows + i, (bf16_t *)g->store.p, g->ctx->stream);
+    }));
     gallery_mark_live(g, g->rows, g->rows + n);
     g->rows += n;
     return RFD_OK;
@@ -2407,17 +2329,9 @@ int rfd_gallery_get_rows(rfd_gallery *g, int row0, int n, float *out)
     RFD_CHECK_ARG(out, "out is null");
     RFD_CHECK_ARG(row0 >= 0 && n <= g->rows - row0, "rows [row0, row0 + n) are not all in the gallery");
     RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
-    RFD_TRY(gallery_host_stage(g));
-    const int chunk = (int)(rfd_gallery::kStageBytes / ((size_t)g->dim * sizeof(float)));
-    for (int i = 0; i < n; i += chunk) {
-        const int m = std::min(chunk, n - i);
-        const size_t bytes = (size_t)m * g->dim * sizeof(float);
-        RFD_TRY(launch_gallery_get((const bf16_t *)g->store.p, row0 + i, m, g->dim, (float *)g->stage.p, g->ctx->stream));
-        RFD_HIP(hipMemcpyAsync(g->pin, g->stage.p, bytes, hipMemcpyDeviceToHost, g->ctx->stream));
-        RFD_HIP(hipStreamSynchronize(g->ctx->stream));
-        memcpy(out + (size_t)i * g->dim, g->pin, bytes);
-    }
-    return RFD_OK;
+    return gallery_staged(g, nullptr, out, n, [&](int i, int m) {
+        return launch_gallery_get((const bf16_t *)g->store.p, row0 + i, m, g->dim, (float *)g->stage.p, g->ctx->stream);
+    });
 }
 
 int rfd_gallery_search_device(rfd_gallery *g, const float *queries, int n, int k, float *scores, int32_t *rows, int async)
@@ -2499,17 +2413,7 @@ int rfd_gallery_replace(rfd_gallery *g, const int32_t *rows, const float *emb, i
     RFD_TRY(gallery_check_distinct(rows, n));
     RFD_TRY(gallery_check_finite(emb, n, g->dim, "row"));
     RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
-    RFD_TRY(gallery_host_stage(g));
-    const int chunk = (int)(rfd_gallery::kStageBytes / ((size_t)g->dim * sizeof(float)));
-    for (int i = 0; i < n; i += chunk) { // one staging buffer: a chunk has left it before the next one is copied in
-        const int m = std::min(chunk, n - i);
-        const size_t bytes = (size_t)m * g->dim * sizeof(float);
-        memcpy(g->pin, emb + (size_t)i * g->dim, bytes);
-        RFD_HIP(hipMemcpyAsync(g->stage.p, g->pin, bytes, hipMemcpyHostToDevice, g->ctx->stream));
-        RFD_TRY(gallery_edit(g, rows + i, (const float *)g->stage.p, m));
-        RFD_HIP(hipStreamSynchronize(g->ctx->stream));
-    }
-    return RFD_OK;
+    return gallery_staged(g, emb, nullptr, n, [&](int i, int m) { return gallery_edit(g, rows + i, (const float *)g->stage.p, m); });
 }
 
 int rfd_gallery_live(const rfd_gallery *g, int *live_rows)
@@ -2561,7 +2465,7 @@ int rfd_gallery_save(rfd_gallery *g, const char *path)
             set_error("copying rows %d..%d of the gallery to the host failed", i, i + m - 1);
             st = RFD_ERR_HIP;
         }
-        if (st == RFD_OK) ok = gallery_file_write_values(f, (const uint16_t *)g->pin, (size_t)m * g->dim);
+        if (st == RFD_OK) ok = gallery_file_write_values(f, (const uint16_t *)g->pin.p, (size_t)m * g->dim);
     }
     ok = (fclose(f) == 0) && ok;
     if (st == RFD_OK && !ok) { set_error("short write to %s", tmp.c_str()); st = RFD_ERR_IO; }
@@ -2583,7 +2487,7 @@ int rfd_gallery_load(rfd_ctx *c, const char *path, int capacity, rfd_gallery **o
     RFD_TRY(rfd_gallery_create(c, r.dim, capacity, &g));
     int st = gallery_host_stage(g);
     const int chunk = (int)(rfd_gallery::kStageBytes / ((size_t)r.dim * sizeof(bf16_t)));
-    uint16_t *h = (uint16_t *)g->pin;
+    uint16_t *h = (uint16_t *)g->pin.p;
     for (int i = 0; st == RFD_OK && i < r.rows; i += chunk) {
         const int m = std::min(chunk, r.rows - i);
         const size_t bytes = (size_t)m * r.dim * sizeof(bf16_t);
@@ -2659,10 +2563,10 @@ static int jpeg_stage_alloc(rfd_ctx *c)
         return RFD_ERR_CAPACITY;
     }
     const size_t bytes = B * sizeof(JpegFrame) + B * blocks * (sizeof(uint32_t) + 64 * sizeof(int16_t));
-    if (!c->jpeg_pin_done) RFD_HIP(hipEventCreateWithFlags(&c->jpeg_pin_done, hipEventDisableTiming));
+    RFD_TRY(c->jpeg_pin_done.create());
     RFD_TRY(c->jpeg_dev.reserve(bytes));
     RFD_TRY(c->jpeg_planes.reserve(B * blocks * 64));
-    RFD_HIP(hipHostMalloc(&c->jpeg_pin, bytes, hipHostMallocDefault));
+    RFD_TRY(c->jpeg_pin.alloc(bytes));
     c->jpeg_blocks_max = blocks;
     return RFD_OK;
 }
@@ -2675,10 +2579,7 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
     RFD_CHECK_ARG(n >= 0, "n < 0");
     if (n == 0) return RFD_OK;
     RFD_CHECK_ARG(bytes && len && out, "null argument");
-    if (n > c->cfg.max_batch_size) {
-        set_error("batch of %d files exceeds max_batch_size %d", n, c->cfg.max_batch_size);
-        return RFD_ERR_CAPACITY;
-    }
+    RFD_TRY(check_batch(c, n, "batch of", " files"));
     std::unique_ptr<JpegHeader[]> hdr(new JpegHeader[(size_t)n]);
     for (int i = 0; i < n; ++i) {
         const int st = jpeg_parse_header(bytes[i], len[i], hdr[i]);
@@ -2698,7 +2599,7 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
     RFD_HIP(hipSetDevice(c->cfg.device_id));
     RFD_TRY(jpeg_stage_alloc(c));
     const size_t B = (size_t)c->cfg.max_batch_size;
-    JpegFrame *fr = (JpegFrame *)c->jpeg_pin;
+    JpegFrame *fr = (JpegFrame *)c->jpeg_pin.p;
     uint32_t *rec = (uint32_t *)(fr + B);
     int16_t *coef = (int16_t *)(rec + B * c->jpeg_blocks_max);
     RFD_HIP(hipEventSynchronize(c->jpeg_pin_done)); // the previous call's copies out of the staging have run
