@@ -580,7 +580,8 @@ RFD_API int64_t rfd_debug_gallery_offset(int dim, int row, int d);
  *      128, clamped to 0..255) into u8 component planes padded to whole MCUs; then libjpeg's fancy (triangle) chroma upsampling
  *      and its fixed-point YCbCr -> RGB tables, cropped to the image and stored as [H][W][3] u8 BGR at the caller's stride.
  *      Contract: the pixels equal libjpeg-turbo's defaults (JDCT_ISLOW, fancy upsampling) -- what cv::imdecode and Pillow return
- *      -- byte for byte (tests/test_jpeg_cpu.py pins the arithmetic against Pillow, tests/test_jpeg_gpu.py the kernels).  Edges
+ *      -- byte for byte (tests/test_jpeg_cpu.py pins the arithmetic against Pillow, tests/test_jpeg_gpu.py and
+ *      tests/test_jpeg_sweep_gpu.py the kernels).  Edges
  *      are part of it: horizontally the filter runs over the component's own ceil(W h / hmax) samples, vertically the first and
  *      the last real sample row stand in for the rows beyond them, and a chroma plane of one or two samples per row is
  *      replicated, not filtered (libjpeg's own rule).  Outside the contract: coefficients that no 8-bit image produces (IDCT

@@ -38,12 +38,16 @@ def _descale(x, n):
     return (x + (1 << (n - 1))) >> n
 
 
-def idct(coef):
-    """[blocks, 64] dequantised coefficients, natural order -> [blocks, 8, 8] u8 samples"""
+def idct_unclamped(coef):
+    """[blocks, 64] dequantised coefficients, natural order -> [blocks, 8, 8] i64 samples before the level shift and the clamp"""
     b = np.asarray(coef, np.int64).reshape(-1, 8, 8)
     ws = np.stack([_descale(v, _CONST_BITS - _PASS1_BITS) for v in _idct_1d([b[:, r, :] for r in range(8)])], 1)   # columns
-    out = np.stack([_descale(v, _CONST_BITS + _PASS1_BITS + 3) for v in _idct_1d([ws[:, :, k] for k in range(8)])], 2)  # rows
-    return np.clip(out + 128, 0, 255).astype(np.uint8)
+    return np.stack([_descale(v, _CONST_BITS + _PASS1_BITS + 3) for v in _idct_1d([ws[:, :, k] for k in range(8)])], 2)  # rows
+
+
+def idct(coef):
+    """[blocks, 64] dequantised coefficients, natural order -> [blocks, 8, 8] u8 samples"""
+    return np.clip(idct_unclamped(coef) + 128, 0, 255).astype(np.uint8)
 
 
 def geometry(width, height, sampling):

@@ -1,7 +1,8 @@
 """JPEG decode on the device (include/rfd.h, "JPEG decode": rfd_decode_jpeg_batch, rfd_decode_jpeg_batch_device) against the
 pixels libjpeg-turbo (Pillow) decoded from the same files, stored under tests/golden/jpeg/.  The bar is byte equality
 throughout: the contract is libjpeg's integer arithmetic, bit for bit.  tests/test_jpeg_cpu.py pins the host half and the
-arithmetic without a GPU; here the two kernels, the batching, the staging and the hand-over to the detector are under test."""
+arithmetic without a GPU; here the two kernels, the batching, the staging and the hand-over to the detector are under test.
+tests/test_jpeg_sweep_gpu.py sweeps the kernels over the geometries, tables and coefficients these 24 fixtures do not reach."""
 import ctypes as C
 import struct
 
