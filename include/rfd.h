@@ -596,7 +596,8 @@ RFD_API int64_t rfd_debug_gallery_offset(int dim, int row, int d);
  *      that was never defined, zero dimensions, a restart marker out of sequence, data that ends before the last MCU.  In both
  *      cases rfd_last_error() names the cause and the byte offset (and, in a batch, the frame), and NOTHING is enqueued for any
  *      frame of the call: every file is parsed and entropy-decoded before the first copy or kernel.  A file may end without EOI
- *      once its last MCU is complete (libjpeg warns and accepts).
+ *      once its last MCU is complete (libjpeg warns and accepts).  (RFD_JPEG_ENTROPY_DEVICE, below, runs its entropy kernel
+ *      before that point; it writes the context's own memory only, and no output frame of a refused call is written.)
  *      Divergence: a grey file gives B = G = R = Y in a 3-channel frame.  The reference decodes with IMREAD_UNCHANGED, which
  *      keeps such a file at one channel, and its detector then fails on it (at_2d::<Vec3b>, face_detection.rs:226). ---- */
 typedef enum rfd_jpeg_sampling { RFD_JPEG_GRAY = 0, RFD_JPEG_444 = 1, RFD_JPEG_422 = 2, RFD_JPEG_420 = 3 } rfd_jpeg_sampling;
@@ -636,6 +637,43 @@ RFD_API int rfd_set_decode_threads(rfd_ctx *ctx, int threads);
  * only) saturates.  *blocks = the file's block count, also when it exceeds cap_blocks (then RFD_ERR_CAPACITY, nothing written);
  * out may be NULL when cap_blocks is 0. */
 RFD_API int rfd_debug_jpeg_coefficients(const uint8_t *bytes, size_t len, int16_t *out, size_t cap_blocks, size_t *blocks);
+
+/* ---- JPEG decode, entropy decoding on the device (opt-in).  A file with a restart interval (DRI) of R MCUs is cut into pieces
+ *      that decode independently: after every R MCUs the bit stream is byte-aligned, a RSTn marker follows and every DC
+ *      predictor is zero again.  In RFD_JPEG_ENTROPY_DEVICE mode the host only finds the markers of such a file (a pre-scan, no
+ *      Huffman decoding); the file's entropy-coded bytes cross PCIe instead of its coefficients, and one device thread per
+ *      restart interval decodes them straight into the pools the inverse-DCT kernel reads.
+ *      Eligible is a frame of a DEVICE-mode call whose file has 1 <= R <= 128 MCUs, whose scan holds exactly ceil(MCUs / R)
+ *      intervals with the markers in the sequence RST0, RST1, .. RST7, RST0, .., and whose scan bytes fit the staging (allocated
+ *      by the first DEVICE-mode call, sized by max_src_w, max_src_h and max_batch_size: DESIGN.md section 5; a context that never
+ *      selects the mode allocates nothing for it).  Every other frame -- no DRI, a longer interval, any structural oddity -- is
+ *      decoded by the host threads exactly as in HOST mode, while the entropy kernel runs.
+ *      Strict acceptance: the device decoder refuses a frame unless every interval decodes to EXACTLY its bytes (after the
+ *      interval's last MCU fewer than 8 bits and no byte are unread), besides a code that is in no table, a coefficient index
+ *      above 63, a zero run past 64 and the use of a bit beyond the interval.  That is a strict subset of what the lenient host
+ *      decoder accepts (garbage in front of a restart marker, say), and on it the coefficients are identical.  A refused frame
+ *      is decoded again by the host threads, which accept it or give the call its status and message.  So status, message,
+ *      pixels and the promise that no output frame is written when any file is refused are the same in both modes for every
+ *      input; only rfd_jpeg_last_paths tells the modes apart.
+ *      async: the call enqueues the entropy kernel, copies one status word per frame back and waits for that copy.  In DEVICE
+ *      mode a call with async != 0 therefore returns after the entropy kernel (and everything enqueued on the context's stream
+ *      before it) has finished; it still returns before the inverse-DCT and colour kernels have run. ---- */
+typedef enum rfd_jpeg_entropy { RFD_JPEG_ENTROPY_HOST = 0, RFD_JPEG_ENTROPY_DEVICE = 1 } rfd_jpeg_entropy;
+/* HOST is the default; any other value than the two: RFD_ERR_INVALID_ARG.  May be changed between calls. */
+RFD_API int rfd_set_jpeg_entropy(rfd_ctx *ctx, int mode);
+/* How each frame of the last rfd_decode_jpeg_batch* call was entropy-decoded: 0 on the host because it was not eligible (always,
+ * in HOST mode), 1 on the device, 2 on the host after the device refused it.  *n = the frames of that call (0 before the first),
+ * also when n > cap (then RFD_ERR_CAPACITY, nothing written).  n may be NULL. */
+RFD_API int rfd_jpeg_last_paths(rfd_ctx *ctx, int32_t *path, int cap, int *n);
+/* Test hook, host only, no context: the marker pre-scan.  Interval k is bytes [begin[k], end[k]) of the file; end is the position
+ * of the first 0xFF of the marker sequence that closes the interval (fill bytes and the marker are excluded).  *count = the
+ * intervals the file must have, also when that exceeds cap (then RFD_ERR_CAPACITY).  RFD_ERR_UNSUPPORTED with a message when the
+ * file is not eligible by its structure (no DRI, R above the limit, another number of intervals, markers out of sequence); the
+ * header's own status where the header is refused. */
+RFD_API int rfd_debug_jpeg_intervals(const uint8_t *bytes, size_t len, uint32_t *begin, uint32_t *end, size_t cap, size_t *count);
+/* Test hook: rfd_debug_jpeg_coefficients with the quantised coefficients taken from the device entropy kernel, whatever the
+ * context's mode.  Never falls back: RFD_ERR_UNSUPPORTED when the file is not eligible or the device refused it. */
+RFD_API int rfd_debug_jpeg_coefficients_device(rfd_ctx *ctx, const uint8_t *bytes, size_t len, int16_t *out, size_t cap_blocks, size_t *blocks);
 
 /* ---- introspection ---- */
 RFD_API int rfd_get_stats(rfd_ctx *ctx, rfd_stats *stats);

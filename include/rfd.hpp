@@ -420,6 +420,19 @@ inline void decode_jpeg_device(RetinaFaceDetection &det, const std::vector<std::
     for (std::size_t i = 0; i < files.size(); ++i) { ptrs[i] = files[i].data(); lens[i] = files[i].size(); }
     check(rfd_decode_jpeg_batch_device(det.raw(), ptrs.data(), lens.data(), (int)files.size(), frames.data(), async ? 1 : 0));
 }
+// RFD_JPEG_ENTROPY_DEVICE: files with a restart interval are Huffman-decoded on the device (rfd.h, "entropy decoding on the
+// device"); every other file, and everything in RFD_JPEG_ENTROPY_HOST (the default), on the host threads
+inline void set_jpeg_entropy(RetinaFaceDetection &det, rfd_jpeg_entropy mode) { check(rfd_set_jpeg_entropy(det.raw(), (int)mode)); }
+// per frame of the last decode call: 0 host, 1 device, 2 host after the device refused the frame
+inline std::vector<int32_t> jpeg_last_paths(RetinaFaceDetection &det)
+{
+    int n = 0;
+    const int st = rfd_jpeg_last_paths(det.raw(), nullptr, 0, &n);
+    if (st != RFD_ERR_CAPACITY) check(st);
+    std::vector<int32_t> out((std::size_t)n);
+    check(rfd_jpeg_last_paths(det.raw(), out.data(), n, &n));
+    return out;
+}
 
 } // namespace rfd
 #endif

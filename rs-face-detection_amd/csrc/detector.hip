@@ -209,6 +209,16 @@ struct rfd_ctx {
     Pinned<char> jpeg_pin;
     Event jpeg_pin_done;
     DevBuf jpeg_dev, jpeg_planes, jpeg_out; // jpeg_out: the device frames of the host-output form
+    // Entropy decoding on the device (rfd_set_jpeg_entropy), all allocated by the first decode call in that mode.  jpeg_ent_pin and
+    // its device twin jpeg_ent_dev: JpegEntropyFrame [B] | status u32 [B] | interval tables u32 [2 * B * jpeg_intervals_max] |
+    // scan bytes [jpeg_scan_pool].  The copies out of jpeg_ent_pin are covered by jpeg_pin_done as well; jpeg_ent_done: the
+    // status words of the last entropy launch have arrived.
+    int jpeg_entropy = RFD_JPEG_ENTROPY_HOST;
+    size_t jpeg_intervals_max = 0, jpeg_scan_pool = 0; // MCUs of the largest frame at 8 x 8 per MCU; bytes of the scan pool
+    Pinned<char> jpeg_ent_pin;
+    DevBuf jpeg_ent_dev;
+    Event jpeg_ent_done;
+    std::vector<int32_t> jpeg_paths; // rfd_jpeg_last_paths
     // pipelined host entry (rfd_submit_batch / rfd_collect_batch): two slots, H2D on its own stream
     struct PipeSlot {
         DevBuf frames, imgs, scale, ob, ol, oc, ot;
@@ -2571,8 +2581,143 @@ static int jpeg_stage_alloc(rfd_ctx *c)
     return RFD_OK;
 }
 
+// ---- entropy decoding on the device (rfd_set_jpeg_entropy): csrc/jpeg_entropy.h, csrc/kernels_jpeg_entropy.hip ----
+constexpr size_t kJpegScanFloor = 64 * 1024, kJpegScanBytesPerBlock = 32;
+
+struct JpegEntLayout { size_t status, ivl, scan, bytes; }; // byte offsets in jpeg_ent_pin / jpeg_ent_dev
+static JpegEntLayout jpeg_ent_layout(const rfd_ctx *c)
+{
+    const size_t B = (size_t)c->cfg.max_batch_size;
+    JpegEntLayout l;
+    l.status = B * sizeof(JpegEntropyFrame);
+    l.ivl = l.status + B * sizeof(uint32_t);
+    l.scan = l.ivl + 2 * B * c->jpeg_intervals_max * sizeof(uint32_t);
+    l.bytes = l.scan + c->jpeg_scan_pool;
+    return l;
+}
+
+// first decode call in DEVICE mode (after jpeg_stage_alloc): the page-locked scan / interval staging and its device twin
+static int jpeg_entropy_stage_alloc(rfd_ctx *c)
+{
+    if (c->jpeg_ent_pin) return RFD_OK;
+    const size_t B = (size_t)c->cfg.max_batch_size;
+    c->jpeg_intervals_max = (size_t)ceil_div(c->cfg.max_src_w, 8) * (size_t)ceil_div(c->cfg.max_src_h, 8);
+    // per frame half a byte per coefficient slot of the largest frame, at least 64 KiB; positions in the pool are 32-bit
+    c->jpeg_scan_pool = std::min(B * std::max(kJpegScanFloor, kJpegScanBytesPerBlock * c->jpeg_blocks_max), (size_t)0xffff0000u);
+    const JpegEntLayout l = jpeg_ent_layout(c);
+    RFD_TRY(c->jpeg_ent_done.create());
+    RFD_TRY(c->jpeg_ent_dev.reserve(l.bytes));
+    RFD_TRY(c->jpeg_ent_pin.alloc(l.bytes));
+    return RFD_OK;
+}
+
+// which frames of a call go to the entropy kernel, and their slices of the two pools
+struct JpegEntropyPlan {
+    std::vector<char> staged;             // per frame: its intervals and scan bytes are in the staging
+    std::vector<uint32_t> scan0, ivl0, nint;
+    size_t scan_used = 0, ivl_used = 0;   // bytes; u32 words
+    explicit JpegEntropyPlan(int n) : staged((size_t)n, 0), scan0((size_t)n, 0), ivl0((size_t)n, 0), nint((size_t)n, 0) {}
+};
+
+// Serial: hands frame i its slices when its header allows the interval path and its scan fits what is left of the pool.
+static bool jpeg_entropy_place(rfd_ctx *c, JpegEntropyPlan &pl, int i, const JpegHeader &h, size_t len, char *msg, size_t msg_cap)
+{
+    size_t want = 0;
+    if (!jpeg_device_eligible(nullptr, len, h, nullptr, nullptr, 0, &want, msg, msg_cap)) return false; // cap 0: the header's part of the rule only
+    const size_t bytes = len - h.scan, B = (size_t)c->cfg.max_batch_size;
+    if (pl.scan_used + bytes > c->jpeg_scan_pool || pl.ivl_used + 2 * want > 2 * B * c->jpeg_intervals_max) {
+        snprintf(msg, msg_cap, "not eligible for device entropy decoding: %zu scan bytes in %zu intervals do not fit the staging", bytes, want);
+        return false;
+    }
+    pl.scan0[(size_t)i] = (uint32_t)pl.scan_used; pl.ivl0[(size_t)i] = (uint32_t)pl.ivl_used; pl.nint[(size_t)i] = (uint32_t)want;
+    pl.scan_used += (bytes + 15) & ~(size_t)15;
+    pl.ivl_used += 2 * want;
+    pl.staged[(size_t)i] = 1;
+    return true;
+}
+
+// Any thread, a placed frame: the pre-scan straight into the frame's interval table, the scan bytes into its slice of the pool.
+static bool jpeg_entropy_stage_frame(rfd_ctx *c, JpegEntropyPlan &pl, int i, const uint8_t *d, size_t len, const JpegHeader &h, char *msg, size_t msg_cap)
+{
+    const JpegEntLayout l = jpeg_ent_layout(c);
+    const size_t nint = pl.nint[(size_t)i];
+    uint32_t *iv = (uint32_t *)(c->jpeg_ent_pin.p + l.ivl) + pl.ivl0[(size_t)i];
+    size_t want = 0;
+    if (!jpeg_device_eligible(d, len, h, iv, iv + nint, nint, &want, msg, msg_cap)) { pl.staged[(size_t)i] = 0; return false; }
+    memcpy(c->jpeg_ent_pin.p + l.scan + pl.scan0[(size_t)i], d + h.scan, (size_t)iv[2 * nint - 1] - h.scan);
+    return true;
+}
+
+// Descriptors, the copies out of the staging, the kernel, the status words back (jpeg_ent_done behind them).  rec0[i]: frame i's
+// first record in the pools of jpeg_dev.
+static int jpeg_entropy_enqueue(rfd_ctx *c, const JpegEntropyPlan &pl, int n, const JpegHeader *hdr, const size_t *rec0)
+{
+    const JpegEntLayout l = jpeg_ent_layout(c);
+    const size_t B = (size_t)c->cfg.max_batch_size;
+    char *pin = c->jpeg_ent_pin.p, *dev = (char *)c->jpeg_ent_dev.p, *pools = (char *)c->jpeg_dev.p;
+    JpegEntropyFrame *ef = (JpegEntropyFrame *)pin;
+    JpegEntropyParams p;
+    memset(&p, 0, sizeof p);
+    for (int i = 0; i < n; ++i) {
+        if (!pl.staged[(size_t)i]) continue;
+        JpegEntropyFrame &f = ef[p.n++];
+        memset(&f, 0, sizeof f);
+        jpeg_scan_geom(hdr[i], f.geom, f.dc, f.ac);
+        const uint32_t *iv = (const uint32_t *)(pin + l.ivl) + pl.ivl0[(size_t)i];
+        f.rec0 = rec0[i];
+        f.scan0 = pl.scan0[(size_t)i];
+        f.file_scan = (uint32_t)hdr[i].scan;
+        f.scan_bytes = iv[2 * pl.nint[(size_t)i] - 1] - f.file_scan;
+        f.interval0 = pl.ivl0[(size_t)i];
+        f.intervals = (int)pl.nint[(size_t)i];
+        f.group0 = p.groups;
+        f.frame = i;
+        p.groups += ceil_div(f.intervals, kJpegEntropyGroup);
+    }
+    auto copies = [&]() -> int {
+        RFD_HIP(hipMemcpyAsync(dev, pin, (size_t)p.n * sizeof(JpegEntropyFrame), hipMemcpyHostToDevice, c->stream));
+        RFD_HIP(hipMemcpyAsync(dev + l.ivl, pin + l.ivl, pl.ivl_used * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        if (pl.scan_used) RFD_HIP(hipMemcpyAsync(dev + l.scan, pin + l.scan, pl.scan_used, hipMemcpyHostToDevice, c->stream));
+        RFD_HIP(hipMemsetAsync(dev + l.status, 0, (size_t)n * sizeof(uint32_t), c->stream));
+        return RFD_OK;
+    };
+    const int copied = copies();
+    const hipError_t recorded = hipEventRecord(c->jpeg_pin_done, c->stream); // the next call waits for these before it writes the staging
+    RFD_TRY(copied);
+    RFD_HIP(recorded);
+    p.frames = (const JpegEntropyFrame *)dev;
+    p.scan = (const uint8_t *)(dev + l.scan);
+    p.intervals = (const uint32_t *)(dev + l.ivl);
+    p.rec = (uint32_t *)(pools + B * sizeof(JpegFrame));
+    p.coef = (int16_t *)(pools + B * sizeof(JpegFrame) + B * c->jpeg_blocks_max * sizeof(uint32_t));
+    p.status = (uint32_t *)(dev + l.status);
+    RFD_TRY(launch_jpeg_entropy(p, c->stream));
+    RFD_HIP(hipMemcpyAsync(pin + l.status, dev + l.status, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipEventRecord(c->jpeg_ent_done, c->stream));
+    return RFD_OK;
+}
+
+// fn(i) for every i of items on min(threads, items) threads that never touch HIP; false: no thread could be started
+static bool jpeg_on_threads(int threads, const std::vector<int> &items, const std::function<void(int)> &fn)
+{
+    if (items.empty()) return true;
+    std::atomic<size_t> next{0};
+    auto work = [&]() {
+        for (size_t k; (k = next.fetch_add(1)) < items.size();) fn(items[k]);
+    };
+    std::vector<std::thread> pool;
+    const int T = std::min(threads, (int)items.size());
+    try {
+        for (int t = 0; t < T; ++t) pool.emplace_back(work);
+    } catch (...) {
+    }
+    for (std::thread &t : pool) t.join();
+    return !pool.empty();
+}
+
 // Both forms.  Everything that can refuse the call -- arguments, headers, entropy data -- is settled before the first copy or
-// kernel is enqueued.
+// kernel that writes an output frame is enqueued.  In DEVICE mode the entropy kernel, which writes the context's own pools only,
+// runs before that point, and the call waits for its status words.
 static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_t *len, int n, const rfd_image *out, bool out_on_device, int async)
 {
     RFD_CHECK_ARG(c, "ctx is null");
@@ -2598,6 +2743,8 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
     }
     RFD_HIP(hipSetDevice(c->cfg.device_id));
     RFD_TRY(jpeg_stage_alloc(c));
+    const bool device_entropy = c->jpeg_entropy == RFD_JPEG_ENTROPY_DEVICE;
+    if (device_entropy) RFD_TRY(jpeg_entropy_stage_alloc(c));
     const size_t B = (size_t)c->cfg.max_batch_size;
     JpegFrame *fr = (JpegFrame *)c->jpeg_pin.p;
     uint32_t *rec = (uint32_t *)(fr + B);
@@ -2608,22 +2755,43 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
     std::vector<int> status((size_t)n, RFD_OK);
     size_t blocks = 0, out_bytes = 0;
     for (int i = 0; i < n; ++i) { rec0[(size_t)i] = blocks; blocks += (size_t)hdr[i].nblocks; out_bytes += (size_t)hdr[i].width * 3 * hdr[i].height; }
-    {
-        // one frame per task; the workers touch nothing but their frame's bytes, header and slice of the staging
-        std::atomic<int> next{0};
-        auto work = [&]() {
-            for (int i; (i = next.fetch_add(1)) < n;)
-                status[(size_t)i] = jpeg_decode_scan(bytes[i], len[i], hdr[i], rec + rec0[(size_t)i], coef + rec0[(size_t)i] * 64, &used[(size_t)i]);
-        };
-        std::vector<std::thread> pool;
-        const int T = std::min(c->decode_threads, n);
-        try {
-            for (int t = 0; t < T; ++t) pool.emplace_back(work);
-        } catch (...) {
+    c->jpeg_paths.assign((size_t)n, 0);
+    // one frame per task; the workers touch nothing but their frame's bytes, header and slices of the staging
+    auto decode_on_host = [&](int i) {
+        status[(size_t)i] = jpeg_decode_scan(bytes[i], len[i], hdr[i], rec + rec0[(size_t)i], coef + rec0[(size_t)i] * 64, &used[(size_t)i]);
+    };
+    JpegEntropyPlan plan(n);
+    std::vector<int> host_frames, placed;
+    bool launched = false;
+    if (device_entropy) {
+        char why[200];
+        for (int i = 0; i < n; ++i)
+            if ((uint64_t)hdr[i].nblocks * 64 <= kJpegMaxCoefs && jpeg_entropy_place(c, plan, i, hdr[i], len[i], why, sizeof why)) placed.push_back(i);
+        if (!jpeg_on_threads(c->decode_threads, placed, [&](int i) {
+                char m[200];
+                jpeg_entropy_stage_frame(c, plan, i, bytes[i], len[i], hdr[i], m, sizeof m);
+            })) {
+            set_error("cannot start a JPEG decode thread");
+            return RFD_ERR_STATE;
         }
-        for (std::thread &t : pool) t.join();
-        if (pool.empty()) { set_error("cannot start a JPEG decode thread"); return RFD_ERR_STATE; }
+        for (int i : placed) launched |= plan.staged[(size_t)i] != 0;
+        if (launched) RFD_TRY(jpeg_entropy_enqueue(c, plan, n, hdr.get(), rec0.data()));
     }
+    for (int i = 0; i < n; ++i)
+        if (!plan.staged[(size_t)i]) host_frames.push_back(i);
+    bool threads_ok = jpeg_on_threads(c->decode_threads, host_frames, decode_on_host); // while the entropy kernel runs
+    if (launched) {
+        RFD_HIP(hipEventSynchronize(c->jpeg_ent_done));
+        const uint32_t *refused = (const uint32_t *)(c->jpeg_ent_pin.p + jpeg_ent_layout(c).status);
+        std::vector<int> again;
+        for (int i = 0; i < n; ++i)
+            if (plan.staged[(size_t)i]) {
+                c->jpeg_paths[(size_t)i] = refused[i] ? 2 : 1;
+                if (refused[i]) { plan.staged[(size_t)i] = 0; again.push_back(i); }
+            }
+        threads_ok = jpeg_on_threads(c->decode_threads, again, decode_on_host) && threads_ok; // the host decoder judges what the device refused
+    }
+    if (!threads_ok) { set_error("cannot start a JPEG decode thread"); return RFD_ERR_STATE; }
     for (int i = 0; i < n; ++i)
         if (status[(size_t)i] != RFD_OK) { set_error("file %d: %s", i, hdr[i].msg); return status[(size_t)i]; }
     if (!out_on_device) RFD_TRY(c->jpeg_out.reserve(out_bytes));
@@ -2657,7 +2825,14 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
     char *dev = (char *)c->jpeg_dev.p;
     const size_t rec_off = B * sizeof(JpegFrame), coef_off = rec_off + B * c->jpeg_blocks_max * sizeof(uint32_t);
     auto copies = [&]() -> int {
-        RFD_HIP(hipMemcpyAsync(dev, fr, rec_off + blocks * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        if (!launched) RFD_HIP(hipMemcpyAsync(dev, fr, rec_off + blocks * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        else { // the records the entropy kernel wrote stay: the descriptors, then the records of the host-decoded frames one by one
+            RFD_HIP(hipMemcpyAsync(dev, fr, (size_t)n * sizeof(JpegFrame), hipMemcpyHostToDevice, c->stream));
+            for (int i = 0; i < n; ++i)
+                if (!plan.staged[(size_t)i])
+                    RFD_HIP(hipMemcpyAsync(dev + rec_off + rec0[(size_t)i] * sizeof(uint32_t), rec + rec0[(size_t)i], (size_t)hdr[i].nblocks * sizeof(uint32_t),
+                                           hipMemcpyHostToDevice, c->stream));
+        }
         for (int i = 0; i < n; ++i)
             if (used[(size_t)i])
                 RFD_HIP(hipMemcpyAsync(dev + coef_off + rec0[(size_t)i] * 64 * sizeof(int16_t), coef + rec0[(size_t)i] * 64, (size_t)used[(size_t)i] * sizeof(int16_t),
@@ -2687,6 +2862,83 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
     if (async && out_on_device) return RFD_OK;
     RFD_HIP(hipStreamSynchronize(c->stream));
     return check_nms_flag(c);
+}
+
+int rfd_set_jpeg_entropy(rfd_ctx *c, int mode)
+{
+    RFD_CHECK_ARG(c, "ctx is null");
+    if (mode != RFD_JPEG_ENTROPY_HOST && mode != RFD_JPEG_ENTROPY_DEVICE) { set_error("invalid argument: JPEG entropy mode %d (0: host, 1: device)", mode); return RFD_ERR_INVALID_ARG; }
+    c->jpeg_entropy = mode;
+    return RFD_OK;
+}
+
+int rfd_jpeg_last_paths(rfd_ctx *c, int32_t *path, int cap, int *n)
+{
+    RFD_CHECK_ARG(c, "ctx is null");
+    RFD_CHECK_ARG(cap >= 0 && (path || cap == 0), "path is null");
+    const int have = (int)c->jpeg_paths.size();
+    if (n) *n = have;
+    if (have > cap) { set_error("the last decode call had %d frames, the output holds %d", have, cap); return RFD_ERR_CAPACITY; }
+    for (int i = 0; i < have; ++i) path[i] = c->jpeg_paths[(size_t)i];
+    return RFD_OK;
+}
+
+int rfd_debug_jpeg_intervals(const uint8_t *bytes, size_t len, uint32_t *begin, uint32_t *end, size_t cap, size_t *count)
+{
+    RFD_CHECK_ARG((begin && end) || cap == 0, "begin or end is null");
+    std::unique_ptr<JpegHeader> h(new JpegHeader);
+    const int st = jpeg_parse_header(bytes, len, *h);
+    if (st != RFD_OK) { set_error("%s", h->msg); return st; }
+    char msg[200] = "";
+    size_t want = 0;
+    bool ok = jpeg_device_eligible(bytes, len, *h, begin, end, 0, &want, msg, sizeof msg); // the header's part of the rule, and the count
+    if (count) *count = want;
+    if (ok && want > cap) { set_error("the file has %zu restart intervals, the output holds %zu", want, cap); return RFD_ERR_CAPACITY; }
+    ok = ok && jpeg_device_eligible(bytes, len, *h, begin, end, cap, &want, msg, sizeof msg);
+    if (!ok) { set_error("%s", msg); return RFD_ERR_UNSUPPORTED; }
+    return RFD_OK;
+}
+
+int rfd_debug_jpeg_coefficients_device(rfd_ctx *c, const uint8_t *bytes, size_t len, int16_t *out, size_t cap_blocks, size_t *blocks)
+{
+    RFD_CHECK_ARG(c, "ctx is null");
+    RFD_CHECK_ARG(out || cap_blocks == 0, "out is null");
+    std::unique_ptr<JpegHeader> h(new JpegHeader);
+    const int st = jpeg_parse_header(bytes, len, *h);
+    if (st != RFD_OK) { set_error("%s", h->msg); return st; }
+    if (blocks) *blocks = (size_t)h->nblocks;
+    if ((uint64_t)h->nblocks * 64 > kJpegMaxCoefs) { set_error("a JPEG frame of %d blocks exceeds the decoder's %u coefficient slots", h->nblocks, kJpegMaxCoefs); return RFD_ERR_CAPACITY; }
+    if ((size_t)h->nblocks > cap_blocks) { set_error("the file has %d blocks, the output holds %zu", h->nblocks, cap_blocks); return RFD_ERR_CAPACITY; }
+    if (h->width > c->cfg.max_src_w || h->height > c->cfg.max_src_h) {
+        set_error("%d x %d exceeds max_src %d x %d", h->width, h->height, c->cfg.max_src_w, c->cfg.max_src_h);
+        return RFD_ERR_CAPACITY;
+    }
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    RFD_TRY(jpeg_stage_alloc(c));
+    RFD_TRY(jpeg_entropy_stage_alloc(c));
+    RFD_HIP(hipEventSynchronize(c->jpeg_pin_done));
+    JpegEntropyPlan plan(1);
+    char msg[200] = "";
+    if (!jpeg_entropy_place(c, plan, 0, *h, len, msg, sizeof msg) || !jpeg_entropy_stage_frame(c, plan, 0, bytes, len, *h, msg, sizeof msg)) {
+        set_error("%s", msg);
+        return RFD_ERR_UNSUPPORTED;
+    }
+    const size_t rec0 = 0, B = (size_t)c->cfg.max_batch_size, nb = (size_t)h->nblocks;
+    RFD_TRY(jpeg_entropy_enqueue(c, plan, 1, h.get(), &rec0));
+    RFD_HIP(hipEventSynchronize(c->jpeg_ent_done));
+    if (*(const uint32_t *)(c->jpeg_ent_pin.p + jpeg_ent_layout(c).status)) {
+        set_error("the device entropy decoder refused the file: an interval of the scan at byte %zu does not decode to exactly its bytes", h->scan);
+        return RFD_ERR_UNSUPPORTED;
+    }
+    std::vector<uint32_t> rec(nb);
+    std::vector<int16_t> coef(nb * 64);
+    const char *pools = (const char *)c->jpeg_dev.p;
+    RFD_HIP(hipMemcpyAsync(rec.data(), pools + B * sizeof(JpegFrame), nb * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipMemcpyAsync(coef.data(), pools + B * sizeof(JpegFrame) + B * c->jpeg_blocks_max * sizeof(uint32_t), nb * 64 * sizeof(int16_t), hipMemcpyDeviceToHost,
+                           c->stream));
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    jpeg_dequantise_natural(*h, rec.data(), coef.data(), out);
+    return RFD_OK;
 }
 
 int rfd_decode_jpeg_batch_device(rfd_ctx *c, const uint8_t *const *bytes, const size_t *len, int n, const rfd_image *out, int async)

@@ -375,6 +375,24 @@ inline int jpeg_info(const uint8_t *d, size_t len, struct rfd_jpeg_info *out, ch
     return RFD_OK;
 }
 
+// records + quantised zigzag runs of a decoded scan -> out [nblocks][64]: dequantised (saturating to i16), natural order
+inline void jpeg_dequantise_natural(const JpegHeader &h, const uint32_t *rec, const int16_t *coef, int16_t *out)
+{
+    memset(out, 0, (size_t)h.nblocks * 64 * sizeof(int16_t));
+    for (int c = 0; c < h.ncomp; ++c) {
+        const JpegComponent &k = h.comp[c];
+        const uint16_t *q = h.quant[k.tq];
+        for (int b = k.blk0; b < k.blk0 + k.bw * k.bh; ++b) {
+            const int16_t *src = coef + (rec[(size_t)b] >> kJpegRecCountBits);
+            const int count = (int)(rec[(size_t)b] & ((1u << kJpegRecCountBits) - 1));
+            for (int z = 0; z < count; ++z) {
+                const int v = (int)src[z] * (int)q[z];
+                out[(size_t)b * 64 + kJpegNatural[z]] = (int16_t)(v < -32768 ? -32768 : v > 32767 ? 32767 : v);
+            }
+        }
+    }
+}
+
 // rfd_debug_jpeg_coefficients: parse, decode, dequantise, zigzag -> natural order
 inline int jpeg_debug_coefficients(const uint8_t *d, size_t len, int16_t *out, size_t cap_blocks, size_t *blocks, char *msg, size_t msg_cap)
 {
@@ -397,19 +415,7 @@ inline int jpeg_debug_coefficients(const uint8_t *d, size_t len, int16_t *out, s
         snprintf(msg, msg_cap, "%s", h->msg);
         return st;
     }
-    memset(out, 0, (size_t)h->nblocks * 64 * sizeof(int16_t));
-    for (int c = 0; c < h->ncomp; ++c) {
-        const JpegComponent &k = h->comp[c];
-        const uint16_t *q = h->quant[k.tq];
-        for (int b = k.blk0; b < k.blk0 + k.bw * k.bh; ++b) {
-            const int16_t *src = coef.data() + (rec[(size_t)b] >> kJpegRecCountBits);
-            const int count = (int)(rec[(size_t)b] & ((1u << kJpegRecCountBits) - 1));
-            for (int z = 0; z < count; ++z) {
-                const int v = (int)src[z] * (int)q[z];
-                out[(size_t)b * 64 + kJpegNatural[z]] = (int16_t)(v < -32768 ? -32768 : v > 32767 ? 32767 : v);
-            }
-        }
-    }
+    jpeg_dequantise_natural(*h, rec.data(), coef.data(), out);
     return RFD_OK;
 }
 

@@ -1,5 +1,6 @@
 // kernels.h -- launch interfaces of the HIP kernels (all gfx950).
 #pragma once
+#include "jpeg_entropy.h"
 #include "rfd_common.h"
 
 namespace rfd {
@@ -238,6 +239,34 @@ constexpr int kJpegGroupBlocks = 32;  // 8 lanes per block
 constexpr int kJpegTilePixels = 1024; // one thread per 4 pixels of a row
 // kernel 1: zigzag run -> dequantise -> libjpeg's accurate integer IDCT -> u8 planes; kernel 2: fancy upsampling + YCbCr -> BGR
 int launch_jpeg_decode(const JpegParams &p, hipStream_t s);
+
+// ---------------------------------------------------------------- JPEG entropy decode (kernels_jpeg_entropy.hip)
+// Huffman decoding of restart-interval files, one thread per interval (jpeg_entropy.h).  One frame of a batch that takes this
+// path; the frames share three pools: scan bytes, interval tables, and the record / coefficient pools of JpegParams.
+struct JpegEntropyFrame {
+    JpegDevHuff dc[3], ac[3];   // per component; the kernel stages the six as one run of words
+    JpegScanGeom geom;
+    unsigned long long rec0;    // the frame's first block record; its coefficients start at rec0 * 64 (JpegFrame)
+    uint32_t scan0, scan_bytes; // the frame's entropy-coded bytes in the scan pool
+    uint32_t file_scan;         // what the interval table's positions count from: the file offset of the first scan byte
+    uint32_t interval0;         // the frame's table in the interval pool: begin[intervals] | end[intervals]
+    int intervals;
+    int group0;                 // the frame's first workgroup
+    int frame;                  // index in the batch: its status word
+    int pad;
+};
+static_assert(offsetof(JpegEntropyFrame, ac) == 3 * sizeof(JpegDevHuff), "dc | ac is one run");
+struct JpegEntropyParams {
+    const JpegEntropyFrame *frames; // device [n]
+    int n, groups;
+    const uint8_t *scan;
+    const uint32_t *intervals;
+    uint32_t *rec;                  // written: (block * 64) << 7 | count
+    int16_t *coef;                  // written: block b's quantised coefficients, zigzag order, at b * 64
+    uint32_t *status;               // per frame of the batch, zeroed by the caller: |= 1 when an interval is refused
+};
+constexpr int kJpegEntropyGroup = 64; // one wave: 64 intervals of one frame
+int launch_jpeg_entropy(const JpegEntropyParams &p, hipStream_t s);
 
 // ---------------------------------------------------------------- convolution engine (kernels_conv.hip)
 // Activations: NHWC bf16.  Weights: [Cout][KH][KW][Cin] bf16 (K contiguous).  f32 accumulate on MFMA.

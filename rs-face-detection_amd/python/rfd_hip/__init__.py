@@ -25,6 +25,8 @@ RFD_ERR_IO = -6
 RFD_ERR_COMM = -7
 RFD_ERR_UNSUPPORTED = -8
 JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = 0, 1, 2, 3   # rfd_jpeg_sampling
+JPEG_ENTROPY_HOST, JPEG_ENTROPY_DEVICE = 0, 1           # rfd_jpeg_entropy
+JPEG_PATH_HOST, JPEG_PATH_DEVICE, JPEG_PATH_REFUSED = 0, 1, 2   # rfd_jpeg_last_paths
 COMM_ID_BYTES = 128
 MAX_FACE_TENSORS = 4   # RFD_MAX_FACE_TENSORS
 GALLERY_MAX_K = 32     # RFD_GALLERY_MAX_K
@@ -147,6 +149,7 @@ API_SYMBOLS = [
     "rfd_gallery_remove", "rfd_gallery_replace", "rfd_gallery_replace_device", "rfd_gallery_live", "rfd_gallery_removed",
     "rfd_gallery_save", "rfd_gallery_load", "rfd_gallery_file_info",
     "rfd_jpeg_info", "rfd_decode_jpeg_batch_device", "rfd_decode_jpeg_batch", "rfd_set_decode_threads", "rfd_debug_jpeg_coefficients",
+    "rfd_set_jpeg_entropy", "rfd_jpeg_last_paths", "rfd_debug_jpeg_intervals", "rfd_debug_jpeg_coefficients_device",
 ]
 
 _lib = None
@@ -276,6 +279,10 @@ def load_library(path=None):
     L.rfd_decode_jpeg_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), ci, C.POINTER(rfd_image)]
     L.rfd_set_decode_threads.argtypes = [vp, ci]
     L.rfd_debug_jpeg_coefficients.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rfd_set_jpeg_entropy.argtypes = [vp, ci]
+    L.rfd_jpeg_last_paths.argtypes = [vp, vp, ci, C.POINTER(ci)]
+    L.rfd_debug_jpeg_intervals.argtypes = [vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rfd_debug_jpeg_coefficients_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     if path is None:
         _lib = L
     return L
@@ -415,6 +422,20 @@ def jpeg_coefficients(data):
     out = np.zeros((blocks.value, 64), np.int16)
     _check(L.rfd_debug_jpeg_coefficients(addr, n, out.ctypes.data, blocks.value, C.byref(blocks)))
     return out
+
+
+def jpeg_intervals(data):
+    """the restart intervals of a JPEG file as the marker pre-scan finds them (rfd_debug_jpeg_intervals; host only, no GPU) ->
+    [(begin, end)] byte positions in the file.  A file that is not eligible for device entropy decoding raises RfdError with
+    RFD_ERR_UNSUPPORTED and the reason."""
+    keep, addr, n = _byte_buffer(data)
+    L, count = load_library(), C.c_size_t(0)
+    st = L.rfd_debug_jpeg_intervals(addr, n, None, None, 0, C.byref(count))
+    if st != RFD_ERR_CAPACITY:
+        _check(st)
+    begin, end = np.zeros(count.value, np.uint32), np.zeros(count.value, np.uint32)
+    _check(L.rfd_debug_jpeg_intervals(addr, n, begin.ctypes.data, end.ctypes.data, count.value, C.byref(count)))
+    return list(zip(begin.tolist(), end.tolist()))
 
 
 def op_kernels_static(backbone, image_w, image_h, n, op, co_running=True, tile=0, schedule=SCHEDULE_THROUGHPUT, cus=256):
@@ -760,6 +781,34 @@ class RetinaFaceDetection:
     def set_decode_threads(self, threads):
         """host threads of the entropy decoder, 1..16 (default 4); the pixels do not depend on it"""
         _check(self._L.rfd_set_decode_threads(self._ctx, int(threads)))
+
+    def set_jpeg_entropy(self, mode):
+        """"host" (default): Huffman decoding on the host threads; "device": files with a restart interval are entropy-decoded
+        by one device thread per interval, every other file as before (rfd.h, "entropy decoding on the device")"""
+        modes = {"host": JPEG_ENTROPY_HOST, "device": JPEG_ENTROPY_DEVICE}
+        _check(self._L.rfd_set_jpeg_entropy(self._ctx, modes[mode] if mode in modes else int(mode)))
+
+    def jpeg_last_paths(self):
+        """per frame of the last decode call: 0 host (not eligible), 1 device, 2 host after the device refused the frame"""
+        n = C.c_int(0)
+        st = self._L.rfd_jpeg_last_paths(self._ctx, None, 0, C.byref(n))
+        if st != RFD_ERR_CAPACITY:
+            _check(st)
+        out = np.zeros(n.value, np.int32)
+        _check(self._L.rfd_jpeg_last_paths(self._ctx, out.ctypes.data, n.value, C.byref(n)))
+        return out.tolist()
+
+    def jpeg_coefficients_device(self, data):
+        """jpeg_coefficients with the quantised coefficients taken from the device entropy kernel; never falls back to the host
+        decoder (RFD_ERR_UNSUPPORTED where the file is not eligible or the device refused it)"""
+        keep, addr, n = _byte_buffer(data)
+        blocks = C.c_size_t(0)
+        st = self._L.rfd_debug_jpeg_coefficients_device(self._ctx, addr, n, None, 0, C.byref(blocks))
+        if st != RFD_ERR_CAPACITY:
+            _check(st)
+        out = np.zeros((blocks.value, 64), np.int16)
+        _check(self._L.rfd_debug_jpeg_coefficients_device(self._ctx, addr, n, out.ctypes.data, blocks.value, C.byref(blocks)))
+        return out
 
     @staticmethod
     def _jpeg_files(files):

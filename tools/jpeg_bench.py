@@ -11,9 +11,14 @@
       coefficients, against the 6.2 MB of a decoded frame;
   (d) Pillow's full decode time on the same host, where Pillow is installed, as the yardstick.
 Files: generated with Pillow where it is installed, or every *.jpg of a directory given as the argument.
+--entropy device selects RFD_JPEG_ENTROPY_DEVICE (rfd.h, "entropy decoding on the device"): (a) is then the call with the entropy
+kernel inside, (b) adds jpeg_entropy_kernel, (c) counts the scan bytes and interval tables that cross PCIe instead, and the
+per-frame paths are printed, so that a run in which the kernel never ran cannot pass for one.  --restart rows writes the
+generated files with a restart interval of one MCU row (Pillow's restart_marker_rows = 1), --restart max with one of
+kJpegDeviceMaxInterval MCUs (restart_marker_blocks); without it the files have no restart interval and stay on the host.
 
-    python tools/jpeg_bench.py [directory] [--files 32] [--reps 5] [--no-trace]
-Record the output in profiles/jpeg_decode.txt."""
+    python tools/jpeg_bench.py [directory] [--files 32] [--reps 5] [--no-trace] [--entropy host|device] [--restart none|rows|max|MCUs]
+Record the output in profiles/jpeg_decode.txt and profiles/jpeg_entropy_device.txt."""
 import argparse
 import glob
 import io
@@ -26,9 +31,10 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "rs-face-detection_amd", "python"))
 STREAM_TBS = 6.3   # float4 copy rate of the chip, TB/s
+MAX_INTERVAL = 128   # kJpegDeviceMaxInterval (csrc/jpeg_entropy.h)
 
 
-def make_files(n):
+def make_files(n, restart="none"):
     from PIL import Image
     out = []
     for i in range(n):
@@ -40,7 +46,8 @@ def make_files(n):
             img[(x - cx) ** 2 + (y - cy) ** 2 < r * r] = rng.integers(0, 256, 3)
         img[:, 1400:] += rng.normal(0, 12, (1080, 520, 3))
         buf = io.BytesIO()
-        Image.fromarray(np.clip(img, 0, 255).astype(np.uint8)).save(buf, "JPEG", quality=90, subsampling=2)
+        kw = {"none": {}, "rows": dict(restart_marker_rows=1), "max": dict(restart_marker_blocks=MAX_INTERVAL)}.get(restart) if not str(restart).isdigit() else dict(restart_marker_blocks=int(restart))
+        Image.fromarray(np.clip(img, 0, 255).astype(np.uint8)).save(buf, "JPEG", quality=90, subsampling=2, **kw)
         out.append(buf.getvalue())
     return out
 
@@ -48,13 +55,14 @@ def make_files(n):
 def load_files(a):
     if a.directory:
         return [open(f, "rb").read() for f in sorted(glob.glob(os.path.join(a.directory, "*.jpg")))[:a.files]]
-    return make_files(a.files)
+    return make_files(a.files, a.restart)
 
 
-def open_detector(R, files):
+def open_detector(R, files, entropy="host"):
     import torch
     infos = [R.jpeg_info(f) for f in files]
     det = R.RetinaFaceDetection(max_batch_size=len(files), max_src=(max(i["width"] for i in infos), max(i["height"] for i in infos)))
+    det.set_jpeg_entropy(entropy)
     dev = torch.device("cuda", 0)
     bufs = [torch.zeros((i["height"], i["width"] * 3), dtype=torch.uint8, device=dev) for i in infos]
     torch.cuda.synchronize()
@@ -66,7 +74,7 @@ def traced_child(a):
     import torch  # noqa: F401  (first: librfd_hip.so then binds to the HIP runtime torch ships)
     import rfd_hip as R
     files = load_files(a)
-    det, infos, bufs, ptrs, shapes = open_detector(R, files)
+    det, infos, bufs, ptrs, shapes = open_detector(R, files, a.entropy)
     for _ in range(1 + a.reps):
         det.decode_jpeg_device(files, ptrs, shapes)
     print("traced calls %d frames %d" % (1 + a.reps, len(files)))
@@ -100,7 +108,7 @@ def kernel_pass(files, a, h2d_bytes_per_call):
                 fh.write(f)
         out = os.path.join(tmp, "trace")
         r = subprocess.run([exe, "--kernel-trace", "--memory-copy-trace", "--stats", "--output-format", "csv", "-d", out, "--", sys.executable,
-                            os.path.abspath(__file__), tmp, "--files", str(len(files)), "--reps", str(a.reps), "--child"],
+                            os.path.abspath(__file__), tmp, "--files", str(len(files)), "--reps", str(a.reps), "--entropy", a.entropy, "--child"],
                            capture_output=True, text=True, timeout=600)
         if r.returncode != 0 or "traced calls" not in r.stdout:
             print("(b) the traced child failed (exit %d): kernel time not measured\n%s" % (r.returncode, (r.stdout + r.stderr)[-600:]))
@@ -112,16 +120,18 @@ def kernel_pass(files, a, h2d_bytes_per_call):
             return
         floor_us = 19e6 / (STREAM_TBS * 1e12) * 1e6
         total = 0.0
-        for name in ("jpeg_idct_kernel", "jpeg_color_kernel"):
+        for name in ("jpeg_entropy_kernel", "jpeg_idct_kernel", "jpeg_color_kernel"):
             hit = [x for x in rows if name in x["Name"]]
             if not hit:
-                print("(b) %s is not in the kernel statistics" % name)
+                if name != "jpeg_entropy_kernel" or a.entropy == "device":
+                    print("(b) %s is not in the kernel statistics" % name)
                 continue
             us = float(hit[0]["AverageNs"]) / 1e3
-            total += us
+            if name != "jpeg_entropy_kernel":   # the HBM floor below is that of the two parallel kernels
+                total += us
             print("(b) %s: %d launches, %.1f us per launch = %.2f us per frame (min %.1f, max %.1f us per launch)" %
                   (name, int(hit[0]["Calls"]), us, us / n, float(hit[0]["MinNs"]) / 1e3, float(hit[0]["MaxNs"]) / 1e3))
-        print("(b) both kernels: %.2f us per frame against the HBM floor of %.1f us per frame (19 MB at %.1f TB/s): %.0f %% of the floor's rate" %
+        print("(b) idct + colour: %.2f us per frame against the HBM floor of %.1f us per frame (19 MB at %.1f TB/s): %.0f %% of the floor's rate" %
               (total / n, floor_us, STREAM_TBS, 100 * floor_us / (total / n) if total else 0))
         copies = read_stats(out, "memory_copy_stats.csv")
         h2d = [x for x in copies or [] if "HOST_TO_DEVICE" in x["Name"].upper() or "H2D" in x["Name"].upper()]
@@ -141,6 +151,8 @@ def main():
     ap.add_argument("--files", type=int, default=32)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-trace", action="store_true", help="skip (b), the child run under rocprofv3")
+    ap.add_argument("--entropy", choices=("host", "device"), default="host", help="where eligible files are entropy-decoded")
+    ap.add_argument("--restart", default="none", help="restart interval of the generated files: none, rows (one MCU row), max (kJpegDeviceMaxInterval MCUs) or a number of MCUs")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
@@ -161,8 +173,21 @@ def main():
     decoded = [i["width"] * i["height"] * 3 for i in infos]
     print("(c) H2D bytes per frame: %.2f MB (records + truncated runs) against %.2f MB decoded = %.1f %%" %
           (np.mean(h2d) / 1e6, np.mean(decoded) / 1e6, 100 * np.sum(h2d) / np.sum(decoded)))
-    det, infos, bufs, ptrs, shapes = open_detector(R, files)
+    det, infos, bufs, ptrs, shapes = open_detector(R, files, a.entropy)
     det.decode_jpeg_device(files, ptrs, shapes)   # allocates the staging, loads the code objects
+    paths = det.jpeg_last_paths()
+    print("entropy mode %s, restart interval of the first file %d MCUs; paths of the batch: %d host, %d device, %d refused by the device" %
+          (a.entropy, infos[0]["restart_interval"], paths.count(0), paths.count(1), paths.count(2)))
+    if a.entropy == "device":   # (c) for the frames that took the device path: the scan bytes and 8 B per interval, plus one descriptor
+        dev, scan = [], []
+        for f, p in zip(files, paths):
+            if p == 1:
+                iv = R.jpeg_intervals(f)
+                dev.append(iv[-1][1] - iv[0][0] + 8 * len(iv) + 8600)
+                scan.append(len(iv))
+        if dev:
+            print("(c) device path: %.3f MB per frame (scan bytes + interval table + descriptor, %d intervals per frame) against %.2f MB on the host path = %.1f %%" %
+                  (np.mean(dev) / 1e6, int(np.mean(scan)), np.mean(h2d) / 1e6, 100 * np.mean(dev) / np.mean(h2d)))
     for threads in (1, 4, 16):
         det.set_decode_threads(threads)
         enq, whole = [], []
