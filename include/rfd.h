@@ -589,7 +589,8 @@ RFD_API int64_t rfd_debug_gallery_offset(int dim, int row, int d);
  *      there; the arithmetic here wraps modulo 2^32 and clamps.
  *      Supported: baseline and extended sequential Huffman files (SOF0, SOF1) with 8-bit samples and ONE interleaved scan of one
  *      component (grey) or of three with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1; 8- and 16-bit quantisation tables;
- *      restart intervals; APPn and COM segments are skipped, fill bytes and 0xFF00 stuffing understood.
+ *      restart intervals; APPn and COM segments are skipped (but for the orientation tag: "EXIF orientation" below), fill bytes
+ *      and 0xFF00 stuffing understood.
  *      RFD_ERR_UNSUPPORTED: progressive (SOF2), lossless, hierarchical and arithmetic-coded files, 12-bit samples, four (or two)
  *      components, other sampling factors, files of more than one scan.  RFD_ERR_INVALID_ARG: a truncated or malformed file -- a
  *      length field that points past the end, a Huffman code that is not in its table, a coefficient index above 63, a table
@@ -613,8 +614,8 @@ struct rfd_jpeg_info {
  * *out untouched.  (The struct shares its name with the function, so C and C++ both spell the type `struct rfd_jpeg_info`.) */
 RFD_API int rfd_jpeg_info(const uint8_t *bytes, size_t len, struct rfd_jpeg_info *out);
 /* Decodes n files into n caller-allocated DEVICE frames: out[i].data is device memory of out[i].height rows of out[i].stride
- * bytes; width and height must equal the file's (else RFD_ERR_INVALID_ARG) and stride must be >= 3 * width; bytes of a row
- * beyond 3 * width are not touched.  rfd_image declares data const because every other entry point reads frames; this one
+ * bytes; width and height must equal the file's (the ORIENTED size in RFD_JPEG_ORIENTATION_APPLY mode, "EXIF orientation" below;
+ * else RFD_ERR_INVALID_ARG) and stride must be >= 3 * width; bytes of a row beyond 3 * width are not touched.  rfd_image declares data const because every other entry point reads frames; this one
  * WRITES through it (the library casts the const away).  The same array is then valid input to rfd_detect_batch_device,
  * rfd_detect_faces_device and rfd_liveness_tensors_device on the same stream, with no synchronisation in between.
  * bytes[] / len[] and the files are host memory and may be freed when the call returns.  Entropy decoding happens inside the
@@ -674,6 +675,51 @@ RFD_API int rfd_debug_jpeg_intervals(const uint8_t *bytes, size_t len, uint32_t 
 /* Test hook: rfd_debug_jpeg_coefficients with the quantised coefficients taken from the device entropy kernel, whatever the
  * context's mode.  Never falls back: RFD_ERR_UNSUPPORTED when the file is not eligible or the device refused it. */
 RFD_API int rfd_debug_jpeg_coefficients_device(rfd_ctx *ctx, const uint8_t *bytes, size_t len, int16_t *out, size_t cap_blocks, size_t *blocks);
+
+/* ---- JPEG decode, EXIF orientation (opt-in).  A phone stores a portrait photo as landscape pixels plus an orientation tag in
+ *      an Exif APP1 segment.  cv::imdecode applies the tag under its default flags; the reference decodes with IMREAD_UNCHANGED
+ *      (utils.rs:18), which does not.  So RFD_JPEG_ORIENTATION_IGNORE is the default, in which every call does what it did
+ *      before the mode existed, bit for bit, and RFD_JPEG_ORIENTATION_APPLY is a mode the caller selects.
+ *      The tag: of the segments between SOI and SOS, the FIRST APP1 whose payload begins with "Exif\0\0" is looked at, and only
+ *      that one.  It holds a TIFF block -- byte order II or MM, the number 42, the 32-bit offset of IFD0 from the start of the
+ *      block, and IFD0 (a 16-bit entry count, then 12-byte entries, anywhere in the payload).  The orientation is the first entry
+ *      with tag 0x0112 that is one SHORT or one LONG, read in the file's byte order; values 1..8 are honoured.  In every other
+ *      case -- no such segment or entry, a bad byte-order mark or 42, another type or count, another value, any read that would
+ *      fall outside the payload -- the orientation is 1 and the decode goes on: EXIF damage never refuses a file.
+ *      APPLY mode: with S[H][W] the stored image, rfd_decode_jpeg_batch* writes out[yo][xo] =
+ *          orientation 1   S[yo][xo]              H x W  (rows x columns)
+ *          orientation 2   S[yo][W-1-xo]          H x W
+ *          orientation 3   S[H-1-yo][W-1-xo]      H x W
+ *          orientation 4   S[H-1-yo][xo]          H x W
+ *          orientation 5   S[xo][yo]              W x H
+ *          orientation 6   S[H-1-xo][yo]          W x H
+ *          orientation 7   S[H-1-xo][W-1-yo]      W x H
+ *          orientation 8   S[xo][W-1-yo]          W x H
+ *      which is what Pillow's ImageOps.exif_transpose gives.  out[i].width / height must equal the ORIENTED size
+ *      (rfd_jpeg_orientation reports it), else RFD_ERR_INVALID_ARG naming the frame, with nothing enqueued and no frame written;
+ *      stride, alignment and the promise that no byte beyond 3 * width of a row is touched hold for the oriented frame.  The
+ *      capacity check against max_src_w / max_src_h stays on the STORED size, which is what the decoder's pools are sized by.
+ *      The detect calls check the size of the frame they are given: a context fed portrait files of 1920 x 1080 stored pixels
+ *      hands 1080 x 1920 frames to rfd_detect_batch_device and therefore needs max_src_h >= 1920.  Boxes and landmarks of a
+ *      later detect call are in the ORIENTED frame's coordinates; the table above maps them back to stored ones.
+ *      Frames of orientation 1 take the same colour kernel in both modes; frames of orientation 2..8 take a third launch, made
+ *      only when a batch holds one, which computes the same pixels and stores them through the map.  The
+ *      orientation does not depend on where a frame was entropy-decoded. ---- */
+typedef enum rfd_jpeg_orientation_mode { RFD_JPEG_ORIENTATION_IGNORE = 0, RFD_JPEG_ORIENTATION_APPLY = 1 } rfd_jpeg_orientation_mode;
+struct rfd_jpeg_orientation {
+    int32_t orientation;                 /* 1..8 */
+    int32_t width, height;               /* of the frame an APPLY-mode decode writes: the stored size, swapped for 5..8 */
+    int32_t stored_width, stored_height; /* as rfd_jpeg_info reports them */
+    int32_t reserved[3];                 /* 0 */
+};
+/* Host only, no context, no device: the header validation of rfd_jpeg_info with the same statuses and messages, then the tag.  A
+ * refused file leaves *out untouched.  (Struct and function share the name, as rfd_jpeg_info does.) */
+RFD_API int rfd_jpeg_orientation(const uint8_t *bytes, size_t len, struct rfd_jpeg_orientation *out);
+/* IGNORE is the default; any other value than the two: RFD_ERR_INVALID_ARG.  May be changed between calls. */
+RFD_API int rfd_set_jpeg_orientation(rfd_ctx *ctx, int mode);
+/* The orientation that was applied to each frame of the last rfd_decode_jpeg_batch* call: all 1 in IGNORE mode.  *n = the frames
+ * of that call (0 before the first), also when n > cap (then RFD_ERR_CAPACITY, nothing written).  n may be NULL. */
+RFD_API int rfd_jpeg_last_orientations(rfd_ctx *ctx, int32_t *orientation, int cap, int *n);
 
 /* ---- introspection ---- */
 RFD_API int rfd_get_stats(rfd_ctx *ctx, rfd_stats *stats);

@@ -386,8 +386,9 @@ struct DecodedImage {
     Mat mat() const { return Mat(pixels.data(), rows, cols); }
 };
 inline void set_decode_threads(RetinaFaceDetection &det, int threads) { check(rfd_set_decode_threads(det.raw(), threads)); }
-// files -> host frames, decoded on the device; throws where the reference's imdecode fails
-inline std::vector<DecodedImage> decode_jpeg(RetinaFaceDetection &det, const std::vector<std::vector<uint8_t>> &files)
+// files -> host frames, decoded on the device; throws where the reference's imdecode fails.  oriented: the context is in
+// RFD_JPEG_ORIENTATION_APPLY mode (set_jpeg_orientation below), so the frames are allocated in the oriented size
+inline std::vector<DecodedImage> decode_jpeg(RetinaFaceDetection &det, const std::vector<std::vector<uint8_t>> &files, bool oriented = false)
 {
     const std::size_t n = files.size();
     std::vector<DecodedImage> out(n);
@@ -398,6 +399,11 @@ inline std::vector<DecodedImage> decode_jpeg(RetinaFaceDetection &det, const std
         JpegInfo info;
         try {
             info = jpeg_info(files[i]);
+            if (oriented) {
+                struct rfd_jpeg_orientation o;
+                check(rfd_jpeg_orientation(files[i].data(), files[i].size(), &o));
+                info.width = o.width; info.height = o.height;
+            }
         } catch (const Error &e) { // name the file, as the batch call itself does
             throw Error(e.status, "file " + std::to_string(i) + ": " + e.message);
         }
@@ -424,6 +430,25 @@ inline void decode_jpeg_device(RetinaFaceDetection &det, const std::vector<std::
 // device"); every other file, and everything in RFD_JPEG_ENTROPY_HOST (the default), on the host threads
 inline void set_jpeg_entropy(RetinaFaceDetection &det, rfd_jpeg_entropy mode) { check(rfd_set_jpeg_entropy(det.raw(), (int)mode)); }
 // per frame of the last decode call: 0 host, 1 device, 2 host after the device refused the frame
+// RFD_JPEG_ORIENTATION_APPLY: frames are written upright, through the file's EXIF orientation tag and in the oriented size (rfd.h,
+// "EXIF orientation"); RFD_JPEG_ORIENTATION_IGNORE (the default): as the file stores them
+inline void set_jpeg_orientation(RetinaFaceDetection &det, rfd_jpeg_orientation_mode mode) { check(rfd_set_jpeg_orientation(det.raw(), (int)mode)); }
+
+struct JpegOrientation {
+    int orientation = 1;                    // 1..8
+    int width = 0, height = 0;              // of the frame an APPLY-mode decode writes
+    int stored_width = 0, stored_height = 0;
+};
+inline JpegOrientation jpeg_orientation(const std::vector<uint8_t> &file)
+{
+    struct rfd_jpeg_orientation o;
+    check(rfd_jpeg_orientation(file.data(), file.size(), &o));
+    JpegOrientation r;
+    r.orientation = o.orientation; r.width = o.width; r.height = o.height;
+    r.stored_width = o.stored_width; r.stored_height = o.stored_height;
+    return r;
+}
+
 inline std::vector<int32_t> jpeg_last_paths(RetinaFaceDetection &det)
 {
     int n = 0;

@@ -219,6 +219,12 @@ struct rfd_ctx {
     DevBuf jpeg_ent_dev;
     Event jpeg_ent_done;
     std::vector<int32_t> jpeg_paths; // rfd_jpeg_last_paths
+    // EXIF orientation (rfd_set_jpeg_orientation).  Behind the coefficients, jpeg_pin and jpeg_dev hold the tables of the colour
+    // launches of a batch with an oriented frame (jpeg_tables_off, 16-byte aligned): JpegOrientedFrame [B] | JpegFrame [B], the
+    // second being the upright frames alone.  A batch without such a frame neither writes nor copies them.
+    int jpeg_orientation = RFD_JPEG_ORIENTATION_IGNORE;
+    size_t jpeg_tables_off = 0;
+    std::vector<int32_t> jpeg_orientations; // rfd_jpeg_last_orientations
     // pipelined host entry (rfd_submit_batch / rfd_collect_batch): two slots, H2D on its own stream
     struct PipeSlot {
         DevBuf frames, imgs, scale, ob, ol, oc, ot;
@@ -2538,6 +2544,14 @@ int rfd_jpeg_info(const uint8_t *bytes, size_t len, struct rfd_jpeg_info *out)
     return st;
 }
 
+int rfd_jpeg_orientation(const uint8_t *bytes, size_t len, struct rfd_jpeg_orientation *out)
+{
+    char msg[256] = "";
+    const int st = jpeg_orientation(bytes, len, out, msg, sizeof msg);
+    if (st != RFD_OK) set_error("%s", msg);
+    return st;
+}
+
 int rfd_debug_jpeg_coefficients(const uint8_t *bytes, size_t len, int16_t *out, size_t cap_blocks, size_t *blocks)
 {
     RFD_CHECK_ARG(out || cap_blocks == 0, "out is null");
@@ -2572,12 +2586,14 @@ static int jpeg_stage_alloc(rfd_ctx *c)
         set_error("max_src %d x %d exceeds the JPEG decoder's %u coefficient slots per frame", c->cfg.max_src_w, c->cfg.max_src_h, kJpegMaxCoefs);
         return RFD_ERR_CAPACITY;
     }
-    const size_t bytes = B * sizeof(JpegFrame) + B * blocks * (sizeof(uint32_t) + 64 * sizeof(int16_t));
+    const size_t tables = (B * sizeof(JpegFrame) + B * blocks * (sizeof(uint32_t) + 64 * sizeof(int16_t)) + 15) & ~(size_t)15;
+    const size_t bytes = tables + B * (sizeof(JpegOrientedFrame) + sizeof(JpegFrame));
     RFD_TRY(c->jpeg_pin_done.create());
     RFD_TRY(c->jpeg_dev.reserve(bytes));
     RFD_TRY(c->jpeg_planes.reserve(B * blocks * 64));
     RFD_TRY(c->jpeg_pin.alloc(bytes));
     c->jpeg_blocks_max = blocks;
+    c->jpeg_tables_off = tables;
     return RFD_OK;
 }
 
@@ -2726,20 +2742,29 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
     RFD_CHECK_ARG(bytes && len && out, "null argument");
     RFD_TRY(check_batch(c, n, "batch of", " files"));
     std::unique_ptr<JpegHeader[]> hdr(new JpegHeader[(size_t)n]);
+    std::vector<int32_t> orient((size_t)n, 1); // what the call applies: the tag in APPLY mode
+    std::vector<int> ow((size_t)n), oh((size_t)n); // the size of the frame it writes
+    int n_oriented = 0;
     for (int i = 0; i < n; ++i) {
         const int st = jpeg_parse_header(bytes[i], len[i], hdr[i]);
         if (st != RFD_OK) { set_error("file %d: %s", i, hdr[i].msg); return st; }
         const JpegHeader &h = hdr[i];
+        if (c->jpeg_orientation == RFD_JPEG_ORIENTATION_APPLY) orient[(size_t)i] = h.orientation;
+        jpeg_oriented_size(orient[(size_t)i], h.width, h.height, &ow[(size_t)i], &oh[(size_t)i]);
+        n_oriented += orient[(size_t)i] != 1;
         if (h.width > c->cfg.max_src_w || h.height > c->cfg.max_src_h) {
             set_error("file %d: %d x %d exceeds max_src %d x %d", i, h.width, h.height, c->cfg.max_src_w, c->cfg.max_src_h);
             return RFD_ERR_CAPACITY;
         }
         if (!out[i].data) { set_error("invalid argument: output frame %d has no data pointer", i); return RFD_ERR_INVALID_ARG; }
-        if (out[i].width != h.width || out[i].height != h.height) {
-            set_error("invalid argument: output frame %d is %d x %d, file %d is %d x %d", i, out[i].width, out[i].height, i, h.width, h.height);
+        if (out[i].width != ow[(size_t)i] || out[i].height != oh[(size_t)i]) {
+            if (orient[(size_t)i] == 1) set_error("invalid argument: output frame %d is %d x %d, file %d is %d x %d", i, out[i].width, out[i].height, i, h.width, h.height);
+            else
+                set_error("invalid argument: output frame %d is %d x %d, file %d is %d x %d in orientation %d (%d x %d stored)", i, out[i].width, out[i].height, i,
+                          ow[(size_t)i], oh[(size_t)i], orient[(size_t)i], h.width, h.height);
             return RFD_ERR_INVALID_ARG;
         }
-        if (out[i].stride < (ptrdiff_t)h.width * 3) { set_error("invalid argument: output frame %d has stride %td < 3 * width", i, out[i].stride); return RFD_ERR_INVALID_ARG; }
+        if (out[i].stride < (ptrdiff_t)ow[(size_t)i] * 3) { set_error("invalid argument: output frame %d has stride %td < 3 * width", i, out[i].stride); return RFD_ERR_INVALID_ARG; }
     }
     RFD_HIP(hipSetDevice(c->cfg.device_id));
     RFD_TRY(jpeg_stage_alloc(c));
@@ -2756,6 +2781,7 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
     size_t blocks = 0, out_bytes = 0;
     for (int i = 0; i < n; ++i) { rec0[(size_t)i] = blocks; blocks += (size_t)hdr[i].nblocks; out_bytes += (size_t)hdr[i].width * 3 * hdr[i].height; }
     c->jpeg_paths.assign((size_t)n, 0);
+    c->jpeg_orientations = orient;
     // one frame per task; the workers touch nothing but their frame's bytes, header and slices of the staging
     auto decode_on_host = [&](int i) {
         status[(size_t)i] = jpeg_decode_scan(bytes[i], len[i], hdr[i], rec + rec0[(size_t)i], coef + rec0[(size_t)i] * 64, &used[(size_t)i]);
@@ -2795,8 +2821,14 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
     for (int i = 0; i < n; ++i)
         if (status[(size_t)i] != RFD_OK) { set_error("file %d: %s", i, hdr[i].msg); return status[(size_t)i]; }
     if (!out_on_device) RFD_TRY(c->jpeg_out.reserve(out_bytes));
-    JpegParams p;
+    JpegParams p, upright;
+    JpegOrientedParams oriented;
     memset(&p, 0, sizeof p);
+    memset(&upright, 0, sizeof upright);
+    memset(&oriented, 0, sizeof oriented);
+    // the tables of the colour launches where a frame is oriented: each launch lists only the frames that have a workgroup in it
+    JpegOrientedFrame *ofr = (JpegOrientedFrame *)(c->jpeg_pin.p + c->jpeg_tables_off);
+    JpegFrame *ufr = (JpegFrame *)(ofr + B);
     size_t out_at = 0;
     for (int i = 0; i < n; ++i) {
         const JpegHeader &h = hdr[i];
@@ -2807,7 +2839,7 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
             f.stride = (long long)out[i].stride;
         } else {
             f.out = (uint8_t *)c->jpeg_out.p + out_at;
-            f.stride = (long long)h.width * 3;
+            f.stride = (long long)ow[(size_t)i] * 3;
             out_at += (size_t)h.width * 3 * h.height;
         }
         f.rec0 = rec0[(size_t)i]; f.coef0 = rec0[(size_t)i] * 64; f.plane0 = rec0[(size_t)i] * 64;
@@ -2820,6 +2852,20 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
         for (int k = 0; k < h.ncomp; ++k) {
             f.bw[k] = h.comp[k].bw; f.bh[k] = h.comp[k].bh; f.blk0[k] = h.comp[k].blk0;
             for (int z = 0; z < 64; ++z) f.quant[k][kJpegNatural[z]] = h.quant[h.comp[k].tq][z];
+        }
+        if (!n_oriented) continue;
+        if (orient[(size_t)i] == 1) {
+            JpegFrame &u = ufr[upright.n++];
+            u = f;
+            u.tile0 = upright.tiles;
+            upright.tiles += p.tiles - f.tile0;
+        } else {
+            JpegOrientedFrame &of = ofr[oriented.n++];
+            of.frame = i;
+            of.orientation = orient[(size_t)i];
+            of.tile0 = oriented.tiles;
+            of.tiles_x = jpeg_oriented_tiles_x(ow[(size_t)i]);
+            oriented.tiles += of.tiles_x * jpeg_oriented_tiles_x(oh[(size_t)i]);
         }
     }
     char *dev = (char *)c->jpeg_dev.p;
@@ -2837,6 +2883,9 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
             if (used[(size_t)i])
                 RFD_HIP(hipMemcpyAsync(dev + coef_off + rec0[(size_t)i] * 64 * sizeof(int16_t), coef + rec0[(size_t)i] * 64, (size_t)used[(size_t)i] * sizeof(int16_t),
                                        hipMemcpyHostToDevice, c->stream));
+        if (n_oriented)
+            RFD_HIP(hipMemcpyAsync(dev + c->jpeg_tables_off, ofr, B * sizeof(JpegOrientedFrame) + (size_t)upright.n * sizeof(JpegFrame), hipMemcpyHostToDevice,
+                                   c->stream));
         return RFD_OK;
     };
     const int copied = copies();
@@ -2849,14 +2898,22 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
     p.rec = (const uint32_t *)(dev + rec_off);
     p.coef = (const int16_t *)(dev + coef_off);
     p.planes = (uint8_t *)c->jpeg_planes.p;
-    RFD_TRY(launch_jpeg_decode(p, c->stream));
+    if (!n_oriented) RFD_TRY(launch_jpeg_decode(p, c->stream));
+    else {
+        upright.frames = (const JpegFrame *)(dev + c->jpeg_tables_off + B * sizeof(JpegOrientedFrame));
+        upright.rec = p.rec; upright.coef = p.coef; upright.planes = p.planes;
+        oriented.frames = p.frames;
+        oriented.oriented = (const JpegOrientedFrame *)(dev + c->jpeg_tables_off);
+        oriented.planes = p.planes;
+        RFD_TRY(launch_jpeg_decode_oriented(p, upright, oriented, c->stream));
+    }
     if (!out_on_device) {
         out_at = 0;
         for (int i = 0; i < n; ++i) {
-            const size_t row = (size_t)hdr[i].width * 3;
-            RFD_HIP(hipMemcpy2DAsync(const_cast<uint8_t *>(out[i].data), (size_t)out[i].stride, (const uint8_t *)c->jpeg_out.p + out_at, row, row, (size_t)hdr[i].height,
+            const size_t row = (size_t)ow[(size_t)i] * 3;
+            RFD_HIP(hipMemcpy2DAsync(const_cast<uint8_t *>(out[i].data), (size_t)out[i].stride, (const uint8_t *)c->jpeg_out.p + out_at, row, row, (size_t)oh[(size_t)i],
                                      hipMemcpyDeviceToHost, c->stream));
-            out_at += row * hdr[i].height;
+            out_at += row * oh[(size_t)i];
         }
     }
     if (async && out_on_device) return RFD_OK;
@@ -2869,6 +2926,25 @@ int rfd_set_jpeg_entropy(rfd_ctx *c, int mode)
     RFD_CHECK_ARG(c, "ctx is null");
     if (mode != RFD_JPEG_ENTROPY_HOST && mode != RFD_JPEG_ENTROPY_DEVICE) { set_error("invalid argument: JPEG entropy mode %d (0: host, 1: device)", mode); return RFD_ERR_INVALID_ARG; }
     c->jpeg_entropy = mode;
+    return RFD_OK;
+}
+
+int rfd_set_jpeg_orientation(rfd_ctx *c, int mode)
+{
+    RFD_CHECK_ARG(c, "ctx is null");
+    if (mode != RFD_JPEG_ORIENTATION_IGNORE && mode != RFD_JPEG_ORIENTATION_APPLY) { set_error("invalid argument: JPEG orientation mode %d (0: ignore, 1: apply)", mode); return RFD_ERR_INVALID_ARG; }
+    c->jpeg_orientation = mode;
+    return RFD_OK;
+}
+
+int rfd_jpeg_last_orientations(rfd_ctx *c, int32_t *orientation, int cap, int *n)
+{
+    RFD_CHECK_ARG(c, "ctx is null");
+    RFD_CHECK_ARG(cap >= 0 && (orientation || cap == 0), "orientation is null");
+    const int have = (int)c->jpeg_orientations.size();
+    if (n) *n = have;
+    if (have > cap) { set_error("the last decode call had %d frames, the output holds %d", have, cap); return RFD_ERR_CAPACITY; }
+    for (int i = 0; i < have; ++i) orientation[i] = c->jpeg_orientations[(size_t)i];
     return RFD_OK;
 }
 

@@ -59,6 +59,7 @@ struct JpegHeader {
     bool have_quant[4] = {false, false, false, false};
     JpegHuff dc[4], ac[4];
     size_t scan = 0; // the first entropy-coded byte
+    int orientation = 1; // the EXIF orientation tag, 1..8 (jpeg_exif_orientation); 1 where the file has none
     char msg[200] = "";
 
     int fail(int status, const char *fmt, ...)
@@ -95,13 +96,43 @@ inline bool jpeg_build_huff(JpegHuff &t, const uint8_t bits[17], const uint8_t *
     return true;
 }
 
+// The orientation tag (0x0112) of an Exif APP1 payload p[0 .. n), which begins with "Exif\0\0": a TIFF header (byte order, 42,
+// the offset of IFD0 from the start of the header) and IFD0, a 16-bit count of 12-byte entries (tag, type, count, value).  The
+// first entry with the tag counts, if it is one SHORT or one LONG with a value of 1..8; 1 in every other case -- EXIF damage is
+// never a reason to refuse a file (libjpeg, OpenCV and Pillow agree).  Every read is checked against the payload first, in size_t
+// sums of values below 2^32 + 2^20, which cannot wrap.
+inline int jpeg_exif_orientation(const uint8_t *p, size_t n)
+{
+    if (n < 6 + 8) return 1;
+    const uint8_t *t = p + 6; // the TIFF block: offsets count from here
+    const size_t tn = n - 6;
+    const bool le = t[0] == 'I' && t[1] == 'I';
+    if (!le && !(t[0] == 'M' && t[1] == 'M')) return 1;
+    auto u16 = [&](size_t at) -> uint32_t { return le ? (uint32_t)t[at] | (uint32_t)t[at + 1] << 8 : (uint32_t)t[at] << 8 | t[at + 1]; };
+    auto u32 = [&](size_t at) -> uint32_t { return le ? u16(at) | u16(at + 2) << 16 : u16(at) << 16 | u16(at + 2); };
+    if (u16(2) != 42) return 1;
+    const size_t ifd = u32(4);
+    if (ifd > tn || tn - ifd < 2) return 1;
+    const size_t entries = u16(ifd);
+    for (size_t e = 0; e < entries; ++e) {
+        const size_t at = ifd + 2 + 12 * e; // below 2^32 + 2 + 12 * 65535
+        if (at > tn || tn - at < 12) return 1; // the directory runs past the payload
+        if (u16(at) != 0x0112) continue;
+        const uint32_t type = u16(at + 2), count = u32(at + 4);
+        if (count != 1 || (type != 3 && type != 4)) return 1;
+        const uint32_t v = type == 3 ? u16(at + 8) : u32(at + 8);
+        return v >= 1 && v <= 8 ? (int)v : 1;
+    }
+    return 1;
+}
+
 // Walks the markers from SOI to the end of the SOS header and validates every one of them.
 inline int jpeg_parse_header(const uint8_t *d, size_t len, JpegHeader &h)
 {
     if (!d) return h.fail(RFD_ERR_INVALID_ARG, "invalid argument: the JPEG data pointer is null");
     if (len < 2 || d[0] != 0xff || d[1] != 0xd8) return h.fail(RFD_ERR_INVALID_ARG, "not a JPEG file: no SOI marker at byte 0");
     size_t pos = 2;
-    bool have_sof = false;
+    bool have_sof = false, have_exif = false;
     for (;;) {
         if (pos >= len) return h.fail(RFD_ERR_INVALID_ARG, "truncated: the data ends at byte %zu, before any SOS marker", len);
         if (d[pos] != 0xff) return h.fail(RFD_ERR_INVALID_ARG, "expected a marker at byte %zu, found 0x%02x", pos, d[pos]);
@@ -223,7 +254,13 @@ inline int jpeg_parse_header(const uint8_t *d, size_t len, JpegHeader &h)
             h.scan = pos + L;
             return RFD_OK;
         }
-        default: break; // APPn, COM and every other marker with a length: skipped
+        case 0xe1: // APP1: the first one that is Exif is asked for the orientation, whatever it answers
+            if (!have_exif && n >= 6 && memcmp(seg, "Exif\0\0", 6) == 0) {
+                have_exif = true;
+                h.orientation = jpeg_exif_orientation(seg, n);
+            }
+            break;
+        default: break; // every other APPn, COM and every other marker with a length: skipped
         }
         pos += L;
     }
@@ -353,6 +390,31 @@ inline int jpeg_decode_scan(const uint8_t *d, size_t len, JpegHeader &h, uint32_
         }
     }
     *used = off;
+    return RFD_OK;
+}
+
+// the stored size of a w x h file in orientation o -> the size of the oriented frame: 5..8 transpose
+inline void jpeg_oriented_size(int o, int w, int h, int *ow, int *oh)
+{
+    *ow = o >= 5 ? h : w;
+    *oh = o >= 5 ? w : h;
+}
+
+// the same validation: rfd_jpeg_orientation
+inline int jpeg_orientation(const uint8_t *d, size_t len, struct rfd_jpeg_orientation *out, char *msg, size_t msg_cap)
+{
+    std::unique_ptr<JpegHeader> h(new JpegHeader);
+    const int st = jpeg_parse_header(d, len, *h);
+    if (st != RFD_OK) {
+        snprintf(msg, msg_cap, "%s", h->msg);
+        return st;
+    }
+    if (out) {
+        memset(out, 0, sizeof *out);
+        out->orientation = h->orientation;
+        jpeg_oriented_size(h->orientation, h->width, h->height, &out->width, &out->height);
+        out->stored_width = h->width; out->stored_height = h->height;
+    }
     return RFD_OK;
 }
 

@@ -239,6 +239,27 @@ constexpr int kJpegGroupBlocks = 32;  // 8 lanes per block
 constexpr int kJpegTilePixels = 1024; // one thread per 4 pixels of a row
 // kernel 1: zigzag run -> dequantise -> libjpeg's accurate integer IDCT -> u8 planes; kernel 2: fancy upsampling + YCbCr -> BGR
 int launch_jpeg_decode(const JpegParams &p, hipStream_t s);
+// EXIF orientation (rfd.h, "EXIF orientation").  A frame of orientation 2..8 takes jpeg_color_oriented_kernel instead of the colour
+// kernel.  Every frame of a launch's table needs at least one workgroup there, so each colour launch has a table of its own: the
+// oriented one below, which points into the batch's JpegFrame table, and for the upright frames a second JpegFrame table that
+// holds only them.  JpegFrame and JpegParams are what they were, so the two kernels that read them are too.
+struct JpegOrientedFrame {
+    int frame;       // index in JpegOrientedParams::frames: sizes (STORED width and height), planes, out, stride
+    int orientation; // 2..8
+    int tile0;       // the frame's first workgroup in the oriented launch
+    int tiles_x;     // tiles per row of tiles of the ORIENTED frame
+};
+struct JpegOrientedParams {
+    const JpegFrame *frames;           // device: the whole batch, as the inverse DCT reads it
+    const JpegOrientedFrame *oriented; // device [n]
+    int n, tiles;
+    const uint8_t *planes;
+};
+constexpr int kJpegOrientTile = 64; // a workgroup's square of OUTPUT pixels; origins are multiples of it
+inline int jpeg_oriented_tiles_x(int out_w) { return (out_w + kJpegOrientTile - 1) / kJpegOrientTile; }
+// a batch with at least one oriented frame: the inverse DCT over p, the colour kernel over `upright` (its own frame table and
+// tile count, the pools of p; skipped where upright.n is 0), the oriented kernel over o
+int launch_jpeg_decode_oriented(const JpegParams &p, const JpegParams &upright, const JpegOrientedParams &o, hipStream_t s);
 
 // ---------------------------------------------------------------- JPEG entropy decode (kernels_jpeg_entropy.hip)
 // Huffman decoding of restart-interval files, one thread per interval (jpeg_entropy.h).  One frame of a batch that takes this

@@ -1,7 +1,8 @@
 // kernels_jpeg.hip -- the parallel half of the baseline JPEG decoder (rfd.h, "JPEG decode"), gfx950.
 //
-// Two launches per batch, whatever the number, sizes and samplings of its frames: every workgroup finds its frame in the
-// descriptor table (JpegFrame, kernels.h) by its own index, as the liveness crops do.
+// Two launches per batch, whatever the number, sizes and samplings of its frames, and a third where a frame is stored through
+// an EXIF orientation: every workgroup finds its frame in the descriptor table (JpegFrame, kernels.h) by its own index, as the
+// liveness crops do.
 //   jpeg_idct_kernel   8 lanes per 8x8 block, 32 blocks per workgroup.  Lane j gathers column j of the block from the block's
 //                      truncated zigzag run (positions past the run are zero), dequantises, runs the column pass of
 //                      jidctint.c, hands the result over through LDS, runs the row pass on row j and stores its 8 samples as
@@ -9,6 +10,8 @@
 //   jpeg_color_kernel  one thread per 4 pixels of an output row: h2v1 / h2v2 fancy upsampling (jdsample.c) of the two chroma
 //                      planes, jdcolor.c's fixed-point YCbCr -> RGB, three 4-byte stores of B,G,R bytes (single bytes where the
 //                      row is not 4-byte aligned or the image ends inside the quad).
+//   jpeg_color_oriented_kernel  frames of orientation 2..8 (rfd.h, "EXIF orientation"): the same pixels, computed along stored
+//                      rows into an LDS tile and stored along output rows; described at the kernel.
 // All arithmetic is 32-bit integer.  The IDCT computes in unsigned words, so that coefficients no 8-bit image produces wrap
 // instead of overflowing a signed type; nothing indexes memory with a data-dependent value except the zigzag run, whose
 // length is masked to 64 and whose extent the host sized.
@@ -181,7 +184,98 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(JpegParams p)
     }
 }
 
+// EXIF orientation 2..8: the pixels of jpeg_color_kernel, stored through the index map of rfd.h ("EXIF orientation").  A workgroup
+// owns a kJpegOrientTile square of the OUTPUT frame, whose origin is a multiple of the tile and so of 4.  The square is the image
+// of a rectangle of the stored frame (mirrored and, for 5..8, transposed); that rectangle may start at any x, and chroma_quad wants
+// a multiple of 4, so the workgroup computes the quads that enclose it: up to 17 per row, 16 where the stored width is a multiple
+// of 4.  It walks them along STORED rows, so the plane reads are row-contiguous as in jpeg_color_kernel, and parks each pixel as
+// one B | G << 8 | R << 16 word in LDS.  After the barrier it walks OUTPUT rows: a thread gathers four neighbouring output pixels
+// and stores them by jpeg_color_kernel's rule.  A wave stores 4 rows of 192 contiguous bytes.
+// LDS pitch 69 words.  The gather is 32-bit reads, which bank by (word mod 32) within each half of a wave.  A half covers 8 quads
+// x 4 output rows.  Transposed (5..8), pixel i of quad q in row r reads word +-(4 q + i) * 69 +- r + c: 4 * 69 q = 20 q (mod 32)
+// runs over the eight multiples of 4 and r fills the residues, 32 distinct banks.  Not transposed, it reads word +-69 r +- (4 q +
+// i) + c = +-5 r +- 4 q (mod 32), distinct again.  The writes of the first phase (16 quads x 2 rows per half, words 69 ry + 4 q + i)
+// are 2-way: q and q + 8 share a bank.
+constexpr int kOrientPitch = kJpegOrientTile + 5;
+
+__global__ __launch_bounds__(256) void jpeg_color_oriented_kernel(JpegOrientedParams p)
+{
+    constexpr int T = kJpegOrientTile;
+    __shared__ uint32_t px[T * kOrientPitch];
+    const int t = blockIdx.x;
+    int lo = 0, hi = p.n - 1; // the frame whose first tile is the last one <= t: tile0 ascends strictly
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (p.oriented[mid].tile0 <= t) lo = mid; else hi = mid - 1;
+    }
+    const JpegOrientedFrame &of = p.oriented[lo];
+    const JpegFrame &f = p.frames[of.frame];
+    const int W = f.width, H = f.height, o = of.orientation; // W, H: the STORED size
+    const bool transposed = o >= 5, flipx = o == 2 || o == 3 || o == 7 || o == 8, flipy = o == 3 || o == 4 || o == 6 || o == 7;
+    const int Wo = transposed ? H : W, Ho = transposed ? W : H;
+    const int tl = t - of.tile0, ty = tl / of.tiles_x, tx = tl - ty * of.tiles_x;
+    const int X0 = tx * T, Y0 = ty * T, X1 = min(X0 + T, Wo) - 1, Y1 = min(Y0 + T, Ho) - 1; // the tile's output pixels, inclusive
+    // the stored rectangle [sx0, sx1] x [sy0, sy1] they come from
+    const int a0 = transposed ? Y0 : X0, a1 = transposed ? Y1 : X1, b0 = transposed ? X0 : Y0, b1 = transposed ? X1 : Y1;
+    const int sx0 = flipx ? W - 1 - a1 : a0, sx1 = flipx ? W - 1 - a0 : a1, sy0 = flipy ? H - 1 - b1 : b0, sy1 = flipy ? H - 1 - b0 : b1;
+    const int sxa = sx0 & ~3, nq = ((sx1 - sxa) >> 2) + 1, rows = sy1 - sy0 + 1; // nq <= 17: word 4 * 16 + 3 < kOrientPitch; rows <= T
+    const uint8_t *base = p.planes + f.plane0;
+    const int hmax = f.hmax, vmax = f.vmax, dw = (W + hmax - 1) / hmax, dh = (H + vmax - 1) / vmax, pwc = f.bw[1] * 8;
+    for (int k = (int)threadIdx.x; k < nq * rows; k += 256) {
+        const int ry = k / nq, y = sy0 + ry, x0 = sxa + (k - ry * nq) * 4; // x0 <= sx1 < W
+        const uint8_t *yr = base + (size_t)y * (f.bw[0] * 8) + x0;        // x0 + 3 stays inside the row: the plane is padded to whole blocks
+        const int Y0s = yr[0], Y1s = yr[1], Y2s = yr[2], Y3s = yr[3];
+        uint32_t *w = px + ry * kOrientPitch + (x0 - sxa);
+        if (f.ncomp == 1) {
+            w[0] = (uint32_t)Y0s * 0x010101u; w[1] = (uint32_t)Y1s * 0x010101u; w[2] = (uint32_t)Y2s * 0x010101u; w[3] = (uint32_t)Y3s * 0x010101u;
+        } else {
+            const Quad cb = chroma_quad(base + (size_t)f.blk0[1] * 64, pwc, hmax, vmax, dw, dh, x0, y);
+            const Quad cr = chroma_quad(base + (size_t)f.blk0[2] * 64, pwc, hmax, vmax, dw, dh, x0, y);
+            w[0] = bgr_of(Y0s, cb.a, cr.a); w[1] = bgr_of(Y1s, cb.b, cr.b); w[2] = bgr_of(Y2s, cb.c, cr.c); w[3] = bgr_of(Y3s, cb.d, cr.d);
+        }
+    }
+    __syncthreads();
+    // one output pixel to the right is this many words further in LDS
+    const int step = transposed ? (flipy ? -kOrientPitch : kOrientPitch) : (flipx ? -1 : 1);
+    for (int k = (int)threadIdx.x; k < T * T / 4; k += 256) {
+        const int xo = X0 + 4 * ((k & 7) | (k >> 2 & 8)), yo = Y0 + ((k >> 3 & 3) | (k >> 6) << 2); // a half wave: 8 quads x 4 rows
+        if (xo > X1 || yo > Y1) continue;
+        const int a = transposed ? yo : xo, b = transposed ? xo : yo;
+        const int at = ((flipy ? H - 1 - b : b) - sy0) * kOrientPitch + (flipx ? W - 1 - a : a) - sxa;
+        uint32_t v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = xo + i <= X1 ? px[at + i * step] : 0u; // X1 <= Wo - 1: a pixel beyond the row has no word
+        uint8_t *dst = f.out + (long long)yo * f.stride + (long long)xo * 3;
+        if (xo + 3 < Wo && (reinterpret_cast<uintptr_t>(dst) & 3) == 0) {
+            uint32_t *d4 = reinterpret_cast<uint32_t *>(dst); // B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3
+            d4[0] = v[0] | v[1] << 24;
+            d4[1] = v[1] >> 8 | v[2] << 16;
+            d4[2] = v[2] >> 16 | v[3] << 8;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (xo + i < Wo) { dst[3 * i] = (uint8_t)v[i]; dst[3 * i + 1] = (uint8_t)(v[i] >> 8); dst[3 * i + 2] = (uint8_t)(v[i] >> 16); }
+        }
+    }
+}
+
 } // namespace
+
+int launch_jpeg_decode_oriented(const JpegParams &p, const JpegParams &upright, const JpegOrientedParams &o, hipStream_t s)
+{
+    if (p.n < 1) return RFD_OK;
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)p.groups), dim3(256), 0, s, p);
+    RFD_HIP(hipGetLastError());
+    if (upright.n > 0) {
+        hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)upright.tiles), dim3(256), 0, s, upright);
+        RFD_HIP(hipGetLastError());
+    }
+    if (o.n > 0) {
+        hipLaunchKernelGGL(jpeg_color_oriented_kernel, dim3((unsigned)o.tiles), dim3(256), 0, s, o);
+        RFD_HIP(hipGetLastError());
+    }
+    return RFD_OK;
+}
 
 int launch_jpeg_decode(const JpegParams &p, hipStream_t s)
 {

@@ -27,6 +27,7 @@ RFD_ERR_UNSUPPORTED = -8
 JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = 0, 1, 2, 3   # rfd_jpeg_sampling
 JPEG_ENTROPY_HOST, JPEG_ENTROPY_DEVICE = 0, 1           # rfd_jpeg_entropy
 JPEG_PATH_HOST, JPEG_PATH_DEVICE, JPEG_PATH_REFUSED = 0, 1, 2   # rfd_jpeg_last_paths
+JPEG_ORIENTATION_IGNORE, JPEG_ORIENTATION_APPLY = 0, 1  # rfd_jpeg_orientation_mode
 COMM_ID_BYTES = 128
 MAX_FACE_TENSORS = 4   # RFD_MAX_FACE_TENSORS
 GALLERY_MAX_K = 32     # RFD_GALLERY_MAX_K
@@ -118,6 +119,11 @@ class rfd_jpeg_info(C.Structure):
                 ("restart_interval", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class rfd_jpeg_orientation(C.Structure):
+    _fields_ = [("orientation", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("stored_width", C.c_int32),
+                ("stored_height", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class rfd_tensor_desc(C.Structure):
     _fields_ = [("channels", C.c_int), ("height", C.c_int), ("width", C.c_int),
                 ("is_f32", C.c_int), ("buffer", C.c_int), ("is_input", C.c_int),
@@ -150,6 +156,7 @@ API_SYMBOLS = [
     "rfd_gallery_save", "rfd_gallery_load", "rfd_gallery_file_info",
     "rfd_jpeg_info", "rfd_decode_jpeg_batch_device", "rfd_decode_jpeg_batch", "rfd_set_decode_threads", "rfd_debug_jpeg_coefficients",
     "rfd_set_jpeg_entropy", "rfd_jpeg_last_paths", "rfd_debug_jpeg_intervals", "rfd_debug_jpeg_coefficients_device",
+    "rfd_jpeg_orientation", "rfd_set_jpeg_orientation", "rfd_jpeg_last_orientations",
 ]
 
 _lib = None
@@ -283,6 +290,9 @@ def load_library(path=None):
     L.rfd_jpeg_last_paths.argtypes = [vp, vp, ci, C.POINTER(ci)]
     L.rfd_debug_jpeg_intervals.argtypes = [vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rfd_debug_jpeg_coefficients_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rfd_jpeg_orientation.argtypes = [vp, C.c_size_t, C.POINTER(rfd_jpeg_orientation)]
+    L.rfd_set_jpeg_orientation.argtypes = [vp, ci]
+    L.rfd_jpeg_last_orientations.argtypes = [vp, vp, ci, C.POINTER(ci)]
     if path is None:
         _lib = L
     return L
@@ -409,6 +419,17 @@ def jpeg_info(data):
     _check(load_library().rfd_jpeg_info(addr, n, C.byref(info)))
     return dict(width=info.width, height=info.height, components=info.components, sampling=info.sampling,
                 restart_interval=info.restart_interval)
+
+
+def jpeg_orientation(data):
+    """the EXIF orientation of a JPEG file (bytes) after the same validation as jpeg_info (rfd_jpeg_orientation; host only, no
+    GPU) -> dict(orientation = 1..8, width, height = the size of the frame a decode in "apply" mode writes (swapped for 5..8),
+    stored_width, stored_height).  A file without a usable tag has orientation 1; EXIF damage never refuses a file."""
+    keep, addr, n = _byte_buffer(data)
+    o = rfd_jpeg_orientation()
+    _check(load_library().rfd_jpeg_orientation(addr, n, C.byref(o)))
+    return dict(orientation=o.orientation, width=o.width, height=o.height, stored_width=o.stored_width,
+                stored_height=o.stored_height)
 
 
 def jpeg_coefficients(data):
@@ -638,6 +659,7 @@ class RetinaFaceDetection:
         _check(self._L.rfd_create(C.byref(cfg), C.byref(self._ctx)))
         self.image_size = (cfg.image_w, cfg.image_h)
         self.max_det = cfg.max_det
+        self._jpeg_apply_orientation = False   # set_jpeg_orientation: decode_jpeg allocates by the oriented size
 
     def gallery(self, dim=512, capacity=1 << 20):
         """a face gallery on this detector's device and stream (rfd_gallery_create); it is closed with the detector at the latest"""
@@ -788,6 +810,24 @@ class RetinaFaceDetection:
         modes = {"host": JPEG_ENTROPY_HOST, "device": JPEG_ENTROPY_DEVICE}
         _check(self._L.rfd_set_jpeg_entropy(self._ctx, modes[mode] if mode in modes else int(mode)))
 
+    def set_jpeg_orientation(self, mode):
+        """"ignore" (default): frames are written as the file stores them, whatever its EXIF orientation tag says; "apply":
+        frames are written upright, in the size jpeg_orientation reports (rfd.h, "EXIF orientation")"""
+        modes = {"ignore": JPEG_ORIENTATION_IGNORE, "apply": JPEG_ORIENTATION_APPLY}
+        mode = modes[mode] if mode in modes else int(mode)
+        _check(self._L.rfd_set_jpeg_orientation(self._ctx, mode))
+        self._jpeg_apply_orientation = mode == JPEG_ORIENTATION_APPLY
+
+    def jpeg_last_orientations(self):
+        """per frame of the last decode call: the orientation that was applied (all 1 in "ignore" mode)"""
+        n = C.c_int(0)
+        st = self._L.rfd_jpeg_last_orientations(self._ctx, None, 0, C.byref(n))
+        if st != RFD_ERR_CAPACITY:
+            _check(st)
+        out = np.zeros(n.value, np.int32)
+        _check(self._L.rfd_jpeg_last_orientations(self._ctx, out.ctypes.data, n.value, C.byref(n)))
+        return out.tolist()
+
     def jpeg_last_paths(self):
         """per frame of the last decode call: 0 host (not eligible), 1 device, 2 host after the device refused the frame"""
         n = C.c_int(0)
@@ -819,12 +859,13 @@ class RetinaFaceDetection:
         return bufs, ptrs, lens
 
     def decode_jpeg(self, files):
-        """list of JPEG files (bytes) -> list of [H, W, 3] u8 BGR host arrays, decoded on the device (a grey file: B = G = R)"""
+        """list of JPEG files (bytes) -> list of [H, W, 3] u8 BGR host arrays, decoded on the device (a grey file: B = G = R);
+        in "apply" mode (set_jpeg_orientation) H, W are the oriented size"""
         bufs, ptrs, lens = self._jpeg_files(files)
         outs = []
         for k, f in enumerate(files):
             try:
-                i = jpeg_info(f)
+                i = jpeg_orientation(f) if self._jpeg_apply_orientation else jpeg_info(f)
             except RfdError as e:   # name the file, as the batch call itself does
                 raise RfdError(e.status, "file %d: %s" % (k, e.message)) from None
             outs.append(np.zeros((i["height"], i["width"], 3), np.uint8))

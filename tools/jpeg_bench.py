@@ -16,9 +16,13 @@ kernel inside, (b) adds jpeg_entropy_kernel, (c) counts the scan bytes and inter
 per-frame paths are printed, so that a run in which the kernel never ran cannot pass for one.  --restart rows writes the
 generated files with a restart interval of one MCU row (Pillow's restart_marker_rows = 1), --restart max with one of
 kJpegDeviceMaxInterval MCUs (restart_marker_blocks); without it the files have no restart interval and stay on the host.
+--orientation N (1..8, default 1) writes an Exif APP1 with that orientation into the generated files and selects
+RFD_JPEG_ORIENTATION_APPLY (rfd.h, "EXIF orientation"), so that the colour stage of (b) is jpeg_color_oriented_kernel for 2..8;
+the files of a directory keep the tags they have.  --no-host skips (a), (c) and (d): the traced child alone.
 
     python tools/jpeg_bench.py [directory] [--files 32] [--reps 5] [--no-trace] [--entropy host|device] [--restart none|rows|max|MCUs]
-Record the output in profiles/jpeg_decode.txt and profiles/jpeg_entropy_device.txt."""
+                               [--orientation 1..8] [--no-host]
+Record the output in profiles/jpeg_decode.txt, profiles/jpeg_entropy_device.txt and profiles/jpeg_orientation.txt."""
 import argparse
 import glob
 import io
@@ -34,7 +38,14 @@ STREAM_TBS = 6.3   # float4 copy rate of the chip, TB/s
 MAX_INTERVAL = 128   # kJpegDeviceMaxInterval (csrc/jpeg_entropy.h)
 
 
-def make_files(n, restart="none"):
+def exif_app1(orientation):
+    """an Exif APP1 segment whose IFD0 holds the orientation alone: "Exif\\0\\0", II, 42, IFD0 at 8, one SHORT entry"""
+    import struct
+    payload = b"Exif\0\0II" + struct.pack("<HIHHHIHHI", 42, 8, 1, 0x0112, 3, 1, orientation, 0, 0)
+    return b"\xff\xe1" + struct.pack(">H", len(payload) + 2) + payload
+
+
+def make_files(n, restart="none", orientation=1):
     from PIL import Image
     out = []
     for i in range(n):
@@ -48,21 +59,26 @@ def make_files(n, restart="none"):
         buf = io.BytesIO()
         kw = {"none": {}, "rows": dict(restart_marker_rows=1), "max": dict(restart_marker_blocks=MAX_INTERVAL)}.get(restart) if not str(restart).isdigit() else dict(restart_marker_blocks=int(restart))
         Image.fromarray(np.clip(img, 0, 255).astype(np.uint8)).save(buf, "JPEG", quality=90, subsampling=2, **kw)
-        out.append(buf.getvalue())
+        data = buf.getvalue()
+        out.append(data[:2] + exif_app1(orientation) + data[2:] if orientation != 1 else data)
     return out
 
 
 def load_files(a):
     if a.directory:
         return [open(f, "rb").read() for f in sorted(glob.glob(os.path.join(a.directory, "*.jpg")))[:a.files]]
-    return make_files(a.files, a.restart)
+    return make_files(a.files, a.restart, a.orientation)
 
 
-def open_detector(R, files, entropy="host"):
+def open_detector(R, files, entropy="host", orientation=1):
+    """the frames are allocated in the size the decode writes: the oriented one when --orientation selects APPLY"""
     import torch
     infos = [R.jpeg_info(f) for f in files]
     det = R.RetinaFaceDetection(max_batch_size=len(files), max_src=(max(i["width"] for i in infos), max(i["height"] for i in infos)))
     det.set_jpeg_entropy(entropy)
+    if orientation != 1:
+        det.set_jpeg_orientation("apply")
+        infos = [dict(i, **{k: v for k, v in R.jpeg_orientation(f).items() if k in ("width", "height")}) for i, f in zip(infos, files)]
     dev = torch.device("cuda", 0)
     bufs = [torch.zeros((i["height"], i["width"] * 3), dtype=torch.uint8, device=dev) for i in infos]
     torch.cuda.synchronize()
@@ -74,10 +90,10 @@ def traced_child(a):
     import torch  # noqa: F401  (first: librfd_hip.so then binds to the HIP runtime torch ships)
     import rfd_hip as R
     files = load_files(a)
-    det, infos, bufs, ptrs, shapes = open_detector(R, files, a.entropy)
+    det, infos, bufs, ptrs, shapes = open_detector(R, files, a.entropy, a.orientation)
     for _ in range(1 + a.reps):
         det.decode_jpeg_device(files, ptrs, shapes)
-    print("traced calls %d frames %d" % (1 + a.reps, len(files)))
+    print("traced calls %d frames %d orientations %s" % (1 + a.reps, len(files), sorted(set(det.jpeg_last_orientations()))))
     det.close()
 
 
@@ -108,7 +124,8 @@ def kernel_pass(files, a, h2d_bytes_per_call):
                 fh.write(f)
         out = os.path.join(tmp, "trace")
         r = subprocess.run([exe, "--kernel-trace", "--memory-copy-trace", "--stats", "--output-format", "csv", "-d", out, "--", sys.executable,
-                            os.path.abspath(__file__), tmp, "--files", str(len(files)), "--reps", str(a.reps), "--entropy", a.entropy, "--child"],
+                            os.path.abspath(__file__), tmp, "--files", str(len(files)), "--reps", str(a.reps), "--entropy", a.entropy, "--orientation",
+                            str(a.orientation), "--child"],
                            capture_output=True, text=True, timeout=600)
         if r.returncode != 0 or "traced calls" not in r.stdout:
             print("(b) the traced child failed (exit %d): kernel time not measured\n%s" % (r.returncode, (r.stdout + r.stderr)[-600:]))
@@ -120,10 +137,12 @@ def kernel_pass(files, a, h2d_bytes_per_call):
             return
         floor_us = 19e6 / (STREAM_TBS * 1e12) * 1e6
         total = 0.0
-        for name in ("jpeg_entropy_kernel", "jpeg_idct_kernel", "jpeg_color_kernel"):
+        print("(b) %s" % [l for l in r.stdout.splitlines() if "traced calls" in l][0])
+        colour = "jpeg_color_kernel" if a.orientation == 1 else "jpeg_color_oriented_kernel"   # every file carries the same tag
+        for name in ("jpeg_entropy_kernel", "jpeg_idct_kernel", "jpeg_color_kernel", "jpeg_color_oriented_kernel"):
             hit = [x for x in rows if name in x["Name"]]
             if not hit:
-                if name != "jpeg_entropy_kernel" or a.entropy == "device":
+                if name == colour or name == "jpeg_idct_kernel" or (name == "jpeg_entropy_kernel" and a.entropy == "device"):
                     print("(b) %s is not in the kernel statistics" % name)
                 continue
             us = float(hit[0]["AverageNs"]) / 1e3
@@ -153,6 +172,8 @@ def main():
     ap.add_argument("--no-trace", action="store_true", help="skip (b), the child run under rocprofv3")
     ap.add_argument("--entropy", choices=("host", "device"), default="host", help="where eligible files are entropy-decoded")
     ap.add_argument("--restart", default="none", help="restart interval of the generated files: none, rows (one MCU row), max (kJpegDeviceMaxInterval MCUs) or a number of MCUs")
+    ap.add_argument("--orientation", type=int, choices=range(1, 9), default=1, help="EXIF orientation written into the generated files; 2..8 select APPLY mode")
+    ap.add_argument("--no-host", action="store_true", help="skip (a), (c) and (d): only the child run under rocprofv3")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
@@ -162,7 +183,8 @@ def main():
     files = load_files(a)
     n = len(files)
     infos = [R.jpeg_info(f) for f in files]
-    print("%d files, %.0f KB each on average, first %dx%d sampling %d" % (n, sum(map(len, files)) / n / 1e3, infos[0]["width"], infos[0]["height"], infos[0]["sampling"]))
+    print("%d files, %.0f KB each on average, first %dx%d sampling %d, orientation %d" %
+          (n, sum(map(len, files)) / n / 1e3, infos[0]["width"], infos[0]["height"], infos[0]["sampling"], R.jpeg_orientation(files[0])["orientation"]))
     # (c) transport bytes: 4 per block + 2 per coefficient up to the last non-zero one of its block (in zigzag order)
     zz = np.argsort(np.array([0, 1, 5, 6, 14, 15, 27, 28, 2, 4, 7, 13, 16, 26, 29, 42, 3, 8, 12, 17, 25, 30, 41, 43, 9, 11, 18, 24, 31, 40, 44, 53, 10, 19, 23, 32,
                               39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63]))
@@ -171,9 +193,11 @@ def main():
         nz = R.jpeg_coefficients(f)[:, zz] != 0
         h2d.append(nz.shape[0] * 4 + 2 * int(np.where(nz.any(1), 64 - np.argmax(nz[:, ::-1], 1), 0).sum()))
     decoded = [i["width"] * i["height"] * 3 for i in infos]
+    if a.no_host:
+        return kernel_pass(files, a, float(np.sum(h2d)) + n * 496)
     print("(c) H2D bytes per frame: %.2f MB (records + truncated runs) against %.2f MB decoded = %.1f %%" %
           (np.mean(h2d) / 1e6, np.mean(decoded) / 1e6, 100 * np.sum(h2d) / np.sum(decoded)))
-    det, infos, bufs, ptrs, shapes = open_detector(R, files, a.entropy)
+    det, infos, bufs, ptrs, shapes = open_detector(R, files, a.entropy, a.orientation)
     det.decode_jpeg_device(files, ptrs, shapes)   # allocates the staging, loads the code objects
     paths = det.jpeg_last_paths()
     print("entropy mode %s, restart interval of the first file %d MCUs; paths of the batch: %d host, %d device, %d refused by the device" %
