@@ -614,8 +614,8 @@ struct rfd_jpeg_info {
  * *out untouched.  (The struct shares its name with the function, so C and C++ both spell the type `struct rfd_jpeg_info`.) */
 RFD_API int rfd_jpeg_info(const uint8_t *bytes, size_t len, struct rfd_jpeg_info *out);
 /* Decodes n files into n caller-allocated DEVICE frames: out[i].data is device memory of out[i].height rows of out[i].stride
- * bytes; width and height must equal the file's (the ORIENTED size in RFD_JPEG_ORIENTATION_APPLY mode, "EXIF orientation" below;
- * else RFD_ERR_INVALID_ARG) and stride must be >= 3 * width; bytes of a row beyond 3 * width are not touched.  rfd_image declares data const because every other entry point reads frames; this one
+ * bytes; width and height must equal the file's (the ORIENTED size in RFD_JPEG_ORIENTATION_APPLY mode, "EXIF orientation" below,
+ * the SCALED size after rfd_set_jpeg_scale, "JPEG decode, reduced size" below; else RFD_ERR_INVALID_ARG) and stride must be >= 3 * width; bytes of a row beyond 3 * width are not touched.  rfd_image declares data const because every other entry point reads frames; this one
  * WRITES through it (the library casts the const away).  The same array is then valid input to rfd_detect_batch_device,
  * rfd_detect_faces_device and rfd_liveness_tensors_device on the same stream, with no synchronisation in between.
  * bytes[] / len[] and the files are host memory and may be freed when the call returns.  Entropy decoding happens inside the
@@ -720,6 +720,61 @@ RFD_API int rfd_set_jpeg_orientation(rfd_ctx *ctx, int mode);
 /* The orientation that was applied to each frame of the last rfd_decode_jpeg_batch* call: all 1 in IGNORE mode.  *n = the frames
  * of that call (0 before the first), also when n > cap (then RFD_ERR_CAPACITY, nothing written).  n may be NULL. */
 RFD_API int rfd_jpeg_last_orientations(rfd_ctx *ctx, int32_t *orientation, int cap, int *n);
+
+/* ---- JPEG decode, reduced size (opt-in).  libjpeg's scale_num / scale_denom = 1 / s for s = 2, 4, 8 (cv::IMREAD_REDUCED_COLOR_2 /
+ *      4 / 8, Pillow's draft): the frame is built at 1/s of the stored size directly from the low frequencies of every block by
+ *      a reduced inverse DCT, instead of being decoded in full and shrunk by a filter of the caller's.  The reference decodes
+ *      with IMREAD_UNCHANGED (utils.rs:18), which is full size.  So denominator 1 is the default, in which every call writes,
+ *      copies and launches exactly what it did before the mode existed, and 2 / 4 / 8 is a mode the caller selects; it applies to
+ *      every frame of a call.
+ *      Contract: the pixels equal libjpeg-turbo's at that scale (what Pillow returns after draft()) byte for byte; the same
+ *      things stay outside it as at full size.  With m = 8 / s:
+ *        size        ceil(W / s) x ceil(H / s)
+ *        IDCT size   per component n_c (jdmaster.c): n = m; while n < 8 and (hmax m) mod (h_c n 2) = 0 and (vmax m) mod (v_c n 2) = 0,
+ *                    n doubles.  The component is then upsampled by (hmax m / (h_c n_c), vmax m / (v_c n_c)).
+ *                      sampling   luma n at s = 2 / 4 / 8   chroma n at s = 2 / 4 / 8   remaining chroma upsampling
+ *                      grey       4 / 2 / 1                 --                          --
+ *                      4:4:4      4 / 2 / 1                 4 / 2 / 1                   none
+ *                      4:2:2      4 / 2 / 1                 4 / 2 / 1                   h2v1
+ *                      4:2:0      4 / 2 / 1                 8 / 4 / 2                   none: the chroma grows through its IDCT
+ *        IDCTs       jidctred.c on dequantised coefficients, PASS1_BITS 2, descale(x, k) = (x + 2^(k-1)) >> k, x[r] the frequencies
+ *                    of a column, then of a row of the work array; + 128, clamped to 0..255
+ *                      4 x 4   reads frequencies 0 1 2 3 5 6 7 of each axis.  t0 = x0 << 14, t2 = 15137 x2 - 6270 x6, t10 = t0 + t2,
+ *                              t12 = t0 - t2, a = -1730 x7 + 11893 x5 - 17799 x3 + 8697 x1, c = -4176 x7 - 4926 x5 + 7373 x3 +
+ *                              20995 x1; outputs t10 + c, t12 + a, t12 - a, t10 - c; descale by 12, then by 19
+ *                      2 x 2   reads 0 1 3 5 7.  t10 = x0 << 15, t0 = -5906 x7 + 6967 x5 - 10426 x3 + 29692 x1; outputs t10 + t0,
+ *                              t10 - t0; descale by 13, then by 20
+ *                      1 x 1   descale(dc, 3)
+ *                      8 x 8   the full-size inverse DCT
+ *        upsampling  the h2v1 left for 4:2:2 is h2v1_fancy_upsample over the component's own ceil(ceil(W / s) / 2) samples at s = 2
+ *                    and 4 (a row of <= 2 samples is replicated); at s = 8 it is plain replication (jdsample.c turns the fancy
+ *                    filter off when the smallest IDCT is 1 x 1).  The colour conversion is the full-size one.
+ *      out[i].width / height must equal the SCALED size, and in RFD_JPEG_ORIENTATION_APPLY mode the scaled and then oriented size
+ *      (rfd_jpeg_scaled_size reports it), else RFD_ERR_INVALID_ARG naming the frame, with nothing enqueued and no frame written;
+ *      stride, alignment and the promise that no byte beyond 3 * width of a row is touched hold for the scaled frame.
+ *      Orientation composes: the stored image is scaled, then the index map of "EXIF orientation" is applied to the scaled image.
+ *      The capacity check against max_src_w / max_src_h stays on the STORED size, which is what the decoder's pools are sized by:
+ *      a reduced decode needs a context as large as a full one.  A scaled frame is an ordinary frame to the detect, faces and
+ *      liveness calls.  Boxes and landmarks are then in the scaled frame's coordinates; multiply by s to map them back, which is
+ *      exact up to the rounding up of the size at the right and bottom edges (less than s stored pixels).
+ *      What it saves is frame bytes, plane bytes, coefficient bytes on PCIe (a block's run ends at the last non-zero coefficient
+ *      its IDCT reads) and kernel time.  It saves NO host time: the Huffman decoder still parses every code of every block. ---- */
+struct rfd_jpeg_scaled_size {
+    int32_t denom;                       /* as given */
+    int32_t width, height;               /* of the frame a decode writes: ceil(stored / denom), swapped for orientations 5..8 in APPLY mode */
+    int32_t stored_width, stored_height; /* as rfd_jpeg_info reports them */
+    int32_t orientation;                 /* the one that will be applied: the tag in APPLY mode, 1 in IGNORE mode */
+    int32_t reserved[2];                 /* 0 */
+};
+/* 1 is the default; any other value than 1, 2, 4, 8: RFD_ERR_INVALID_ARG.  May be changed between calls. */
+RFD_API int rfd_set_jpeg_scale(rfd_ctx *ctx, int denom);
+/* Host only, no context, no device: the header validation of rfd_jpeg_info with the same statuses and messages, then the size of
+ * the frame a decode with this denominator and this rfd_jpeg_orientation_mode writes.  A denominator or a mode outside their
+ * sets: RFD_ERR_INVALID_ARG.  A refused file leaves *out untouched. */
+RFD_API int rfd_jpeg_scaled_size(const uint8_t *bytes, size_t len, int denom, int orientation_mode, struct rfd_jpeg_scaled_size *out);
+/* Test hook, host only: the `count` the host entropy decoder puts into each block's record at this denominator (csrc/jpeg_parse.h),
+ * one byte per block in the block order and with the capacity convention of rfd_debug_jpeg_coefficients. */
+RFD_API int rfd_debug_jpeg_block_counts(const uint8_t *bytes, size_t len, int denom, uint8_t *count, size_t cap_blocks, size_t *blocks);
 
 /* ---- introspection ---- */
 RFD_API int rfd_get_stats(rfd_ctx *ctx, rfd_stats *stats);

@@ -387,8 +387,10 @@ struct DecodedImage {
 };
 inline void set_decode_threads(RetinaFaceDetection &det, int threads) { check(rfd_set_decode_threads(det.raw(), threads)); }
 // files -> host frames, decoded on the device; throws where the reference's imdecode fails.  oriented: the context is in
-// RFD_JPEG_ORIENTATION_APPLY mode (set_jpeg_orientation below), so the frames are allocated in the oriented size
-inline std::vector<DecodedImage> decode_jpeg(RetinaFaceDetection &det, const std::vector<std::vector<uint8_t>> &files, bool oriented = false)
+// RFD_JPEG_ORIENTATION_APPLY mode (set_jpeg_orientation below), so the frames are allocated in the oriented size; denom: the
+// context's set_jpeg_scale, so they are allocated in the scaled size.  Both repeat what the context was told: where they differ
+// from it, the decode refuses the call by its size rule (RFD_ERR_INVALID_ARG naming the frame) and writes nothing
+inline std::vector<DecodedImage> decode_jpeg(RetinaFaceDetection &det, const std::vector<std::vector<uint8_t>> &files, bool oriented = false, int denom = 1)
 {
     const std::size_t n = files.size();
     std::vector<DecodedImage> out(n);
@@ -403,6 +405,11 @@ inline std::vector<DecodedImage> decode_jpeg(RetinaFaceDetection &det, const std
                 struct rfd_jpeg_orientation o;
                 check(rfd_jpeg_orientation(files[i].data(), files[i].size(), &o));
                 info.width = o.width; info.height = o.height;
+            }
+            if (denom != 1) {
+                struct rfd_jpeg_scaled_size z;
+                check(rfd_jpeg_scaled_size(files[i].data(), files[i].size(), denom, oriented ? RFD_JPEG_ORIENTATION_APPLY : RFD_JPEG_ORIENTATION_IGNORE, &z));
+                info.width = z.width; info.height = z.height;
             }
         } catch (const Error &e) { // name the file, as the batch call itself does
             throw Error(e.status, "file " + std::to_string(i) + ": " + e.message);
@@ -446,6 +453,25 @@ inline JpegOrientation jpeg_orientation(const std::vector<uint8_t> &file)
     JpegOrientation r;
     r.orientation = o.orientation; r.width = o.width; r.height = o.height;
     r.stored_width = o.stored_width; r.stored_height = o.stored_height;
+    return r;
+}
+
+// 1 / denom of the stored size, denom 1 (the default), 2, 4 or 8, built by libjpeg's reduced inverse DCTs (rfd.h, "JPEG decode,
+// reduced size"); applies to every frame of the calls that follow
+inline void set_jpeg_scale(RetinaFaceDetection &det, int denom) { check(rfd_set_jpeg_scale(det.raw(), denom)); }
+struct JpegScaledSize {
+    int denom = 1;
+    int width = 0, height = 0;              // of the frame a decode with that denominator and orientation mode writes
+    int stored_width = 0, stored_height = 0;
+    int orientation = 1;                    // the one that will be applied
+};
+inline JpegScaledSize jpeg_scaled_size(const std::vector<uint8_t> &file, int denom, rfd_jpeg_orientation_mode mode = RFD_JPEG_ORIENTATION_IGNORE)
+{
+    struct rfd_jpeg_scaled_size z;
+    check(rfd_jpeg_scaled_size(file.data(), file.size(), denom, (int)mode, &z));
+    JpegScaledSize r;
+    r.denom = z.denom; r.width = z.width; r.height = z.height;
+    r.stored_width = z.stored_width; r.stored_height = z.stored_height; r.orientation = z.orientation;
     return r;
 }
 

@@ -225,6 +225,10 @@ struct rfd_ctx {
     int jpeg_orientation = RFD_JPEG_ORIENTATION_IGNORE;
     size_t jpeg_tables_off = 0;
     std::vector<int32_t> jpeg_orientations; // rfd_jpeg_last_orientations
+    // Reduced size (rfd_set_jpeg_scale).  Behind the orientation tables, jpeg_pin and jpeg_dev hold the tables of a scaled batch
+    // (jpeg_scaled_off, 16-byte aligned): JpegScaledFrame [B] | JpegOrientedFrame [B] upright | JpegOrientedFrame [B] oriented.
+    int jpeg_scale = 1;
+    size_t jpeg_scaled_off = 0;
     // pipelined host entry (rfd_submit_batch / rfd_collect_batch): two slots, H2D on its own stream
     struct PipeSlot {
         DevBuf frames, imgs, scale, ob, ol, oc, ot;
@@ -2561,6 +2565,29 @@ int rfd_debug_jpeg_coefficients(const uint8_t *bytes, size_t len, int16_t *out, 
     return st;
 }
 
+int rfd_jpeg_scaled_size(const uint8_t *bytes, size_t len, int denom, int orientation_mode, struct rfd_jpeg_scaled_size *out)
+{
+    if (!jpeg_scale_valid(denom)) { set_error("invalid argument: JPEG scale denominator %d (1, 2, 4 or 8)", denom); return RFD_ERR_INVALID_ARG; }
+    if (orientation_mode != RFD_JPEG_ORIENTATION_IGNORE && orientation_mode != RFD_JPEG_ORIENTATION_APPLY) {
+        set_error("invalid argument: JPEG orientation mode %d (0: ignore, 1: apply)", orientation_mode);
+        return RFD_ERR_INVALID_ARG;
+    }
+    char msg[256] = "";
+    const int st = jpeg_scaled_size(bytes, len, denom, orientation_mode, out, msg, sizeof msg);
+    if (st != RFD_OK) set_error("%s", msg);
+    return st;
+}
+
+int rfd_debug_jpeg_block_counts(const uint8_t *bytes, size_t len, int denom, uint8_t *count, size_t cap_blocks, size_t *blocks)
+{
+    RFD_CHECK_ARG(count || cap_blocks == 0, "count is null");
+    if (!jpeg_scale_valid(denom)) { set_error("invalid argument: JPEG scale denominator %d (1, 2, 4 or 8)", denom); return RFD_ERR_INVALID_ARG; }
+    char msg[256] = "";
+    const int st = jpeg_debug_coefficients(bytes, len, nullptr, cap_blocks, blocks, msg, sizeof msg, denom, count);
+    if (st != RFD_OK) set_error("%s", msg);
+    return st;
+}
+
 int rfd_set_decode_threads(rfd_ctx *c, int threads)
 {
     RFD_CHECK_ARG(c, "ctx is null");
@@ -2587,13 +2614,15 @@ static int jpeg_stage_alloc(rfd_ctx *c)
         return RFD_ERR_CAPACITY;
     }
     const size_t tables = (B * sizeof(JpegFrame) + B * blocks * (sizeof(uint32_t) + 64 * sizeof(int16_t)) + 15) & ~(size_t)15;
-    const size_t bytes = tables + B * (sizeof(JpegOrientedFrame) + sizeof(JpegFrame));
+    const size_t scaled = (tables + B * (sizeof(JpegOrientedFrame) + sizeof(JpegFrame)) + 15) & ~(size_t)15;
+    const size_t bytes = scaled + B * (sizeof(JpegScaledFrame) + 2 * sizeof(JpegOrientedFrame));
     RFD_TRY(c->jpeg_pin_done.create());
     RFD_TRY(c->jpeg_dev.reserve(bytes));
     RFD_TRY(c->jpeg_planes.reserve(B * blocks * 64));
     RFD_TRY(c->jpeg_pin.alloc(bytes));
     c->jpeg_blocks_max = blocks;
     c->jpeg_tables_off = tables;
+    c->jpeg_scaled_off = scaled;
     return RFD_OK;
 }
 
@@ -2745,12 +2774,13 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
     std::vector<int32_t> orient((size_t)n, 1); // what the call applies: the tag in APPLY mode
     std::vector<int> ow((size_t)n), oh((size_t)n); // the size of the frame it writes
     int n_oriented = 0;
+    const int scale = c->jpeg_scale; // 1: every step below is what it was before the mode existed
     for (int i = 0; i < n; ++i) {
         const int st = jpeg_parse_header(bytes[i], len[i], hdr[i]);
         if (st != RFD_OK) { set_error("file %d: %s", i, hdr[i].msg); return st; }
         const JpegHeader &h = hdr[i];
         if (c->jpeg_orientation == RFD_JPEG_ORIENTATION_APPLY) orient[(size_t)i] = h.orientation;
-        jpeg_oriented_size(orient[(size_t)i], h.width, h.height, &ow[(size_t)i], &oh[(size_t)i]);
+        jpeg_oriented_size(orient[(size_t)i], jpeg_scaled_dim(h.width, scale), jpeg_scaled_dim(h.height, scale), &ow[(size_t)i], &oh[(size_t)i]);
         n_oriented += orient[(size_t)i] != 1;
         if (h.width > c->cfg.max_src_w || h.height > c->cfg.max_src_h) {
             set_error("file %d: %d x %d exceeds max_src %d x %d", i, h.width, h.height, c->cfg.max_src_w, c->cfg.max_src_h);
@@ -2758,7 +2788,10 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
         }
         if (!out[i].data) { set_error("invalid argument: output frame %d has no data pointer", i); return RFD_ERR_INVALID_ARG; }
         if (out[i].width != ow[(size_t)i] || out[i].height != oh[(size_t)i]) {
-            if (orient[(size_t)i] == 1) set_error("invalid argument: output frame %d is %d x %d, file %d is %d x %d", i, out[i].width, out[i].height, i, h.width, h.height);
+            if (scale != 1)
+                set_error("invalid argument: output frame %d is %d x %d, file %d is %d x %d at scale 1/%d in orientation %d (%d x %d stored)", i, out[i].width,
+                          out[i].height, i, ow[(size_t)i], oh[(size_t)i], scale, orient[(size_t)i], h.width, h.height);
+            else if (orient[(size_t)i] == 1) set_error("invalid argument: output frame %d is %d x %d, file %d is %d x %d", i, out[i].width, out[i].height, i, h.width, h.height);
             else
                 set_error("invalid argument: output frame %d is %d x %d, file %d is %d x %d in orientation %d (%d x %d stored)", i, out[i].width, out[i].height, i,
                           ow[(size_t)i], oh[(size_t)i], orient[(size_t)i], h.width, h.height);
@@ -2779,12 +2812,16 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
     std::vector<uint32_t> used((size_t)n, 0);
     std::vector<int> status((size_t)n, RFD_OK);
     size_t blocks = 0, out_bytes = 0;
-    for (int i = 0; i < n; ++i) { rec0[(size_t)i] = blocks; blocks += (size_t)hdr[i].nblocks; out_bytes += (size_t)hdr[i].width * 3 * hdr[i].height; }
+    for (int i = 0; i < n; ++i) { rec0[(size_t)i] = blocks; blocks += (size_t)hdr[i].nblocks; out_bytes += (size_t)ow[(size_t)i] * 3 * oh[(size_t)i]; }
+    std::vector<int> idct_n((size_t)n * 3, 8); // per frame and component: the inverse-DCT size (jpeg_idct_sizes)
+    if (scale != 1)
+        for (int i = 0; i < n; ++i) jpeg_idct_sizes(hdr[i], scale, &idct_n[(size_t)i * 3]);
     c->jpeg_paths.assign((size_t)n, 0);
     c->jpeg_orientations = orient;
     // one frame per task; the workers touch nothing but their frame's bytes, header and slices of the staging
     auto decode_on_host = [&](int i) {
-        status[(size_t)i] = jpeg_decode_scan(bytes[i], len[i], hdr[i], rec + rec0[(size_t)i], coef + rec0[(size_t)i] * 64, &used[(size_t)i]);
+        status[(size_t)i] = jpeg_decode_scan(bytes[i], len[i], hdr[i], rec + rec0[(size_t)i], coef + rec0[(size_t)i] * 64, &used[(size_t)i],
+                                             scale != 1 ? &idct_n[(size_t)i * 3] : nullptr);
     };
     JpegEntropyPlan plan(n);
     std::vector<int> host_frames, placed;
@@ -2829,6 +2866,11 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
     // the tables of the colour launches where a frame is oriented: each launch lists only the frames that have a workgroup in it
     JpegOrientedFrame *ofr = (JpegOrientedFrame *)(c->jpeg_pin.p + c->jpeg_tables_off);
     JpegFrame *ufr = (JpegFrame *)(ofr + B);
+    // the tables of a scaled batch: the per-frame additions, then the lists of its two colour launches
+    JpegScaledParams sp;
+    memset(&sp, 0, sizeof sp);
+    JpegScaledFrame *sfr = (JpegScaledFrame *)(c->jpeg_pin.p + c->jpeg_scaled_off);
+    JpegOrientedFrame *sup = (JpegOrientedFrame *)(sfr + B), *sor = sup + B;
     size_t out_at = 0;
     for (int i = 0; i < n; ++i) {
         const JpegHeader &h = hdr[i];
@@ -2840,7 +2882,7 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
         } else {
             f.out = (uint8_t *)c->jpeg_out.p + out_at;
             f.stride = (long long)ow[(size_t)i] * 3;
-            out_at += (size_t)h.width * 3 * h.height;
+            out_at += (size_t)ow[(size_t)i] * 3 * oh[(size_t)i];
         }
         f.rec0 = rec0[(size_t)i]; f.coef0 = rec0[(size_t)i] * 64; f.plane0 = rec0[(size_t)i] * 64;
         f.width = h.width; f.height = h.height;
@@ -2852,6 +2894,36 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
         for (int k = 0; k < h.ncomp; ++k) {
             f.bw[k] = h.comp[k].bw; f.bh[k] = h.comp[k].bh; f.blk0[k] = h.comp[k].blk0;
             for (int z = 0; z < 64; ++z) f.quant[k][kJpegNatural[z]] = h.quant[h.comp[k].tq][z];
+        }
+        if (scale != 1) {
+            JpegScaledFrame &sf = sfr[i];
+            memset(&sf, 0, sizeof sf);
+            size_t at = f.plane0; // n^2 <= 64 bytes per block: the scaled planes fit the frame's share of the pool
+            for (int k = 0; k < h.ncomp; ++k) {
+                const int nk = idct_n[(size_t)i * 3 + (size_t)k], blk = h.comp[k].bw * h.comp[k].bh;
+                sf.n[k] = nk;
+                sf.plane[k] = at;
+                sf.pitch[k] = h.comp[k].bw * nk;
+                sf.cgroup[k] = sp.groups;
+                sp.groups += ceil_div(blk, 256 / nk);
+                at += (size_t)blk * nk * nk;
+            }
+            sf.width = jpeg_scaled_dim(h.width, scale); sf.height = jpeg_scaled_dim(h.height, scale);
+            sf.hup = h.ncomp == 3 ? h.hmax * (8 / scale) / (h.comp[1].h * sf.n[1]) : 1; // 2 for 4:2:2; the vertical factor is always 1
+            sf.replicate = scale == 8;
+            JpegOrientedFrame &e = orient[(size_t)i] == 1 ? sup[sp.n_upright++] : sor[sp.n_oriented++];
+            e.frame = i;
+            e.orientation = orient[(size_t)i];
+            if (orient[(size_t)i] == 1) {
+                e.tile0 = sp.tiles_upright;
+                e.tiles_x = 0;
+                sp.tiles_upright += (int)(((size_t)ceil_div(sf.width, 4) * sf.height + 255) / 256);
+            } else {
+                e.tile0 = sp.tiles_oriented;
+                e.tiles_x = jpeg_oriented_tiles_x(ow[(size_t)i]);
+                sp.tiles_oriented += e.tiles_x * jpeg_oriented_tiles_x(oh[(size_t)i]);
+            }
+            continue;
         }
         if (!n_oriented) continue;
         if (orient[(size_t)i] == 1) {
@@ -2883,7 +2955,10 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
             if (used[(size_t)i])
                 RFD_HIP(hipMemcpyAsync(dev + coef_off + rec0[(size_t)i] * 64 * sizeof(int16_t), coef + rec0[(size_t)i] * 64, (size_t)used[(size_t)i] * sizeof(int16_t),
                                        hipMemcpyHostToDevice, c->stream));
-        if (n_oriented)
+        if (scale != 1)
+            RFD_HIP(hipMemcpyAsync(dev + c->jpeg_scaled_off, sfr, B * (sizeof(JpegScaledFrame) + sizeof(JpegOrientedFrame)) + (size_t)sp.n_oriented * sizeof(JpegOrientedFrame),
+                                   hipMemcpyHostToDevice, c->stream));
+        else if (n_oriented)
             RFD_HIP(hipMemcpyAsync(dev + c->jpeg_tables_off, ofr, B * sizeof(JpegOrientedFrame) + (size_t)upright.n * sizeof(JpegFrame), hipMemcpyHostToDevice,
                                    c->stream));
         return RFD_OK;
@@ -2898,7 +2973,15 @@ static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_
     p.rec = (const uint32_t *)(dev + rec_off);
     p.coef = (const int16_t *)(dev + coef_off);
     p.planes = (uint8_t *)c->jpeg_planes.p;
-    if (!n_oriented) RFD_TRY(launch_jpeg_decode(p, c->stream));
+    if (scale != 1) {
+        sp.frames = p.frames;
+        sp.scaled = (const JpegScaledFrame *)(dev + c->jpeg_scaled_off);
+        sp.upright = (const JpegOrientedFrame *)(sp.scaled + B);
+        sp.oriented = sp.upright + B;
+        sp.n = n;
+        sp.rec = p.rec; sp.coef = p.coef; sp.planes = p.planes;
+        RFD_TRY(launch_jpeg_decode_scaled(sp, c->stream));
+    } else if (!n_oriented) RFD_TRY(launch_jpeg_decode(p, c->stream));
     else {
         upright.frames = (const JpegFrame *)(dev + c->jpeg_tables_off + B * sizeof(JpegOrientedFrame));
         upright.rec = p.rec; upright.coef = p.coef; upright.planes = p.planes;
@@ -2926,6 +3009,14 @@ int rfd_set_jpeg_entropy(rfd_ctx *c, int mode)
     RFD_CHECK_ARG(c, "ctx is null");
     if (mode != RFD_JPEG_ENTROPY_HOST && mode != RFD_JPEG_ENTROPY_DEVICE) { set_error("invalid argument: JPEG entropy mode %d (0: host, 1: device)", mode); return RFD_ERR_INVALID_ARG; }
     c->jpeg_entropy = mode;
+    return RFD_OK;
+}
+
+int rfd_set_jpeg_scale(rfd_ctx *c, int denom)
+{
+    RFD_CHECK_ARG(c, "ctx is null");
+    if (!jpeg_scale_valid(denom)) { set_error("invalid argument: JPEG scale denominator %d (1, 2, 4 or 8)", denom); return RFD_ERR_INVALID_ARG; }
+    c->jpeg_scale = denom;
     return RFD_OK;
 }
 

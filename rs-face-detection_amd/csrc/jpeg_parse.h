@@ -17,6 +17,9 @@
 //   rec[block]  = (offset << 7) | count     offset: index of the block's first value in coef[]; count: 0..64
 //   coef[offset .. offset + count)          the QUANTISED coefficients in zigzag order up to the last non-zero one
 // The blocks of an MCU are consecutive in coef[] (decode order), which is why every block carries its own offset.
+// A reduced-size decode (rfd.h, "JPEG decode, reduced size") tells the decoder each component's inverse-DCT size n; `count` is
+// then 1 + the zigzag position of the last non-zero coefficient that an n x n inverse DCT READS (jpeg_idct_reads), so the run
+// ends earlier; values at unread positions inside the run still travel.
 #ifndef RFD_JPEG_PARSE_H
 #define RFD_JPEG_PARSE_H
 #include <cstdarg>
@@ -320,9 +323,45 @@ inline int jpeg_receive_extend(JpegBits &br, int s)
     return r < (1 << (s - 1)) ? r - (1 << s) + 1 : r;
 }
 
+// ---- reduced-size decode (rfd.h, "JPEG decode, reduced size"): libjpeg's scale_num / scale_denom = 1 / s, s in {1, 2, 4, 8} ----
+inline bool jpeg_scale_valid(int denom) { return denom == 1 || denom == 2 || denom == 4 || denom == 8; }
+inline int jpeg_scaled_dim(int v, int denom) { return (v + denom - 1) / denom; }
+
+// jdmaster.c: the inverse-DCT size of each component.  With m = 8 / s the minimum size, a component whose sampling factor leaves
+// room takes a size doubled (up to 8) instead of being upsampled afterwards: 4:2:0 chroma gets 2 m in both directions.
+inline void jpeg_idct_sizes(const JpegHeader &h, int denom, int n[3])
+{
+    const int m = 8 / denom;
+    for (int c = 0; c < 3; ++c) {
+        n[c] = m;
+        if (c >= h.ncomp) continue;
+        while (n[c] < 8 && (h.hmax * m) % (h.comp[c].h * n[c] * 2) == 0 && (h.vmax * m) % (h.comp[c].v * n[c] * 2) == 0) n[c] *= 2;
+    }
+}
+
+// jidctred.c: does the n x n inverse DCT read the coefficient at natural index nat?  Per axis it reads the frequencies
+// n = 8: 0..7    n = 4: 0 1 2 3 5 6 7    n = 2: 0 1 3 5 7    n = 1: 0
+constexpr bool jpeg_idct_reads(int n, int nat)
+{
+    const unsigned axis = n == 8 ? 0xffu : n == 4 ? 0xefu : n == 2 ? 0xabu : 0x01u;
+    return (axis >> (nat >> 3) & 1u) && (axis >> (nat & 7) & 1u);
+}
+// the same by zigzag position, one bit each: what the entropy decoder tests per non-zero coefficient
+constexpr uint64_t jpeg_idct_read_mask(int n)
+{
+    uint64_t m = 0;
+    for (int z = 0; z < 64; ++z)
+        if (jpeg_idct_reads(n, kJpegNatural[z])) m |= (uint64_t)1 << z;
+    return m;
+}
+constexpr uint64_t kJpegReadMask[4] = {jpeg_idct_read_mask(1), jpeg_idct_read_mask(2), jpeg_idct_read_mask(4), jpeg_idct_read_mask(8)};
+static_assert(kJpegReadMask[3] == ~(uint64_t)0 && kJpegReadMask[0] == 1, "8 x 8 reads everything, 1 x 1 the DC alone");
+inline uint64_t jpeg_read_mask_of(int n) { return kJpegReadMask[n == 8 ? 3 : n == 4 ? 2 : n == 2 ? 1 : 0]; }
+
 // Decodes the scan of a parsed file.  rec: h.nblocks records; coef: room for 64 * h.nblocks values (never more are written);
-// *used = the values written.  h.msg holds the cause of a failure.
-inline int jpeg_decode_scan(const uint8_t *d, size_t len, JpegHeader &h, uint32_t *rec, int16_t *coef, uint32_t *used)
+// *used = the values written.  h.msg holds the cause of a failure.  idct_n: the inverse-DCT size per component of a reduced-size
+// decode, which shortens the runs to what that size reads; null: full size.
+inline int jpeg_decode_scan(const uint8_t *d, size_t len, JpegHeader &h, uint32_t *rec, int16_t *coef, uint32_t *used, const int *idct_n = nullptr)
 {
     if ((uint64_t)h.nblocks * 64 > kJpegMaxCoefs) return h.fail(RFD_ERR_CAPACITY, "a JPEG frame of %d blocks exceeds the decoder's %u coefficient slots", h.nblocks, kJpegMaxCoefs);
     JpegBits br{d, h.scan, len};
@@ -351,16 +390,17 @@ inline int jpeg_decode_scan(const uint8_t *d, size_t len, JpegHeader &h, uint32_
         for (int c = 0; c < h.ncomp; ++c) {
             const JpegComponent &k = h.comp[c];
             const JpegHuff &dc = h.dc[k.td], &ac = h.ac[k.ta];
+            const uint64_t reads = jpeg_read_mask_of(idct_n ? idct_n[c] : 8);
             for (int v = 0; v < k.v; ++v)
                 for (int u = 0; u < k.h; ++u) {
                     int16_t *out = coef + off;
-                    int count = 0;
+                    int count = 0, keep = 0; // values written so far; how many of them travel (full size: all)
                     br.fill();
                     int s = jpeg_huff_decode(br, dc);
                     if (s < 0) return h.fail(RFD_ERR_INVALID_ARG, "a Huffman code not in DC table %d near byte %zu (MCU %d)", k.td, br.pos, mcu);
                     if (s) pred[c] = (int)((unsigned)pred[c] + (unsigned)jpeg_receive_extend(br, s));
                     out[0] = (int16_t)pred[c]; // wraps where a hostile file drives the predictor out of range, as libjpeg's store does
-                    if (out[0]) count = 1;
+                    if (out[0]) count = keep = 1;
                     for (int i = 1; i < 64;) {
                         br.fill();
                         const int rs = jpeg_huff_decode(br, ac);
@@ -378,14 +418,15 @@ inline int jpeg_decode_scan(const uint8_t *d, size_t len, JpegHeader &h, uint32_
                         for (int z = count ? count : 1; z < i; ++z) out[z] = 0;
                         out[i] = (int16_t)jpeg_receive_extend(br, s);
                         count = ++i;
+                        if (reads >> (i - 1) & 1) keep = count;
                     }
                     if (br.overrun()) {
                         if (br.marker > 0) return h.fail(RFD_ERR_INVALID_ARG, "marker 0xFF%02X at byte %zu ends the entropy-coded data before MCU %d of %d is complete", br.marker, br.marker_at, mcu, mcus);
                         return h.fail(RFD_ERR_INVALID_ARG, "truncated: the data ends at byte %zu, before MCU %d of %d is complete", len, mcu, mcus);
                     }
                     const int blk = k.blk0 + (my * k.v + v) * k.bw + mx * k.h + u;
-                    rec[blk] = off << kJpegRecCountBits | (uint32_t)count;
-                    off += (uint32_t)count;
+                    rec[blk] = off << kJpegRecCountBits | (uint32_t)keep;
+                    off += (uint32_t)keep;
                 }
         }
     }
@@ -437,6 +478,25 @@ inline int jpeg_info(const uint8_t *d, size_t len, struct rfd_jpeg_info *out, ch
     return RFD_OK;
 }
 
+// the same validation: rfd_jpeg_scaled_size
+inline int jpeg_scaled_size(const uint8_t *d, size_t len, int denom, int orientation_mode, struct rfd_jpeg_scaled_size *out, char *msg, size_t msg_cap)
+{
+    std::unique_ptr<JpegHeader> h(new JpegHeader);
+    const int st = jpeg_parse_header(d, len, *h);
+    if (st != RFD_OK) {
+        snprintf(msg, msg_cap, "%s", h->msg);
+        return st;
+    }
+    if (out) {
+        memset(out, 0, sizeof *out);
+        out->denom = denom;
+        out->orientation = orientation_mode == RFD_JPEG_ORIENTATION_APPLY ? h->orientation : 1;
+        jpeg_oriented_size(out->orientation, jpeg_scaled_dim(h->width, denom), jpeg_scaled_dim(h->height, denom), &out->width, &out->height);
+        out->stored_width = h->width; out->stored_height = h->height;
+    }
+    return RFD_OK;
+}
+
 // records + quantised zigzag runs of a decoded scan -> out [nblocks][64]: dequantised (saturating to i16), natural order
 inline void jpeg_dequantise_natural(const JpegHeader &h, const uint32_t *rec, const int16_t *coef, int16_t *out)
 {
@@ -455,8 +515,10 @@ inline void jpeg_dequantise_natural(const JpegHeader &h, const uint32_t *rec, co
     }
 }
 
-// rfd_debug_jpeg_coefficients: parse, decode, dequantise, zigzag -> natural order
-inline int jpeg_debug_coefficients(const uint8_t *d, size_t len, int16_t *out, size_t cap_blocks, size_t *blocks, char *msg, size_t msg_cap)
+// rfd_debug_jpeg_coefficients: parse, decode, dequantise, zigzag -> natural order.  rfd_debug_jpeg_block_counts (count_out): the
+// same walk at a denominator, reporting each record's count instead
+inline int jpeg_debug_coefficients(const uint8_t *d, size_t len, int16_t *out, size_t cap_blocks, size_t *blocks, char *msg, size_t msg_cap, int denom = 1,
+                                   uint8_t *count_out = nullptr)
 {
     std::unique_ptr<JpegHeader> h(new JpegHeader);
     int st = jpeg_parse_header(d, len, *h);
@@ -471,13 +533,18 @@ inline int jpeg_debug_coefficients(const uint8_t *d, size_t len, int16_t *out, s
     if (st == RFD_OK) {
         rec.resize((size_t)h->nblocks);
         coef.resize((size_t)h->nblocks * 64);
-        st = jpeg_decode_scan(d, len, *h, rec.data(), coef.data(), &used);
+        int n[3];
+        jpeg_idct_sizes(*h, denom, n);
+        st = jpeg_decode_scan(d, len, *h, rec.data(), coef.data(), &used, denom == 1 ? nullptr : n);
     }
     if (st != RFD_OK) {
         snprintf(msg, msg_cap, "%s", h->msg);
         return st;
     }
-    jpeg_dequantise_natural(*h, rec.data(), coef.data(), out);
+    if (count_out)
+        for (int b = 0; b < h->nblocks; ++b) count_out[b] = (uint8_t)(rec[(size_t)b] & ((1u << kJpegRecCountBits) - 1));
+    else
+        jpeg_dequantise_natural(*h, rec.data(), coef.data(), out);
     return RFD_OK;
 }
 

@@ -260,6 +260,32 @@ inline int jpeg_oriented_tiles_x(int out_w) { return (out_w + kJpegOrientTile - 
 // a batch with at least one oriented frame: the inverse DCT over p, the colour kernel over `upright` (its own frame table and
 // tile count, the pools of p; skipped where upright.n is 0), the oriented kernel over o
 int launch_jpeg_decode_oriented(const JpegParams &p, const JpegParams &upright, const JpegOrientedParams &o, hipStream_t s);
+// Reduced size (rfd.h, "JPEG decode, reduced size").  What a scaled frame adds to its JpegFrame, which keeps the STORED sizes, the
+// block counts, the records and the quantisers: component c is inverse-transformed at n[c] x n[c] samples per block into a plane
+// of its own pitch.  JpegFrame and JpegParams are what they were, so the kernels of unscaled batches are too.
+struct JpegScaledFrame {
+    unsigned long long plane[3]; // per component: the plane's first byte in the plane pool, n[c]^2 bytes per block, row-major
+    int n[3];                    // the component's inverse-DCT size: 8, 4, 2 or 1
+    int pitch[3];                // bytes per plane row: bw[c] * n[c]
+    int cgroup[3];               // the component's first workgroup in the reduced inverse-DCT launch (256 / n[c] blocks each)
+    int width, height;           // the SCALED size: ceil(stored / s)
+    int hup;                     // the horizontal upsampling left for the chroma planes: 2 for 4:2:2, else 1; never a vertical one
+    int replicate;               // s = 8: that upsampling is plain replication
+};
+struct JpegScaledParams {
+    const JpegFrame *frames;           // device: the whole batch; out and stride describe the scaled (and oriented) frame
+    const JpegScaledFrame *scaled;     // device: the whole batch, frame by frame
+    const JpegOrientedFrame *upright;  // device [n_upright]: frame, tile0 (256 x 4 pixels of the scaled frame per workgroup)
+    const JpegOrientedFrame *oriented; // device [n_oriented]: as in JpegOrientedParams, tiles over the scaled oriented size
+    int n, groups;                     // frames; workgroups of the reduced inverse DCT
+    int n_upright, tiles_upright, n_oriented, tiles_oriented;
+    const uint32_t *rec;
+    const int16_t *coef;
+    uint8_t *planes;
+};
+// one reduced inverse DCT over the batch, one colour launch over the upright frames, one over the oriented ones, each where it
+// has a frame
+int launch_jpeg_decode_scaled(const JpegScaledParams &p, hipStream_t s);
 
 // ---------------------------------------------------------------- JPEG entropy decode (kernels_jpeg_entropy.hip)
 // Huffman decoding of restart-interval files, one thread per interval (jpeg_entropy.h).  One frame of a batch that takes this

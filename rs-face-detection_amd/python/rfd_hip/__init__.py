@@ -124,6 +124,11 @@ class rfd_jpeg_orientation(C.Structure):
                 ("stored_height", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class rfd_jpeg_scaled_size(C.Structure):
+    _fields_ = [("denom", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("stored_width", C.c_int32),
+                ("stored_height", C.c_int32), ("orientation", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class rfd_tensor_desc(C.Structure):
     _fields_ = [("channels", C.c_int), ("height", C.c_int), ("width", C.c_int),
                 ("is_f32", C.c_int), ("buffer", C.c_int), ("is_input", C.c_int),
@@ -157,6 +162,7 @@ API_SYMBOLS = [
     "rfd_jpeg_info", "rfd_decode_jpeg_batch_device", "rfd_decode_jpeg_batch", "rfd_set_decode_threads", "rfd_debug_jpeg_coefficients",
     "rfd_set_jpeg_entropy", "rfd_jpeg_last_paths", "rfd_debug_jpeg_intervals", "rfd_debug_jpeg_coefficients_device",
     "rfd_jpeg_orientation", "rfd_set_jpeg_orientation", "rfd_jpeg_last_orientations",
+    "rfd_set_jpeg_scale", "rfd_jpeg_scaled_size", "rfd_debug_jpeg_block_counts",
 ]
 
 _lib = None
@@ -293,6 +299,9 @@ def load_library(path=None):
     L.rfd_jpeg_orientation.argtypes = [vp, C.c_size_t, C.POINTER(rfd_jpeg_orientation)]
     L.rfd_set_jpeg_orientation.argtypes = [vp, ci]
     L.rfd_jpeg_last_orientations.argtypes = [vp, vp, ci, C.POINTER(ci)]
+    L.rfd_set_jpeg_scale.argtypes = [vp, ci]
+    L.rfd_jpeg_scaled_size.argtypes = [vp, C.c_size_t, ci, ci, C.POINTER(rfd_jpeg_scaled_size)]
+    L.rfd_debug_jpeg_block_counts.argtypes = [vp, C.c_size_t, ci, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     if path is None:
         _lib = L
     return L
@@ -430,6 +439,31 @@ def jpeg_orientation(data):
     _check(load_library().rfd_jpeg_orientation(addr, n, C.byref(o)))
     return dict(orientation=o.orientation, width=o.width, height=o.height, stored_width=o.stored_width,
                 stored_height=o.stored_height)
+
+
+def jpeg_scaled_size(data, denom, orientation="ignore"):
+    """the size of the frame a decode at 1 / denom (1, 2, 4, 8) in this orientation mode ("ignore" / "apply") writes, after the
+    same validation as jpeg_info (rfd_jpeg_scaled_size; host only, no GPU) -> dict(denom, width, height = ceil(stored / denom),
+    swapped for orientations 5..8 in "apply" mode, stored_width, stored_height, orientation = the one that will be applied)"""
+    keep, addr, n = _byte_buffer(data)
+    modes = {"ignore": JPEG_ORIENTATION_IGNORE, "apply": JPEG_ORIENTATION_APPLY}
+    z = rfd_jpeg_scaled_size()
+    _check(load_library().rfd_jpeg_scaled_size(addr, n, int(denom), modes[orientation] if orientation in modes else int(orientation), C.byref(z)))
+    return dict(denom=z.denom, width=z.width, height=z.height, stored_width=z.stored_width, stored_height=z.stored_height,
+                orientation=z.orientation)
+
+
+def jpeg_block_counts(data, denom):
+    """the count of every block's record as the host entropy decoder writes it at 1 / denom, [blocks] u8 in the block order of
+    jpeg_coefficients (rfd_debug_jpeg_block_counts; host only, no GPU)"""
+    keep, addr, n = _byte_buffer(data)
+    L, blocks = load_library(), C.c_size_t(0)
+    st = L.rfd_debug_jpeg_block_counts(addr, n, int(denom), None, 0, C.byref(blocks))
+    if st != RFD_ERR_CAPACITY:
+        _check(st)
+    out = np.zeros(blocks.value, np.uint8)
+    _check(L.rfd_debug_jpeg_block_counts(addr, n, int(denom), out.ctypes.data, blocks.value, C.byref(blocks)))
+    return out
 
 
 def jpeg_coefficients(data):
@@ -660,6 +694,7 @@ class RetinaFaceDetection:
         self.image_size = (cfg.image_w, cfg.image_h)
         self.max_det = cfg.max_det
         self._jpeg_apply_orientation = False   # set_jpeg_orientation: decode_jpeg allocates by the oriented size
+        self._jpeg_scale = 1                   # set_jpeg_scale: ... and by the scaled size
 
     def gallery(self, dim=512, capacity=1 << 20):
         """a face gallery on this detector's device and stream (rfd_gallery_create); it is closed with the detector at the latest"""
@@ -818,6 +853,12 @@ class RetinaFaceDetection:
         _check(self._L.rfd_set_jpeg_orientation(self._ctx, mode))
         self._jpeg_apply_orientation = mode == JPEG_ORIENTATION_APPLY
 
+    def set_jpeg_scale(self, denom):
+        """1 (default): frames are written at the stored size; 2, 4, 8: at ceil(size / denom), built by libjpeg's reduced inverse
+        DCTs, for every frame of the calls that follow (rfd.h, "JPEG decode, reduced size")"""
+        _check(self._L.rfd_set_jpeg_scale(self._ctx, int(denom)))
+        self._jpeg_scale = int(denom)
+
     def jpeg_last_orientations(self):
         """per frame of the last decode call: the orientation that was applied (all 1 in "ignore" mode)"""
         n = C.c_int(0)
@@ -860,12 +901,15 @@ class RetinaFaceDetection:
 
     def decode_jpeg(self, files):
         """list of JPEG files (bytes) -> list of [H, W, 3] u8 BGR host arrays, decoded on the device (a grey file: B = G = R);
-        in "apply" mode (set_jpeg_orientation) H, W are the oriented size"""
+        in "apply" mode (set_jpeg_orientation) H, W are the oriented size, after set_jpeg_scale the scaled one"""
         bufs, ptrs, lens = self._jpeg_files(files)
         outs = []
         for k, f in enumerate(files):
             try:
-                i = jpeg_orientation(f) if self._jpeg_apply_orientation else jpeg_info(f)
+                if self._jpeg_scale != 1:
+                    i = jpeg_scaled_size(f, self._jpeg_scale, "apply" if self._jpeg_apply_orientation else "ignore")
+                else:
+                    i = jpeg_orientation(f) if self._jpeg_apply_orientation else jpeg_info(f)
             except RfdError as e:   # name the file, as the batch call itself does
                 raise RfdError(e.status, "file %d: %s" % (k, e.message)) from None
             outs.append(np.zeros((i["height"], i["width"], 3), np.uint8))

@@ -19,10 +19,14 @@ kJpegDeviceMaxInterval MCUs (restart_marker_blocks); without it the files have n
 --orientation N (1..8, default 1) writes an Exif APP1 with that orientation into the generated files and selects
 RFD_JPEG_ORIENTATION_APPLY (rfd.h, "EXIF orientation"), so that the colour stage of (b) is jpeg_color_oriented_kernel for 2..8;
 the files of a directory keep the tags they have.  --no-host skips (a), (c) and (d): the traced child alone.
+--scale D (1, 2, 4, 8; default 1) selects rfd_set_jpeg_scale(D) (rfd.h, "JPEG decode, reduced size"): the kernels of (b) are then
+jpeg_idct_reduced_kernel and jpeg_color_scaled_kernel (jpeg_color_scaled_oriented_kernel for tagged files), each against the
+floor of its OWN bytes; (c) counts the shortened runs; the plane and frame bytes per frame are printed.
 
     python tools/jpeg_bench.py [directory] [--files 32] [--reps 5] [--no-trace] [--entropy host|device] [--restart none|rows|max|MCUs]
-                               [--orientation 1..8] [--no-host]
-Record the output in profiles/jpeg_decode.txt, profiles/jpeg_entropy_device.txt and profiles/jpeg_orientation.txt."""
+                               [--orientation 1..8] [--scale 1|2|4|8] [--no-host]
+Record the output in profiles/jpeg_decode.txt, profiles/jpeg_entropy_device.txt, profiles/jpeg_orientation.txt and
+profiles/jpeg_scaled.txt."""
 import argparse
 import glob
 import io
@@ -70,8 +74,21 @@ def load_files(a):
     return make_files(a.files, a.restart, a.orientation)
 
 
-def open_detector(R, files, entropy="host", orientation=1):
-    """the frames are allocated in the size the decode writes: the oriented one when --orientation selects APPLY"""
+def plane_bytes(info, scale):
+    """bytes of the component planes of one frame at 1 / scale: per block n x n samples, n per component as jdmaster.c chooses it"""
+    h, v = {0: (1, 1), 1: (1, 1), 2: (2, 1), 3: (2, 2)}[info["sampling"]]
+    mx, my = -(-info["width"] // (8 * h)), -(-info["height"] // (8 * v))
+    m = 8 // scale
+    luma = mx * h * my * v * m * m
+    if info["components"] == 1:
+        return luma
+    n = 2 * m if (h, v) == (2, 2) and scale != 1 else m   # 4:2:0 chroma grows through its inverse DCT instead of being upsampled
+    return luma + 2 * mx * my * n * n
+
+
+def open_detector(R, files, entropy="host", orientation=1, scale=1):
+    """the frames are allocated in the size the decode writes: the oriented one when --orientation selects APPLY, the scaled one
+    when --scale is not 1"""
     import torch
     infos = [R.jpeg_info(f) for f in files]
     det = R.RetinaFaceDetection(max_batch_size=len(files), max_src=(max(i["width"] for i in infos), max(i["height"] for i in infos)))
@@ -79,6 +96,10 @@ def open_detector(R, files, entropy="host", orientation=1):
     if orientation != 1:
         det.set_jpeg_orientation("apply")
         infos = [dict(i, **{k: v for k, v in R.jpeg_orientation(f).items() if k in ("width", "height")}) for i, f in zip(infos, files)]
+    if scale != 1:
+        det.set_jpeg_scale(scale)
+        mode = "apply" if orientation != 1 else "ignore"
+        infos = [dict(i, **{k: v for k, v in R.jpeg_scaled_size(f, scale, mode).items() if k in ("width", "height")}) for i, f in zip(infos, files)]
     dev = torch.device("cuda", 0)
     bufs = [torch.zeros((i["height"], i["width"] * 3), dtype=torch.uint8, device=dev) for i in infos]
     torch.cuda.synchronize()
@@ -90,7 +111,7 @@ def traced_child(a):
     import torch  # noqa: F401  (first: librfd_hip.so then binds to the HIP runtime torch ships)
     import rfd_hip as R
     files = load_files(a)
-    det, infos, bufs, ptrs, shapes = open_detector(R, files, a.entropy, a.orientation)
+    det, infos, bufs, ptrs, shapes = open_detector(R, files, a.entropy, a.orientation, a.scale)
     for _ in range(1 + a.reps):
         det.decode_jpeg_device(files, ptrs, shapes)
     print("traced calls %d frames %d orientations %s" % (1 + a.reps, len(files), sorted(set(det.jpeg_last_orientations()))))
@@ -108,7 +129,33 @@ def read_stats(directory, suffix):
     return None
 
 
-def kernel_pass(files, a, h2d_bytes_per_call):
+def scaled_kernel_lines(rows, a, infos, h2d_bytes_per_call):
+    """(b) at --scale 2, 4, 8: each reduced kernel against the floor of its own bytes.  The inverse DCT reads the records and runs
+    that crossed PCIe and writes the planes; the colour kernel reads the planes and writes the frames."""
+    n = len(infos)
+    planes = sum(plane_bytes(i, a.scale) for i in infos)
+    frames = sum(-(-i["width"] // a.scale) * -(-i["height"] // a.scale) * 3 for i in infos)
+    colour = "jpeg_color_scaled_kernel" if a.orientation == 1 else "jpeg_color_scaled_oriented_kernel"
+    for name, moved in (("jpeg_entropy_kernel", None), ("jpeg_idct_reduced_kernel", h2d_bytes_per_call + planes), (colour, planes + frames)):
+        hit = [x for x in rows if name in x["Name"]]
+        if not hit:
+            if moved is not None or a.entropy == "device":
+                print("(b) %s is not in the kernel statistics" % name)
+            continue
+        us = float(hit[0]["AverageNs"]) / 1e3
+        line = "(b) %s: %d launches, %.1f us per launch = %.2f us per frame (min %.1f, max %.1f us per launch)" % (
+            name, int(hit[0]["Calls"]), us, us / n, float(hit[0]["MinNs"]) / 1e3, float(hit[0]["MaxNs"]) / 1e3)
+        if moved is not None:
+            floor = moved / (STREAM_TBS * 1e12) * 1e6
+            line += "; its bytes %.1f MB per launch = %.2f TB/s, floor %.1f us at %.1f TB/s: %.0f %% of the floor's rate" % (
+                moved / 1e6, moved / us / 1e6, floor, STREAM_TBS, 100 * floor / us)
+        print(line)
+    for other in ("jpeg_idct_kernel", "jpeg_color_kernel", "jpeg_color_oriented_kernel"):
+        if [x for x in rows if other in x["Name"]]:
+            print("(b) UNEXPECTED: %s ran in a scaled window" % other)
+
+
+def kernel_pass(files, a, h2d_bytes_per_call, infos):
     """(b): a child of this script under rocprofv3, a process of its own started with subprocess; prints the figures"""
     import shutil
     import subprocess
@@ -125,7 +172,7 @@ def kernel_pass(files, a, h2d_bytes_per_call):
         out = os.path.join(tmp, "trace")
         r = subprocess.run([exe, "--kernel-trace", "--memory-copy-trace", "--stats", "--output-format", "csv", "-d", out, "--", sys.executable,
                             os.path.abspath(__file__), tmp, "--files", str(len(files)), "--reps", str(a.reps), "--entropy", a.entropy, "--orientation",
-                            str(a.orientation), "--child"],
+                            str(a.orientation), "--scale", str(a.scale), "--child"],
                            capture_output=True, text=True, timeout=600)
         if r.returncode != 0 or "traced calls" not in r.stdout:
             print("(b) the traced child failed (exit %d): kernel time not measured\n%s" % (r.returncode, (r.stdout + r.stderr)[-600:]))
@@ -138,6 +185,8 @@ def kernel_pass(files, a, h2d_bytes_per_call):
         floor_us = 19e6 / (STREAM_TBS * 1e12) * 1e6
         total = 0.0
         print("(b) %s" % [l for l in r.stdout.splitlines() if "traced calls" in l][0])
+        if a.scale != 1:
+            return scaled_kernel_lines(rows, a, infos, h2d_bytes_per_call)
         colour = "jpeg_color_kernel" if a.orientation == 1 else "jpeg_color_oriented_kernel"   # every file carries the same tag
         for name in ("jpeg_entropy_kernel", "jpeg_idct_kernel", "jpeg_color_kernel", "jpeg_color_oriented_kernel"):
             hit = [x for x in rows if name in x["Name"]]
@@ -173,6 +222,7 @@ def main():
     ap.add_argument("--entropy", choices=("host", "device"), default="host", help="where eligible files are entropy-decoded")
     ap.add_argument("--restart", default="none", help="restart interval of the generated files: none, rows (one MCU row), max (kJpegDeviceMaxInterval MCUs) or a number of MCUs")
     ap.add_argument("--orientation", type=int, choices=range(1, 9), default=1, help="EXIF orientation written into the generated files; 2..8 select APPLY mode")
+    ap.add_argument("--scale", type=int, choices=(1, 2, 4, 8), default=1, help="rfd_set_jpeg_scale: decode at 1 / this")
     ap.add_argument("--no-host", action="store_true", help="skip (a), (c) and (d): only the child run under rocprofv3")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -182,7 +232,7 @@ def main():
     import rfd_hip as R
     files = load_files(a)
     n = len(files)
-    infos = [R.jpeg_info(f) for f in files]
+    infos = stored = [R.jpeg_info(f) for f in files]   # stored: the files' own sizes, whatever size the frames below get
     print("%d files, %.0f KB each on average, first %dx%d sampling %d, orientation %d" %
           (n, sum(map(len, files)) / n / 1e3, infos[0]["width"], infos[0]["height"], infos[0]["sampling"], R.jpeg_orientation(files[0])["orientation"]))
     # (c) transport bytes: 4 per block + 2 per coefficient up to the last non-zero one of its block (in zigzag order)
@@ -190,14 +240,21 @@ def main():
                               39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63]))
     h2d = []
     for f in files:
+        if a.scale != 1:   # the runs end at the last non-zero coefficient the reduced inverse DCT reads: the decoder's own counts
+            counts = R.jpeg_block_counts(f, a.scale)
+            h2d.append(counts.shape[0] * 4 + 2 * int(counts.astype(np.int64).sum()))
+            continue
         nz = R.jpeg_coefficients(f)[:, zz] != 0
         h2d.append(nz.shape[0] * 4 + 2 * int(np.where(nz.any(1), 64 - np.argmax(nz[:, ::-1], 1), 0).sum()))
-    decoded = [i["width"] * i["height"] * 3 for i in infos]
+    decoded = [-(-i["width"] // a.scale) * -(-i["height"] // a.scale) * 3 for i in infos]
+    print("scale 1/%d: %.3f MB of planes and %.3f MB of frame per frame (full size: %.3f and %.3f MB)" %
+          (a.scale, np.mean([plane_bytes(i, a.scale) for i in infos]) / 1e6, np.mean(decoded) / 1e6, np.mean([plane_bytes(i, 1) for i in infos]) / 1e6,
+           np.mean([i["width"] * i["height"] * 3 for i in infos]) / 1e6))
     if a.no_host:
-        return kernel_pass(files, a, float(np.sum(h2d)) + n * 496)
+        return kernel_pass(files, a, float(np.sum(h2d)) + n * 496, stored)
     print("(c) H2D bytes per frame: %.2f MB (records + truncated runs) against %.2f MB decoded = %.1f %%" %
           (np.mean(h2d) / 1e6, np.mean(decoded) / 1e6, 100 * np.sum(h2d) / np.sum(decoded)))
-    det, infos, bufs, ptrs, shapes = open_detector(R, files, a.entropy, a.orientation)
+    det, infos, bufs, ptrs, shapes = open_detector(R, files, a.entropy, a.orientation, a.scale)
     det.decode_jpeg_device(files, ptrs, shapes)   # allocates the staging, loads the code objects
     paths = det.jpeg_last_paths()
     print("entropy mode %s, restart interval of the first file %d MCUs; paths of the batch: %d host, %d device, %d refused by the device" %
@@ -236,7 +293,7 @@ def main():
     except ImportError:
         print("(d) Pillow is not installed here")
     if not a.no_trace:
-        kernel_pass(files, a, float(np.sum(h2d)) + n * 496)
+        kernel_pass(files, a, float(np.sum(h2d)) + n * 496, stored)
 
 
 if __name__ == "__main__":
