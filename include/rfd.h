@@ -567,6 +567,64 @@ RFD_API int rfd_gallery_file_info(const char *path, int *dim, int *rows, int *li
  * kernel scatters by this function and tests pin that it is a bijection and that an MFMA operand fetch is one 1 KiB span */
 RFD_API int64_t rfd_debug_gallery_offset(int dim, int row, int d);
 
+/* ---- every detected face of a frame: the packed face list.  FaceSelection keeps one face per frame (eKYC); the gallery's
+ *      search pass scores 32 queries at once, and a group photo or a door camera holds many faces.  Here up to max_faces
+ *      detections of each of n frames become ONE dense list of T faces in HBM, and every listed face is aligned and tensorised
+ *      by the arithmetic of the one-face path (the same kernels, reading frame[t] instead of frame t).  The whole path runs in the
+ *      context's stream order with no host synchronisation; T itself is a number the host never needs.
+ *      The list rule.  For frame b, walk rows i = 0 .. count[b]-1 of its detection slab in the detector's order (descending
+ *      score; a count outside [0, max_det] is clamped).  A row PASSES when
+ *          x2 - x1 >= min_face_px  &&  y2 - y1 >= min_face_px  &&  score >= min_score
+ *      i.e. fminf(x2 - x1, y2 - y1) >= min_face_px on numbers; each difference is one f32 subtraction; a NaN in any of the five
+ *      values makes its comparison false, so the row fails.  The first max_faces passing rows are TAKEN; c[b] is their number.
+ *      first[b] = c[0] + .. + c[b-1] (first[0] = 0), first[n] = T = total[0].  Packed face t in [first[b], first[b+1]) is the
+ *      (t - first[b])-th taken row of frame b: frame[t] = b, row[t] = its slab row, box[t] / kps[t] = that row's values.
+ *      The caller gives the capacity `cap` of the per-face arrays, in faces (any cap >= 1: it is not bound by max_batch_size).
+ *      total[0] = T is the untruncated count, as rfd_dets.total is; first[] is not truncated either.  Faces t >= cap are dropped,
+ *      so later frames lose first.  EVERY PER-FACE OUTPUT ROW t >= min(T, cap) IS LEFT EXACTLY AS THE CALLER PASSED IT.
+ *      Per packed face t < min(T, cap): status[t] is 0, 1 or -3 (-1 and -2 cannot occur: a listed face has a box and key
+ *      points); crops[t] is written unless crops is NULL; tensors[j][t] for j < k.  All of them are byte-identical to what
+ *      rfd_align_faces_tensors returns for the single frame frame[t] with box[t], kps[t] and found = 3.
+ *      Errors: max_faces < 1, cap < 1, a negative or non-finite min_face_px, a non-finite min_score: RFD_ERR_INVALID_ARG, and
+ *      rfd_last_error() names the field; k > RFD_MAX_FACE_TENSORS: RFD_ERR_CAPACITY; n > max_batch_size: RFD_ERR_CAPACITY.
+ *      A NULL list config is the default one, a NULL alignment config the reference's. ---- */
+typedef struct rfd_face_list_config {
+    int32_t max_faces;     /* per frame, >= 1 */
+    float   min_face_px;   /* >= 0, finite: the narrower side of the box, in source pixels */
+    float   min_score;     /* finite */
+    int32_t reserved[4];
+} rfd_face_list_config;
+RFD_API void rfd_face_list_config_default(rfd_face_list_config *cfg); /* 32, 0, 0: one gallery search pass per frame */
+typedef struct rfd_face_list {
+    int32_t *total;   /* [1]   */
+    int32_t *first;   /* [n+1] */
+    int32_t *frame;   /* [cap] */
+    int32_t *row;     /* [cap] */
+    float   *box;     /* [cap][5]  */
+    float   *kps;     /* [cap][10] */
+    int32_t *status;  /* [cap] */
+    uint8_t *crops;   /* [cap][out_h][out_w][3], may be NULL */
+    float   *tensors[RFD_MAX_FACE_TENSORS]; /* [j < k]: [cap][3][cfgs[j].out_h][cfgs[j].out_w] */
+} rfd_face_list;
+/* Stage-level, host pointers: frames, and detections as rfd_detect_batch returns them (dets->boxes / landmarks / count, as
+ * rfd_select_faces takes them) -> the list, through the kernels of the two entries below.  k = 0 with crops = NULL gives the
+ * list (and the status) alone.  The call waits for the stream once, to learn T, and then fetches only the min(T, cap) listed
+ * rows: the tail of the caller's host arrays stays untouched too. */
+RFD_API int rfd_align_detections(rfd_ctx *ctx, const rfd_image *imgs, int n, const rfd_dets *dets,
+                                 const rfd_face_list_config *list_cfg, const rfd_alignment_config *align_cfg,
+                                 const rfd_face_tensor_config *cfgs, int k, int cap, rfd_face_list *out);
+/* Fused: host frames in, host list out; the frames cross PCIe once, detections never leave HBM. */
+RFD_API int rfd_detect_align_all_batch(rfd_ctx *ctx, const rfd_image *imgs, int n, const rfd_face_list_config *list_cfg,
+                                       const rfd_alignment_config *align_cfg, const rfd_face_tensor_config *cfgs, int k,
+                                       int cap, rfd_face_list *out);
+/* The device-resident form (conventions of rfd_detect_faces_device): every imgs[i].data and every pointer of `out` is DEVICE
+ * memory.  Detection, the list, alignment and tensors are enqueued on the context's stream; async = 0 returns after the stream
+ * has drained, any other value at once with nothing waited for.  tensors[j] with n = cap rows is what the models and then
+ * rfd_normalize_embeddings_device -> rfd_gallery_search_device take; the rows past total are the caller's to ignore. */
+RFD_API int rfd_detect_all_faces_device(rfd_ctx *ctx, const rfd_image *imgs, int n, const rfd_face_list_config *list_cfg,
+                                        const rfd_alignment_config *align_cfg, const rfd_face_tensor_config *cfgs, int k,
+                                        int cap, rfd_face_list *out, int async);
+
 /* ---- JPEG decode: the first line of FacePipeline::extract (pipeline.rs:188-249), byte_data_to_opencv (src/utils/utils.rs:8-52),
  *      an imdecode of the file's bytes.  File bytes in, BGR frames in HBM out: the frames rfd_detect_batch_device and
  *      rfd_detect_faces_device read, with no JPEG library in the caller, no decoded frame on PCIe.

@@ -236,6 +236,76 @@ inline std::vector<float> normalize_embeddings(RetinaFaceDetection &det, const s
     return out;
 }
 
+// Every detected face of a frame (rfd.h, "the packed face list"): up to max_faces detections per frame as one dense list of
+// aligned crops and model inputs.  Vectors are sized for `cap` faces; the library writes the first valid() of them.
+struct FaceListConfig : rfd_face_list_config {
+    FaceListConfig() { rfd_face_list_config_default(this); }   // 32 faces per frame, no size or score floor
+};
+struct FaceList {
+    int32_t total = 0;                         // T, not clamped to cap
+    int cap = 0;
+    std::vector<int32_t> first, frame, row, status;   // [n + 1], [cap] x 3
+    std::vector<float> box, kps;               // [cap][5], [cap][10]
+    std::vector<uint8_t> crops;                // [cap][out_h][out_w][3], empty if not asked for
+    std::vector<std::vector<float>> tensors;   // per config: [cap][3][out_h][out_w]
+    int valid() const { return total < cap ? total : cap; }
+};
+namespace detail {
+inline rfd_face_list face_list_pointers(FaceList &r, std::size_t n, int cap, const rfd_alignment_config &ac,
+                                        const std::vector<FaceTensorConfig> &cfgs, bool want_crops)
+{
+    const std::size_t c = cap > 0 ? (std::size_t)cap : 1, k = cfgs.size() <= RFD_MAX_FACE_TENSORS ? cfgs.size() : 0;
+    r.cap = cap;
+    r.first.assign(n + 1, 0); r.frame.assign(c, 0); r.row.assign(c, 0); r.status.assign(c, 0);
+    r.box.assign(c * 5, 0.f); r.kps.assign(c * 10, 0.f);
+    if (want_crops) r.crops.assign(c * 3 * (ac.out_w > 0 ? ac.out_w : 0) * (ac.out_h > 0 ? ac.out_h : 0), 0);
+    r.tensors.resize(k);
+    rfd_face_list p = {&r.total, r.first.data(), r.frame.data(), r.row.data(), r.box.data(), r.kps.data(), r.status.data(),
+                       want_crops ? r.crops.data() : nullptr, {}};
+    for (std::size_t j = 0; j < k; ++j) {
+        r.tensors[j].assign(c * 3 * (cfgs[j].out_w > 0 ? cfgs[j].out_w : 0) * (cfgs[j].out_h > 0 ? cfgs[j].out_h : 0), 0.f);
+        p.tensors[j] = r.tensors[j].data();
+    }
+    return p;
+}
+} // namespace detail
+// frames + the detections rfd_detect_batch returned for them -> the list (stage level: the kernels of detect_align_all)
+inline FaceList align_detections(RetinaFaceDetection &det, const std::vector<rfd_image> &imgs, const rfd_dets &dets,
+                                 const std::vector<FaceTensorConfig> &cfgs, int cap, const FaceListConfig &lc = FaceListConfig(),
+                                 const rfd_alignment_config *ac = nullptr, bool want_crops = true)
+{
+    rfd_alignment_config a;
+    rfd_alignment_config_default(&a);
+    if (ac) a = *ac;
+    FaceList r;
+    rfd_face_list p = detail::face_list_pointers(r, imgs.size(), cap, a, cfgs, want_crops);
+    std::vector<rfd_face_tensor_config> c(cfgs.begin(), cfgs.end());
+    check(rfd_align_detections(det.raw(), imgs.data(), (int)imgs.size(), &dets, &lc, &a, c.data(), (int)c.size(), cap, &p));
+    return r;
+}
+// detect, list, align, tensorise: host frames in, host list out; the frames cross PCIe once
+inline FaceList detect_align_all(RetinaFaceDetection &det, const std::vector<rfd_image> &imgs, const std::vector<FaceTensorConfig> &cfgs,
+                                 int cap, const FaceListConfig &lc = FaceListConfig(), const rfd_alignment_config *ac = nullptr,
+                                 bool want_crops = true)
+{
+    rfd_alignment_config a;
+    rfd_alignment_config_default(&a);
+    if (ac) a = *ac;
+    FaceList r;
+    rfd_face_list p = detail::face_list_pointers(r, imgs.size(), cap, a, cfgs, want_crops);
+    std::vector<rfd_face_tensor_config> c(cfgs.begin(), cfgs.end());
+    check(rfd_detect_align_all_batch(det.raw(), imgs.data(), (int)imgs.size(), &lc, &a, c.data(), (int)c.size(), cap, &p));
+    return r;
+}
+// the device-resident form: frames and every pointer of `out` in device memory; async: no host synchronisation
+inline void detect_all_faces_device(RetinaFaceDetection &det, const std::vector<rfd_image> &imgs, const std::vector<FaceTensorConfig> &cfgs,
+                                    int cap, rfd_face_list &out, const FaceListConfig &lc = FaceListConfig(),
+                                    const rfd_alignment_config *ac = nullptr, bool async = false)
+{
+    std::vector<rfd_face_tensor_config> c(cfgs.begin(), cfgs.end());
+    check(rfd_detect_all_faces_device(det.raw(), imgs.data(), (int)imgs.size(), &lc, ac, c.data(), (int)c.size(), cap, &out, async ? 1 : 0));
+}
+
 // FaceAntiSpoofing (face_antispoofing.rs) minus the remote miniFAS models: FAS config, the model inputs, the decision rule.
 // Defined per face (rfd.h: the reference's two bugs are not copied).
 struct LivenessConfig : rfd_liveness_config {

@@ -6,7 +6,9 @@
 #include <stdarg.h>
 #include <stdlib.h>
 
+#include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -193,6 +195,10 @@ struct rfd_ctx {
     // model inputs of the quality / ID stages: staged crops and per-config planes of the host entries; in / out staging of the
     // host forms of the decision rule and the normalisation
     DevBuf face_in, face_tensors[kMaxFaceTensors], face_io[2];
+    // packed face list of the host-output entries (FaceListView), and the page-locked copy of total | first [B + 1] that tells
+    // the host how many rows to fetch; both allocated by the first such call
+    DevBuf list_out;
+    Pinned<int> h_list;
     // Per-call descriptors travel through rings of page-locked slots, so enqueueing never blocks on the previous call.
     static constexpr int kRing = 4;
     PinnedRing<kRing> frame_ring; // PreImage [B] | det_scale f32 [B]; its events can be timed
@@ -1815,6 +1821,198 @@ int rfd_detect_faces_device(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_
     RFD_TRY(select_enqueue(c, dev.boxes, dev.landmarks, dev.count, hh.data(), ww.data(), n, sel_cfg, is_enroll, out->box, out->kps,
                            out->found));
     RFD_TRY(align_tensors_enqueue(c, n, out->box, out->kps, out->found, align_cfg, cfgs, k, out->tensors, out->crops, out->status));
+    if (async) return RFD_OK;
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    return check_nms_flag(c);
+}
+
+// ---- every detected face of a frame: the packed face list (rfd.h) ----
+void rfd_face_list_config_default(rfd_face_list_config *cfg)
+{
+    if (!cfg) return;
+    memset(cfg, 0, sizeof *cfg);
+    cfg->max_faces = RFD_GALLERY_MAX_K; // one gallery search pass (32 queries) per frame
+    cfg->min_face_px = 0.0f;
+    cfg->min_score = 0.0f;
+}
+
+// the caller's list config or, for null, the default (into *def); every refusal names its field
+static int resolve_list_cfg(const rfd_face_list_config **cfg, rfd_face_list_config *def, int cap)
+{
+    if (!*cfg) { rfd_face_list_config_default(def); *cfg = def; }
+    if ((*cfg)->max_faces < 1) { set_error("invalid argument: max_faces %d < 1", (*cfg)->max_faces); return RFD_ERR_INVALID_ARG; }
+    if (!std::isfinite((*cfg)->min_face_px) || (*cfg)->min_face_px < 0.0f) {
+        set_error("invalid argument: min_face_px %g is negative or not finite", (double)(*cfg)->min_face_px);
+        return RFD_ERR_INVALID_ARG;
+    }
+    if (!std::isfinite((*cfg)->min_score)) { set_error("invalid argument: min_score %g is not finite", (double)(*cfg)->min_score); return RFD_ERR_INVALID_ARG; }
+    if (cap < 1) { set_error("invalid argument: cap %d < 1", cap); return RFD_ERR_INVALID_ARG; }
+    return RFD_OK;
+}
+
+static int check_face_list_out(const rfd_face_list *out)
+{
+    RFD_CHECK_ARG(out && out->total && out->first && out->frame && out->row && out->box && out->kps && out->status,
+                  "face list output pointers are null");
+    return RFD_OK;
+}
+
+// the faces a call can list at most: what the set-up and warp launches are sized by (the true count stays in HBM)
+static int face_list_bound(const rfd_ctx *c, int n, const rfd_face_list_config *cfg, int cap)
+{
+    return (int)std::min<long long>(cap, (long long)n * std::min(cfg->max_faces, c->cfg.max_det));
+}
+
+// The list of the detections in the device slabs `dets` of the n frames whose descriptors sit in c->imgs, then set-up, warp
+// and tensors over it, all into the DEVICE arrays of `out`; enqueued only.  align_tensors_enqueue with a frame map: the same
+// kernels, sized by the host-known bound, every face past min(total, cap) leaving its rows alone.
+static int face_list_enqueue(rfd_ctx *c, int n, const rfd_dets &dets, const rfd_face_list_config *lc,
+                             const rfd_alignment_config *cfg, const rfd_face_tensor_config *cfgs, int k, int cap,
+                             const rfd_face_list &out)
+{
+    FaceListParams lp;
+    memset(&lp, 0, sizeof lp);
+    lp.boxes = dets.boxes; lp.lmk = dets.landmarks; lp.count = dets.count;
+    lp.n = n; lp.max_det = c->cfg.max_det; lp.max_faces = lc->max_faces; lp.cap = cap;
+    lp.min_face_px = lc->min_face_px; lp.min_score = lc->min_score;
+    lp.total = out.total; lp.first = out.first; lp.frame = out.frame; lp.row = out.row; lp.box = out.box; lp.kps = out.kps;
+    RFD_TRY(launch_face_list(lp, c->stream));
+    const int bound = face_list_bound(c, n, lc, cap);
+    FaceTensorParams fused, rest;
+    memset(&fused, 0, sizeof fused);
+    memset(&rest, 0, sizeof rest);
+    for (int j = 0; j < k; ++j) {
+        FaceTensorParams &t = (cfgs[j].out_w == cfg->out_w && cfgs[j].out_h == cfg->out_h) ? fused : rest;
+        fill_face_tensor_cfg(t.cfg[t.k++], cfgs[j], out.tensors[j], cfg->out_w, cfg->out_h);
+    }
+    uint8_t *d_crops = out.crops;
+    if (!d_crops && rest.k) {
+        RFD_TRY(c->align_out.reserve((size_t)bound * cfg->out_w * cfg->out_h * 3));
+        d_crops = (uint8_t *)c->align_out.p;
+    }
+    RFD_TRY(c->align_faces.reserve((size_t)bound * sizeof(AlignFace)));
+    AlignParams ap;
+    memset(&ap, 0, sizeof ap);
+    ap.imgs = (const PreImage *)c->imgs.p;
+    ap.box = out.box; ap.kps = out.kps; // found null: a listed face has both
+    memcpy(ap.std_lmk, cfg->standard_landmarks, sizeof ap.std_lmk);
+    ap.out_w = cfg->out_w; ap.out_h = cfg->out_h; ap.n = bound;
+    ap.faces = (AlignFace *)c->align_faces.p;
+    ap.status = out.status;
+    ap.out = d_crops;
+    ap.frame = out.frame; ap.total = out.total; ap.cap = cap;
+    fused.n = rest.n = bound;
+    fused.crop_w = rest.crop_w = cfg->out_w;
+    fused.crop_h = rest.crop_h = cfg->out_h;
+    rest.crops = d_crops;
+    rest.status = out.status;
+    rest.total = out.total; rest.cap = cap;
+    RFD_TRY(launch_face_align_tensors(ap, fused, c->stream));
+    return launch_face_tensors(rest, c->stream);
+}
+
+// c->list_out holds the list of a host-output call: total [1] | first [n + 1] | frame, row, status [bound] each |
+// box [bound][5] | kps [bound][10]
+static int face_list_own(rfd_ctx *c, int n, int bound, const rfd_alignment_config *cfg, const rfd_face_tensor_config *cfgs, int k,
+                         bool want_crops, rfd_face_list *v)
+{
+    RFD_TRY(c->list_out.reserve(((size_t)n + 2 + (size_t)bound * 18) * sizeof(int)));
+    RFD_TRY(c->h_list.alloc((size_t)c->cfg.max_batch_size + 2));
+    memset(v, 0, sizeof *v);
+    int32_t *o = (int32_t *)c->list_out.p;
+    v->total = o; v->first = o + 1;
+    v->frame = o + n + 2; v->row = v->frame + bound; v->status = v->row + bound;
+    v->box = (float *)(v->status + bound); v->kps = v->box + (size_t)bound * 5;
+    if (want_crops) {
+        RFD_TRY(c->align_out.reserve((size_t)bound * cfg->out_w * cfg->out_h * 3));
+        v->crops = (uint8_t *)c->align_out.p;
+    }
+    for (int j = 0; j < k; ++j) {
+        RFD_TRY(c->face_tensors[j].reserve((size_t)bound * 3 * cfgs[j].out_w * cfgs[j].out_h * sizeof(float)));
+        v->tensors[j] = (float *)c->face_tensors[j].p;
+    }
+    return RFD_OK;
+}
+
+// face_list_enqueue into the context's own buffers, then to the host pointers of `out`: the stream is waited for once, for
+// total and first, and only the min(T, cap) listed rows are fetched after it -- the caller's rows past them stay as they are.
+static int face_list_to_host(rfd_ctx *c, int n, const rfd_dets &dets, const rfd_face_list_config *lc,
+                             const rfd_alignment_config *cfg, const rfd_face_tensor_config *cfgs, int k, int cap,
+                             rfd_face_list *out)
+{
+    rfd_face_list v;
+    RFD_TRY(face_list_own(c, n, face_list_bound(c, n, lc, cap), cfg, cfgs, k, out->crops != nullptr, &v));
+    RFD_TRY(face_list_enqueue(c, n, dets, lc, cfg, cfgs, k, cap, v));
+    RFD_HIP(hipMemcpyAsync(c->h_list, v.total, ((size_t)n + 2) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    RFD_TRY(check_nms_flag(c));
+    out->total[0] = c->h_list[0];
+    memcpy(out->first, c->h_list + 1, ((size_t)n + 1) * sizeof(int));
+    const size_t rows = (size_t)std::min(c->h_list[0], cap);
+    if (!rows) return RFD_OK;
+    RFD_HIP(hipMemcpy(out->frame, v.frame, rows * sizeof(int), hipMemcpyDeviceToHost));
+    RFD_HIP(hipMemcpy(out->row, v.row, rows * sizeof(int), hipMemcpyDeviceToHost));
+    RFD_HIP(hipMemcpy(out->status, v.status, rows * sizeof(int), hipMemcpyDeviceToHost));
+    RFD_HIP(hipMemcpy(out->box, v.box, rows * 5 * sizeof(float), hipMemcpyDeviceToHost));
+    RFD_HIP(hipMemcpy(out->kps, v.kps, rows * 10 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out->crops) RFD_HIP(hipMemcpy(out->crops, v.crops, rows * cfg->out_w * cfg->out_h * 3, hipMemcpyDeviceToHost));
+    for (int j = 0; j < k; ++j)
+        RFD_HIP(hipMemcpy(out->tensors[j], v.tensors[j], rows * 3 * cfgs[j].out_w * cfgs[j].out_h * sizeof(float), hipMemcpyDeviceToHost));
+    return RFD_OK;
+}
+
+// the argument checks the three entries share
+static int check_face_list_call(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_face_list_config **lc, rfd_face_list_config *ldef,
+                                const rfd_alignment_config **ac, rfd_alignment_config *adef, const rfd_face_tensor_config *cfgs,
+                                int k, int cap, const rfd_face_list *out)
+{
+    RFD_CHECK_ARG(c != nullptr, "ctx is null");
+    RFD_TRY(check_face_list_out(out));
+    RFD_TRY(check_face_tensor_args(cfgs, k, out->tensors, 0));
+    RFD_TRY(resolve_list_cfg(lc, ldef, cap));
+    RFD_TRY(resolve_align_cfg(ac, adef));
+    return check_images(c, imgs, n);
+}
+
+int rfd_align_detections(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_dets *dets, const rfd_face_list_config *list_cfg,
+                         const rfd_alignment_config *align_cfg, const rfd_face_tensor_config *cfgs, int k, int cap,
+                         rfd_face_list *out)
+{
+    rfd_face_list_config ldef;
+    rfd_alignment_config adef;
+    RFD_TRY(check_face_list_call(c, imgs, n, &list_cfg, &ldef, &align_cfg, &adef, cfgs, k, cap, out));
+    RFD_CHECK_ARG(dets && dets->boxes && dets->landmarks && dets->count, "detections are null");
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    RFD_TRY(stage_frames(c, imgs, n, false));
+    rfd_dets dev = own_slabs(c);
+    dev.total = nullptr; // the list does not read it
+    RFD_TRY(copy_slabs(c, dev, *dets, n, hipMemcpyHostToDevice));
+    return face_list_to_host(c, n, dev, list_cfg, align_cfg, cfgs, k, cap, out);
+}
+
+int rfd_detect_align_all_batch(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_face_list_config *list_cfg,
+                               const rfd_alignment_config *align_cfg, const rfd_face_tensor_config *cfgs, int k, int cap,
+                               rfd_face_list *out)
+{
+    rfd_face_list_config ldef;
+    rfd_alignment_config adef;
+    RFD_TRY(check_face_list_call(c, imgs, n, &list_cfg, &ldef, &align_cfg, &adef, cfgs, k, cap, out));
+    rfd_dets dev = own_slabs(c);
+    // the staged frames and their descriptors (c->staging / c->imgs) stay valid until the next call on this context
+    RFD_TRY(detect_impl(c, imgs, n, &dev, /*outputs stay on the device*/ true, /*async*/ 1, /*frames on host*/ false));
+    return face_list_to_host(c, n, dev, list_cfg, align_cfg, cfgs, k, cap, out);
+}
+
+int rfd_detect_all_faces_device(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_face_list_config *list_cfg,
+                                const rfd_alignment_config *align_cfg, const rfd_face_tensor_config *cfgs, int k, int cap,
+                                rfd_face_list *out, int async)
+{
+    rfd_face_list_config ldef;
+    rfd_alignment_config adef;
+    RFD_TRY(check_face_list_call(c, imgs, n, &list_cfg, &ldef, &align_cfg, &adef, cfgs, k, cap, out));
+    rfd_dets dev = own_slabs(c);
+    RFD_TRY(detect_impl(c, imgs, n, &dev, /*outputs stay on the device*/ true, /*async*/ 1, /*frames on device*/ true));
+    RFD_TRY(face_list_enqueue(c, n, dev, list_cfg, align_cfg, cfgs, k, cap, *out));
     if (async) return RFD_OK;
     RFD_HIP(hipStreamSynchronize(c->stream));
     return check_nms_flag(c);

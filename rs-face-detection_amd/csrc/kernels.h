@@ -88,6 +88,23 @@ struct SelectParams {
 };
 int launch_face_select(const SelectParams &p, hipStream_t s);
 
+// The packed face list (rfd.h, "every detected face"): the first max_faces rows of every frame's slab that pass the
+// predicate, in (frame, row) order, as one dense list.  One workgroup; the order is decided by ballots and prefix sums alone.
+struct FaceListParams {
+    const float *boxes; // [n][max_det][5]
+    const float *lmk;   // [n][max_det][10]
+    const int *count;   // [n]
+    int n, max_det, max_faces, cap;
+    float min_face_px, min_score;
+    int *total;         // [1]: T, not clamped to cap
+    int *first;         // [n + 1]: exclusive prefix of the per-frame counts; also the kernel's scratch for those counts
+    int *frame;         // [cap]
+    int *row;           // [cap]
+    float *box;         // [cap][5]
+    float *kps;         // [cap][10]
+};
+int launch_face_list(const FaceListParams &p, hipStream_t s);
+
 // FaceAlignment::call on the device (face_alignment.rs:27-141): 5-point similarity to the template + cv::warpAffine
 // (INTER_LINEAR, BORDER_CONSTANT 0) of the source frame, or the reference's crop + resize fallback
 struct AlignFace {      // per face, filled by the set-up kernel
@@ -101,13 +118,19 @@ struct AlignParams {
     const PreImage *imgs; // [n] frames of the batch (device descriptors)
     const float *box;     // [n][5] selected detection
     const float *kps;     // [n][10] its key points
-    const int *found;     // [n] selection flags: bit 0 box, bit 1 key points
+    const int *found;     // [n] selection flags: bit 0 box, bit 1 key points; null: 3 for every face (a face list)
     float std_lmk[10];    // template (config.rs:46-52)
     int out_w, out_h, n;
     AlignFace *faces;     // [n] scratch
     int *status;          // [n]: 0 aligned, 1 fallback crop, -1 no key points (the reference's call errors), -2 no face,
                           //      -3 fallback ROI outside the frame (Mat::roi error)
     uint8_t *out;         // [n][out_h][out_w][3] u8 BGR
+    // A packed face list: face t reads frame frame[t], and a face t >= min(*total, cap), both read on the device, is left
+    // alone: nothing of it is written.  n is then the host-known bound of the launch.  Null / null: face b is frame b and all
+    // n faces are done -- the one-face entries.  face0: the first face of this launch (the launchers split at the grid limit).
+    const int *frame;
+    const int *total;
+    int cap, face0;
 };
 int launch_face_align(const AlignParams &p, hipStream_t s);
 
@@ -127,6 +150,8 @@ struct FaceTensorParams {
     const int *status;       // [n] alignment status or null: a face with a negative status gets all-zero tensors
     int n, crop_w, crop_h, k;
     FaceTensorCfg cfg[kMaxFaceTensors];
+    const int *total;        // as in AlignParams (null: all n faces)
+    int cap, face0;
 };
 // every config of p from crops in HBM: one launch for all k configs and n faces
 int launch_face_tensors(const FaceTensorParams &p, hipStream_t s);

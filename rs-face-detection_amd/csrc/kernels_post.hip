@@ -862,6 +862,95 @@ int launch_face_select(const SelectParams &p, hipStream_t s)
     return RFD_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The packed face list (rfd.h, "every detected face of a frame"): every frame's first max_faces rows that pass
+//     x2 - x1 >= min_face_px && y2 - y1 >= min_face_px && score >= min_score
+// (= fminf(x2 - x1, y2 - y1) >= min_face_px on numbers; every comparison is false on a NaN) become one dense list in
+// (frame, row) order.  One workgroup of 16 waves, wave w takes frames w, w + 16, ...:
+//   1. a wave walks its frame's rows 64 at a time: predicate, __ballot, popcount -> c[b], kept in first[b + 1];
+//   2. wave 0 turns first[1..n] into the inclusive prefix of c (shuffle scan, 64 frames a step, carry in a register);
+//   3. every wave walks its frames again and stores row i of frame b at first[b] + (taken rows of b below i),
+//      the latter from the ballot mask below its own lane.
+// A row's place follows from (frame, row) alone: no atomics, the same list on every run.  first[] doubles as the scratch of
+// step 1, so n is bounded by nothing here; a walk stops once max_faces rows are taken.  Latency-bound scalar work, like the
+// selection it sits next to: n * max_det * 20 bytes of boxes are read at most twice.
+// ------------------------------------------------------------------------------------------------
+constexpr int kFaceListThreads = 1024;
+
+// rows of slab `boxes` taken below row base + 64 (at most max_faces); pass / below: this lane's row base + lane passes, and
+// how many taken rows precede it
+__device__ __forceinline__ bool face_list_step(const float *boxes, int cnt, int base, int lane, float min_face_px, float min_score,
+                                               int &taken, int &below)
+{
+    const int i = base + lane;
+    bool pass = false;
+    if (i < cnt) {
+        const float *r = boxes + 5 * i;
+        pass = __fsub_rn(r[2], r[0]) >= min_face_px && __fsub_rn(r[3], r[1]) >= min_face_px && r[4] >= min_score;
+    }
+    const unsigned long long m = __ballot(pass);
+    below = taken + __popcll(m & ((1ull << lane) - 1ull));
+    taken += __popcll(m);
+    return pass;
+}
+
+__global__ void __launch_bounds__(kFaceListThreads) face_list_kernel(FaceListParams p)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr int kWaves = kFaceListThreads / 64;
+    for (int b = wave; b < p.n; b += kWaves) { // 1: c[b]
+        const int cnt = min(max(p.count[b], 0), p.max_det);
+        const float *boxes = p.boxes + (size_t)b * p.max_det * 5;
+        int taken = 0, below;
+        for (int base = 0; base < cnt && taken < p.max_faces; base += 64)
+            face_list_step(boxes, cnt, base, lane, p.min_face_px, p.min_score, taken, below);
+        if (lane == 0) p.first[b + 1] = min(taken, p.max_faces);
+    }
+    __syncthreads();
+    if (wave == 0) { // 2: first[b + 1] = c[0] + ... + c[b]
+        int carry = 0;
+        for (int base = 0; base < p.n; base += 64) {
+            const int b = base + lane;
+            int v = b < p.n ? p.first[b + 1] : 0;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int u = __shfl_up(v, d);
+                if (lane >= d) v += u;
+            }
+            if (b < p.n) p.first[b + 1] = carry + v;
+            carry += __shfl(v, 63);
+        }
+        if (lane == 0) { p.first[0] = 0; p.total[0] = carry; }
+    }
+    __syncthreads();
+    for (int b = wave; b < p.n; b += kWaves) { // 3: the rows themselves
+        const int cnt = min(max(p.count[b], 0), p.max_det);
+        const float *boxes = p.boxes + (size_t)b * p.max_det * 5;
+        const float *kps = p.lmk + (size_t)b * p.max_det * 10;
+        const int t0 = p.first[b];
+        int taken = 0, below;
+        for (int base = 0; base < cnt && taken < p.max_faces && t0 + taken < p.cap; base += 64) {
+            const bool pass = face_list_step(boxes, cnt, base, lane, p.min_face_px, p.min_score, taken, below);
+            const int t = t0 + below;
+            if (!pass || below >= p.max_faces || t >= p.cap) continue;
+            const int i = base + lane;
+            p.frame[t] = b;
+            p.row[t] = i;
+#pragma unroll
+            for (int c = 0; c < 5; ++c) p.box[(size_t)t * 5 + c] = boxes[5 * i + c];
+#pragma unroll
+            for (int c = 0; c < 10; ++c) p.kps[(size_t)t * 10 + c] = kps[10 * i + c];
+        }
+    }
+}
+
+int launch_face_list(const FaceListParams &p, hipStream_t s)
+{
+    hipLaunchKernelGGL(face_list_kernel, dim3(1), dim3(kFaceListThreads), 0, s, p);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
 size_t nms_lds_bytes(int total_anchors, bool reg)
 {
     const int nwords = ceil_div(total_anchors, 64);

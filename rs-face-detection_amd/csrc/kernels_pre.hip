@@ -261,14 +261,18 @@ __device__ __forceinline__ int cv_round_sat(double v)
     return __double2int_rn(v);
 }
 
+// A face of a launch is done always (total null: the one-face entries) or, in a packed face list, while it lies below
+// min(*total, cap): the count is read from HBM, the host never sees it.
+__device__ __forceinline__ bool face_in_list(const int *total, int cap, int b) { return !total || b < min(*total, cap); }
+
 __global__ void align_setup_kernel(AlignParams p)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= p.n) return;
+    if (b >= p.n || !face_in_list(p.total, p.cap, b)) return;
     AlignFace f;
     memset(&f, 0, sizeof f);
-    const int found = p.found[b];
-    const PreImage im = p.imgs[b];
+    const int found = p.found ? p.found[b] : 3;
+    const PreImage im = p.imgs[p.frame ? p.frame[b] : b];
     if (!(found & 1)) {
         f.mode = -2;
     } else if (!(found & 2)) {
@@ -342,25 +346,30 @@ __device__ __forceinline__ void align_warp_px(const AlignFace &f, const PreImage
 
 __global__ void __launch_bounds__(256) align_warp_kernel(AlignParams p)
 {
-    const int b = blockIdx.y;
+    const int b = p.face0 + blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= p.out_w * p.out_h) return;
+    if (i >= p.out_w * p.out_h || !face_in_list(p.total, p.cap, b)) return;
     const int y = i / p.out_w, x = i - y * p.out_w;
     const AlignFace &f = p.faces[b];
     uint8_t *d = p.out + ((size_t)b * p.out_h * p.out_w + i) * 3;
     if (f.mode < 0) { d[0] = d[1] = d[2] = 0; return; }
-    const PreImage im = p.imgs[b];
+    const PreImage im = p.imgs[p.frame ? p.frame[b] : b];
     int v[3];
     align_warp_px(f, im, x, y, v);
     d[0] = (uint8_t)v[0]; d[1] = (uint8_t)v[1]; d[2] = (uint8_t)v[2];
 }
 
+constexpr int kMaxGridY = 65535; // faces per launch of the kernels that take the face from blockIdx.y
+
 int launch_face_align(const AlignParams &p, hipStream_t s)
 {
     hipLaunchKernelGGL(align_setup_kernel, dim3(ceil_div(p.n, 64)), dim3(64), 0, s, p);
     RFD_HIP(hipGetLastError());
-    hipLaunchKernelGGL(align_warp_kernel, dim3(ceil_div(p.out_w * p.out_h, 256), p.n), dim3(256), 0, s, p);
-    RFD_HIP(hipGetLastError());
+    AlignParams q = p;
+    for (q.face0 = 0; q.face0 < p.n; q.face0 += kMaxGridY) {
+        hipLaunchKernelGGL(align_warp_kernel, dim3(ceil_div(p.out_w * p.out_h, 256), min(p.n - q.face0, kMaxGridY)), dim3(256), 0, s, q);
+        RFD_HIP(hipGetLastError());
+    }
     return RFD_OK;
 }
 
@@ -381,15 +390,15 @@ __device__ __forceinline__ void face_tensor_store(const FaceTensorCfg &c, int b,
 // align_warp_kernel + the planes of every config of the crop's own size, from the registers that hold the pixel
 __global__ void __launch_bounds__(256) align_warp_tensor_kernel(AlignParams p, FaceTensorParams t)
 {
-    const int b = blockIdx.y;
+    const int b = p.face0 + blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= p.out_w * p.out_h) return;
+    if (i >= p.out_w * p.out_h || !face_in_list(p.total, p.cap, b)) return;
     const int y = i / p.out_w, x = i - y * p.out_w;
     const AlignFace &f = p.faces[b];
     const bool zero = f.mode < 0;
     int v[3] = {0, 0, 0};
     if (!zero) {
-        const PreImage im = p.imgs[b];
+        const PreImage im = p.imgs[p.frame ? p.frame[b] : b];
         align_warp_px(f, im, x, y, v);
     }
     if (p.out) {
@@ -405,8 +414,12 @@ int launch_face_align_tensors(const AlignParams &a, const FaceTensorParams &t, h
 {
     hipLaunchKernelGGL(align_setup_kernel, dim3(ceil_div(a.n, 64)), dim3(64), 0, s, a);
     RFD_HIP(hipGetLastError());
-    hipLaunchKernelGGL(align_warp_tensor_kernel, dim3(ceil_div(a.out_w * a.out_h, 256), a.n), dim3(256), 0, s, a, t);
-    RFD_HIP(hipGetLastError());
+    if (a.total && !a.out && !t.k) return RFD_OK; // a face list alone: the status is all that was asked for
+    AlignParams q = a;
+    for (q.face0 = 0; q.face0 < a.n; q.face0 += kMaxGridY) {
+        hipLaunchKernelGGL(align_warp_tensor_kernel, dim3(ceil_div(a.out_w * a.out_h, 256), min(a.n - q.face0, kMaxGridY)), dim3(256), 0, s, q, t);
+        RFD_HIP(hipGetLastError());
+    }
     return RFD_OK;
 }
 
@@ -414,9 +427,9 @@ int launch_face_align_tensors(const AlignParams &a, const FaceTensorParams &t, h
 __global__ void __launch_bounds__(256) face_tensor_kernel(FaceTensorParams p)
 {
     const FaceTensorCfg &c = p.cfg[blockIdx.z];
-    const int b = blockIdx.y;
+    const int b = p.face0 + blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= c.out_w * c.out_h) return;
+    if (i >= c.out_w * c.out_h || !face_in_list(p.total, p.cap, b)) return;
     const bool zero = p.status && p.status[b] < 0;
     int v[3] = {0, 0, 0};
     if (!zero) {
@@ -438,8 +451,11 @@ int launch_face_tensors(const FaceTensorParams &p, hipStream_t s)
     if (p.k < 1) return RFD_OK;
     int px = 0;
     for (int j = 0; j < p.k; ++j) px = max(px, p.cfg[j].out_w * p.cfg[j].out_h);
-    hipLaunchKernelGGL(face_tensor_kernel, dim3(ceil_div(px, 256), p.n, p.k), dim3(256), 0, s, p);
-    RFD_HIP(hipGetLastError());
+    FaceTensorParams q = p;
+    for (q.face0 = 0; q.face0 < p.n; q.face0 += kMaxGridY) {
+        hipLaunchKernelGGL(face_tensor_kernel, dim3(ceil_div(px, 256), min(p.n - q.face0, kMaxGridY), p.k), dim3(256), 0, s, q);
+        RFD_HIP(hipGetLastError());
+    }
     return RFD_OK;
 }
 

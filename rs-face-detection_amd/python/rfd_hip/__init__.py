@@ -109,6 +109,15 @@ class rfd_faces(C.Structure):
                 ("status", C.c_void_p), ("tensors", C.c_void_p * MAX_FACE_TENSORS)]
 
 
+class rfd_face_list_config(C.Structure):
+    _fields_ = [("max_faces", C.c_int32), ("min_face_px", C.c_float), ("min_score", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+class rfd_face_list(C.Structure):
+    _fields_ = [("total", C.c_void_p), ("first", C.c_void_p), ("frame", C.c_void_p), ("row", C.c_void_p), ("box", C.c_void_p),
+                ("kps", C.c_void_p), ("status", C.c_void_p), ("crops", C.c_void_p), ("tensors", C.c_void_p * MAX_FACE_TENSORS)]
+
+
 class rfd_liveness_config(C.Structure):
     _fields_ = [("k", C.c_int32), ("scale", C.c_float * MAX_FACE_TENSORS), ("out_w", C.c_int32 * MAX_FACE_TENSORS),
                 ("out_h", C.c_int32 * MAX_FACE_TENSORS), ("reserved", C.c_int32 * 4)]
@@ -163,6 +172,7 @@ API_SYMBOLS = [
     "rfd_set_jpeg_entropy", "rfd_jpeg_last_paths", "rfd_debug_jpeg_intervals", "rfd_debug_jpeg_coefficients_device",
     "rfd_jpeg_orientation", "rfd_set_jpeg_orientation", "rfd_jpeg_last_orientations",
     "rfd_set_jpeg_scale", "rfd_jpeg_scaled_size", "rfd_debug_jpeg_block_counts",
+    "rfd_face_list_config_default", "rfd_align_detections", "rfd_detect_align_all_batch", "rfd_detect_all_faces_device",
 ]
 
 _lib = None
@@ -255,6 +265,11 @@ def load_library(path=None):
     L.rfd_detect_select_align_tensors_batch.argtypes = [vp, C.POINTER(rfd_image), ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, C.POINTER(vp)]
     L.rfd_align_faces_tensors.argtypes = [vp, C.POINTER(rfd_image), ci, vp, vp, vp, vp, vp, vp, vp, ci, C.POINTER(vp)]
     L.rfd_detect_faces_device.argtypes = [vp, C.POINTER(rfd_image), ci, vp, ci, vp, vp, ci, C.POINTER(rfd_faces), ci]
+    L.rfd_face_list_config_default.argtypes = [C.POINTER(rfd_face_list_config)]
+    L.rfd_face_list_config_default.restype = None
+    L.rfd_align_detections.argtypes = [vp, C.POINTER(rfd_image), ci, C.POINTER(rfd_dets), vp, vp, vp, ci, ci, C.POINTER(rfd_face_list)]
+    L.rfd_detect_align_all_batch.argtypes = [vp, C.POINTER(rfd_image), ci, vp, vp, vp, ci, ci, C.POINTER(rfd_face_list)]
+    L.rfd_detect_all_faces_device.argtypes = [vp, C.POINTER(rfd_image), ci, vp, vp, vp, ci, ci, C.POINTER(rfd_face_list), ci]
     L.rfd_quality_decide.argtypes = [vp, vp, ci, ci, C.c_float, vp, vp]
     L.rfd_quality_decide_device.argtypes = [vp, vp, ci, ci, C.c_float, vp, vp]
     L.rfd_normalize_embeddings.argtypes = [vp, vp, ci, ci, vp]
@@ -355,6 +370,47 @@ def liveness_config(scales=None, image_sizes=None):
             c.scale[j] = scales[j]
             c.out_w[j], c.out_h[j] = int(image_sizes[j][0]), int(image_sizes[j][1])
     return c
+
+
+def face_list_config(max_faces=None, min_face_px=None, min_score=None):
+    """rfd_face_list_config: the default (32 faces per frame, no size or score floor) with the given fields replaced"""
+    c = rfd_face_list_config()
+    load_library().rfd_face_list_config_default(C.byref(c))
+    if max_faces is not None:
+        c.max_faces = int(max_faces)
+    if min_face_px is not None:
+        c.min_face_px = min_face_px
+    if min_score is not None:
+        c.min_score = min_score
+    return c
+
+
+class FaceList:
+    """The host arrays of an rfd_face_list for n frames and cap faces: total [1], first [n + 1], frame / row / status [cap],
+    box [cap, 5], kps [cap, 5, 2], crops [cap, h, w, 3] or None, tensors [k] of [cap, 3, out_h, out_w].  The library writes
+    rows below `valid` = min(total, cap) only; whatever the arrays held beyond them stays (fill: the byte they start with)."""
+
+    def __init__(self, n, cap, cfgs, crop_size=(112, 112), want_crops=True, fill=0):
+        cap = max(int(cap), 1)
+        new = lambda shape, dt: np.frombuffer(bytes([fill]) * (int(np.prod(shape)) * np.dtype(dt).itemsize), dt).reshape(shape).copy()
+        self.cap = cap
+        self.total, self.first = new((1,), np.int32), new((n + 1,), np.int32)
+        self.frame, self.row, self.status = new((cap,), np.int32), new((cap,), np.int32), new((cap,), np.int32)
+        self.box, self.kps = new((cap, 5), np.float32), new((cap, 5, 2), np.float32)
+        self.crops = new((cap, crop_size[1], crop_size[0], 3), np.uint8) if want_crops else None
+        self.tensors = [new((cap, 3, max(c.out_h, 1), max(c.out_w, 1)), np.float32) for c in cfgs[:MAX_FACE_TENSORS]]
+
+    @property
+    def valid(self):
+        return min(int(self.total[0]), self.cap)
+
+    def struct(self):
+        s = rfd_face_list(self.total.ctypes.data, self.first.ctypes.data, self.frame.ctypes.data, self.row.ctypes.data,
+                          self.box.ctypes.data, self.kps.ctypes.data, self.status.ctypes.data,
+                          None if self.crops is None else self.crops.ctypes.data)
+        for j, t in enumerate(self.tensors):
+            s.tensors[j] = t.ctypes.data
+        return s
 
 
 def _face_tensor_args(cfgs, n):
@@ -1112,6 +1168,63 @@ class RetinaFaceDetection:
             out.tensors[j] = p
         _check(self._L.rfd_detect_faces_device(self._ctx, arr, n, C.addressof(sc), 1 if is_enroll else 0, C.addressof(c),
                                                C.addressof(tc), len(cfgs), C.byref(out), int(async_)))
+
+    # ---- every detected face of a frame: the packed face list (rfd.h) ----
+    def _face_list_call(self, frames, cfgs, cap, list_cfg, image_size, standard_landmarks, want_crops, out):
+        arr, keep = self._images(frames)
+        c = self._align_cfg(image_size, standard_landmarks)
+        lc = list_cfg if list_cfg is not None else face_list_config()
+        if out is None:
+            out = FaceList(len(frames), cap, cfgs, (max(c.out_w, 1), max(c.out_h, 1)), want_crops)
+        tc = (rfd_face_tensor_config * max(len(cfgs), 1))(*cfgs)
+        return arr, keep, c, lc, tc, out
+
+    def align_detections(self, frames, dets, cfgs=(), cap=1, list_cfg=None, image_size=None, standard_landmarks=None,
+                         want_crops=True, out=None):
+        """frames: list of HxWx3 u8 BGR; dets: list of (det [K,5], kps [K,5,2]) per frame, as call_batch returns them.
+        -> FaceList of up to cap faces (out: a caller-made FaceList to write into)"""
+        cfgs = list(cfgs)
+        arr, keep, c, lc, tc, out = self._face_list_call(frames, cfgs, cap, list_cfg, image_size, standard_landmarks, want_crops, out)
+        n = len(frames)
+        d, boxes, lmk, count, total = self._alloc_dets(n)
+        for i, (a, b) in enumerate(dets):
+            k = min(len(a), self.max_det)
+            boxes[i, :k] = a[:k]
+            lmk[i, :k] = np.asarray(b, np.float32).reshape(-1, 5, 2)[:k]
+            count[i] = k
+        st = out.struct()
+        _check(self._L.rfd_align_detections(self._ctx, arr, n, C.byref(d), C.addressof(lc), C.addressof(c), C.addressof(tc),
+                                            len(cfgs), int(cap), C.byref(st)))
+        return out
+
+    def detect_align_all(self, frames, cfgs=(), cap=1, list_cfg=None, image_size=None, standard_landmarks=None,
+                         want_crops=True, out=None):
+        """detect, list every face, align and tensorise: host frames in -> FaceList of up to cap faces"""
+        cfgs = list(cfgs)
+        arr, keep, c, lc, tc, out = self._face_list_call(frames, cfgs, cap, list_cfg, image_size, standard_landmarks, want_crops, out)
+        st = out.struct()
+        _check(self._L.rfd_detect_align_all_batch(self._ctx, arr, len(frames), C.addressof(lc), C.addressof(c), C.addressof(tc),
+                                                  len(cfgs), int(cap), C.byref(st)))
+        return out
+
+    def detect_all_faces_device(self, frame_ptrs, shapes, cfgs, cap, total_ptr, first_ptr, frame_ptr, row_ptr, box_ptr, kps_ptr,
+                                status_ptr, crops_ptr, tensor_ptrs, list_cfg=None, image_size=None, standard_landmarks=None,
+                                async_=False):
+        """Frames and every output already in device memory (raw device addresses; crops_ptr may be None); enqueued on the
+        context's stream, with no host synchronisation when async_ is set (then sync() before reading)."""
+        n = len(frame_ptrs)
+        arr = (rfd_image * n)()
+        for i, (p, (h, w)) in enumerate(zip(frame_ptrs, shapes)):
+            arr[i].data, arr[i].height, arr[i].width, arr[i].stride = p, h, w, w * 3
+        c = self._align_cfg(image_size, standard_landmarks)
+        lc = list_cfg if list_cfg is not None else face_list_config()
+        cfgs = list(cfgs)
+        tc = (rfd_face_tensor_config * max(len(cfgs), 1))(*cfgs)
+        out = rfd_face_list(total_ptr, first_ptr, frame_ptr, row_ptr, box_ptr, kps_ptr, status_ptr, crops_ptr)
+        for j, p in enumerate(tensor_ptrs):
+            out.tensors[j] = p
+        _check(self._L.rfd_detect_all_faces_device(self._ctx, arr, n, C.addressof(lc), C.addressof(c), C.addressof(tc), len(cfgs),
+                                                   int(cap), C.byref(out), int(async_)))
 
     def quality_decide(self, logits, threshold):
         """logits [n, classes] of the quality model -> (score [n] f32, klass [n] i32), face_quality.rs:159-168"""
