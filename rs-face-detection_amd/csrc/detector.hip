@@ -17,7 +17,7 @@
 
 #include "gallery_file.h"
 #include "host_resources.h"
-#include "jpeg_parse.h"
+#include "jpeg_host.h"
 #include "network.h"
 
 namespace rfd {
@@ -207,34 +207,7 @@ struct rfd_ctx {
     // liveness stage, all allocated by its first call: frame descriptors, the per-(face, model) geometry, the in / out staging of
     // the host forms, the running sums of a decide call of many models
     DevBuf live_imgs, live_geo, live_io, live_acc;
-    // JPEG decode (rfd.h, "JPEG decode"), all allocated by its first call.  jpeg_pin is the page-locked staging the decode threads
-    // write and jpeg_dev its device twin, both laid out as: JpegFrame [B] | block records u32 [B * jpeg_blocks_max] | coefficients
-    // i16 [B * jpeg_blocks_max * 64], B = max_batch_size.  jpeg_pin_done: the copies out of jpeg_pin that the last call enqueued.
-    int decode_threads = 4;
-    size_t jpeg_blocks_max = 0; // blocks of the largest frame (max_src_w x max_src_h) in its most expensive sampling
-    Pinned<char> jpeg_pin;
-    Event jpeg_pin_done;
-    DevBuf jpeg_dev, jpeg_planes, jpeg_out; // jpeg_out: the device frames of the host-output form
-    // Entropy decoding on the device (rfd_set_jpeg_entropy), all allocated by the first decode call in that mode.  jpeg_ent_pin and
-    // its device twin jpeg_ent_dev: JpegEntropyFrame [B] | status u32 [B] | interval tables u32 [2 * B * jpeg_intervals_max] |
-    // scan bytes [jpeg_scan_pool].  The copies out of jpeg_ent_pin are covered by jpeg_pin_done as well; jpeg_ent_done: the
-    // status words of the last entropy launch have arrived.
-    int jpeg_entropy = RFD_JPEG_ENTROPY_HOST;
-    size_t jpeg_intervals_max = 0, jpeg_scan_pool = 0; // MCUs of the largest frame at 8 x 8 per MCU; bytes of the scan pool
-    Pinned<char> jpeg_ent_pin;
-    DevBuf jpeg_ent_dev;
-    Event jpeg_ent_done;
-    std::vector<int32_t> jpeg_paths; // rfd_jpeg_last_paths
-    // EXIF orientation (rfd_set_jpeg_orientation).  Behind the coefficients, jpeg_pin and jpeg_dev hold the tables of the colour
-    // launches of a batch with an oriented frame (jpeg_tables_off, 16-byte aligned): JpegOrientedFrame [B] | JpegFrame [B], the
-    // second being the upright frames alone.  A batch without such a frame neither writes nor copies them.
-    int jpeg_orientation = RFD_JPEG_ORIENTATION_IGNORE;
-    size_t jpeg_tables_off = 0;
-    std::vector<int32_t> jpeg_orientations; // rfd_jpeg_last_orientations
-    // Reduced size (rfd_set_jpeg_scale).  Behind the orientation tables, jpeg_pin and jpeg_dev hold the tables of a scaled batch
-    // (jpeg_scaled_off, 16-byte aligned): JpegScaledFrame [B] | JpegOrientedFrame [B] upright | JpegOrientedFrame [B] oriented.
-    int jpeg_scale = 1;
-    size_t jpeg_scaled_off = 0;
+    JpegDecoder jpeg; // JPEG decode (rfd.h, "JPEG decode"): jpeg_host.h
     // pipelined host entry (rfd_submit_batch / rfd_collect_batch): two slots, H2D on its own stream
     struct PipeSlot {
         DevBuf frames, imgs, scale, ob, ol, oc, ot;
@@ -2737,7 +2710,7 @@ int rfd_gallery_load(rfd_ctx *c, const char *path, int capacity, rfd_gallery **o
     return RFD_OK;
 }
 
-// ---- JPEG decode (rfd.h, "JPEG decode"): csrc/jpeg_parse.h on host threads, then csrc/kernels_jpeg.hip ----
+// ---- JPEG decode (rfd.h, "JPEG decode"): the entries; the host side of a decode call is csrc/jpeg_host.hip ----
 int rfd_jpeg_info(const uint8_t *bytes, size_t len, struct rfd_jpeg_info *out)
 {
     char msg[256] = "";
@@ -2790,423 +2763,15 @@ int rfd_set_decode_threads(rfd_ctx *c, int threads)
 {
     RFD_CHECK_ARG(c, "ctx is null");
     if (threads < 1 || threads > 16) { set_error("invalid argument: %d decode threads (1..16)", threads); return RFD_ERR_INVALID_ARG; }
-    c->decode_threads = threads;
+    c->jpeg.decode_threads = threads;
     return RFD_OK;
-}
-
-// blocks of a w x h frame in the sampling that needs most: 4:4:4, 4:2:2 or 4:2:0, each padded to its own MCU
-static size_t jpeg_blocks_bound(int w, int h)
-{
-    const size_t a8 = (size_t)ceil_div(w, 8), b8 = (size_t)ceil_div(h, 8), a16 = (size_t)ceil_div(w, 16), b16 = (size_t)ceil_div(h, 16);
-    return std::max(3 * a8 * b8, std::max(4 * a16 * b8, 6 * a16 * b16));
-}
-
-// first decode call of a context: the page-locked staging, its device twin, the plane pool
-static int jpeg_stage_alloc(rfd_ctx *c)
-{
-    if (c->jpeg_pin) return RFD_OK;
-    RFD_CHECK_ARG(c->cfg.max_src_w >= 1 && c->cfg.max_src_h >= 1, "max_src_w / max_src_h < 1");
-    const size_t B = (size_t)c->cfg.max_batch_size, blocks = jpeg_blocks_bound(c->cfg.max_src_w, c->cfg.max_src_h);
-    if (blocks * 64 > kJpegMaxCoefs) {
-        set_error("max_src %d x %d exceeds the JPEG decoder's %u coefficient slots per frame", c->cfg.max_src_w, c->cfg.max_src_h, kJpegMaxCoefs);
-        return RFD_ERR_CAPACITY;
-    }
-    const size_t tables = (B * sizeof(JpegFrame) + B * blocks * (sizeof(uint32_t) + 64 * sizeof(int16_t)) + 15) & ~(size_t)15;
-    const size_t scaled = (tables + B * (sizeof(JpegOrientedFrame) + sizeof(JpegFrame)) + 15) & ~(size_t)15;
-    const size_t bytes = scaled + B * (sizeof(JpegScaledFrame) + 2 * sizeof(JpegOrientedFrame));
-    RFD_TRY(c->jpeg_pin_done.create());
-    RFD_TRY(c->jpeg_dev.reserve(bytes));
-    RFD_TRY(c->jpeg_planes.reserve(B * blocks * 64));
-    RFD_TRY(c->jpeg_pin.alloc(bytes));
-    c->jpeg_blocks_max = blocks;
-    c->jpeg_tables_off = tables;
-    c->jpeg_scaled_off = scaled;
-    return RFD_OK;
-}
-
-// ---- entropy decoding on the device (rfd_set_jpeg_entropy): csrc/jpeg_entropy.h, csrc/kernels_jpeg_entropy.hip ----
-constexpr size_t kJpegScanFloor = 64 * 1024, kJpegScanBytesPerBlock = 32;
-
-struct JpegEntLayout { size_t status, ivl, scan, bytes; }; // byte offsets in jpeg_ent_pin / jpeg_ent_dev
-static JpegEntLayout jpeg_ent_layout(const rfd_ctx *c)
-{
-    const size_t B = (size_t)c->cfg.max_batch_size;
-    JpegEntLayout l;
-    l.status = B * sizeof(JpegEntropyFrame);
-    l.ivl = l.status + B * sizeof(uint32_t);
-    l.scan = l.ivl + 2 * B * c->jpeg_intervals_max * sizeof(uint32_t);
-    l.bytes = l.scan + c->jpeg_scan_pool;
-    return l;
-}
-
-// first decode call in DEVICE mode (after jpeg_stage_alloc): the page-locked scan / interval staging and its device twin
-static int jpeg_entropy_stage_alloc(rfd_ctx *c)
-{
-    if (c->jpeg_ent_pin) return RFD_OK;
-    const size_t B = (size_t)c->cfg.max_batch_size;
-    c->jpeg_intervals_max = (size_t)ceil_div(c->cfg.max_src_w, 8) * (size_t)ceil_div(c->cfg.max_src_h, 8);
-    // per frame half a byte per coefficient slot of the largest frame, at least 64 KiB; positions in the pool are 32-bit
-    c->jpeg_scan_pool = std::min(B * std::max(kJpegScanFloor, kJpegScanBytesPerBlock * c->jpeg_blocks_max), (size_t)0xffff0000u);
-    const JpegEntLayout l = jpeg_ent_layout(c);
-    RFD_TRY(c->jpeg_ent_done.create());
-    RFD_TRY(c->jpeg_ent_dev.reserve(l.bytes));
-    RFD_TRY(c->jpeg_ent_pin.alloc(l.bytes));
-    return RFD_OK;
-}
-
-// which frames of a call go to the entropy kernel, and their slices of the two pools
-struct JpegEntropyPlan {
-    std::vector<char> staged;             // per frame: its intervals and scan bytes are in the staging
-    std::vector<uint32_t> scan0, ivl0, nint;
-    size_t scan_used = 0, ivl_used = 0;   // bytes; u32 words
-    explicit JpegEntropyPlan(int n) : staged((size_t)n, 0), scan0((size_t)n, 0), ivl0((size_t)n, 0), nint((size_t)n, 0) {}
-};
-
-// Serial: hands frame i its slices when its header allows the interval path and its scan fits what is left of the pool.
-static bool jpeg_entropy_place(rfd_ctx *c, JpegEntropyPlan &pl, int i, const JpegHeader &h, size_t len, char *msg, size_t msg_cap)
-{
-    size_t want = 0;
-    if (!jpeg_device_eligible(nullptr, len, h, nullptr, nullptr, 0, &want, msg, msg_cap)) return false; // cap 0: the header's part of the rule only
-    const size_t bytes = len - h.scan, B = (size_t)c->cfg.max_batch_size;
-    if (pl.scan_used + bytes > c->jpeg_scan_pool || pl.ivl_used + 2 * want > 2 * B * c->jpeg_intervals_max) {
-        snprintf(msg, msg_cap, "not eligible for device entropy decoding: %zu scan bytes in %zu intervals do not fit the staging", bytes, want);
-        return false;
-    }
-    pl.scan0[(size_t)i] = (uint32_t)pl.scan_used; pl.ivl0[(size_t)i] = (uint32_t)pl.ivl_used; pl.nint[(size_t)i] = (uint32_t)want;
-    pl.scan_used += (bytes + 15) & ~(size_t)15;
-    pl.ivl_used += 2 * want;
-    pl.staged[(size_t)i] = 1;
-    return true;
-}
-
-// Any thread, a placed frame: the pre-scan straight into the frame's interval table, the scan bytes into its slice of the pool.
-static bool jpeg_entropy_stage_frame(rfd_ctx *c, JpegEntropyPlan &pl, int i, const uint8_t *d, size_t len, const JpegHeader &h, char *msg, size_t msg_cap)
-{
-    const JpegEntLayout l = jpeg_ent_layout(c);
-    const size_t nint = pl.nint[(size_t)i];
-    uint32_t *iv = (uint32_t *)(c->jpeg_ent_pin.p + l.ivl) + pl.ivl0[(size_t)i];
-    size_t want = 0;
-    if (!jpeg_device_eligible(d, len, h, iv, iv + nint, nint, &want, msg, msg_cap)) { pl.staged[(size_t)i] = 0; return false; }
-    memcpy(c->jpeg_ent_pin.p + l.scan + pl.scan0[(size_t)i], d + h.scan, (size_t)iv[2 * nint - 1] - h.scan);
-    return true;
-}
-
-// Descriptors, the copies out of the staging, the kernel, the status words back (jpeg_ent_done behind them).  rec0[i]: frame i's
-// first record in the pools of jpeg_dev.
-static int jpeg_entropy_enqueue(rfd_ctx *c, const JpegEntropyPlan &pl, int n, const JpegHeader *hdr, const size_t *rec0)
-{
-    const JpegEntLayout l = jpeg_ent_layout(c);
-    const size_t B = (size_t)c->cfg.max_batch_size;
-    char *pin = c->jpeg_ent_pin.p, *dev = (char *)c->jpeg_ent_dev.p, *pools = (char *)c->jpeg_dev.p;
-    JpegEntropyFrame *ef = (JpegEntropyFrame *)pin;
-    JpegEntropyParams p;
-    memset(&p, 0, sizeof p);
-    for (int i = 0; i < n; ++i) {
-        if (!pl.staged[(size_t)i]) continue;
-        JpegEntropyFrame &f = ef[p.n++];
-        memset(&f, 0, sizeof f);
-        jpeg_scan_geom(hdr[i], f.geom, f.dc, f.ac);
-        const uint32_t *iv = (const uint32_t *)(pin + l.ivl) + pl.ivl0[(size_t)i];
-        f.rec0 = rec0[i];
-        f.scan0 = pl.scan0[(size_t)i];
-        f.file_scan = (uint32_t)hdr[i].scan;
-        f.scan_bytes = iv[2 * pl.nint[(size_t)i] - 1] - f.file_scan;
-        f.interval0 = pl.ivl0[(size_t)i];
-        f.intervals = (int)pl.nint[(size_t)i];
-        f.group0 = p.groups;
-        f.frame = i;
-        p.groups += ceil_div(f.intervals, kJpegEntropyGroup);
-    }
-    auto copies = [&]() -> int {
-        RFD_HIP(hipMemcpyAsync(dev, pin, (size_t)p.n * sizeof(JpegEntropyFrame), hipMemcpyHostToDevice, c->stream));
-        RFD_HIP(hipMemcpyAsync(dev + l.ivl, pin + l.ivl, pl.ivl_used * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        if (pl.scan_used) RFD_HIP(hipMemcpyAsync(dev + l.scan, pin + l.scan, pl.scan_used, hipMemcpyHostToDevice, c->stream));
-        RFD_HIP(hipMemsetAsync(dev + l.status, 0, (size_t)n * sizeof(uint32_t), c->stream));
-        return RFD_OK;
-    };
-    const int copied = copies();
-    const hipError_t recorded = hipEventRecord(c->jpeg_pin_done, c->stream); // the next call waits for these before it writes the staging
-    RFD_TRY(copied);
-    RFD_HIP(recorded);
-    p.frames = (const JpegEntropyFrame *)dev;
-    p.scan = (const uint8_t *)(dev + l.scan);
-    p.intervals = (const uint32_t *)(dev + l.ivl);
-    p.rec = (uint32_t *)(pools + B * sizeof(JpegFrame));
-    p.coef = (int16_t *)(pools + B * sizeof(JpegFrame) + B * c->jpeg_blocks_max * sizeof(uint32_t));
-    p.status = (uint32_t *)(dev + l.status);
-    RFD_TRY(launch_jpeg_entropy(p, c->stream));
-    RFD_HIP(hipMemcpyAsync(pin + l.status, dev + l.status, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipEventRecord(c->jpeg_ent_done, c->stream));
-    return RFD_OK;
-}
-
-// fn(i) for every i of items on min(threads, items) threads that never touch HIP; false: no thread could be started
-static bool jpeg_on_threads(int threads, const std::vector<int> &items, const std::function<void(int)> &fn)
-{
-    if (items.empty()) return true;
-    std::atomic<size_t> next{0};
-    auto work = [&]() {
-        for (size_t k; (k = next.fetch_add(1)) < items.size();) fn(items[k]);
-    };
-    std::vector<std::thread> pool;
-    const int T = std::min(threads, (int)items.size());
-    try {
-        for (int t = 0; t < T; ++t) pool.emplace_back(work);
-    } catch (...) {
-    }
-    for (std::thread &t : pool) t.join();
-    return !pool.empty();
-}
-
-// Both forms.  Everything that can refuse the call -- arguments, headers, entropy data -- is settled before the first copy or
-// kernel that writes an output frame is enqueued.  In DEVICE mode the entropy kernel, which writes the context's own pools only,
-// runs before that point, and the call waits for its status words.
-static int jpeg_decode_impl(rfd_ctx *c, const uint8_t *const *bytes, const size_t *len, int n, const rfd_image *out, bool out_on_device, int async)
-{
-    RFD_CHECK_ARG(c, "ctx is null");
-    RFD_CHECK_ARG(n >= 0, "n < 0");
-    if (n == 0) return RFD_OK;
-    RFD_CHECK_ARG(bytes && len && out, "null argument");
-    RFD_TRY(check_batch(c, n, "batch of", " files"));
-    std::unique_ptr<JpegHeader[]> hdr(new JpegHeader[(size_t)n]);
-    std::vector<int32_t> orient((size_t)n, 1); // what the call applies: the tag in APPLY mode
-    std::vector<int> ow((size_t)n), oh((size_t)n); // the size of the frame it writes
-    int n_oriented = 0;
-    const int scale = c->jpeg_scale; // 1: every step below is what it was before the mode existed
-    for (int i = 0; i < n; ++i) {
-        const int st = jpeg_parse_header(bytes[i], len[i], hdr[i]);
-        if (st != RFD_OK) { set_error("file %d: %s", i, hdr[i].msg); return st; }
-        const JpegHeader &h = hdr[i];
-        if (c->jpeg_orientation == RFD_JPEG_ORIENTATION_APPLY) orient[(size_t)i] = h.orientation;
-        jpeg_oriented_size(orient[(size_t)i], jpeg_scaled_dim(h.width, scale), jpeg_scaled_dim(h.height, scale), &ow[(size_t)i], &oh[(size_t)i]);
-        n_oriented += orient[(size_t)i] != 1;
-        if (h.width > c->cfg.max_src_w || h.height > c->cfg.max_src_h) {
-            set_error("file %d: %d x %d exceeds max_src %d x %d", i, h.width, h.height, c->cfg.max_src_w, c->cfg.max_src_h);
-            return RFD_ERR_CAPACITY;
-        }
-        if (!out[i].data) { set_error("invalid argument: output frame %d has no data pointer", i); return RFD_ERR_INVALID_ARG; }
-        if (out[i].width != ow[(size_t)i] || out[i].height != oh[(size_t)i]) {
-            if (scale != 1)
-                set_error("invalid argument: output frame %d is %d x %d, file %d is %d x %d at scale 1/%d in orientation %d (%d x %d stored)", i, out[i].width,
-                          out[i].height, i, ow[(size_t)i], oh[(size_t)i], scale, orient[(size_t)i], h.width, h.height);
-            else if (orient[(size_t)i] == 1) set_error("invalid argument: output frame %d is %d x %d, file %d is %d x %d", i, out[i].width, out[i].height, i, h.width, h.height);
-            else
-                set_error("invalid argument: output frame %d is %d x %d, file %d is %d x %d in orientation %d (%d x %d stored)", i, out[i].width, out[i].height, i,
-                          ow[(size_t)i], oh[(size_t)i], orient[(size_t)i], h.width, h.height);
-            return RFD_ERR_INVALID_ARG;
-        }
-        if (out[i].stride < (ptrdiff_t)ow[(size_t)i] * 3) { set_error("invalid argument: output frame %d has stride %td < 3 * width", i, out[i].stride); return RFD_ERR_INVALID_ARG; }
-    }
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    RFD_TRY(jpeg_stage_alloc(c));
-    const bool device_entropy = c->jpeg_entropy == RFD_JPEG_ENTROPY_DEVICE;
-    if (device_entropy) RFD_TRY(jpeg_entropy_stage_alloc(c));
-    const size_t B = (size_t)c->cfg.max_batch_size;
-    JpegFrame *fr = (JpegFrame *)c->jpeg_pin.p;
-    uint32_t *rec = (uint32_t *)(fr + B);
-    int16_t *coef = (int16_t *)(rec + B * c->jpeg_blocks_max);
-    RFD_HIP(hipEventSynchronize(c->jpeg_pin_done)); // the previous call's copies out of the staging have run
-    std::vector<size_t> rec0((size_t)n);
-    std::vector<uint32_t> used((size_t)n, 0);
-    std::vector<int> status((size_t)n, RFD_OK);
-    size_t blocks = 0, out_bytes = 0;
-    for (int i = 0; i < n; ++i) { rec0[(size_t)i] = blocks; blocks += (size_t)hdr[i].nblocks; out_bytes += (size_t)ow[(size_t)i] * 3 * oh[(size_t)i]; }
-    std::vector<int> idct_n((size_t)n * 3, 8); // per frame and component: the inverse-DCT size (jpeg_idct_sizes)
-    if (scale != 1)
-        for (int i = 0; i < n; ++i) jpeg_idct_sizes(hdr[i], scale, &idct_n[(size_t)i * 3]);
-    c->jpeg_paths.assign((size_t)n, 0);
-    c->jpeg_orientations = orient;
-    // one frame per task; the workers touch nothing but their frame's bytes, header and slices of the staging
-    auto decode_on_host = [&](int i) {
-        status[(size_t)i] = jpeg_decode_scan(bytes[i], len[i], hdr[i], rec + rec0[(size_t)i], coef + rec0[(size_t)i] * 64, &used[(size_t)i],
-                                             scale != 1 ? &idct_n[(size_t)i * 3] : nullptr);
-    };
-    JpegEntropyPlan plan(n);
-    std::vector<int> host_frames, placed;
-    bool launched = false;
-    if (device_entropy) {
-        char why[200];
-        for (int i = 0; i < n; ++i)
-            if ((uint64_t)hdr[i].nblocks * 64 <= kJpegMaxCoefs && jpeg_entropy_place(c, plan, i, hdr[i], len[i], why, sizeof why)) placed.push_back(i);
-        if (!jpeg_on_threads(c->decode_threads, placed, [&](int i) {
-                char m[200];
-                jpeg_entropy_stage_frame(c, plan, i, bytes[i], len[i], hdr[i], m, sizeof m);
-            })) {
-            set_error("cannot start a JPEG decode thread");
-            return RFD_ERR_STATE;
-        }
-        for (int i : placed) launched |= plan.staged[(size_t)i] != 0;
-        if (launched) RFD_TRY(jpeg_entropy_enqueue(c, plan, n, hdr.get(), rec0.data()));
-    }
-    for (int i = 0; i < n; ++i)
-        if (!plan.staged[(size_t)i]) host_frames.push_back(i);
-    bool threads_ok = jpeg_on_threads(c->decode_threads, host_frames, decode_on_host); // while the entropy kernel runs
-    if (launched) {
-        RFD_HIP(hipEventSynchronize(c->jpeg_ent_done));
-        const uint32_t *refused = (const uint32_t *)(c->jpeg_ent_pin.p + jpeg_ent_layout(c).status);
-        std::vector<int> again;
-        for (int i = 0; i < n; ++i)
-            if (plan.staged[(size_t)i]) {
-                c->jpeg_paths[(size_t)i] = refused[i] ? 2 : 1;
-                if (refused[i]) { plan.staged[(size_t)i] = 0; again.push_back(i); }
-            }
-        threads_ok = jpeg_on_threads(c->decode_threads, again, decode_on_host) && threads_ok; // the host decoder judges what the device refused
-    }
-    if (!threads_ok) { set_error("cannot start a JPEG decode thread"); return RFD_ERR_STATE; }
-    for (int i = 0; i < n; ++i)
-        if (status[(size_t)i] != RFD_OK) { set_error("file %d: %s", i, hdr[i].msg); return status[(size_t)i]; }
-    if (!out_on_device) RFD_TRY(c->jpeg_out.reserve(out_bytes));
-    JpegParams p, upright;
-    JpegOrientedParams oriented;
-    memset(&p, 0, sizeof p);
-    memset(&upright, 0, sizeof upright);
-    memset(&oriented, 0, sizeof oriented);
-    // the tables of the colour launches where a frame is oriented: each launch lists only the frames that have a workgroup in it
-    JpegOrientedFrame *ofr = (JpegOrientedFrame *)(c->jpeg_pin.p + c->jpeg_tables_off);
-    JpegFrame *ufr = (JpegFrame *)(ofr + B);
-    // the tables of a scaled batch: the per-frame additions, then the lists of its two colour launches
-    JpegScaledParams sp;
-    memset(&sp, 0, sizeof sp);
-    JpegScaledFrame *sfr = (JpegScaledFrame *)(c->jpeg_pin.p + c->jpeg_scaled_off);
-    JpegOrientedFrame *sup = (JpegOrientedFrame *)(sfr + B), *sor = sup + B;
-    size_t out_at = 0;
-    for (int i = 0; i < n; ++i) {
-        const JpegHeader &h = hdr[i];
-        JpegFrame &f = fr[i];
-        memset(&f, 0, sizeof f);
-        if (out_on_device) {
-            f.out = const_cast<uint8_t *>(out[i].data); // the one entry point that writes a frame (rfd.h)
-            f.stride = (long long)out[i].stride;
-        } else {
-            f.out = (uint8_t *)c->jpeg_out.p + out_at;
-            f.stride = (long long)ow[(size_t)i] * 3;
-            out_at += (size_t)ow[(size_t)i] * 3 * oh[(size_t)i];
-        }
-        f.rec0 = rec0[(size_t)i]; f.coef0 = rec0[(size_t)i] * 64; f.plane0 = rec0[(size_t)i] * 64;
-        f.width = h.width; f.height = h.height;
-        f.ncomp = h.ncomp; f.hmax = h.hmax; f.vmax = h.vmax;
-        f.nblocks = h.nblocks;
-        f.group0 = p.groups; f.tile0 = p.tiles;
-        p.groups += ceil_div(h.nblocks, kJpegGroupBlocks);
-        p.tiles += (int)(((size_t)ceil_div(h.width, 4) * h.height + 255) / 256);
-        for (int k = 0; k < h.ncomp; ++k) {
-            f.bw[k] = h.comp[k].bw; f.bh[k] = h.comp[k].bh; f.blk0[k] = h.comp[k].blk0;
-            for (int z = 0; z < 64; ++z) f.quant[k][kJpegNatural[z]] = h.quant[h.comp[k].tq][z];
-        }
-        if (scale != 1) {
-            JpegScaledFrame &sf = sfr[i];
-            memset(&sf, 0, sizeof sf);
-            size_t at = f.plane0; // n^2 <= 64 bytes per block: the scaled planes fit the frame's share of the pool
-            for (int k = 0; k < h.ncomp; ++k) {
-                const int nk = idct_n[(size_t)i * 3 + (size_t)k], blk = h.comp[k].bw * h.comp[k].bh;
-                sf.n[k] = nk;
-                sf.plane[k] = at;
-                sf.pitch[k] = h.comp[k].bw * nk;
-                sf.cgroup[k] = sp.groups;
-                sp.groups += ceil_div(blk, 256 / nk);
-                at += (size_t)blk * nk * nk;
-            }
-            sf.width = jpeg_scaled_dim(h.width, scale); sf.height = jpeg_scaled_dim(h.height, scale);
-            sf.hup = h.ncomp == 3 ? h.hmax * (8 / scale) / (h.comp[1].h * sf.n[1]) : 1; // 2 for 4:2:2; the vertical factor is always 1
-            sf.replicate = scale == 8;
-            JpegOrientedFrame &e = orient[(size_t)i] == 1 ? sup[sp.n_upright++] : sor[sp.n_oriented++];
-            e.frame = i;
-            e.orientation = orient[(size_t)i];
-            if (orient[(size_t)i] == 1) {
-                e.tile0 = sp.tiles_upright;
-                e.tiles_x = 0;
-                sp.tiles_upright += (int)(((size_t)ceil_div(sf.width, 4) * sf.height + 255) / 256);
-            } else {
-                e.tile0 = sp.tiles_oriented;
-                e.tiles_x = jpeg_oriented_tiles_x(ow[(size_t)i]);
-                sp.tiles_oriented += e.tiles_x * jpeg_oriented_tiles_x(oh[(size_t)i]);
-            }
-            continue;
-        }
-        if (!n_oriented) continue;
-        if (orient[(size_t)i] == 1) {
-            JpegFrame &u = ufr[upright.n++];
-            u = f;
-            u.tile0 = upright.tiles;
-            upright.tiles += p.tiles - f.tile0;
-        } else {
-            JpegOrientedFrame &of = ofr[oriented.n++];
-            of.frame = i;
-            of.orientation = orient[(size_t)i];
-            of.tile0 = oriented.tiles;
-            of.tiles_x = jpeg_oriented_tiles_x(ow[(size_t)i]);
-            oriented.tiles += of.tiles_x * jpeg_oriented_tiles_x(oh[(size_t)i]);
-        }
-    }
-    char *dev = (char *)c->jpeg_dev.p;
-    const size_t rec_off = B * sizeof(JpegFrame), coef_off = rec_off + B * c->jpeg_blocks_max * sizeof(uint32_t);
-    auto copies = [&]() -> int {
-        if (!launched) RFD_HIP(hipMemcpyAsync(dev, fr, rec_off + blocks * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        else { // the records the entropy kernel wrote stay: the descriptors, then the records of the host-decoded frames one by one
-            RFD_HIP(hipMemcpyAsync(dev, fr, (size_t)n * sizeof(JpegFrame), hipMemcpyHostToDevice, c->stream));
-            for (int i = 0; i < n; ++i)
-                if (!plan.staged[(size_t)i])
-                    RFD_HIP(hipMemcpyAsync(dev + rec_off + rec0[(size_t)i] * sizeof(uint32_t), rec + rec0[(size_t)i], (size_t)hdr[i].nblocks * sizeof(uint32_t),
-                                           hipMemcpyHostToDevice, c->stream));
-        }
-        for (int i = 0; i < n; ++i)
-            if (used[(size_t)i])
-                RFD_HIP(hipMemcpyAsync(dev + coef_off + rec0[(size_t)i] * 64 * sizeof(int16_t), coef + rec0[(size_t)i] * 64, (size_t)used[(size_t)i] * sizeof(int16_t),
-                                       hipMemcpyHostToDevice, c->stream));
-        if (scale != 1)
-            RFD_HIP(hipMemcpyAsync(dev + c->jpeg_scaled_off, sfr, B * (sizeof(JpegScaledFrame) + sizeof(JpegOrientedFrame)) + (size_t)sp.n_oriented * sizeof(JpegOrientedFrame),
-                                   hipMemcpyHostToDevice, c->stream));
-        else if (n_oriented)
-            RFD_HIP(hipMemcpyAsync(dev + c->jpeg_tables_off, ofr, B * sizeof(JpegOrientedFrame) + (size_t)upright.n * sizeof(JpegFrame), hipMemcpyHostToDevice,
-                                   c->stream));
-        return RFD_OK;
-    };
-    const int copied = copies();
-    // also where a copy failed after others were enqueued: the next call must wait for those before it writes the staging
-    const hipError_t recorded = hipEventRecord(c->jpeg_pin_done, c->stream);
-    RFD_TRY(copied);
-    RFD_HIP(recorded);
-    p.frames = (const JpegFrame *)dev;
-    p.n = n;
-    p.rec = (const uint32_t *)(dev + rec_off);
-    p.coef = (const int16_t *)(dev + coef_off);
-    p.planes = (uint8_t *)c->jpeg_planes.p;
-    if (scale != 1) {
-        sp.frames = p.frames;
-        sp.scaled = (const JpegScaledFrame *)(dev + c->jpeg_scaled_off);
-        sp.upright = (const JpegOrientedFrame *)(sp.scaled + B);
-        sp.oriented = sp.upright + B;
-        sp.n = n;
-        sp.rec = p.rec; sp.coef = p.coef; sp.planes = p.planes;
-        RFD_TRY(launch_jpeg_decode_scaled(sp, c->stream));
-    } else if (!n_oriented) RFD_TRY(launch_jpeg_decode(p, c->stream));
-    else {
-        upright.frames = (const JpegFrame *)(dev + c->jpeg_tables_off + B * sizeof(JpegOrientedFrame));
-        upright.rec = p.rec; upright.coef = p.coef; upright.planes = p.planes;
-        oriented.frames = p.frames;
-        oriented.oriented = (const JpegOrientedFrame *)(dev + c->jpeg_tables_off);
-        oriented.planes = p.planes;
-        RFD_TRY(launch_jpeg_decode_oriented(p, upright, oriented, c->stream));
-    }
-    if (!out_on_device) {
-        out_at = 0;
-        for (int i = 0; i < n; ++i) {
-            const size_t row = (size_t)ow[(size_t)i] * 3;
-            RFD_HIP(hipMemcpy2DAsync(const_cast<uint8_t *>(out[i].data), (size_t)out[i].stride, (const uint8_t *)c->jpeg_out.p + out_at, row, row, (size_t)oh[(size_t)i],
-                                     hipMemcpyDeviceToHost, c->stream));
-            out_at += row * oh[(size_t)i];
-        }
-    }
-    if (async && out_on_device) return RFD_OK;
-    RFD_HIP(hipStreamSynchronize(c->stream));
-    return check_nms_flag(c);
 }
 
 int rfd_set_jpeg_entropy(rfd_ctx *c, int mode)
 {
     RFD_CHECK_ARG(c, "ctx is null");
     if (mode != RFD_JPEG_ENTROPY_HOST && mode != RFD_JPEG_ENTROPY_DEVICE) { set_error("invalid argument: JPEG entropy mode %d (0: host, 1: device)", mode); return RFD_ERR_INVALID_ARG; }
-    c->jpeg_entropy = mode;
+    c->jpeg.entropy = mode;
     return RFD_OK;
 }
 
@@ -3214,7 +2779,7 @@ int rfd_set_jpeg_scale(rfd_ctx *c, int denom)
 {
     RFD_CHECK_ARG(c, "ctx is null");
     if (!jpeg_scale_valid(denom)) { set_error("invalid argument: JPEG scale denominator %d (1, 2, 4 or 8)", denom); return RFD_ERR_INVALID_ARG; }
-    c->jpeg_scale = denom;
+    c->jpeg.scale = denom;
     return RFD_OK;
 }
 
@@ -3222,7 +2787,7 @@ int rfd_set_jpeg_orientation(rfd_ctx *c, int mode)
 {
     RFD_CHECK_ARG(c, "ctx is null");
     if (mode != RFD_JPEG_ORIENTATION_IGNORE && mode != RFD_JPEG_ORIENTATION_APPLY) { set_error("invalid argument: JPEG orientation mode %d (0: ignore, 1: apply)", mode); return RFD_ERR_INVALID_ARG; }
-    c->jpeg_orientation = mode;
+    c->jpeg.orientation = mode;
     return RFD_OK;
 }
 
@@ -3230,10 +2795,10 @@ int rfd_jpeg_last_orientations(rfd_ctx *c, int32_t *orientation, int cap, int *n
 {
     RFD_CHECK_ARG(c, "ctx is null");
     RFD_CHECK_ARG(cap >= 0 && (orientation || cap == 0), "orientation is null");
-    const int have = (int)c->jpeg_orientations.size();
+    const int have = (int)c->jpeg.orientations.size();
     if (n) *n = have;
     if (have > cap) { set_error("the last decode call had %d frames, the output holds %d", have, cap); return RFD_ERR_CAPACITY; }
-    for (int i = 0; i < have; ++i) orientation[i] = c->jpeg_orientations[(size_t)i];
+    for (int i = 0; i < have; ++i) orientation[i] = c->jpeg.orientations[(size_t)i];
     return RFD_OK;
 }
 
@@ -3241,10 +2806,10 @@ int rfd_jpeg_last_paths(rfd_ctx *c, int32_t *path, int cap, int *n)
 {
     RFD_CHECK_ARG(c, "ctx is null");
     RFD_CHECK_ARG(cap >= 0 && (path || cap == 0), "path is null");
-    const int have = (int)c->jpeg_paths.size();
+    const int have = (int)c->jpeg.paths.size();
     if (n) *n = have;
     if (have > cap) { set_error("the last decode call had %d frames, the output holds %d", have, cap); return RFD_ERR_CAPACITY; }
-    for (int i = 0; i < have; ++i) path[i] = c->jpeg_paths[(size_t)i];
+    for (int i = 0; i < have; ++i) path[i] = c->jpeg.paths[(size_t)i];
     return RFD_OK;
 }
 
@@ -3268,52 +2833,30 @@ int rfd_debug_jpeg_coefficients_device(rfd_ctx *c, const uint8_t *bytes, size_t 
 {
     RFD_CHECK_ARG(c, "ctx is null");
     RFD_CHECK_ARG(out || cap_blocks == 0, "out is null");
-    std::unique_ptr<JpegHeader> h(new JpegHeader);
-    const int st = jpeg_parse_header(bytes, len, *h);
-    if (st != RFD_OK) { set_error("%s", h->msg); return st; }
-    if (blocks) *blocks = (size_t)h->nblocks;
-    if ((uint64_t)h->nblocks * 64 > kJpegMaxCoefs) { set_error("a JPEG frame of %d blocks exceeds the decoder's %u coefficient slots", h->nblocks, kJpegMaxCoefs); return RFD_ERR_CAPACITY; }
-    if ((size_t)h->nblocks > cap_blocks) { set_error("the file has %d blocks, the output holds %zu", h->nblocks, cap_blocks); return RFD_ERR_CAPACITY; }
-    if (h->width > c->cfg.max_src_w || h->height > c->cfg.max_src_h) {
-        set_error("%d x %d exceeds max_src %d x %d", h->width, h->height, c->cfg.max_src_w, c->cfg.max_src_h);
-        return RFD_ERR_CAPACITY;
-    }
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    RFD_TRY(jpeg_stage_alloc(c));
-    RFD_TRY(jpeg_entropy_stage_alloc(c));
-    RFD_HIP(hipEventSynchronize(c->jpeg_pin_done));
-    JpegEntropyPlan plan(1);
-    char msg[200] = "";
-    if (!jpeg_entropy_place(c, plan, 0, *h, len, msg, sizeof msg) || !jpeg_entropy_stage_frame(c, plan, 0, bytes, len, *h, msg, sizeof msg)) {
-        set_error("%s", msg);
-        return RFD_ERR_UNSUPPORTED;
-    }
-    const size_t rec0 = 0, B = (size_t)c->cfg.max_batch_size, nb = (size_t)h->nblocks;
-    RFD_TRY(jpeg_entropy_enqueue(c, plan, 1, h.get(), &rec0));
-    RFD_HIP(hipEventSynchronize(c->jpeg_ent_done));
-    if (*(const uint32_t *)(c->jpeg_ent_pin.p + jpeg_ent_layout(c).status)) {
-        set_error("the device entropy decoder refused the file: an interval of the scan at byte %zu does not decode to exactly its bytes", h->scan);
-        return RFD_ERR_UNSUPPORTED;
-    }
-    std::vector<uint32_t> rec(nb);
-    std::vector<int16_t> coef(nb * 64);
-    const char *pools = (const char *)c->jpeg_dev.p;
-    RFD_HIP(hipMemcpyAsync(rec.data(), pools + B * sizeof(JpegFrame), nb * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipMemcpyAsync(coef.data(), pools + B * sizeof(JpegFrame) + B * c->jpeg_blocks_max * sizeof(uint32_t), nb * 64 * sizeof(int16_t), hipMemcpyDeviceToHost,
-                           c->stream));
-    RFD_HIP(hipStreamSynchronize(c->stream));
-    jpeg_dequantise_natural(*h, rec.data(), coef.data(), out);
-    return RFD_OK;
+    return c->jpeg.debug_coefficients(c->stream, c->cfg, bytes, len, out, cap_blocks, blocks);
+}
+
+// both forms of the decode: the argument checks that need the context, JpegDecoder::decode, and the fault word where it synchronised
+static int jpeg_decode_entry(rfd_ctx *c, const uint8_t *const *bytes, const size_t *len, int n, const rfd_image *out, bool out_on_device, int async)
+{
+    RFD_CHECK_ARG(c, "ctx is null");
+    RFD_CHECK_ARG(n >= 0, "n < 0");
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(bytes && len && out, "null argument");
+    RFD_TRY(check_batch(c, n, "batch of", " files"));
+    RFD_TRY(c->jpeg.decode(c->stream, c->cfg, bytes, len, n, out, out_on_device, async != 0));
+    if (async && out_on_device) return RFD_OK;
+    return check_nms_flag(c);
 }
 
 int rfd_decode_jpeg_batch_device(rfd_ctx *c, const uint8_t *const *bytes, const size_t *len, int n, const rfd_image *out, int async)
 {
-    return jpeg_decode_impl(c, bytes, len, n, out, true, async);
+    return jpeg_decode_entry(c, bytes, len, n, out, true, async);
 }
 
 int rfd_decode_jpeg_batch(rfd_ctx *c, const uint8_t *const *bytes, const size_t *len, int n, const rfd_image *out)
 {
-    return jpeg_decode_impl(c, bytes, len, n, out, false, 0);
+    return jpeg_decode_entry(c, bytes, len, n, out, false, 0);
 }
 
 } // extern "C"

@@ -1,6 +1,6 @@
-// host_resources.h -- what the host layer of detector.hip owns, by type: device buffer, page-locked block, event, stream, and the
-// ring of page-locked slots that per-call descriptors travel through.  Host only.  A holder frees in its destructor and cannot
-// be copied; creating what is already held is a no-op, so a "first call" may simply ask again.
+// host_resources.h -- what the host layer (detector.hip, jpeg_host.h) owns, by type: device buffer, page-locked block, event,
+// stream, and the ring of page-locked slots that per-call descriptors travel through.  Host only.  A holder frees in its
+// destructor and cannot be copied; creating what is already held is a no-op, so a "first call" may simply ask again.
 #pragma once
 #include "rfd_common.h"
 

@@ -1,7 +1,7 @@
 // jpeg_parse.h -- the serial half of the baseline JPEG decoder (include/rfd.h, "JPEG decode"): marker parsing, all of the
 // validation, and the Huffman decoder that turns a file into quantised coefficients.  Plain host C++ with no HIP in it:
-// detector.hip includes it for rfd_jpeg_info / rfd_decode_jpeg_batch* / rfd_debug_jpeg_coefficients, and
-// tests/cpp/jpeg_parse_check.cpp builds it with the host compiler alone.  The parser and the scan decoder allocate nothing,
+// detector.hip includes it for rfd_jpeg_info / rfd_debug_jpeg_coefficients, jpeg_plan.h and jpeg_host.hip for
+// rfd_decode_jpeg_batch*, and tests/cpp/jpeg_parse_check.cpp builds it with the host compiler alone.  The parser and the scan decoder allocate nothing,
 // take no lock and touch no shared state, so one frame per worker thread decodes without any synchronisation.
 //
 // Supported: SOF0 / SOF1 with 8-bit samples, Huffman coding, ONE interleaved scan of one component (grey) or of three with

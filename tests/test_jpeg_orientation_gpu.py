@@ -23,14 +23,14 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FILL = 0xA5
 GUARD = 16                         # sentinel bytes in front of, between and behind the frames of an arena
-T = 64                             # the oriented kernel's tile side (kJpegOrientTile, csrc/kernels.h)
+T = 64                             # the oriented kernel's tile side (kJpegOrientTile, csrc/jpeg_desc.h)
 WIDTHS, HEIGHTS = [1, 2, 3, 4, 5, 8, 9, 17], [1, 2, 3, 8, 9, 16, 17]
 TILE_EDGES = [(T - 1, 1), (1, T + 1), (T, T), (T + 1, T - 1), (2 * T + 3, T + 2)]   # (width, height)
 ODD = (37, 23)                     # the output-contract test's size: partial quads in both directions, odd MCU edges
 
 
 def test_the_tile_side_is_the_kernels():
-    txt = open(os.path.join(ROOT, "rs-face-detection_amd", "csrc", "kernels.h")).read()
+    txt = open(os.path.join(ROOT, "rs-face-detection_amd", "csrc", "jpeg_desc.h")).read()
     assert int(re.search(r"kJpegOrientTile = (\d+);", txt).group(1)) == T
 
 

@@ -249,3 +249,28 @@ def test_the_scaled_host_decoder_alone_under_address_and_ub_sanitizers(tmp_path)
     files = [os.path.join(GOLDEN, n + ".jpg") for n in ("37x53_420", "37x53_420_rst2", "37x53_GRAY", "37x53_422")]
     run = subprocess.run([exe] + files, capture_output=True, text=True)
     assert run.returncode == 0 and " 0 failures" in run.stdout, run.stdout + run.stderr
+
+
+def test_the_planning_of_a_decode_call_alone_under_address_and_ub_sanitizers(tmp_path):
+    """tests/cpp/jpeg_plan_check.cpp: the layout of the staging, the per-file argument check and the descriptor tables of the
+    launches (csrc/jpeg_plan.h) on files of 1 x 1 to 130 x 70 in every sampling and with the orientation tags 1, 3, 6 and 8,
+    planned alone, in pairs and all together, in a program of its own whose every out-of-bounds access or undefined operation
+    aborts it.  Built as the program above; a plain build where the sanitizer runtimes cannot be linked."""
+    exe = str(tmp_path / "jpeg_plan_check")
+    src = os.path.join(ROOT, "tests", "cpp", "jpeg_plan_check.cpp")
+    base = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", src, "-o", exe]
+    san = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"], capture_output=True, text=True)
+    if san.returncode != 0:
+        plain = subprocess.run(base, capture_output=True, text=True)
+        assert plain.returncode == 0, "the build failed:\n" + san.stderr + plain.stderr
+    rng = np.random.default_rng(7)
+    files = []
+    for w, h in ((1, 1), (8, 8), (9, 17), (64, 64), (65, 63), (130, 70)):
+        for sampling in (GRAY, S444, S422, S420):
+            plain = jpeg_scaled_cases.sparse(rng, "plan_%dx%d" % (w, h), w, h, sampling).data
+            for o in (1, 3, 6, 8):
+                files.append(str(tmp_path / ("%dx%d_%d_%d.jpg" % (w, h, sampling, o))))
+                with open(files[-1], "wb") as f:
+                    f.write(tagged(plain, app1(value=o)))
+    run = subprocess.run([exe] + files, capture_output=True, text=True)
+    assert run.returncode == 0 and "96 files" in run.stdout and " 0 failures" in run.stdout, run.stdout[-3000:] + run.stderr[-3000:]
