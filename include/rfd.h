@@ -475,7 +475,8 @@ RFD_API int rfd_liveness_decide_device(rfd_ctx *ctx, const float *const *logits,
  *      rfd_normalize_embeddings_device -> rfd_gallery_search_device runs back to back and only n * k pairs cross PCIe.
  *      A gallery belongs to ONE context (its device, its stream; same thread rule) and is destroyed BEFORE it.  It holds up to
  *      `capacity` rows of `dim` values, both fixed at creation, so no device pointer moves under enqueued work.  A row's index is
- *      its insertion order; the caller keeps the table from rows to identities.  rfd_gallery_clear empties the gallery; single
+ *      its insertion order; the caller keeps the table from rows to identities and may hand it to the gallery ("identities" below), which then
+ *      searches the k best identities instead of the k best rows.  rfd_gallery_clear empties the gallery; single
  *      rows leave and change through rfd_gallery_remove / _replace, and a gallery outlives its process through
  *      rfd_gallery_save / _load (both below).
  *      Storage: every added f32 value is stored as bf16, rounded to nearest-even.  Rows are expected to be unit vectors (the
@@ -544,6 +545,48 @@ RFD_API int rfd_gallery_live(const rfd_gallery *g, int *live_rows);
 /* the removed rows in ascending order: at most cap of them into out (may be NULL when cap is 0); *count = how many there are,
  * also when that exceeds cap */
 RFD_API int rfd_gallery_removed(const rfd_gallery *g, int32_t *out, int cap, int *count);
+/* ---- identities.  A gallery holds several enrolments of a person (a passport photo, a selfie, a corrected enrolment), and the
+ *      decision a gallery is for compares the best PERSON with the runner-up person; the k best rows of a well-enrolled person
+ *      are k rows of that one person.  So every row carries an int32_t identity, and rfd_gallery_search_identities returns the
+ *      k best identities.  RFD_GALLERY_NO_IDENTITY (-1) means unlabelled: the row is an identity of its own.  It is the value
+ *      of every row after add, add_device, load and clear.  Valid identities are >= 0.
+ *      Setting: rfd_gallery_set_identities gives rows[i] the identity ids[i] (>= 0, or RFD_GALLERY_NO_IDENTITY to unlabel it).
+ *      It is enqueued on the context's stream in call order with no synchronisation (the lists travel through the gallery's
+ *      page-locked memory, as remove's do), so add_device -> set_identities -> search_identities_device(async) -> rfd_sync is
+ *      one sequence without a host wait.  A row outside [0, rows), a removed row, a row listed twice or an identity < -1
+ *      returns RFD_ERR_INVALID_ARG, rfd_last_error() names the offender and nothing is changed; n = 0 is a no-op.
+ *      Reading: _get_identities and _identities are answered from a host copy, as _live and _removed are, without a device wait.
+ *      With the other calls: remove resets the row's identity to -1, in HBM too and in stream order (nothing of an erased
+ *      enrolment stays); replace / replace_device leave it alone (they correct an enrolment; a reused hole is unlabelled, because
+ *      its remove unlabelled it); clear resets all.  save / load and the "RFDG" file are unchanged: identities are NOT in the
+ *      file.  The caller owns the table from rows to identities anyway and re-applies it with one set_identities after load.
+ *      Memory: the identity array in HBM (capacity x 4 bytes) is allocated by the first set_identities.  Until then, and for
+ *      rfd_gallery_search / _search_device always, every call launches exactly the kernels it launched before, with the same
+ *      arguments.
+ *      Search: for each query, every identity's key is its best live row under the total order (score descending, row
+ *      ascending); unlabelled rows each form their own identity.  The result is the k best identity keys under that same
+ *      order: the score, the row that achieved it and the identity (-1 for an unlabelled row).  Scores keep their bits, and the
+ *      result does not depend on n, the query's place or how rows are spread over waves and workgroups.  Entries with
+ *      !(score >= min_score) are replaced by the empty entry (-inf, -1, -1); they form a suffix.  min_score = -INFINITY disables
+ *      the threshold; a NaN min_score is RFD_ERR_INVALID_ARG.  Fewer than k identities leave the tail empty.  Removed rows never
+ *      count, NaN and -inf scores are never selected.  On a gallery that never had an identity set the call is the plain search
+ *      plus ids = -1.  k, n, alignment and the host / device forms follow rfd_gallery_search / _search_device.
+ *      Cost: the scan reads the identities of a block of 16 rows (64 bytes) only if a key of that block passes a list's
+ *      filter, so its HBM traffic stays the gallery's bytes.  What grows is the selection: a key that beats the k-th best
+ *      identity costs an insertion even where its identity is already listed with a better key, so few identities with many
+ *      rows each, arriving together, are the expensive case (README, "Gallery search"). ---- */
+#define RFD_GALLERY_NO_IDENTITY (-1)
+RFD_API int rfd_gallery_set_identities(rfd_gallery *g, const int32_t *rows /* host [n], distinct */, const int32_t *ids /* host [n] */, int n);
+/* out: host [n], the identities of rows [row0, row0 + n) (removed rows read -1) */
+RFD_API int rfd_gallery_get_identities(const rfd_gallery *g, int row0, int n, int32_t *out);
+/* the number of live rows with an identity >= 0 */
+RFD_API int rfd_gallery_identities(const rfd_gallery *g, int *labelled_rows);
+/* queries: host [n][dim], any n, in passes of 32; scores [n][k] f32, rows [n][k] i32, ids [n][k] i32, host */
+RFD_API int rfd_gallery_search_identities(rfd_gallery *g, const float *queries, int n, int k, float min_score, float *scores, int32_t *rows,
+                                          int32_t *ids);
+/* The same with DEVICE pointers (queries 16-byte aligned); async as in rfd_gallery_search_device. */
+RFD_API int rfd_gallery_search_identities_device(rfd_gallery *g, const float *queries, int n, int k, float min_score, float *scores, int32_t *rows,
+                                                 int32_t *ids, int async);
 
 /* ---- gallery file "RFDG", version 1, little-endian, in logical row order (not the private storage layout):
  *          bytes 0..19  "RFDG", u32 version = 1, u32 dim, u32 rows, u32 reserved = 0

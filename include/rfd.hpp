@@ -18,6 +18,7 @@
 
 #include <array>
 #include <cstdint>
+#include <limits>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -426,6 +427,41 @@ class Gallery {
         m.scores.resize((std::size_t)m.n * (std::size_t)(k > 0 ? k : 0));
         m.rows.resize(m.scores.size());
         check(rfd_gallery_search(g_, queries.data(), m.n, k, m.scores.data(), m.rows.data()));
+        return m;
+    }
+    // identities (rfd.h, "identities"): rows[i] gets ids[i] (>= 0, or RFD_GALLERY_NO_IDENTITY); enqueued, no synchronisation
+    struct IdentityMatches : Matches {
+        std::vector<int32_t> ids;  // [n][k], the identity of each entry; -1 for an unlabelled row and in the empty tail
+    };
+    void set_identities(const std::vector<int32_t> &rows, const std::vector<int32_t> &ids)
+    {
+        if (ids.size() != rows.size()) throw Error(RFD_ERR_INVALID_ARG, "set_identities: one identity per row");
+        check(rfd_gallery_set_identities(g_, rows.data(), ids.data(), (int)rows.size()));
+    }
+    // the identities of rows [row0, row0 + n)
+    std::vector<int32_t> identities(int row0, int n) const
+    {
+        std::vector<int32_t> out((std::size_t)(n > 0 ? n : 0));
+        check(rfd_gallery_get_identities(g_, row0, n, out.data()));
+        return out;
+    }
+    // the number of live rows that carry an identity >= 0
+    int labelled() const
+    {
+        int n = 0;
+        check(rfd_gallery_identities(g_, &n));
+        return n;
+    }
+    // queries [n][dim] -> the k best identities of each, every identity under its best row; entries below min_score are empty
+    IdentityMatches search_identities(const std::vector<float> &queries, int k, float min_score = -std::numeric_limits<float>::infinity())
+    {
+        IdentityMatches m;
+        m.n = (int)(queries.size() / (std::size_t)dim_);
+        m.k = k;
+        m.scores.resize((std::size_t)m.n * (std::size_t)(k > 0 ? k : 0));
+        m.rows.resize(m.scores.size());
+        m.ids.resize(m.scores.size());
+        check(rfd_gallery_search_identities(g_, queries.data(), m.n, k, min_score, m.scores.data(), m.rows.data(), m.ids.data()));
         return m;
     }
 

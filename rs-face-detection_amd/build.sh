@@ -22,3 +22,6 @@ echo "built $HERE/librfd_hip.so"
 # compiled-language user of the C ABI through include/rfd.hpp (tests/test_cpp_facade_*.py)
 g++ -std=c++17 -O2 -Wall -I"$HERE/../include" "$HERE/../tests/cpp/facade_demo.cpp" -o "$OBJ/facade_demo" -L"$HERE" -lrfd_hip -Wl,-rpath,'$ORIGIN/..' -Wl,-rpath,"$HERE" -Wl,-rpath,/opt/rocm/lib
 echo "built $OBJ/facade_demo"
+# the gallery's identity calls through include/rfd.hpp (tests/test_gallery_identity_cpp_gpu.py)
+g++ -std=c++17 -O2 -Wall -I"$HERE/../include" "$HERE/../tests/cpp/gallery_identity_demo.cpp" -o "$OBJ/gallery_identity_demo" -L"$HERE" -lrfd_hip -Wl,-rpath,'$ORIGIN/..' -Wl,-rpath,"$HERE" -Wl,-rpath,/opt/rocm/lib
+echo "built $OBJ/gallery_identity_demo"

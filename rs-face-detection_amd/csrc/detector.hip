@@ -269,10 +269,18 @@ struct rfd_gallery {
     int removed = 0, live_synced = 0;
     DevBuf live; // ceil(capacity / 16) words, zero beyond live_synced
     // row lists of remove / replace travel through a ring of page-locked slots (like the context's frame descriptors), so the
-    // calls enqueue without waiting for the stream; allocated by the first such call.  A slot: rows | blocks | their new words.
-    static constexpr int kRing = 4, kEditRows = 1024;
+    // calls enqueue without waiting for the stream; allocated by the first such call.  A slot: rows | blocks | their new words |
+    // the rows whose identity a remove clears; for rfd_gallery_set_identities: rows | identities.
+    static constexpr int kRing = 4, kEditRows = 1024, kEditInts = 4 * kEditRows;
     PinnedRing<kRing> edit_ring;
     DevBuf edit;
+    // Identities (rfd.h, "identities").  The device array (one int32 per row, in whole blocks of 16; -1 = unlabelled) is
+    // allocated by the first rfd_gallery_set_identities; until then no call touches it and every search runs without it.  The
+    // host copy is the truth for _get_identities / _identities: it covers rows [0, ident.size()), the rows behind it are
+    // unlabelled.
+    DevBuf ids;
+    std::vector<int32_t> ident;
+    int labelled = 0; // live rows with an identity >= 0
 };
 
 namespace {
@@ -2376,19 +2384,27 @@ static int gallery_check_rows(const rfd_gallery *g, const int32_t *rows, int n)
     return RFD_OK;
 }
 
+// the ring of page-locked list slots and their device twin, allocated by the first call that sends a list
+static int gallery_edit_lists(rfd_gallery *g)
+{
+    RFD_TRY(g->edit_ring.ensure((size_t)rfd_gallery::kEditInts * sizeof(int32_t)));
+    return g->edit.reserve((size_t)rfd_gallery::kEditInts * sizeof(int32_t));
+}
+
 // Rows `rows` (host, checked) take bf16(emb[i]) and become live (emb: device [n][dim]), or are erased and become removed (emb
 // null).  Enqueued in chunks of kEditRows, each through the next ring slot; no synchronisation with the stream.
 static int gallery_edit(rfd_gallery *g, const int32_t *rows, const float *emb, int n)
 {
     constexpr int kEdit = rfd_gallery::kEditRows;
-    RFD_TRY(g->edit_ring.ensure((size_t)3 * kEdit * sizeof(int32_t))); // first call on this gallery
-    RFD_TRY(g->edit.reserve((size_t)3 * kEdit * sizeof(int32_t)));
+    RFD_TRY(gallery_edit_lists(g)); // first call on this gallery
     RFD_TRY(gallery_live_sync(g));
     for (int at = 0; at < n; at += kEdit) {
         const int m = std::min(kEdit, n - at);
         int32_t *list;
         RFD_TRY(g->edit_ring.acquire(&list));
         int32_t *blk = list + m;
+        int32_t unlabel[kEdit]; // a remove: the rows that lose an identity >= 0; each row once, its second mention finds it removed
+        int nu = 0;
         for (int i = 0; i < m; ++i) {
             const int r = rows[at + i];
             list[i] = r;
@@ -2396,17 +2412,23 @@ static int gallery_edit(rfd_gallery *g, const int32_t *rows, const float *emb, i
             uint16_t &w = g->live_words[r >> 4];
             const uint16_t bit = (uint16_t)(1u << (r & 15));
             if (emb && !(w & bit)) { w |= bit; --g->removed; }
-            if (!emb && (w & bit)) { w &= (uint16_t)~bit; ++g->removed; }
+            if (!emb && (w & bit)) {
+                w &= (uint16_t)~bit;
+                ++g->removed;
+                if ((size_t)r < g->ident.size() && g->ident[r] >= 0) { g->ident[r] = RFD_GALLERY_NO_IDENTITY; --g->labelled; unlabel[nu++] = r; }
+            }
         }
         std::sort(blk, blk + m);
         const int nb = (int)(std::unique(blk, blk + m) - blk);
         int32_t *word = blk + nb;
         for (int j = 0; j < nb; ++j) word[j] = g->live_words[blk[j]];
-        RFD_HIP(hipMemcpyAsync(g->edit.p, list, (size_t)(m + 2 * nb) * sizeof(int32_t), hipMemcpyHostToDevice, g->ctx->stream));
+        std::copy(unlabel, unlabel + nu, word + nb); // nu = 0 unless identities were set: the copy below is then what it always was
+        RFD_HIP(hipMemcpyAsync(g->edit.p, list, (size_t)(m + 2 * nb + nu) * sizeof(int32_t), hipMemcpyHostToDevice, g->ctx->stream));
         RFD_TRY(g->edit_ring.record(g->ctx->stream));
         const int32_t *d = (const int32_t *)g->edit.p;
         RFD_TRY(launch_gallery_put(emb ? emb + (size_t)at * g->dim : nullptr, d, m, g->dim, (bf16_t *)g->store.p, d + m, d + m + nb, nb, (uint16_t *)g->live.p,
                                    g->ctx->stream));
+        if (nu > 0) RFD_TRY(launch_gallery_set_identities((int32_t *)g->ids.p, d + m + 2 * nb, nullptr, nu, g->ctx->stream));
     }
     return RFD_OK;
 }
@@ -2477,8 +2499,10 @@ int rfd_gallery_clear(rfd_gallery *g)
     RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
     if (g->rows > 0) RFD_HIP(hipMemsetAsync(g->store.p, 0, (size_t)ceil_div(g->rows, 16) * 16 * g->dim * sizeof(bf16_t), g->ctx->stream));
     if (g->live_synced > 0) RFD_HIP(hipMemsetAsync(g->live.p, 0, (size_t)ceil_div(g->live_synced, 16) * sizeof(uint16_t), g->ctx->stream));
-    g->rows = g->removed = g->live_synced = 0;
+    if (g->ids.p && g->rows > 0) RFD_HIP(hipMemsetAsync(g->ids.p, 0xff, (size_t)g->rows * sizeof(int32_t), g->ctx->stream)); // all -1 again
+    g->rows = g->removed = g->live_synced = g->labelled = 0;
     g->live_words.clear();
+    g->ident.clear();
     return RFD_OK;
 }
 
@@ -2621,6 +2645,132 @@ int rfd_gallery_removed(const rfd_gallery *g, int32_t *out, int cap, int *count)
     int at = 0;
     for (int r = 0; r < g->rows && at < cap && at < g->removed; ++r)
         if (!((g->live_words[r >> 4] >> (r & 15)) & 1)) out[at++] = r;
+    return RFD_OK;
+}
+
+// ---- identities (rfd.h, "identities") ----
+int rfd_gallery_set_identities(rfd_gallery *g, const int32_t *rows, const int32_t *ids, int n)
+{
+    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(rows && ids, "rows or ids is null");
+    RFD_TRY(gallery_check_rows(g, rows, n));
+    for (int i = 0; i < n; ++i) {
+        if (!((g->live_words[rows[i] >> 4] >> (rows[i] & 15)) & 1)) {
+            set_error("invalid argument: rows[%d] = %d is a removed row", i, rows[i]);
+            return RFD_ERR_INVALID_ARG;
+        }
+        if (ids[i] < RFD_GALLERY_NO_IDENTITY) {
+            set_error("invalid argument: ids[%d] = %d is neither an identity (>= 0) nor RFD_GALLERY_NO_IDENTITY", i, ids[i]);
+            return RFD_ERR_INVALID_ARG;
+        }
+    }
+    RFD_TRY(gallery_check_distinct(rows, n));
+    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
+    RFD_TRY(gallery_edit_lists(g));
+    if (!g->ids.p) { // the first labels of this gallery: the array, all unlabelled, in stream order ahead of every use
+        const size_t bytes = (size_t)ceil_div(g->capacity, 16) * 16 * sizeof(int32_t); // whole blocks: the scan reads a block's 16 words
+        RFD_TRY(g->ids.reserve(bytes));
+        if (hipMemsetAsync(g->ids.p, 0xff, bytes, g->ctx->stream) != hipSuccess) {
+            set_error("hipMemsetAsync of the gallery's identities failed");
+            (void)hipStreamSynchronize(g->ctx->stream);
+            g->ids.release();
+            return RFD_ERR_HIP;
+        }
+    }
+    if (g->ident.size() < (size_t)g->rows) g->ident.resize((size_t)g->rows, RFD_GALLERY_NO_IDENTITY);
+    constexpr int kEdit = rfd_gallery::kEditRows;
+    for (int at = 0; at < n; at += kEdit) {
+        const int m = std::min(kEdit, n - at);
+        int32_t *list;
+        RFD_TRY(g->edit_ring.acquire(&list));
+        for (int i = 0; i < m; ++i) {
+            int32_t &have = g->ident[rows[at + i]];
+            g->labelled += (ids[at + i] >= 0) - (have >= 0);
+            have = list[m + i] = ids[at + i];
+            list[i] = rows[at + i];
+        }
+        RFD_HIP(hipMemcpyAsync(g->edit.p, list, (size_t)2 * m * sizeof(int32_t), hipMemcpyHostToDevice, g->ctx->stream));
+        RFD_TRY(g->edit_ring.record(g->ctx->stream));
+        const int32_t *d = (const int32_t *)g->edit.p;
+        RFD_TRY(launch_gallery_set_identities((int32_t *)g->ids.p, d, d + m, m, g->ctx->stream));
+    }
+    return RFD_OK;
+}
+
+int rfd_gallery_get_identities(const rfd_gallery *g, int row0, int n, int32_t *out)
+{
+    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(out, "out is null");
+    RFD_CHECK_ARG(row0 >= 0 && n <= g->rows - row0, "rows [row0, row0 + n) are not all in the gallery");
+    for (int i = 0; i < n; ++i) out[i] = (size_t)(row0 + i) < g->ident.size() ? g->ident[row0 + i] : RFD_GALLERY_NO_IDENTITY;
+    return RFD_OK;
+}
+
+int rfd_gallery_identities(const rfd_gallery *g, int *labelled_rows)
+{
+    RFD_CHECK_ARG(g && labelled_rows, "null argument");
+    *labelled_rows = g->labelled;
+    return RFD_OK;
+}
+
+static int gallery_check_min_score(float min_score)
+{
+    RFD_CHECK_ARG(min_score == min_score, "min_score is NaN");
+    return RFD_OK;
+}
+
+int rfd_gallery_search_identities_device(rfd_gallery *g, const float *queries, int n, int k, float min_score, float *scores, int32_t *rows, int32_t *ids,
+                                         int async)
+{
+    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
+    RFD_TRY(gallery_check_k(k));
+    RFD_TRY(gallery_check_min_score(min_score));
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(queries && scores && rows && ids, "null argument");
+    RFD_CHECK_ARG((uintptr_t)queries % 16 == 0, "queries are not 16-byte aligned");
+    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
+    const uint16_t *live = nullptr;
+    RFD_TRY(gallery_search_mask(g, &live));
+    for (int i = 0; i < n; i += kGalleryMaxQueries)
+        RFD_TRY(launch_gallery_search_identities((const bf16_t *)g->store.p, live, (const int32_t *)g->ids.p, g->rows, g->dim, queries + (size_t)i * g->dim,
+                                                 std::min(kGalleryMaxQueries, n - i), k, min_score, (uint2 *)g->ws.p, g->groups_max, scores + (size_t)i * k,
+                                                 rows + (size_t)i * k, ids + (size_t)i * k, g->ctx->stream));
+    if (!async) RFD_HIP(hipStreamSynchronize(g->ctx->stream));
+    return RFD_OK;
+}
+
+int rfd_gallery_search_identities(rfd_gallery *g, const float *queries, int n, int k, float min_score, float *scores, int32_t *rows, int32_t *ids)
+{
+    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
+    RFD_TRY(gallery_check_k(k));
+    RFD_TRY(gallery_check_min_score(min_score));
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(queries && scores && rows && ids, "null argument");
+    RFD_TRY(gallery_check_finite(queries, n, g->dim, "query"));
+    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
+    RFD_TRY(gallery_host_stage(g));
+    const uint16_t *live = nullptr;
+    RFD_TRY(gallery_search_mask(g, &live));
+    // the staging buffer holds one group: its queries, then its scores, rows and identities
+    const size_t qcap = (size_t)kGalleryMaxQueries * g->dim * sizeof(float), rcap = (size_t)kGalleryMaxQueries * RFD_GALLERY_MAX_K * sizeof(float);
+    float *d_q = (float *)g->stage.p, *d_s = (float *)((char *)g->stage.p + qcap);
+    int32_t *d_r = (int32_t *)((char *)g->stage.p + qcap + rcap), *d_i = (int32_t *)((char *)g->stage.p + qcap + 2 * rcap);
+    char *h = (char *)g->pin;
+    for (int i = 0; i < n; i += kGalleryMaxQueries) {
+        const int m = std::min(kGalleryMaxQueries, n - i);
+        const size_t qbytes = (size_t)m * g->dim * sizeof(float), rbytes = (size_t)m * k * sizeof(float);
+        memcpy(h, queries + (size_t)i * g->dim, qbytes);
+        RFD_HIP(hipMemcpyAsync(d_q, h, qbytes, hipMemcpyHostToDevice, g->ctx->stream));
+        RFD_TRY(launch_gallery_search_identities((const bf16_t *)g->store.p, live, (const int32_t *)g->ids.p, g->rows, g->dim, d_q, m, k, min_score,
+                                                 (uint2 *)g->ws.p, g->groups_max, d_s, d_r, d_i, g->ctx->stream));
+        RFD_HIP(hipMemcpyAsync(h + qcap, d_s, 3 * rcap, hipMemcpyDeviceToHost, g->ctx->stream)); // the three results lie side by side
+        RFD_HIP(hipStreamSynchronize(g->ctx->stream));
+        memcpy(scores + (size_t)i * k, h + qcap, rbytes);
+        memcpy(rows + (size_t)i * k, h + qcap + rcap, rbytes);
+        memcpy(ids + (size_t)i * k, h + qcap + 2 * rcap, rbytes);
+    }
     return RFD_OK;
 }
 

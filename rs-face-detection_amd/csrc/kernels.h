@@ -226,6 +226,13 @@ int gallery_search_groups(int rows, int groups_max);
 // live: null (every row counts: the scan without the mask), or one 16-bit word per block of 16 rows, bit i = row 16 b + i counts
 int launch_gallery_search(const bf16_t *store, const uint16_t *live, int rows, int dim, const float *queries, int n, int k, uint2 *ws, int groups_max,
                           float *scores, int32_t *out_rows, hipStream_t s);
+// The identity form (rfd.h, "identities"): the k best identities of each query, each under its best row's key -> scores /
+// out_rows / out_ids [n][k]; entries with !(score >= min_score) become the empty entry (-inf, -1, -1).  ids: one int32 per row
+// (-1: the row is an identity of its own), allocated in whole blocks of 16 rows (the scan reads a block's 16 words), or null: no row is labelled, the plain scan runs and out_ids is all -1.
+int launch_gallery_search_identities(const bf16_t *store, const uint16_t *live, const int32_t *ids, int rows, int dim, const float *queries, int n, int k,
+                                     float min_score, uint2 *ws, int groups_max, float *scores, int32_t *out_rows, int32_t *out_ids, hipStream_t s);
+// ids[rows[i]] = vals[i] for i < n, or -1 where vals is null (rows: device list of distinct rows)
+int launch_gallery_set_identities(int32_t *ids, const int32_t *rows, const int32_t *vals, int n, hipStream_t s);
 // rows[i] (device list, distinct unless emb is null) of store takes bf16(emb[i]), or zeros where emb is null; then live[blk[j]] =
 // word[j] for j < nwords <= n (device lists, blk distinct)
 int launch_gallery_put(const float *emb, const int32_t *rows, int n, int dim, bf16_t *store, const int32_t *blk, const int32_t *word, int nwords,

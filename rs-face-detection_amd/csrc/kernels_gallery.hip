@@ -16,6 +16,16 @@
 // the end one barrier, the four lists of a query are merged, and the workgroup writes k keys per query to the workspace
 // [groups][n][k]; gallery_merge_kernel reduces the groups' lists per query with the same two routines.  The order is total (rows
 // are unique), so the result does not depend on which wave or workgroup scored a row.
+//
+// Identity search (rfd.h, "identities"): rows carry an int32 identity in HBM (-1: a row of its own); the IDENT instantiations of the
+// scan and gallery_merge_identities_kernel keep the k best IDENTITIES, each under its best row's key, with the same lists plus one
+// identity word per key in LDS, so a list entry's identity never has to be fetched again and a sentinel never indexes the array.
+// The scan reads the identities of a block's 16 rows (64 bytes) only if a key of the block passes a list's filter.
+// Why the two-level reduction stays exact: an identity of the global top k has its best key in the rows of some wave.  In that
+// wave's list it is among the k best distinct identities -- were it not, k other identities of that wave alone would hold keys
+// better than its best key, and the same k identities would beat it globally.  A later row of the identity in that wave cannot
+// push it out either: it only replaces the identity's key by a better one.  The same holds one level up for a workgroup's merged
+// list among the workgroups, so every level may drop all but its k best distinct identities.
 #include "conv_device.h"
 
 namespace rfd {
@@ -83,6 +93,95 @@ __device__ __forceinline__ void merge_wave_lists(const uint2 *lists, int wave_pi
     }
 }
 
+template <class T, class... Rest>
+__device__ __forceinline__ T pack_first(T first, Rest...) { return first; }
+template <class T>
+__device__ __forceinline__ T pack_last(T last) { return last; }
+template <class T, class... Rest>
+__device__ __forceinline__ auto pack_last(T, Rest... rest) { return pack_last(rest...); }
+
+// ---- the identity forms of the three routines above.  A list holds no identity >= 0 twice; lid[i] is the identity of list[i]
+//      (-1 for an unlabelled row and for the sentinel, which never equals a candidate's identity >= 0). ----
+
+// list_insert with the candidate's identity c.  An entry of identity c >= 0 ahead of the new key rejects it; one behind it, at p,
+// is the entry the new key replaces: it goes in at pos <= p and only [pos, p] shifts.  Without such an entry p is the last index
+// and this is list_insert.  At most one lane can hold c (the invariant), and the invariant holds afterwards: c is in the list once.
+__device__ __forceinline__ void list_insert_ident(uint2 *list, int32_t *lid, int k, float cs, int crow, int c, int lane)
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    const bool in = lane < k;
+    uint2 e = gallery_sentinel(), ep = e;
+    int id = -1, idp = -1;
+    if (in) {
+        e = list[lane];
+        id = lid[lane];
+        if (lane > 0) { ep = list[lane - 1]; idp = lid[lane - 1]; }
+    }
+    const bool ahead = in && key_better(__uint_as_float(e.x), (int)e.y, cs, crow);
+    const int pos = __popcll(__ballot(ahead));
+    const unsigned long long same = __ballot(in && c >= 0 && id == c);
+    const int p = same ? __ffsll(same) - 1 : k - 1; // p < pos: the listed key of c is the better one (or the list is full of better keys)
+    if (in && lane >= pos && lane <= p) {
+        list[lane] = lane == pos ? make_uint2(__float_as_uint(cs), (uint32_t)crow) : ep;
+        lid[lane] = lane == pos ? c : idp;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+
+// list_offer for identities; c is the identity of the lane's row (read by the caller; unused where !valid).  The last key is
+// still a correct filter: a key worse than the last key of a full list either repeats a listed identity, whose listed key is
+// then the better one, or loses to k distinct identities; a list that is not full ends in the sentinel, which every key of a
+// valid lane beats.
+__device__ __forceinline__ void list_offer_ident(uint2 *lists, int32_t *lids, int li, int k, float s, int row, int c, bool valid, int lane)
+{
+    bool pass = false;
+    if (valid) {
+        const uint2 t = lists[li * k + k - 1];
+        pass = key_better(s, row, __uint_as_float(t.x), (int)t.y);
+    }
+    unsigned long long m = __ballot(pass);
+    while (m) {
+        const int l = __ffsll(m) - 1;
+        m &= m - 1;
+        const int at = __builtin_amdgcn_readlane(li, l) * k;
+        list_insert_ident(lists + at, lids + at, k, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), l)), __builtin_amdgcn_readlane(row, l),
+                          __builtin_amdgcn_readlane(c, l), lane);
+    }
+}
+
+// merge_wave_lists for identities: the k best keys of distinct identities, handed to out(j, key, identity); one thread.  A head
+// whose identity was already emitted is skipped.  Head indices: every key taken from a list is either emitted or skipped because
+// its identity is in the output, and a list holds k distinct identities (unlabelled keys and sentinels are never skipped), so a
+// list is exhausted only once k keys are out: every head index is < k while fewer than k keys are emitted.  The emitted
+// identities stay in registers (k <= 32).
+template <class Out>
+__device__ __forceinline__ void merge_wave_lists_ident(const uint2 *lists, const int32_t *lids, int wave_pitch, int k, Out out)
+{
+    static_assert(RFD_GALLERY_MAX_K == 32, "the emitted identities are kept in 32 registers");
+    int seen[32];
+#pragma unroll
+    for (int t = 0; t < 32; ++t) seen[t] = -1;
+    int h0 = 0, h1 = 0, h2 = 0, h3 = 0;
+    for (int j = 0; j < k;) {
+        const uint2 e0 = lists[h0], e1 = lists[wave_pitch + h1], e2 = lists[2 * wave_pitch + h2], e3 = lists[3 * wave_pitch + h3];
+        uint2 b = e0;
+        int bi = 0;
+        if (key_better(__uint_as_float(e1.x), (int)e1.y, __uint_as_float(b.x), (int)b.y)) { b = e1; bi = 1; }
+        if (key_better(__uint_as_float(e2.x), (int)e2.y, __uint_as_float(b.x), (int)b.y)) { b = e2; bi = 2; }
+        if (key_better(__uint_as_float(e3.x), (int)e3.y, __uint_as_float(b.x), (int)b.y)) { b = e3; bi = 3; }
+        const int id = lids[bi * wave_pitch + (bi == 0 ? h0 : bi == 1 ? h1 : bi == 2 ? h2 : h3)];
+        h0 += bi == 0; h1 += bi == 1; h2 += bi == 2; h3 += bi == 3;
+        bool emitted = false;
+#pragma unroll
+        for (int t = 0; t < 32; ++t) emitted |= seen[t] == id;
+        if (id >= 0 && emitted) continue;
+#pragma unroll
+        for (int t = 0; t < 32; ++t) seen[t] = t == j ? id : seen[t];
+        out(j, b, id);
+        ++j;
+    }
+}
+
 } // namespace
 
 // ---- add: f32 -> bf16 (RNE), scattered into the fragment-major layout.  One thread per 16-byte operand. ----
@@ -134,20 +233,30 @@ int launch_gallery_get(const bf16_t *store, int row0, int n, int dim, float *out
 // every load in flight (vmcnt(0)) inside the loop, which this one does not: loading with the last K step alone (the word becomes
 // a value merged from two paths, and all words are copied at every step); loading 16 bits (the words are zero-extended, or packed
 // in pairs, at the loop's back edge); using the word after the next loads were issued (old and new value live side by side and
-// are copied at the back edge).  The words' address is the one member of the pack `Live` of a MASKED instantiation; without
-// MASKED the pack is empty, so that instantiation has the arguments and the code of the scan as it was.
-template <int NMT, bool MASKED, class... Live>
+// are copied at the back edge).  The words' address is the last member of the pack `Live` of a MASKED instantiation; without
+// MASKED and IDENT the pack is empty, so that instantiation has the arguments and the code of the scan as it was.
+// IDENT: the identity scan.  The pack then begins with the identity array (one int32 per row), the lists carry an identity word
+// per key behind them in LDS, and the selection goes through the identity forms of the list routines; the MFMA loop, the
+// prefetch and the `any` pre-check are the same code.  Without IDENT nothing of this is instantiated.
+template <int NMT, bool MASKED, bool IDENT, class... Live>
 __global__ void __launch_bounds__(kGalleryWaves * 64) gallery_search_kernel(const bf16_t *__restrict__ store, int rows, int ksteps,
                                                                              const float *__restrict__ queries, int n, int k,
                                                                              uint2 *__restrict__ ws, Live... live)
 {
-    static_assert(sizeof...(Live) == (MASKED ? 1 : 0), "a masked scan takes the live words, the other nothing");
+    static_assert(sizeof...(Live) == (IDENT ? 1 : 0) + (MASKED ? 1 : 0), "an identity scan takes the identities, a masked scan the live words behind them");
     extern __shared__ __attribute__((aligned(16))) unsigned char gallery_smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6); // scalar: the walk below is wave-uniform
     const int dim = ksteps * 32, quads = dim >> 2;
     uint2 *afrag = reinterpret_cast<uint2 *>(gallery_smem);  // [NMT][ksteps][2 halves][64 lanes] x 4 bf16
     uint2 *lists = afrag + NMT * ksteps * 128;               // [waves][NMT * 16 queries][k]
     uint2 *mine = lists + wave * (NMT * 16 * k);
+    [[maybe_unused]] int32_t *lids = nullptr, *mine_ids = nullptr;  // IDENT: [waves][NMT * 16 queries][k] identities of the keys
+    [[maybe_unused]] const int32_t *ids = nullptr;
+    if constexpr (IDENT) {
+        lids = reinterpret_cast<int32_t *>(lists + kGalleryWaves * NMT * 16 * k);
+        mine_ids = lids + wave * (NMT * 16 * k);
+        ids = pack_first(live...);
+    }
 
     // queries -> bf16 A fragments: lane (q & 15) + 16 * ((d & 31) >> 3) of K step d >> 5 holds elements d & ~7 .. + 7 of query q
     for (int i = tid; i < NMT * 16 * quads; i += kGalleryWaves * 64) {
@@ -157,6 +266,8 @@ __global__ void __launch_bounds__(kGalleryWaves * 64) gallery_search_kernel(cons
         afrag[(((q >> 4) * ksteps + (d >> 5)) * 2 + ((d & 7) >> 2)) * 64 + (q & 15) + 16 * ((d & 31) >> 3)] = pack_bf16x4(v.x, v.y, v.z, v.w);
     }
     for (int i = lane; i < NMT * 16 * k; i += 64) mine[i] = gallery_sentinel();
+    if constexpr (IDENT)
+        for (int i = lane; i < NMT * 16 * k; i += 64) mine_ids[i] = -1;
     __syncthreads();
 
     const int nblocks = (rows + 15) >> 4;
@@ -176,7 +287,7 @@ __global__ void __launch_bounds__(kGalleryWaves * 64) gallery_search_kernel(cons
         auto issue = [&](uint4 &dst, uint32_t &words) {
             const int b = pblk < nblocks ? pblk : nblocks - 1;
             dst = src[((size_t)b * ksteps + pks) * 64];
-            if constexpr (MASKED) words = reinterpret_cast<const uint32_t *>((live, ...))[(b >> 1) + lane_zero];
+            if constexpr (MASKED) words = reinterpret_cast<const uint32_t *>(pack_last(live...))[(b >> 1) + lane_zero];
             if (++pks == ksteps) { pks = 0; pblk += stride; }
         };
 #pragma unroll
@@ -218,12 +329,28 @@ __global__ void __launch_bounds__(kGalleryWaves * 64) gallery_search_kernel(cons
                                 }
                             }
                         if (__ballot(any)) {
+                            // IDENT: the identities of the block's 16 rows, read once for all its offers and only here, in a
+                            // block with a key that passes a filter: one wait per such block.
+                            // The address is wave-uniform, so these are scalar loads (the array has 16 words per block, also
+                            // for a partial last block): they are waited for by lgkmcnt like the LDS reads around them.  A
+                            // per-lane ids[row] is a vector load in a branch, behind which the compiler no longer counts the
+                            // operand loads in flight and waits for all of them (vmcnt(0)) at every K step of the loop.
+                            [[maybe_unused]] int cid = -1;
+                            if constexpr (IDENT) {
+                                const int32_t *block_ids = ids + (size_t)__builtin_amdgcn_readfirstlane(blk) * 16;
+#pragma unroll
+                                for (int i = 0; i < 16; ++i) {
+                                    const int v = block_ids[i];
+                                    cid = (lane & 15) == i ? v : cid;
+                                }
+                            }
 #pragma unroll
                             for (int mt = 0; mt < NMT; ++mt)
 #pragma unroll
                                 for (int r = 0; r < 4; ++r) {
                                     const int q = mt * 16 + 4 * (lane >> 4) + r;
-                                    list_offer(mine, q, k, acc[mt][r], row, row_ok && q < n, lane);
+                                    if constexpr (IDENT) list_offer_ident(mine, mine_ids, q, k, acc[mt][r], row, cid, row_ok && q < n, lane);
+                                    else list_offer(mine, q, k, acc[mt][r], row, row_ok && q < n, lane);
                                 }
                         }
                     }
@@ -238,7 +365,9 @@ __global__ void __launch_bounds__(kGalleryWaves * 64) gallery_search_kernel(cons
     __syncthreads();
     if (tid < n) {
         uint2 *dst = ws + ((size_t)blockIdx.x * n + tid) * k;
-        merge_wave_lists(lists + tid * k, NMT * 16 * k, k, [&](int j, uint2 key) { dst[j] = key; });
+        // IDENT: the workspace keeps keys alone; the merge kernel reads the identities of the few keys it is handed once more
+        if constexpr (IDENT) merge_wave_lists_ident(lists + tid * k, lids + tid * k, NMT * 16 * k, k, [&](int j, uint2 key, int) { dst[j] = key; });
+        else merge_wave_lists(lists + tid * k, NMT * 16 * k, k, [&](int j, uint2 key) { dst[j] = key; });
     }
 }
 
@@ -284,13 +413,13 @@ static int launch_gallery_scan(int groups, size_t lds, hipStream_t s, const bf16
     constexpr int kLdsMax = 2 * 16 * 1024 * 2 + kGalleryWaves * 32 * RFD_GALLERY_MAX_K * 8; // dim 1024, 32 queries, k 32: 96 KiB
     static DynLdsOnce once;
     const void *kernel = nullptr;
-    if constexpr (MASKED) kernel = (const void *)gallery_search_kernel<NMT, true, GalleryLiveWords>;
-    else kernel = (const void *)gallery_search_kernel<NMT, false>;
+    if constexpr (MASKED) kernel = (const void *)gallery_search_kernel<NMT, true, false, GalleryLiveWords>;
+    else kernel = (const void *)gallery_search_kernel<NMT, false, false>;
     RFD_TRY(once.ensure(kernel, kLdsMax));
     if constexpr (MASKED)
-        hipLaunchKernelGGL((gallery_search_kernel<NMT, true, GalleryLiveWords>), dim3(groups), dim3(kGalleryWaves * 64), lds, s, store, rows, ksteps, queries, n, k, ws, live);
+        hipLaunchKernelGGL((gallery_search_kernel<NMT, true, false, GalleryLiveWords>), dim3(groups), dim3(kGalleryWaves * 64), lds, s, store, rows, ksteps, queries, n, k, ws, live);
     else
-        hipLaunchKernelGGL((gallery_search_kernel<NMT, false>), dim3(groups), dim3(kGalleryWaves * 64), lds, s, store, rows, ksteps, queries, n, k, ws);
+        hipLaunchKernelGGL((gallery_search_kernel<NMT, false, false>), dim3(groups), dim3(kGalleryWaves * 64), lds, s, store, rows, ksteps, queries, n, k, ws);
     RFD_HIP(hipGetLastError());
     return RFD_OK;
 }
@@ -307,6 +436,108 @@ int launch_gallery_search(const bf16_t *store, const uint16_t *live, int rows, i
     auto *scan = live ? (nmt == 2 ? launch_gallery_scan<2, true> : launch_gallery_scan<1, true>) : (nmt == 2 ? launch_gallery_scan<2, false> : launch_gallery_scan<1, false>);
     RFD_TRY(scan(groups, lds, s, store, rows, ksteps, queries, n, k, ws, live));
     hipLaunchKernelGGL(gallery_merge_kernel, dim3(n), dim3(kGalleryWaves * 64), 0, s, ws, groups, n, k, scores, out_rows);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+// ---- identity merge: gallery_merge_kernel with the identity forms of the two routines; writes the k best identities' keys and
+//      identities, and the empty entry where !(score >= min_score) (a suffix: the keys are in descending order).  ids: the
+//      identity array, read for the keys of the workspace (rows >= 0 only), or null: all unlabelled. ----
+__global__ void __launch_bounds__(kGalleryWaves * 64) gallery_merge_identities_kernel(const uint2 *__restrict__ ws, int groups, int n, int k,
+                                                                                       const int32_t *__restrict__ ids, float min_score,
+                                                                                       float *__restrict__ scores, int32_t *__restrict__ out_rows,
+                                                                                       int32_t *__restrict__ out_ids)
+{
+    __shared__ uint2 lists[kGalleryWaves * 32];
+    __shared__ int32_t lids[kGalleryWaves * 32];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), q = blockIdx.x;
+    uint2 *mine = lists + wave * k;
+    int32_t *mine_ids = lids + wave * k;
+    if (lane < k) {
+        mine[lane] = gallery_sentinel();
+        mine_ids[lane] = -1;
+    }
+    const int total = groups * k;
+    for (int base = wave * 64; base < total; base += kGalleryWaves * 64) { // wave-uniform bounds: list_offer_ident runs with all lanes
+        const int idx = base + lane;
+        uint2 c = gallery_sentinel();
+        if (idx < total) {
+            const int g = idx / k, j = idx - g * k;
+            c = ws[((size_t)g * n + q) * k + j];
+        }
+        const bool valid = (int)c.y >= 0; // a sentinel's row never indexes the identity array
+        int cid = -1;
+        if (valid && ids) cid = ids[c.y];
+        list_offer_ident(mine, mine_ids, 0, k, __uint_as_float(c.x), (int)c.y, cid, valid, lane);
+    }
+    __syncthreads();
+    if (tid == 0)
+        merge_wave_lists_ident(lists, lids, k, k, [&](int j, uint2 key, int id) {
+            const float sc = __uint_as_float(key.x);
+            const bool keep = sc >= min_score; // false for the sentinel unless min_score is -inf, and then the sentinel is what is written
+            scores[(size_t)q * k + j] = keep ? sc : __uint_as_float(gallery_sentinel().x);
+            out_rows[(size_t)q * k + j] = keep ? (int32_t)key.y : -1;
+            out_ids[(size_t)q * k + j] = keep ? id : -1;
+        });
+}
+
+using GalleryIdentities = const int32_t *__restrict__;
+
+template <int NMT, bool MASKED>
+static int launch_gallery_scan_identities(int groups, size_t lds, hipStream_t s, const bf16_t *store, int rows, int ksteps, const float *queries, int n,
+                                          int k, uint2 *ws, const int32_t *ids, const uint16_t *live)
+{
+    // dim 1024, 32 queries, k 32: 96 KiB of fragments and keys, 16 KiB of identities: 112 of the CU's 160 KiB
+    constexpr int kLdsMax = 2 * 16 * 1024 * 2 + kGalleryWaves * 32 * RFD_GALLERY_MAX_K * (8 + 4);
+    static DynLdsOnce once;
+    const void *kernel = nullptr;
+    if constexpr (MASKED) kernel = (const void *)gallery_search_kernel<NMT, true, true, GalleryIdentities, GalleryLiveWords>;
+    else kernel = (const void *)gallery_search_kernel<NMT, false, true, GalleryIdentities>;
+    RFD_TRY(once.ensure(kernel, kLdsMax));
+    if constexpr (MASKED)
+        hipLaunchKernelGGL((gallery_search_kernel<NMT, true, true, GalleryIdentities, GalleryLiveWords>), dim3(groups), dim3(kGalleryWaves * 64), lds, s, store, rows, ksteps,
+                           queries, n, k, ws, ids, live);
+    else
+        hipLaunchKernelGGL((gallery_search_kernel<NMT, false, true, GalleryIdentities>), dim3(groups), dim3(kGalleryWaves * 64), lds, s, store, rows, ksteps, queries, n, k,
+                           ws, ids);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+int launch_gallery_search_identities(const bf16_t *store, const uint16_t *live, const int32_t *ids, int rows, int dim, const float *queries, int n, int k,
+                                     float min_score, uint2 *ws, int groups_max, float *scores, int32_t *out_rows, int32_t *out_ids, hipStream_t s)
+{
+    if (n < 1 || n > kGalleryMaxQueries || k < 1 || k > RFD_GALLERY_MAX_K || dim % 32 != 0 || rows < 0 || groups_max < 1) {
+        set_error("launch_gallery_search_identities: n %d, k %d, dim %d, rows %d out of range", n, k, dim, rows);
+        return RFD_ERR_INVALID_ARG;
+    }
+    const int groups = gallery_search_groups(rows, groups_max), ksteps = dim / 32, nmt = n > 16 ? 2 : 1;
+    const size_t keys = (size_t)kGalleryWaves * nmt * 16 * k, lds = (size_t)nmt * 16 * dim * sizeof(bf16_t) + keys * sizeof(uint2);
+    if (ids) { // the identity scan; its lists carry an identity word per key
+        auto *scan = live ? (nmt == 2 ? launch_gallery_scan_identities<2, true> : launch_gallery_scan_identities<1, true>)
+                          : (nmt == 2 ? launch_gallery_scan_identities<2, false> : launch_gallery_scan_identities<1, false>);
+        RFD_TRY(scan(groups, lds + keys * sizeof(int32_t), s, store, rows, ksteps, queries, n, k, ws, ids, live));
+    } else { // no identity was ever set: every row is its own identity, and the plain scan selects exactly that
+        auto *scan = live ? (nmt == 2 ? launch_gallery_scan<2, true> : launch_gallery_scan<1, true>) : (nmt == 2 ? launch_gallery_scan<2, false> : launch_gallery_scan<1, false>);
+        RFD_TRY(scan(groups, lds, s, store, rows, ksteps, queries, n, k, ws, live));
+    }
+    hipLaunchKernelGGL(gallery_merge_identities_kernel, dim3(n), dim3(kGalleryWaves * 64), 0, s, ws, groups, n, k, ids, min_score, scores, out_rows, out_ids);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+// ---- identities of rows: ids[rows[i]] = vals[i], or -1 where vals is null (remove).  rows: a device list of distinct rows, so
+//      every word has one writer. ----
+__global__ void __launch_bounds__(256) gallery_set_identities_kernel(int32_t *__restrict__ ids, const int32_t *__restrict__ rows,
+                                                                     const int32_t *__restrict__ vals, int n)
+{
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i < n) ids[rows[i]] = vals ? vals[i] : -1;
+}
+
+int launch_gallery_set_identities(int32_t *ids, const int32_t *rows, const int32_t *vals, int n, hipStream_t s)
+{
+    hipLaunchKernelGGL(gallery_set_identities_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ids, rows, vals, n);
     RFD_HIP(hipGetLastError());
     return RFD_OK;
 }

@@ -31,6 +31,7 @@ JPEG_ORIENTATION_IGNORE, JPEG_ORIENTATION_APPLY = 0, 1  # rfd_jpeg_orientation_m
 COMM_ID_BYTES = 128
 MAX_FACE_TENSORS = 4   # RFD_MAX_FACE_TENSORS
 GALLERY_MAX_K = 32     # RFD_GALLERY_MAX_K
+NO_IDENTITY = -1       # RFD_GALLERY_NO_IDENTITY: an unlabelled gallery row, an identity of its own
 
 # debug_set_conv_tile / op_kernels_static: the forced tiles, enum ConvTile of csrc/kernels.h (each value's meaning is there)
 (TILE_HEURISTIC, TILE_128, TILE_256x128, TILE_256x64, TILE_NO_128, TILE_NO_PW_STREAM, TILE_PERSISTENT, TILE_GENERIC, TILE_PW_STREAM,
@@ -168,6 +169,8 @@ API_SYMBOLS = [
     "rfd_gallery_get_rows", "rfd_gallery_search", "rfd_gallery_search_device", "rfd_debug_gallery_offset",
     "rfd_gallery_remove", "rfd_gallery_replace", "rfd_gallery_replace_device", "rfd_gallery_live", "rfd_gallery_removed",
     "rfd_gallery_save", "rfd_gallery_load", "rfd_gallery_file_info",
+    "rfd_gallery_set_identities", "rfd_gallery_get_identities", "rfd_gallery_identities", "rfd_gallery_search_identities",
+    "rfd_gallery_search_identities_device",
     "rfd_jpeg_info", "rfd_decode_jpeg_batch_device", "rfd_decode_jpeg_batch", "rfd_set_decode_threads", "rfd_debug_jpeg_coefficients",
     "rfd_set_jpeg_entropy", "rfd_jpeg_last_paths", "rfd_debug_jpeg_intervals", "rfd_debug_jpeg_coefficients_device",
     "rfd_jpeg_orientation", "rfd_set_jpeg_orientation", "rfd_jpeg_last_orientations",
@@ -299,6 +302,11 @@ def load_library(path=None):
     L.rfd_gallery_replace_device.argtypes = [vp, vp, vp, ci]
     L.rfd_gallery_live.argtypes = [vp, C.POINTER(ci)]
     L.rfd_gallery_removed.argtypes = [vp, vp, ci, C.POINTER(ci)]
+    L.rfd_gallery_set_identities.argtypes = [vp, vp, vp, ci]
+    L.rfd_gallery_get_identities.argtypes = [vp, ci, ci, vp]
+    L.rfd_gallery_identities.argtypes = [vp, C.POINTER(ci)]
+    L.rfd_gallery_search_identities.argtypes = [vp, vp, ci, ci, C.c_float, vp, vp, vp]
+    L.rfd_gallery_search_identities_device.argtypes = [vp, vp, ci, ci, C.c_float, vp, vp, vp, ci]
     L.rfd_gallery_save.argtypes = [vp, C.c_char_p]
     L.rfd_gallery_load.argtypes = [vp, C.c_char_p, ci, C.POINTER(vp)]
     L.rfd_gallery_file_info.argtypes = [C.c_char_p, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
@@ -718,6 +726,41 @@ class Gallery:
         """the same on raw device addresses (torch tensors' data_ptr()); enqueued on the detector's stream, with no host
         synchronisation when async_ is set (then det.sync() before reading)"""
         _check(self._L.rfd_gallery_search_device(self._g, queries_ptr, int(n), int(k), scores_ptr, rows_ptr, int(async_)))
+
+    def set_identities(self, rows, ids):
+        """row rows[i] (live, distinct) gets the identity ids[i] (>= 0, or NO_IDENTITY to unlabel it); enqueued on the detector's
+        stream, no synchronisation (rfd.h, "identities")"""
+        r, i = self._row_list(rows), self._row_list(ids)
+        assert r.shape[0] == i.shape[0], "one identity per row"
+        _check(self._L.rfd_gallery_set_identities(self._g, r.ctypes.data, i.ctypes.data, r.shape[0]))
+
+    def identities(self, row0, n):
+        """the identities of rows [row0, row0 + n) (i32 array; NO_IDENTITY for unlabelled and removed rows)"""
+        out = np.zeros(int(n), np.int32)
+        _check(self._L.rfd_gallery_get_identities(self._g, int(row0), int(n), out.ctypes.data))
+        return out
+
+    def labelled(self):
+        """live rows that carry an identity >= 0"""
+        n = C.c_int()
+        _check(self._L.rfd_gallery_identities(self._g, C.byref(n)))
+        return n.value
+
+    def search_identities(self, queries, k, min_score=-np.inf):
+        """queries [n, dim] f32 -> (scores [n, k] f32, rows [n, k] i32, ids [n, k] i32): the k best identities of every query,
+        each under its best live row (an unlabelled row is an identity of its own); entries with not score >= min_score and the
+        tail beyond the gallery's identities are (-inf, -1, -1)"""
+        x = self._rows2d(queries)
+        shape = (x.shape[0], max(int(k), 0))
+        scores, rows, ids = np.zeros(shape, np.float32), np.zeros(shape, np.int32), np.zeros(shape, np.int32)
+        _check(self._L.rfd_gallery_search_identities(self._g, x.ctypes.data, x.shape[0], int(k), float(min_score), scores.ctypes.data, rows.ctypes.data,
+                                                     ids.ctypes.data))
+        return scores, rows, ids
+
+    def search_identities_device(self, queries_ptr, n, k, min_score, scores_ptr, rows_ptr, ids_ptr, async_=False):
+        """the same on raw device addresses, by the conventions of search_device"""
+        _check(self._L.rfd_gallery_search_identities_device(self._g, queries_ptr, int(n), int(k), float(min_score), scores_ptr, rows_ptr, ids_ptr,
+                                                            int(async_)))
 
 
 class RetinaFaceDetection:

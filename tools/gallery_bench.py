@@ -14,6 +14,12 @@ rounded to bf16 before the top-k, so its rows are compared with the library's on
 removed (rfd_gallery_remove) and the same windows are timed on the masked scan, then the rows are put back
 (rfd_gallery_replace_device with their own embeddings) and the plain windows are timed again, so a drift of the machine shows
 as a difference between the two plain series.  The masked scan reads 2 more bytes per block of 16 rows.
+
+--identities M measures the identity search (rfd_gallery_search_identities_device) against the plain one on the same gallery in
+the same process: --repeats windows of plain searches, then the rows are labelled with M identities as row % M (an identity's
+rows lie M apart, in every wave's walk) and the identity search is timed, then with M contiguous runs of rows (an identity's rows
+arrive together), then the plain windows again; the spread of the two plain series is the yardstick.  The identity scan reads
+4 bytes of identity for a key that passes a list's filter and nothing else beyond the plain scan's bytes.
 Prints one JSON line per size."""
 import argparse
 import json
@@ -35,9 +41,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--rows", type=int, nargs="*", default=[100_000, 1_000_000])
     ap.add_argument("--removed", type=float, default=0.0, help="share of the rows to remove at random before timing the masked scan")
-    ap.add_argument("--repeats", type=int, default=5, help="timed windows per series of a --removed run")
+    ap.add_argument("--identities", type=int, default=0, help="label the rows with this many identities and time the identity search")
+    ap.add_argument("--repeats", type=int, default=5, help="timed windows per series of a --removed or --identities run")
     args = ap.parse_args()
-    assert 0.0 <= args.removed < 1.0
+    assert 0.0 <= args.removed < 1.0 and args.identities >= 0
     import torch
     import rfd_hip
     det = rfd_hip.RetinaFaceDetection(image_size=(640, 640), max_batch_size=1, max_det=16)
@@ -109,6 +116,44 @@ def main():
                       "plain_again": stats(plain_again), "plain_spread_ms": round(spread, 4),
                       "masked_minus_plain_median_ms": round(float(np.median(with_mask) - np.median(plain + plain_again)), 4),
                       "masked_extra_bytes": (rows + 15) // 16 * 2}
+        if args.identities > 0:
+            import numpy as np
+            m_ids = min(args.identities, rows)
+            d_i = torch.zeros(NQ, K, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()
+
+            def ours_ids(n):
+                for _ in range(n):
+                    gal.search_identities_device(q.data_ptr(), NQ, K, float("-inf"), d_s.data_ptr(), d_r.data_ptr(), d_i.data_ptr(), async_=True)
+                det.sync()
+
+            def id_window():
+                t0 = time.perf_counter()
+                ours_ids(args.steps)
+                return (time.perf_counter() - t0) * 1e3 / args.steps
+
+            stats = lambda w: {"windows_ms": w, "median_ms": round(float(np.median(w)), 4), "min_ms": min(w), "max_ms": max(w)}
+            plain = [round(window(), 4) for _ in range(args.repeats)]
+            every = np.arange(rows)
+            series = {}
+            for name, ids in (("row_mod_m", every % m_ids), ("runs", every * m_ids // rows)):
+                gal.set_identities(every, ids)
+                det.sync()
+                assert gal.labelled() == rows
+                ours_ids(args.warmup)                  # the identity instantiation's first launches
+                series[name] = [round(id_window(), 4) for _ in range(args.repeats)]
+                got_r, got_i = d_r.cpu().numpy(), d_i.cpu().numpy()
+                assert (got_r >= 0).all() or m_ids < K
+                assert all(len(set(row[row >= 0].tolist())) == int((row >= 0).sum()) for row in got_i)   # k distinct identities per query
+                assert (got_i[got_r >= 0] == ids[got_r[got_r >= 0]]).all()
+            ours(args.warmup)
+            plain_again = [round(window(), 4) for _ in range(args.repeats)]
+            both = plain + plain_again
+            masked.update({"identities": m_ids, "repeats": args.repeats, "plain": stats(plain), "identity_row_mod_m": stats(series["row_mod_m"]),
+                           "identity_runs": stats(series["runs"]), "plain_again": stats(plain_again), "plain_spread_ms": round(max(both) - min(both), 4),
+                           "row_mod_m_minus_plain_median_ms": round(float(np.median(series["row_mod_m"]) - np.median(both)), 4),
+                           "runs_minus_plain_median_ms": round(float(np.median(series["runs"]) - np.median(both)), 4),
+                           "identity_array_bytes": rows * 4})
         theirs(args.warmup)
         t0 = time.perf_counter()
         ref = theirs(args.steps)
