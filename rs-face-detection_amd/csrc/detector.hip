@@ -2,6 +2,8 @@
 // `RetinaFaceDetection` (src/pipeline/module/face_detection.rs:19-513) driving the HIP kernels, and
 // the C ABI of include/rfd.h on top of it.  (The reference's host language, Rust, has no toolchain
 // in this image; INTEGRATION.md shows the `extern "C"` facade that keeps its `call` signature.)
+// Two stateful layers of the ABI have files of their own: the JPEG decode (jpeg_host.hip) and the face gallery
+// (gallery_host.hip), which reaches the context through the two accessors of gallery_host.h alone.
 #include <dlfcn.h>
 #include <stdarg.h>
 #include <stdlib.h>
@@ -15,7 +17,7 @@
 #include <thread>
 #include <vector>
 
-#include "gallery_file.h"
+#include "gallery_host.h"
 #include "host_resources.h"
 #include "jpeg_host.h"
 #include "network.h"
@@ -249,39 +251,9 @@ struct rfd_ctx {
     }
 };
 
-// A face gallery: the enrolled embeddings of one context in HBM (rfd.h, "gallery").  Next to the context, which lends it its
-// device and stream; the caller destroys it first.
-struct rfd_gallery {
-    rfd_ctx *ctx = nullptr;
-    int dim = 0, capacity = 0, rows = 0;
-    int groups_max = 0; // workgroups of a search, from the CU count: the workspace holds their lists
-    DevBuf store;       // ceil(capacity / 16) blocks of 16 rows, bf16, fragment-major (gallery_offset)
-    DevBuf ws;          // [groups_max][32][RFD_GALLERY_MAX_K] keys
-    // host forms, allocated by the first of them: a page-locked buffer and its device twin
-    static constexpr size_t kStageBytes = 4u << 20;
-    DevBuf stage;
-    Pinned<char> pin;
-    // Liveness (rfd.h, "remove and replace").  The host's words are the truth: one per block of 16 rows enrolled so far, bit i =
-    // row 16 b + i is live.  Their device twin is read by the masked scan only, which runs while removed > 0, so it is brought
-    // up to date lazily: it is right for rows [0, live_synced), the rows added since are all live, and gallery_live_sync sets
-    // their bits before the twin is next written or read.  A gallery that never removes a row never touches it.
-    std::vector<uint16_t> live_words;
-    int removed = 0, live_synced = 0;
-    DevBuf live; // ceil(capacity / 16) words, zero beyond live_synced
-    // row lists of remove / replace travel through a ring of page-locked slots (like the context's frame descriptors), so the
-    // calls enqueue without waiting for the stream; allocated by the first such call.  A slot: rows | blocks | their new words |
-    // the rows whose identity a remove clears; for rfd_gallery_set_identities: rows | identities.
-    static constexpr int kRing = 4, kEditRows = 1024, kEditInts = 4 * kEditRows;
-    PinnedRing<kRing> edit_ring;
-    DevBuf edit;
-    // Identities (rfd.h, "identities").  The device array (one int32 per row, in whole blocks of 16; -1 = unlabelled) is
-    // allocated by the first rfd_gallery_set_identities; until then no call touches it and every search runs without it.  The
-    // host copy is the truth for _get_identities / _identities: it covers rows [0, ident.size()), the rows behind it are
-    // unlabelled.
-    DevBuf ids;
-    std::vector<int32_t> ident;
-    int labelled = 0; // live rows with an identity >= 0
-};
+// what a face gallery asks of its context (gallery_host.h)
+hipStream_t rfd::ctx_stream(const rfd_ctx *c) { return c->stream; }
+int rfd::ctx_device(const rfd_ctx *c) { return c->cfg.device_id; }
 
 namespace {
 
@@ -2282,582 +2254,6 @@ void _nms(int32_t *keep, int *num_out, float *boxes, int boxes_num, int boxes_di
         if (rfd_create(&cfg, &g_nms_ctx[device_id]) != RFD_OK) { g_nms_ctx[device_id] = nullptr; return; }
     }
     if (rfd_nms_sorted(g_nms_ctx[device_id], keep, num_out, boxes, boxes_num, boxes_dim, thresh) != RFD_OK) *num_out = -1;
-}
-
-// ---- face gallery: enrol embeddings, search the k best rows (rfd.h; kernels_gallery.hip) ----
-static int gallery_host_stage(rfd_gallery *g)
-{
-    if (g->pin) return RFD_OK;
-    RFD_TRY(g->stage.reserve(rfd_gallery::kStageBytes));
-    return g->pin.alloc(rfd_gallery::kStageBytes);
-}
-
-// The host forms move rows of `dim` floats through the one staging buffer, in chunks that fit it; a chunk has left the buffer
-// (the stream is drained) before the next one enters.  With `src`, rows [first, first + count) of it are copied in before
-// `op(first, count)` is enqueued; with `dst`, op fills the device buffer and the rows are copied out behind it.
-static int gallery_staged(rfd_gallery *g, const float *src, float *dst, int n, const std::function<int(int, int)> &op)
-{
-    RFD_TRY(gallery_host_stage(g));
-    const int chunk = (int)(rfd_gallery::kStageBytes / ((size_t)g->dim * sizeof(float)));
-    for (int i = 0; i < n; i += chunk) {
-        const int m = std::min(chunk, n - i);
-        const size_t bytes = (size_t)m * g->dim * sizeof(float);
-        if (src) {
-            memcpy(g->pin, src + (size_t)i * g->dim, bytes);
-            RFD_HIP(hipMemcpyAsync(g->stage.p, g->pin, bytes, hipMemcpyHostToDevice, g->ctx->stream));
-        }
-        RFD_TRY(op(i, m));
-        if (dst) RFD_HIP(hipMemcpyAsync(g->pin, g->stage.p, bytes, hipMemcpyDeviceToHost, g->ctx->stream));
-        RFD_HIP(hipStreamSynchronize(g->ctx->stream));
-        if (dst) memcpy(dst + (size_t)i * g->dim, g->pin, bytes);
-    }
-    return RFD_OK;
-}
-
-// first non-finite value of x [n][dim], named in the error message (`what` = "row" / "query")
-static int gallery_check_finite(const float *x, int n, int dim, const char *what)
-{
-    for (int i = 0; i < n; ++i)
-        for (int d = 0; d < dim; ++d) {
-            uint32_t u;
-            memcpy(&u, &x[(size_t)i * dim + d], 4);
-            if ((u & 0x7f800000u) == 0x7f800000u) {
-                set_error("invalid argument: %s %d holds a non-finite value (%g) at element %d", what, i, (double)x[(size_t)i * dim + d], d);
-                return RFD_ERR_INVALID_ARG;
-            }
-        }
-    return RFD_OK;
-}
-
-static int gallery_check_k(int k)
-{
-    RFD_CHECK_ARG(k >= 1, "k < 1");
-    if (k > RFD_GALLERY_MAX_K) { set_error("k = %d exceeds RFD_GALLERY_MAX_K (%d)", k, RFD_GALLERY_MAX_K); return RFD_ERR_CAPACITY; }
-    return RFD_OK;
-}
-
-static int gallery_check_room(const rfd_gallery *g, int n)
-{
-    if (n > g->capacity - g->rows) {
-        set_error("the gallery holds %d of %d rows: %d more do not fit", g->rows, g->capacity, n);
-        return RFD_ERR_CAPACITY;
-    }
-    return RFD_OK;
-}
-
-// the host's live words: rows [row0, row1) become live (an add; the words grow with the rows)
-static void gallery_mark_live(rfd_gallery *g, int row0, int row1)
-{
-    g->live_words.resize((size_t)ceil_div(row1, 16), 0);
-    for (int r = row0; r < row1;) {
-        const int b = r >> 4, end = std::min(row1, (b + 1) * 16);
-        g->live_words[b] |= (uint16_t)((0xffffu >> (16 - (end - b * 16))) & (0xffffu << (r & 15)));
-        r = end;
-    }
-}
-
-// brings the device's live words up to the rows added since they were last written or read
-static int gallery_live_sync(rfd_gallery *g)
-{
-    if (g->live_synced < g->rows) RFD_TRY(launch_gallery_live_range((uint16_t *)g->live.p, g->live_synced, g->rows, g->ctx->stream));
-    g->live_synced = g->rows;
-    return RFD_OK;
-}
-
-// what a search passes for `live`: null while no row is removed (the scan without the mask), else the device's words
-static int gallery_search_mask(rfd_gallery *g, const uint16_t **live)
-{
-    *live = nullptr;
-    if (g->removed == 0) return RFD_OK;
-    RFD_TRY(gallery_live_sync(g));
-    *live = (const uint16_t *)g->live.p;
-    return RFD_OK;
-}
-
-static int gallery_check_rows(const rfd_gallery *g, const int32_t *rows, int n)
-{
-    for (int i = 0; i < n; ++i)
-        if (rows[i] < 0 || rows[i] >= g->rows) {
-            set_error("invalid argument: rows[%d] = %d is not in [0, %d)", i, rows[i], g->rows);
-            return RFD_ERR_INVALID_ARG;
-        }
-    return RFD_OK;
-}
-
-// the ring of page-locked list slots and their device twin, allocated by the first call that sends a list
-static int gallery_edit_lists(rfd_gallery *g)
-{
-    RFD_TRY(g->edit_ring.ensure((size_t)rfd_gallery::kEditInts * sizeof(int32_t)));
-    return g->edit.reserve((size_t)rfd_gallery::kEditInts * sizeof(int32_t));
-}
-
-// Rows `rows` (host, checked) take bf16(emb[i]) and become live (emb: device [n][dim]), or are erased and become removed (emb
-// null).  Enqueued in chunks of kEditRows, each through the next ring slot; no synchronisation with the stream.
-static int gallery_edit(rfd_gallery *g, const int32_t *rows, const float *emb, int n)
-{
-    constexpr int kEdit = rfd_gallery::kEditRows;
-    RFD_TRY(gallery_edit_lists(g)); // first call on this gallery
-    RFD_TRY(gallery_live_sync(g));
-    for (int at = 0; at < n; at += kEdit) {
-        const int m = std::min(kEdit, n - at);
-        int32_t *list;
-        RFD_TRY(g->edit_ring.acquire(&list));
-        int32_t *blk = list + m;
-        int32_t unlabel[kEdit]; // a remove: the rows that lose an identity >= 0; each row once, its second mention finds it removed
-        int nu = 0;
-        for (int i = 0; i < m; ++i) {
-            const int r = rows[at + i];
-            list[i] = r;
-            blk[i] = r >> 4;
-            uint16_t &w = g->live_words[r >> 4];
-            const uint16_t bit = (uint16_t)(1u << (r & 15));
-            if (emb && !(w & bit)) { w |= bit; --g->removed; }
-            if (!emb && (w & bit)) {
-                w &= (uint16_t)~bit;
-                ++g->removed;
-                if ((size_t)r < g->ident.size() && g->ident[r] >= 0) { g->ident[r] = RFD_GALLERY_NO_IDENTITY; --g->labelled; unlabel[nu++] = r; }
-            }
-        }
-        std::sort(blk, blk + m);
-        const int nb = (int)(std::unique(blk, blk + m) - blk);
-        int32_t *word = blk + nb;
-        for (int j = 0; j < nb; ++j) word[j] = g->live_words[blk[j]];
-        std::copy(unlabel, unlabel + nu, word + nb); // nu = 0 unless identities were set: the copy below is then what it always was
-        RFD_HIP(hipMemcpyAsync(g->edit.p, list, (size_t)(m + 2 * nb + nu) * sizeof(int32_t), hipMemcpyHostToDevice, g->ctx->stream));
-        RFD_TRY(g->edit_ring.record(g->ctx->stream));
-        const int32_t *d = (const int32_t *)g->edit.p;
-        RFD_TRY(launch_gallery_put(emb ? emb + (size_t)at * g->dim : nullptr, d, m, g->dim, (bf16_t *)g->store.p, d + m, d + m + nb, nb, (uint16_t *)g->live.p,
-                                   g->ctx->stream));
-        if (nu > 0) RFD_TRY(launch_gallery_set_identities((int32_t *)g->ids.p, d + m + 2 * nb, nullptr, nu, g->ctx->stream));
-    }
-    return RFD_OK;
-}
-
-static int gallery_check_distinct(const int32_t *rows, int n)
-{
-    std::vector<int32_t> sorted(rows, rows + n);
-    std::sort(sorted.begin(), sorted.end());
-    for (int i = 1; i < n; ++i)
-        if (sorted[i] == sorted[i - 1]) {
-            set_error("invalid argument: row %d is listed more than once", sorted[i]);
-            return RFD_ERR_INVALID_ARG;
-        }
-    return RFD_OK;
-}
-
-int64_t rfd_debug_gallery_offset(int dim, int row, int d)
-{
-    if (dim < 32 || dim > 1024 || dim % 32 != 0 || row < 0 || d < 0 || d >= dim) return -1;
-    return (int64_t)gallery_offset(dim, row, d);
-}
-
-int rfd_gallery_create(rfd_ctx *c, int dim, int capacity, rfd_gallery **out)
-{
-    RFD_CHECK_ARG(c && out, "null argument");
-    *out = nullptr;
-    RFD_CHECK_ARG(dim >= 32 && dim <= 1024 && dim % 32 == 0, "dim must be a multiple of 32 in 32..1024");
-    RFD_CHECK_ARG(capacity >= 1 && capacity <= (1 << 30), "capacity out of range");
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    std::unique_ptr<rfd_gallery> g(new rfd_gallery()); // an early return frees whatever was built so far
-    g->ctx = c; g->dim = dim; g->capacity = capacity;
-    g->groups_max = 2 * device_cus(); // two workgroups of four waves per CU: what the scan's registers admit
-    const size_t bytes = (size_t)ceil_div(capacity, 16) * 16 * dim * sizeof(bf16_t);
-    RFD_TRY(g->store.reserve(bytes));
-    RFD_TRY(g->ws.reserve((size_t)g->groups_max * kGalleryMaxQueries * RFD_GALLERY_MAX_K * sizeof(uint2)));
-    const size_t live_bytes = (size_t)ceil_div(ceil_div(capacity, 16), 2) * 2 * sizeof(uint16_t); // the masked scan loads aligned pairs of words
-    RFD_TRY(g->live.reserve(live_bytes));
-    // rows that were never added read as zeros (the tail of the last block is scored, then masked by its row index)
-    if (hipMemsetAsync(g->store.p, 0, bytes, c->stream) != hipSuccess || hipMemsetAsync(g->live.p, 0, live_bytes, c->stream) != hipSuccess) {
-        set_error("hipMemsetAsync of the gallery failed");
-        (void)hipStreamSynchronize(c->stream); // a fill that was enqueued has run before its buffer is freed
-        return RFD_ERR_HIP;
-    }
-    *out = g.release();
-    return RFD_OK;
-}
-
-void rfd_gallery_destroy(rfd_gallery *g)
-{
-    if (!g) return;
-    (void)hipSetDevice(g->ctx->cfg.device_id);
-    (void)hipStreamSynchronize(g->ctx->stream);
-    delete g;
-}
-
-int rfd_gallery_size(const rfd_gallery *g, int *rows, int *capacity, int *dim)
-{
-    RFD_CHECK_ARG(g, "gallery is null");
-    if (rows) *rows = g->rows;
-    if (capacity) *capacity = g->capacity;
-    if (dim) *dim = g->dim;
-    return RFD_OK;
-}
-
-int rfd_gallery_clear(rfd_gallery *g)
-{
-    RFD_CHECK_ARG(g, "gallery is null");
-    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
-    if (g->rows > 0) RFD_HIP(hipMemsetAsync(g->store.p, 0, (size_t)ceil_div(g->rows, 16) * 16 * g->dim * sizeof(bf16_t), g->ctx->stream));
-    if (g->live_synced > 0) RFD_HIP(hipMemsetAsync(g->live.p, 0, (size_t)ceil_div(g->live_synced, 16) * sizeof(uint16_t), g->ctx->stream));
-    if (g->ids.p && g->rows > 0) RFD_HIP(hipMemsetAsync(g->ids.p, 0xff, (size_t)g->rows * sizeof(int32_t), g->ctx->stream)); // all -1 again
-    g->rows = g->removed = g->live_synced = g->labelled = 0;
-    g->live_words.clear();
-    g->ident.clear();
-    return RFD_OK;
-}
-
-int rfd_gallery_add_device(rfd_gallery *g, const float *emb, int n, int *first_row)
-{
-    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
-    if (first_row) *first_row = g->rows;
-    if (n == 0) return RFD_OK;
-    RFD_CHECK_ARG(emb && (uintptr_t)emb % 16 == 0, "emb is null or not 16-byte aligned");
-    RFD_TRY(gallery_check_room(g, n));
-    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
-    RFD_TRY(launch_gallery_add(emb, n, g->dim, g->rows, (bf16_t *)g->store.p, g->ctx->stream));
-    gallery_mark_live(g, g->rows, g->rows + n);
-    g->rows += n;
-    return RFD_OK;
-}
-
-int rfd_gallery_add(rfd_gallery *g, const float *emb, int n, int *first_row)
-{
-    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
-    if (first_row) *first_row = g->rows;
-    if (n == 0) return RFD_OK;
-    RFD_CHECK_ARG(emb, "emb is null");
-    RFD_TRY(gallery_check_room(g, n));
-    RFD_TRY(gallery_check_finite(emb, n, g->dim, "row"));
-    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
-    RFD_TRY(gallery_staged(g, emb, nullptr, n, [&](int i, int m) {
-        return launch_gallery_add((const float *)g->stage.p, m, g->dim, g->rows + i, (bf16_t *)g->store.p, g->ctx->stream);
-    }));
-    gallery_mark_live(g, g->rows, g->rows + n);
-    g->rows += n;
-    return RFD_OK;
-}
-
-int rfd_gallery_get_rows(rfd_gallery *g, int row0, int n, float *out)
-{
-    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
-    if (n == 0) return RFD_OK;
-    RFD_CHECK_ARG(out, "out is null");
-    RFD_CHECK_ARG(row0 >= 0 && n <= g->rows - row0, "rows [row0, row0 + n) are not all in the gallery");
-    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
-    return gallery_staged(g, nullptr, out, n, [&](int i, int m) {
-        return launch_gallery_get((const bf16_t *)g->store.p, row0 + i, m, g->dim, (float *)g->stage.p, g->ctx->stream);
-    });
-}
-
-int rfd_gallery_search_device(rfd_gallery *g, const float *queries, int n, int k, float *scores, int32_t *rows, int async)
-{
-    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
-    RFD_TRY(gallery_check_k(k));
-    if (n == 0) return RFD_OK;
-    RFD_CHECK_ARG(queries && scores && rows, "null argument");
-    RFD_CHECK_ARG((uintptr_t)queries % 16 == 0, "queries are not 16-byte aligned");
-    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
-    const uint16_t *live = nullptr;
-    RFD_TRY(gallery_search_mask(g, &live));
-    for (int i = 0; i < n; i += kGalleryMaxQueries) // one pass over the gallery per group of queries; the passes share the workspace in stream order
-        RFD_TRY(launch_gallery_search((const bf16_t *)g->store.p, live, g->rows, g->dim, queries + (size_t)i * g->dim, std::min(kGalleryMaxQueries, n - i), k,
-                                      (uint2 *)g->ws.p, g->groups_max, scores + (size_t)i * k, rows + (size_t)i * k, g->ctx->stream));
-    if (!async) RFD_HIP(hipStreamSynchronize(g->ctx->stream));
-    return RFD_OK;
-}
-
-int rfd_gallery_search(rfd_gallery *g, const float *queries, int n, int k, float *scores, int32_t *rows)
-{
-    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
-    RFD_TRY(gallery_check_k(k));
-    if (n == 0) return RFD_OK;
-    RFD_CHECK_ARG(queries && scores && rows, "null argument");
-    RFD_TRY(gallery_check_finite(queries, n, g->dim, "query"));
-    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
-    RFD_TRY(gallery_host_stage(g));
-    const uint16_t *live = nullptr;
-    RFD_TRY(gallery_search_mask(g, &live));
-    // the staging buffer holds one group: its queries, then its scores and rows
-    const size_t qcap = (size_t)kGalleryMaxQueries * g->dim * sizeof(float), rcap = (size_t)kGalleryMaxQueries * RFD_GALLERY_MAX_K * sizeof(float);
-    float *d_q = (float *)g->stage.p, *d_s = (float *)((char *)g->stage.p + qcap);
-    int32_t *d_r = (int32_t *)((char *)g->stage.p + qcap + rcap);
-    char *h = (char *)g->pin;
-    for (int i = 0; i < n; i += kGalleryMaxQueries) {
-        const int m = std::min(kGalleryMaxQueries, n - i);
-        const size_t qbytes = (size_t)m * g->dim * sizeof(float), rbytes = (size_t)m * k * sizeof(float);
-        memcpy(h, queries + (size_t)i * g->dim, qbytes);
-        RFD_HIP(hipMemcpyAsync(d_q, h, qbytes, hipMemcpyHostToDevice, g->ctx->stream));
-        RFD_TRY(launch_gallery_search((const bf16_t *)g->store.p, live, g->rows, g->dim, d_q, m, k, (uint2 *)g->ws.p, g->groups_max, d_s, d_r, g->ctx->stream));
-        RFD_HIP(hipMemcpyAsync(h + qcap, d_s, rbytes, hipMemcpyDeviceToHost, g->ctx->stream));
-        RFD_HIP(hipMemcpyAsync(h + qcap + rcap, d_r, rbytes, hipMemcpyDeviceToHost, g->ctx->stream));
-        RFD_HIP(hipStreamSynchronize(g->ctx->stream));
-        memcpy(scores + (size_t)i * k, h + qcap, rbytes);
-        memcpy(rows + (size_t)i * k, h + qcap + rcap, rbytes);
-    }
-    return RFD_OK;
-}
-
-int rfd_gallery_remove(rfd_gallery *g, const int32_t *rows, int n)
-{
-    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
-    if (n == 0) return RFD_OK;
-    RFD_CHECK_ARG(rows, "rows is null");
-    RFD_TRY(gallery_check_rows(g, rows, n));
-    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
-    return gallery_edit(g, rows, nullptr, n);
-}
-
-int rfd_gallery_replace_device(rfd_gallery *g, const int32_t *rows, const float *emb, int n)
-{
-    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
-    if (n == 0) return RFD_OK;
-    RFD_CHECK_ARG(rows, "rows is null");
-    RFD_CHECK_ARG(emb && (uintptr_t)emb % 16 == 0, "emb is null or not 16-byte aligned");
-    RFD_TRY(gallery_check_rows(g, rows, n));
-    RFD_TRY(gallery_check_distinct(rows, n));
-    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
-    return gallery_edit(g, rows, emb, n);
-}
-
-int rfd_gallery_replace(rfd_gallery *g, const int32_t *rows, const float *emb, int n)
-{
-    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
-    if (n == 0) return RFD_OK;
-    RFD_CHECK_ARG(rows && emb, "rows or emb is null");
-    RFD_TRY(gallery_check_rows(g, rows, n));
-    RFD_TRY(gallery_check_distinct(rows, n));
-    RFD_TRY(gallery_check_finite(emb, n, g->dim, "row"));
-    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
-    return gallery_staged(g, emb, nullptr, n, [&](int i, int m) { return gallery_edit(g, rows + i, (const float *)g->stage.p, m); });
-}
-
-int rfd_gallery_live(const rfd_gallery *g, int *live_rows)
-{
-    RFD_CHECK_ARG(g && live_rows, "null argument");
-    *live_rows = g->rows - g->removed;
-    return RFD_OK;
-}
-
-int rfd_gallery_removed(const rfd_gallery *g, int32_t *out, int cap, int *count)
-{
-    RFD_CHECK_ARG(g && count && cap >= 0 && (out || cap == 0), "null argument or cap < 0");
-    *count = g->removed;
-    int at = 0;
-    for (int r = 0; r < g->rows && at < cap && at < g->removed; ++r)
-        if (!((g->live_words[r >> 4] >> (r & 15)) & 1)) out[at++] = r;
-    return RFD_OK;
-}
-
-// ---- identities (rfd.h, "identities") ----
-int rfd_gallery_set_identities(rfd_gallery *g, const int32_t *rows, const int32_t *ids, int n)
-{
-    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
-    if (n == 0) return RFD_OK;
-    RFD_CHECK_ARG(rows && ids, "rows or ids is null");
-    RFD_TRY(gallery_check_rows(g, rows, n));
-    for (int i = 0; i < n; ++i) {
-        if (!((g->live_words[rows[i] >> 4] >> (rows[i] & 15)) & 1)) {
-            set_error("invalid argument: rows[%d] = %d is a removed row", i, rows[i]);
-            return RFD_ERR_INVALID_ARG;
-        }
-        if (ids[i] < RFD_GALLERY_NO_IDENTITY) {
-            set_error("invalid argument: ids[%d] = %d is neither an identity (>= 0) nor RFD_GALLERY_NO_IDENTITY", i, ids[i]);
-            return RFD_ERR_INVALID_ARG;
-        }
-    }
-    RFD_TRY(gallery_check_distinct(rows, n));
-    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
-    RFD_TRY(gallery_edit_lists(g));
-    if (!g->ids.p) { // the first labels of this gallery: the array, all unlabelled, in stream order ahead of every use
-        const size_t bytes = (size_t)ceil_div(g->capacity, 16) * 16 * sizeof(int32_t); // whole blocks: the scan reads a block's 16 words
-        RFD_TRY(g->ids.reserve(bytes));
-        if (hipMemsetAsync(g->ids.p, 0xff, bytes, g->ctx->stream) != hipSuccess) {
-            set_error("hipMemsetAsync of the gallery's identities failed");
-            (void)hipStreamSynchronize(g->ctx->stream);
-            g->ids.release();
-            return RFD_ERR_HIP;
-        }
-    }
-    if (g->ident.size() < (size_t)g->rows) g->ident.resize((size_t)g->rows, RFD_GALLERY_NO_IDENTITY);
-    constexpr int kEdit = rfd_gallery::kEditRows;
-    for (int at = 0; at < n; at += kEdit) {
-        const int m = std::min(kEdit, n - at);
-        int32_t *list;
-        RFD_TRY(g->edit_ring.acquire(&list));
-        for (int i = 0; i < m; ++i) {
-            int32_t &have = g->ident[rows[at + i]];
-            g->labelled += (ids[at + i] >= 0) - (have >= 0);
-            have = list[m + i] = ids[at + i];
-            list[i] = rows[at + i];
-        }
-        RFD_HIP(hipMemcpyAsync(g->edit.p, list, (size_t)2 * m * sizeof(int32_t), hipMemcpyHostToDevice, g->ctx->stream));
-        RFD_TRY(g->edit_ring.record(g->ctx->stream));
-        const int32_t *d = (const int32_t *)g->edit.p;
-        RFD_TRY(launch_gallery_set_identities((int32_t *)g->ids.p, d, d + m, m, g->ctx->stream));
-    }
-    return RFD_OK;
-}
-
-int rfd_gallery_get_identities(const rfd_gallery *g, int row0, int n, int32_t *out)
-{
-    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
-    if (n == 0) return RFD_OK;
-    RFD_CHECK_ARG(out, "out is null");
-    RFD_CHECK_ARG(row0 >= 0 && n <= g->rows - row0, "rows [row0, row0 + n) are not all in the gallery");
-    for (int i = 0; i < n; ++i) out[i] = (size_t)(row0 + i) < g->ident.size() ? g->ident[row0 + i] : RFD_GALLERY_NO_IDENTITY;
-    return RFD_OK;
-}
-
-int rfd_gallery_identities(const rfd_gallery *g, int *labelled_rows)
-{
-    RFD_CHECK_ARG(g && labelled_rows, "null argument");
-    *labelled_rows = g->labelled;
-    return RFD_OK;
-}
-
-static int gallery_check_min_score(float min_score)
-{
-    RFD_CHECK_ARG(min_score == min_score, "min_score is NaN");
-    return RFD_OK;
-}
-
-int rfd_gallery_search_identities_device(rfd_gallery *g, const float *queries, int n, int k, float min_score, float *scores, int32_t *rows, int32_t *ids,
-                                         int async)
-{
-    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
-    RFD_TRY(gallery_check_k(k));
-    RFD_TRY(gallery_check_min_score(min_score));
-    if (n == 0) return RFD_OK;
-    RFD_CHECK_ARG(queries && scores && rows && ids, "null argument");
-    RFD_CHECK_ARG((uintptr_t)queries % 16 == 0, "queries are not 16-byte aligned");
-    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
-    const uint16_t *live = nullptr;
-    RFD_TRY(gallery_search_mask(g, &live));
-    for (int i = 0; i < n; i += kGalleryMaxQueries)
-        RFD_TRY(launch_gallery_search_identities((const bf16_t *)g->store.p, live, (const int32_t *)g->ids.p, g->rows, g->dim, queries + (size_t)i * g->dim,
-                                                 std::min(kGalleryMaxQueries, n - i), k, min_score, (uint2 *)g->ws.p, g->groups_max, scores + (size_t)i * k,
-                                                 rows + (size_t)i * k, ids + (size_t)i * k, g->ctx->stream));
-    if (!async) RFD_HIP(hipStreamSynchronize(g->ctx->stream));
-    return RFD_OK;
-}
-
-int rfd_gallery_search_identities(rfd_gallery *g, const float *queries, int n, int k, float min_score, float *scores, int32_t *rows, int32_t *ids)
-{
-    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
-    RFD_TRY(gallery_check_k(k));
-    RFD_TRY(gallery_check_min_score(min_score));
-    if (n == 0) return RFD_OK;
-    RFD_CHECK_ARG(queries && scores && rows && ids, "null argument");
-    RFD_TRY(gallery_check_finite(queries, n, g->dim, "query"));
-    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
-    RFD_TRY(gallery_host_stage(g));
-    const uint16_t *live = nullptr;
-    RFD_TRY(gallery_search_mask(g, &live));
-    // the staging buffer holds one group: its queries, then its scores, rows and identities
-    const size_t qcap = (size_t)kGalleryMaxQueries * g->dim * sizeof(float), rcap = (size_t)kGalleryMaxQueries * RFD_GALLERY_MAX_K * sizeof(float);
-    float *d_q = (float *)g->stage.p, *d_s = (float *)((char *)g->stage.p + qcap);
-    int32_t *d_r = (int32_t *)((char *)g->stage.p + qcap + rcap), *d_i = (int32_t *)((char *)g->stage.p + qcap + 2 * rcap);
-    char *h = (char *)g->pin;
-    for (int i = 0; i < n; i += kGalleryMaxQueries) {
-        const int m = std::min(kGalleryMaxQueries, n - i);
-        const size_t qbytes = (size_t)m * g->dim * sizeof(float), rbytes = (size_t)m * k * sizeof(float);
-        memcpy(h, queries + (size_t)i * g->dim, qbytes);
-        RFD_HIP(hipMemcpyAsync(d_q, h, qbytes, hipMemcpyHostToDevice, g->ctx->stream));
-        RFD_TRY(launch_gallery_search_identities((const bf16_t *)g->store.p, live, (const int32_t *)g->ids.p, g->rows, g->dim, d_q, m, k, min_score,
-                                                 (uint2 *)g->ws.p, g->groups_max, d_s, d_r, d_i, g->ctx->stream));
-        RFD_HIP(hipMemcpyAsync(h + qcap, d_s, 3 * rcap, hipMemcpyDeviceToHost, g->ctx->stream)); // the three results lie side by side
-        RFD_HIP(hipStreamSynchronize(g->ctx->stream));
-        memcpy(scores + (size_t)i * k, h + qcap, rbytes);
-        memcpy(rows + (size_t)i * k, h + qcap + rcap, rbytes);
-        memcpy(ids + (size_t)i * k, h + qcap + 2 * rcap, rbytes);
-    }
-    return RFD_OK;
-}
-
-int rfd_gallery_file_info(const char *path, int *dim, int *rows, int *live)
-{
-    RFD_CHECK_ARG(path, "path is null");
-    char msg[256];
-    const int st = gallery_file_info(path, dim, rows, live, msg, sizeof msg);
-    if (st != RFD_OK) set_error("%s", msg);
-    return st;
-}
-
-int rfd_gallery_save(rfd_gallery *g, const char *path)
-{
-    RFD_CHECK_ARG(g && path, "null argument");
-    RFD_HIP(hipSetDevice(g->ctx->cfg.device_id));
-    RFD_TRY(gallery_host_stage(g));
-    RFD_HIP(hipStreamSynchronize(g->ctx->stream));
-    const std::string tmp = std::string(path) + ".tmp";
-    FILE *f = fopen(tmp.c_str(), "wb");
-    if (!f) { set_error("cannot open %s for writing", tmp.c_str()); return RFD_ERR_IO; }
-    std::vector<unsigned char> bits((size_t)ceil_div(g->rows, 8), 0);
-    for (size_t i = 0; i < bits.size(); ++i) bits[i] = (unsigned char)(g->live_words[i >> 1] >> (8 * (i & 1)));
-    bool ok = gallery_file_write_head(f, g->dim, g->rows, bits.data());
-    int st = RFD_OK;
-    const int chunk = (int)(rfd_gallery::kStageBytes / ((size_t)g->dim * sizeof(bf16_t)));
-    for (int i = 0; ok && st == RFD_OK && i < g->rows; i += chunk) {
-        const int m = std::min(chunk, g->rows - i);
-        const size_t bytes = (size_t)m * g->dim * sizeof(bf16_t);
-        st = launch_gallery_export((const bf16_t *)g->store.p, i, m, g->dim, (bf16_t *)g->stage.p, g->ctx->stream);
-        if (st == RFD_OK && (hipMemcpyAsync(g->pin, g->stage.p, bytes, hipMemcpyDeviceToHost, g->ctx->stream) != hipSuccess ||
-                             hipStreamSynchronize(g->ctx->stream) != hipSuccess)) {
-            set_error("copying rows %d..%d of the gallery to the host failed", i, i + m - 1);
-            st = RFD_ERR_HIP;
-        }
-        if (st == RFD_OK) ok = gallery_file_write_values(f, (const uint16_t *)g->pin.p, (size_t)m * g->dim);
-    }
-    ok = (fclose(f) == 0) && ok;
-    if (st == RFD_OK && !ok) { set_error("short write to %s", tmp.c_str()); st = RFD_ERR_IO; }
-    if (st == RFD_OK && rename(tmp.c_str(), path) != 0) { set_error("cannot rename %s to %s", tmp.c_str(), path); st = RFD_ERR_IO; }
-    if (st != RFD_OK) (void)remove(tmp.c_str());
-    return st;
-}
-
-int rfd_gallery_load(rfd_ctx *c, const char *path, int capacity, rfd_gallery **out)
-{
-    RFD_CHECK_ARG(c && path && out && capacity >= 0, "null argument or capacity < 0");
-    *out = nullptr;
-    RFD_TRY(rfd_gallery_file_info(path, nullptr, nullptr, nullptr)); // the whole validation, before anything is allocated
-    GalleryFileReader r;
-    if (int st = r.open(path)) { set_error("%s", r.msg); return st; }
-    if (capacity == 0) capacity = std::max(r.rows, 1);
-    if (capacity < r.rows) { set_error("%s holds %d rows: a capacity of %d does not fit them", path, r.rows, capacity); return RFD_ERR_CAPACITY; }
-    rfd_gallery *g = nullptr;
-    RFD_TRY(rfd_gallery_create(c, r.dim, capacity, &g));
-    int st = gallery_host_stage(g);
-    const int chunk = (int)(rfd_gallery::kStageBytes / ((size_t)r.dim * sizeof(bf16_t)));
-    uint16_t *h = (uint16_t *)g->pin.p;
-    for (int i = 0; st == RFD_OK && i < r.rows; i += chunk) {
-        const int m = std::min(chunk, r.rows - i);
-        const size_t bytes = (size_t)m * r.dim * sizeof(bf16_t);
-        st = r.read_rows(m, h);
-        if (st != RFD_OK) { set_error("%s", r.msg); break; }
-        for (int j = 0; j < m; ++j) // a removed row is erased whatever the file holds for it
-            if (!r.is_live(i + j)) memset(h + (size_t)j * r.dim, 0, (size_t)r.dim * sizeof(uint16_t));
-        if (hipMemcpyAsync(g->stage.p, h, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) { set_error("copying rows of %s to the device failed", path); st = RFD_ERR_HIP; }
-        if (st == RFD_OK) st = launch_gallery_import((const bf16_t *)g->stage.p, m, r.dim, i, (bf16_t *)g->store.p, c->stream);
-        if (st == RFD_OK && hipStreamSynchronize(c->stream) != hipSuccess) { set_error("loading rows of %s failed", path); st = RFD_ERR_HIP; }
-    }
-    if (st == RFD_OK && r.rows > 0) {
-        g->rows = g->live_synced = r.rows;
-        g->removed = r.rows - r.live;
-        g->live_words.assign((size_t)ceil_div(r.rows, 16), 0);
-        for (size_t i = 0; i < r.bits.size(); ++i) g->live_words[i >> 1] |= (uint16_t)(r.bits[i] << (8 * (i & 1)));
-        const size_t bytes = g->live_words.size() * sizeof(uint16_t); // <= ceil(2^30 / 16) * 2 = 128 MiB: in pieces
-        for (size_t at = 0; st == RFD_OK && at < bytes; at += rfd_gallery::kStageBytes) {
-            const size_t m = std::min(rfd_gallery::kStageBytes, bytes - at);
-            memcpy(g->pin, (const char *)g->live_words.data() + at, m);
-            if (hipMemcpyAsync((char *)g->live.p + at, g->pin, m, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
-                set_error("copying the live words of %s to the device failed", path);
-                st = RFD_ERR_HIP;
-            }
-        }
-    }
-    if (st != RFD_OK) { rfd_gallery_destroy(g); return st; }
-    *out = g;
-    return RFD_OK;
 }
 
 // ---- JPEG decode (rfd.h, "JPEG decode"): the entries; the host side of a decode call is csrc/jpeg_host.hip ----

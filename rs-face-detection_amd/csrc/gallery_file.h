@@ -1,5 +1,5 @@
 // gallery_file.h -- the gallery file "RFDG" (include/rfd.h, "gallery file"): the one statement of the format and all of its
-// validation.  Plain host C++ with no HIP in it: detector.hip includes it for rfd_gallery_save / _load / _file_info, and
+// validation.  Plain host C++ with no HIP in it: gallery_host.hip includes it for rfd_gallery_save / _load / _file_info, and
 // tests/cpp/gallery_file_check.cpp builds it with the host compiler alone.
 //
 // Version 1, little-endian, in LOGICAL row order (not the fragment-major layout of the storage, so a file survives a change of

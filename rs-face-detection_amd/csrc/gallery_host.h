@@ -1,0 +1,38 @@
+// gallery_host.h -- rfd_gallery: what a face gallery (include/rfd.h, "gallery") owns on the device, next to the book of its rows
+// (gallery_book.h).  gallery_host.hip holds every rfd_gallery_* entry; the kernels are kernels_gallery.hip.  Host only.
+#pragma once
+#include "gallery_book.h"
+#include "host_resources.h"
+
+namespace rfd {
+
+// What a gallery needs of its context, which stays private to detector.hip: the stream its commands go on (the caller's after
+// rfd_set_stream, so it is asked for at every call), and the device.
+hipStream_t ctx_stream(const rfd_ctx *c);
+int ctx_device(const rfd_ctx *c);
+
+} // namespace rfd
+
+// The enrolled embeddings of one context in HBM.  Next to the context, which lends it its device and stream; the caller destroys
+// it first.
+struct rfd_gallery {
+    rfd_ctx *ctx = nullptr;
+    rfd::GalleryBook book; // dim, capacity, rows, liveness, identities: the host's truth
+    int groups_max = 0;    // workgroups of a search, from the CU count: the workspace holds their lists
+    rfd::DevBuf store;     // ceil(capacity / 16) blocks of 16 rows, bf16, fragment-major (gallery_offset)
+    rfd::DevBuf ws;        // [groups_max][32][RFD_GALLERY_MAX_K] keys
+    // host forms, allocated by the first of them: a page-locked buffer and its device twin
+    static constexpr size_t kStageBytes = 4u << 20;
+    rfd::DevBuf stage;
+    rfd::Pinned<char> pin;
+    rfd::DevBuf live; // the device twin of the book's live words: ceil(capacity / 16) words, zero beyond book.unsynced().row0
+    // row lists of remove / replace / set-identities travel through a ring of page-locked slots (like the context's frame
+    // descriptors), so the calls enqueue without waiting for the stream; allocated by the first such call.  A slot is laid out
+    // by the book (kEditInts).
+    static constexpr int kRing = 4;
+    rfd::PinnedRing<kRing> edit_ring;
+    rfd::DevBuf edit;
+    // The identities on the device (one int32 per row, in whole blocks of 16; -1 = unlabelled), allocated by the first
+    // rfd_gallery_set_identities; until then no call touches them and every search runs without them.
+    rfd::DevBuf ids;
+};

@@ -405,36 +405,69 @@ int gallery_search_groups(int rows, int groups_max)
 }
 
 using GalleryLiveWords = const uint16_t *__restrict__;
+using GalleryIdentities = const int32_t *__restrict__;
 
-template <int NMT, bool MASKED>
-static int launch_gallery_scan(int groups, size_t lds, hipStream_t s, const bf16_t *store, int rows, int ksteps, const float *queries, int n, int k,
-                               uint2 *ws, const uint16_t *live)
+// One pass of the scan as both searches enqueue it: what is common to them, stated once.
+struct GalleryScan {
+    const bf16_t *store;
+    const uint16_t *live; // null: the scan without the mask
+    const int32_t *ids;   // null: the plain scan; else the identity scan, whose lists carry an identity word per key
+    int rows, dim;
+    const float *queries;
+    int n, k;
+    uint2 *ws;
+    int groups_max;
+};
+
+// The one launch of the scan.  The kernel's pack `Live` is named in full (deduction would drop the pointers' __restrict__, and
+// with it the instantiation).
+template <int NMT, bool MASKED, bool IDENT>
+static int launch_gallery_scan(const GalleryScan &a, int groups, size_t lds, hipStream_t s)
 {
-    constexpr int kLdsMax = 2 * 16 * 1024 * 2 + kGalleryWaves * 32 * RFD_GALLERY_MAX_K * 8; // dim 1024, 32 queries, k 32: 96 KiB
+    constexpr int kLdsMaxPlain = 2 * 16 * 1024 * 2 + kGalleryWaves * 32 * RFD_GALLERY_MAX_K * 8; // dim 1024, 32 queries, k 32: 96 KiB
+    // dim 1024, 32 queries, k 32: 96 KiB of fragments and keys, 16 KiB of identities: 112 of the CU's 160 KiB
+    constexpr int kLdsMaxIdent = 2 * 16 * 1024 * 2 + kGalleryWaves * 32 * RFD_GALLERY_MAX_K * (8 + 4);
     static DynLdsOnce once;
-    const void *kernel = nullptr;
-    if constexpr (MASKED) kernel = (const void *)gallery_search_kernel<NMT, true, false, GalleryLiveWords>;
-    else kernel = (const void *)gallery_search_kernel<NMT, false, false>;
-    RFD_TRY(once.ensure(kernel, kLdsMax));
-    if constexpr (MASKED)
-        hipLaunchKernelGGL((gallery_search_kernel<NMT, true, false, GalleryLiveWords>), dim3(groups), dim3(kGalleryWaves * 64), lds, s, store, rows, ksteps, queries, n, k, ws, live);
-    else
-        hipLaunchKernelGGL((gallery_search_kernel<NMT, false, false>), dim3(groups), dim3(kGalleryWaves * 64), lds, s, store, rows, ksteps, queries, n, k, ws);
-    RFD_HIP(hipGetLastError());
-    return RFD_OK;
+    auto launch = [&](auto *kernel, auto... live) -> int {
+        RFD_TRY(once.ensure((const void *)kernel, IDENT ? kLdsMaxIdent : kLdsMaxPlain));
+        hipLaunchKernelGGL(kernel, dim3(groups), dim3(kGalleryWaves * 64), lds, s, a.store, a.rows, a.dim / 32, a.queries, a.n, a.k, a.ws, live...);
+        RFD_HIP(hipGetLastError());
+        return RFD_OK;
+    };
+    if constexpr (IDENT && MASKED) return launch(gallery_search_kernel<NMT, true, true, GalleryIdentities, GalleryLiveWords>, a.ids, a.live);
+    else if constexpr (IDENT) return launch(gallery_search_kernel<NMT, false, true, GalleryIdentities>, a.ids);
+    else if constexpr (MASKED) return launch(gallery_search_kernel<NMT, true, false, GalleryLiveWords>, a.live);
+    else return launch(gallery_search_kernel<NMT, false, false>);
+}
+
+// the instantiation for a pass: one or two M-tiles, with or without the mask
+template <bool IDENT>
+static int launch_gallery_scan_for(const GalleryScan &a, int nmt, int groups, size_t lds, hipStream_t s)
+{
+    auto *scan = a.live ? (nmt == 2 ? launch_gallery_scan<2, true, IDENT> : launch_gallery_scan<1, true, IDENT>)
+                        : (nmt == 2 ? launch_gallery_scan<2, false, IDENT> : launch_gallery_scan<1, false, IDENT>);
+    return scan(a, groups, lds, s);
+}
+
+// checks the pass, enqueues its scan and returns the workgroups whose lists the merge reduces
+static int launch_gallery_scan_pass(const char *who, const GalleryScan &a, hipStream_t s, int *groups)
+{
+    if (a.n < 1 || a.n > kGalleryMaxQueries || a.k < 1 || a.k > RFD_GALLERY_MAX_K || a.dim % 32 != 0 || a.rows < 0 || a.groups_max < 1) {
+        set_error("%s: n %d, k %d, dim %d, rows %d out of range", who, a.n, a.k, a.dim, a.rows);
+        return RFD_ERR_INVALID_ARG;
+    }
+    *groups = gallery_search_groups(a.rows, a.groups_max);
+    const int nmt = a.n > 16 ? 2 : 1;
+    const size_t keys = (size_t)kGalleryWaves * nmt * 16 * a.k, lds = (size_t)nmt * 16 * a.dim * sizeof(bf16_t) + keys * sizeof(uint2);
+    if (!a.ids) return launch_gallery_scan_for<false>(a, nmt, *groups, lds, s);
+    return launch_gallery_scan_for<true>(a, nmt, *groups, lds + keys * sizeof(int32_t), s); // an identity word per key
 }
 
 int launch_gallery_search(const bf16_t *store, const uint16_t *live, int rows, int dim, const float *queries, int n, int k, uint2 *ws, int groups_max,
                           float *scores, int32_t *out_rows, hipStream_t s)
 {
-    if (n < 1 || n > kGalleryMaxQueries || k < 1 || k > RFD_GALLERY_MAX_K || dim % 32 != 0 || rows < 0 || groups_max < 1) {
-        set_error("launch_gallery_search: n %d, k %d, dim %d, rows %d out of range", n, k, dim, rows);
-        return RFD_ERR_INVALID_ARG;
-    }
-    const int groups = gallery_search_groups(rows, groups_max), ksteps = dim / 32, nmt = n > 16 ? 2 : 1;
-    const size_t lds = (size_t)nmt * 16 * dim * sizeof(bf16_t) + (size_t)kGalleryWaves * nmt * 16 * k * sizeof(uint2);
-    auto *scan = live ? (nmt == 2 ? launch_gallery_scan<2, true> : launch_gallery_scan<1, true>) : (nmt == 2 ? launch_gallery_scan<2, false> : launch_gallery_scan<1, false>);
-    RFD_TRY(scan(groups, lds, s, store, rows, ksteps, queries, n, k, ws, live));
+    int groups = 0;
+    RFD_TRY(launch_gallery_scan_pass("launch_gallery_search", {store, live, nullptr, rows, dim, queries, n, k, ws, groups_max}, s, &groups));
     hipLaunchKernelGGL(gallery_merge_kernel, dim3(n), dim3(kGalleryWaves * 64), 0, s, ws, groups, n, k, scores, out_rows);
     RFD_HIP(hipGetLastError());
     return RFD_OK;
@@ -481,46 +514,12 @@ __global__ void __launch_bounds__(kGalleryWaves * 64) gallery_merge_identities_k
         });
 }
 
-using GalleryIdentities = const int32_t *__restrict__;
-
-template <int NMT, bool MASKED>
-static int launch_gallery_scan_identities(int groups, size_t lds, hipStream_t s, const bf16_t *store, int rows, int ksteps, const float *queries, int n,
-                                          int k, uint2 *ws, const int32_t *ids, const uint16_t *live)
-{
-    // dim 1024, 32 queries, k 32: 96 KiB of fragments and keys, 16 KiB of identities: 112 of the CU's 160 KiB
-    constexpr int kLdsMax = 2 * 16 * 1024 * 2 + kGalleryWaves * 32 * RFD_GALLERY_MAX_K * (8 + 4);
-    static DynLdsOnce once;
-    const void *kernel = nullptr;
-    if constexpr (MASKED) kernel = (const void *)gallery_search_kernel<NMT, true, true, GalleryIdentities, GalleryLiveWords>;
-    else kernel = (const void *)gallery_search_kernel<NMT, false, true, GalleryIdentities>;
-    RFD_TRY(once.ensure(kernel, kLdsMax));
-    if constexpr (MASKED)
-        hipLaunchKernelGGL((gallery_search_kernel<NMT, true, true, GalleryIdentities, GalleryLiveWords>), dim3(groups), dim3(kGalleryWaves * 64), lds, s, store, rows, ksteps,
-                           queries, n, k, ws, ids, live);
-    else
-        hipLaunchKernelGGL((gallery_search_kernel<NMT, false, true, GalleryIdentities>), dim3(groups), dim3(kGalleryWaves * 64), lds, s, store, rows, ksteps, queries, n, k,
-                           ws, ids);
-    RFD_HIP(hipGetLastError());
-    return RFD_OK;
-}
-
 int launch_gallery_search_identities(const bf16_t *store, const uint16_t *live, const int32_t *ids, int rows, int dim, const float *queries, int n, int k,
                                      float min_score, uint2 *ws, int groups_max, float *scores, int32_t *out_rows, int32_t *out_ids, hipStream_t s)
 {
-    if (n < 1 || n > kGalleryMaxQueries || k < 1 || k > RFD_GALLERY_MAX_K || dim % 32 != 0 || rows < 0 || groups_max < 1) {
-        set_error("launch_gallery_search_identities: n %d, k %d, dim %d, rows %d out of range", n, k, dim, rows);
-        return RFD_ERR_INVALID_ARG;
-    }
-    const int groups = gallery_search_groups(rows, groups_max), ksteps = dim / 32, nmt = n > 16 ? 2 : 1;
-    const size_t keys = (size_t)kGalleryWaves * nmt * 16 * k, lds = (size_t)nmt * 16 * dim * sizeof(bf16_t) + keys * sizeof(uint2);
-    if (ids) { // the identity scan; its lists carry an identity word per key
-        auto *scan = live ? (nmt == 2 ? launch_gallery_scan_identities<2, true> : launch_gallery_scan_identities<1, true>)
-                          : (nmt == 2 ? launch_gallery_scan_identities<2, false> : launch_gallery_scan_identities<1, false>);
-        RFD_TRY(scan(groups, lds + keys * sizeof(int32_t), s, store, rows, ksteps, queries, n, k, ws, ids, live));
-    } else { // no identity was ever set: every row is its own identity, and the plain scan selects exactly that
-        auto *scan = live ? (nmt == 2 ? launch_gallery_scan<2, true> : launch_gallery_scan<1, true>) : (nmt == 2 ? launch_gallery_scan<2, false> : launch_gallery_scan<1, false>);
-        RFD_TRY(scan(groups, lds, s, store, rows, ksteps, queries, n, k, ws, live));
-    }
+    // ids null: no identity was ever set, every row is its own identity, and the plain scan selects exactly that
+    int groups = 0;
+    RFD_TRY(launch_gallery_scan_pass("launch_gallery_search_identities", {store, live, ids, rows, dim, queries, n, k, ws, groups_max}, s, &groups));
     hipLaunchKernelGGL(gallery_merge_identities_kernel, dim3(n), dim3(kGalleryWaves * 64), 0, s, ws, groups, n, k, ids, min_score, scores, out_rows, out_ids);
     RFD_HIP(hipGetLastError());
     return RFD_OK;
