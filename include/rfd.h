@@ -587,6 +587,49 @@ RFD_API int rfd_gallery_search_identities(rfd_gallery *g, const float *queries, 
 /* The same with DEVICE pointers (queries 16-byte aligned); async as in rfd_gallery_search_device. */
 RFD_API int rfd_gallery_search_identities_device(rfd_gallery *g, const float *queries, int n, int k, float min_score, float *scores, int32_t *rows,
                                                  int32_t *ids, int async);
+/* ---- tags.  One gallery often holds several populations: a tenant per customer, an access list per door, a watch list beside
+ *      the staff list, or "verify against the claimed person only".  So every row carries a uint32_t tag, and a filtered
+ *      search gives every query q its own pair (mask[q], value[q]): row r is ELIGIBLE for q iff (tag[r] & mask[q]) == value[q].
+ *      mask = 0xFFFFFFFF, value = t searches partition t (2^32 partitions); mask = value = 1u << b searches the rows on list
+ *      b; a tenant number in the high bits and list bits in the low bits compose; mask = value = 0 matches every row.  A value
+ *      with bits outside its mask matches nothing; it is not an error (the device form cannot look at it), the query's result
+ *      is then all empty entries.  "Any of these bits" is not a rule: issue the query once per list in the same pass.
+ *      The tag is 0 after add, add_device, load and clear; every 32-bit value is a valid tag.
+ *      Setting: rfd_gallery_set_tags gives rows[i] the tag tags[i].  It follows rfd_gallery_set_identities in every rule:
+ *      enqueued on the context's stream in call order with no synchronisation (the lists travel through the gallery's
+ *      page-locked memory), so add_device -> set_tags -> search_filtered_device(async) -> rfd_sync is one sequence without a
+ *      host wait.  A row outside [0, rows), a removed row or a row listed twice returns RFD_ERR_INVALID_ARG, rfd_last_error()
+ *      names the offender and nothing is changed; n = 0 is a no-op.
+ *      Reading: _get_tags is answered from a host copy, without a device wait.
+ *      With the other calls: remove resets the row's tag to 0, in HBM too and in stream order (nothing of an erased enrolment
+ *      stays); replace / replace_device leave it alone (a reused hole has tag 0, because its remove reset it); clear resets
+ *      all.  save / load and the "RFDG" file are unchanged: tags are NOT in the file, the caller re-applies them after load.
+ *      Memory: the tag array in HBM (capacity x 4 bytes, rounded up to whole blocks of 16 rows, zeroed) is allocated by the
+ *      first set_tags or the first filtered search, in stream order ahead of every use.  Until then every other call launches
+ *      exactly the kernels it launched before, with the same arguments; rfd_gallery_search* and
+ *      rfd_gallery_search_identities* always do.
+ *      Search: the result is that of rfd_gallery_search_identities computed on the rows that are live and eligible for the
+ *      query.  Every identity's key is its best live, eligible row under (score descending, row ascending); unlabelled rows
+ *      each form their own identity; the k best identity keys come back as (score, row, identity).  So an identity whose best
+ *      row is not eligible for a query is represented by its best eligible row, and one without an eligible row is absent
+ *      for that query alone.  Entries with !(score >= min_score) are the empty entry (-inf, -1, -1), a suffix; fewer than k
+ *      eligible identities leave the tail empty; NaN and -inf scores are never selected.  Scores keep their bits, and the
+ *      result does not depend on n, the query's place or how rows are spread over waves and workgroups.  On a gallery
+ *      without identities ids is -1 throughout, so the filtered row search needs no entry of its own.  k, n (any, in passes
+ *      of 32), min_score, alignment, async and the host / device forms follow rfd_gallery_search_identities / _device; the
+ *      host form refuses non-finite queries; a null mask or value with n > 0 is RFD_ERR_INVALID_ARG.
+ *      Cost: the scan reads the tags of a block of 16 rows (64 bytes beside its 16 KiB of operands at dim 512) only if a key
+ *      of that block passes a list's filter.  A small partition's lists stay empty, so for it every block passes and pays that
+ *      read and its wait; a block with nothing eligible then costs no offer (README, "Gallery search"). ---- */
+RFD_API int rfd_gallery_set_tags(rfd_gallery *g, const int32_t *rows /* host [n], distinct */, const uint32_t *tags /* host [n] */, int n);
+/* out: host [n], the tags of rows [row0, row0 + n) (removed rows read 0); host copy, no device wait */
+RFD_API int rfd_gallery_get_tags(const rfd_gallery *g, int row0, int n, uint32_t *out);
+/* queries: host [n][dim]; mask, value: host [n] each; scores [n][k] f32, rows [n][k] i32, ids [n][k] i32, host */
+RFD_API int rfd_gallery_search_filtered(rfd_gallery *g, const float *queries, int n, int k, float min_score, const uint32_t *mask, const uint32_t *value,
+                                        float *scores, int32_t *rows, int32_t *ids);
+/* The same with DEVICE pointers (queries 16-byte aligned; mask, value: DEVICE [n] each); async as in rfd_gallery_search_device. */
+RFD_API int rfd_gallery_search_filtered_device(rfd_gallery *g, const float *queries, int n, int k, float min_score, const uint32_t *mask,
+                                               const uint32_t *value, float *scores, int32_t *rows, int32_t *ids, int async);
 
 /* ---- gallery file "RFDG", version 1, little-endian, in logical row order (not the private storage layout):
  *          bytes 0..19  "RFDG", u32 version = 1, u32 dim, u32 rows, u32 reserved = 0

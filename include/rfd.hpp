@@ -464,6 +464,40 @@ class Gallery {
         check(rfd_gallery_search_identities(g_, queries.data(), m.n, k, min_score, m.scores.data(), m.rows.data(), m.ids.data()));
         return m;
     }
+    // tags (rfd.h, "tags"): rows[i] (live, distinct) gets the tag tags[i], any 32-bit value; enqueued, no synchronisation
+    void set_tags(const std::vector<int32_t> &rows, const std::vector<uint32_t> &tags)
+    {
+        if (tags.size() != rows.size()) throw Error(RFD_ERR_INVALID_ARG, "set_tags: one tag per row");
+        check(rfd_gallery_set_tags(g_, rows.data(), tags.data(), (int)rows.size()));
+    }
+    // the tags of rows [row0, row0 + n); 0 for a row that never got one and for a removed row
+    std::vector<uint32_t> tags(int row0, int n) const
+    {
+        std::vector<uint32_t> out((std::size_t)(n > 0 ? n : 0));
+        check(rfd_gallery_get_tags(g_, row0, n, out.data()));
+        return out;
+    }
+    // search_identities among the rows r with (tag[r] & mask[q]) == value[q] for query q; one mask and one value per query
+    IdentityMatches search_filtered(const std::vector<float> &queries, int k, const std::vector<uint32_t> &mask, const std::vector<uint32_t> &value,
+                                    float min_score = -std::numeric_limits<float>::infinity())
+    {
+        IdentityMatches m;
+        m.n = (int)(queries.size() / (std::size_t)dim_);
+        if (mask.size() != (std::size_t)m.n || value.size() != (std::size_t)m.n) throw Error(RFD_ERR_INVALID_ARG, "search_filtered: one mask and one value per query");
+        m.k = k;
+        m.scores.resize((std::size_t)m.n * (std::size_t)(k > 0 ? k : 0));
+        m.rows.resize(m.scores.size());
+        m.ids.resize(m.scores.size());
+        check(rfd_gallery_search_filtered(g_, queries.data(), m.n, k, min_score, mask.data(), value.data(), m.scores.data(), m.rows.data(), m.ids.data()));
+        return m;
+    }
+    // the same with every pointer in device memory (queries 16-byte aligned; mask, value [n]; scores, rows, ids [n][k]);
+    // enqueued, and with async no synchronisation
+    void search_filtered_device(const float *queries, int n, int k, float min_score, const uint32_t *mask, const uint32_t *value, float *scores, int32_t *rows,
+                                int32_t *ids, bool async = false)
+    {
+        check(rfd_gallery_search_filtered_device(g_, queries, n, k, min_score, mask, value, scores, rows, ids, async ? 1 : 0));
+    }
 
   private:
     rfd_gallery *g_ = nullptr;

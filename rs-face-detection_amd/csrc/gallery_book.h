@@ -1,6 +1,6 @@
 // gallery_book.h -- GalleryBook: the host bookkeeping of a face gallery (include/rfd.h, "gallery"): which rows exist, which are
-// live, which carry an identity, what the device's live words still lack, and what a remove / replace / set-identities call
-// sends to the device.  Plain host C++ with no HIP in it: gallery_host.hip owns one book per gallery and enqueues what it plans,
+// live, which carry an identity or a tag, what the device's live words still lack, and what a remove / replace / set-identities
+// / set-tags call sends to the device.  Plain host C++ with no HIP in it: gallery_host.hip owns one book per gallery and enqueues what it plans,
 // and tests/cpp/gallery_book_check.cpp builds it with the host compiler alone.  A check that refuses leaves its reason in the
 // caller's msg and the book unchanged.
 #ifndef RFD_GALLERY_BOOK_H
@@ -17,6 +17,7 @@ namespace rfd {
 // A list of rows travels to the device in chunks of at most kEditRows, each through one slot of kEditInts ints:
 //   remove / replace (plan_edit):        rows [m] | blocks [nb] | their new live words [nb] | rows that lose an identity [nu]
 //   set identities (plan_identities):    rows [m] | identities [m]
+//   set tags (plan_tags):                rows [m] | tags [m] (the 32 bits of each, carried in an int)
 // nb <= m (a block per row at most) and nu <= m (each row once), so m + 2 nb + nu <= 4 m <= kEditInts.
 constexpr int kEditRows = 1024, kEditInts = 4 * kEditRows;
 static_assert(kEditInts >= 4 * kEditRows, "a slot holds the worst case of plan_edit: every row in a block of its own, every row labelled");
@@ -81,6 +82,17 @@ public:
         return RFD_OK;
     }
 
+    // rows (all in the gallery: check_rows) that may take a tag: none removed.  Every 32-bit value is a tag.
+    int check_tags(const int32_t *rows, int n, char *msg, size_t cap) const
+    {
+        for (int i = 0; i < n; ++i)
+            if (!is_live(rows[i])) {
+                snprintf(msg, cap, "invalid argument: rows[%d] = %d is a removed row", i, rows[i]);
+                return RFD_ERR_INVALID_ARG;
+            }
+        return RFD_OK;
+    }
+
     // n more rows (check_room), all live; returns the first of them
     int add(int n)
     {
@@ -109,7 +121,8 @@ public:
     // One chunk of a replace (revive: the rows become live) or a remove (they become removed and lose their identity): m <=
     // kEditRows rows, all in the gallery.  Updates the book and fills slot [kEditInts] as laid out above; the blocks ascend.  A
     // removed row is always unlabelled, so the rows that lose an identity are the listed ones that still have one; a row's
-    // second mention finds it gone, and each is listed once.
+    // second mention finds it gone, and each is listed once.  A remove also zeroes the rows' tags in the book; on the device
+    // the caller zeroes the tags of all m listed rows (the slot's first m ints).
     GalleryEditPlan plan_edit(const int32_t *rows, int m, bool revive, int32_t *slot)
     {
         int32_t *blk = slot + m;
@@ -117,6 +130,7 @@ public:
             const int r = rows[i];
             slot[i] = r;
             blk[i] = r >> 4;
+            if (!revive && (size_t)r < tag_.size()) tag_[r] = 0;
             if (is_live(r) == revive) continue;
             live_words_[(size_t)r >> 4] ^= (uint16_t)(1u << (r & 15));
             removed_ += revive ? -1 : 1;
@@ -149,11 +163,24 @@ public:
         }
     }
 
+    // One chunk of a set-tags call: m <= kEditRows distinct live rows and their tags (check_tags).  Updates the book and fills
+    // slot with rows | tags.
+    void plan_tags(const int32_t *rows, const uint32_t *tags, int m, int32_t *slot)
+    {
+        if (tag_.size() < (size_t)rows_) tag_.resize((size_t)rows_, 0u);
+        for (int i = 0; i < m; ++i) {
+            tag_[rows[i]] = tags[i];
+            slot[i] = rows[i];
+            slot[m + i] = (int32_t)tags[i];
+        }
+    }
+
     void clear() // no rows; dim and capacity stay
     {
         rows_ = removed_ = live_synced_ = labelled_ = 0;
         live_words_.clear();
         ident_.clear();
+        tag_.clear();
     }
 
     // the liveness bytes of the gallery file (gallery_file.h): bit (r & 7) of byte r >> 3 is set while row r is live
@@ -163,7 +190,7 @@ public:
         for (size_t i = 0; i < bits.size(); ++i) bits[i] = (unsigned char)(live_words_[i >> 1] >> (8 * (i & 1)));
         return bits;
     }
-    // the book of a file of `rows` rows <= capacity, `live` of them live by `bits`; no identities.  The caller copies
+    // the book of a file of `rows` rows <= capacity, `live` of them live by `bits`; no identities, no tags.  The caller copies
     // live_words() to the device: the book counts them as synced.
     void from_file(int rows, int live, const std::vector<unsigned char> &bits)
     {
@@ -187,12 +214,18 @@ public:
     {
         for (int i = 0; i < n; ++i) out[i] = (size_t)(row0 + i) < ident_.size() ? ident_[row0 + i] : RFD_GALLERY_NO_IDENTITY;
     }
+    // tags of rows [row0, row0 + n), all in the gallery; the rows behind the last one ever tagged have tag 0
+    void tags(int row0, int n, uint32_t *out) const
+    {
+        for (int i = 0; i < n; ++i) out[i] = (size_t)(row0 + i) < tag_.size() ? tag_[row0 + i] : 0u;
+    }
 
 private:
     int dim_ = 0, capacity_ = 0, rows_ = 0;
     int removed_ = 0, live_synced_ = 0, labelled_ = 0;
     std::vector<uint16_t> live_words_; // the truth about liveness; the device's words follow it (unsynced)
     std::vector<int32_t> ident_;       // the truth about identities: rows [0, size()), shorter than rows_ until a label is set
+    std::vector<uint32_t> tag_;        // the truth about tags: rows [0, size()), shorter than rows_ until a tag is set; 0 beyond
 };
 
 } // namespace rfd

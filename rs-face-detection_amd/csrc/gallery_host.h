@@ -26,7 +26,7 @@ struct rfd_gallery {
     rfd::DevBuf stage;
     rfd::Pinned<char> pin;
     rfd::DevBuf live; // the device twin of the book's live words: ceil(capacity / 16) words, zero beyond book.unsynced().row0
-    // row lists of remove / replace / set-identities travel through a ring of page-locked slots (like the context's frame
+    // row lists of remove / replace / set-identities / set-tags travel through a ring of page-locked slots (like the context's frame
     // descriptors), so the calls enqueue without waiting for the stream; allocated by the first such call.  A slot is laid out
     // by the book (kEditInts).
     static constexpr int kRing = 4;
@@ -35,4 +35,8 @@ struct rfd_gallery {
     // The identities on the device (one int32 per row, in whole blocks of 16; -1 = unlabelled), allocated by the first
     // rfd_gallery_set_identities; until then no call touches them and every search runs without them.
     rfd::DevBuf ids;
+    // The tags on the device (one uint32 per row, in whole blocks of 16, zero for every row without one), allocated by the first
+    // rfd_gallery_set_tags or the first filtered search; until then no call touches them, and the plain and the identity
+    // searches never do.
+    rfd::DevBuf tags;
 };

@@ -87,6 +87,7 @@ static int gallery_check_identities(const rfd_gallery *g, const int32_t *rows, c
     char msg[256];
     return book_status(g->book.check_identities(rows, ids, n, msg, sizeof msg), msg);
 }
+static int gallery_check_tags(const rfd_gallery *g, const int32_t *rows, int n) { char msg[256]; return book_status(g->book.check_tags(rows, n, msg, sizeof msg), msg); }
 
 // ---- the device's live words and the row lists ----
 // brings the device's live words up to the rows added since they were last written or read
@@ -132,6 +133,7 @@ static int gallery_edit(rfd_gallery *g, const int32_t *rows, const float *emb, i
         const int32_t *d = (const int32_t *)g->edit.p, *blk = d + p.m, *word = blk + p.nb, *unlabel = word + p.nb;
         RFD_TRY(launch_gallery_put(emb ? emb + (size_t)at * dim : nullptr, d, p.m, dim, (bf16_t *)g->store.p, blk, word, p.nb, (uint16_t *)g->live.p, s));
         if (p.nu > 0) RFD_TRY(launch_gallery_set_identities((int32_t *)g->ids.p, unlabel, nullptr, p.nu, s));
+        if (!emb && g->tags.p) RFD_TRY(launch_gallery_set_tags((uint32_t *)g->tags.p, d, nullptr, p.m, s)); // a removed row's tag is 0
     }
     return RFD_OK;
 }
@@ -196,6 +198,7 @@ int rfd_gallery_clear(rfd_gallery *g)
     if (rows > 0) RFD_HIP(hipMemsetAsync(g->store.p, 0, (size_t)ceil_div(rows, 16) * 16 * g->book.dim() * sizeof(bf16_t), s));
     if (synced > 0) RFD_HIP(hipMemsetAsync(g->live.p, 0, (size_t)ceil_div(synced, 16) * sizeof(uint16_t), s));
     if (g->ids.p && rows > 0) RFD_HIP(hipMemsetAsync(g->ids.p, 0xff, (size_t)rows * sizeof(int32_t), s)); // all -1 again
+    if (g->tags.p && rows > 0) RFD_HIP(hipMemsetAsync(g->tags.p, 0, (size_t)rows * sizeof(uint32_t), s));
     g->book.clear();
     return RFD_OK;
 }
@@ -242,34 +245,63 @@ int rfd_gallery_get_rows(rfd_gallery *g, int row0, int n, float *out)
     });
 }
 
-// ---- search: the k best rows, or with `ids` (rfd.h, "identities") the k best identities, in both forms of both ----
+// the first tags of a gallery, or its first filtered search: the device array, all zero, in stream order ahead of every use
+static int gallery_tag_array(rfd_gallery *g, hipStream_t s)
+{
+    if (g->tags.p) return RFD_OK;
+    const size_t bytes = (size_t)ceil_div(g->book.capacity(), 16) * 16 * sizeof(uint32_t); // whole blocks: the scan reads a block's 16 words
+    RFD_TRY(g->tags.reserve(bytes));
+    if (hipMemsetAsync(g->tags.p, 0, bytes, s) != hipSuccess) {
+        set_error("hipMemsetAsync of the gallery's tags failed");
+        (void)hipStreamSynchronize(s);
+        g->tags.release();
+        return RFD_ERR_HIP;
+    }
+    return RFD_OK;
+}
+
+// ---- search: the k best rows, or with `ids` (rfd.h, "identities") the k best identities, or with a filter (rfd.h, "tags") the
+//      k best identities among each query's eligible rows, in both forms of each ----
+// the filter of the queries of a call or of a pass: one mask and one value per query, on the device; null: no filter
+struct GalleryFilter {
+    const uint32_t *mask = nullptr, *value = nullptr;
+    explicit operator bool() const { return mask != nullptr; }
+    GalleryFilter from(int i) const { return mask ? GalleryFilter{mask + i, value + i} : GalleryFilter{}; }
+};
+
 // one pass over the gallery for m <= kGalleryMaxQueries queries on the device; results on the device
 static int gallery_search_pass(rfd_gallery *g, hipStream_t s, const uint16_t *live, const float *queries, int m, int k, float min_score, float *scores,
-                               int32_t *rows, int32_t *ids)
+                               int32_t *rows, int32_t *ids, GalleryFilter f = {})
 {
     const GalleryBook &b = g->book;
+    if (f)
+        return launch_gallery_search_filtered((const bf16_t *)g->store.p, live, (const int32_t *)g->ids.p, (const uint32_t *)g->tags.p, f.mask, f.value, b.rows(),
+                                              b.dim(), queries, m, k, min_score, (uint2 *)g->ws.p, g->groups_max, scores, rows, ids, s);
     if (!ids) return launch_gallery_search((const bf16_t *)g->store.p, live, b.rows(), b.dim(), queries, m, k, (uint2 *)g->ws.p, g->groups_max, scores, rows, s);
     return launch_gallery_search_identities((const bf16_t *)g->store.p, live, (const int32_t *)g->ids.p, b.rows(), b.dim(), queries, m, k, min_score,
                                             (uint2 *)g->ws.p, g->groups_max, scores, rows, ids, s);
 }
 
-// n >= 1 queries and their results on the device; ids null: the rows alone
-static int gallery_search_device(rfd_gallery *g, const float *queries, int n, int k, float min_score, float *scores, int32_t *rows, int32_t *ids, int async)
+// n >= 1 queries and their results on the device; ids null: the rows alone; f: device lists of n
+static int gallery_search_device(rfd_gallery *g, const float *queries, int n, int k, float min_score, float *scores, int32_t *rows, int32_t *ids, int async,
+                                 GalleryFilter f = {})
 {
     RFD_CHECK_ARG((uintptr_t)queries % 16 == 0, "queries are not 16-byte aligned");
     RFD_HIP(hipSetDevice(ctx_device(g->ctx)));
     const hipStream_t s = ctx_stream(g->ctx);
     const uint16_t *live = nullptr;
     RFD_TRY(gallery_search_mask(g, s, &live));
+    if (f) RFD_TRY(gallery_tag_array(g, s));
     for (int i = 0; i < n; i += kGalleryMaxQueries) // one pass over the gallery per group of queries; the passes share the workspace in stream order
         RFD_TRY(gallery_search_pass(g, s, live, queries + (size_t)i * g->book.dim(), std::min(kGalleryMaxQueries, n - i), k, min_score, scores + (size_t)i * k,
-                                    rows + (size_t)i * k, ids ? ids + (size_t)i * k : nullptr));
+                                    rows + (size_t)i * k, ids ? ids + (size_t)i * k : nullptr, f.from(i)));
     if (!async) RFD_HIP(hipStreamSynchronize(s));
     return RFD_OK;
 }
 
-// n >= 1 queries and their results on the host; ids null: the rows alone
-static int gallery_search_host(rfd_gallery *g, const float *queries, int n, int k, float min_score, float *scores, int32_t *rows, int32_t *ids)
+// n >= 1 queries and their results on the host; ids null: the rows alone; f: host lists of n
+static int gallery_search_host(rfd_gallery *g, const float *queries, int n, int k, float min_score, float *scores, int32_t *rows, int32_t *ids,
+                               GalleryFilter f = {})
 {
     const int dim = g->book.dim();
     RFD_TRY(gallery_check_finite(queries, n, dim, "query"));
@@ -278,17 +310,26 @@ static int gallery_search_host(rfd_gallery *g, const float *queries, int n, int 
     RFD_TRY(gallery_host_stage(g));
     const uint16_t *live = nullptr;
     RFD_TRY(gallery_search_mask(g, s, &live));
-    // the staging buffer holds one group: its queries, then its scores, its rows and (with ids) its identities
-    const size_t qcap = (size_t)kGalleryMaxQueries * dim * sizeof(float), rcap = (size_t)kGalleryMaxQueries * RFD_GALLERY_MAX_K * sizeof(float);
+    if (f) RFD_TRY(gallery_tag_array(g, s));
+    // the staging buffer holds one group: its queries (with a filter: and behind them its masks | values, in the same copy), then
+    // its scores, its rows and (with ids) its identities
+    const size_t fcap = f ? (size_t)kGalleryMaxQueries * 2 * sizeof(uint32_t) : 0;
+    const size_t qcap = (size_t)kGalleryMaxQueries * dim * sizeof(float) + fcap, rcap = (size_t)kGalleryMaxQueries * RFD_GALLERY_MAX_K * sizeof(float);
     char *d = (char *)g->stage.p, *h = (char *)g->pin;
     float *d_q = (float *)d, *d_s = (float *)(d + qcap);
     int32_t *d_r = (int32_t *)(d + qcap + rcap), *d_i = ids ? (int32_t *)(d + qcap + 2 * rcap) : nullptr;
     for (int i = 0; i < n; i += kGalleryMaxQueries) {
         const int m = std::min(kGalleryMaxQueries, n - i);
         const size_t qbytes = (size_t)m * dim * sizeof(float), rbytes = (size_t)m * k * sizeof(float);
+        const size_t fbytes = f ? (size_t)m * sizeof(uint32_t) : 0;
         memcpy(h, queries + (size_t)i * dim, qbytes);
-        RFD_HIP(hipMemcpyAsync(d_q, h, qbytes, hipMemcpyHostToDevice, s));
-        RFD_TRY(gallery_search_pass(g, s, live, d_q, m, k, min_score, d_s, d_r, d_i));
+        if (f) {
+            memcpy(h + qbytes, f.mask + i, fbytes);
+            memcpy(h + qbytes + fbytes, f.value + i, fbytes);
+        }
+        RFD_HIP(hipMemcpyAsync(d_q, h, qbytes + 2 * fbytes, hipMemcpyHostToDevice, s));
+        const uint32_t *d_f = (const uint32_t *)(d + qbytes);
+        RFD_TRY(gallery_search_pass(g, s, live, d_q, m, k, min_score, d_s, d_r, d_i, f ? GalleryFilter{d_f, d_f + m} : GalleryFilter{}));
         if (ids) {
             RFD_HIP(hipMemcpyAsync(h + qcap, d_s, 3 * rcap, hipMemcpyDeviceToHost, s)); // the three results lie side by side
         } else {
@@ -340,6 +381,30 @@ int rfd_gallery_search_identities(rfd_gallery *g, const float *queries, int n, i
     if (n == 0) return RFD_OK;
     RFD_CHECK_ARG(queries && scores && rows && ids, "null argument");
     return gallery_search_host(g, queries, n, k, min_score, scores, rows, ids);
+}
+
+int rfd_gallery_search_filtered_device(rfd_gallery *g, const float *queries, int n, int k, float min_score, const uint32_t *mask, const uint32_t *value,
+                                       float *scores, int32_t *rows, int32_t *ids, int async)
+{
+    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
+    RFD_TRY(gallery_check_k(k));
+    RFD_TRY(gallery_check_min_score(min_score));
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(queries && scores && rows && ids, "null argument");
+    RFD_CHECK_ARG(mask && value, "mask or value is null");
+    return gallery_search_device(g, queries, n, k, min_score, scores, rows, ids, async, GalleryFilter{mask, value});
+}
+
+int rfd_gallery_search_filtered(rfd_gallery *g, const float *queries, int n, int k, float min_score, const uint32_t *mask, const uint32_t *value, float *scores,
+                                int32_t *rows, int32_t *ids)
+{
+    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
+    RFD_TRY(gallery_check_k(k));
+    RFD_TRY(gallery_check_min_score(min_score));
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(queries && scores && rows && ids, "null argument");
+    RFD_CHECK_ARG(mask && value, "mask or value is null");
+    return gallery_search_host(g, queries, n, k, min_score, scores, rows, ids, GalleryFilter{mask, value});
 }
 
 // ---- remove and replace (rfd.h, "remove and replace") ----
@@ -447,6 +512,42 @@ int rfd_gallery_identities(const rfd_gallery *g, int *labelled_rows)
 {
     RFD_CHECK_ARG(g && labelled_rows, "null argument");
     *labelled_rows = g->book.labelled();
+    return RFD_OK;
+}
+
+// ---- tags (rfd.h, "tags") ----
+int rfd_gallery_set_tags(rfd_gallery *g, const int32_t *rows, const uint32_t *tags, int n)
+{
+    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(rows && tags, "rows or tags is null");
+    RFD_TRY(gallery_check_rows(g, rows, n));
+    RFD_TRY(gallery_check_tags(g, rows, n));
+    RFD_TRY(gallery_check_distinct(rows, n));
+    RFD_HIP(hipSetDevice(ctx_device(g->ctx)));
+    const hipStream_t s = ctx_stream(g->ctx);
+    RFD_TRY(gallery_edit_lists(g));
+    RFD_TRY(gallery_tag_array(g, s));
+    for (int at = 0; at < n; at += kEditRows) {
+        const int m = std::min(kEditRows, n - at);
+        int32_t *slot;
+        RFD_TRY(g->edit_ring.acquire(&slot));
+        g->book.plan_tags(rows + at, tags + at, m, slot);
+        RFD_HIP(hipMemcpyAsync(g->edit.p, slot, (size_t)2 * m * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        RFD_TRY(g->edit_ring.record(s));
+        const int32_t *d = (const int32_t *)g->edit.p;
+        RFD_TRY(launch_gallery_set_tags((uint32_t *)g->tags.p, d, (const uint32_t *)(d + m), m, s));
+    }
+    return RFD_OK;
+}
+
+int rfd_gallery_get_tags(const rfd_gallery *g, int row0, int n, uint32_t *out)
+{
+    RFD_CHECK_ARG(g && n >= 0, "gallery is null or n < 0");
+    if (n == 0) return RFD_OK;
+    RFD_CHECK_ARG(out, "out is null");
+    RFD_CHECK_ARG(row0 >= 0 && n <= g->book.rows() - row0, "rows [row0, row0 + n) are not all in the gallery");
+    g->book.tags(row0, n, out);
     return RFD_OK;
 }
 

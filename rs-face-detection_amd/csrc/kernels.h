@@ -233,6 +233,14 @@ int launch_gallery_search_identities(const bf16_t *store, const uint16_t *live, 
                                      float min_score, uint2 *ws, int groups_max, float *scores, int32_t *out_rows, int32_t *out_ids, hipStream_t s);
 // ids[rows[i]] = vals[i] for i < n, or -1 where vals is null (rows: device list of distinct rows)
 int launch_gallery_set_identities(int32_t *ids, const int32_t *rows, const int32_t *vals, int n, hipStream_t s);
+// The filtered form (rfd.h, "tags"): launch_gallery_search_identities on the rows r that are eligible for query q, (tags[r] &
+// fmask[q]) == fvalue[q].  tags: one uint32 per row, allocated in whole blocks of 16 rows and zero beyond the rows (the scan
+// reads a block's 16 words); fmask / fvalue: device [n].  ids as above (null: out_ids is all -1).
+int launch_gallery_search_filtered(const bf16_t *store, const uint16_t *live, const int32_t *ids, const uint32_t *tags, const uint32_t *fmask,
+                                   const uint32_t *fvalue, int rows, int dim, const float *queries, int n, int k, float min_score, uint2 *ws, int groups_max,
+                                   float *scores, int32_t *out_rows, int32_t *out_ids, hipStream_t s);
+// tags[rows[i]] = vals[i] for i < n, or 0 where vals is null (rows: device list, distinct where vals is given)
+int launch_gallery_set_tags(uint32_t *tags, const int32_t *rows, const uint32_t *vals, int n, hipStream_t s);
 // rows[i] (device list, distinct unless emb is null) of store takes bf16(emb[i]), or zeros where emb is null; then live[blk[j]] =
 // word[j] for j < nwords <= n (device lists, blk distinct)
 int launch_gallery_put(const float *emb, const int32_t *rows, int n, int dim, bf16_t *store, const int32_t *blk, const int32_t *word, int nwords,

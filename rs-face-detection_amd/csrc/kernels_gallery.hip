@@ -26,6 +26,13 @@
 // better than its best key, and the same k identities would beat it globally.  A later row of the identity in that wave cannot
 // push it out either: it only replaces the identity's key by a better one.  The same holds one level up for a workgroup's merged
 // list among the workgroups, so every level may drop all but its k best distinct identities.
+//
+// Filtered search (rfd.h, "tags"): rows carry a uint32 tag in HBM, and every query of a pass its own (mask, value); row r counts
+// for query q iff (tag[r] & mask[q]) == value[q].  The TAGGED instantiations of the scan keep the pass's pairs in LDS next to the
+// A fragments and read a block's 16 tags where they read its identities, in a block with a key that passes a list's filter; the
+// eligibility is one more term of the predicate a key is offered under.  The merges are unchanged: they see eligible keys only,
+// and the argument above holds per query with "live and eligible for the query" in place of "live", because the set of rows
+// that count for a query is fixed for the whole pass and every level reduces keys of that one set.
 #include "conv_device.h"
 
 namespace rfd {
@@ -99,6 +106,12 @@ template <class T>
 __device__ __forceinline__ T pack_last(T last) { return last; }
 template <class T, class... Rest>
 __device__ __forceinline__ auto pack_last(T, Rest... rest) { return pack_last(rest...); }
+template <int I, class T, class... Rest>
+__device__ __forceinline__ auto pack_at(T first, Rest... rest)
+{
+    if constexpr (I == 0) return first;
+    else return pack_at<I - 1>(rest...);
+}
 
 // ---- the identity forms of the three routines above.  A list holds no identity >= 0 twice; lid[i] is the identity of list[i]
 //      (-1 for an unlabelled row and for the sentinel, which never equals a candidate's identity >= 0). ----
@@ -238,17 +251,26 @@ int launch_gallery_get(const bf16_t *store, int row0, int n, int dim, float *out
 // IDENT: the identity scan.  The pack then begins with the identity array (one int32 per row), the lists carry an identity word
 // per key behind them in LDS, and the selection goes through the identity forms of the list routines; the MFMA loop, the
 // prefetch and the `any` pre-check are the same code.  Without IDENT nothing of this is instantiated.
-template <int NMT, bool MASKED, bool IDENT, class... Live>
+// TAGGED: the filtered scan.  Behind the identity array (if any) the pack then holds the tag array (one uint32 per row, whole
+// blocks of 16) and the pass's masks and values (device, [n] each).  The pairs lie in LDS behind the A fragments, one uint2 per
+// query, and are read there as 64-bit broadcasts (the 16 lanes of a group hold the same four queries): held in registers they
+// would take 8 * NMT VGPRs that the NMT = 2 instantiations do not have.  The tags of a block are read like its identities, by
+// scalar loads inside the `any` branch.  A second ballot, over "eligible and passes its list's filter", then skips the offers
+// of a block with nothing eligible in it: a small tenant's lists stay at the sentinel, so every block passes the first one.
+// The MFMA loop, the prefetch and the live words are the same code.  Without TAGGED nothing of this is instantiated.
+template <int NMT, bool MASKED, bool IDENT, bool TAGGED, class... Live>
 __global__ void __launch_bounds__(kGalleryWaves * 64) gallery_search_kernel(const bf16_t *__restrict__ store, int rows, int ksteps,
                                                                              const float *__restrict__ queries, int n, int k,
                                                                              uint2 *__restrict__ ws, Live... live)
 {
-    static_assert(sizeof...(Live) == (IDENT ? 1 : 0) + (MASKED ? 1 : 0), "an identity scan takes the identities, a masked scan the live words behind them");
+    static_assert(sizeof...(Live) == (IDENT ? 1 : 0) + (TAGGED ? 3 : 0) + (MASKED ? 1 : 0),
+                  "an identity scan takes the identities, a filtered scan the tags, masks and values behind them, a masked scan the live words last");
     extern __shared__ __attribute__((aligned(16))) unsigned char gallery_smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6); // scalar: the walk below is wave-uniform
     const int dim = ksteps * 32, quads = dim >> 2;
     uint2 *afrag = reinterpret_cast<uint2 *>(gallery_smem);  // [NMT][ksteps][2 halves][64 lanes] x 4 bf16
-    uint2 *lists = afrag + NMT * ksteps * 128;               // [waves][NMT * 16 queries][k]
+    [[maybe_unused]] uint2 *filt = afrag + NMT * ksteps * 128; // TAGGED: [NMT * 16 queries] (mask, value)
+    uint2 *lists = afrag + NMT * ksteps * 128 + (TAGGED ? NMT * 16 : 0); // [waves][NMT * 16 queries][k]
     uint2 *mine = lists + wave * (NMT * 16 * k);
     [[maybe_unused]] int32_t *lids = nullptr, *mine_ids = nullptr;  // IDENT: [waves][NMT * 16 queries][k] identities of the keys
     [[maybe_unused]] const int32_t *ids = nullptr;
@@ -256,6 +278,14 @@ __global__ void __launch_bounds__(kGalleryWaves * 64) gallery_search_kernel(cons
         lids = reinterpret_cast<int32_t *>(lists + kGalleryWaves * NMT * 16 * k);
         mine_ids = lids + wave * (NMT * 16 * k);
         ids = pack_first(live...);
+    }
+    [[maybe_unused]] const uint32_t *tags = nullptr;
+    if constexpr (TAGGED) {
+        constexpr int at = IDENT ? 1 : 0;
+        tags = pack_at<at>(live...);
+        const uint32_t *fmask = pack_at<at + 1>(live...), *fvalue = pack_at<at + 2>(live...);
+        // a query beyond n is never offered; its pair (0, 1) matches no tag
+        if (tid < NMT * 16) filt[tid] = tid < n ? make_uint2(fmask[tid], fvalue[tid]) : make_uint2(0u, 1u);
     }
 
     // queries -> bf16 A fragments: lane (q & 15) + 16 * ((d & 31) >> 3) of K step d >> 5 holds elements d & ~7 .. + 7 of query q
@@ -344,14 +374,45 @@ __global__ void __launch_bounds__(kGalleryWaves * 64) gallery_search_kernel(cons
                                     cid = (lane & 15) == i ? v : cid;
                                 }
                             }
+                            // TAGGED: the tags of the block's 16 rows, read like the identities and with them (one wait for
+                            // both); bit 4 mt + r of `elig` = the lane's row is live and eligible for its query of (mt, r).
+                            [[maybe_unused]] uint32_t elig = 0;
+                            [[maybe_unused]] bool offer = true;
+                            if constexpr (TAGGED) {
+                                const uint32_t *block_tags = tags + (size_t)__builtin_amdgcn_readfirstlane(blk) * 16;
+                                uint32_t tag = 0;
 #pragma unroll
-                            for (int mt = 0; mt < NMT; ++mt)
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) {
-                                    const int q = mt * 16 + 4 * (lane >> 4) + r;
-                                    if constexpr (IDENT) list_offer_ident(mine, mine_ids, q, k, acc[mt][r], row, cid, row_ok && q < n, lane);
-                                    else list_offer(mine, q, k, acc[mt][r], row, row_ok && q < n, lane);
+                                for (int i = 0; i < 16; ++i) {
+                                    const uint32_t v = block_tags[i];
+                                    tag = (lane & 15) == i ? v : tag;
                                 }
+                                bool any_eligible = false;
+#pragma unroll
+                                for (int mt = 0; mt < NMT; ++mt)
+#pragma unroll
+                                    for (int r = 0; r < 4; ++r) {
+                                        const int q = mt * 16 + 4 * (lane >> 4) + r;
+                                        const uint2 f = filt[q];
+                                        if (row_ok && q < n && (tag & f.x) == f.y) {
+                                            elig |= 1u << (4 * mt + r);
+                                            const uint2 t = mine[q * k + k - 1];
+                                            any_eligible |= key_better(acc[mt][r], row, __uint_as_float(t.x), (int)t.y);
+                                        }
+                                    }
+                                offer = __ballot(any_eligible) != 0; // wave-uniform
+                            }
+                            if (offer) {
+#pragma unroll
+                                for (int mt = 0; mt < NMT; ++mt)
+#pragma unroll
+                                    for (int r = 0; r < 4; ++r) {
+                                        const int q = mt * 16 + 4 * (lane >> 4) + r;
+                                        bool valid = row_ok && q < n;
+                                        if constexpr (TAGGED) valid = (elig >> (4 * mt + r)) & 1u;
+                                        if constexpr (IDENT) list_offer_ident(mine, mine_ids, q, k, acc[mt][r], row, cid, valid, lane);
+                                        else list_offer(mine, q, k, acc[mt][r], row, valid, lane);
+                                    }
+                            }
                         }
                     }
 #pragma unroll
@@ -406,6 +467,7 @@ int gallery_search_groups(int rows, int groups_max)
 
 using GalleryLiveWords = const uint16_t *__restrict__;
 using GalleryIdentities = const int32_t *__restrict__;
+using GalleryTags = const uint32_t *__restrict__; // the tag array, and the masks and the values of a pass
 
 // One pass of the scan as both searches enqueue it: what is common to them, stated once.
 struct GalleryScan {
@@ -417,35 +479,47 @@ struct GalleryScan {
     int n, k;
     uint2 *ws;
     int groups_max;
+    // null: no filter; else the filtered scan: one uint32 per row, and the pass's masks and values (device, [n] each)
+    const uint32_t *tags = nullptr, *fmask = nullptr, *fvalue = nullptr;
 };
 
 // The one launch of the scan.  The kernel's pack `Live` is named in full (deduction would drop the pointers' __restrict__, and
 // with it the instantiation).
-template <int NMT, bool MASKED, bool IDENT>
+template <int NMT, bool MASKED, bool IDENT, bool TAGGED>
 static int launch_gallery_scan(const GalleryScan &a, int groups, size_t lds, hipStream_t s)
 {
+    constexpr int kLdsFilters = TAGGED ? kGalleryMaxQueries * (int)sizeof(uint2) : 0; // the filtered scan's (mask, value) pairs
     constexpr int kLdsMaxPlain = 2 * 16 * 1024 * 2 + kGalleryWaves * 32 * RFD_GALLERY_MAX_K * 8; // dim 1024, 32 queries, k 32: 96 KiB
     // dim 1024, 32 queries, k 32: 96 KiB of fragments and keys, 16 KiB of identities: 112 of the CU's 160 KiB
     constexpr int kLdsMaxIdent = 2 * 16 * 1024 * 2 + kGalleryWaves * 32 * RFD_GALLERY_MAX_K * (8 + 4);
     static DynLdsOnce once;
     auto launch = [&](auto *kernel, auto... live) -> int {
-        RFD_TRY(once.ensure((const void *)kernel, IDENT ? kLdsMaxIdent : kLdsMaxPlain));
+        RFD_TRY(once.ensure((const void *)kernel, (IDENT ? kLdsMaxIdent : kLdsMaxPlain) + kLdsFilters));
         hipLaunchKernelGGL(kernel, dim3(groups), dim3(kGalleryWaves * 64), lds, s, a.store, a.rows, a.dim / 32, a.queries, a.n, a.k, a.ws, live...);
         RFD_HIP(hipGetLastError());
         return RFD_OK;
     };
-    if constexpr (IDENT && MASKED) return launch(gallery_search_kernel<NMT, true, true, GalleryIdentities, GalleryLiveWords>, a.ids, a.live);
-    else if constexpr (IDENT) return launch(gallery_search_kernel<NMT, false, true, GalleryIdentities>, a.ids);
-    else if constexpr (MASKED) return launch(gallery_search_kernel<NMT, true, false, GalleryLiveWords>, a.live);
-    else return launch(gallery_search_kernel<NMT, false, false>);
+    if constexpr (TAGGED) {
+        if constexpr (IDENT && MASKED)
+            return launch(gallery_search_kernel<NMT, true, true, true, GalleryIdentities, GalleryTags, GalleryTags, GalleryTags, GalleryLiveWords>, a.ids, a.tags,
+                          a.fmask, a.fvalue, a.live);
+        else if constexpr (IDENT)
+            return launch(gallery_search_kernel<NMT, false, true, true, GalleryIdentities, GalleryTags, GalleryTags, GalleryTags>, a.ids, a.tags, a.fmask, a.fvalue);
+        else if constexpr (MASKED)
+            return launch(gallery_search_kernel<NMT, true, false, true, GalleryTags, GalleryTags, GalleryTags, GalleryLiveWords>, a.tags, a.fmask, a.fvalue, a.live);
+        else return launch(gallery_search_kernel<NMT, false, false, true, GalleryTags, GalleryTags, GalleryTags>, a.tags, a.fmask, a.fvalue);
+    } else if constexpr (IDENT && MASKED) return launch(gallery_search_kernel<NMT, true, true, false, GalleryIdentities, GalleryLiveWords>, a.ids, a.live);
+    else if constexpr (IDENT) return launch(gallery_search_kernel<NMT, false, true, false, GalleryIdentities>, a.ids);
+    else if constexpr (MASKED) return launch(gallery_search_kernel<NMT, true, false, false, GalleryLiveWords>, a.live);
+    else return launch(gallery_search_kernel<NMT, false, false, false>);
 }
 
 // the instantiation for a pass: one or two M-tiles, with or without the mask
-template <bool IDENT>
+template <bool IDENT, bool TAGGED>
 static int launch_gallery_scan_for(const GalleryScan &a, int nmt, int groups, size_t lds, hipStream_t s)
 {
-    auto *scan = a.live ? (nmt == 2 ? launch_gallery_scan<2, true, IDENT> : launch_gallery_scan<1, true, IDENT>)
-                        : (nmt == 2 ? launch_gallery_scan<2, false, IDENT> : launch_gallery_scan<1, false, IDENT>);
+    auto *scan = a.live ? (nmt == 2 ? launch_gallery_scan<2, true, IDENT, TAGGED> : launch_gallery_scan<1, true, IDENT, TAGGED>)
+                        : (nmt == 2 ? launch_gallery_scan<2, false, IDENT, TAGGED> : launch_gallery_scan<1, false, IDENT, TAGGED>);
     return scan(a, groups, lds, s);
 }
 
@@ -459,8 +533,14 @@ static int launch_gallery_scan_pass(const char *who, const GalleryScan &a, hipSt
     *groups = gallery_search_groups(a.rows, a.groups_max);
     const int nmt = a.n > 16 ? 2 : 1;
     const size_t keys = (size_t)kGalleryWaves * nmt * 16 * a.k, lds = (size_t)nmt * 16 * a.dim * sizeof(bf16_t) + keys * sizeof(uint2);
-    if (!a.ids) return launch_gallery_scan_for<false>(a, nmt, *groups, lds, s);
-    return launch_gallery_scan_for<true>(a, nmt, *groups, lds + keys * sizeof(int32_t), s); // an identity word per key
+    if (a.tags) { // the pairs of the M-tiles' queries lie between the fragments and the keys
+        if (!a.fmask || !a.fvalue) { set_error("%s: a filtered pass without its masks or values", who); return RFD_ERR_INVALID_ARG; }
+        const size_t flds = lds + (size_t)nmt * 16 * sizeof(uint2);
+        if (!a.ids) return launch_gallery_scan_for<false, true>(a, nmt, *groups, flds, s);
+        return launch_gallery_scan_for<true, true>(a, nmt, *groups, flds + keys * sizeof(int32_t), s);
+    }
+    if (!a.ids) return launch_gallery_scan_for<false, false>(a, nmt, *groups, lds, s);
+    return launch_gallery_scan_for<true, false>(a, nmt, *groups, lds + keys * sizeof(int32_t), s); // an identity word per key
 }
 
 int launch_gallery_search(const bf16_t *store, const uint16_t *live, int rows, int dim, const float *queries, int n, int k, uint2 *ws, int groups_max,
@@ -525,6 +605,20 @@ int launch_gallery_search_identities(const bf16_t *store, const uint16_t *live, 
     return RFD_OK;
 }
 
+// The filtered form (rfd.h, "tags"): launch_gallery_search_identities on the rows r with (tags[r] & fmask[q]) == fvalue[q] for
+// query q.  The merge is the identity merge: the workspace holds eligible keys only.
+int launch_gallery_search_filtered(const bf16_t *store, const uint16_t *live, const int32_t *ids, const uint32_t *tags, const uint32_t *fmask,
+                                   const uint32_t *fvalue, int rows, int dim, const float *queries, int n, int k, float min_score, uint2 *ws, int groups_max,
+                                   float *scores, int32_t *out_rows, int32_t *out_ids, hipStream_t s)
+{
+    if (!tags) { set_error("launch_gallery_search_filtered: the tag array is null"); return RFD_ERR_INVALID_ARG; }
+    int groups = 0;
+    RFD_TRY(launch_gallery_scan_pass("launch_gallery_search_filtered", {store, live, ids, rows, dim, queries, n, k, ws, groups_max, tags, fmask, fvalue}, s, &groups));
+    hipLaunchKernelGGL(gallery_merge_identities_kernel, dim3(n), dim3(kGalleryWaves * 64), 0, s, ws, groups, n, k, ids, min_score, scores, out_rows, out_ids);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
 // ---- identities of rows: ids[rows[i]] = vals[i], or -1 where vals is null (remove).  rows: a device list of distinct rows, so
 //      every word has one writer. ----
 __global__ void __launch_bounds__(256) gallery_set_identities_kernel(int32_t *__restrict__ ids, const int32_t *__restrict__ rows,
@@ -537,6 +631,22 @@ __global__ void __launch_bounds__(256) gallery_set_identities_kernel(int32_t *__
 int launch_gallery_set_identities(int32_t *ids, const int32_t *rows, const int32_t *vals, int n, hipStream_t s)
 {
     hipLaunchKernelGGL(gallery_set_identities_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ids, rows, vals, n);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+// ---- tags of rows: tags[rows[i]] = vals[i], or 0 where vals is null (remove, whose list may name a row twice: every writer
+//      of a word then writes 0).  rows: a device list of rows, distinct where vals is given. ----
+__global__ void __launch_bounds__(256) gallery_set_tags_kernel(uint32_t *__restrict__ tags, const int32_t *__restrict__ rows,
+                                                               const uint32_t *__restrict__ vals, int n)
+{
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i < n) tags[rows[i]] = vals ? vals[i] : 0u;
+}
+
+int launch_gallery_set_tags(uint32_t *tags, const int32_t *rows, const uint32_t *vals, int n, hipStream_t s)
+{
+    hipLaunchKernelGGL(gallery_set_tags_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, tags, rows, vals, n);
     RFD_HIP(hipGetLastError());
     return RFD_OK;
 }

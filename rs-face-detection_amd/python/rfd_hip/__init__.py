@@ -171,6 +171,7 @@ API_SYMBOLS = [
     "rfd_gallery_save", "rfd_gallery_load", "rfd_gallery_file_info",
     "rfd_gallery_set_identities", "rfd_gallery_get_identities", "rfd_gallery_identities", "rfd_gallery_search_identities",
     "rfd_gallery_search_identities_device",
+    "rfd_gallery_set_tags", "rfd_gallery_get_tags", "rfd_gallery_search_filtered", "rfd_gallery_search_filtered_device",
     "rfd_jpeg_info", "rfd_decode_jpeg_batch_device", "rfd_decode_jpeg_batch", "rfd_set_decode_threads", "rfd_debug_jpeg_coefficients",
     "rfd_set_jpeg_entropy", "rfd_jpeg_last_paths", "rfd_debug_jpeg_intervals", "rfd_debug_jpeg_coefficients_device",
     "rfd_jpeg_orientation", "rfd_set_jpeg_orientation", "rfd_jpeg_last_orientations",
@@ -307,6 +308,10 @@ def load_library(path=None):
     L.rfd_gallery_identities.argtypes = [vp, C.POINTER(ci)]
     L.rfd_gallery_search_identities.argtypes = [vp, vp, ci, ci, C.c_float, vp, vp, vp]
     L.rfd_gallery_search_identities_device.argtypes = [vp, vp, ci, ci, C.c_float, vp, vp, vp, ci]
+    L.rfd_gallery_set_tags.argtypes = [vp, vp, vp, ci]
+    L.rfd_gallery_get_tags.argtypes = [vp, ci, ci, vp]
+    L.rfd_gallery_search_filtered.argtypes = [vp, vp, ci, ci, C.c_float, vp, vp, vp, vp, vp]
+    L.rfd_gallery_search_filtered_device.argtypes = [vp, vp, ci, ci, C.c_float, vp, vp, vp, vp, vp, ci]
     L.rfd_gallery_save.argtypes = [vp, C.c_char_p]
     L.rfd_gallery_load.argtypes = [vp, C.c_char_p, ci, C.POINTER(vp)]
     L.rfd_gallery_file_info.argtypes = [C.c_char_p, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
@@ -761,6 +766,39 @@ class Gallery:
         """the same on raw device addresses, by the conventions of search_device"""
         _check(self._L.rfd_gallery_search_identities_device(self._g, queries_ptr, int(n), int(k), float(min_score), scores_ptr, rows_ptr, ids_ptr,
                                                             int(async_)))
+
+    @staticmethod
+    def _tag_list(x):
+        return np.ascontiguousarray(np.asarray(x, np.int64).reshape(-1) & 0xFFFFFFFF, np.uint32)
+
+    def set_tags(self, rows, tags):
+        """row rows[i] (live, distinct) gets the tag tags[i], any 32-bit value; enqueued on the detector's stream, no
+        synchronisation (rfd.h, "tags")"""
+        r, t = self._row_list(rows), self._tag_list(tags)
+        assert r.shape[0] == t.shape[0], "one tag per row"
+        _check(self._L.rfd_gallery_set_tags(self._g, r.ctypes.data, t.ctypes.data, r.shape[0]))
+
+    def tags(self, row0, n):
+        """the tags of rows [row0, row0 + n) (u32 array; 0 for a row that never got one and for a removed row)"""
+        out = np.zeros(int(n), np.uint32)
+        _check(self._L.rfd_gallery_get_tags(self._g, int(row0), int(n), out.ctypes.data))
+        return out
+
+    def search_filtered(self, queries, k, mask, value, min_score=-np.inf):
+        """search_identities among the rows r with (tag[r] & mask[q]) == value[q] for query q (mask, value: one u32 per query) ->
+        (scores [n, k] f32, rows [n, k] i32, ids [n, k] i32); ids is -1 throughout on a gallery without identities"""
+        x, m, v = self._rows2d(queries), self._tag_list(mask), self._tag_list(value)
+        assert m.shape[0] == v.shape[0] == x.shape[0], "one mask and one value per query"
+        shape = (x.shape[0], max(int(k), 0))
+        scores, rows, ids = np.zeros(shape, np.float32), np.zeros(shape, np.int32), np.zeros(shape, np.int32)
+        _check(self._L.rfd_gallery_search_filtered(self._g, x.ctypes.data, x.shape[0], int(k), float(min_score), m.ctypes.data, v.ctypes.data,
+                                                   scores.ctypes.data, rows.ctypes.data, ids.ctypes.data))
+        return scores, rows, ids
+
+    def search_filtered_device(self, queries_ptr, n, k, min_score, mask_ptr, value_ptr, scores_ptr, rows_ptr, ids_ptr, async_=False):
+        """the same on raw device addresses (mask, value: u32 [n] each), by the conventions of search_device"""
+        _check(self._L.rfd_gallery_search_filtered_device(self._g, queries_ptr, int(n), int(k), float(min_score), mask_ptr, value_ptr, scores_ptr, rows_ptr,
+                                                          ids_ptr, int(async_)))
 
 
 class RetinaFaceDetection:

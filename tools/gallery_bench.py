@@ -20,6 +20,13 @@ the same process: --repeats windows of plain searches, then the rows are labelle
 rows lie M apart, in every wave's walk) and the identity search is timed, then with M contiguous runs of rows (an identity's rows
 arrive together), then the plain windows again; the spread of the two plain series is the yardstick.  The identity scan reads
 4 bytes of identity for a key that passes a list's filter and nothing else beyond the plain scan's bytes.
+
+--tenants T measures the filtered search (rfd_gallery_search_filtered_device) against the plain one on the same gallery in the
+same process: --repeats windows of plain searches, then for each --tenant-layout the rows are tagged with T tenants, as row % T
+(mod: a tenant's rows lie T apart, in every wave's walk) or in T contiguous runs (runs: a tenant's rows arrive together, and
+most blocks hold nothing of it), and the filtered search is timed with mask = 0xFFFFFFFF and, per query, the tenant of the row
+the query is a noisy copy of; then the plain windows again; the spread of the two plain series is the yardstick.  The filtered
+scan reads the 64 bytes of a block's tags only in a block with a key that passes a list's filter.
 Prints one JSON line per size."""
 import argparse
 import json
@@ -42,9 +49,11 @@ def main():
     ap.add_argument("--rows", type=int, nargs="*", default=[100_000, 1_000_000])
     ap.add_argument("--removed", type=float, default=0.0, help="share of the rows to remove at random before timing the masked scan")
     ap.add_argument("--identities", type=int, default=0, help="label the rows with this many identities and time the identity search")
-    ap.add_argument("--repeats", type=int, default=5, help="timed windows per series of a --removed or --identities run")
+    ap.add_argument("--tenants", type=int, default=0, help="tag the rows with this many tenants and time the filtered search of one tenant per query")
+    ap.add_argument("--tenant-layout", nargs="+", choices=("mod", "runs"), default=["mod", "runs"], help="row %% T, or T contiguous runs of rows")
+    ap.add_argument("--repeats", type=int, default=5, help="timed windows per series of a --removed, --identities or --tenants run")
     args = ap.parse_args()
-    assert 0.0 <= args.removed < 1.0 and args.identities >= 0
+    assert 0.0 <= args.removed < 1.0 and args.identities >= 0 and args.tenants >= 0
     import torch
     import rfd_hip
     det = rfd_hip.RetinaFaceDetection(image_size=(640, 640), max_batch_size=1, max_det=16)
@@ -154,6 +163,50 @@ def main():
                            "row_mod_m_minus_plain_median_ms": round(float(np.median(series["row_mod_m"]) - np.median(both)), 4),
                            "runs_minus_plain_median_ms": round(float(np.median(series["runs"]) - np.median(both)), 4),
                            "identity_array_bytes": rows * 4})
+        if args.tenants > 0:
+            import numpy as np
+            t_n = min(args.tenants, rows)
+            d_i = torch.zeros(NQ, K, dtype=torch.int32, device=dev)
+            d_mask = torch.full((NQ,), -1, dtype=torch.int32, device=dev)   # 0xFFFFFFFF: the whole word
+            d_value = torch.zeros(NQ, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()
+
+            def ours_filtered(n):
+                for _ in range(n):
+                    gal.search_filtered_device(q.data_ptr(), NQ, K, float("-inf"), d_mask.data_ptr(), d_value.data_ptr(), d_s.data_ptr(), d_r.data_ptr(),
+                                               d_i.data_ptr(), async_=True)
+                det.sync()
+
+            def filtered_window():
+                t0 = time.perf_counter()
+                ours_filtered(args.steps)
+                return (time.perf_counter() - t0) * 1e3 / args.steps
+
+            stats = lambda w: {"windows_ms": w, "median_ms": round(float(np.median(w)), 4), "min_ms": min(w), "max_ms": max(w)}
+            plain = [round(window(), 4) for _ in range(args.repeats)]
+            every = np.arange(rows)
+            series = {}
+            for name in args.tenant_layout:
+                tags = every % t_n if name == "mod" else every * t_n // rows
+                gal.set_tags(every, tags)
+                d_value.copy_(torch.from_numpy(tags[:NQ].astype(np.int32)))   # query i is a noisy copy of row i
+                det.sync()
+                torch.cuda.synchronize()
+                ours_filtered(args.warmup)             # the filtered instantiation's first launches
+                series[name] = [round(filtered_window(), 4) for _ in range(args.repeats)]
+                got_r = d_r.cpu().numpy()
+                assert (got_r[:, 0] == np.arange(NQ)).all()                              # every query finds its row, in its tenant
+                assert all((tags[row[row >= 0]] == tags[a]).all() for a, row in enumerate(got_r))   # and rows of its tenant alone
+                assert (got_r >= 0).all() or rows // t_n < K
+            ours(args.warmup)
+            plain_again = [round(window(), 4) for _ in range(args.repeats)]
+            both = plain + plain_again
+            base = float(np.median(both))
+            masked.update({"tenants": t_n, "repeats": args.repeats, "plain": stats(plain), "plain_again": stats(plain_again),
+                           "plain_spread_ms": round(max(both) - min(both), 4), "tag_array_bytes": (rows + 15) // 16 * 64})
+            for name, w in series.items():
+                masked.update({"filtered_" + name: stats(w), name + "_minus_plain_median_ms": round(float(np.median(w)) - base, 4),
+                               name + "_over_plain": round(float(np.median(w)) / base, 3)})
         theirs(args.warmup)
         t0 = time.perf_counter()
         ref = theirs(args.steps)
