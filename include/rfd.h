@@ -630,6 +630,52 @@ RFD_API int rfd_gallery_search_filtered(rfd_gallery *g, const float *queries, in
 /* The same with DEVICE pointers (queries 16-byte aligned; mask, value: DEVICE [n] each); async as in rfd_gallery_search_device. */
 RFD_API int rfd_gallery_search_filtered_device(rfd_gallery *g, const float *queries, int n, int k, float min_score, const uint32_t *mask,
                                                const uint32_t *value, float *scores, int32_t *rows, int32_t *ids, int async);
+/* ---- nearest.  A deployment that enrols people also asks a question about the gallery itself: is this person already in it,
+ *      under another name (de-duplication)?  It is asked of every enrolment batch, new rows against everything, and as a
+ *      periodic sweep, every row against every row.  rfd_gallery_nearest answers it on the device: the rows are already stored
+ *      as matrix-core operands, so nothing crosses PCIe but the answer, the gallery is read once per tile of rows instead of
+ *      once per 32 queries, and the self-match never appears.
+ *      Contract: for every row a in [row0, row0 + n), entry a - row0 is the best row b under the gallery's total order, which is
+ *      score descending, then row ascending.  The candidates are the rows b that meet all of these conditions:
+ *        - b is live;
+ *        - b != a;
+ *        - b is allowed by `mode`: RFD_GALLERY_NEAREST_OTHER_ROW allows every b, RFD_GALLERY_NEAREST_OTHER_IDENTITY additionally
+ *          refuses id[a] >= 0 && id[b] == id[a] (an unlabelled row is an identity of its own, as in the identity search);
+ *        - b is allowed by the tag rule: (tag[a] & tag_mask) == (tag[b] & tag_mask); tag_mask = 0 allows every row;
+ *        - b's score is neither NaN nor -inf, and is >= min_score.
+ *      `ids` receives the identity of b.  The empty entry is (-inf, -1, -1); it is written where a is removed, where no
+ *      candidate qualifies, and where the gallery has one row.  min_score = -INFINITY disables the threshold.
+ *      Score bits: score(a, b) has exactly the bits that rfd_gallery_search returns for row b when the query is
+ *      rfd_gallery_get_rows(a): the same instruction, K ascending, one accumulator chain starting from +0 per (a, b).  So
+ *      score(a, b) and score(b, a) have equal bits, and the result does not depend on row0, n, the number of CUs, or how the
+ *      work is tiled and split.
+ *      k is 1 on purpose: one best key per row lives in registers, the output has a fixed size, and a caller who wants
+ *      clusters joins the links on the host.  Mind what that gives: nearest-neighbour links above a threshold CONNECT
+ *      duplicates, they do NOT ENUMERATE all pairs -- of three enrolments of one person each may name only its best partner.
+ *      Errors: row0 < 0, n < 0 or row0 + n beyond the rows handed out, an unknown mode, a non-zero reserved word, and a null or
+ *      misaligned `scores` or `rows` (4-byte alignment suffices; `ids` may be NULL, else it follows the same rule) return
+ *      RFD_ERR_INVALID_ARG; n = 0 is a no-op; a refused call writes nothing.
+ *      Stream: the device form is enqueued on the context's stream in call order with no host wait, so add_device ->
+ *      nearest_device runs back to back; async as in rfd_gallery_search_device.  The host form is synchronous and moves its
+ *      outputs through the gallery's page-locked memory.  The call's workspace belongs to the gallery and is allocated on
+ *      first use; the identity and the tag array are read where they exist and never allocated here.  Every other gallery
+ *      call launches the kernels and arguments it launched before.
+ *      Cost: rows are processed in tiles (rfd_debug_gallery_nearest_plan), and the gallery is read ceil(n / tile_rows) times;
+ *      few rows against a large gallery are split over the gallery and merged, so they still occupy every CU. ---- */
+#define RFD_GALLERY_NEAREST_OTHER_ROW      0   /* any live row b != a */
+#define RFD_GALLERY_NEAREST_OTHER_IDENTITY 1   /* additionally not (id[a] >= 0 && id[b] == id[a]) */
+typedef struct rfd_gallery_nearest_config {
+    int32_t  mode;        /* one of the two above */
+    float    min_score;   /* an entry whose best score is not >= min_score is empty; -inf: none is */
+    uint32_t tag_mask;    /* b counts for a iff (tag[a] & tag_mask) == (tag[b] & tag_mask); 0: every row */
+    int32_t  reserved[5]; /* must be 0 */
+} rfd_gallery_nearest_config;                  /* 32 bytes */
+RFD_API void rfd_gallery_nearest_config_default(rfd_gallery_nearest_config *cfg); /* OTHER_ROW, -inf, 0 */
+RFD_API int rfd_gallery_nearest(rfd_gallery *g, int row0, int n, const rfd_gallery_nearest_config *cfg /* NULL: default */,
+                                float *scores /* host [n] */, int32_t *rows /* host [n] */, int32_t *ids /* host [n] or NULL */);
+/* The same with DEVICE outputs */
+RFD_API int rfd_gallery_nearest_device(rfd_gallery *g, int row0, int n, const rfd_gallery_nearest_config *cfg,
+                                       float *scores, int32_t *rows, int32_t *ids, int async);
 
 /* ---- gallery file "RFDG", version 1, little-endian, in logical row order (not the private storage layout):
  *          bytes 0..19  "RFDG", u32 version = 1, u32 dim, u32 rows, u32 reserved = 0
@@ -652,6 +698,18 @@ RFD_API int rfd_gallery_file_info(const char *path, int *dim, int *rows, int *li
 /* host only, no GPU: element offset of (row, d) in the private storage layout (-1: dim or an index out of range); the add
  * kernel scatters by this function and tests pin that it is a bijection and that an MFMA operand fetch is one 1 KiB span */
 RFD_API int64_t rfd_debug_gallery_offset(int dim, int row, int d);
+/* host only, no GPU, no context: how rfd_gallery_nearest of rows [row0, row0 + n) decomposes on a gallery of `rows` rows handed
+ * out and `dim` values per row, on a device of `cus` compute units.  A workgroup owns one tile of tile_rows rows of the range
+ * and one split: the row blocks (of 16 rows) b < blocks with (b / 4) % splits == s, at most blocks_per_split of them; grid =
+ * tiles * splits <= ceil(n / tile_rows) + 4 * cus.  form: 0 = the rows of a tile in LDS (any dim), 1 = in registers (dim 512, calls
+ * of more than 32 rows); tile_rows follows the form.
+ * Arguments outside the gallery's rules return RFD_ERR_INVALID_ARG and a plan of zeros. */
+typedef struct rfd_gallery_nearest_plan {
+    int32_t form, tile_rows, tiles, splits, blocks, blocks_per_split;
+    int64_t grid;     /* workgroups of the scan */
+    int64_t ws_bytes; /* splits * n keys of 8 bytes */
+} rfd_gallery_nearest_plan;
+RFD_API int rfd_debug_gallery_nearest_plan(int rows, int row0, int n, int dim, int cus, rfd_gallery_nearest_plan *out);
 
 /* ---- every detected face of a frame: the packed face list.  FaceSelection keeps one face per frame (eKYC); the gallery's
  *      search pass scores 32 queries at once, and a group photo or a door camera holds many faces.  Here up to max_faces

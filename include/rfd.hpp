@@ -498,6 +498,36 @@ class Gallery {
     {
         check(rfd_gallery_search_filtered_device(g_, queries, n, k, min_score, mask, value, scores, rows, ids, async ? 1 : 0));
     }
+    // nearest (rfd.h, "nearest"): for every row a of [row0, row0 + n) the best live row b != a that cfg allows; entry i belongs to
+    // row row0 + i, and is (-inf, -1, -1) where a is removed or nothing qualifies
+    struct Nearest {
+        std::vector<float> scores;
+        std::vector<int32_t> rows, ids;
+    };
+    static rfd_gallery_nearest_config nearest_config(int mode = RFD_GALLERY_NEAREST_OTHER_ROW, float min_score = -std::numeric_limits<float>::infinity(),
+                                                     uint32_t tag_mask = 0)
+    {
+        rfd_gallery_nearest_config cfg;
+        rfd_gallery_nearest_config_default(&cfg);
+        cfg.mode = mode;
+        cfg.min_score = min_score;
+        cfg.tag_mask = tag_mask;
+        return cfg;
+    }
+    Nearest nearest(int row0, int n, const rfd_gallery_nearest_config &cfg = nearest_config())
+    {
+        Nearest r;
+        r.scores.resize((std::size_t)(n > 0 ? n : 0));
+        r.rows.resize(r.scores.size());
+        r.ids.resize(r.scores.size());
+        check(rfd_gallery_nearest(g_, row0, n, &cfg, r.scores.data(), r.rows.data(), r.ids.data()));
+        return r;
+    }
+    // the same with the outputs in device memory ([n] each; ids may be null); enqueued, and with async no synchronisation
+    void nearest_device(int row0, int n, const rfd_gallery_nearest_config &cfg, float *scores, int32_t *rows, int32_t *ids, bool async = false)
+    {
+        check(rfd_gallery_nearest_device(g_, row0, n, &cfg, scores, rows, ids, async ? 1 : 0));
+    }
 
   private:
     rfd_gallery *g_ = nullptr;

@@ -39,4 +39,8 @@ struct rfd_gallery {
     // rfd_gallery_set_tags or the first filtered search; until then no call touches them, and the plain and the identity
     // searches never do.
     rfd::DevBuf tags;
+    // The workspace of rfd_gallery_nearest (rfd.h, "nearest"): the splits' keys, sized once for any call on this gallery
+    // (gallery_nearest_ws_bound) by the first such call, so it never moves under enqueued work.
+    int cus = 0; // of the gallery's device, from creation
+    rfd::DevBuf nearest_ws;
 };

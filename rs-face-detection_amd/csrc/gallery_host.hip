@@ -1,7 +1,7 @@
 // gallery_host.hip -- the host side of the face gallery (include/rfd.h, "gallery"): every rfd_gallery_* entry.  What a call
 // changes in the bookkeeping is decided by the gallery's GalleryBook (gallery_book.h); this file checks the arguments, enqueues
-// the copies and the kernels of kernels_gallery.hip on the context's stream, and reads and writes the gallery file
-// (gallery_file.h).
+// the copies and the kernels of kernels_gallery.hip and kernels_gallery_nearest.hip (as gallery_nearest_plan.h plans them) on
+// the context's stream, and reads and writes the gallery file (gallery_file.h).
 #include "gallery_host.h"
 
 #include <algorithm>
@@ -156,7 +156,8 @@ int rfd_gallery_create(rfd_ctx *c, int dim, int capacity, rfd_gallery **out)
     std::unique_ptr<rfd_gallery> g(new rfd_gallery()); // an early return frees whatever was built so far
     g->ctx = c;
     g->book.init(dim, capacity);
-    g->groups_max = 2 * device_cus(); // two workgroups of four waves per CU: what the scan's registers admit
+    g->cus = device_cus();
+    g->groups_max = 2 * g->cus; // two workgroups of four waves per CU: what the scan's registers admit
     const size_t bytes = (size_t)ceil_div(capacity, 16) * 16 * dim * sizeof(bf16_t);
     RFD_TRY(g->store.reserve(bytes));
     RFD_TRY(g->ws.reserve((size_t)g->groups_max * kGalleryMaxQueries * RFD_GALLERY_MAX_K * sizeof(uint2)));
@@ -548,6 +549,98 @@ int rfd_gallery_get_tags(const rfd_gallery *g, int row0, int n, uint32_t *out)
     RFD_CHECK_ARG(out, "out is null");
     RFD_CHECK_ARG(row0 >= 0 && n <= g->book.rows() - row0, "rows [row0, row0 + n) are not all in the gallery");
     g->book.tags(row0, n, out);
+    return RFD_OK;
+}
+
+// ---- nearest (rfd.h, "nearest"; gallery_nearest_plan.h, kernels_gallery_nearest.hip) ----
+void rfd_gallery_nearest_config_default(rfd_gallery_nearest_config *cfg)
+{
+    if (!cfg) return;
+    memset(cfg, 0, sizeof *cfg);
+    cfg->mode = RFD_GALLERY_NEAREST_OTHER_ROW;
+    cfg->min_score = -INFINITY;
+    cfg->tag_mask = 0u;
+}
+
+int rfd_debug_gallery_nearest_plan(int rows, int row0, int n, int dim, int cus, rfd_gallery_nearest_plan *out)
+{
+    RFD_CHECK_ARG(out, "out is null");
+    memset(out, 0, sizeof *out);
+    RFD_CHECK_ARG(dim >= 32 && dim <= 1024 && dim % 32 == 0, "dim must be a multiple of 32 in 32..1024");
+    RFD_CHECK_ARG(rows >= 0 && row0 >= 0 && n >= 0 && n <= rows - row0 && cus >= 1, "rows [row0, row0 + n) are not all in the gallery, or cus < 1");
+    const GalleryNearestPlan p = gallery_nearest_plan(rows, row0, n, dim, cus); // n = 0: nothing to launch, grid 0
+    *out = {p.form, p.tile_rows, p.tiles, p.splits, p.blocks, p.blocks_per_split, p.grid, p.ws_bytes};
+    return RFD_OK;
+}
+
+// the checks of both forms, in the contract's order; *cfg: the call's configuration (the default where the caller passed none)
+static int gallery_nearest_check(const rfd_gallery *g, int row0, int n, const rfd_gallery_nearest_config *in, rfd_gallery_nearest_config *cfg)
+{
+    RFD_CHECK_ARG(g, "gallery is null");
+    RFD_CHECK_ARG(row0 >= 0 && n >= 0 && n <= g->book.rows() - row0, "rows [row0, row0 + n) are not all in the gallery");
+    rfd_gallery_nearest_config_default(cfg);
+    if (in) *cfg = *in;
+    RFD_CHECK_ARG(cfg->mode == RFD_GALLERY_NEAREST_OTHER_ROW || cfg->mode == RFD_GALLERY_NEAREST_OTHER_IDENTITY, "unknown mode");
+    for (int i = 0; i < 5; ++i) RFD_CHECK_ARG(cfg->reserved[i] == 0, "a reserved word is not 0");
+    return RFD_OK;
+}
+
+static int gallery_nearest_outputs(const float *scores, const int32_t *rows, const int32_t *ids)
+{
+    RFD_CHECK_ARG(scores && rows, "scores or rows is null");
+    RFD_CHECK_ARG((uintptr_t)scores % 4 == 0 && (uintptr_t)rows % 4 == 0 && (uintptr_t)ids % 4 == 0, "an output is not 4-byte aligned");
+    return RFD_OK;
+}
+
+// rows [row0, row0 + n), n >= 1, checked: the scan and the merge on the stream, outputs on the device
+static int gallery_nearest_enqueue(rfd_gallery *g, hipStream_t s, int row0, int n, const rfd_gallery_nearest_config &cfg, float *scores, int32_t *rows,
+                                   int32_t *ids)
+{
+    const GalleryBook &b = g->book;
+    RFD_TRY(g->nearest_ws.reserve((size_t)gallery_nearest_ws_bound(b.capacity(), b.dim(), g->cus))); // first call on this gallery
+    const uint16_t *live = nullptr;
+    RFD_TRY(gallery_search_mask(g, s, &live));
+    const GalleryNearestPlan plan = gallery_nearest_plan(b.rows(), row0, n, b.dim(), g->cus);
+    return launch_gallery_nearest((const bf16_t *)g->store.p, live, (const int32_t *)g->ids.p, (const uint32_t *)g->tags.p, b.rows(), b.dim(), row0, n, cfg.mode,
+                                  cfg.min_score, cfg.tag_mask, plan, (uint2 *)g->nearest_ws.p, scores, rows, ids, s);
+}
+
+int rfd_gallery_nearest_device(rfd_gallery *g, int row0, int n, const rfd_gallery_nearest_config *cfg, float *scores, int32_t *rows, int32_t *ids, int async)
+{
+    rfd_gallery_nearest_config c;
+    RFD_TRY(gallery_nearest_check(g, row0, n, cfg, &c));
+    if (n == 0) return RFD_OK;
+    RFD_TRY(gallery_nearest_outputs(scores, rows, ids));
+    RFD_HIP(hipSetDevice(ctx_device(g->ctx)));
+    const hipStream_t s = ctx_stream(g->ctx);
+    RFD_TRY(gallery_nearest_enqueue(g, s, row0, n, c, scores, rows, ids));
+    if (!async) RFD_HIP(hipStreamSynchronize(s));
+    return RFD_OK;
+}
+
+int rfd_gallery_nearest(rfd_gallery *g, int row0, int n, const rfd_gallery_nearest_config *cfg, float *scores, int32_t *rows, int32_t *ids)
+{
+    rfd_gallery_nearest_config c;
+    RFD_TRY(gallery_nearest_check(g, row0, n, cfg, &c));
+    if (n == 0) return RFD_OK;
+    RFD_TRY(gallery_nearest_outputs(scores, rows, ids));
+    RFD_HIP(hipSetDevice(ctx_device(g->ctx)));
+    const hipStream_t s = ctx_stream(g->ctx);
+    RFD_TRY(gallery_host_stage(g));
+    // the staging buffer holds a chunk's scores, rows and identities side by side; a chunk has left it before the next enters
+    const int chunk = (int)(rfd_gallery::kStageBytes / (3 * sizeof(float)));
+    for (int i = 0; i < n; i += chunk) {
+        const int m = std::min(chunk, n - i);
+        const size_t bytes = (size_t)m * sizeof(float);
+        float *d_s = (float *)g->stage.p;
+        int32_t *d_r = (int32_t *)(d_s + m), *d_i = d_r + m;
+        RFD_TRY(gallery_nearest_enqueue(g, s, row0 + i, m, c, d_s, d_r, d_i));
+        RFD_HIP(hipMemcpyAsync(g->pin, g->stage.p, 3 * bytes, hipMemcpyDeviceToHost, s));
+        RFD_HIP(hipStreamSynchronize(s));
+        memcpy(scores + i, g->pin, bytes);
+        memcpy(rows + i, g->pin + bytes, bytes);
+        if (ids) memcpy(ids + i, g->pin + 2 * bytes, bytes);
+    }
     return RFD_OK;
 }
 

@@ -1,5 +1,6 @@
 // kernels.h -- launch interfaces of the HIP kernels (all gfx950).
 #pragma once
+#include "gallery_nearest_plan.h"
 #include "jpeg_desc.h"
 #include "jpeg_entropy.h"
 #include "rfd_common.h"
@@ -250,6 +251,14 @@ int launch_gallery_live_range(uint16_t *live, int row0, int row1, hipStream_t s)
 // bf16 values [n][dim] in row-major order (device, 16-byte aligned) <-> rows [row0, row0 + n) of store, bit for bit
 int launch_gallery_import(const bf16_t *src, int n, int dim, int row0, bf16_t *store, hipStream_t s);
 int launch_gallery_export(const bf16_t *store, int row0, int n, int dim, bf16_t *out, hipStream_t s);
+// The self-join (rfd.h, "nearest"; kernels_gallery_nearest.hip): for every row a of [row0, row0 + n), the best live row b != a
+// that `mode` and the tag rule allow -> scores / out_rows / out_ids [n] (device; out_ids may be null); entries with
+// !(score >= min_score) or without a candidate become (-inf, -1, -1).  plan: gallery_nearest_plan(rows, row0, n, dim, cus); ws
+// holds plan.ws_bytes.  live / ids / tags as in the searches, each may be null (all live / all unlabelled / all 0).  Two
+// launches (scan, merge of the splits), no synchronisation.
+int launch_gallery_nearest(const bf16_t *store, const uint16_t *live, const int32_t *ids, const uint32_t *tags, int rows, int dim, int row0, int n, int mode,
+                           float min_score, uint32_t tag_mask, const GalleryNearestPlan &plan, uint2 *ws, float *scores, int32_t *out_rows, int32_t *out_ids,
+                           hipStream_t s);
 
 // ---------------------------------------------------------------- JPEG decode (kernels_jpeg.hip)
 // The parallel half of the baseline JPEG decoder (rfd.h, "JPEG decode"); the serial half is csrc/jpeg_parse.h on the host.  The

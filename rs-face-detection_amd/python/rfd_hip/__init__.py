@@ -32,6 +32,7 @@ COMM_ID_BYTES = 128
 MAX_FACE_TENSORS = 4   # RFD_MAX_FACE_TENSORS
 GALLERY_MAX_K = 32     # RFD_GALLERY_MAX_K
 NO_IDENTITY = -1       # RFD_GALLERY_NO_IDENTITY: an unlabelled gallery row, an identity of its own
+NEAREST_OTHER_ROW, NEAREST_OTHER_IDENTITY = 0, 1   # RFD_GALLERY_NEAREST_*: the modes of Gallery.nearest
 
 # debug_set_conv_tile / op_kernels_static: the forced tiles, enum ConvTile of csrc/kernels.h (each value's meaning is there)
 (TILE_HEURISTIC, TILE_128, TILE_256x128, TILE_256x64, TILE_NO_128, TILE_NO_PW_STREAM, TILE_PERSISTENT, TILE_GENERIC, TILE_PW_STREAM,
@@ -124,6 +125,15 @@ class rfd_liveness_config(C.Structure):
                 ("out_h", C.c_int32 * MAX_FACE_TENSORS), ("reserved", C.c_int32 * 4)]
 
 
+class rfd_gallery_nearest_config(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("min_score", C.c_float), ("tag_mask", C.c_uint32), ("reserved", C.c_int32 * 5)]
+
+
+class rfd_gallery_nearest_plan(C.Structure):
+    _fields_ = [("form", C.c_int32), ("tile_rows", C.c_int32), ("tiles", C.c_int32), ("splits", C.c_int32), ("blocks", C.c_int32),
+                ("blocks_per_split", C.c_int32), ("grid", C.c_int64), ("ws_bytes", C.c_int64)]
+
+
 class rfd_jpeg_info(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("sampling", C.c_int32),
                 ("restart_interval", C.c_int32), ("reserved", C.c_int32 * 3)]
@@ -172,6 +182,7 @@ API_SYMBOLS = [
     "rfd_gallery_set_identities", "rfd_gallery_get_identities", "rfd_gallery_identities", "rfd_gallery_search_identities",
     "rfd_gallery_search_identities_device",
     "rfd_gallery_set_tags", "rfd_gallery_get_tags", "rfd_gallery_search_filtered", "rfd_gallery_search_filtered_device",
+    "rfd_gallery_nearest_config_default", "rfd_gallery_nearest", "rfd_gallery_nearest_device", "rfd_debug_gallery_nearest_plan",
     "rfd_jpeg_info", "rfd_decode_jpeg_batch_device", "rfd_decode_jpeg_batch", "rfd_set_decode_threads", "rfd_debug_jpeg_coefficients",
     "rfd_set_jpeg_entropy", "rfd_jpeg_last_paths", "rfd_debug_jpeg_intervals", "rfd_debug_jpeg_coefficients_device",
     "rfd_jpeg_orientation", "rfd_set_jpeg_orientation", "rfd_jpeg_last_orientations",
@@ -312,6 +323,11 @@ def load_library(path=None):
     L.rfd_gallery_get_tags.argtypes = [vp, ci, ci, vp]
     L.rfd_gallery_search_filtered.argtypes = [vp, vp, ci, ci, C.c_float, vp, vp, vp, vp, vp]
     L.rfd_gallery_search_filtered_device.argtypes = [vp, vp, ci, ci, C.c_float, vp, vp, vp, vp, vp, ci]
+    L.rfd_gallery_nearest_config_default.argtypes = [C.POINTER(rfd_gallery_nearest_config)]
+    L.rfd_gallery_nearest_config_default.restype = None
+    L.rfd_gallery_nearest.argtypes = [vp, ci, ci, C.POINTER(rfd_gallery_nearest_config), vp, vp, vp]
+    L.rfd_gallery_nearest_device.argtypes = [vp, ci, ci, C.POINTER(rfd_gallery_nearest_config), vp, vp, vp, ci]
+    L.rfd_debug_gallery_nearest_plan.argtypes = [ci, ci, ci, ci, ci, C.POINTER(rfd_gallery_nearest_plan)]
     L.rfd_gallery_save.argtypes = [vp, C.c_char_p]
     L.rfd_gallery_load.argtypes = [vp, C.c_char_p, ci, C.POINTER(vp)]
     L.rfd_gallery_file_info.argtypes = [C.c_char_p, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
@@ -448,6 +464,14 @@ def _bf16_bits(values):
     bits = np.ascontiguousarray(values, np.float32).view(np.uint32)
     assert not np.any(bits & 0xffff), "values are not exact in bf16"
     return (bits >> 16).astype("<u2")
+
+
+def gallery_nearest_plan(rows, row0, n, dim, cus):
+    """how Gallery.nearest(row0, n) decomposes on a gallery of `rows` rows and a device of `cus` compute units
+    (rfd_debug_gallery_nearest_plan; host only) -> dict of form, tile_rows, tiles, splits, blocks, blocks_per_split, grid, ws_bytes"""
+    p = rfd_gallery_nearest_plan()
+    _check(load_library().rfd_debug_gallery_nearest_plan(int(rows), int(row0), int(n), int(dim), int(cus), C.byref(p)))
+    return {k: int(getattr(p, k)) for k, _ in p._fields_}
 
 
 def gallery_file_write(path, values_bf16_as_f32, live):
@@ -799,6 +823,27 @@ class Gallery:
         """the same on raw device addresses (mask, value: u32 [n] each), by the conventions of search_device"""
         _check(self._L.rfd_gallery_search_filtered_device(self._g, queries_ptr, int(n), int(k), float(min_score), mask_ptr, value_ptr, scores_ptr, rows_ptr,
                                                           ids_ptr, int(async_)))
+
+    def _nearest_config(self, mode, min_score, tag_mask):
+        cfg = rfd_gallery_nearest_config()
+        self._L.rfd_gallery_nearest_config_default(C.byref(cfg))
+        cfg.mode, cfg.min_score, cfg.tag_mask = int(mode), float(min_score), int(tag_mask) & 0xFFFFFFFF
+        return cfg
+
+    def nearest(self, row0, n, mode=NEAREST_OTHER_ROW, min_score=-np.inf, tag_mask=0):
+        """for every row a of [row0, row0 + n): the best live row b != a (mode NEAREST_OTHER_IDENTITY: of another identity) with
+        (tag[a] & tag_mask) == (tag[b] & tag_mask) -> (scores [n] f32, rows [n] i32, ids [n] i32); (-inf, -1, -1) where a is
+        removed or nothing reaches min_score (rfd.h, "nearest")"""
+        n = int(n)
+        scores, rows, ids = np.zeros(max(n, 0), np.float32), np.zeros(max(n, 0), np.int32), np.zeros(max(n, 0), np.int32)
+        cfg = self._nearest_config(mode, min_score, tag_mask)
+        _check(self._L.rfd_gallery_nearest(self._g, int(row0), n, C.byref(cfg), scores.ctypes.data, rows.ctypes.data, ids.ctypes.data))
+        return scores, rows, ids
+
+    def nearest_device(self, row0, n, scores_ptr, rows_ptr, ids_ptr, mode=NEAREST_OTHER_ROW, min_score=-np.inf, tag_mask=0, async_=False):
+        """the same into raw device addresses ([n] each, 4-byte aligned; ids_ptr may be None), by the conventions of search_device"""
+        cfg = self._nearest_config(mode, min_score, tag_mask)
+        _check(self._L.rfd_gallery_nearest_device(self._g, int(row0), int(n), C.byref(cfg), scores_ptr, rows_ptr, ids_ptr, int(async_)))
 
 
 class RetinaFaceDetection:

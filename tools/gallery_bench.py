@@ -27,6 +27,13 @@ same process: --repeats windows of plain searches, then for each --tenant-layout
 most blocks hold nothing of it), and the filtered search is timed with mask = 0xFFFFFFFF and, per query, the tenant of the row
 the query is a noisy copy of; then the plain windows again; the spread of the two plain series is the yardstick.  The filtered
 scan reads the 64 bytes of a block's tags only in a block with a key that passes a list's filter.
+
+--nearest N [N ...] measures the self-join (rfd_gallery_nearest_device of the first N rows: every row's best other row) against
+the route the interface offered before it, in the same process: rfd_gallery_search_device of those rows' stored values with k = 2
+(one pass over the gallery per 32 of them; the caller then drops the self-match).  Windows of the two alternate, --repeats of
+each, a window holding as many calls as fit about half a second (at most --steps); the spread of the search route's windows is the
+noise.  Both answers are compared.  Two floors: the matrix work N * rows * dim * 2 at 2.5 PFLOP/s, and the bytes the scan reads,
+ceil(N / tile_rows) times the gallery, at the streaming rate above.  Keep N <= 65 536 at 1 M rows.
 Prints one JSON line per size."""
 import argparse
 import json
@@ -39,6 +46,7 @@ sys.path.insert(0, os.path.join(ROOT, "rs-face-detection_amd", "python"))
 
 DIM, NQ, K = 512, 32, 5
 STREAM_RATE = 6.2e12   # bytes / s
+MFMA_RATE = 2.5e15     # bf16 FLOP / s, dense peak
 CHUNK = 100_000
 
 
@@ -51,7 +59,8 @@ def main():
     ap.add_argument("--identities", type=int, default=0, help="label the rows with this many identities and time the identity search")
     ap.add_argument("--tenants", type=int, default=0, help="tag the rows with this many tenants and time the filtered search of one tenant per query")
     ap.add_argument("--tenant-layout", nargs="+", choices=("mod", "runs"), default=["mod", "runs"], help="row %% T, or T contiguous runs of rows")
-    ap.add_argument("--repeats", type=int, default=5, help="timed windows per series of a --removed, --identities or --tenants run")
+    ap.add_argument("--nearest", type=int, nargs="+", default=[], help="time the self-join of the first N rows against the search route to the same answer")
+    ap.add_argument("--repeats", type=int, default=5, help="timed windows per series of a --removed, --identities, --tenants or --nearest run")
     args = ap.parse_args()
     assert 0.0 <= args.removed < 1.0 and args.identities >= 0 and args.tenants >= 0
     import torch
@@ -207,6 +216,66 @@ def main():
             for name, w in series.items():
                 masked.update({"filtered_" + name: stats(w), name + "_minus_plain_median_ms": round(float(np.median(w)) - base, 4),
                                name + "_over_plain": round(float(np.median(w)) / base, 3)})
+        if args.nearest:
+            import numpy as np
+            cus = torch.cuda.get_device_properties(0).multi_processor_count
+            masked["nearest"] = []
+            for n_a in args.nearest:
+                n_a = min(n_a, rows)
+                plan = rfd_hip.gallery_nearest_plan(rows, 0, n_a, DIM, cus)
+                qa = g16[:n_a].float().contiguous()                  # the stored values of the rows: what get_rows returns
+                n_s, n_r, n_i = (torch.zeros(n_a, dtype=t, device=dev) for t in (torch.float32, torch.int32, torch.int32))
+                s_s, s_r = torch.zeros(n_a, 2, device=dev), torch.zeros(n_a, 2, dtype=torch.int32, device=dev)
+                torch.cuda.synchronize()
+
+                def join(n):
+                    for _ in range(n):
+                        gal.nearest_device(0, n_a, n_s.data_ptr(), n_r.data_ptr(), n_i.data_ptr(), async_=True)
+                    det.sync()
+
+                def route(n):
+                    for _ in range(n):
+                        gal.search_device(qa.data_ptr(), n_a, 2, s_s.data_ptr(), s_r.data_ptr(), async_=True)
+                    det.sync()
+
+                def timed(f):
+                    f(1)                                                 # first launches, and how many calls a window holds
+                    t0 = time.perf_counter()
+                    f(1)
+                    calls = max(1, min(args.steps, int(0.5 / max(time.perf_counter() - t0, 1e-6))))
+                    return lambda: _window(f, calls), calls
+
+                def _window(f, calls):
+                    t0 = time.perf_counter()
+                    f(calls)
+                    return (time.perf_counter() - t0) * 1e3 / calls
+
+                join_w, join_calls = timed(join)
+                route_w, route_calls = timed(route)
+                joins, routes = [], []
+                for _ in range(args.repeats):                           # alternating windows
+                    joins.append(round(join_w(), 4))
+                    routes.append(round(route_w(), 4))
+                # the two answers: the search's two best rows with the row itself dropped
+                sr, ss, nr, ns = s_r.cpu().numpy(), s_s.cpu().numpy(), n_r.cpu().numpy(), n_s.cpu().numpy()
+                other = np.where(sr[:, 0] == np.arange(n_a), 1, 0)
+                same_rows = float((sr[np.arange(n_a), other] == nr).mean())
+                same_bits = float((ss[np.arange(n_a), other].view(np.uint32) == ns.view(np.uint32)).mean())
+                stats = lambda w: {"windows_ms": w, "median_ms": round(float(np.median(w)), 4), "min_ms": min(w), "max_ms": max(w)}
+                j_ms, r_ms = float(np.median(joins)), float(np.median(routes))
+                gallery_bytes = (rows + 15) // 16 * 16 * DIM * 2
+                mfma_floor = n_a * float(rows) * DIM * 2 / MFMA_RATE * 1e3
+                stream_floor = plan["tiles"] * gallery_bytes / STREAM_RATE * 1e3
+                masked["nearest"].append({
+                    "n": n_a, "form": plan["form"], "tile_rows": plan["tile_rows"], "tiles": plan["tiles"], "splits": plan["splits"], "grid": plan["grid"],
+                    "repeats": args.repeats, "nearest_calls_per_window": join_calls, "search_route_calls_per_window": route_calls,
+                    "nearest": stats(joins), "search_route_k2_groups_of_32": stats(routes), "search_route_spread_ms": round(max(routes) - min(routes), 4),
+                    "search_route_over_nearest": round(r_ms / j_ms, 2),
+                    "mfma_floor_ms_at_2.5_PF": round(mfma_floor, 4), "fraction_of_mfma_floor": round(mfma_floor / j_ms, 3),
+                    "stream_floor_ms_at_6.2_TB_per_s": round(stream_floor, 4), "fraction_of_stream_floor": round(stream_floor / j_ms, 3),
+                    "achieved_TFLOP_per_s": round(n_a * float(rows) * DIM * 2 / j_ms / 1e9, 1),
+                    "rows_equal_search_route": same_rows, "score_bits_equal_search_route": same_bits})
+                del qa, n_s, n_r, n_i, s_s, s_r
         theirs(args.warmup)
         t0 = time.perf_counter()
         ref = theirs(args.steps)
