@@ -1032,6 +1032,15 @@ RFD_API int rfd_debug_set_concurrency(rfd_ctx *ctx, int multi_stream, int split_
 /* Sets the device word through which a chunk workgroup of the dense-crowd NMS -- or a wave of a ring convolution -- reports that
  * it gave up waiting (tests: the next call that synchronises must then fail with RFD_ERR_HIP and clear the word). */
 RFD_API int rfd_debug_poke_nms_flag(rfd_ctx *ctx, int value);
+/* Test hook: what the alignment's set-up kernel decides, which the crops show only rounded to 1/32 pixel.  boxes [n][5],
+ * kps [n][10], found [n] and cfg as rfd_align_faces takes them, img_w / img_h [n] = the frame sizes (the set-up reads no
+ * pixels); all host pointers, n <= max_batch_size.  Runs align_setup_kernel as rfd_align_faces launches it and copies back, per
+ * face: mode (= the status), M [n][6] (the INVERTED map, crop -> frame, as cv::warpAffine computes it; zeros unless mode 0),
+ * roi [n][4] = x0, y0, rw, rh and scale [n][2] = scale_x, scale_y of the fallback (zeros unless it was entered; the scales only
+ * for mode 1), area_fast [n]. */
+RFD_API int rfd_debug_align_setup(rfd_ctx *ctx, int n, const float *boxes, const float *kps, const int32_t *found,
+                                  const int32_t *img_w, const int32_t *img_h, const rfd_alignment_config *cfg, int32_t *mode,
+                                  double *M, int32_t *roi, double *scale, int32_t *area_fast);
 /* The list of PERSISTENT kernels (one workgroup per CU, looping over work items) and the dynamic LDS every launch of one
  * requests -- always the CU's whole 160 KiB, so that no other kernel's workgroup can share the CU.
  * Needs no context and no GPU: tests/test_build_cpu.py walks it against the kernels of the code object.  Returns the number

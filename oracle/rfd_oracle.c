@@ -687,6 +687,15 @@ static void similarity_errors(const float *src, const float *dst, int n, const d
     }
 }
 
+/* the key LMedS orders an error by: its bit pattern as an int, the largest int for a NaN of either sign */
+static int32_t lmeds_error_key(float e)
+{
+    int32_t b;
+    if (e != e) return INT32_MAX;
+    memcpy(&b, &e, 4);
+    return b;
+}
+
 #define RFD_ORACLE_MAX_PTS 64
 /* the index pairs LMeDS samples for `n` points (at most `cap` pairs written); returns their number */
 RFD_API int rfd_oracle_lmeds_samples(int n, int *pairs, int cap)
@@ -726,14 +735,15 @@ RFD_API int rfd_oracle_estimate_similarity_lmeds(const float *src, const float *
         similarity_2pt(src, dst, pairs[2 * s], pairs[2 * s + 1], Ms);
         similarity_errors(src, dst, n, Ms, err);
         /* std::nth_element(errf.ptr<int>(), ... + count / 2, ...): the f32 errors ordered by their BIT PATTERNS as ints (they are
-         * >= +0, or NaN -- which then ranks above every number); the median is element count / 2 of that order */
+         * >= +0, or NaN); the median is element count / 2 of that order.  EVERY NaN ranks above every number here: as an int a
+         * NaN whose sign bit is set would rank below them all, and which sign an invalid operation gives its NaN is the
+         * platform's choice (x86: set), so OpenCV has no single behaviour to copy */
         for (int i = 0; i < n; ++i) srt[i] = err[i];
         for (int i = 1; i < n; ++i) {
             const float v = srt[i];
-            int32_t vb, jb;
-            memcpy(&vb, &v, 4);
+            const int32_t vb = lmeds_error_key(v);
             int j = i - 1;
-            while (j >= 0 && (memcpy(&jb, &srt[j], 4), jb > vb)) { srt[j + 1] = srt[j]; --j; }
+            while (j >= 0 && lmeds_error_key(srt[j]) > vb) { srt[j + 1] = srt[j]; --j; }
             srt[j + 1] = v;
         }
         const double median = (double)srt[n / 2];

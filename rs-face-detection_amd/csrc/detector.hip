@@ -1545,6 +1545,22 @@ static int resolve_align_cfg(const rfd_alignment_config **cfg, rfd_alignment_con
     return RFD_OK;
 }
 
+// what the set-up kernel of align_impl needs: the descriptors in c->imgs, the selection, the template, its two outputs
+static int align_setup_params(rfd_ctx *c, int n, const float *d_box, const float *d_kps, const int *d_found,
+                              const rfd_alignment_config *cfg, AlignParams *ap)
+{
+    RFD_TRY(c->align_faces.reserve((size_t)n * sizeof(AlignFace)));
+    RFD_TRY(c->align_status.reserve((size_t)n * sizeof(int)));
+    memset(ap, 0, sizeof *ap);
+    ap->imgs = (const PreImage *)c->imgs.p;
+    ap->box = d_box; ap->kps = d_kps; ap->found = d_found;
+    memcpy(ap->std_lmk, cfg->standard_landmarks, sizeof ap->std_lmk);
+    ap->out_w = cfg->out_w; ap->out_h = cfg->out_h; ap->n = n;
+    ap->faces = (AlignFace *)c->align_faces.p;
+    ap->status = (int *)c->align_status.p;
+    return RFD_OK;
+}
+
 // alignment of the frames whose descriptors sit in c->imgs (the last staged batch); selection results are device
 // arrays; crops and status are copied to the host pointers
 static int align_impl(rfd_ctx *c, int n, const float *d_box, const float *d_kps, const int *d_found,
@@ -1553,17 +1569,9 @@ static int align_impl(rfd_ctx *c, int n, const float *d_box, const float *d_kps,
     rfd_alignment_config def;
     RFD_TRY(resolve_align_cfg(&cfg, &def));
     const size_t crop = (size_t)cfg->out_w * cfg->out_h * 3;
-    RFD_TRY(c->align_faces.reserve((size_t)n * sizeof(AlignFace)));
     RFD_TRY(c->align_out.reserve((size_t)n * crop));
-    RFD_TRY(c->align_status.reserve((size_t)n * sizeof(int)));
     AlignParams ap;
-    memset(&ap, 0, sizeof ap);
-    ap.imgs = (const PreImage *)c->imgs.p;
-    ap.box = d_box; ap.kps = d_kps; ap.found = d_found;
-    memcpy(ap.std_lmk, cfg->standard_landmarks, sizeof ap.std_lmk);
-    ap.out_w = cfg->out_w; ap.out_h = cfg->out_h; ap.n = n;
-    ap.faces = (AlignFace *)c->align_faces.p;
-    ap.status = (int *)c->align_status.p;
+    RFD_TRY(align_setup_params(c, n, d_box, d_kps, d_found, cfg, &ap));
     ap.out = (uint8_t *)c->align_out.p;
     RFD_TRY(launch_face_align(ap, c->stream));
     RFD_HIP(hipMemcpyAsync(out_crops, ap.out, (size_t)n * crop, hipMemcpyDeviceToHost, c->stream));
@@ -1582,6 +1590,42 @@ int rfd_align_faces(rfd_ctx *c, const rfd_image *imgs, int n, const float *boxes
     RFD_TRY(sel_upload(c, n, boxes, kps, found));
     const SelView v = sel_view(c, n);
     return align_impl(c, n, v.box, v.kps, v.found, cfg, out_crops, status);
+}
+
+// the set-up records of n faces on frames of which only the sizes exist: descriptors without pixels, then the launch of align_impl
+int rfd_debug_align_setup(rfd_ctx *c, int n, const float *boxes, const float *kps, const int32_t *found, const int32_t *img_w,
+                          const int32_t *img_h, const rfd_alignment_config *cfg, int32_t *mode, double *M, int32_t *roi,
+                          double *scale, int32_t *area_fast)
+{
+    RFD_CHECK_ARG(c && boxes && kps && found && img_w && img_h && mode && M && roi && scale && area_fast, "null argument");
+    RFD_TRY(check_batch(c, n, "batch of", " faces"));
+    rfd_alignment_config def;
+    RFD_TRY(resolve_align_cfg(&cfg, &def));
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    PreImage *pis;
+    float *pin_scales;
+    RFD_TRY(acquire_frame_slot(c, &pis, &pin_scales));
+    memset(pis, 0, (size_t)n * sizeof(PreImage));
+    for (int i = 0; i < n; ++i) { pis[i].w = img_w[i]; pis[i].h = img_h[i]; }
+    RFD_HIP(hipMemcpyAsync(c->imgs.p, pis, n * sizeof(PreImage), hipMemcpyHostToDevice, c->stream));
+    RFD_TRY(c->frame_ring.record(c->stream));
+    RFD_TRY(sel_upload(c, n, boxes, kps, found));
+    const SelView v = sel_view(c, n);
+    AlignParams ap;
+    RFD_TRY(align_setup_params(c, n, v.box, v.kps, v.found, cfg, &ap));
+    RFD_TRY(launch_face_align_setup(ap, c->stream));
+    std::vector<AlignFace> faces(n);
+    RFD_HIP(hipMemcpyAsync(faces.data(), ap.faces, (size_t)n * sizeof(AlignFace), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < n; ++i) {
+        const AlignFace &f = faces[i];
+        mode[i] = f.mode;
+        for (int k = 0; k < 6; ++k) M[6 * i + k] = f.M[k];
+        roi[4 * i] = f.x0; roi[4 * i + 1] = f.y0; roi[4 * i + 2] = f.rw; roi[4 * i + 3] = f.rh;
+        scale[2 * i] = f.scale_x; scale[2 * i + 1] = f.scale_y;
+        area_fast[i] = f.area_fast;
+    }
+    return check_nms_flag(c);
 }
 
 int rfd_detect_select_align_batch(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_selection_config *sel_cfg, int is_enroll,

@@ -135,6 +135,8 @@ struct AlignParams {
     int cap, face0;
 };
 int launch_face_align(const AlignParams &p, hipStream_t s);
+// the set-up launch of the two aligners alone: faces and status of p, no pixel read (rfd_debug_align_setup)
+int launch_face_align_setup(const AlignParams &p, hipStream_t s);
 
 // The model inputs of FaceQuality::call / FaceExtraction::call (face_quality.rs:43-44,56-101, face_extraction.rs:38-77):
 // cv::resize(INTER_LINEAR) of the aligned crop to the model's image_size, COLOR_BGR2RGB, (p - mean) * scale, NHWC -> NCHW.

@@ -190,6 +190,11 @@ __device__ __forceinline__ void similarity_errors5(const float *src, const float
     }
 }
 
+// The key LMedS orders an error by: its bit pattern as an int, the largest int for a NaN of either sign.  As an int a NaN whose
+// sign bit is set would rank below every number, and which sign an invalid operation gives its NaN is the platform's choice
+// (DESIGN.md section 2), so EVERY NaN ranks above every number.  As lmeds_error_key in oracle/rfd_oracle.c.
+__device__ __forceinline__ int lmeds_error_key(float e) { return e != e ? 0x7fffffff : __float_as_int(e); }
+
 // returns false: no model (the reference's empty matrix).  Every array is indexed at compile time (no scratch: tests/test_build_cpu.py).
 __device__ bool estimate_similarity_lmeds5(const float *src, const float *dst, double M[6])
 {
@@ -203,8 +208,8 @@ __device__ bool estimate_similarity_lmeds5(const float *src, const float *dst, d
         double Ms[6];
         similarity_2pt(src, dst, i0, i1, Ms);
         similarity_errors5(src, dst, Ms, err);
-        // element 2 of the errors ordered by their bit patterns as ints (std::nth_element on errf.ptr<int>(): NaN above every number)
-        int e0 = __float_as_int(err[0]), e1 = __float_as_int(err[1]), e2 = __float_as_int(err[2]), e3 = __float_as_int(err[3]), e4 = __float_as_int(err[4]);
+        // element 2 of the errors ordered by their keys (std::nth_element on errf.ptr<int>())
+        int e0 = lmeds_error_key(err[0]), e1 = lmeds_error_key(err[1]), e2 = lmeds_error_key(err[2]), e3 = lmeds_error_key(err[3]), e4 = lmeds_error_key(err[4]);
 #define RFD_CS(a, b) { const int lo_ = min(a, b), hi_ = max(a, b); a = lo_; b = hi_; }
         RFD_CS(e0, e1) RFD_CS(e3, e4) RFD_CS(e2, e4) RFD_CS(e2, e3) RFD_CS(e1, e4) RFD_CS(e0, e3) RFD_CS(e0, e2) RFD_CS(e1, e3) RFD_CS(e1, e2)
 #undef RFD_CS
@@ -361,10 +366,16 @@ __global__ void __launch_bounds__(256) align_warp_kernel(AlignParams p)
 
 constexpr int kMaxGridY = 65535; // faces per launch of the kernels that take the face from blockIdx.y
 
-int launch_face_align(const AlignParams &p, hipStream_t s)
+int launch_face_align_setup(const AlignParams &p, hipStream_t s)
 {
     hipLaunchKernelGGL(align_setup_kernel, dim3(ceil_div(p.n, 64)), dim3(64), 0, s, p);
     RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
+int launch_face_align(const AlignParams &p, hipStream_t s)
+{
+    RFD_TRY(launch_face_align_setup(p, s));
     AlignParams q = p;
     for (q.face0 = 0; q.face0 < p.n; q.face0 += kMaxGridY) {
         hipLaunchKernelGGL(align_warp_kernel, dim3(ceil_div(p.out_w * p.out_h, 256), min(p.n - q.face0, kMaxGridY)), dim3(256), 0, s, q);
@@ -412,8 +423,7 @@ __global__ void __launch_bounds__(256) align_warp_tensor_kernel(AlignParams p, F
 
 int launch_face_align_tensors(const AlignParams &a, const FaceTensorParams &t, hipStream_t s)
 {
-    hipLaunchKernelGGL(align_setup_kernel, dim3(ceil_div(a.n, 64)), dim3(64), 0, s, a);
-    RFD_HIP(hipGetLastError());
+    RFD_TRY(launch_face_align_setup(a, s));
     if (a.total && !a.out && !t.k) return RFD_OK; // a face list alone: the status is all that was asked for
     AlignParams q = a;
     for (q.face0 = 0; q.face0 < a.n; q.face0 += kMaxGridY) {

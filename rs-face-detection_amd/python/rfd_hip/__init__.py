@@ -167,7 +167,7 @@ API_SYMBOLS = [
     "rfd_get_conv_profile", "rfd_get_op_profile", "rfd_debug_tensor_io", "rfd_debug_run_ops", "rfd_debug_run_chain", "rfd_debug_pass_chains", "rfd_debug_buffer_io",
     "rfd_debug_set_conv_tile", "rfd_debug_op_kernels", "rfd_debug_op_kernels_static", "rfd_debug_set_concurrency", "rfd_debug_persistent_kernel", "rfd_debug_poke_nms_flag", "rfd_selection_config_default",
     "rfd_select_faces", "rfd_detect_select_batch", "rfd_save_weights", "rfd_load_weights",
-    "rfd_alignment_config_default", "rfd_align_faces", "rfd_detect_select_align_batch",
+    "rfd_alignment_config_default", "rfd_align_faces", "rfd_detect_select_align_batch", "rfd_debug_align_setup",
     "rfd_host_alloc", "rfd_host_free", "rfd_submit_batch", "rfd_collect_batch",
     "rfd_comm_get_unique_id", "rfd_comm_init", "rfd_comm_info", "rfd_gather_detections", "rfd_comm_destroy",
     "rfd_face_tensor_config_quality", "rfd_face_tensor_config_extraction", "rfd_face_tensors",
@@ -273,6 +273,7 @@ def load_library(path=None):
     L.rfd_alignment_config_default.restype = None
     L.rfd_align_faces.argtypes = [vp, C.POINTER(rfd_image), ci, vp, vp, vp, vp, vp, vp]
     L.rfd_detect_select_align_batch.argtypes = [vp, C.POINTER(rfd_image), ci, vp, ci, vp, vp, vp, vp, vp, vp]
+    L.rfd_debug_align_setup.argtypes = [vp, ci] + [vp] * 11
     for f in (L.rfd_face_tensor_config_quality, L.rfd_face_tensor_config_extraction):
         f.argtypes = [C.POINTER(rfd_face_tensor_config)]
         f.restype = None
@@ -1215,6 +1216,29 @@ class RetinaFaceDetection:
         _check(self._L.rfd_align_faces(self._ctx, arr, n, ob.ctypes.data, ok.ctypes.data, fd.ctypes.data, C.addressof(c),
                                        crops.ctypes.data, status.ctypes.data))
         return crops, status
+
+    def debug_align_setup(self, sizes, selected, image_size=None, standard_landmarks=None):
+        """Test hook: the records align_setup_kernel leaves for faces on frames of sizes [(h, w)] (no pixels are read); selected
+        as align_faces takes it.  -> dict(mode [n], M [n, 2, 3] f64: the inverted map, roi [n, 4]: x0, y0, rw, rh,
+        scale [n, 2] f64: scale_x, scale_y, area_fast [n])."""
+        n = len(selected)
+        ob, ok, fd = np.zeros((n, 5), np.float32), np.zeros((n, 10), np.float32), np.zeros(n, np.int32)
+        for i, (b, k) in enumerate(selected):
+            if b is not None:
+                ob[i] = b
+                fd[i] |= 1
+            if k is not None:
+                ok[i] = np.asarray(k, np.float32).reshape(10)
+                fd[i] |= 2
+        hh = np.array([s[0] for s in sizes], np.int32)
+        ww = np.array([s[1] for s in sizes], np.int32)
+        c = self._align_cfg(image_size, standard_landmarks)
+        out = dict(mode=np.zeros(n, np.int32), M=np.zeros((n, 2, 3), np.float64), roi=np.zeros((n, 4), np.int32),
+                   scale=np.zeros((n, 2), np.float64), area_fast=np.zeros(n, np.int32))
+        _check(self._L.rfd_debug_align_setup(self._ctx, n, ob.ctypes.data, ok.ctypes.data, fd.ctypes.data, ww.ctypes.data,
+                                             hh.ctypes.data, C.addressof(c), out["mode"].ctypes.data, out["M"].ctypes.data,
+                                             out["roi"].ctypes.data, out["scale"].ctypes.data, out["area_fast"].ctypes.data))
+        return out
 
     def detect_select_align(self, frames, is_enroll=False, sel_cfg=None, image_size=None, standard_landmarks=None):
         """FacePipeline::extract lines 198-216: detect, select, align -> (selected list, crops, status)."""
