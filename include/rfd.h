@@ -978,6 +978,70 @@ RFD_API int rfd_jpeg_scaled_size(const uint8_t *bytes, size_t len, int denom, in
  * one byte per block in the block order and with the capacity convention of rfd_debug_jpeg_coefficients. */
 RFD_API int rfd_debug_jpeg_block_counts(const uint8_t *bytes, size_t len, int denom, uint8_t *count, size_t cap_blocks, size_t *blocks);
 
+/* ---- views: detection over overlapping views of a frame, merged on the device.  No counterpart in the reference, whose
+ *      RetinaFaceDetection::call letterboxes one image (face_detection.rs:131-198): a 1080p frame is then read at 1/3 scale, a
+ *      4K frame at 1/6, and a face below about 50 px (100 px) meets no anchor.  Opt-in: no other entry changes.
+ *
+ *      A VIEW is a rectangle of a frame that goes through the network as an image of its own: letterboxed to the network size
+ *      like a frame, one slot of the network batch.  The views of a frame may overlap and may include the whole frame.  The
+ *      candidates of all views of a frame are decoded into ONE list in frame pixels; one sort and one greedy NMS run per
+ *      FRAME, and the result is an ordinary rfd_dets slab [n_frames][max_det] that rfd_select_faces, rfd_align_detections, the
+ *      face list and the liveness entries take as it is.
+ *
+ *      The rule, per candidate of a view, in NETWORK pixels on the clipped box (x1, y1, x2, y2), m = edge_margin, new_w x new_h
+ *      the letterboxed extent of the view: for every set bit of the view's `inner` the matching inequality must hold,
+ *          left x1 >= m,  top y1 >= m,  right x2 <= (float)(new_w - 1) - m,  bottom y2 <= (float)(new_h - 1) - m,
+ *      else the candidate is dropped (a comparison with a NaN is false).  A face cut by an inner tile edge is thus left to the
+ *      neighbouring tile, or to the full view, where it is whole.  Then X = x / det_scale + (float)x_offset in f32 (one
+ *      division, one addition, each rounded) for the four box and ten landmark coordinates; the score is untouched.
+ *      Order: score descending, then the view's position v among its frame's views, then the anchor -- total, deterministic.
+ *      NMS runs in frame pixels with the context's iou_threshold, so duplicates from different scales meet in one unit.
+ *
+ *      Argument rules.  views: host, sorted by frame; every view non-empty and inside its frame; 1 <= n_views <=
+ *      max_batch_size; edge_margin >= 0 and finite; `inner` uses bits 0..3 only: else RFD_ERR_INVALID_ARG, and a view that
+ *      letterboxes to an empty image refuses the call like such a frame does.  A frame with no view yields count 0.
+ *      Capacity, both RFD_ERR_CAPACITY: n_frames * Vmax <= max_batch_size, Vmax the most views any frame of the call has (the
+ *      merge works in the context's per-image buffers, a frame taking Vmax of them); and Vmax * anchors must fit the NMS
+ *      kernel's LDS bitmap -- 18 views at 640x640.  A refused call enqueues nothing.
+ *      Cost: from 17 409 candidate slots per frame up (two views at 640x640) the NMS is the one-workgroup-per-frame streaming
+ *      form; the register and chunked forms stop there ("views").
+ *
+ *      edge_margin: rfd_view_config_default gives 4 network pixels.  That is a CHOSEN value, not tuned on data: this
+ *      repository has no trained weights to tune it on. ---- */
+typedef struct rfd_view {
+    int32_t frame;  /* index into frames[] */
+    int32_t x, y;   /* top-left corner in the frame, pixels */
+    int32_t w, h;   /* extent, pixels */
+    uint32_t inner; /* bit 0 left, 1 top, 2 right, 3 bottom: that side of the view lies inside the frame, not on its border */
+} rfd_view;
+typedef struct rfd_view_config {
+    int32_t tile_w, tile_h; /* tile extent in frame pixels */
+    int32_t overlap;        /* least overlap of neighbouring tiles, 0 <= overlap < tile_w, tile_h */
+    int32_t full_view;      /* non-zero: the whole frame is the first view when there is more than one tile */
+    float edge_margin;      /* network pixels; not used by the plan, carried for the detect calls */
+} rfd_view_config;
+/* tile = the network size (scale 1), overlap = net_w / 5, full_view = 1, edge_margin = 4.0f */
+RFD_API void rfd_view_config_default(rfd_view_config *cfg, int net_w, int net_h);
+/* The views of one frame, host only (no context, no device).  Per axis of extent W, tile t, overlap o: W <= t gives one tile
+ * [0, W); else n = ceil((W - o) / (t - o)) tiles of extent t, tile i at floor(i * (W - t) / (n - 1)) -- the last ends at W,
+ * neighbours overlap by at least o, every pixel is covered.  Order: the whole frame (inner 0) if full_view and more than one
+ * tile, then the tiles row-major, `inner` from the geometry.  *count is always written; count > cap: RFD_ERR_CAPACITY, nothing
+ * else written.  overlap outside [0, tile), a non-positive extent, frame < 0: RFD_ERR_INVALID_ARG, *count = 0. */
+RFD_API int rfd_view_plan(int frame, int frame_w, int frame_h, const rfd_view_config *cfg, rfd_view *out, int cap, int *count);
+/* frames[]: host array, `data` in DEVICE memory; out: DEVICE slabs [n_frames][max_det], total required.  Enqueued on the
+ * context's stream; async as rfd_detect_batch_device (non-zero: no host wait; the overlap mode does not exist here). */
+RFD_API int rfd_detect_views_batch_device(rfd_ctx *ctx, const rfd_image *frames, int n_frames, const rfd_view *views, int n_views,
+                                          float edge_margin, rfd_dets *out, int async);
+/* Host frames, host slabs, synchronous.  Each FRAME is copied to the device once; its views read that copy. */
+RFD_API int rfd_detect_views_batch(rfd_ctx *ctx, const rfd_image *frames, int n_frames, const rfd_view *views, int n_views,
+                                   float edge_margin, rfd_dets *out);
+/* Stage-level: everything after the network on caller-supplied heads of n_views images (the contract of rfd_forward's
+ * outputs), image i being view i.  Host pointers.  gidx (may be NULL) [n_frames][max_det] receives v * anchors + g of every
+ * kept row, v the view's position among its frame's views and g the anchor.  The views' frames are not seen: "inside its
+ * frame" is not checked here. */
+RFD_API int rfd_decode_nms_views(rfd_ctx *ctx, const float *const heads[9], const rfd_view *views, int n_views, int n_frames,
+                                 float edge_margin, rfd_dets *out, int32_t *gidx);
+
 /* ---- introspection ---- */
 RFD_API int rfd_get_stats(rfd_ctx *ctx, rfd_stats *stats);
 RFD_API int rfd_get_config(const rfd_ctx *ctx, rfd_config *cfg);

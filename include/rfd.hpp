@@ -655,5 +655,36 @@ inline std::vector<int32_t> jpeg_last_paths(RetinaFaceDetection &det)
     return out;
 }
 
+// ---- views (rfd.h, "views"): detection over overlapping views of a frame, merged on the device ----
+// the defaults for a network of net_w x net_h: tile = the network size, overlap = net_w / 5, the full view, a margin of 4 px
+inline rfd_view_config view_config(int net_w = 640, int net_h = 640)
+{
+    rfd_view_config c;
+    rfd_view_config_default(&c, net_w, net_h);
+    return c;
+}
+// the views of one frame: the whole frame first where there is more than one tile, then the tiles row-major; host only
+inline std::vector<rfd_view> view_plan(int frame_w, int frame_h, const rfd_view_config &cfg, int frame = 0)
+{
+    int n = 0;
+    const int st = rfd_view_plan(frame, frame_w, frame_h, &cfg, nullptr, 0, &n);
+    if (st != RFD_ERR_CAPACITY) check(st);
+    std::vector<rfd_view> out((std::size_t)n);
+    check(rfd_view_plan(frame, frame_w, frame_h, &cfg, out.data(), n, &n));
+    return out;
+}
+// DEVICE frames and DEVICE slabs [frames.size()][max_det] (out.total required), views sorted by frame; the slabs feed the
+// selection, alignment and face-list calls as those of rfd_detect_batch_device do.  async: no host synchronisation
+inline void detect_views_device(RetinaFaceDetection &det, const std::vector<rfd_image> &frames, const std::vector<rfd_view> &views, float edge_margin,
+                                rfd_dets out, bool async = false)
+{
+    check(rfd_detect_views_batch_device(det.raw(), frames.data(), (int)frames.size(), views.data(), (int)views.size(), edge_margin, &out, async ? 1 : 0));
+}
+// host frames and host slabs, synchronous
+inline void detect_views(RetinaFaceDetection &det, const std::vector<rfd_image> &frames, const std::vector<rfd_view> &views, float edge_margin, rfd_dets out)
+{
+    check(rfd_detect_views_batch(det.raw(), frames.data(), (int)frames.size(), views.data(), (int)views.size(), edge_margin, &out));
+}
+
 } // namespace rfd
 #endif

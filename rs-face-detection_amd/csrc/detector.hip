@@ -21,6 +21,7 @@
 #include "host_resources.h"
 #include "jpeg_host.h"
 #include "network.h"
+#include "view_plan.h"
 
 namespace rfd {
 
@@ -209,6 +210,9 @@ struct rfd_ctx {
     // liveness stage, all allocated by its first call: frame descriptors, the per-(face, model) geometry, the in / out staging of
     // the host forms, the running sums of a decide call of many models
     DevBuf live_imgs, live_geo, live_io, live_acc;
+    // views (rfd.h, "views"), both allocated by the first views call: the per-view descriptors of decode_views_kernel
+    DevBuf view_desc;
+    PinnedRing<kRing> views_ring; // ViewDesc [B]
     JpegDecoder jpeg; // JPEG decode (rfd.h, "JPEG decode"): jpeg_host.h
     // pipelined host entry (rfd_submit_batch / rfd_collect_batch): two slots, H2D on its own stream
     struct PipeSlot {
@@ -413,15 +417,21 @@ int copy_slabs(rfd_ctx *c, const rfd_dets &dst, const rfd_dets &src, int n, hipM
     return RFD_OK;
 }
 
-// decode -> sort -> NMS on device-resident heads; outputs to device slabs `o*`.
+// The views of a call as post_network sees them: n_views images of heads decoded into the lists of n frames, vmax slots each.
+struct ViewsPost { const ViewDesc *desc; int n_views, vmax; float edge_margin; };
+
+// decode -> sort -> NMS on device-resident heads; outputs to device slabs `o*`.  views: the n images of the sort and the NMS are
+// frames of views->vmax * total_anchors anchors each, filled by decode_views_kernel from views->n_views images of heads.
 int post_network(rfd_ctx *c, DecodeParams &dp, bool nchw, int n, float *oboxes, float *olmk, int *ocount,
-                 int *ototal, int *ogidx, const float *det_scale = nullptr)
+                 int *ototal, int *ogidx, const float *det_scale = nullptr, const ViewsPost *views = nullptr)
 {
+    const int anchors = views ? views->vmax * c->total_anchors : c->total_anchors;
     RFD_HIP(hipMemsetAsync(c->count.p, 0, n * sizeof(int), c->stream));
-    RFD_TRY(launch_decode(dp, n, nchw, c->stream));
+    if (views) RFD_TRY(launch_decode_views(dp, views->desc, views->n_views, views->vmax, views->edge_margin, nchw, c->stream));
+    else RFD_TRY(launch_decode(dp, n, nchw, c->stream));
     RFD_HIP(hipEventRecord(c->ev[4], c->stream));
     RFD_TRY(launch_sort((uint64_t *)c->keys.p, (const int *)c->count.p, (const float *)c->rows.p,
-                        (uint64_t *)c->sorted_keys.p, (float4 *)c->sorted_boxes.p, c->total_anchors, n, c->stream));
+                        (uint64_t *)c->sorted_keys.p, (float4 *)c->sorted_boxes.p, anchors, n, c->stream));
     RFD_HIP(hipEventRecord(c->ev[5], c->stream));
     NmsParams np;
     memset(&np, 0, sizeof np);
@@ -431,7 +441,7 @@ int post_network(rfd_ctx *c, DecodeParams &dp, bool nchw, int n, float *oboxes, 
     np.count = (const int *)c->count.p;
     np.det_scale = det_scale ? det_scale : (const float *)c->det_scale.p;
     np.presorted_n = -1;
-    np.total_anchors = c->total_anchors;
+    np.total_anchors = anchors;
     np.max_det = c->cfg.max_det;
     np.iou_thr = c->cfg.iou_threshold;
     np.out_boxes = oboxes; np.out_lmk = olmk; np.out_count = ocount; np.out_total = ototal; np.out_gidx = ogidx;
@@ -605,6 +615,137 @@ int detect_impl(rfd_ctx *c, const rfd_image *imgs, int n, rfd_dets *out, bool on
     RFD_TRY(finish_stats(c, n, true, true));
     if (!on_device)
         for (int i = 0; i < n; ++i) c->stats.detections += out->total ? out->total[i] : out->count[i];
+    return RFD_OK;
+}
+
+// host head tensors of n images (rfd_forward's contract) -> scratch[3..11], named in dp
+int upload_heads(rfd_ctx *c, const float *const heads[9], int n, DecodeParams &dp)
+{
+    static const int chans[3] = {2 * kA, 4 * kA, 10 * kA};
+    for (int l = 0; l < kNumLevels; ++l)
+        for (int k = 0; k < 3; ++k) {
+            const size_t bytes = (size_t)n * chans[k] * c->fh[l] * c->fw[l] * sizeof(float);
+            DevBuf &b = c->scratch[3 + 3 * l + k];
+            RFD_TRY(b.reserve(bytes));
+            RFD_HIP(hipMemcpyAsync(b.p, heads[3 * l + k], bytes, hipMemcpyHostToDevice, c->stream));
+            (k == 0 ? dp.cls[l] : k == 1 ? dp.bbox[l] : dp.lmk[l]) = (const float *)b.p;
+        }
+    return RFD_OK;
+}
+
+// ---- views (rfd.h, "views") ----
+// Everything a views call decides before it enqueues: the argument rules, each view's slot among its frame's views
+// (view_plan.h), its letterbox, and the two capacity limits.  frames may be null (rfd_decode_nms_views: the frames are not
+// seen).  Fills vd [n_views] and, where given, the geometry of pis [n_views] (src / stride are the caller's).
+int plan_views(const rfd_ctx *c, const rfd_image *frames, int n_frames, const rfd_view *views, int n_views, float edge_margin,
+               ViewDesc *vd, PreImage *pis, int *vmax)
+{
+    RFD_CHECK_ARG(views != nullptr, "views is null");
+    RFD_CHECK_ARG(n_frames >= 1, "n_frames < 1");
+    RFD_TRY(check_batch(c, n_views, "batch of", " views"));
+    RFD_CHECK_ARG(edge_margin >= 0.0f && std::isfinite(edge_margin), "edge_margin must be finite and >= 0");
+    std::vector<int32_t> slot(n_views);
+    int bad = -1;
+    switch (view_slots(views, n_views, n_frames, slot.data(), vmax, &bad)) {
+    case kViewOk: break;
+    case kViewFrameRange: set_error("invalid argument: view %d names frame %d of %d", bad, views[bad].frame, n_frames); return RFD_ERR_INVALID_ARG;
+    case kViewFrameOrder: set_error("invalid argument: views must be sorted by frame (view %d names frame %d after frame %d)", bad, views[bad].frame, views[bad - 1].frame); return RFD_ERR_INVALID_ARG;
+    case kViewEmpty: set_error("invalid argument: view %d is empty (%dx%d)", bad, views[bad].w, views[bad].h); return RFD_ERR_INVALID_ARG;
+    case kViewOrigin: set_error("invalid argument: view %d starts at (%d, %d), outside its frame", bad, views[bad].x, views[bad].y); return RFD_ERR_INVALID_ARG;
+    case kViewInnerBits: set_error("invalid argument: view %d sets bits of inner (0x%x) beyond the four sides", bad, views[bad].inner); return RFD_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < n_views; ++i) {
+        const rfd_view &v = views[i];
+        if (frames && !view_inside(v, frames[v.frame].width, frames[v.frame].height)) {
+            set_error("invalid argument: view %d (%dx%d at %d, %d) does not lie inside frame %d (%dx%d)", i, v.w, v.h, v.x, v.y, v.frame,
+                      frames[v.frame].width, frames[v.frame].height);
+            return RFD_ERR_INVALID_ARG;
+        }
+        PreImage pi;
+        float det_scale;
+        letterbox(v.h, v.w, c->cfg.image_w, c->cfg.image_h, &pi, &det_scale);
+        if (pi.new_w <= 0 || pi.new_h <= 0) { // as fill_pre_image refuses such a frame
+            set_error("invalid argument: view %d (%dx%d) letterboxes to an empty %dx%d image", i, v.w, v.h, pi.new_w, pi.new_h);
+            return RFD_ERR_INVALID_ARG;
+        }
+        vd[i] = ViewDesc{v.frame, slot[i], v.x, v.y, pi.new_w, pi.new_h, v.inner, det_scale};
+        if (pis) pis[i] = pi;
+    }
+    if ((long long)n_frames * *vmax > c->cfg.max_batch_size) {
+        set_error("%d frames of up to %d views each take %lld image slots, max_batch_size is %d", n_frames, *vmax, (long long)n_frames * *vmax,
+                  c->cfg.max_batch_size);
+        return RFD_ERR_CAPACITY;
+    }
+    if (!nms_fits_lds(*vmax * c->total_anchors)) {
+        set_error("%d views of a frame make %d candidate slots (%d anchors each): the NMS bitmap does not fit LDS", *vmax, *vmax * c->total_anchors,
+                  c->total_anchors);
+        return RFD_ERR_CAPACITY;
+    }
+    return RFD_OK;
+}
+
+// the descriptors of a planned call to the device, and ones as the det_scale of its frames (the rows are in frame pixels already)
+int stage_views(rfd_ctx *c, const ViewDesc *vd, int n_views, float *pin_ones, int n_frames)
+{
+    for (int i = 0; i < n_frames; ++i) pin_ones[i] = 1.0f;
+    RFD_HIP(hipMemcpyAsync(c->view_desc.p, vd, n_views * sizeof(ViewDesc), hipMemcpyHostToDevice, c->stream));
+    RFD_HIP(hipMemcpyAsync(c->det_scale.p, pin_ones, n_frames * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    RFD_TRY(c->views_ring.record(c->stream));
+    return c->frame_ring.record(c->stream);
+}
+
+int acquire_views_slot(rfd_ctx *c, ViewDesc **vd)
+{
+    RFD_TRY(c->view_desc.reserve((size_t)c->cfg.max_batch_size * sizeof(ViewDesc)));
+    RFD_TRY(c->views_ring.ensure((size_t)c->cfg.max_batch_size * sizeof(ViewDesc)));
+    return c->views_ring.acquire(vd);
+}
+
+int detect_views_impl(rfd_ctx *c, const rfd_image *frames, int n_frames, const rfd_view *views, int n_views, float edge_margin,
+                      rfd_dets *out, bool on_device, int async)
+{
+    RFD_CHECK_ARG(c != nullptr, "ctx is null");
+    RFD_CHECK_ARG(out && out->boxes && out->landmarks && out->count, "output buffers are null");
+    RFD_CHECK_ARG(!on_device || out->total, "the device form needs out->total");
+    RFD_TRY(check_images(c, frames, n_frames));
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    PreImage *pis;
+    float *pin_ones;
+    ViewDesc *vd;
+    int vmax = 0;
+    RFD_TRY(acquire_frame_slot(c, &pis, &pin_ones));
+    RFD_TRY(acquire_views_slot(c, &vd));
+    RFD_TRY(plan_views(c, frames, n_frames, views, n_views, edge_margin, vd, pis, &vmax));
+    RFD_TRY(c->ensure_network());
+    if (!c->net.weights_ready) { set_error("network weights are not initialised"); return RFD_ERR_STATE; }
+    c->ov_last_n = -1;
+    RFD_HIP(hipEventRecord(c->ev[0], c->stream));
+    std::vector<PreImage> where(n_frames); // each FRAME is placed once; its views point into it
+    RFD_TRY(place_frames(c, frames, n_frames, on_device, where.data()));
+    for (int i = 0; i < n_views; ++i) {
+        const PreImage &f = where[views[i].frame];
+        pis[i].src = f.src + (long long)views[i].y * f.stride + 3ll * views[i].x;
+        pis[i].stride = f.stride;
+    }
+    RFD_HIP(hipMemcpyAsync(c->imgs.p, pis, n_views * sizeof(PreImage), hipMemcpyHostToDevice, c->stream));
+    RFD_TRY(stage_views(c, vd, n_views, pin_ones, n_frames));
+    RFD_HIP(hipEventRecord(c->ev[1], c->stream));
+    RFD_TRY(launch_preprocess(pre_params(c, c->imgs.p, 0), n_views, c->stream));
+    RFD_HIP(hipEventRecord(c->ev[2], c->stream));
+    RFD_TRY(c->net.run_graphed(n_views, c->stream));
+    RFD_HIP(hipEventRecord(c->ev[3], c->stream));
+    DecodeParams dp = decode_params(c, true);
+    const ViewsPost vp = {(const ViewDesc *)c->view_desc.p, n_views, vmax, edge_margin};
+    const rfd_dets dev = on_device ? *out : own_slabs(c);
+    RFD_TRY(post_network(c, dp, false, n_frames, dev.boxes, dev.landmarks, dev.count, dev.total, nullptr, nullptr, &vp));
+    if (!on_device) RFD_TRY(copy_slabs(c, *out, dev, n_frames, hipMemcpyDeviceToHost));
+    RFD_HIP(hipEventRecord(c->ev[7], c->stream));
+    if (async && on_device) return RFD_OK;
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    RFD_TRY(check_nms_flag(c));
+    RFD_TRY(finish_stats(c, n_frames, true, true));
+    if (!on_device)
+        for (int i = 0; i < n_frames; ++i) c->stats.detections += out->total ? out->total[i] : out->count[i];
     return RFD_OK;
 }
 
@@ -1403,16 +1544,8 @@ int rfd_decode_nms(rfd_ctx *c, const float *const heads[9], int n, const float *
     for (int i = 0; i < 9; ++i) RFD_CHECK_ARG(heads[i] != nullptr, "head pointer is null");
     RFD_TRY(check_batch(c, n, "batch"));
     RFD_HIP(hipSetDevice(c->cfg.device_id));
-    static const int chans[3] = {2 * kA, 4 * kA, 10 * kA};
     DecodeParams dp = decode_params(c, false);
-    for (int l = 0; l < kNumLevels; ++l)
-        for (int k = 0; k < 3; ++k) {
-            const size_t bytes = (size_t)n * chans[k] * c->fh[l] * c->fw[l] * sizeof(float);
-            DevBuf &b = c->scratch[3 + 3 * l + k];
-            RFD_TRY(b.reserve(bytes));
-            RFD_HIP(hipMemcpyAsync(b.p, heads[3 * l + k], bytes, hipMemcpyHostToDevice, c->stream));
-            (k == 0 ? dp.cls[l] : k == 1 ? dp.bbox[l] : dp.lmk[l]) = (const float *)b.p;
-        }
+    RFD_TRY(upload_heads(c, heads, n, dp));
     RFD_HIP(hipMemcpyAsync(c->det_scale.p, det_scale, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     RFD_HIP(hipEventRecord(c->ev[3], c->stream));
     const rfd_dets dev = own_slabs(c);
@@ -1424,6 +1557,63 @@ int rfd_decode_nms(rfd_ctx *c, const float *const heads[9], int n, const float *
     RFD_TRY(check_nms_flag(c));
     RFD_TRY(finish_stats(c, n, false, false));
     for (int i = 0; i < n; ++i) c->stats.detections += out->total ? out->total[i] : out->count[i];
+    return RFD_OK;
+}
+
+// ---- views (rfd.h, "views") ----
+void rfd_view_config_default(rfd_view_config *cfg, int net_w, int net_h)
+{
+    if (cfg) view_config_default(cfg, net_w, net_h);
+}
+
+int rfd_view_plan(int frame, int frame_w, int frame_h, const rfd_view_config *cfg, rfd_view *out, int cap, int *count)
+{
+    const int status = view_plan(frame, frame_w, frame_h, cfg, out, cap, count);
+    if (status == RFD_ERR_CAPACITY) set_error("the plan of a %dx%d frame has %d views, cap is %d", frame_w, frame_h, *count, cap);
+    else if (status != RFD_OK)
+        set_error("invalid argument: a view plan needs cfg and count, frame >= 0, a frame and tiles of at least 1x1 and 0 <= overlap < tile_w, tile_h");
+    return status;
+}
+
+int rfd_detect_views_batch_device(rfd_ctx *c, const rfd_image *frames, int n_frames, const rfd_view *views, int n_views, float edge_margin,
+                                  rfd_dets *out, int async)
+{
+    return detect_views_impl(c, frames, n_frames, views, n_views, edge_margin, out, true, async);
+}
+
+int rfd_detect_views_batch(rfd_ctx *c, const rfd_image *frames, int n_frames, const rfd_view *views, int n_views, float edge_margin, rfd_dets *out)
+{
+    return detect_views_impl(c, frames, n_frames, views, n_views, edge_margin, out, false, 0);
+}
+
+int rfd_decode_nms_views(rfd_ctx *c, const float *const heads[9], const rfd_view *views, int n_views, int n_frames, float edge_margin,
+                         rfd_dets *out, int32_t *gidx)
+{
+    RFD_CHECK_ARG(c && heads, "null argument");
+    RFD_CHECK_ARG(out && out->boxes && out->landmarks && out->count, "output buffers are null");
+    for (int i = 0; i < 9; ++i) RFD_CHECK_ARG(heads[i] != nullptr, "head pointer is null");
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    PreImage *pis;
+    float *pin_ones;
+    ViewDesc *vd;
+    int vmax = 0;
+    RFD_TRY(acquire_frame_slot(c, &pis, &pin_ones));
+    RFD_TRY(acquire_views_slot(c, &vd));
+    RFD_TRY(plan_views(c, nullptr, n_frames, views, n_views, edge_margin, vd, nullptr, &vmax));
+    DecodeParams dp = decode_params(c, false);
+    RFD_TRY(upload_heads(c, heads, n_views, dp));
+    RFD_TRY(stage_views(c, vd, n_views, pin_ones, n_frames));
+    RFD_HIP(hipEventRecord(c->ev[3], c->stream));
+    const ViewsPost vp = {(const ViewDesc *)c->view_desc.p, n_views, vmax, edge_margin};
+    const rfd_dets dev = own_slabs(c);
+    RFD_TRY(post_network(c, dp, true, n_frames, dev.boxes, dev.landmarks, dev.count, dev.total, gidx ? (int *)c->out_gidx.p : nullptr, nullptr, &vp));
+    RFD_TRY(copy_slabs(c, *out, dev, n_frames, hipMemcpyDeviceToHost));
+    if (gidx) RFD_HIP(hipMemcpyAsync(gidx, c->out_gidx.p, (size_t)n_frames * c->cfg.max_det * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    RFD_HIP(hipEventRecord(c->ev[7], c->stream));
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    RFD_TRY(check_nms_flag(c));
+    RFD_TRY(finish_stats(c, n_frames, false, false));
+    for (int i = 0; i < n_frames; ++i) c->stats.detections += out->total ? out->total[i] : out->count[i];
     return RFD_OK;
 }
 

@@ -46,6 +46,20 @@ struct DecodeParams {
 };
 int launch_decode(const DecodeParams &p, int n, bool nchw, hipStream_t s);
 
+// Decode into per-FRAME lists (rfd.h, "views"): image b of the network batch is view b, the v-th view of frame f.  A candidate
+// that passes the threshold and the inner-edge rule is written in frame pixels to rows[(f * vmax + v) * total_anchors + g] and
+// its key (score bits << 32 | v * total_anchors + g) appended to keys[f * vmax * total_anchors + ...] through count[f]: frame f
+// then looks to launch_sort / launch_nms like an image of vmax * total_anchors anchors.
+struct ViewDesc {
+    int frame, slot;  // f, v
+    int x, y;         // the view's corner in the frame
+    int new_w, new_h; // its letterboxed extent
+    uint32_t inner;   // rfd_view::inner
+    float det_scale;  // its letterbox scale
+};
+// views: device [n_views]; p.count [frames] zeroed before launch; p.rows / p.keys hold frames * vmax * total_anchors entries
+int launch_decode_views(const DecodeParams &p, const ViewDesc *views, int n_views, int vmax, float edge_margin, bool nchw, hipStream_t s);
+
 int launch_sort(uint64_t *keys, const int *count, const float *rows, uint64_t *sorted_keys,
                 float4 *sorted_boxes, int total_anchors, int n, hipStream_t s);
 
@@ -75,6 +89,8 @@ struct NmsParams {
 };
 constexpr int kNmsChunks = 4;
 int launch_nms(NmsParams p, int n_images, hipStream_t s, bool *used_chunked = nullptr);
+// launch_nms accepts this many anchors per image (its LDS check), so that a caller can refuse before it enqueues anything
+bool nms_fits_lds(int total_anchors);
 
 // FaceSelection::call on the device (face_selection.rs:72-189): per image, over its kept detections
 struct SelectParams {

@@ -156,6 +156,122 @@ int launch_decode(const DecodeParams &p, int n, bool nchw, hipStream_t s)
     return RFD_OK;
 }
 
+// Views (rfd.h, "views"; kernels.h, ViewDesc): decode_kernel with three steps between the clip and the store.  One thread per
+// (view b of the network batch, anchor g).  Threshold, bbox_pred, clip_boxes and landmark_pred are decode_kernel's, the same
+// operations in the same order, restated here so that decode_kernel's own code stays what it was (profiles/views_device_code.txt).
+//   1. the inner-edge rule on the clipped box, in network pixels: every side of the view that lies inside the frame must keep
+//      the box `margin` away; written as !(a >= b) so that a NaN drops the candidate;
+//   2. the map to frame pixels, X = x / det_scale + (float)offset: one IEEE division, one addition (no contraction: the file is
+//      built with -ffp-contract=off), box and landmarks alike, the score untouched;
+//   3. the row goes to slot (f * vmax + v) of the row buffer and the key, with v * total_anchors + g in its low word, to frame
+//      f's list: ascending keys = (score descending, view, anchor).
+// f < frames and v < vmax are the host's promise (view_slots), so a row index stays below frames * vmax * total_anchors.
+template <bool NCHW>
+__global__ void __launch_bounds__(256) decode_views_kernel(DecodeParams p, const ViewDesc *__restrict__ views, int vmax, float margin)
+{
+    const int b = blockIdx.y;
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= p.total_anchors) return;
+    int l = 0;
+    if (g >= p.level_off[1]) l = 1;
+    if (g >= p.level_off[2]) l = 2;
+    const int r = g - p.level_off[l];
+    const int a = r % kA;
+    const int pos = r / kA;
+    const int fw = p.fw[l], fh = p.fh[l];
+    const int h = pos / fw, w = pos - h * fw;
+    const int stride = p.stride[l];
+    const size_t hw = (size_t)fh * fw;
+
+    float score;
+    if (NCHW)
+        score = p.cls[l][((size_t)b * 2 * kA + kA + a) * hw + pos];
+    else
+        score = p.cls[l][((size_t)b * hw + pos) * 32 + kA + a];
+    if (!(score >= p.conf_thr)) return;
+
+    float d[4], ld[10];
+    if (NCHW) {
+        const float *bb = p.bbox[l] + ((size_t)b * 4 * kA + 4 * a) * hw + pos;
+        const float *lm = p.lmk[l] + ((size_t)b * 10 * kA + 10 * a) * hw + pos;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) d[c] = bb[c * hw];
+#pragma unroll
+        for (int c = 0; c < 10; ++c) ld[c] = lm[c * hw];
+    } else {
+        const float *bb = p.cls[l] + ((size_t)b * hw + pos) * 32 + 2 * kA + 4 * a;
+        const float *lm = p.cls[l] + ((size_t)b * hw + pos) * 32 + 6 * kA + 10 * a;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) d[c] = bb[c];
+#pragma unroll
+        for (int c = 0; c < 10; ++c) ld[c] = lm[c];
+    }
+    const float sw = (float)(w * stride), sh = (float)(h * stride);
+    const float ax1 = p.base_anchor[l][a][0] + sw, ay1 = p.base_anchor[l][a][1] + sh;
+    const float ax2 = p.base_anchor[l][a][2] + sw, ay2 = p.base_anchor[l][a][3] + sh;
+    const float bw = ax2 - ax1 + 1.0f;
+    const float bh = ay2 - ay1 + 1.0f;
+    const float cx = ax1 + 0.5f * (bw - 1.0f);
+    const float cy = ay1 + 0.5f * (bh - 1.0f);
+    const float pcx = d[0] * 1.0f * bw + cx;
+    const float pcy = d[1] * 1.0f * bh + cy;
+    const float pw = exp_cr(d[2] * 1.0f) * bw;
+    const float ph = exp_cr(d[3] * 1.0f) * bh;
+    float x1 = pcx - 0.5f * (pw - 1.0f);
+    float y1 = pcy - 0.5f * (ph - 1.0f);
+    float x2 = pcx + 0.5f * (pw - 1.0f);
+    float y2 = pcy + 0.5f * (ph - 1.0f);
+    const float wmax = (float)p.net_w - 1.0f, hmax = (float)p.net_h - 1.0f;
+    x1 = fmaxf(fminf(x1, wmax), 0.0f);
+    y1 = fmaxf(fminf(y1, hmax), 0.0f);
+    x2 = fmaxf(fminf(x2, wmax), 0.0f);
+    y2 = fmaxf(fminf(y2, hmax), 0.0f);
+
+    const ViewDesc v = views[b];
+    // 1. a box that comes within `margin` of an inner side may be a face the side cuts: the neighbour, or the full view, has it whole
+    if ((v.inner & 1u) && !(x1 >= margin)) return;
+    if ((v.inner & 2u) && !(y1 >= margin)) return;
+    if ((v.inner & 4u) && !(x2 <= (float)(v.new_w - 1) - margin)) return;
+    if ((v.inner & 8u) && !(y2 <= (float)(v.new_h - 1) - margin)) return;
+
+    float lo[10];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        lo[2 * k + 0] = ld[2 * k + 0] * 1.0f * bw + cx;
+        lo[2 * k + 1] = ld[2 * k + 1] * 1.0f * bh + cy;
+    }
+    // 2. frame pixels
+    const float sc = v.det_scale, ox = (float)v.x, oy = (float)v.y;
+    x1 = x1 / sc + ox; y1 = y1 / sc + oy; x2 = x2 / sc + ox; y2 = y2 / sc + oy;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        lo[2 * k + 0] = lo[2 * k + 0] / sc + ox;
+        lo[2 * k + 1] = lo[2 * k + 1] / sc + oy;
+    }
+    // 3. the frame's list
+    const size_t frame_anchors = (size_t)vmax * p.total_anchors;
+    const uint32_t vg = (uint32_t)v.slot * (uint32_t)p.total_anchors + (uint32_t)g;
+    float4 *row = reinterpret_cast<float4 *>(p.rows + ((size_t)v.frame * frame_anchors + vg) * kDetRow);
+    row[0] = make_float4(x1, y1, x2, y2);
+    row[1] = make_float4(score, lo[0], lo[1], lo[2]);
+    row[2] = make_float4(lo[3], lo[4], lo[5], lo[6]);
+    row[3] = make_float4(lo[7], lo[8], lo[9], 0.0f);
+
+    const int slot = atomicAdd(p.count + v.frame, 1);
+    p.keys[(size_t)v.frame * frame_anchors + slot] = ((uint64_t)score_sort_bits(score) << 32) | vg;
+}
+
+int launch_decode_views(const DecodeParams &p, const ViewDesc *views, int n_views, int vmax, float edge_margin, bool nchw, hipStream_t s)
+{
+    dim3 grid(ceil_div(p.total_anchors, 256), n_views);
+    if (nchw)
+        hipLaunchKernelGGL(decode_views_kernel<true>, grid, dim3(256), 0, s, p, views, vmax, edge_margin);
+    else
+        hipLaunchKernelGGL(decode_views_kernel<false>, grid, dim3(256), 0, s, p, views, vmax, edge_margin);
+    RFD_HIP(hipGetLastError());
+    return RFD_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // sort: the reference stable-sorts the level-concatenated candidates by score descending
 // (utils.rs:87-95); level concatenation order == ascending g, so the order is the total order
@@ -958,6 +1074,8 @@ size_t nms_lds_bytes(int total_anchors, bool reg)
     return (size_t)64 * sizeof(float4) + (size_t)(2 * nwords_cap + 2) * sizeof(uint64_t) +
            (size_t)nwords_cap * sizeof(int) + (reg ? 0 : (size_t)kNmsLdsBoxes * sizeof(float4));
 }
+
+bool nms_fits_lds(int total_anchors) { return nms_lds_bytes(total_anchors, total_anchors <= kNmsRegCap) <= 160 * 1024; }
 
 int launch_nms(NmsParams p, int n_images, hipStream_t s, bool *used_chunked)
 {

@@ -134,6 +134,14 @@ class rfd_gallery_nearest_plan(C.Structure):
                 ("blocks_per_split", C.c_int32), ("grid", C.c_int64), ("ws_bytes", C.c_int64)]
 
 
+class rfd_view(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("inner", C.c_uint32)]
+
+
+class rfd_view_config(C.Structure):
+    _fields_ = [("tile_w", C.c_int32), ("tile_h", C.c_int32), ("overlap", C.c_int32), ("full_view", C.c_int32), ("edge_margin", C.c_float)]
+
+
 class rfd_jpeg_info(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("sampling", C.c_int32),
                 ("restart_interval", C.c_int32), ("reserved", C.c_int32 * 3)]
@@ -188,6 +196,7 @@ API_SYMBOLS = [
     "rfd_jpeg_orientation", "rfd_set_jpeg_orientation", "rfd_jpeg_last_orientations",
     "rfd_set_jpeg_scale", "rfd_jpeg_scaled_size", "rfd_debug_jpeg_block_counts",
     "rfd_face_list_config_default", "rfd_align_detections", "rfd_detect_align_all_batch", "rfd_detect_all_faces_device",
+    "rfd_view_config_default", "rfd_view_plan", "rfd_detect_views_batch_device", "rfd_detect_views_batch", "rfd_decode_nms_views",
 ]
 
 _lib = None
@@ -347,6 +356,12 @@ def load_library(path=None):
     L.rfd_set_jpeg_scale.argtypes = [vp, ci]
     L.rfd_jpeg_scaled_size.argtypes = [vp, C.c_size_t, ci, ci, C.POINTER(rfd_jpeg_scaled_size)]
     L.rfd_debug_jpeg_block_counts.argtypes = [vp, C.c_size_t, ci, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rfd_view_config_default.argtypes = [C.POINTER(rfd_view_config), ci, ci]
+    L.rfd_view_config_default.restype = None
+    L.rfd_view_plan.argtypes = [ci, ci, ci, C.POINTER(rfd_view_config), C.POINTER(rfd_view), ci, C.POINTER(ci)]
+    L.rfd_detect_views_batch_device.argtypes = [vp, C.POINTER(rfd_image), ci, C.POINTER(rfd_view), ci, C.c_float, C.POINTER(rfd_dets), ci]
+    L.rfd_detect_views_batch.argtypes = [vp, C.POINTER(rfd_image), ci, C.POINTER(rfd_view), ci, C.c_float, C.POINTER(rfd_dets)]
+    L.rfd_decode_nms_views.argtypes = [vp, C.POINTER(vp), C.POINTER(rfd_view), ci, ci, C.c_float, C.POINTER(rfd_dets), vp]
     if path is None:
         _lib = L
     return L
@@ -473,6 +488,41 @@ def gallery_nearest_plan(rows, row0, n, dim, cus):
     p = rfd_gallery_nearest_plan()
     _check(load_library().rfd_debug_gallery_nearest_plan(int(rows), int(row0), int(n), int(dim), int(cus), C.byref(p)))
     return {k: int(getattr(p, k)) for k, _ in p._fields_}
+
+
+def view_config(net_size=(640, 640), tile=None, overlap=None, full_view=None, edge_margin=None):
+    """rfd_view_config (rfd.h, "views"): the defaults for a network of net_size (w, h) -- tile = the network size, overlap =
+    net_w / 5, the full view, a margin of 4 network pixels -- with the fields given replaced; tile is (w, h)"""
+    c = rfd_view_config()
+    load_library().rfd_view_config_default(C.byref(c), int(net_size[0]), int(net_size[1]))
+    if tile is not None:
+        c.tile_w, c.tile_h = int(tile[0]), int(tile[1])
+    if overlap is not None:
+        c.overlap = int(overlap)
+    if full_view is not None:
+        c.full_view = int(bool(full_view))
+    if edge_margin is not None:
+        c.edge_margin = float(edge_margin)
+    return c
+
+
+def view_plan(frame_w, frame_h, cfg, frame=0):
+    """the views of one frame (rfd_view_plan), as a list of rfd_view; needs no context and no device"""
+    L, n = load_library(), C.c_int(0)
+    status = L.rfd_view_plan(int(frame), int(frame_w), int(frame_h), C.byref(cfg), None, 0, C.byref(n))
+    if status != RFD_ERR_CAPACITY:
+        _check(status)
+    out = (rfd_view * max(n.value, 1))()
+    _check(L.rfd_view_plan(int(frame), int(frame_w), int(frame_h), C.byref(cfg), out, n.value, C.byref(n)))
+    return [rfd_view(v.frame, v.x, v.y, v.w, v.h, v.inner) for v in out[:n.value]]
+
+
+def _view_array(views):
+    """views: rfd_view structures or (frame, x, y, w, h, inner) tuples"""
+    arr = (rfd_view * max(len(views), 1))()
+    for i, v in enumerate(views):
+        arr[i] = v if isinstance(v, rfd_view) else rfd_view(*[int(a) for a in v])
+    return arr
 
 
 def gallery_file_write(path, values_bf16_as_f32, live):
@@ -1482,6 +1532,45 @@ class RetinaFaceDetection:
         gidx = np.zeros((n, self.max_det), np.int32)
         _check(self._L.rfd_decode_nms(self._ctx, ptrs, n, sc.ctypes.data, C.byref(d),
                                       gidx.ctypes.data if want_gidx else None))
+        self.last_total = total
+        res = self._split(boxes, lmk, count)
+        if want_gidx:
+            res = [(a, b, gidx[i, :count[i]].copy()) for i, (a, b) in enumerate(res)]
+        return res
+
+    # ---- views (rfd.h, "views"): detection over overlapping views of a frame, merged on the device ----
+    def detect_views(self, frames, views, edge_margin=4.0):
+        """frames: HxWx3 u8 BGR arrays; views: rfd_view or (frame, x, y, w, h, inner), sorted by frame (view_plan) -> one
+        (det [K,5], kps [K,5,2]) per FRAME, in source-frame pixels"""
+        arr, keep = self._images(frames)
+        d, boxes, lmk, count, total = self._alloc_dets(len(frames))
+        _check(self._L.rfd_detect_views_batch(self._ctx, arr, len(frames), _view_array(views), len(views), float(edge_margin), C.byref(d)))
+        self.last_total = total
+        return self._split(boxes, lmk, count)
+
+    def detect_views_device(self, frame_ptrs, shapes, views, out_boxes_ptr, out_lmk_ptr, out_count_ptr, out_total_ptr, edge_margin=4.0,
+                            strides=None, async_=False):
+        """frames and output slabs [n_frames][max_det] already in device memory (raw device pointers)"""
+        n = len(frame_ptrs)
+        arr = (rfd_image * n)()
+        for i, (p, (h, w)) in enumerate(zip(frame_ptrs, shapes)):
+            arr[i].data, arr[i].height, arr[i].width, arr[i].stride = p, h, w, strides[i] if strides else w * 3
+        d = rfd_dets(out_boxes_ptr, out_lmk_ptr, out_count_ptr, out_total_ptr)
+        _check(self._L.rfd_detect_views_batch_device(self._ctx, arr, n, _view_array(views), len(views), float(edge_margin), C.byref(d), int(async_)))
+
+    def decode_nms_views(self, heads, views, n_frames, edge_margin=4.0, want_gidx=False):
+        """9 head tensors [n_views,C,h,w], image i being view i -> per FRAME (det, kps[, gidx]); gidx = v * anchors + g"""
+        hs = [np.ascontiguousarray(x, np.float32) for x in heads]
+        n = len(views)
+        w, h = self.image_size
+        for x, s in zip(hs, head_shapes(n, h, w)):
+            if x.shape != s:
+                raise RfdError(RFD_ERR_INVALID_ARG, "head shape %s != %s" % (x.shape, s))
+        ptrs = (C.c_void_p * 9)(*[x.ctypes.data for x in hs])
+        d, boxes, lmk, count, total = self._alloc_dets(max(n_frames, 1))
+        gidx = np.zeros((max(n_frames, 1), self.max_det), np.int32)
+        _check(self._L.rfd_decode_nms_views(self._ctx, ptrs, _view_array(views), n, int(n_frames), float(edge_margin), C.byref(d),
+                                            gidx.ctypes.data if want_gidx else None))
         self.last_total = total
         res = self._split(boxes, lmk, count)
         if want_gidx:
