@@ -1042,6 +1042,107 @@ RFD_API int rfd_detect_views_batch(rfd_ctx *ctx, const rfd_image *frames, int n_
 RFD_API int rfd_decode_nms_views(rfd_ctx *ctx, const float *const heads[9], const rfd_view *views, int n_views, int n_frames,
                                  float edge_margin, rfd_dets *out, int32_t *gidx);
 
+/* ---- tracker: faces followed over the frames of a video stream, on the device.  No counterpart in the reference, whose
+ *      FacePipeline::extract sees one image.  A person in front of a door for four seconds is 100 detections at 25 fps; the
+ *      remote models are the stage this library cannot speed up, so the tracker's job is to send them fewer faces: one when a
+ *      track is new, another only when the shot has improved.  The state lives in HBM and an update runs in the context's
+ *      stream order between detection and the face list, with no host wait.
+ *
+ *      An rfd_tracker belongs to ONE context (its device, its stream; same thread rule) and is destroyed BEFORE it.  It follows
+ *      `streams` cameras, each with max_tracks slots {serial (0 = free), box[4], missed, hits, shot_q} and a next_serial that
+ *      starts at 1.  A track's public name is (stream, serial): an int32, unique within its stream, never reused by a reset;
+ *      after INT32_MAX the counter restarts at 1 (2^31 - 1 births of one camera: a track born then may share its serial with a
+ *      live one of that age).
+ *
+ *      The rule, for one frame of stream s: an IoU tracker (Bochinski et al. 2017: no motion model, association by overlap with
+ *      the last box) with the two score thresholds of ByteTrack (Zhang et al. 2022).  Rows i = 0 .. min(max(count, 0), max_det)
+ *      - 1 of the frame's slab, in slab order; every operation is f32 in the written order.
+ *      1. Eligibility: row i is eligible when score >= min_score (false for a NaN).  Other rows get track 0, flags 0.
+ *      2. Association, for eligible rows in row order: among the stream's live slots not yet matched in this frame, the IoU of the
+ *         row's box with the slot's box -- the NMS's arithmetic (nms.rs:39-54: the +1 convention, inter / (area_i + area_j -
+ *         inter), one IEEE division).  Candidates are the slots with iou >= iou_min (false for a NaN).  The row takes the
+ *         candidate of greatest IoU, equal IoUs going to the lowest slot: box = the row's box, missed = 0, hits += 1, the slot is
+ *         matched and the row gets its serial.  A row with no candidate stays unmatched.
+ *      3. Ageing: every live slot not matched in this frame gets missed += 1.
+ *      4. Ending: a slot with missed > max_missed ends: its serial goes to the frame's `ended` list, in ascending slot order, and
+ *         the slot is free.
+ *      5. Birth, in row order: an unmatched eligible row with score >= new_score takes the lowest free slot (those freed in step
+ *         4 count): serial = next_serial++, the row's box, missed 0, hits 1, shot_q = -inf; the row gets RFD_TRACK_NEW.  With no
+ *         free slot the row gets track 0 and counts as dropped.  An unmatched eligible row below new_score gets track 0.
+ *      6. Confirmation: a matched or born row gets RFD_TRACK_CONFIRMED when its slot has hits >= min_hits.
+ *      7. DUE: q = quality[b][i] if a quality array was given, else the row's score.  A matched or born row is RFD_TRACK_DUE when
+ *         its slot is confirmed and q > shot_q * improve (one multiplication, one comparison; any finite q passes -inf, a NaN q
+ *         never passes); then shot_q = q.  DUE means "hand this face to the models".
+ *      Frames of one stream within a call are consecutive in time, in call order; frames of different streams are independent.
+ *      A frame with no detections still ages its stream: pass it with count = 0.  Splitting a sequence of frames into calls in
+ *      any way gives the same outputs and the same state.  Nothing here is atomic or order-dependent: the same bits on every run.
+ *
+ *      Outputs, all caller-allocated; EVERY ROW AT OR PAST A FRAME'S COUNT IS LEFT EXACTLY AS THE CALLER PASSED IT (track and
+ *      flags past the frame's rows, the due slab and due_track past due.count[b], ended past stats[b][2]).  No output may
+ *      overlap an input or another output.
+ *      The defaults (rfd_tracker_config_default) are CHOSEN values, not tuned on data: this repository has no trained weights.
+ *      Errors: RFD_ERR_INVALID_ARG with the field named in rfd_last_error() for every bound in the config comments, a NULL
+ *      required pointer, a half-set `due` slab or a stream outside [0, streams); RFD_ERR_CAPACITY for n > max_batch_size, and at
+ *      creation for a context whose max_det exceeds RFD_TRACKER_MAX_DET (the per-row results of a frame live in LDS); n = 0 is a
+ *      no-op; nothing is enqueued when a check fails. ---- */
+#define RFD_TRACK_NEW 1u
+#define RFD_TRACK_CONFIRMED 2u
+#define RFD_TRACK_DUE 4u
+#define RFD_TRACKER_MAX_DET 8192
+typedef struct rfd_tracker rfd_tracker;
+typedef struct rfd_tracker_config {
+    int32_t streams;     /* cameras, 1..4096 */
+    int32_t max_tracks;  /* slots per stream: 64, 128 or 256 */
+    float   iou_min;     /* a detection may take a track when iou >= iou_min; finite, > 0 */
+    int32_t max_missed;  /* >= 0: a track ends at the frame that leaves it unmatched more than max_missed frames running */
+    float   min_score;   /* rows below take no part */
+    float   new_score;   /* an unmatched row starts a track when score >= new_score; new_score >= min_score */
+    int32_t min_hits;    /* >= 1: a track is confirmed from its min_hits-th matched frame on (its birth counts) */
+    float   improve;     /* >= 1, finite: see DUE */
+    int32_t reserved[4];
+} rfd_tracker_config;   /* default: 1, 64, 0.3, 5, ctx confidence threshold, the same, 2, 1.1 */
+typedef struct rfd_track_out {
+    int32_t  *track;     /* [n][max_det]  serial, 0 = none */
+    uint32_t *flags;     /* [n][max_det]  RFD_TRACK_NEW 1, RFD_TRACK_CONFIRMED 2, RFD_TRACK_DUE 4 */
+    int32_t  *stats;     /* [n][4] matched, born, ended, dropped; may be NULL */
+    int32_t  *ended;     /* [n][max_tracks]; the first stats[b][2] entries are written; may be NULL */
+    rfd_dets  due;       /* boxes/landmarks/count all NULL, or all set (total optional): the DUE rows of frame b, in row order */
+    int32_t  *due_track; /* [n][max_det] serial of each due row; may be NULL */
+} rfd_track_out;
+typedef struct rfd_track {
+    int32_t slot, serial;
+    float   box[4];
+    int32_t missed, hits;
+    float   shot_q;
+} rfd_track;
+/* ctx NULL: the confidence threshold of rfd_config_default */
+RFD_API int rfd_tracker_config_default(const rfd_ctx *ctx, rfd_tracker_config *cfg);
+RFD_API int rfd_tracker_create(rfd_ctx *ctx, const rfd_tracker_config *cfg /* NULL: the default */, rfd_tracker **out);
+RFD_API void rfd_tracker_destroy(rfd_tracker *t);
+/* stream: host [n], the camera of each frame; dets: DEVICE slabs of n frames as rfd_detect_batch_device leaves them (boxes,
+ * landmarks, count; total is not read); quality: DEVICE [n][max_det] or NULL; every pointer of `out`: DEVICE.  Enqueued on the
+ * context's stream with no host wait (the stream list travels through a ring of page-locked slots); async = 0 returns after
+ * the stream has drained, any other value at once.  n <= max_batch_size. */
+RFD_API int rfd_tracker_update_device(rfd_tracker *t, const int32_t *stream, const rfd_dets *dets, const float *quality, int n,
+                                      const rfd_track_out *out, int async);
+/* Stage-level: the same with host pointers, through the same kernel; synchronous.  The output arrays travel to the device
+ * and back whole, so what they held past the counts comes back as it was. */
+RFD_API int rfd_tracker_update(rfd_tracker *t, const int32_t *stream, const rfd_dets *dets, const float *quality, int n,
+                               const rfd_track_out *out);
+/* The tracks of `stream` (-1: of all streams) vanish without an `ended` entry; next_serial is kept, so a serial is never
+ * reused.  Enqueued in stream order, no host wait. */
+RFD_API int rfd_tracker_reset(rfd_tracker *t, int stream);
+/* The live slots of `stream` in ascending slot order: at most cap of them into out (may be NULL when cap is 0); *count = how
+ * many there are, also when that exceeds cap.  Waits for the stream. */
+RFD_API int rfd_tracker_get_tracks(rfd_tracker *t, int stream, rfd_track *out, int cap, int *count);
+/* The device-resident form of rfd_align_detections (conventions of rfd_detect_all_faces_device, without its detection): every
+ * imgs[i].data, every pointer of `dets` and of `out` is DEVICE memory.  The list, alignment and tensors are enqueued on the
+ * context's stream; async = 0 returns after the stream has drained.  With the tracker's `due` slab as `dets`: detect -> track
+ * -> align the due faces -> models -> gallery, in one stream order. */
+RFD_API int rfd_align_detections_device(rfd_ctx *ctx, const rfd_image *imgs, int n, const rfd_dets *dets,
+                                        const rfd_face_list_config *list_cfg, const rfd_alignment_config *align_cfg,
+                                        const rfd_face_tensor_config *cfgs, int k, int cap, rfd_face_list *out, int async);
+
 /* ---- introspection ---- */
 RFD_API int rfd_get_stats(rfd_ctx *ctx, rfd_stats *stats);
 RFD_API int rfd_get_config(const rfd_ctx *ctx, rfd_config *cfg);

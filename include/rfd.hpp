@@ -16,6 +16,7 @@
 #ifndef RFD_HPP
 #define RFD_HPP
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <limits>
@@ -684,6 +685,99 @@ inline void detect_views_device(RetinaFaceDetection &det, const std::vector<rfd_
 inline void detect_views(RetinaFaceDetection &det, const std::vector<rfd_image> &frames, const std::vector<rfd_view> &views, float edge_margin, rfd_dets out)
 {
     check(rfd_detect_views_batch(det.raw(), frames.data(), (int)frames.size(), views.data(), (int)views.size(), edge_margin, &out));
+}
+
+// ---- tracker (rfd.h, "tracker"): faces followed over the frames of a video stream ----
+// Owns the rfd_tracker; destroy it before the detector it was made from.
+class Tracker {
+  public:
+    // one frame's answer of the host form: a serial (0 = none) and RFD_TRACK_* flags per row of the frame
+    struct Frame {
+        std::vector<int32_t> track;
+        std::vector<uint32_t> flags;
+        int matched = 0, born = 0, dropped = 0;
+        std::vector<int32_t> ended;  // serials of the tracks that ended at this frame, in ascending slot order
+        std::vector<int32_t> due;    // the rows that are RFD_TRACK_DUE, in row order: the faces to hand to the models
+    };
+    static rfd_tracker_config default_config(RetinaFaceDetection &det)
+    {
+        rfd_tracker_config c;
+        check(rfd_tracker_config_default(det.raw(), &c));
+        return c;
+    }
+    explicit Tracker(RetinaFaceDetection &det) : max_det_(det.max_det()), cfg_(default_config(det)) { check(rfd_tracker_create(det.raw(), &cfg_, &t_)); }
+    Tracker(RetinaFaceDetection &det, const rfd_tracker_config &cfg) : max_det_(det.max_det()), cfg_(cfg) { check(rfd_tracker_create(det.raw(), &cfg_, &t_)); }
+    Tracker(const Tracker &) = delete;
+    Tracker &operator=(const Tracker &) = delete;
+    ~Tracker() { rfd_tracker_destroy(t_); }
+    rfd_tracker *raw() { return t_; }
+    const rfd_tracker_config &config() const { return cfg_; }
+    // frames[i] = the detections of a frame of camera streams[i] as call_batch returns them; frames of one camera in time order.
+    // quality (optional): one value per row of every frame
+    std::vector<Frame> update(const std::vector<int32_t> &streams, const std::vector<Detections> &frames,
+                              const std::vector<std::vector<float>> *quality = nullptr)
+    {
+        const std::size_t n = frames.size(), md = max_det_, mt = (std::size_t)cfg_.max_tracks;
+        if (streams.size() != n || (quality && quality->size() != n)) throw Error(RFD_ERR_INVALID_ARG, "tracker - one stream (and quality list) per frame");
+        std::vector<float> boxes(n * md * 5), lmk(n * md * 10), q(quality ? n * md : 0);
+        std::vector<int32_t> count(n), track(n * md), stats(n * 4), ended(n * mt);
+        std::vector<uint32_t> flags(n * md);
+        for (std::size_t i = 0; i < n; ++i) {
+            const std::size_t k = std::min(frames[i].k, md);
+            std::copy(frames[i].det.begin(), frames[i].det.begin() + (std::ptrdiff_t)(k * 5), boxes.begin() + (std::ptrdiff_t)(i * md * 5));
+            std::copy(frames[i].kps.begin(), frames[i].kps.begin() + (std::ptrdiff_t)(k * 10), lmk.begin() + (std::ptrdiff_t)(i * md * 10));
+            count[i] = (int32_t)k;
+            if (quality) {
+                if ((*quality)[i].size() < k) throw Error(RFD_ERR_INVALID_ARG, "tracker - a quality value per row");
+                std::copy((*quality)[i].begin(), (*quality)[i].begin() + (std::ptrdiff_t)k, q.begin() + (std::ptrdiff_t)(i * md));
+            }
+        }
+        const rfd_dets dets{boxes.data(), lmk.data(), count.data(), nullptr};
+        rfd_track_out out{};
+        out.track = track.data(); out.flags = flags.data(); out.stats = stats.data(); out.ended = ended.data();
+        check(rfd_tracker_update(t_, streams.data(), &dets, quality ? q.data() : nullptr, (int)n, &out));
+        std::vector<Frame> res(n);
+        for (std::size_t i = 0; i < n; ++i) {
+            Frame &f = res[i];
+            const std::size_t k = (std::size_t)count[i];
+            f.track.assign(track.begin() + (std::ptrdiff_t)(i * md), track.begin() + (std::ptrdiff_t)(i * md + k));
+            f.flags.assign(flags.begin() + (std::ptrdiff_t)(i * md), flags.begin() + (std::ptrdiff_t)(i * md + k));
+            f.matched = stats[i * 4]; f.born = stats[i * 4 + 1]; f.dropped = stats[i * 4 + 3];
+            f.ended.assign(ended.begin() + (std::ptrdiff_t)(i * mt), ended.begin() + (std::ptrdiff_t)(i * mt) + stats[i * 4 + 2]);
+            for (std::size_t r = 0; r < k; ++r)
+                if (f.flags[r] & RFD_TRACK_DUE) f.due.push_back((int32_t)r);
+        }
+        return res;
+    }
+    // DEVICE slabs and outputs, enqueued on the detector's stream; async: no host synchronisation
+    void update_device(const std::vector<int32_t> &streams, const rfd_dets &dets, const float *quality, const rfd_track_out &out, bool async = false)
+    {
+        check(rfd_tracker_update_device(t_, streams.data(), &dets, quality, (int)streams.size(), &out, async ? 1 : 0));
+    }
+    void reset(int stream = -1) { check(rfd_tracker_reset(t_, stream)); }
+    // the live tracks of a stream in ascending slot order (waits for the stream)
+    std::vector<rfd_track> tracks(int stream)
+    {
+        int n = 0;
+        check(rfd_tracker_get_tracks(t_, stream, nullptr, 0, &n));
+        std::vector<rfd_track> out((std::size_t)n);
+        check(rfd_tracker_get_tracks(t_, stream, out.data(), n, &n));
+        return out;
+    }
+
+  private:
+    rfd_tracker *t_ = nullptr;
+    std::size_t max_det_ = 0;
+    rfd_tracker_config cfg_{};
+};
+
+// The device-resident form of the face list over caller-made DEVICE slabs (rfd_align_detections_device): with a tracker's
+// `due` slab as dets, only the faces worth a model call are aligned.
+inline void align_detections_device(RetinaFaceDetection &det, const std::vector<rfd_image> &imgs, const rfd_dets &dets,
+                                    const rfd_face_list_config *list_cfg, const rfd_alignment_config *align_cfg,
+                                    const std::vector<rfd_face_tensor_config> &cfgs, int cap, rfd_face_list out, bool async = false)
+{
+    check(rfd_align_detections_device(det.raw(), imgs.data(), (int)imgs.size(), &dets, list_cfg, align_cfg, cfgs.data(), (int)cfgs.size(), cap, &out, async ? 1 : 0));
 }
 
 } // namespace rfd

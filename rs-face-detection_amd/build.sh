@@ -25,3 +25,6 @@ echo "built $OBJ/facade_demo"
 # the gallery's identity calls through include/rfd.hpp (tests/test_gallery_identity_cpp_gpu.py)
 g++ -std=c++17 -O2 -Wall -I"$HERE/../include" "$HERE/../tests/cpp/gallery_identity_demo.cpp" -o "$OBJ/gallery_identity_demo" -L"$HERE" -lrfd_hip -Wl,-rpath,'$ORIGIN/..' -Wl,-rpath,"$HERE" -Wl,-rpath,/opt/rocm/lib
 echo "built $OBJ/gallery_identity_demo"
+# the tracker through include/rfd.hpp (tests/test_tracker_cpp_gpu.py)
+g++ -std=c++17 -O2 -Wall -I"$HERE/../include" "$HERE/../tests/cpp/tracker_demo.cpp" -o "$OBJ/tracker_demo" -L"$HERE" -lrfd_hip -Wl,-rpath,'$ORIGIN/..' -Wl,-rpath,"$HERE" -Wl,-rpath,/opt/rocm/lib
+echo "built $OBJ/tracker_demo"

@@ -2205,6 +2205,23 @@ int rfd_detect_all_faces_device(rfd_ctx *c, const rfd_image *imgs, int n, const 
     return check_nms_flag(c);
 }
 
+// The device-resident form of rfd_align_detections: the frames' descriptors, then the list over the caller's device slabs.
+int rfd_align_detections_device(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_dets *dets, const rfd_face_list_config *list_cfg,
+                                const rfd_alignment_config *align_cfg, const rfd_face_tensor_config *cfgs, int k, int cap,
+                                rfd_face_list *out, int async)
+{
+    rfd_face_list_config ldef;
+    rfd_alignment_config adef;
+    RFD_TRY(check_face_list_call(c, imgs, n, &list_cfg, &ldef, &align_cfg, &adef, cfgs, k, cap, out));
+    RFD_CHECK_ARG(dets && dets->boxes && dets->landmarks && dets->count, "detections are null");
+    RFD_HIP(hipSetDevice(c->cfg.device_id));
+    RFD_TRY(stage_frames(c, imgs, n, true));
+    RFD_TRY(face_list_enqueue(c, n, *dets, list_cfg, align_cfg, cfgs, k, cap, *out));
+    if (async) return RFD_OK;
+    RFD_HIP(hipStreamSynchronize(c->stream));
+    return check_nms_flag(c);
+}
+
 // ---- after the two models: quality decision rule (face_quality.rs:159-168), embedding normalisation (utils.rs:148-154) ----
 static int check_quality_args(const rfd_ctx *c, const float *logits, int n, int classes, const float *score, const int32_t *klass)
 {

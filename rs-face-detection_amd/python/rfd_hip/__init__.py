@@ -142,6 +142,22 @@ class rfd_view_config(C.Structure):
     _fields_ = [("tile_w", C.c_int32), ("tile_h", C.c_int32), ("overlap", C.c_int32), ("full_view", C.c_int32), ("edge_margin", C.c_float)]
 
 
+class rfd_tracker_config(C.Structure):
+    _fields_ = [("streams", C.c_int32), ("max_tracks", C.c_int32), ("iou_min", C.c_float), ("max_missed", C.c_int32),
+                ("min_score", C.c_float), ("new_score", C.c_float), ("min_hits", C.c_int32), ("improve", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
+class rfd_track_out(C.Structure):
+    _fields_ = [("track", C.c_void_p), ("flags", C.c_void_p), ("stats", C.c_void_p), ("ended", C.c_void_p), ("due", rfd_dets),
+                ("due_track", C.c_void_p)]
+
+
+class rfd_track(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("serial", C.c_int32), ("box", C.c_float * 4), ("missed", C.c_int32), ("hits", C.c_int32),
+                ("shot_q", C.c_float)]
+
+
 class rfd_jpeg_info(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("sampling", C.c_int32),
                 ("restart_interval", C.c_int32), ("reserved", C.c_int32 * 3)]
@@ -197,6 +213,8 @@ API_SYMBOLS = [
     "rfd_set_jpeg_scale", "rfd_jpeg_scaled_size", "rfd_debug_jpeg_block_counts",
     "rfd_face_list_config_default", "rfd_align_detections", "rfd_detect_align_all_batch", "rfd_detect_all_faces_device",
     "rfd_view_config_default", "rfd_view_plan", "rfd_detect_views_batch_device", "rfd_detect_views_batch", "rfd_decode_nms_views",
+    "rfd_tracker_config_default", "rfd_tracker_create", "rfd_tracker_destroy", "rfd_tracker_update_device", "rfd_tracker_update",
+    "rfd_tracker_reset", "rfd_tracker_get_tracks", "rfd_align_detections_device",
 ]
 
 _lib = None
@@ -362,6 +380,15 @@ def load_library(path=None):
     L.rfd_detect_views_batch_device.argtypes = [vp, C.POINTER(rfd_image), ci, C.POINTER(rfd_view), ci, C.c_float, C.POINTER(rfd_dets), ci]
     L.rfd_detect_views_batch.argtypes = [vp, C.POINTER(rfd_image), ci, C.POINTER(rfd_view), ci, C.c_float, C.POINTER(rfd_dets)]
     L.rfd_decode_nms_views.argtypes = [vp, C.POINTER(vp), C.POINTER(rfd_view), ci, ci, C.c_float, C.POINTER(rfd_dets), vp]
+    L.rfd_tracker_config_default.argtypes = [vp, C.POINTER(rfd_tracker_config)]
+    L.rfd_tracker_create.argtypes = [vp, C.POINTER(rfd_tracker_config), C.POINTER(vp)]
+    L.rfd_tracker_destroy.argtypes = [vp]
+    L.rfd_tracker_destroy.restype = None
+    L.rfd_tracker_update_device.argtypes = [vp, vp, C.POINTER(rfd_dets), vp, ci, C.POINTER(rfd_track_out), ci]
+    L.rfd_tracker_update.argtypes = [vp, vp, C.POINTER(rfd_dets), vp, ci, C.POINTER(rfd_track_out)]
+    L.rfd_tracker_reset.argtypes = [vp, ci]
+    L.rfd_tracker_get_tracks.argtypes = [vp, ci, C.POINTER(rfd_track), ci, C.POINTER(ci)]
+    L.rfd_align_detections_device.argtypes = [vp, C.POINTER(rfd_image), ci, C.POINTER(rfd_dets), vp, vp, vp, ci, ci, C.POINTER(rfd_face_list), ci]
     if path is None:
         _lib = L
     return L
@@ -897,6 +924,104 @@ class Gallery:
         _check(self._L.rfd_gallery_nearest_device(self._g, int(row0), int(n), C.byref(cfg), scores_ptr, rows_ptr, ids_ptr, int(async_)))
 
 
+TRACK_NEW, TRACK_CONFIRMED, TRACK_DUE = 1, 2, 4   # RFD_TRACK_*: the flags of a tracked row
+TRACKER_MAX_DET = 8192                            # RFD_TRACKER_MAX_DET
+
+
+def tracker_config(det, **fields):
+    """rfd_tracker_config: the default of a detector (1 stream, 64 slots, iou_min 0.3, max_missed 5, both scores = its confidence
+    threshold, min_hits 2, improve 1.1 -- chosen values, not tuned on data) with the given fields replaced"""
+    c = rfd_tracker_config()
+    _check(load_library().rfd_tracker_config_default(det._ctx, C.byref(c)))
+    for k, v in fields.items():
+        if k not in dict(rfd_tracker_config._fields_) or k == "reserved":
+            raise TypeError("rfd_tracker_config has no field %r" % k)
+        setattr(c, k, v)
+    return c
+
+
+class TrackOut:
+    """The host arrays of an rfd_track_out for n frames: track / flags [n, max_det], stats [n, 4] (matched, born, ended,
+    dropped), ended [n, max_tracks], the due slab (boxes [n, max_det, 5], landmarks [n, max_det, 5, 2], count / total [n]) and
+    due_track [n, max_det].  The library writes the rows below each frame's counts only; whatever the arrays held beyond them
+    stays (fill: the byte they start with)."""
+
+    def __init__(self, n, max_det, max_tracks, fill=0, want_due=True):
+        new = lambda shape, dt: np.frombuffer(bytes([fill]) * (int(np.prod(shape)) * np.dtype(dt).itemsize), dt).reshape(shape).copy()
+        self.track, self.flags = new((n, max_det), np.int32), new((n, max_det), np.uint32)
+        self.stats, self.ended = new((n, 4), np.int32), new((n, max_tracks), np.int32)
+        self.due_boxes = new((n, max_det, 5), np.float32) if want_due else None
+        self.due_landmarks = new((n, max_det, 5, 2), np.float32) if want_due else None
+        self.due_count = new((n,), np.int32) if want_due else None
+        self.due_total = new((n,), np.int32) if want_due else None
+        self.due_track = new((n, max_det), np.int32)
+
+    def arrays(self):
+        return [(k, v) for k, v in sorted(vars(self).items()) if v is not None]
+
+    def struct(self):
+        p = lambda a: None if a is None else a.ctypes.data
+        return rfd_track_out(p(self.track), p(self.flags), p(self.stats), p(self.ended),
+                             rfd_dets(p(self.due_boxes), p(self.due_landmarks), p(self.due_count), p(self.due_total)), p(self.due_track))
+
+
+class Tracker:
+    """Faces followed over the frames of video streams, in HBM (rfd.h, "tracker").  Obtained from RetinaFaceDetection.tracker();
+    close it before the detector."""
+
+    def __init__(self, det, cfg=None):
+        self._L, self._det, self._t = det._L, det, C.c_void_p()
+        self.cfg = cfg if cfg is not None else tracker_config(det)
+        _check(self._L.rfd_tracker_create(det._ctx, C.byref(self.cfg), C.byref(self._t)))
+
+    def close(self):
+        if getattr(self, "_t", None) and getattr(self._det, "_ctx", None):
+            self._L.rfd_tracker_destroy(self._t)
+        self._t = None
+
+    def __del__(self):
+        self.close()
+
+    @staticmethod
+    def _streams(streams):
+        return np.ascontiguousarray(np.asarray(streams, np.int64).reshape(-1), np.int32)
+
+    def update(self, streams, boxes, landmarks, count, quality=None, out=None):
+        """the host form: streams [n]; boxes [n, max_det, 5], landmarks [n, max_det, 5, 2], count [n] as the detect calls fill
+        them; quality [n, max_det] or None -> TrackOut (out: a caller-made one to write into)"""
+        s = self._streams(streams)
+        n, md = len(s), self._det.max_det
+        b = np.ascontiguousarray(boxes, np.float32).reshape(n, md, 5)
+        l = np.ascontiguousarray(landmarks, np.float32).reshape(n, md, 10)
+        c = np.ascontiguousarray(count, np.int32).reshape(n)
+        q = None if quality is None else np.ascontiguousarray(quality, np.float32).reshape(n, md)
+        if out is None:
+            out = TrackOut(n, md, self.cfg.max_tracks)
+        d = rfd_dets(b.ctypes.data, l.ctypes.data, c.ctypes.data, None)
+        st = out.struct()
+        _check(self._L.rfd_tracker_update(self._t, s.ctypes.data, C.byref(d), None if q is None else q.ctypes.data, n, C.byref(st)))
+        return out
+
+    def update_device(self, streams, boxes_ptr, landmarks_ptr, count_ptr, out, quality_ptr=None, async_=False):
+        """the same from raw device addresses; out: an rfd_track_out of device addresses.  Enqueued on the detector's stream,
+        with no host synchronisation when async_ is set"""
+        s = self._streams(streams)
+        d = rfd_dets(boxes_ptr, landmarks_ptr, count_ptr, None)
+        _check(self._L.rfd_tracker_update_device(self._t, s.ctypes.data, C.byref(d), quality_ptr, len(s), C.byref(out), int(async_)))
+
+    def reset(self, stream=-1):
+        """the tracks of a stream (-1: of all) vanish without an ended entry; serials go on from where they were"""
+        _check(self._L.rfd_tracker_reset(self._t, int(stream)))
+
+    def tracks(self, stream):
+        """the live slots of a stream in ascending slot order, as rfd_track structures (waits for the stream)"""
+        n = C.c_int(0)
+        _check(self._L.rfd_tracker_get_tracks(self._t, int(stream), None, 0, C.byref(n)))
+        arr = (rfd_track * max(n.value, 1))()
+        _check(self._L.rfd_tracker_get_tracks(self._t, int(stream), arr, n.value, C.byref(n)))
+        return list(arr[:n.value])
+
+
 class RetinaFaceDetection:
     """Host mirror of the reference's RetinaFaceDetection (face_detection.rs:19-513).
 
@@ -941,7 +1066,17 @@ class RetinaFaceDetection:
         self._galleries = getattr(self, "_galleries", []) + [g]
         return g
 
+    def tracker(self, cfg=None, **fields):
+        """a tracker on this detector's device and stream (rfd_tracker_create): cfg, or the default with `fields` replaced; it is
+        closed with the detector at the latest"""
+        t = Tracker(self, cfg if cfg is not None else tracker_config(self, **fields))
+        self._trackers = getattr(self, "_trackers", []) + [t]
+        return t
+
     def close(self):
+        for t in getattr(self, "_trackers", []):
+            t.close()
+        self._trackers = []
         for g in getattr(self, "_galleries", []):
             g.close()
         self._galleries = []
@@ -1425,6 +1560,22 @@ class RetinaFaceDetection:
             out.tensors[j] = p
         _check(self._L.rfd_detect_all_faces_device(self._ctx, arr, n, C.addressof(lc), C.addressof(c), C.addressof(tc), len(cfgs),
                                                    int(cap), C.byref(out), int(async_)))
+
+    def align_detections_device(self, frame_ptrs, shapes, boxes_ptr, landmarks_ptr, count_ptr, cfgs, cap, out, list_cfg=None,
+                                image_size=None, standard_landmarks=None, async_=False):
+        """rfd_align_detections_device: the face list over DEVICE detection slabs (a tracker's due slab, say) of DEVICE frames;
+        out: an rfd_face_list of device addresses.  Enqueued on the context's stream, as detect_all_faces_device."""
+        n = len(frame_ptrs)
+        arr = (rfd_image * n)()
+        for i, (p, (h, w)) in enumerate(zip(frame_ptrs, shapes)):
+            arr[i].data, arr[i].height, arr[i].width, arr[i].stride = p, h, w, w * 3
+        c = self._align_cfg(image_size, standard_landmarks)
+        lc = list_cfg if list_cfg is not None else face_list_config()
+        cfgs = list(cfgs)
+        tc = (rfd_face_tensor_config * max(len(cfgs), 1))(*cfgs)
+        d = rfd_dets(boxes_ptr, landmarks_ptr, count_ptr, None)
+        _check(self._L.rfd_align_detections_device(self._ctx, arr, n, C.byref(d), C.addressof(lc), C.addressof(c), C.addressof(tc),
+                                                   len(cfgs), int(cap), C.byref(out), int(async_)))
 
     def quality_decide(self, logits, threshold):
         """logits [n, classes] of the quality model -> (score [n] f32, klass [n] i32), face_quality.rs:159-168"""
