@@ -1143,6 +1143,71 @@ RFD_API int rfd_align_detections_device(rfd_ctx *ctx, const rfd_image *imgs, int
                                         const rfd_face_list_config *list_cfg, const rfd_alignment_config *align_cfg,
                                         const rfd_face_tensor_config *cfgs, int k, int cap, rfd_face_list *out, int async);
 
+/* ---- shot quality: a figure of merit in [0, 1] for every detection row, on the device, from the pixels under its box and its
+ *      landmarks.  No counterpart in the reference.  It fills the quality[n][max_det] array that rfd_tracker_update_device reads,
+ *      so that the tracker's DUE rule ("a better shot") compares sharpness, pose, exposure and size instead of the detector's
+ *      score: detect -> quality -> track -> align the due faces -> models -> gallery is one stream order with no host wait.
+ *
+ *      The measure, for frame b (H x W, BGR u8, byte stride) and row i < min(max(count[b], 0), max_det); box row x1, y1, x2, y2,
+ *      score; landmark row left eye (lx, ly), right eye (rx, ry), nose (nx, ny), left mouth (mlx, mly), right mouth (mrx, mry).
+ *      Every step is integer, or one IEEE f32 / f64 operation in the written order with no contraction; as_i32(f) truncates
+ *      toward zero, saturates at the int32 ends and maps a NaN to 0.
+ *      Region.   X0 = max(as_i32(x1), 0), Y0 = max(as_i32(y1), 0), X1 = min(as_i32(x2), W - 1), Y1 = min(as_i32(y2), H - 1);
+ *                w = X1 - X0 + 1, h = Y1 - Y0 + 1 as int64.  If w < 32 or h < 32 the row is UNMEASURED: status 1, sharp = mean =
+ *                expo = 0 and q = +0 whatever the score; its landmark parts and its size are still computed.  Otherwise status 0.
+ *      Cells.    A 32 x 32 grid over the region: column edges cx[k] = X0 + (k * w) / 32, row edges cy[k] = Y0 + (k * h) / 32,
+ *                k = 0 .. 32, integer division; cell (r, c) holds the pixels cy[r] <= y < cy[r + 1], cx[c] <= x < cx[c + 1] (never
+ *                empty).  Grey of a pixel: (B * 1868 + G * 9617 + R * 4899 + 8192) >> 14 (OpenCV's fixed-point BGR2GRAY).  Cell
+ *                mean in 8.4 fixed point: m = (16 * S + cnt / 2) / cnt, S the cell's grey sum, cnt its pixel count; 0 .. 4080.
+ *      Sharp.    Over the 30 x 30 interior cells L = 4 m[r][c] - m[r-1][c] - m[r+1][c] - m[r][c-1] - m[r][c+1]; A1 = sum L (int32),
+ *                A2 = sum L * L (int64), V = 900 * A2 - A1 * A1 (int64, 0 <= V < 2^53); sharp = (f32)((f64)V / 207360000.0): the
+ *                variance of the Laplacian of the face normalised to 32 x 32, in grey levels squared.
+ *      Exposure. mean = (f32)((f64)(sum of the 1024 m) / 16384.0); n_lo = cells with m <= 16 * dark, n_hi = cells with m >= 16 *
+ *                bright; expo = 1 - (f32)(n_lo + n_hi) / 1024.
+ *      Pose.     d = rx - lx; ey = (ly + ry) * 0.5; my = (mly + mry) * 0.5; v = my - ey.  If !(d > 0) or !(v > 0) (a NaN fails
+ *                either) pose = yaw = roll = pitch = 0.  Otherwise yaw = |(nx - lx) - (rx - nx)| / d, roll = |ry - ly| / d, pitch =
+ *                |(ny - ey) / v - pitch0|, t = (yaw * w_yaw + roll * w_roll) + pitch * w_pitch, pose = t < 1 ? 1 - t : 0 (0 for a
+ *                NaN t).
+ *      Size.     size = (f32)min(w, h) (from int64; it may be zero or negative for a box outside the frame).
+ *      Quality.  a = times_score ? score * pose : pose; q = ((a * min(sharp / sharp_ref, 1)) * min(size / size_ref, 1)) * expo,
+ *                min(x, 1) = x < 1 ? x : 1.  A NaN score with times_score gives a NaN q, which the tracker never marks DUE.
+ *      A NaN yaw, roll, pitch or q is stored as the quiet NaN 0x7FC00000, so every output bit is defined by the above.
+ *      parts[8] of a row: sharp, mean, expo, yaw, roll, pitch, pose, size.
+ *
+ *      EVERY ROW AT OR PAST A FRAME'S COUNT IS LEFT EXACTLY AS THE CALLER PASSED IT, in quality, parts and status.
+ *      The defaults (rfd_shot_quality_config_default) are CHOSEN values, not tuned on data: this repository has no trained weights
+ *      and no labelled shots.  One workgroup reads a whole region, so a face that fills a 1080p frame is 6 MB through one CU.
+ *      Errors: RFD_ERR_INVALID_ARG with the field named in rfd_last_error() for every bound in the config comments, for a NULL
+ *      required pointer (ctx, imgs, dets and its boxes / landmarks / count, quality), for a frame with a NULL data pointer, a
+ *      non-positive size, a side above RFD_SHOT_QUALITY_MAX_SIDE (the cell sums are int32) or a stride below 3 * width;
+ *      RFD_ERR_CAPACITY for n > max_batch_size; n = 0 is a no-op; nothing is enqueued when a check fails. ---- */
+#define RFD_SHOT_QUALITY_MAX_SIDE 32768
+#define RFD_SHOT_QUALITY_PARTS 8
+typedef struct rfd_shot_quality_config {
+    int32_t dark;         /* 0..255, dark < bright: a cell with m <= 16 * dark is under-exposed */
+    int32_t bright;       /* 0..255: a cell with m >= 16 * bright is over-exposed */
+    float   pitch0;       /* finite: (ny - ey) / v of a frontal face */
+    float   w_yaw;        /* finite, >= 0 */
+    float   w_roll;       /* finite, >= 0 */
+    float   w_pitch;      /* finite, >= 0 */
+    float   sharp_ref;    /* finite, > 0: the sharpness from which a face counts as sharp */
+    float   size_ref;     /* finite, > 0: the side in pixels from which a face counts as large */
+    int32_t times_score;  /* 0 or 1 */
+    int32_t reserved[4];
+} rfd_shot_quality_config; /* default: 30, 225, 0.495 (the nose of the 112 x 112 alignment template), 1, 1, 2, 64, 112, 0 */
+RFD_API int rfd_shot_quality_config_default(rfd_shot_quality_config *cfg);
+/* imgs[] and cfg: host memory; every imgs[i].data, every pointer of `dets` (boxes, landmarks, count; total is not read) and
+ * every output: DEVICE memory.  The counts are read on the device.  Enqueued on the context's stream, one launch, no host wait
+ * (the frame descriptors travel through a ring of page-locked slots); async = 0 returns after the stream has drained, any other
+ * value at once.  parts and status may be NULL. */
+RFD_API int rfd_shot_quality_device(rfd_ctx *ctx, const rfd_image *imgs, int n, const rfd_dets *dets,
+                                    const rfd_shot_quality_config *cfg /* NULL: the default */, float *quality /* [n][max_det] */,
+                                    float *parts /* [n][max_det][8] or NULL */, int32_t *status /* [n][max_det] or NULL */, int async);
+/* Stage-level: the same with host pointers (frames included), through the same kernel; synchronous.  The output arrays travel
+ * to the device and back whole, so what they held past the counts comes back as it was. */
+RFD_API int rfd_shot_quality(rfd_ctx *ctx, const rfd_image *imgs, int n, const rfd_dets *dets, const rfd_shot_quality_config *cfg,
+                             float *quality, float *parts, int32_t *status);
+
 /* ---- introspection ---- */
 RFD_API int rfd_get_stats(rfd_ctx *ctx, rfd_stats *stats);
 RFD_API int rfd_get_config(const rfd_ctx *ctx, rfd_config *cfg);

@@ -780,5 +780,53 @@ inline void align_detections_device(RetinaFaceDetection &det, const std::vector<
     check(rfd_align_detections_device(det.raw(), imgs.data(), (int)imgs.size(), &dets, list_cfg, align_cfg, cfgs.data(), (int)cfgs.size(), cap, &out, async ? 1 : 0));
 }
 
+// ---- shot quality (rfd.h, "shot quality"): a figure of merit in [0, 1] per detection row, the tracker's `quality` ----
+// one frame's answer of the host form, a value per row of the frame
+struct ShotQuality {
+    std::vector<float> quality;
+    std::vector<std::array<float, RFD_SHOT_QUALITY_PARTS>> parts; // sharp, mean, expo, yaw, roll, pitch, pose, size
+    std::vector<int32_t> status;                                  // 1 = unmeasured: the region is below 32 x 32 pixels
+};
+inline rfd_shot_quality_config shot_quality_default_config()
+{
+    rfd_shot_quality_config c;
+    check(rfd_shot_quality_config_default(&c));
+    return c;
+}
+// frames[i] with its detections dets[i] as call_batch returns them; cfg = nullptr: the default
+inline std::vector<ShotQuality> shot_quality(RetinaFaceDetection &det, const std::vector<rfd_image> &frames, const std::vector<Detections> &dets,
+                                             const rfd_shot_quality_config *cfg = nullptr)
+{
+    const std::size_t n = frames.size(), md = det.max_det();
+    if (dets.size() != n) throw Error(RFD_ERR_INVALID_ARG, "shot quality - one detection list per frame");
+    std::vector<float> boxes(n * md * 5), lmk(n * md * 10), q(n * md), parts(n * md * RFD_SHOT_QUALITY_PARTS);
+    std::vector<int32_t> count(n), status(n * md);
+    for (std::size_t i = 0; i < n; ++i) {
+        const std::size_t k = std::min(dets[i].k, md);
+        std::copy(dets[i].det.begin(), dets[i].det.begin() + (std::ptrdiff_t)(k * 5), boxes.begin() + (std::ptrdiff_t)(i * md * 5));
+        std::copy(dets[i].kps.begin(), dets[i].kps.begin() + (std::ptrdiff_t)(k * 10), lmk.begin() + (std::ptrdiff_t)(i * md * 10));
+        count[i] = (int32_t)k;
+    }
+    const rfd_dets d{boxes.data(), lmk.data(), count.data(), nullptr};
+    check(rfd_shot_quality(det.raw(), frames.data(), (int)n, &d, cfg, q.data(), parts.data(), status.data()));
+    std::vector<ShotQuality> res(n);
+    for (std::size_t i = 0; i < n; ++i) {
+        const std::size_t k = (std::size_t)count[i];
+        res[i].quality.assign(q.begin() + (std::ptrdiff_t)(i * md), q.begin() + (std::ptrdiff_t)(i * md + k));
+        res[i].status.assign(status.begin() + (std::ptrdiff_t)(i * md), status.begin() + (std::ptrdiff_t)(i * md + k));
+        res[i].parts.resize(k);
+        for (std::size_t r = 0; r < k; ++r)
+            std::copy_n(parts.begin() + (std::ptrdiff_t)((i * md + r) * RFD_SHOT_QUALITY_PARTS), RFD_SHOT_QUALITY_PARTS, res[i].parts[r].begin());
+    }
+    return res;
+}
+// DEVICE frames, slabs and outputs (parts and status may be null), enqueued on the detector's stream; async: no host
+// synchronisation.  `quality` is what Tracker::update_device takes.
+inline void shot_quality_device(RetinaFaceDetection &det, const std::vector<rfd_image> &imgs, const rfd_dets &dets, const rfd_shot_quality_config *cfg,
+                                float *quality, float *parts = nullptr, int32_t *status = nullptr, bool async = false)
+{
+    check(rfd_shot_quality_device(det.raw(), imgs.data(), (int)imgs.size(), &dets, cfg, quality, parts, status, async ? 1 : 0));
+}
+
 } // namespace rfd
 #endif

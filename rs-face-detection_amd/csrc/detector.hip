@@ -21,6 +21,7 @@
 #include "host_resources.h"
 #include "jpeg_host.h"
 #include "network.h"
+#include "shot_quality_host.h"
 #include "view_plan.h"
 
 namespace rfd {
@@ -214,6 +215,7 @@ struct rfd_ctx {
     DevBuf view_desc;
     PinnedRing<kRing> views_ring; // ViewDesc [B]
     JpegDecoder jpeg; // JPEG decode (rfd.h, "JPEG decode"): jpeg_host.h
+    ShotQuality shot; // shot quality (rfd.h, "shot quality"): shot_quality_host.h
     // pipelined host entry (rfd_submit_batch / rfd_collect_batch): two slots, H2D on its own stream
     struct PipeSlot {
         DevBuf frames, imgs, scale, ob, ol, oc, ot;
@@ -258,6 +260,8 @@ struct rfd_ctx {
 // what a face gallery asks of its context (gallery_host.h)
 hipStream_t rfd::ctx_stream(const rfd_ctx *c) { return c->stream; }
 int rfd::ctx_device(const rfd_ctx *c) { return c->cfg.device_id; }
+// and the shot quality (shot_quality_host.h)
+ShotQuality &rfd::ctx_shot_quality(rfd_ctx *c) { return c->shot; }
 
 namespace {
 

@@ -158,6 +158,12 @@ class rfd_track(C.Structure):
                 ("shot_q", C.c_float)]
 
 
+class rfd_shot_quality_config(C.Structure):
+    _fields_ = [("dark", C.c_int32), ("bright", C.c_int32), ("pitch0", C.c_float), ("w_yaw", C.c_float), ("w_roll", C.c_float),
+                ("w_pitch", C.c_float), ("sharp_ref", C.c_float), ("size_ref", C.c_float), ("times_score", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
 class rfd_jpeg_info(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("sampling", C.c_int32),
                 ("restart_interval", C.c_int32), ("reserved", C.c_int32 * 3)]
@@ -215,6 +221,7 @@ API_SYMBOLS = [
     "rfd_view_config_default", "rfd_view_plan", "rfd_detect_views_batch_device", "rfd_detect_views_batch", "rfd_decode_nms_views",
     "rfd_tracker_config_default", "rfd_tracker_create", "rfd_tracker_destroy", "rfd_tracker_update_device", "rfd_tracker_update",
     "rfd_tracker_reset", "rfd_tracker_get_tracks", "rfd_align_detections_device",
+    "rfd_shot_quality_config_default", "rfd_shot_quality_device", "rfd_shot_quality",
 ]
 
 _lib = None
@@ -389,6 +396,9 @@ def load_library(path=None):
     L.rfd_tracker_reset.argtypes = [vp, ci]
     L.rfd_tracker_get_tracks.argtypes = [vp, ci, C.POINTER(rfd_track), ci, C.POINTER(ci)]
     L.rfd_align_detections_device.argtypes = [vp, C.POINTER(rfd_image), ci, C.POINTER(rfd_dets), vp, vp, vp, ci, ci, C.POINTER(rfd_face_list), ci]
+    L.rfd_shot_quality_config_default.argtypes = [C.POINTER(rfd_shot_quality_config)]
+    L.rfd_shot_quality_device.argtypes = [vp, C.POINTER(rfd_image), ci, C.POINTER(rfd_dets), C.POINTER(rfd_shot_quality_config), vp, vp, vp, ci]
+    L.rfd_shot_quality.argtypes = [vp, C.POINTER(rfd_image), ci, C.POINTER(rfd_dets), C.POINTER(rfd_shot_quality_config), vp, vp, vp]
     if path is None:
         _lib = L
     return L
@@ -1022,6 +1032,22 @@ class Tracker:
         return list(arr[:n.value])
 
 
+SHOT_QUALITY_PARTS = 8            # RFD_SHOT_QUALITY_PARTS: sharp, mean, expo, yaw, roll, pitch, pose, size
+SHOT_QUALITY_MAX_SIDE = 32768     # RFD_SHOT_QUALITY_MAX_SIDE
+
+
+def shot_quality_config(**fields):
+    """rfd_shot_quality_config: the default (dark 30, bright 225, pitch0 0.495, w_yaw 1, w_roll 1, w_pitch 2, sharp_ref 64,
+    size_ref 112, times_score 0 -- chosen values, not tuned on data) with the given fields replaced"""
+    c = rfd_shot_quality_config()
+    _check(load_library().rfd_shot_quality_config_default(C.byref(c)))
+    for k, v in fields.items():
+        if k not in dict(rfd_shot_quality_config._fields_) or k == "reserved":
+            raise TypeError("rfd_shot_quality_config has no field %r" % k)
+        setattr(c, k, v)
+    return c
+
+
 class RetinaFaceDetection:
     """Host mirror of the reference's RetinaFaceDetection (face_detection.rs:19-513).
 
@@ -1576,6 +1602,38 @@ class RetinaFaceDetection:
         d = rfd_dets(boxes_ptr, landmarks_ptr, count_ptr, None)
         _check(self._L.rfd_align_detections_device(self._ctx, arr, n, C.byref(d), C.addressof(lc), C.addressof(c), C.addressof(tc),
                                                    len(cfgs), int(cap), C.byref(out), int(async_)))
+
+    # ---- shot quality: a figure of merit per detection row from the frame, the box and the landmarks (rfd.h, "shot quality") ----
+    def shot_quality(self, frames, dets, cfg=None, device=False, out=None, async_=False):
+        """rfd_shot_quality / rfd_shot_quality_device -> (quality [n, max_det] f32, parts [n, max_det, 8] f32 (sharp, mean, expo,
+        yaw, roll, pitch, pose, size), status [n, max_det] i32); cfg: an rfd_shot_quality_config (shot_quality_config()), None =
+        the default.  Rows at or past a frame's count keep what `out` held.
+        device=False: frames = HxWx3 u8 BGR arrays, dets = (boxes [n, max_det, 5], landmarks [n, max_det, 5, 2], count [n]) as
+        the detect calls fill them; out = (quality, parts, status) arrays to write into (default: zeros), which are returned.
+        device=True: frames = [(device address, height, width[, stride])], dets = (boxes, landmarks, count) device addresses, out =
+        (quality, parts or None, status or None) device addresses, which are returned; enqueued on the context's stream, with no
+        host synchronisation when async_ is set."""
+        n, md = len(frames), self.max_det
+        cp = None if cfg is None else C.byref(cfg)
+        if device:
+            arr = (rfd_image * max(n, 1))()
+            for i, f in enumerate(frames):
+                arr[i].data, arr[i].height, arr[i].width = f[0], f[1], f[2]
+                arr[i].stride = f[3] if len(f) > 3 else f[2] * 3
+            d = rfd_dets(dets[0], dets[1], dets[2], None)
+            _check(self._L.rfd_shot_quality_device(self._ctx, arr, n, C.byref(d), cp, out[0], out[1], out[2], int(async_)))
+            return out
+        arr, keep = self._images(frames)
+        b = np.ascontiguousarray(dets[0], np.float32).reshape(n, md, 5)
+        l = np.ascontiguousarray(dets[1], np.float32).reshape(n, md, 10)
+        c = np.ascontiguousarray(dets[2], np.int32).reshape(n)
+        if out is None:
+            out = (np.zeros((n, md), np.float32), np.zeros((n, md, SHOT_QUALITY_PARTS), np.float32), np.zeros((n, md), np.int32))
+        q, parts, status = out
+        d = rfd_dets(b.ctypes.data, l.ctypes.data, c.ctypes.data, None)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        _check(self._L.rfd_shot_quality(self._ctx, arr, n, C.byref(d), cp, ptr(q), ptr(parts), ptr(status)))
+        return q, parts, status
 
     def quality_decide(self, logits, threshold):
         """logits [n, classes] of the quality model -> (score [n] f32, klass [n] i32), face_quality.rs:159-168"""
