@@ -1208,6 +1208,81 @@ RFD_API int rfd_shot_quality_device(rfd_ctx *ctx, const rfd_image *imgs, int n, 
 RFD_API int rfd_shot_quality(rfd_ctx *ctx, const rfd_image *imgs, int n, const rfd_dets *dets, const rfd_shot_quality_config *cfg,
                              float *quality, float *parts, int32_t *status);
 
+/* ---- frames in camera and decoder formats: what a stream hands out -- NV12 or I420 from a video decoder, YUYV from a V4L2 or USB
+ *      camera, BGRA from a screen or compositor surface -- converted on the device into the packed BGR frames every other entry
+ *      point reads.  In the reference this is the channel handling of byte_data_to_opencv (src/utils/utils.rs:26-49): the fourth
+ *      channel of a 4-channel Mat is dropped (utils.rs:29), a grey one is expanded.  It has no counterpart for the YUV formats.
+ *      Uploading the planes (rfd_upload_frames_device) moves 1.5 bytes per pixel of NV12 over PCIe where a BGR frame is 3.
+ *
+ *      Layouts, for a frame of W x H pixels (rfd_frame_layout_of answers the same); every plane has its own byte stride >= the
+ *      bytes of its rows; odd W and H are legal, cw = ceil(W / 2), ch = ceil(H / 2):
+ *        BGR, RGB      1 plane  [H][W][3]
+ *        BGRA, RGBA    1 plane  [H][W][4], the fourth byte is dropped whatever it holds
+ *        GRAY          1 plane  [H][W], B = G = R = Y, bytes unchanged (no range expansion)
+ *        NV12, NV21    2 planes Y [H][W]; chroma [ch][2 * cw], interleaved U V (NV12) or V U (NV21)
+ *        I420          3 planes Y [H][W]; U [ch][cw]; V [ch][cw]
+ *        YUYV, UYVY    1 plane  [H][4 * cw]: Y0 U Y1 V (YUYV) or U Y0 V Y1 (UYVY) per pair of pixels
+ *      A chroma sample serves its 2 x 2 (NV12, NV21, I420) or 2 x 1 (YUYV, UYVY) luma samples UNFILTERED: pixel (x, y) takes the
+ *      chroma of column x >> 1 (and row y >> 1).  In an odd-width YUYV / UYVY row the second luma byte of the last pair is not used.
+ *
+ *      The arithmetic of the YUV formats, with u = U - 128, v = V - 128, y = limited ? max(Y - 16, 0) : Y, everything int32,
+ *      >> arithmetic (a floor), clamp255 to 0 .. 255:
+ *        R = clamp255((CY * y + CVR * v           + 524288) >> 20)
+ *        G = clamp255((CY * y + CUG * u + CVG * v + 524288) >> 20)
+ *        B = clamp255((CY * y + CUB * u           + 524288) >> 20)
+ *                              CY       CVR      CUG      CVG      CUB    the real coefficients x 2^20, rounded
+ *        BT601_LIMITED    1220542  1673527  -409993  -852492  2116026    1.164, 1.596, -0.391, -0.813, 2.018
+ *        BT601_FULL       1048576  1470104  -360853  -748826  1858077    1, 1.402, -0.344136, -0.714136, 1.772
+ *        BT709_LIMITED    1220542  1880097  -223347  -558891  2214593    1.164, 1.793, -0.213, -0.533, 2.112
+ *        BT709_FULL       1048576  1651297  -196423  -490864  1945738    1, 1.5748, -0.187324, -0.468124, 1.8556
+ *      No sum leaves int32 (the largest magnitude is about 5.6e8).  The BT601_LIMITED row and the replication are what
+ *      cv::cvtColor(COLOR_YUV2BGR_NV12 / _I420 / _YUY2) computes (the ITUR_BT_601_* constants and shift 20 of OpenCV's color_yuv);
+ *      that is RESTATED here, unpinned against a running OpenCV, like the alignment.  tests/frame_ref.py is the same in numpy, and
+ *      the kernel equals it bit for bit.  The other formats are byte moves.
+ *
+ *      Errors.  RFD_ERR_INVALID_ARG, with the frame and the cause named in rfd_last_error(): out[i].width / height differs from
+ *      src[i]'s; out[i].stride < 3 * width; a stride below the layout's row_bytes; a needed plane (or out[i].data) is NULL; an
+ *      unknown format, or an unknown colour of a YUV frame; a non-positive size; reserved not zero.  RFD_ERR_CAPACITY: n >
+ *      max_batch_size, a frame wider than max_src_w or higher than max_src_h, a frame of 2^31 - 256 or more groups of four pixels.  n = 0 is a no-op.  A refused call enqueues nothing
+ *      and writes no byte of any output frame.  Bytes of an output row at or past 3 * width are never written. ---- */
+typedef enum rfd_pixel_format {
+    RFD_PIXEL_BGR = 0,  RFD_PIXEL_RGB = 1,      /* [H][W][3]                                   1 plane  */
+    RFD_PIXEL_BGRA = 2, RFD_PIXEL_RGBA = 3,     /* [H][W][4], 4th byte dropped (utils.rs:29)   1 plane  */
+    RFD_PIXEL_GRAY = 4,                         /* [H][W], B = G = R = Y, bytes unchanged       1 plane  */
+    RFD_PIXEL_NV12 = 5, RFD_PIXEL_NV21 = 6,     /* Y [H][W]; UV (VU) [ceil(H/2)][2*ceil(W/2)]   2 planes */
+    RFD_PIXEL_I420 = 7,                         /* Y; U, V [ceil(H/2)][ceil(W/2)] each          3 planes */
+    RFD_PIXEL_YUYV = 8, RFD_PIXEL_UYVY = 9      /* [H][4*ceil(W/2)]: Y0 U Y1 V / U Y0 V Y1      1 plane  */
+} rfd_pixel_format;
+typedef enum rfd_color { RFD_COLOR_BT601_LIMITED = 0, RFD_COLOR_BT601_FULL = 1,
+                         RFD_COLOR_BT709_LIMITED = 2, RFD_COLOR_BT709_FULL = 3 } rfd_color;
+typedef struct rfd_frame {
+    const uint8_t *plane[3]; ptrdiff_t stride[3];   /* planes the format does not have are not read */
+    int32_t width, height, format, color;           /* color is ignored by formats 0..4 */
+    int32_t reserved[4];                            /* 0 */
+} rfd_frame;                                        /* 80 bytes */
+typedef struct rfd_frame_layout { int32_t planes; int32_t row_bytes[3]; int32_t rows[3]; int32_t reserved; } rfd_frame_layout;
+
+/* Host only, no context: the planes of `format` at width x height.  RFD_ERR_INVALID_ARG for an unknown format, a NULL out or a
+ * side outside 1 .. 2^28; *out is then untouched. */
+RFD_API int rfd_frame_layout_of(int format, int width, int height, rfd_frame_layout *out);
+/* Converts n frames into n caller-allocated DEVICE frames: every needed src[i].plane and out[i].data are device memory; src[] and
+ * out[] themselves are host memory and may be freed when the call returns.  rfd_image declares data const because every other
+ * entry point reads frames; this one WRITES through it (the library casts the const away), as rfd_decode_jpeg_batch_device
+ * does.  The same array is then valid input to rfd_detect_batch_device, the views, the shot quality, the alignment and the
+ * liveness calls on the same stream, with no synchronisation in between.  One launch per batch on the context's stream, whatever
+ * the number, sizes and formats of its frames; the descriptors travel through a ring of page-locked slots, so a warm call
+ * allocates nothing and does not wait for the previous one.  async as in rfd_decode_jpeg_batch_device: 0 returns after the
+ * stream has drained, any other value at once (rfd_sync before reading the frames from another stream).  No output frame may
+ * overlap a plane of the call: the conversion is not in place. */
+RFD_API int rfd_convert_frames_device(rfd_ctx *ctx, const rfd_frame *src, int n, const rfd_image *out, int async);
+/* The same with the planes in HOST memory, pageable or from rfd_host_alloc: each plane goes to device staging of the context with
+ * one 2-D copy of tight rows, then the same launch writes the caller's DEVICE frames.  With async != 0 the planes must stay as
+ * they are until the stream has run the copies (rfd_sync).  Staging reuse: the staging grows on demand and is reused by the next
+ * call, whose copies follow this call's kernel in stream order, so two asynchronous calls back to back are safe. */
+RFD_API int rfd_upload_frames_device(rfd_ctx *ctx, const rfd_frame *src, int n, const rfd_image *out, int async);
+/* The same with everything in HOST memory (out[i].data is host memory, written through the same const cast); synchronous. */
+RFD_API int rfd_convert_frames(rfd_ctx *ctx, const rfd_frame *src, int n, const rfd_image *out);
+
 /* ---- introspection ---- */
 RFD_API int rfd_get_stats(rfd_ctx *ctx, rfd_stats *stats);
 RFD_API int rfd_get_config(const rfd_ctx *ctx, rfd_config *cfg);

@@ -17,6 +17,7 @@
 #include <thread>
 #include <vector>
 
+#include "frame_host.h"
 #include "gallery_host.h"
 #include "host_resources.h"
 #include "jpeg_host.h"
@@ -216,6 +217,7 @@ struct rfd_ctx {
     PinnedRing<kRing> views_ring; // ViewDesc [B]
     JpegDecoder jpeg; // JPEG decode (rfd.h, "JPEG decode"): jpeg_host.h
     ShotQuality shot; // shot quality (rfd.h, "shot quality"): shot_quality_host.h
+    FrameConvert frames; // frames in camera and decoder formats (rfd.h): frame_host.h
     // pipelined host entry (rfd_submit_batch / rfd_collect_batch): two slots, H2D on its own stream
     struct PipeSlot {
         DevBuf frames, imgs, scale, ob, ol, oc, ot;
@@ -262,6 +264,8 @@ hipStream_t rfd::ctx_stream(const rfd_ctx *c) { return c->stream; }
 int rfd::ctx_device(const rfd_ctx *c) { return c->cfg.device_id; }
 // and the shot quality (shot_quality_host.h)
 ShotQuality &rfd::ctx_shot_quality(rfd_ctx *c) { return c->shot; }
+// and the frame conversion (frame_host.h)
+FrameConvert &rfd::ctx_frame_convert(rfd_ctx *c) { return c->frames; }
 
 namespace {
 

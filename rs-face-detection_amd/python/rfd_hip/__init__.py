@@ -164,6 +164,15 @@ class rfd_shot_quality_config(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+class rfd_frame(C.Structure):
+    _fields_ = [("plane", C.c_void_p * 3), ("stride", C.c_ssize_t * 3), ("width", C.c_int32), ("height", C.c_int32),
+                ("format", C.c_int32), ("color", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class rfd_frame_layout(C.Structure):
+    _fields_ = [("planes", C.c_int32), ("row_bytes", C.c_int32 * 3), ("rows", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+
 class rfd_jpeg_info(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("sampling", C.c_int32),
                 ("restart_interval", C.c_int32), ("reserved", C.c_int32 * 3)]
@@ -222,6 +231,7 @@ API_SYMBOLS = [
     "rfd_tracker_config_default", "rfd_tracker_create", "rfd_tracker_destroy", "rfd_tracker_update_device", "rfd_tracker_update",
     "rfd_tracker_reset", "rfd_tracker_get_tracks", "rfd_align_detections_device",
     "rfd_shot_quality_config_default", "rfd_shot_quality_device", "rfd_shot_quality",
+    "rfd_frame_layout_of", "rfd_convert_frames_device", "rfd_upload_frames_device", "rfd_convert_frames",
 ]
 
 _lib = None
@@ -399,6 +409,10 @@ def load_library(path=None):
     L.rfd_shot_quality_config_default.argtypes = [C.POINTER(rfd_shot_quality_config)]
     L.rfd_shot_quality_device.argtypes = [vp, C.POINTER(rfd_image), ci, C.POINTER(rfd_dets), C.POINTER(rfd_shot_quality_config), vp, vp, vp, ci]
     L.rfd_shot_quality.argtypes = [vp, C.POINTER(rfd_image), ci, C.POINTER(rfd_dets), C.POINTER(rfd_shot_quality_config), vp, vp, vp]
+    L.rfd_frame_layout_of.argtypes = [ci, ci, ci, C.POINTER(rfd_frame_layout)]
+    L.rfd_convert_frames_device.argtypes = [vp, C.POINTER(rfd_frame), ci, C.POINTER(rfd_image), ci]
+    L.rfd_upload_frames_device.argtypes = [vp, C.POINTER(rfd_frame), ci, C.POINTER(rfd_image), ci]
+    L.rfd_convert_frames.argtypes = [vp, C.POINTER(rfd_frame), ci, C.POINTER(rfd_image)]
     if path is None:
         _lib = L
     return L
@@ -1048,6 +1062,37 @@ def shot_quality_config(**fields):
     return c
 
 
+# rfd_pixel_format and rfd_color (rfd.h, "frames in camera and decoder formats")
+PIXEL_BGR, PIXEL_RGB, PIXEL_BGRA, PIXEL_RGBA, PIXEL_GRAY, PIXEL_NV12, PIXEL_NV21, PIXEL_I420, PIXEL_YUYV, PIXEL_UYVY = range(10)
+COLOR_BT601_LIMITED, COLOR_BT601_FULL, COLOR_BT709_LIMITED, COLOR_BT709_FULL = range(4)
+PIXEL_FORMAT_NAMES = ("bgr", "rgb", "bgra", "rgba", "gray", "nv12", "nv21", "i420", "yuyv", "uyvy")
+
+
+def pixel_format(fmt):
+    """a PIXEL_* value from a value or a lower-case name ("nv12")"""
+    return PIXEL_FORMAT_NAMES.index(fmt) if isinstance(fmt, str) else int(fmt)
+
+
+def frame_layout(fmt, w, h):
+    """rfd_frame_layout_of -> {"planes", "row_bytes" [planes], "rows" [planes]}: host only, no context"""
+    l = rfd_frame_layout()
+    _check(load_library().rfd_frame_layout_of(pixel_format(fmt), int(w), int(h), C.byref(l)))
+    return {"planes": l.planes, "row_bytes": list(l.row_bytes[:l.planes]), "rows": list(l.rows[:l.planes])}
+
+
+def frame(fmt, width, height, planes, strides=None, color=COLOR_BT601_LIMITED):
+    """an rfd_frame from raw addresses: planes = the address of each plane the format has, strides = their byte strides
+    (default: the layout's row_bytes)"""
+    f = rfd_frame()
+    f.format, f.width, f.height, f.color = pixel_format(fmt), int(width), int(height), int(color)
+    if strides is None:
+        strides = frame_layout(fmt, width, height)["row_bytes"]
+    for k, a in enumerate(planes):
+        f.plane[k] = a
+        f.stride[k] = int(strides[k])
+    return f
+
+
 class RetinaFaceDetection:
     """Host mirror of the reference's RetinaFaceDetection (face_detection.rs:19-513).
 
@@ -1634,6 +1679,47 @@ class RetinaFaceDetection:
         ptr = lambda a: None if a is None else a.ctypes.data
         _check(self._L.rfd_shot_quality(self._ctx, arr, n, C.byref(d), cp, ptr(q), ptr(parts), ptr(status)))
         return q, parts, status
+
+    # ---- frames in camera and decoder formats (rfd.h): NV12, I420, YUYV, BGRA ... -> the BGR frames every other call reads ----
+    def convert_frames(self, frames):
+        """rfd_convert_frames.  frames: list of (format, width, height, planes[, color]); format a PIXEL_* value or its lower-case
+        name, planes the 2-D u8 host arrays of the format's planes ([rows, row_bytes], any row stride, unit byte stride), color
+        a COLOR_* value (default BT.601 limited).  -> list of [H, W, 3] u8 BGR host arrays, converted on the device."""
+        n = len(frames)
+        src, keep, outs = (rfd_frame * max(n, 1))(), [], []
+        for i, fr in enumerate(frames):
+            fmt, w, h, planes = fr[0], int(fr[1]), int(fr[2]), fr[3]
+            for a in planes:
+                if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 2 and (a.shape[1] <= 1 or a.strides[1] == 1)):
+                    raise RfdError(RFD_ERR_INVALID_ARG, "frame %d: planes must be 2-D uint8 arrays with contiguous rows" % i)
+            keep.append(planes)
+            src[i] = frame(fmt, w, h, [a.ctypes.data for a in planes], [a.strides[0] for a in planes], fr[4] if len(fr) > 4 else 0)
+            outs.append(np.zeros((h, w, 3), np.uint8))
+        arr, keep_out = self._images(outs) if outs else ((rfd_image * 1)(), [])
+        _check(self._L.rfd_convert_frames(self._ctx, src, n, arr))
+        return outs
+
+    def _frames_call(self, fn, frames, frame_ptrs, strides, async_):
+        n = len(frames)
+        src, arr = (rfd_frame * max(n, 1))(), (rfd_image * max(n, 1))()
+        for i, f in enumerate(frames):
+            src[i] = f
+            arr[i].data, arr[i].height, arr[i].width = frame_ptrs[i], f.height, f.width
+            arr[i].stride = int(strides[i]) if strides is not None else f.width * 3
+        _check(fn(self._ctx, src, n, arr, int(async_)))
+        return arr
+
+    def convert_frames_device(self, frames, frame_ptrs, strides=None, async_=False):
+        """rfd_convert_frames_device.  frames: rfd_frame structures (frame()) whose planes are raw DEVICE addresses; frame_ptrs[i]:
+        the raw device address of output frame i, of frames[i].height rows of strides[i] bytes (default 3 * width).  Returns the
+        rfd_image array, which is valid input to the device-resident detect calls; enqueued on the detector's stream, with no
+        host synchronisation when async_ is set."""
+        return self._frames_call(self._L.rfd_convert_frames_device, frames, frame_ptrs, strides, async_)
+
+    def upload_frames_device(self, frames, frame_ptrs, strides=None, async_=False):
+        """rfd_upload_frames_device: the same with the planes at raw HOST addresses (pageable or host_alloc memory), which must
+        stay as they are until the stream has run the copies when async_ is set."""
+        return self._frames_call(self._L.rfd_upload_frames_device, frames, frame_ptrs, strides, async_)
 
     def quality_decide(self, logits, threshold):
         """logits [n, classes] of the quality model -> (score [n] f32, klass [n] i32), face_quality.rs:159-168"""
