@@ -2,23 +2,24 @@
 // `RetinaFaceDetection` (src/pipeline/module/face_detection.rs:19-513) driving the HIP kernels, and
 // the C ABI of include/rfd.h on top of it.  (The reference's host language, Rust, has no toolchain
 // in this image; INTEGRATION.md shows the `extern "C"` facade that keeps its `call` signature.)
-// Two stateful layers of the ABI have files of their own: the JPEG decode (jpeg_host.hip) and the face gallery
-// (gallery_host.hip), which reaches the context through the two accessors of gallery_host.h alone.
+// This file is the context (rfd_ctx, private to it) and the detection alone: frames in, network, decode / sort / NMS, the
+// views, the pipelined and multi-GPU entries, weights, and the test hooks of those.  Every other stateful layer of the ABI has a
+// file of its own and sees the context through ctx_access.h: the face stage behind the detection (face_host.hip), the JPEG decode
+// (jpeg_host.hip), the frame conversion (frame_host.hip), the shot quality (shot_quality_host.hip), the face gallery
+// (gallery_host.hip) and the tracker (tracker_host.hip).
 #include <dlfcn.h>
 #include <stdarg.h>
 #include <stdlib.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <functional>
 #include <memory>
 #include <mutex>
-#include <thread>
 #include <vector>
 
+#include "ctx_access.h"
+#include "face_host.h"
 #include "frame_host.h"
-#include "gallery_host.h"
 #include "host_resources.h"
 #include "jpeg_host.h"
 #include "network.h"
@@ -85,12 +86,8 @@ static void letterbox(int img_h, int img_w, int size_w, int size_h, PreImage *pi
     pi->scale_x = pi->scale_y = 1.0;
     pi->area_fast = 0;
     if (new_w > 0 && new_h > 0) {
-        const double inv_x = (double)new_w / img_w, inv_y = (double)new_h / img_h;
-        pi->scale_x = 1.0 / inv_x;
-        pi->scale_y = 1.0 / inv_y;
-        const int ix = (int)lrint(pi->scale_x), iy = (int)lrint(pi->scale_y);
-        pi->area_fast = fabs(pi->scale_x - ix) < 2.220446049250313e-16 &&
-                        fabs(pi->scale_y - iy) < 2.220446049250313e-16 && ix == 2 && iy == 2;
+        const ResizeScale r = resize_scale(img_w, img_h, new_w, new_h);
+        pi->scale_x = r.scale_x; pi->scale_y = r.scale_y; pi->area_fast = r.area_fast;
     }
 }
 
@@ -195,23 +192,10 @@ struct rfd_ctx {
     Pinned<int> h_nms_flag;
     DevBuf out_boxes, out_lmk, out_count, out_total, out_gidx;
     DevBuf scratch[12];
-    DevBuf sel_dims, sel_out;
-    DevBuf align_faces, align_out, align_status;
-    // model inputs of the quality / ID stages: staged crops and per-config planes of the host entries; in / out staging of the
-    // host forms of the decision rule and the normalisation
-    DevBuf face_in, face_tensors[kMaxFaceTensors], face_io[2];
-    // packed face list of the host-output entries (FaceListView), and the page-locked copy of total | first [B + 1] that tells
-    // the host how many rows to fetch; both allocated by the first such call
-    DevBuf list_out;
-    Pinned<int> h_list;
+    FaceStage face; // selection, alignment, model inputs, face list, liveness (rfd.h): face_host.h
     // Per-call descriptors travel through rings of page-locked slots, so enqueueing never blocks on the previous call.
     static constexpr int kRing = 4;
     PinnedRing<kRing> frame_ring; // PreImage [B] | det_scale f32 [B]; its events can be timed
-    PinnedRing<kRing> dims_ring;  // frame sizes of the selection epilogue: h i32 [n] | w i32 [n]
-    PinnedRing<kRing> live_ring;  // LiveImage [B]; allocated by the first liveness call
-    // liveness stage, all allocated by its first call: frame descriptors, the per-(face, model) geometry, the in / out staging of
-    // the host forms, the running sums of a decide call of many models
-    DevBuf live_imgs, live_geo, live_io, live_acc;
     // views (rfd.h, "views"), both allocated by the first views call: the per-view descriptors of decode_views_kernel
     DevBuf view_desc;
     PinnedRing<kRing> views_ring; // ViewDesc [B]
@@ -258,14 +242,6 @@ struct rfd_ctx {
         return RFD_OK;
     }
 };
-
-// what a face gallery asks of its context (gallery_host.h)
-hipStream_t rfd::ctx_stream(const rfd_ctx *c) { return c->stream; }
-int rfd::ctx_device(const rfd_ctx *c) { return c->cfg.device_id; }
-// and the shot quality (shot_quality_host.h)
-ShotQuality &rfd::ctx_shot_quality(rfd_ctx *c) { return c->shot; }
-// and the frame conversion (frame_host.h)
-FrameConvert &rfd::ctx_frame_convert(rfd_ctx *c) { return c->frames; }
 
 namespace {
 
@@ -320,25 +296,32 @@ size_t frames_bytes(const rfd_image *imgs, int n) // packed back to back with ti
     return total;
 }
 
-// Where the kernels read frame i: desc[i].src / .stride (PreImage, LiveImage).  Device frames are read where they lie; host
-// frames are packed into c->staging on the context's stream, one 2-D copy each.
-template <class Desc> int place_frames(rfd_ctx *c, const rfd_image *imgs, int n, bool frames_on_device, Desc *desc)
+// Where the kernels read frame i: the two leading members of descriptor i (PreImage, LiveImage), the descriptors `pitch` bytes
+// apart.  Device frames are read where they lie; host frames are packed into c->staging on the context's stream, one 2-D copy
+// each.
+struct FrameWhere {
+    const uint8_t *src;
+    long long stride;
+};
+static_assert(offsetof(PreImage, src) == 0 && offsetof(PreImage, stride) == offsetof(FrameWhere, stride) &&
+              offsetof(LiveImage, src) == 0 && offsetof(LiveImage, stride) == offsetof(FrameWhere, stride),
+              "place_frames writes src and stride there");
+
+int place_frames(rfd_ctx *c, const rfd_image *imgs, int n, bool frames_on_device, void *desc, size_t pitch)
 {
     if (!frames_on_device) RFD_TRY(c->staging.reserve(frames_bytes(imgs, n)));
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
-        if (frames_on_device) {
-            desc[i].src = imgs[i].data;
-            desc[i].stride = (long long)imgs[i].stride;
-        } else {
+        FrameWhere w = {imgs[i].data, (long long)imgs[i].stride};
+        if (!frames_on_device) {
             uint8_t *dst = (uint8_t *)c->staging.p + off;
             const size_t row = (size_t)imgs[i].width * 3;
             RFD_HIP(hipMemcpy2DAsync(dst, row, imgs[i].data, (size_t)imgs[i].stride, row, imgs[i].height,
                                      hipMemcpyHostToDevice, c->stream));
-            desc[i].src = dst;
-            desc[i].stride = (long long)row;
+            w = FrameWhere{dst, (long long)row};
             off += row * imgs[i].height;
         }
+        memcpy((char *)desc + (size_t)i * pitch, &w, sizeof w);
     }
     return RFD_OK;
 }
@@ -371,7 +354,7 @@ int stage_frames(rfd_ctx *c, const rfd_image *imgs, int n, bool frames_on_device
     RFD_TRY(acquire_frame_slot(c, &pis, &pin_scales));
     for (int i = 0; i < n; ++i) RFD_TRY(fill_pre_image(c, imgs[i], i, &pis[i], &pin_scales[i]));
     if (det_scales) *det_scales = pin_scales; // the slot: good until kRing - 1 more calls have taken theirs
-    RFD_TRY(place_frames(c, imgs, n, frames_on_device, pis));
+    RFD_TRY(place_frames(c, imgs, n, frames_on_device, pis, sizeof *pis));
     RFD_HIP(hipMemcpyAsync(c->imgs.p, pis, n * sizeof(PreImage), hipMemcpyHostToDevice, c->stream));
     RFD_HIP(hipMemcpyAsync(c->det_scale.p, pin_scales, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     return c->frame_ring.record(c->stream);
@@ -545,7 +528,7 @@ int detect_overlapped(rfd_ctx *c, const rfd_image *imgs, int n, rfd_dets *out, h
     float *pin_scales;
     RFD_TRY(acquire_frame_slot(c, &pis, &pin_scales));
     for (int i = 0; i < n; ++i) RFD_TRY(fill_pre_image(c, imgs[i], i, &pis[i], &pin_scales[i]));
-    RFD_TRY(place_frames(c, imgs, n, true, pis));
+    RFD_TRY(place_frames(c, imgs, n, true, pis, sizeof *pis));
     hipStream_t st[2] = {net.part_stream[0], net.part_stream[1]};
     if (c->ov_last_n != n) {
         // Different slices than the previous call's chains (another batch size), or the previous call ran on the caller's
@@ -728,10 +711,10 @@ int detect_views_impl(rfd_ctx *c, const rfd_image *frames, int n_frames, const r
     if (!c->net.weights_ready) { set_error("network weights are not initialised"); return RFD_ERR_STATE; }
     c->ov_last_n = -1;
     RFD_HIP(hipEventRecord(c->ev[0], c->stream));
-    std::vector<PreImage> where(n_frames); // each FRAME is placed once; its views point into it
-    RFD_TRY(place_frames(c, frames, n_frames, on_device, where.data()));
+    std::vector<FrameWhere> where(n_frames); // each FRAME is placed once; its views point into it
+    RFD_TRY(place_frames(c, frames, n_frames, on_device, where.data(), sizeof(FrameWhere)));
     for (int i = 0; i < n_views; ++i) {
-        const PreImage &f = where[views[i].frame];
+        const FrameWhere &f = where[views[i].frame];
         pis[i].src = f.src + (long long)views[i].y * f.stride + 3ll * views[i].x;
         pis[i].stride = f.stride;
     }
@@ -761,6 +744,47 @@ std::mutex g_nms_mu;
 rfd_ctx *g_nms_ctx[16] = {};
 
 } // namespace
+
+// ---- what the layers next to this file ask of their context (ctx_access.h) ----
+hipStream_t rfd::ctx_stream(const rfd_ctx *c) { return c->stream; }
+int rfd::ctx_device(const rfd_ctx *c) { return c->cfg.device_id; }
+int rfd::ctx_max_batch_size(const rfd_ctx *c) { return c->cfg.max_batch_size; }
+int rfd::ctx_max_det(const rfd_ctx *c) { return c->cfg.max_det; }
+ShotQuality &rfd::ctx_shot_quality(rfd_ctx *c) { return c->shot; }
+FrameConvert &rfd::ctx_frame_convert(rfd_ctx *c) { return c->frames; }
+FaceStage &rfd::ctx_face_stage(rfd_ctx *c) { return c->face; }
+int rfd::ctx_check_batch(const rfd_ctx *c, int n, const char *what, const char *unit) { return check_batch(c, n, what, unit); }
+int rfd::ctx_check_images(const rfd_ctx *c, const rfd_image *imgs, int n) { return check_images(c, imgs, n); }
+int rfd::ctx_place_frames(rfd_ctx *c, const rfd_image *imgs, int n, bool frames_on_device, void *desc, size_t pitch)
+{
+    return place_frames(c, imgs, n, frames_on_device, desc, pitch);
+}
+int rfd::ctx_stage_frames(rfd_ctx *c, const rfd_image *imgs, int n, bool frames_on_device, const PreImage **staged)
+{
+    *staged = (const PreImage *)c->imgs.p;
+    return stage_frames(c, imgs, n, frames_on_device);
+}
+int rfd::ctx_stage_frame_sizes(rfd_ctx *c, const int32_t *img_w, const int32_t *img_h, int n, const PreImage **staged)
+{
+    PreImage *pis;
+    float *pin_scales;
+    RFD_TRY(acquire_frame_slot(c, &pis, &pin_scales));
+    memset(pis, 0, (size_t)n * sizeof(PreImage));
+    for (int i = 0; i < n; ++i) { pis[i].w = img_w[i]; pis[i].h = img_h[i]; }
+    RFD_HIP(hipMemcpyAsync(c->imgs.p, pis, n * sizeof(PreImage), hipMemcpyHostToDevice, c->stream));
+    *staged = (const PreImage *)c->imgs.p;
+    return c->frame_ring.record(c->stream);
+}
+rfd_dets rfd::ctx_own_slabs(const rfd_ctx *c) { return own_slabs(c); }
+int rfd::ctx_copy_slabs(rfd_ctx *c, const rfd_dets &dst, const rfd_dets &src, int n, hipMemcpyKind kind) { return copy_slabs(c, dst, src, n, kind); }
+int rfd::ctx_detect_own_slabs(rfd_ctx *c, const rfd_image *imgs, int n, bool frames_on_device, rfd_dets *dev, const PreImage **staged)
+{
+    RFD_CHECK_ARG(c != nullptr, "ctx is null");
+    *dev = own_slabs(c);
+    *staged = (const PreImage *)c->imgs.p;
+    return detect_impl(c, imgs, n, dev, /*outputs stay on the device*/ true, /*async*/ 1, frames_on_device);
+}
+int rfd::ctx_check_nms_flag(rfd_ctx *c) { return check_nms_flag(c); }
 
 // ================================================================================================
 // C ABI
@@ -829,7 +853,7 @@ int rfd_create(const rfd_config *cfg, rfd_ctx **out)
     c->stream = c->own_stream;
     for (Event &e : c->ev) RFD_TRY(e.create(hipEventDefault));
     RFD_TRY(c->frame_ring.ensure(B * (sizeof(PreImage) + sizeof(float)), hipEventDefault));
-    RFD_TRY(c->dims_ring.ensure(B * 2 * sizeof(int)));
+    RFD_TRY(c->face.dims_ring.ensure(B * 2 * sizeof(int)));
     RFD_TRY(c->h_nms_flag.alloc(1));
     *c->h_nms_flag = 0;
     RFD_TRY(ctx_alloc(c.get()));
@@ -1622,846 +1646,6 @@ int rfd_decode_nms_views(rfd_ctx *c, const float *const heads[9], const rfd_view
     RFD_TRY(check_nms_flag(c));
     RFD_TRY(finish_stats(c, n_frames, false, false));
     for (int i = 0; i < n_frames; ++i) c->stats.detections += out->total ? out->total[i] : out->count[i];
-    return RFD_OK;
-}
-
-void rfd_selection_config_default(rfd_selection_config *cfg)
-{
-    if (!cfg) return;
-    cfg->margin_center_left_ratio = 0.3f;  // config.rs:110
-    cfg->margin_center_right_ratio = 0.3f; // config.rs:111
-    cfg->margin_edge_ratio = 0.1f;         // config.rs:112
-    cfg->minimum_face_ratio = 0.0075f;     // config.rs:113
-}
-
-// selection over device-resident detection slabs into device arrays d_box [n][5], d_kps [n][10], d_found [n]; enqueued only.
-// The frame sizes go through a ring of page-locked arrays (as the frame descriptors do, stage_frames), so nothing here
-// needs the host to wait for the stream.
-static int select_enqueue(rfd_ctx *c, const float *d_boxes, const float *d_lmk, const int *d_count, const int *img_h,
-                          const int *img_w, int n, const rfd_selection_config *cfg, int is_enroll, float *d_box,
-                          float *d_kps, int32_t *d_found)
-{
-    rfd_selection_config def;
-    rfd_selection_config_default(&def);
-    if (!cfg) cfg = &def;
-    RFD_TRY(c->sel_dims.reserve((size_t)2 * n * sizeof(int)));
-    int *dims;
-    RFD_TRY(c->dims_ring.acquire(&dims));
-    for (int i = 0; i < n; ++i) { dims[i] = img_h[i]; dims[n + i] = img_w[i]; }
-    RFD_HIP(hipMemcpyAsync(c->sel_dims.p, dims, 2 * n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    RFD_TRY(c->dims_ring.record(c->stream));
-    SelectParams sp;
-    memset(&sp, 0, sizeof sp);
-    sp.boxes = d_boxes; sp.lmk = d_lmk; sp.count = d_count;
-    sp.img_h = (const int *)c->sel_dims.p; sp.img_w = sp.img_h + n;
-    sp.n = n; sp.max_det = c->cfg.max_det; sp.is_enroll = is_enroll;
-    sp.margin_center_left_ratio = cfg->margin_center_left_ratio;
-    sp.margin_center_right_ratio = cfg->margin_center_right_ratio;
-    sp.margin_edge_ratio = cfg->margin_edge_ratio;
-    sp.minimum_face_ratio = cfg->minimum_face_ratio;
-    sp.out_box = d_box; sp.out_kps = d_kps; sp.out_found = d_found;
-    return launch_face_select(sp, c->stream);
-}
-
-// c->sel_out holds the selection of n frames as box [n][5] | kps [n][10] | found [n]
-struct SelView { float *box, *kps; int32_t *found; };
-static SelView sel_view(const rfd_ctx *c, int n)
-{
-    float *o = (float *)c->sel_out.p;
-    return SelView{o, o + (size_t)n * 5, (int32_t *)(o + (size_t)n * 15)};
-}
-static int sel_reserve(rfd_ctx *c, int n) { return c->sel_out.reserve((size_t)n * 16 * sizeof(float)); }
-
-// a selection the caller holds on the host, into c->sel_out
-static int sel_upload(rfd_ctx *c, int n, const float *boxes, const float *kps, const int32_t *found)
-{
-    RFD_TRY(sel_reserve(c, n));
-    const SelView v = sel_view(c, n);
-    RFD_HIP(hipMemcpyAsync(v.box, boxes, (size_t)n * 5 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    RFD_HIP(hipMemcpyAsync(v.kps, kps, (size_t)n * 10 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    RFD_HIP(hipMemcpyAsync(v.found, found, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    return RFD_OK;
-}
-
-// select_enqueue into c->sel_out, then copied to the host pointers
-static int select_impl(rfd_ctx *c, const float *d_boxes, const float *d_lmk, const int *d_count, const int *img_h,
-                       const int *img_w, int n, const rfd_selection_config *cfg, int is_enroll, float *out_box,
-                       float *out_kps, int32_t *found)
-{
-    RFD_TRY(sel_reserve(c, n));
-    const SelView v = sel_view(c, n);
-    RFD_TRY(select_enqueue(c, d_boxes, d_lmk, d_count, img_h, img_w, n, cfg, is_enroll, v.box, v.kps, v.found));
-    RFD_HIP(hipMemcpyAsync(out_box, v.box, (size_t)n * 5 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipMemcpyAsync(out_kps, v.kps, (size_t)n * 10 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipMemcpyAsync(found, v.found, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipStreamSynchronize(c->stream)); // the results are read by the caller
-    return check_nms_flag(c);
-}
-
-int rfd_select_faces(rfd_ctx *c, const rfd_dets *dets, const int *img_h, const int *img_w, int n,
-                     const rfd_selection_config *cfg, int is_enroll, float *out_box, float *out_kps, int32_t *found)
-{
-    RFD_CHECK_ARG(c && dets && dets->boxes && dets->landmarks && dets->count && img_h && img_w && out_box && out_kps && found,
-                  "null argument");
-    RFD_TRY(check_batch(c, n, "batch"));
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    rfd_dets dev = own_slabs(c);
-    dev.total = nullptr; // the selection does not read it
-    RFD_TRY(copy_slabs(c, dev, *dets, n, hipMemcpyHostToDevice));
-    return select_impl(c, dev.boxes, dev.landmarks, dev.count, img_h, img_w, n, cfg, is_enroll, out_box, out_kps, found);
-}
-
-int rfd_detect_select_batch(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_selection_config *cfg, int is_enroll,
-                            float *out_box, float *out_kps, int32_t *found)
-{
-    RFD_CHECK_ARG(c && out_box && out_kps && found, "null argument");
-    RFD_TRY(check_images(c, imgs, n));
-    rfd_dets dev = own_slabs(c);
-    RFD_TRY(detect_impl(c, imgs, n, &dev, /*outputs stay on the device*/ true, /*async*/ 1, /*frames on host*/ false));
-    std::vector<int> hh(n), ww(n);
-    for (int i = 0; i < n; ++i) { hh[i] = imgs[i].height; ww[i] = imgs[i].width; }
-    return select_impl(c, dev.boxes, dev.landmarks, dev.count, hh.data(), ww.data(), n, cfg, is_enroll, out_box, out_kps, found);
-}
-
-void rfd_alignment_config_default(rfd_alignment_config *cfg)
-{
-    if (!cfg) return;
-    memset(cfg, 0, sizeof *cfg);
-    cfg->out_w = 112; cfg->out_h = 112; // config.rs:46
-    static const float tmpl[10] = {38.2946f, 51.6963f, 73.5318f, 51.5014f, 56.0252f, 71.7366f, 41.5493f, 92.3655f, 70.7299f, 92.2041f}; // :47-52
-    memcpy(cfg->standard_landmarks, tmpl, sizeof tmpl);
-}
-
-// the caller's alignment config or, for null, the reference's (into *def); refused if its output size is out of range
-static int resolve_align_cfg(const rfd_alignment_config **cfg, rfd_alignment_config *def)
-{
-    if (!*cfg) { rfd_alignment_config_default(def); *cfg = def; }
-    if ((*cfg)->out_w < 1 || (*cfg)->out_h < 1 || (*cfg)->out_w > 4096 || (*cfg)->out_h > 4096) {
-        set_error("alignment output size %dx%d out of range", (*cfg)->out_w, (*cfg)->out_h);
-        return RFD_ERR_INVALID_ARG;
-    }
-    return RFD_OK;
-}
-
-// what the set-up kernel of align_impl needs: the descriptors in c->imgs, the selection, the template, its two outputs
-static int align_setup_params(rfd_ctx *c, int n, const float *d_box, const float *d_kps, const int *d_found,
-                              const rfd_alignment_config *cfg, AlignParams *ap)
-{
-    RFD_TRY(c->align_faces.reserve((size_t)n * sizeof(AlignFace)));
-    RFD_TRY(c->align_status.reserve((size_t)n * sizeof(int)));
-    memset(ap, 0, sizeof *ap);
-    ap->imgs = (const PreImage *)c->imgs.p;
-    ap->box = d_box; ap->kps = d_kps; ap->found = d_found;
-    memcpy(ap->std_lmk, cfg->standard_landmarks, sizeof ap->std_lmk);
-    ap->out_w = cfg->out_w; ap->out_h = cfg->out_h; ap->n = n;
-    ap->faces = (AlignFace *)c->align_faces.p;
-    ap->status = (int *)c->align_status.p;
-    return RFD_OK;
-}
-
-// alignment of the frames whose descriptors sit in c->imgs (the last staged batch); selection results are device
-// arrays; crops and status are copied to the host pointers
-static int align_impl(rfd_ctx *c, int n, const float *d_box, const float *d_kps, const int *d_found,
-                      const rfd_alignment_config *cfg, uint8_t *out_crops, int32_t *status)
-{
-    rfd_alignment_config def;
-    RFD_TRY(resolve_align_cfg(&cfg, &def));
-    const size_t crop = (size_t)cfg->out_w * cfg->out_h * 3;
-    RFD_TRY(c->align_out.reserve((size_t)n * crop));
-    AlignParams ap;
-    RFD_TRY(align_setup_params(c, n, d_box, d_kps, d_found, cfg, &ap));
-    ap.out = (uint8_t *)c->align_out.p;
-    RFD_TRY(launch_face_align(ap, c->stream));
-    RFD_HIP(hipMemcpyAsync(out_crops, ap.out, (size_t)n * crop, hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipMemcpyAsync(status, ap.status, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipStreamSynchronize(c->stream));
-    return check_nms_flag(c);
-}
-
-int rfd_align_faces(rfd_ctx *c, const rfd_image *imgs, int n, const float *boxes, const float *kps, const int32_t *found,
-                    const rfd_alignment_config *cfg, uint8_t *out_crops, int32_t *status)
-{
-    RFD_CHECK_ARG(c && boxes && kps && found && out_crops && status, "null argument");
-    RFD_TRY(check_images(c, imgs, n));
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    RFD_TRY(stage_frames(c, imgs, n, false));
-    RFD_TRY(sel_upload(c, n, boxes, kps, found));
-    const SelView v = sel_view(c, n);
-    return align_impl(c, n, v.box, v.kps, v.found, cfg, out_crops, status);
-}
-
-// the set-up records of n faces on frames of which only the sizes exist: descriptors without pixels, then the launch of align_impl
-int rfd_debug_align_setup(rfd_ctx *c, int n, const float *boxes, const float *kps, const int32_t *found, const int32_t *img_w,
-                          const int32_t *img_h, const rfd_alignment_config *cfg, int32_t *mode, double *M, int32_t *roi,
-                          double *scale, int32_t *area_fast)
-{
-    RFD_CHECK_ARG(c && boxes && kps && found && img_w && img_h && mode && M && roi && scale && area_fast, "null argument");
-    RFD_TRY(check_batch(c, n, "batch of", " faces"));
-    rfd_alignment_config def;
-    RFD_TRY(resolve_align_cfg(&cfg, &def));
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    PreImage *pis;
-    float *pin_scales;
-    RFD_TRY(acquire_frame_slot(c, &pis, &pin_scales));
-    memset(pis, 0, (size_t)n * sizeof(PreImage));
-    for (int i = 0; i < n; ++i) { pis[i].w = img_w[i]; pis[i].h = img_h[i]; }
-    RFD_HIP(hipMemcpyAsync(c->imgs.p, pis, n * sizeof(PreImage), hipMemcpyHostToDevice, c->stream));
-    RFD_TRY(c->frame_ring.record(c->stream));
-    RFD_TRY(sel_upload(c, n, boxes, kps, found));
-    const SelView v = sel_view(c, n);
-    AlignParams ap;
-    RFD_TRY(align_setup_params(c, n, v.box, v.kps, v.found, cfg, &ap));
-    RFD_TRY(launch_face_align_setup(ap, c->stream));
-    std::vector<AlignFace> faces(n);
-    RFD_HIP(hipMemcpyAsync(faces.data(), ap.faces, (size_t)n * sizeof(AlignFace), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < n; ++i) {
-        const AlignFace &f = faces[i];
-        mode[i] = f.mode;
-        for (int k = 0; k < 6; ++k) M[6 * i + k] = f.M[k];
-        roi[4 * i] = f.x0; roi[4 * i + 1] = f.y0; roi[4 * i + 2] = f.rw; roi[4 * i + 3] = f.rh;
-        scale[2 * i] = f.scale_x; scale[2 * i + 1] = f.scale_y;
-        area_fast[i] = f.area_fast;
-    }
-    return check_nms_flag(c);
-}
-
-int rfd_detect_select_align_batch(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_selection_config *sel_cfg, int is_enroll,
-                                  const rfd_alignment_config *align_cfg, float *out_box, float *out_kps, int32_t *found,
-                                  uint8_t *out_crops, int32_t *status)
-{
-    RFD_CHECK_ARG(c && out_crops && status, "null argument");
-    // the staged frames and their descriptors (c->staging / c->imgs) stay valid until the next call on this context
-    RFD_TRY(rfd_detect_select_batch(c, imgs, n, sel_cfg, is_enroll, out_box, out_kps, found));
-    const SelView v = sel_view(c, n);
-    return align_impl(c, n, v.box, v.kps, v.found, align_cfg, out_crops, status);
-}
-
-// ---- model inputs of the quality and ID stages (face_quality.rs:43-44,56-101, face_extraction.rs:38-77) ----
-void rfd_face_tensor_config_quality(rfd_face_tensor_config *cfg)
-{
-    if (!cfg) return;
-    memset(cfg, 0, sizeof *cfg);
-    cfg->out_w = 112; cfg->out_h = 112;
-    static const float mean[3] = {123.675f, 116.28f, 103.53f};          // face_quality.rs:43
-    static const float scale[3] = {0.01712475f, 0.017507f, 0.01742919f}; // :44 (named `std`, applied as a factor :93)
-    memcpy(cfg->mean, mean, sizeof mean);
-    memcpy(cfg->scale, scale, sizeof scale);
-}
-
-void rfd_face_tensor_config_extraction(rfd_face_tensor_config *cfg)
-{
-    if (!cfg) return;
-    memset(cfg, 0, sizeof *cfg);
-    cfg->out_w = 112; cfg->out_h = 112;
-    for (int i = 0; i < 3; ++i) { cfg->mean[i] = 127.5f; cfg->scale[i] = 0.0078125f; } // face_extraction.rs:38-39
-}
-
-static int check_face_tensor_args(const rfd_face_tensor_config *cfgs, int k, float *const *tensors, int k_min)
-{
-    if (k > RFD_MAX_FACE_TENSORS) { set_error("%d tensor configs exceed RFD_MAX_FACE_TENSORS (%d)", k, RFD_MAX_FACE_TENSORS); return RFD_ERR_CAPACITY; }
-    RFD_CHECK_ARG(k >= k_min, "too few tensor configs");
-    RFD_CHECK_ARG(k == 0 || (cfgs && tensors), "tensor configs / tensor pointers are null");
-    for (int j = 0; j < k; ++j) {
-        if (cfgs[j].out_w < 1 || cfgs[j].out_h < 1 || cfgs[j].out_w > 4096 || cfgs[j].out_h > 4096) {
-            set_error("tensor config %d: size %dx%d out of range", j, cfgs[j].out_w, cfgs[j].out_h);
-            return RFD_ERR_INVALID_ARG;
-        }
-        if (!tensors[j]) { set_error("tensor pointer %d is null", j); return RFD_ERR_INVALID_ARG; }
-    }
-    return RFD_OK;
-}
-
-// cv::resize's scale bookkeeping for a crop_w x crop_h crop (as letterbox() does for a frame)
-static void fill_face_tensor_cfg(FaceTensorCfg &d, const rfd_face_tensor_config &s, float *out, int crop_w, int crop_h)
-{
-    d.out = out; d.out_w = s.out_w; d.out_h = s.out_h;
-    memcpy(d.mean, s.mean, sizeof d.mean);
-    memcpy(d.scale, s.scale, sizeof d.scale);
-    d.same = s.out_w == crop_w && s.out_h == crop_h;
-    const double inv_x = (double)s.out_w / crop_w, inv_y = (double)s.out_h / crop_h;
-    d.scale_x = 1.0 / inv_x;
-    d.scale_y = 1.0 / inv_y;
-    const int ix = (int)lrint(d.scale_x), iy = (int)lrint(d.scale_y);
-    d.area_fast = fabs(d.scale_x - ix) < 2.220446049250313e-16 && fabs(d.scale_y - iy) < 2.220446049250313e-16 && ix == 2 && iy == 2;
-}
-
-int rfd_face_tensors(rfd_ctx *c, const uint8_t *crops, int n, int crop_w, int crop_h, const rfd_face_tensor_config *cfgs, int k,
-                     float *const *tensors)
-{
-    RFD_CHECK_ARG(c && crops, "null argument");
-    RFD_TRY(check_face_tensor_args(cfgs, k, tensors, 1));
-    RFD_CHECK_ARG(crop_w >= 1 && crop_h >= 1 && crop_w <= 4096 && crop_h <= 4096, "crop size out of range");
-    RFD_TRY(check_batch(c, n, "batch"));
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    const size_t crop = (size_t)crop_w * crop_h * 3;
-    RFD_TRY(c->face_in.reserve((size_t)n * crop));
-    RFD_HIP(hipMemcpyAsync(c->face_in.p, crops, (size_t)n * crop, hipMemcpyHostToDevice, c->stream));
-    FaceTensorParams tp;
-    memset(&tp, 0, sizeof tp);
-    tp.crops = (const uint8_t *)c->face_in.p;
-    tp.n = n; tp.crop_w = crop_w; tp.crop_h = crop_h; tp.k = k;
-    for (int j = 0; j < k; ++j) {
-        RFD_TRY(c->face_tensors[j].reserve((size_t)n * 3 * cfgs[j].out_w * cfgs[j].out_h * sizeof(float)));
-        fill_face_tensor_cfg(tp.cfg[j], cfgs[j], (float *)c->face_tensors[j].p, crop_w, crop_h);
-    }
-    RFD_TRY(launch_face_tensors(tp, c->stream));
-    for (int j = 0; j < k; ++j)
-        RFD_HIP(hipMemcpyAsync(tensors[j], tp.cfg[j].out, (size_t)n * 3 * cfgs[j].out_w * cfgs[j].out_h * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipStreamSynchronize(c->stream));
-    return RFD_OK;
-}
-
-// Alignment of the frames whose descriptors sit in c->imgs plus the k model inputs of every face, into DEVICE arrays; enqueued
-// only.  Configs of the crop's own size are written by the warp itself, from the registers that hold the pixel; the others are
-// resized from the crop in HBM (d_crops, or the context's own buffer when the caller wants no crop).
-static int align_tensors_enqueue(rfd_ctx *c, int n, const float *d_box, const float *d_kps, const int *d_found,
-                                 const rfd_alignment_config *cfg, const rfd_face_tensor_config *cfgs, int k,
-                                 float *const *d_tensors, uint8_t *d_crops, int32_t *d_status)
-{
-    rfd_alignment_config def;
-    RFD_TRY(resolve_align_cfg(&cfg, &def));
-    FaceTensorParams fused, rest;
-    memset(&fused, 0, sizeof fused);
-    memset(&rest, 0, sizeof rest);
-    for (int j = 0; j < k; ++j) {
-        FaceTensorParams &t = (cfgs[j].out_w == cfg->out_w && cfgs[j].out_h == cfg->out_h) ? fused : rest;
-        fill_face_tensor_cfg(t.cfg[t.k++], cfgs[j], d_tensors[j], cfg->out_w, cfg->out_h);
-    }
-    if (!d_crops && rest.k) {
-        RFD_TRY(c->align_out.reserve((size_t)n * cfg->out_w * cfg->out_h * 3));
-        d_crops = (uint8_t *)c->align_out.p;
-    }
-    RFD_TRY(c->align_faces.reserve((size_t)n * sizeof(AlignFace)));
-    AlignParams ap;
-    memset(&ap, 0, sizeof ap);
-    ap.imgs = (const PreImage *)c->imgs.p;
-    ap.box = d_box; ap.kps = d_kps; ap.found = d_found;
-    memcpy(ap.std_lmk, cfg->standard_landmarks, sizeof ap.std_lmk);
-    ap.out_w = cfg->out_w; ap.out_h = cfg->out_h; ap.n = n;
-    ap.faces = (AlignFace *)c->align_faces.p;
-    ap.status = d_status;
-    ap.out = d_crops;
-    fused.n = rest.n = n;
-    fused.crop_w = rest.crop_w = cfg->out_w;
-    fused.crop_h = rest.crop_h = cfg->out_h;
-    rest.crops = d_crops;
-    rest.status = d_status;
-    RFD_TRY(launch_face_align_tensors(ap, fused, c->stream));
-    return launch_face_tensors(rest, c->stream);
-}
-
-// align_tensors_enqueue on the selection results in c->sel_out, into the context's own buffers, then copied to the host pointers
-static int align_tensors_to_host(rfd_ctx *c, int n, const rfd_alignment_config *align_cfg, uint8_t *out_crops, int32_t *status,
-                                 const rfd_face_tensor_config *cfgs, int k, float *const *tensors)
-{
-    const size_t crop = (size_t)align_cfg->out_w * align_cfg->out_h * 3;
-    RFD_TRY(c->align_status.reserve((size_t)n * sizeof(int)));
-    if (out_crops) RFD_TRY(c->align_out.reserve((size_t)n * crop));
-    float *d_tensors[kMaxFaceTensors] = {};
-    for (int j = 0; j < k; ++j) {
-        RFD_TRY(c->face_tensors[j].reserve((size_t)n * 3 * cfgs[j].out_w * cfgs[j].out_h * sizeof(float)));
-        d_tensors[j] = (float *)c->face_tensors[j].p;
-    }
-    const SelView v = sel_view(c, n);
-    RFD_TRY(align_tensors_enqueue(c, n, v.box, v.kps, v.found, align_cfg, cfgs, k, d_tensors,
-                                  out_crops ? (uint8_t *)c->align_out.p : nullptr, (int32_t *)c->align_status.p));
-    if (out_crops) RFD_HIP(hipMemcpyAsync(out_crops, c->align_out.p, (size_t)n * crop, hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipMemcpyAsync(status, c->align_status.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    for (int j = 0; j < k; ++j)
-        RFD_HIP(hipMemcpyAsync(tensors[j], d_tensors[j], (size_t)n * 3 * cfgs[j].out_w * cfgs[j].out_h * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipStreamSynchronize(c->stream));
-    return check_nms_flag(c);
-}
-
-int rfd_align_faces_tensors(rfd_ctx *c, const rfd_image *imgs, int n, const float *boxes, const float *kps, const int32_t *found,
-                            const rfd_alignment_config *cfg, uint8_t *out_crops, int32_t *status,
-                            const rfd_face_tensor_config *cfgs, int k, float *const *tensors)
-{
-    RFD_CHECK_ARG(c && boxes && kps && found && status, "null argument");
-    RFD_TRY(check_face_tensor_args(cfgs, k, tensors, 0));
-    rfd_alignment_config def;
-    RFD_TRY(resolve_align_cfg(&cfg, &def));
-    RFD_TRY(check_images(c, imgs, n));
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    RFD_TRY(stage_frames(c, imgs, n, false));
-    RFD_TRY(sel_upload(c, n, boxes, kps, found));
-    return align_tensors_to_host(c, n, cfg, out_crops, status, cfgs, k, tensors);
-}
-
-int rfd_detect_select_align_tensors_batch(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_selection_config *sel_cfg,
-                                          int is_enroll, const rfd_alignment_config *align_cfg, float *out_box, float *out_kps,
-                                          int32_t *found, uint8_t *out_crops, int32_t *status,
-                                          const rfd_face_tensor_config *cfgs, int k, float *const *tensors)
-{
-    RFD_CHECK_ARG(c && status, "null argument");
-    RFD_TRY(check_face_tensor_args(cfgs, k, tensors, 0));
-    rfd_alignment_config def;
-    RFD_TRY(resolve_align_cfg(&align_cfg, &def));
-    RFD_TRY(rfd_detect_select_batch(c, imgs, n, sel_cfg, is_enroll, out_box, out_kps, found));
-    return align_tensors_to_host(c, n, align_cfg, out_crops, status, cfgs, k, tensors);
-}
-
-int rfd_detect_faces_device(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_selection_config *sel_cfg, int is_enroll,
-                            const rfd_alignment_config *align_cfg, const rfd_face_tensor_config *cfgs, int k, rfd_faces *out,
-                            int async)
-{
-    RFD_CHECK_ARG(c && out && out->box && out->kps && out->found && out->status, "null argument");
-    RFD_TRY(check_face_tensor_args(cfgs, k, out->tensors, 0));
-    RFD_TRY(check_images(c, imgs, n));
-    rfd_dets dev = own_slabs(c);
-    RFD_TRY(detect_impl(c, imgs, n, &dev, /*outputs stay on the device*/ true, /*async*/ 1, /*frames on device*/ true));
-    std::vector<int> hh(n), ww(n);
-    for (int i = 0; i < n; ++i) { hh[i] = imgs[i].height; ww[i] = imgs[i].width; }
-    RFD_TRY(select_enqueue(c, dev.boxes, dev.landmarks, dev.count, hh.data(), ww.data(), n, sel_cfg, is_enroll, out->box, out->kps,
-                           out->found));
-    RFD_TRY(align_tensors_enqueue(c, n, out->box, out->kps, out->found, align_cfg, cfgs, k, out->tensors, out->crops, out->status));
-    if (async) return RFD_OK;
-    RFD_HIP(hipStreamSynchronize(c->stream));
-    return check_nms_flag(c);
-}
-
-// ---- every detected face of a frame: the packed face list (rfd.h) ----
-void rfd_face_list_config_default(rfd_face_list_config *cfg)
-{
-    if (!cfg) return;
-    memset(cfg, 0, sizeof *cfg);
-    cfg->max_faces = RFD_GALLERY_MAX_K; // one gallery search pass (32 queries) per frame
-    cfg->min_face_px = 0.0f;
-    cfg->min_score = 0.0f;
-}
-
-// the caller's list config or, for null, the default (into *def); every refusal names its field
-static int resolve_list_cfg(const rfd_face_list_config **cfg, rfd_face_list_config *def, int cap)
-{
-    if (!*cfg) { rfd_face_list_config_default(def); *cfg = def; }
-    if ((*cfg)->max_faces < 1) { set_error("invalid argument: max_faces %d < 1", (*cfg)->max_faces); return RFD_ERR_INVALID_ARG; }
-    if (!std::isfinite((*cfg)->min_face_px) || (*cfg)->min_face_px < 0.0f) {
-        set_error("invalid argument: min_face_px %g is negative or not finite", (double)(*cfg)->min_face_px);
-        return RFD_ERR_INVALID_ARG;
-    }
-    if (!std::isfinite((*cfg)->min_score)) { set_error("invalid argument: min_score %g is not finite", (double)(*cfg)->min_score); return RFD_ERR_INVALID_ARG; }
-    if (cap < 1) { set_error("invalid argument: cap %d < 1", cap); return RFD_ERR_INVALID_ARG; }
-    return RFD_OK;
-}
-
-static int check_face_list_out(const rfd_face_list *out)
-{
-    RFD_CHECK_ARG(out && out->total && out->first && out->frame && out->row && out->box && out->kps && out->status,
-                  "face list output pointers are null");
-    return RFD_OK;
-}
-
-// the faces a call can list at most: what the set-up and warp launches are sized by (the true count stays in HBM)
-static int face_list_bound(const rfd_ctx *c, int n, const rfd_face_list_config *cfg, int cap)
-{
-    return (int)std::min<long long>(cap, (long long)n * std::min(cfg->max_faces, c->cfg.max_det));
-}
-
-// The list of the detections in the device slabs `dets` of the n frames whose descriptors sit in c->imgs, then set-up, warp
-// and tensors over it, all into the DEVICE arrays of `out`; enqueued only.  align_tensors_enqueue with a frame map: the same
-// kernels, sized by the host-known bound, every face past min(total, cap) leaving its rows alone.
-static int face_list_enqueue(rfd_ctx *c, int n, const rfd_dets &dets, const rfd_face_list_config *lc,
-                             const rfd_alignment_config *cfg, const rfd_face_tensor_config *cfgs, int k, int cap,
-                             const rfd_face_list &out)
-{
-    FaceListParams lp;
-    memset(&lp, 0, sizeof lp);
-    lp.boxes = dets.boxes; lp.lmk = dets.landmarks; lp.count = dets.count;
-    lp.n = n; lp.max_det = c->cfg.max_det; lp.max_faces = lc->max_faces; lp.cap = cap;
-    lp.min_face_px = lc->min_face_px; lp.min_score = lc->min_score;
-    lp.total = out.total; lp.first = out.first; lp.frame = out.frame; lp.row = out.row; lp.box = out.box; lp.kps = out.kps;
-    RFD_TRY(launch_face_list(lp, c->stream));
-    const int bound = face_list_bound(c, n, lc, cap);
-    FaceTensorParams fused, rest;
-    memset(&fused, 0, sizeof fused);
-    memset(&rest, 0, sizeof rest);
-    for (int j = 0; j < k; ++j) {
-        FaceTensorParams &t = (cfgs[j].out_w == cfg->out_w && cfgs[j].out_h == cfg->out_h) ? fused : rest;
-        fill_face_tensor_cfg(t.cfg[t.k++], cfgs[j], out.tensors[j], cfg->out_w, cfg->out_h);
-    }
-    uint8_t *d_crops = out.crops;
-    if (!d_crops && rest.k) {
-        RFD_TRY(c->align_out.reserve((size_t)bound * cfg->out_w * cfg->out_h * 3));
-        d_crops = (uint8_t *)c->align_out.p;
-    }
-    RFD_TRY(c->align_faces.reserve((size_t)bound * sizeof(AlignFace)));
-    AlignParams ap;
-    memset(&ap, 0, sizeof ap);
-    ap.imgs = (const PreImage *)c->imgs.p;
-    ap.box = out.box; ap.kps = out.kps; // found null: a listed face has both
-    memcpy(ap.std_lmk, cfg->standard_landmarks, sizeof ap.std_lmk);
-    ap.out_w = cfg->out_w; ap.out_h = cfg->out_h; ap.n = bound;
-    ap.faces = (AlignFace *)c->align_faces.p;
-    ap.status = out.status;
-    ap.out = d_crops;
-    ap.frame = out.frame; ap.total = out.total; ap.cap = cap;
-    fused.n = rest.n = bound;
-    fused.crop_w = rest.crop_w = cfg->out_w;
-    fused.crop_h = rest.crop_h = cfg->out_h;
-    rest.crops = d_crops;
-    rest.status = out.status;
-    rest.total = out.total; rest.cap = cap;
-    RFD_TRY(launch_face_align_tensors(ap, fused, c->stream));
-    return launch_face_tensors(rest, c->stream);
-}
-
-// c->list_out holds the list of a host-output call: total [1] | first [n + 1] | frame, row, status [bound] each |
-// box [bound][5] | kps [bound][10]
-static int face_list_own(rfd_ctx *c, int n, int bound, const rfd_alignment_config *cfg, const rfd_face_tensor_config *cfgs, int k,
-                         bool want_crops, rfd_face_list *v)
-{
-    RFD_TRY(c->list_out.reserve(((size_t)n + 2 + (size_t)bound * 18) * sizeof(int)));
-    RFD_TRY(c->h_list.alloc((size_t)c->cfg.max_batch_size + 2));
-    memset(v, 0, sizeof *v);
-    int32_t *o = (int32_t *)c->list_out.p;
-    v->total = o; v->first = o + 1;
-    v->frame = o + n + 2; v->row = v->frame + bound; v->status = v->row + bound;
-    v->box = (float *)(v->status + bound); v->kps = v->box + (size_t)bound * 5;
-    if (want_crops) {
-        RFD_TRY(c->align_out.reserve((size_t)bound * cfg->out_w * cfg->out_h * 3));
-        v->crops = (uint8_t *)c->align_out.p;
-    }
-    for (int j = 0; j < k; ++j) {
-        RFD_TRY(c->face_tensors[j].reserve((size_t)bound * 3 * cfgs[j].out_w * cfgs[j].out_h * sizeof(float)));
-        v->tensors[j] = (float *)c->face_tensors[j].p;
-    }
-    return RFD_OK;
-}
-
-// face_list_enqueue into the context's own buffers, then to the host pointers of `out`: the stream is waited for once, for
-// total and first, and only the min(T, cap) listed rows are fetched after it -- the caller's rows past them stay as they are.
-static int face_list_to_host(rfd_ctx *c, int n, const rfd_dets &dets, const rfd_face_list_config *lc,
-                             const rfd_alignment_config *cfg, const rfd_face_tensor_config *cfgs, int k, int cap,
-                             rfd_face_list *out)
-{
-    rfd_face_list v;
-    RFD_TRY(face_list_own(c, n, face_list_bound(c, n, lc, cap), cfg, cfgs, k, out->crops != nullptr, &v));
-    RFD_TRY(face_list_enqueue(c, n, dets, lc, cfg, cfgs, k, cap, v));
-    RFD_HIP(hipMemcpyAsync(c->h_list, v.total, ((size_t)n + 2) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipStreamSynchronize(c->stream));
-    RFD_TRY(check_nms_flag(c));
-    out->total[0] = c->h_list[0];
-    memcpy(out->first, c->h_list + 1, ((size_t)n + 1) * sizeof(int));
-    const size_t rows = (size_t)std::min(c->h_list[0], cap);
-    if (!rows) return RFD_OK;
-    RFD_HIP(hipMemcpy(out->frame, v.frame, rows * sizeof(int), hipMemcpyDeviceToHost));
-    RFD_HIP(hipMemcpy(out->row, v.row, rows * sizeof(int), hipMemcpyDeviceToHost));
-    RFD_HIP(hipMemcpy(out->status, v.status, rows * sizeof(int), hipMemcpyDeviceToHost));
-    RFD_HIP(hipMemcpy(out->box, v.box, rows * 5 * sizeof(float), hipMemcpyDeviceToHost));
-    RFD_HIP(hipMemcpy(out->kps, v.kps, rows * 10 * sizeof(float), hipMemcpyDeviceToHost));
-    if (out->crops) RFD_HIP(hipMemcpy(out->crops, v.crops, rows * cfg->out_w * cfg->out_h * 3, hipMemcpyDeviceToHost));
-    for (int j = 0; j < k; ++j)
-        RFD_HIP(hipMemcpy(out->tensors[j], v.tensors[j], rows * 3 * cfgs[j].out_w * cfgs[j].out_h * sizeof(float), hipMemcpyDeviceToHost));
-    return RFD_OK;
-}
-
-// the argument checks the three entries share
-static int check_face_list_call(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_face_list_config **lc, rfd_face_list_config *ldef,
-                                const rfd_alignment_config **ac, rfd_alignment_config *adef, const rfd_face_tensor_config *cfgs,
-                                int k, int cap, const rfd_face_list *out)
-{
-    RFD_CHECK_ARG(c != nullptr, "ctx is null");
-    RFD_TRY(check_face_list_out(out));
-    RFD_TRY(check_face_tensor_args(cfgs, k, out->tensors, 0));
-    RFD_TRY(resolve_list_cfg(lc, ldef, cap));
-    RFD_TRY(resolve_align_cfg(ac, adef));
-    return check_images(c, imgs, n);
-}
-
-int rfd_align_detections(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_dets *dets, const rfd_face_list_config *list_cfg,
-                         const rfd_alignment_config *align_cfg, const rfd_face_tensor_config *cfgs, int k, int cap,
-                         rfd_face_list *out)
-{
-    rfd_face_list_config ldef;
-    rfd_alignment_config adef;
-    RFD_TRY(check_face_list_call(c, imgs, n, &list_cfg, &ldef, &align_cfg, &adef, cfgs, k, cap, out));
-    RFD_CHECK_ARG(dets && dets->boxes && dets->landmarks && dets->count, "detections are null");
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    RFD_TRY(stage_frames(c, imgs, n, false));
-    rfd_dets dev = own_slabs(c);
-    dev.total = nullptr; // the list does not read it
-    RFD_TRY(copy_slabs(c, dev, *dets, n, hipMemcpyHostToDevice));
-    return face_list_to_host(c, n, dev, list_cfg, align_cfg, cfgs, k, cap, out);
-}
-
-int rfd_detect_align_all_batch(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_face_list_config *list_cfg,
-                               const rfd_alignment_config *align_cfg, const rfd_face_tensor_config *cfgs, int k, int cap,
-                               rfd_face_list *out)
-{
-    rfd_face_list_config ldef;
-    rfd_alignment_config adef;
-    RFD_TRY(check_face_list_call(c, imgs, n, &list_cfg, &ldef, &align_cfg, &adef, cfgs, k, cap, out));
-    rfd_dets dev = own_slabs(c);
-    // the staged frames and their descriptors (c->staging / c->imgs) stay valid until the next call on this context
-    RFD_TRY(detect_impl(c, imgs, n, &dev, /*outputs stay on the device*/ true, /*async*/ 1, /*frames on host*/ false));
-    return face_list_to_host(c, n, dev, list_cfg, align_cfg, cfgs, k, cap, out);
-}
-
-int rfd_detect_all_faces_device(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_face_list_config *list_cfg,
-                                const rfd_alignment_config *align_cfg, const rfd_face_tensor_config *cfgs, int k, int cap,
-                                rfd_face_list *out, int async)
-{
-    rfd_face_list_config ldef;
-    rfd_alignment_config adef;
-    RFD_TRY(check_face_list_call(c, imgs, n, &list_cfg, &ldef, &align_cfg, &adef, cfgs, k, cap, out));
-    rfd_dets dev = own_slabs(c);
-    RFD_TRY(detect_impl(c, imgs, n, &dev, /*outputs stay on the device*/ true, /*async*/ 1, /*frames on device*/ true));
-    RFD_TRY(face_list_enqueue(c, n, dev, list_cfg, align_cfg, cfgs, k, cap, *out));
-    if (async) return RFD_OK;
-    RFD_HIP(hipStreamSynchronize(c->stream));
-    return check_nms_flag(c);
-}
-
-// The device-resident form of rfd_align_detections: the frames' descriptors, then the list over the caller's device slabs.
-int rfd_align_detections_device(rfd_ctx *c, const rfd_image *imgs, int n, const rfd_dets *dets, const rfd_face_list_config *list_cfg,
-                                const rfd_alignment_config *align_cfg, const rfd_face_tensor_config *cfgs, int k, int cap,
-                                rfd_face_list *out, int async)
-{
-    rfd_face_list_config ldef;
-    rfd_alignment_config adef;
-    RFD_TRY(check_face_list_call(c, imgs, n, &list_cfg, &ldef, &align_cfg, &adef, cfgs, k, cap, out));
-    RFD_CHECK_ARG(dets && dets->boxes && dets->landmarks && dets->count, "detections are null");
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    RFD_TRY(stage_frames(c, imgs, n, true));
-    RFD_TRY(face_list_enqueue(c, n, *dets, list_cfg, align_cfg, cfgs, k, cap, *out));
-    if (async) return RFD_OK;
-    RFD_HIP(hipStreamSynchronize(c->stream));
-    return check_nms_flag(c);
-}
-
-// ---- after the two models: quality decision rule (face_quality.rs:159-168), embedding normalisation (utils.rs:148-154) ----
-static int check_quality_args(const rfd_ctx *c, const float *logits, int n, int classes, const float *score, const int32_t *klass)
-{
-    RFD_CHECK_ARG(c && logits && score && klass, "null argument");
-    RFD_CHECK_ARG(n >= 1 && classes >= 1, "n < 1 or classes < 1");
-    return RFD_OK;
-}
-
-int rfd_quality_decide_device(rfd_ctx *c, const float *logits, int n, int classes, float threshold, float *score, int32_t *klass)
-{
-    RFD_TRY(check_quality_args(c, logits, n, classes, score, klass));
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    return launch_quality_decide(logits, n, classes, threshold, score, klass, c->stream);
-}
-
-int rfd_quality_decide(rfd_ctx *c, const float *logits, int n, int classes, float threshold, float *score, int32_t *klass)
-{
-    RFD_TRY(check_quality_args(c, logits, n, classes, score, klass));
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    const size_t in_bytes = (size_t)n * classes * sizeof(float);
-    RFD_TRY(c->face_io[0].reserve(in_bytes));
-    RFD_TRY(c->face_io[1].reserve((size_t)n * (sizeof(float) + sizeof(int32_t))));
-    float *d_score = (float *)c->face_io[1].p;
-    int32_t *d_klass = (int32_t *)(d_score + n);
-    RFD_HIP(hipMemcpyAsync(c->face_io[0].p, logits, in_bytes, hipMemcpyHostToDevice, c->stream));
-    RFD_TRY(rfd_quality_decide_device(c, (const float *)c->face_io[0].p, n, classes, threshold, d_score, d_klass));
-    RFD_HIP(hipMemcpyAsync(score, d_score, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipMemcpyAsync(klass, d_klass, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < n; ++i)
-        if (klass[i] < 0) { // the reference panics here (partial_cmp(..).unwrap(), face_quality.rs:160)
-            set_error("invalid argument: the logits of frame %d hold a NaN", i);
-            return RFD_ERR_INVALID_ARG;
-        }
-    return RFD_OK;
-}
-
-static int check_normalize_args(const rfd_ctx *c, const float *emb, int n, int dim, const float *out)
-{
-    RFD_CHECK_ARG(c && emb && out, "null argument");
-    RFD_CHECK_ARG(n >= 1 && dim >= 1, "n < 1 or dim < 1");
-    return RFD_OK;
-}
-
-int rfd_normalize_embeddings_device(rfd_ctx *c, const float *emb, int n, int dim, float *out)
-{
-    RFD_TRY(check_normalize_args(c, emb, n, dim, out));
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    return launch_l2_normalize(emb, n, dim, out, c->stream);
-}
-
-int rfd_normalize_embeddings(rfd_ctx *c, const float *emb, int n, int dim, float *out)
-{
-    RFD_TRY(check_normalize_args(c, emb, n, dim, out));
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    const size_t bytes = (size_t)n * dim * sizeof(float);
-    RFD_TRY(c->face_io[0].reserve(bytes));
-    RFD_TRY(c->face_io[1].reserve(bytes));
-    RFD_HIP(hipMemcpyAsync(c->face_io[0].p, emb, bytes, hipMemcpyHostToDevice, c->stream));
-    RFD_TRY(rfd_normalize_embeddings_device(c, (const float *)c->face_io[0].p, n, dim, (float *)c->face_io[1].p));
-    RFD_HIP(hipMemcpyAsync(out, c->face_io[1].p, bytes, hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipStreamSynchronize(c->stream));
-    return RFD_OK;
-}
-
-// ---- liveness (face_antispoofing.rs): the inputs of the miniFAS models from the frame and the selected box, and the rule
-//      on their outputs.  The models themselves are remote, like the quality and the ID model. ----
-void rfd_face_tensor_config_quality_assessment(rfd_face_tensor_config *cfg, int w, int h)
-{
-    if (!cfg) return;
-    memset(cfg, 0, sizeof *cfg);
-    cfg->out_w = w; cfg->out_h = h;
-    for (int i = 0; i < 3; ++i) { cfg->mean[i] = 127.5f; cfg->scale[i] = 0.00784313725f; } // face_quality_assessment.rs:76
-}
-
-void rfd_liveness_config_default(rfd_liveness_config *cfg)
-{
-    if (!cfg) return;
-    memset(cfg, 0, sizeof *cfg);
-    // face_antispoofing.rs:448-485, the only place that names the models: miniFAS_4, miniFAS_2_7, miniFAS_2, miniFAS_1
-    static const float scale[4] = {4.0f, 2.7f, 2.0f, 1.0f};
-    static const int32_t size[4] = {80, 80, 256, 128};
-    cfg->k = 4;
-    for (int j = 0; j < 4; ++j) { cfg->scale[j] = scale[j]; cfg->out_w[j] = cfg->out_h[j] = size[j]; }
-}
-
-static int check_liveness_cfg(const rfd_liveness_config *cfg)
-{
-    if (cfg->k > RFD_MAX_FACE_TENSORS) { set_error("liveness config: k = %d exceeds RFD_MAX_FACE_TENSORS (%d)", cfg->k, RFD_MAX_FACE_TENSORS); return RFD_ERR_CAPACITY; }
-    if (cfg->k < 1) { set_error("invalid argument: liveness config: k = %d, at least one model is needed", cfg->k); return RFD_ERR_INVALID_ARG; }
-    for (int j = 0; j < cfg->k; ++j) {
-        if (cfg->out_w[j] < 1 || cfg->out_w[j] > 4096) { set_error("invalid argument: liveness config: out_w[%d] = %d out of range", j, cfg->out_w[j]); return RFD_ERR_INVALID_ARG; }
-        if (cfg->out_h[j] < 1 || cfg->out_h[j] > 4096) { set_error("invalid argument: liveness config: out_h[%d] = %d out of range", j, cfg->out_h[j]); return RFD_ERR_INVALID_ARG; }
-        if (!(cfg->scale[j] > 0.0f && cfg->scale[j] <= 3.402823466e38f)) { set_error("invalid argument: liveness config: scale[%d] = %g is not finite and positive", j, (double)cfg->scale[j]); return RFD_ERR_INVALID_ARG; }
-    }
-    return RFD_OK;
-}
-
-// Both kernels of the tensor call on DEVICE boxes / flags into DEVICE outputs; enqueued only.  The frame descriptors go
-// through a ring of page-locked arrays, so nothing here waits for the stream; host frames are staged first.
-static int liveness_enqueue(rfd_ctx *c, const rfd_image *imgs, int n, bool frames_on_device, const float *d_box, const int *d_found,
-                            const rfd_liveness_config *cfg, float *const *d_tensors, float *d_weights, int32_t *d_rois,
-                            int32_t *d_status)
-{
-    const size_t B = (size_t)c->cfg.max_batch_size;
-    RFD_TRY(c->live_ring.ensure(B * sizeof(LiveImage))); // first call on this context
-    RFD_TRY(c->live_imgs.reserve(B * sizeof(LiveImage)));
-    RFD_TRY(c->live_geo.reserve(B * kMaxFaceTensors * sizeof(LiveRoi)));
-    LiveImage *li;
-    RFD_TRY(c->live_ring.acquire(&li));
-    for (int i = 0; i < n; ++i) { li[i].h = imgs[i].height; li[i].w = imgs[i].width; }
-    RFD_TRY(place_frames(c, imgs, n, frames_on_device, li));
-    RFD_HIP(hipMemcpyAsync(c->live_imgs.p, li, n * sizeof(LiveImage), hipMemcpyHostToDevice, c->stream));
-    RFD_TRY(c->live_ring.record(c->stream));
-    LiveParams p;
-    memset(&p, 0, sizeof p);
-    p.imgs = (const LiveImage *)c->live_imgs.p;
-    p.box = d_box; p.found = d_found;
-    p.n = n; p.k = cfg->k;
-    for (int j = 0; j < cfg->k; ++j) {
-        p.cfg[j].out = d_tensors[j]; p.cfg[j].scale = cfg->scale[j];
-        p.cfg[j].out_w = cfg->out_w[j]; p.cfg[j].out_h = cfg->out_h[j];
-        p.cfg[j].tile0 = p.tiles;
-        p.tiles += ceil_div(cfg->out_w[j] * cfg->out_h[j], 256);
-    }
-    p.geo = (LiveRoi *)c->live_geo.p;
-    p.weights = d_weights; p.rois = d_rois; p.status = d_status;
-    return launch_liveness_tensors(p, c->stream);
-}
-
-static int check_liveness_args(rfd_ctx *c, const rfd_image *imgs, int n, const float *boxes, const int32_t *found,
-                               const rfd_liveness_config **cfg, rfd_liveness_config *def, float *const *tensors,
-                               const float *weights, const int32_t *status)
-{
-    RFD_CHECK_ARG(c && boxes && found && tensors && weights && status, "null argument");
-    if (!*cfg) { rfd_liveness_config_default(def); *cfg = def; }
-    RFD_TRY(check_liveness_cfg(*cfg));
-    for (int j = 0; j < (*cfg)->k; ++j)
-        if (!tensors[j]) { set_error("invalid argument: tensor pointer %d is null", j); return RFD_ERR_INVALID_ARG; }
-    return check_images(c, imgs, n);
-}
-
-int rfd_liveness_tensors_device(rfd_ctx *c, const rfd_image *imgs, int n, const float *boxes, const int32_t *found,
-                                const rfd_liveness_config *cfg, float *const *tensors, float *weights, int32_t *rois,
-                                int32_t *status, int async)
-{
-    rfd_liveness_config def;
-    RFD_TRY(check_liveness_args(c, imgs, n, boxes, found, &cfg, &def, tensors, weights, status));
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    RFD_TRY(liveness_enqueue(c, imgs, n, true, boxes, found, cfg, tensors, weights, rois, status));
-    if (async) return RFD_OK;
-    RFD_HIP(hipStreamSynchronize(c->stream));
-    return check_nms_flag(c);
-}
-
-int rfd_liveness_tensors(rfd_ctx *c, const rfd_image *imgs, int n, const float *boxes, const int32_t *found,
-                         const rfd_liveness_config *cfg, float *const *tensors, float *weights, int32_t *rois, int32_t *status)
-{
-    rfd_liveness_config def;
-    RFD_TRY(check_liveness_args(c, imgs, n, boxes, found, &cfg, &def, tensors, weights, status));
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    const int k = cfg->k;
-    // box [n][5] | found [n] | weights [n][k] | rois [n][k][4] | status [n]: all 4-byte words
-    RFD_TRY(c->live_io.reserve((size_t)n * (5 + 1 + k + 4 * k + 1) * 4));
-    float *d_box = (float *)c->live_io.p;
-    int32_t *d_found = (int32_t *)(d_box + (size_t)n * 5);
-    float *d_weights = (float *)(d_found + n);
-    int32_t *d_rois = (int32_t *)(d_weights + (size_t)n * k), *d_status = d_rois + (size_t)n * k * 4;
-    float *d_tensors[kMaxFaceTensors] = {};
-    size_t bytes[kMaxFaceTensors] = {};
-    for (int j = 0; j < k; ++j) {
-        bytes[j] = (size_t)n * 3 * cfg->out_w[j] * cfg->out_h[j] * sizeof(float);
-        RFD_TRY(c->face_tensors[j].reserve(bytes[j]));
-        d_tensors[j] = (float *)c->face_tensors[j].p;
-    }
-    RFD_HIP(hipMemcpyAsync(d_box, boxes, (size_t)n * 5 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    RFD_HIP(hipMemcpyAsync(d_found, found, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    RFD_TRY(liveness_enqueue(c, imgs, n, false, d_box, d_found, cfg, d_tensors, d_weights, d_rois, d_status));
-    for (int j = 0; j < k; ++j) RFD_HIP(hipMemcpyAsync(tensors[j], d_tensors[j], bytes[j], hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipMemcpyAsync(weights, d_weights, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (rois) RFD_HIP(hipMemcpyAsync(rois, d_rois, (size_t)n * k * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipMemcpyAsync(status, d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipStreamSynchronize(c->stream));
-    return check_nms_flag(c);
-}
-
-static int check_liveness_decide_args(const rfd_ctx *c, const float *const *logits, int k, int n, int classes, const float *weights,
-                                      const float *score, const int32_t *live)
-{
-    RFD_CHECK_ARG(c && logits && weights && score && live, "null argument");
-    RFD_CHECK_ARG(k >= 1 && n >= 1 && classes >= 2, "k < 1, n < 1 or classes < 2");
-    for (int j = 0; j < k; ++j)
-        if (!logits[j]) { set_error("invalid argument: logits pointer %d is null", j); return RFD_ERR_INVALID_ARG; }
-    return RFD_OK;
-}
-
-int rfd_liveness_decide_device(rfd_ctx *c, const float *const *logits, int k, int n, int classes, const float *weights,
-                               float threshold, float *score, int32_t *live)
-{
-    RFD_TRY(check_liveness_decide_args(c, logits, k, n, classes, weights, score, live));
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    if (k > kLiveDecideChunk) RFD_TRY(c->live_acc.reserve((size_t)n * 2 * sizeof(float)));
-    for (int j0 = 0; j0 < k; j0 += kLiveDecideChunk) {
-        LiveLogits l;
-        memset(&l, 0, sizeof l);
-        const int kc = std::min(kLiveDecideChunk, k - j0);
-        for (int q = 0; q < kc; ++q) l.p[q] = logits[j0 + q];
-        RFD_TRY(launch_liveness_decide(l, kc, k, j0, n, classes, weights, threshold, (float *)c->live_acc.p, score, live, c->stream));
-    }
-    return RFD_OK;
-}
-
-int rfd_liveness_decide(rfd_ctx *c, const float *const *logits, int k, int n, int classes, const float *weights, float threshold,
-                        float *score, int32_t *live)
-{
-    RFD_TRY(check_liveness_decide_args(c, logits, k, n, classes, weights, score, live));
-    RFD_HIP(hipSetDevice(c->cfg.device_id));
-    const size_t one = (size_t)n * classes;
-    // logits [k][n][classes] | weights [n][k] | score [n] | live [n]
-    RFD_TRY(c->live_io.reserve(((size_t)k * one + (size_t)n * k + 2 * (size_t)n) * 4));
-    float *d_logits = (float *)c->live_io.p, *d_weights = d_logits + (size_t)k * one, *d_score = d_weights + (size_t)n * k;
-    int32_t *d_live = (int32_t *)(d_score + n);
-    std::vector<const float *> ptrs(k);
-    for (int j = 0; j < k; ++j) {
-        ptrs[j] = d_logits + (size_t)j * one;
-        RFD_HIP(hipMemcpyAsync(d_logits + (size_t)j * one, logits[j], one * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    }
-    RFD_HIP(hipMemcpyAsync(d_weights, weights, (size_t)n * k * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    RFD_TRY(rfd_liveness_decide_device(c, ptrs.data(), k, n, classes, d_weights, threshold, d_score, d_live));
-    RFD_HIP(hipMemcpyAsync(score, d_score, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipMemcpyAsync(live, d_live, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    RFD_HIP(hipStreamSynchronize(c->stream));
     return RFD_OK;
 }
 

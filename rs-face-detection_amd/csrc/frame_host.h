@@ -2,6 +2,7 @@
 // its kernel is told.  frame_host.hip holds the three rfd_*_frames* entries; the kernel is kernels_frame.hip; layouts, checks,
 // descriptors and the work decomposition are frame_plan.h.
 #pragma once
+#include "ctx_access.h" // what the entries need of their context: ctx_stream, ctx_device, ctx_frame_convert
 #include "frame_plan.h"
 #include "host_resources.h"
 
@@ -26,10 +27,5 @@ struct FrameConvert {
     // them follow this call's kernel, so two asynchronous calls back to back are safe.
     DevBuf staging, packed;
 };
-
-// What the entries need of their context, which stays private to detector.hip.
-hipStream_t ctx_stream(const rfd_ctx *c);
-int ctx_device(const rfd_ctx *c);
-FrameConvert &ctx_frame_convert(rfd_ctx *c);
 
 } // namespace rfd

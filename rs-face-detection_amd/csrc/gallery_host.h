@@ -1,17 +1,9 @@
 // gallery_host.h -- rfd_gallery: what a face gallery (include/rfd.h, "gallery") owns on the device, next to the book of its rows
 // (gallery_book.h).  gallery_host.hip holds every rfd_gallery_* entry; the kernels are kernels_gallery.hip.  Host only.
 #pragma once
+#include "ctx_access.h" // what a gallery needs of its context: ctx_stream, ctx_device
 #include "gallery_book.h"
 #include "host_resources.h"
-
-namespace rfd {
-
-// What a gallery needs of its context, which stays private to detector.hip: the stream its commands go on (the caller's after
-// rfd_set_stream, so it is asked for at every call), and the device.
-hipStream_t ctx_stream(const rfd_ctx *c);
-int ctx_device(const rfd_ctx *c);
-
-} // namespace rfd
 
 // The enrolled embeddings of one context in HBM.  Next to the context, which lends it its device and stream; the caller destroys
 // it first.

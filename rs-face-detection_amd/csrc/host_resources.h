@@ -1,4 +1,4 @@
-// host_resources.h -- what the host layer (detector.hip, jpeg_host.h, gallery_host.h) owns, by type: device buffer, page-locked block, event,
+// host_resources.h -- what the host layer (detector.hip and the *_host.h layers next to it) owns, by type: device buffer, page-locked block, event,
 // stream, and the ring of page-locked slots that per-call descriptors travel through.  Host only.  A holder frees in its
 // destructor and cannot be copied; creating what is already held is a no-op, so a "first call" may simply ask again.
 #pragma once

@@ -2,6 +2,7 @@
 // shot_quality_host.hip holds both rfd_shot_quality* entries; the kernel is kernels_shot_quality.hip; the geometry and the
 // argument checks are shot_quality_plan.h.
 #pragma once
+#include "ctx_access.h" // what the entries need of their context: ctx_stream, ctx_device, ctx_shot_quality
 #include "host_resources.h"
 #include "shot_quality_plan.h"
 
@@ -44,10 +45,5 @@ struct ShotQuality {
     // host form: the packed frames and the device twins of the caller's arrays
     DevBuf h_frames, h_boxes, h_lmk, h_count, h_quality, h_parts, h_status;
 };
-
-// What the entries need of their context, which stays private to detector.hip.
-hipStream_t ctx_stream(const rfd_ctx *c);
-int ctx_device(const rfd_ctx *c);
-ShotQuality &ctx_shot_quality(rfd_ctx *c);
 
 } // namespace rfd

@@ -1,14 +1,11 @@
 // tracker_host.h -- rfd_tracker: what a tracker (include/rfd.h, "tracker") owns on the device, and what its kernel is told.
 // tracker_host.hip holds every rfd_tracker_* entry; the kernel is kernels_track.hip; the host decisions are track_plan.h.
 #pragma once
+#include "ctx_access.h" // what a tracker needs of its context: ctx_stream, ctx_device
 #include "host_resources.h"
 #include "track_plan.h"
 
 namespace rfd {
-
-// What a tracker needs of its context, which stays private to detector.hip (as gallery_host.h asks for it).
-hipStream_t ctx_stream(const rfd_ctx *c);
-int ctx_device(const rfd_ctx *c);
 
 // One slot of a stream in HBM: 32 bytes, read and written as two 16-byte halves.  serial 0 = free.
 struct TrackSlot {
