@@ -1283,6 +1283,88 @@ RFD_API int rfd_upload_frames_device(rfd_ctx *ctx, const rfd_frame *src, int n, 
 /* The same with everything in HOST memory (out[i].data is host memory, written through the same const cast); synchronous. */
 RFD_API int rfd_convert_frames(rfd_ctx *ctx, const rfd_frame *src, int n, const rfd_image *out);
 
+/* ---- JPEG encode: BGR frames and crops in device memory to baseline JPEG files, the inverse of "JPEG decode" above.  What a
+ *      deployment stores as evidence (the best shot of a track, the enrolment thumbnail, the frame of an alarm) leaves the device
+ *      as a file of some tens of KB, not as 6.2 MB of raw 1080p pixels for a JPEG library on the host.
+ *
+ *      Contract: the file equals, byte for byte from SOI to EOI, what libjpeg-turbo's default compressor writes for the same
+ *      pixels and settings (JDCT_ISLOW, no smoothing, the standard Huffman tables, optimize off) -- Pillow's
+ *      Image.save(f, "JPEG", quality=q, subsampling=s, restart_marker_rows=r).  tests/jpeg_encode_ref.py restates the rules in
+ *      numpy, tests/test_jpeg_encode_cpu.py pins the restatement against Pillow, tests/test_jpeg_encode_gpu.py the kernels against
+ *      the restatement.  Limits: baseline sequential only, 8 bits, the Annex-K tables (no optimised Huffman tables), one
+ *      interleaved scan, no progressive files, no EXIF or other metadata (APP0 JFIF 1.01 alone), no arithmetic coding.
+ *
+ *      The arithmetic, all integer, FIX(x) = (int)(x * 65536 + 0.5):
+ *        Y  = ( FIX(.299) R   + FIX(.587) G   + FIX(.114) B                 + 32768) >> 16
+ *        Cb = (-FIX(.16874) R - FIX(.33126) G + FIX(.5) B     + (128 << 16) + 32767) >> 16
+ *        Cr = ( FIX(.5) R     - FIX(.41869) G - FIX(.08131) B + (128 << 16) + 32767) >> 16      (a GRAY file holds Y only)
+ *      A component of luma factors h x v under hmax x vmax (1x1, 2x1 for 4:2:2, 2x2 for 4:2:0; chroma is 1x1) has
+ *      ceil(W h / hmax) x ceil(H v / vmax) samples in wb x hb real blocks.  Edges: the columns of the downsampler's INPUT are
+ *      extended to wb * 8 * (hmax / h) by repeating the last pixel; its rows only to a whole row group (a multiple of vmax / v);
+ *      the DOWNSAMPLED rows are then repeated down to hb * 8 (for 4:2:0 and H = 8 that differs from padding the input to 16
+ *      rows).  Downsampling is a plain mean: (a + b + c + d + bias) >> 2 with bias 1, 2, 1, 2 .. along the output columns (2x2),
+ *      (a + b + bias) >> 1 with bias 0, 1, 0, 1 .. (2x1).  Forward DCT: jfdctint.c on samples - 128 (rows first), the DCT scaled
+ *      by 8.  Quantisation: libjpeg's quality scaling (5000 / q below 50, else 200 - 2 q; clamp((base * scale + 50) / 100, 1,
+ *      255) on the two Annex-K tables, luma table 0, chroma table 1), v = (|c| + d / 2) / d with d = 8 * table and the sign put
+ *      back; the kernel multiplies by a reciprocal that tests/cpp/jpeg_encode_plan_check.cpp proves equal for every |c| < 2^15 and
+ *      every d.  The blocks of an MCU beyond wb or hb (dummy blocks) have zero AC and the DC of the block before them in the MCU's
+ *      block order; in a dummy bottom row, every block takes the DC of the last block of the row above within the MCU.  Entropy
+ *      coding: Annex-K tables, DC / AC 0 for Y and 1 for chroma, DC prediction per component and reset at each restart, every
+ *      interval padded with 1-bits to a byte, FF -> FF 00 inside entropy data, FF D0+(i mod 8) between intervals.  Header: SOI,
+ *      APP0, DQT 0 (and 1), SOF0 (component ids 1, 2, 3), DHT DC0 AC0 (DC1 AC1), DRI if there are restart rows, SOS.
+ *
+ *      Kernels (csrc/kernels_jpeg_encode.hip), all on the context's stream, four launches per call whatever the number and sizes
+ *      of its images: pixels -> quantised coefficients (8 threads per block); the length of every restart interval (one workgroup
+ *      per interval packs its blocks in parallel: a prefix sum of the blocks' bit lengths places them, LDS `or` packs them, a
+ *      second prefix sum counts the stuffed FF bytes); one workgroup per image scans the interval lengths, checks the capacity
+ *      and writes the header and size; the second run of the interval kernel writes its bytes where they belong in the slot.
+ *      Running the entropy coder twice costs less memory than it saves: a workspace that held every interval at its worst case
+ *      would be 20 MB per 1080p frame.  A file with restart_rows = 0 is ONE interval, hence one workgroup per image in the
+ *      entropy kernels: right for crops, where a call has many images, slow for a lone large frame -- give frames restart rows.
+ *      Workspace of a call: 128 bytes per block (3 bytes per pixel at 4:2:0), grown on demand and kept by the context. ---- */
+typedef struct rfd_jpeg_encode_config {
+    int32_t quality;      /* 1 .. 100, libjpeg's scale */
+    int32_t sampling;     /* rfd_jpeg_sampling */
+    int32_t restart_rows; /* 0: no restart markers; r >= 1: one interval per r MCU rows (Pillow's restart_marker_rows).  An
+                             interval above 65535 MCUs (what DRI can say) is refused */
+    int32_t reserved[5];  /* 0 */
+} rfd_jpeg_encode_config; /* 32 bytes */
+/* quality 90, RFD_JPEG_420, restart_rows 1 */
+RFD_API int rfd_jpeg_encode_config_default(rfd_jpeg_encode_config *cfg);
+/* Host only, no context.  *bytes = a size no file of this geometry can exceed.  It follows from the code-length limits of the
+ * tables alone: a block is at most 22 + 63 * 26 bits (a DC symbol of at most 11 + 11 bits, 63 AC symbols of 16 + 10 bits), every interval
+ * is padded to a byte, every byte may be FF and stuffed, then RSTn or EOI, plus the header.  Real files are some hundred times
+ * smaller; a slot is better sized from experience and the -1 of size_dev handled. */
+RFD_API int rfd_jpeg_encode_bound(int width, int height, const rfd_jpeg_encode_config *cfg, size_t *bytes);
+/* Host only, no context.  The bytes of the file up to and including the SOS segment.  *len is set whenever the arguments are
+ * valid; RFD_ERR_CAPACITY if cap < *len (out may then be NULL). */
+RFD_API int rfd_jpeg_encode_header(int width, int height, const rfd_jpeg_encode_config *cfg, uint8_t *out, size_t cap, size_t *len);
+/* Encodes n images: imgs[i].data, out, size_dev and the optional count_dev are DEVICE memory, imgs[] itself is host memory.  The
+ * file of image i goes to out + i * slot_bytes and size_dev[i] is its length, or -1 if it does not fit slot_bytes (or exceeds
+ * 2^31 - 1 bytes); then no byte of the slot is written.  Nothing is ever written outside a slot, nor behind a file's EOI.  With
+ * count_dev given, the images i >= *count_dev are not read, their slots stay untouched and size_dev[i] = 0: rfd_face_list.total is
+ * a ready count_dev and rfd_face_list.crops + t * crop bytes the image of crop t (stride 3 * out_w), so detect -> track -> align
+ * the due faces -> encode their crops is one stream order.  A rectangle of a frame is a data pointer into it with the frame's
+ * stride; any byte alignment and any stride >= 3 * width are legal.  The images of a call may differ in size; one config applies
+ * to all.  Enqueued on the context's stream with no host wait inside; async as in rfd_convert_frames_device.
+ * Errors, RFD_ERR_INVALID_ARG naming the field, with nothing enqueued: quality, sampling, restart_rows, reserved; a width or
+ * height outside 1 .. 65535; stride < 3 * width; a NULL pointer.  RFD_ERR_CAPACITY: n > max_batch_size; a call of more than
+ * 2^30 blocks.  n = 0 is a no-op. */
+RFD_API int rfd_encode_jpeg_batch_device(rfd_ctx *ctx, const rfd_image *imgs, int n, const int32_t *count_dev, const rfd_jpeg_encode_config *cfg, uint8_t *out,
+                                         size_t slot_bytes, int32_t *size_dev, int async);
+/* The same with everything in HOST memory; synchronous.  The frames go to device staging with one 2-D copy each; only size[i]
+ * bytes of file i come back over PCIe.  size[i] = -1: slot i is untouched. */
+RFD_API int rfd_encode_jpeg_batch(rfd_ctx *ctx, const rfd_image *imgs, int n, const rfd_jpeg_encode_config *cfg, uint8_t *out, size_t slot_bytes, int32_t *size);
+/* Test hook: the quantised coefficients the first kernel produced for one HOST image, dummy blocks included, in the layout of
+ * rfd_debug_jpeg_coefficients ([blocks][64] i16, natural order, component-major over planes padded to whole MCUs).  *blocks is
+ * always set; RFD_ERR_CAPACITY if cap_blocks < *blocks. */
+RFD_API int rfd_debug_jpeg_encode_blocks(rfd_ctx *ctx, const rfd_image *img, const rfd_jpeg_encode_config *cfg, int16_t *out, size_t cap_blocks, size_t *blocks);
+/* Test hook: the entropy and assembly kernels alone, on coefficients the caller supplies in that layout (HOST memory; DC within
+ * -1024 .. 1023 and AC within -1023 .. 1023, else RFD_ERR_INVALID_ARG) for a file of width x height -> the file in out (HOST
+ * memory, cap bytes) and its length, -1 if it does not fit. */
+RFD_API int rfd_debug_jpeg_encode_coefficients(rfd_ctx *ctx, const int16_t *coef, size_t blocks, int width, int height, const rfd_jpeg_encode_config *cfg, uint8_t *out,
+                                               size_t cap, int32_t *len);
+
 /* ---- introspection ---- */
 RFD_API int rfd_get_stats(rfd_ctx *ctx, rfd_stats *stats);
 RFD_API int rfd_get_config(const rfd_ctx *ctx, rfd_config *cfg);

@@ -10,6 +10,7 @@
 //   rfd::FaceSelection::call          <- FaceSelection::call                 src/pipeline/module/face_selection.rs:72-189
 //   rfd::FaceAlignment::call          <- FaceAlignment::call                 src/pipeline/module/face_alignment.rs:27-141
 //   rfd::decode_jpeg / _device        <- byte_data_to_opencv (imdecode)      src/utils/utils.rs:8-52
+//   rfd::encode_jpeg / _device        (no counterpart: the reference hands raw frames on)
 //   rfd::Error                        <- anyhow::Error: every failing entry point throws it (status + message)
 // What changed against the reference constructor: the Triton client / model config / model name arguments are gone
 // (the network runs in-process); device_id, max_det and the backbone are new.
@@ -603,6 +604,41 @@ inline void decode_jpeg_device(RetinaFaceDetection &det, const std::vector<std::
     std::vector<std::size_t> lens(files.size());
     for (std::size_t i = 0; i < files.size(); ++i) { ptrs[i] = files[i].data(); lens[i] = files[i].size(); }
     check(rfd_decode_jpeg_batch_device(det.raw(), ptrs.data(), lens.data(), (int)files.size(), frames.data(), async ? 1 : 0));
+}
+// The library's default encode settings (quality 90, 4:2:0, one restart row) with the given fields replaced (rfd.h, "JPEG encode")
+inline rfd_jpeg_encode_config jpeg_encode_config(int quality = 90, rfd_jpeg_sampling sampling = RFD_JPEG_420, int restart_rows = 1)
+{
+    rfd_jpeg_encode_config c;
+    check(rfd_jpeg_encode_config_default(&c));
+    c.quality = quality; c.sampling = (int32_t)sampling; c.restart_rows = restart_rows;
+    return c;
+}
+// host BGR frames -> baseline JPEG files, encoded on the device, byte for byte what libjpeg-turbo's default compressor writes.
+// slot_bytes: the room of a file (0: the largest rfd_jpeg_encode_bound of the frames); a file that does not fit comes back empty
+inline std::vector<std::vector<uint8_t>> encode_jpeg(RetinaFaceDetection &det, const std::vector<rfd_image> &frames, const rfd_jpeg_encode_config &cfg,
+                                                     std::size_t slot_bytes = 0)
+{
+    const std::size_t n = frames.size();
+    if (slot_bytes == 0)
+        for (const rfd_image &f : frames) {
+            std::size_t b = 0;
+            check(rfd_jpeg_encode_bound(f.width, f.height, &cfg, &b));
+            slot_bytes = std::max(slot_bytes, b);
+        }
+    std::vector<uint8_t> slots(n * slot_bytes);
+    std::vector<int32_t> size(n, 0);
+    check(rfd_encode_jpeg_batch(det.raw(), frames.data(), (int)n, &cfg, slots.data(), slot_bytes, size.data()));
+    std::vector<std::vector<uint8_t>> out(n);
+    for (std::size_t i = 0; i < n; ++i)
+        if (size[i] > 0) out[i].assign(slots.begin() + (std::ptrdiff_t)(i * slot_bytes), slots.begin() + (std::ptrdiff_t)(i * slot_bytes + (std::size_t)size[i]));
+    return out;
+}
+// DEVICE frames or crops -> files in DEVICE slots of slot_bytes each, size_dev[i] their lengths (-1: does not fit); count_dev
+// (device, may be null): images at and past it are left alone, e.g. rfd_face_list.total for its crops.  async: no host wait.
+inline void encode_jpeg_device(RetinaFaceDetection &det, const std::vector<rfd_image> &frames, const rfd_jpeg_encode_config &cfg, uint8_t *out, std::size_t slot_bytes,
+                               int32_t *size_dev, const int32_t *count_dev = nullptr, bool async = false)
+{
+    check(rfd_encode_jpeg_batch_device(det.raw(), frames.data(), (int)frames.size(), count_dev, &cfg, out, slot_bytes, size_dev, async ? 1 : 0));
 }
 // RFD_JPEG_ENTROPY_DEVICE: files with a restart interval are Huffman-decoded on the device (rfd.h, "entropy decoding on the
 // device"); every other file, and everything in RFD_JPEG_ENTROPY_HOST (the default), on the host threads

@@ -188,6 +188,10 @@ class rfd_jpeg_scaled_size(C.Structure):
                 ("stored_height", C.c_int32), ("orientation", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class rfd_jpeg_encode_config(C.Structure):
+    _fields_ = [("quality", C.c_int32), ("sampling", C.c_int32), ("restart_rows", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
 class rfd_tensor_desc(C.Structure):
     _fields_ = [("channels", C.c_int), ("height", C.c_int), ("width", C.c_int),
                 ("is_f32", C.c_int), ("buffer", C.c_int), ("is_input", C.c_int),
@@ -232,6 +236,8 @@ API_SYMBOLS = [
     "rfd_tracker_reset", "rfd_tracker_get_tracks", "rfd_align_detections_device",
     "rfd_shot_quality_config_default", "rfd_shot_quality_device", "rfd_shot_quality",
     "rfd_frame_layout_of", "rfd_convert_frames_device", "rfd_upload_frames_device", "rfd_convert_frames",
+    "rfd_jpeg_encode_config_default", "rfd_jpeg_encode_bound", "rfd_jpeg_encode_header", "rfd_encode_jpeg_batch_device", "rfd_encode_jpeg_batch",
+    "rfd_debug_jpeg_encode_blocks", "rfd_debug_jpeg_encode_coefficients",
 ]
 
 _lib = None
@@ -413,6 +419,14 @@ def load_library(path=None):
     L.rfd_convert_frames_device.argtypes = [vp, C.POINTER(rfd_frame), ci, C.POINTER(rfd_image), ci]
     L.rfd_upload_frames_device.argtypes = [vp, C.POINTER(rfd_frame), ci, C.POINTER(rfd_image), ci]
     L.rfd_convert_frames.argtypes = [vp, C.POINTER(rfd_frame), ci, C.POINTER(rfd_image)]
+    ecfg = C.POINTER(rfd_jpeg_encode_config)
+    L.rfd_jpeg_encode_config_default.argtypes = [ecfg]
+    L.rfd_jpeg_encode_bound.argtypes = [ci, ci, ecfg, C.POINTER(C.c_size_t)]
+    L.rfd_jpeg_encode_header.argtypes = [ci, ci, ecfg, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rfd_encode_jpeg_batch_device.argtypes = [vp, C.POINTER(rfd_image), ci, vp, ecfg, vp, C.c_size_t, vp, ci]
+    L.rfd_encode_jpeg_batch.argtypes = [vp, C.POINTER(rfd_image), ci, ecfg, vp, C.c_size_t, vp]
+    L.rfd_debug_jpeg_encode_blocks.argtypes = [vp, C.POINTER(rfd_image), ecfg, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rfd_debug_jpeg_encode_coefficients.argtypes = [vp, vp, C.c_size_t, ci, ci, ecfg, vp, C.c_size_t, C.POINTER(C.c_int32)]
     if path is None:
         _lib = L
     return L
@@ -686,6 +700,32 @@ def jpeg_intervals(data):
     begin, end = np.zeros(count.value, np.uint32), np.zeros(count.value, np.uint32)
     _check(L.rfd_debug_jpeg_intervals(addr, n, begin.ctypes.data, end.ctypes.data, count.value, C.byref(count)))
     return list(zip(begin.tolist(), end.tolist()))
+
+
+def jpeg_encode_config(quality=None, sampling=None, restart_rows=None):
+    """rfd_jpeg_encode_config: the library's default (90, 4:2:0, 1) with the given fields replaced; sampling a JPEG_* value"""
+    c = rfd_jpeg_encode_config()
+    _check(load_library().rfd_jpeg_encode_config_default(C.byref(c)))
+    for k, v in (("quality", quality), ("sampling", sampling), ("restart_rows", restart_rows)):
+        if v is not None:
+            setattr(c, k, int(v))
+    return c
+
+
+def jpeg_encode_bound(width, height, cfg=None):
+    """a size no file of this geometry can exceed (rfd_jpeg_encode_bound; host only, no GPU)"""
+    cfg = cfg or jpeg_encode_config()
+    n = C.c_size_t(0)
+    _check(load_library().rfd_jpeg_encode_bound(int(width), int(height), C.byref(cfg), C.byref(n)))
+    return n.value
+
+
+def jpeg_encode_header(width, height, cfg=None):
+    """the bytes of the file up to and including SOS (rfd_jpeg_encode_header; host only, no GPU)"""
+    cfg = cfg or jpeg_encode_config()
+    buf, n = (C.c_uint8 * 1024)(), C.c_size_t(0)
+    _check(load_library().rfd_jpeg_encode_header(int(width), int(height), C.byref(cfg), buf, 1024, C.byref(n)))
+    return bytes(buf[:n.value])
 
 
 def op_kernels_static(backbone, image_w, image_h, n, op, co_running=True, tile=0, schedule=SCHEDULE_THROUGHPUT, cus=256):
@@ -1720,6 +1760,56 @@ class RetinaFaceDetection:
         """rfd_upload_frames_device: the same with the planes at raw HOST addresses (pageable or host_alloc memory), which must
         stay as they are until the stream has run the copies when async_ is set."""
         return self._frames_call(self._L.rfd_upload_frames_device, frames, frame_ptrs, strides, async_)
+
+    def encode_jpeg(self, frames, cfg=None, slot_bytes=None):
+        """rfd_encode_jpeg_batch.  frames: list of [H, W, 3] u8 BGR host arrays (any row stride, unit pixel stride) -> list of
+        files (bytes), encoded on the device; None where a file does not fit slot_bytes (default: the largest bound)"""
+        cfg = cfg or jpeg_encode_config()
+        n = len(frames)
+        arr, keep = self._images(frames) if n else ((rfd_image * 1)(), [])
+        if slot_bytes is None:
+            slot_bytes = max([jpeg_encode_bound(f.shape[1], f.shape[0], cfg) for f in frames] + [1])
+        out = np.zeros((max(n, 1), int(slot_bytes)), np.uint8)
+        size = np.zeros(max(n, 1), np.int32)
+        _check(self._L.rfd_encode_jpeg_batch(self._ctx, arr, n, C.byref(cfg), out.ctypes.data, int(slot_bytes), size.ctypes.data))
+        return [out[i, :size[i]].tobytes() if size[i] >= 0 else None for i in range(n)]
+
+    def encode_jpeg_device(self, frame_ptrs, shapes, out_ptr, slot_bytes, size_ptr, cfg=None, strides=None, count_ptr=None, async_=False):
+        """rfd_encode_jpeg_batch_device.  frame_ptrs[i]: the raw DEVICE address of image i, shapes[i] = (h, w) rows of strides[i]
+        bytes (default 3 * w); out_ptr: device slots of slot_bytes each; size_ptr: device i32 [n]; count_ptr: device i32 or
+        None.  Enqueued on the detector's stream, with no host synchronisation when async_ is set."""
+        cfg = cfg or jpeg_encode_config()
+        n = len(frame_ptrs)
+        arr = (rfd_image * max(n, 1))()
+        for i in range(n):
+            h, w = shapes[i]
+            arr[i].data, arr[i].height, arr[i].width = frame_ptrs[i], int(h), int(w)
+            arr[i].stride = int(strides[i]) if strides is not None else int(w) * 3
+        _check(self._L.rfd_encode_jpeg_batch_device(self._ctx, arr, n, count_ptr, C.byref(cfg), out_ptr, int(slot_bytes), size_ptr, int(async_)))
+
+    def jpeg_encode_blocks(self, frame, cfg=None):
+        """test hook rfd_debug_jpeg_encode_blocks: one [H, W, 3] u8 BGR host frame -> [blocks, 64] i16 quantised coefficients,
+        natural order, dummy blocks included"""
+        cfg = cfg or jpeg_encode_config()
+        arr, keep = self._images([frame])
+        blocks = C.c_size_t(0)
+        st = self._L.rfd_debug_jpeg_encode_blocks(self._ctx, arr, C.byref(cfg), None, 0, C.byref(blocks))
+        if st != RFD_ERR_CAPACITY:
+            _check(st)
+        out = np.zeros((blocks.value, 64), np.int16)
+        _check(self._L.rfd_debug_jpeg_encode_blocks(self._ctx, arr, C.byref(cfg), out.ctypes.data, blocks.value, C.byref(blocks)))
+        return out
+
+    def jpeg_encode_coefficients(self, coef, width, height, cfg=None, cap=None):
+        """test hook rfd_debug_jpeg_encode_coefficients: [blocks, 64] i16 coefficients, natural order -> the file (bytes) the
+        entropy and assembly kernels write for them, None if it does not fit cap (default: the bound)"""
+        cfg = cfg or jpeg_encode_config()
+        coef = np.ascontiguousarray(coef, np.int16)
+        cap = int(cap if cap is not None else jpeg_encode_bound(width, height, cfg))
+        out, n = np.zeros(max(cap, 1), np.uint8), C.c_int32(0)
+        _check(self._L.rfd_debug_jpeg_encode_coefficients(self._ctx, coef.ctypes.data, coef.shape[0], int(width), int(height), C.byref(cfg),
+                                                           out.ctypes.data, cap, C.byref(n)))
+        return out[:n.value].tobytes() if n.value >= 0 else None
 
     def quality_decide(self, logits, threshold):
         """logits [n, classes] of the quality model -> (score [n] f32, klass [n] i32), face_quality.rs:159-168"""
