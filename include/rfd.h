@@ -1365,6 +1365,72 @@ RFD_API int rfd_debug_jpeg_encode_blocks(rfd_ctx *ctx, const rfd_image *img, con
 RFD_API int rfd_debug_jpeg_encode_coefficients(rfd_ctx *ctx, const int16_t *coef, size_t blocks, int width, int height, const rfd_jpeg_encode_config *cfg, uint8_t *out,
                                                size_t cap, int32_t *len);
 
+/* ---- redaction: pixelate or fill the faces of detection rows in BGR frames on the device, between "we know where the faces are"
+ *      and "write the file".  No counterpart in the reference.  The frame of an alarm also shows everyone else in front of the
+ *      camera; detect -> track -> redact (out of place) -> rfd_encode_jpeg_batch_device is one stream order with no host wait, and
+ *      the unredacted source stays available for the alignment and as evidence.
+ *
+ *      The rule, for frame b (H x W, BGR u8, byte stride).  Every step is integer, or one IEEE f32 operation in the written order
+ *      with no contraction; as_i32 as in "shot quality" above (toward zero, saturating, NaN -> 0).
+ *      Rows.     i < min(max(count[b], 0), max_det).  Row i is SELECTED when sel == NULL or (sel[b][i] & sel_mask) == sel_value:
+ *                the tracker's flags array with sel_mask = sel_value = RFD_TRACK_CONFIRMED redacts confirmed tracks, a caller-written
+ *                array can carry "not on the watch list", sel_mask = sel_value = 0 selects every row.
+ *      Region.   bw = x2 - x1, bh = y2 - y1; xa = x1 - bw * margin_x, xb = x2 + bw * margin_x, ya = y1 - bh * margin_top, yb = y2 +
+ *                bh * margin_bottom.  The row is SKIPPED if one of x1, y1, x2, y2 is not finite, if !(bw >= 0) or !(bh >= 0), or
+ *                if one of xa, xb, ya, yb is a NaN.  X0 = max(as_i32(xa), 0), Y0 = max(as_i32(ya), 0), X1 = min(as_i32(xb), W - 1),
+ *                Y1 = min(as_i32(yb), H - 1); the row is also skipped if X1 < X0 or Y1 < Y0.  w = X1 - X0 + 1, h = Y1 - Y0 + 1.
+ *      Cover.    RECT: every pixel of the region.  ELLIPSE: with dx = 2 (x - X0) + 1 - w and dy = 2 (y - Y0) + 1 - h, pixel (x, y) of
+ *                the region is covered iff dx^2 h^2 + dy^2 w^2 <= w^2 h^2 in int64 (sides <= 32768: a term is below 2^60).
+ *      Colour.   FILL: (fill[0], fill[1], fill[2]).  PIXELATE: the pixel lies in the FRAME-ANCHORED cell (y / cell, x / cell); per
+ *                channel m = (S + cnt / 2) / cnt, S the sum and cnt the count over ALL pixels of that cell inside the frame, read
+ *                from the SOURCE frame.  The cells belong to the frame, not to a box: the result is a pure function of (source
+ *                frame, set of covered pixels) and depends neither on the order of the rows nor on their overlaps.
+ *      Output.   A pixel covered by at least one selected, non-skipped row gets its colour, every other pixel its source value.
+ *                In place (dst == NULL): no byte of a non-covered pixel and no stride padding is ever written.  Out of place:
+ *                dst[b] has the size of imgs[b] and a stride >= 3 * width, overlaps no source frame, receives all 3 * W bytes of
+ *                every row (its padding is untouched), and the source is untouched.  applied[b] = the number of selected,
+ *                non-skipped rows of frame b, written for every b < n.
+ *
+ *      Limits.  One cell size per call (no per-face cells), no Gaussian or box blur (a blur needs a halo and an out-of-place
+ *      source), no outlines or landmarks drawn, and sel is the caller's: the library does not derive it from gallery results.
+ *      PIXELATION WITH A FIXED CELL IS WEAK ON VERY LARGE FACES (a 400-pixel face at cell 16 keeps 25 x 25 samples); FILL is the mode
+ *      that guarantees removal.  The defaults (rfd_redact_config_default) are CHOSEN values, not tuned on data.
+ *      Errors, all with nothing enqueued: RFD_ERR_INVALID_ARG with the field named in rfd_last_error() for every bound in the
+ *      config comments, a non-zero reserved word, a NULL required pointer (ctx, imgs, dets and its boxes / count), a frame or dst
+ *      with a NULL data pointer, a non-positive size, a side above RFD_REDACT_MAX_SIDE or a stride below 3 * width, a dst of
+ *      another size than its frame; RFD_ERR_CAPACITY for n > max_batch_size; n = 0 is a no-op. ---- */
+#define RFD_REDACT_FILL     0
+#define RFD_REDACT_PIXELATE 1
+#define RFD_REDACT_RECT     0
+#define RFD_REDACT_ELLIPSE  1
+#define RFD_REDACT_MAX_SIDE 32768
+typedef struct rfd_redact_config {
+    int32_t  mode;          /* RFD_REDACT_FILL or RFD_REDACT_PIXELATE */
+    int32_t  shape;         /* RFD_REDACT_RECT or RFD_REDACT_ELLIPSE */
+    int32_t  cell;          /* PIXELATE: side of the frame-anchored cells, 2 .. 64 (checked in both modes) */
+    uint8_t  fill[4];       /* FILL: B, G, R; fill[3] = 0 */
+    float    margin_x;      /* finite, 0 .. 4: the box grows by margin_x * its width on each side */
+    float    margin_top;    /* finite, 0 .. 4: ... by margin_top * its height upwards (hair, forehead) */
+    float    margin_bottom; /* finite, 0 .. 4: ... by margin_bottom * its height downwards */
+    uint32_t sel_mask, sel_value;
+    int32_t  reserved[6];   /* 0 */
+} rfd_redact_config;        /* 60 bytes */
+/* PIXELATE, ELLIPSE, cell 16, fill 0 0 0, margins 0.1 / 0.2 / 0.1, sel_mask 0, sel_value 0 (every row) */
+RFD_API int rfd_redact_config_default(rfd_redact_config *cfg);
+/* imgs[], dst[] and cfg: host memory; every imgs[i].data and dst[i].data, every pointer of `dets` (boxes, count; landmarks and
+ * total are not read), sel and applied: DEVICE memory.  The counts are read on the device.  rfd_image declares data const; this
+ * call WRITES through dst[i].data -- through imgs[i].data when dst is NULL -- as rfd_decode_jpeg_batch_device writes its `out`
+ * frames.  Enqueued on the context's stream, ONE launch whatever the number, sizes and alignment of the frames, no host wait
+ * (the frame descriptors travel through a ring of page-locked slots); async = 0 returns after the stream has drained, any other
+ * value at once.  The frames of a call may differ in size; any byte alignment of data and any stride >= 3 * width are legal. */
+RFD_API int rfd_redact_faces_device(rfd_ctx *ctx, const rfd_image *imgs, const rfd_image *dst /* NULL: in place */, int n,
+                                    const rfd_dets *dets, const uint32_t *sel /* [n][max_det] or NULL */,
+                                    const rfd_redact_config *cfg /* NULL: the default */, int32_t *applied /* [n] or NULL */, int async);
+/* Stage-level: the same with host pointers (frames included), through the same kernel; synchronous.  The rows of dst[i] (of
+ * imgs[i] when dst is NULL, written through the same const cast) come back with one 2-D copy of 3 * W bytes per row. */
+RFD_API int rfd_redact_faces(rfd_ctx *ctx, const rfd_image *imgs, const rfd_image *dst, int n, const rfd_dets *dets, const uint32_t *sel,
+                             const rfd_redact_config *cfg, int32_t *applied);
+
 /* ---- introspection ---- */
 RFD_API int rfd_get_stats(rfd_ctx *ctx, rfd_stats *stats);
 RFD_API int rfd_get_config(const rfd_ctx *ctx, rfd_config *cfg);

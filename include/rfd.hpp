@@ -864,5 +864,44 @@ inline void shot_quality_device(RetinaFaceDetection &det, const std::vector<rfd_
     check(rfd_shot_quality_device(det.raw(), imgs.data(), (int)imgs.size(), &dets, cfg, quality, parts, status, async ? 1 : 0));
 }
 
+// ---- redaction (rfd.h, "redaction"): pixelate or fill the faces of detection rows in frames ----
+inline rfd_redact_config redact_default_config()
+{
+    rfd_redact_config c;
+    check(rfd_redact_config_default(&c));
+    return c;
+}
+// Host frames[i] with their detections dets[i] as call_batch returns them, painted into dst[i] (frames of the same sizes), or in
+// place when dst is empty: the frames' data is then written through.  sel: empty, or one word per frame and row (rfd.h);
+// cfg = nullptr: the default.  -> applied per frame.
+inline std::vector<int32_t> redact_faces(RetinaFaceDetection &det, const std::vector<rfd_image> &frames, const std::vector<rfd_image> &dst,
+                                         const std::vector<Detections> &dets, const std::vector<std::vector<uint32_t>> &sel = {},
+                                         const rfd_redact_config *cfg = nullptr)
+{
+    const std::size_t n = frames.size(), md = det.max_det();
+    if (dets.size() != n) throw Error(RFD_ERR_INVALID_ARG, "redact faces - one detection list per frame");
+    if (!dst.empty() && dst.size() != n) throw Error(RFD_ERR_INVALID_ARG, "redact faces - one dst per frame, or none");
+    if (!sel.empty() && sel.size() != n) throw Error(RFD_ERR_INVALID_ARG, "redact faces - one sel list per frame, or none");
+    std::vector<float> boxes(n * md * 5);
+    std::vector<int32_t> count(n), applied(n);
+    std::vector<uint32_t> words(sel.empty() ? 0 : n * md);
+    for (std::size_t i = 0; i < n; ++i) {
+        const std::size_t k = std::min(dets[i].k, md);
+        std::copy(dets[i].det.begin(), dets[i].det.begin() + (std::ptrdiff_t)(k * 5), boxes.begin() + (std::ptrdiff_t)(i * md * 5));
+        count[i] = (int32_t)k;
+        if (!sel.empty()) std::copy_n(sel[i].begin(), std::min(sel[i].size(), md), words.begin() + (std::ptrdiff_t)(i * md));
+    }
+    const rfd_dets d{boxes.data(), nullptr, count.data(), nullptr};
+    check(rfd_redact_faces(det.raw(), frames.data(), dst.empty() ? nullptr : dst.data(), (int)n, &d, sel.empty() ? nullptr : words.data(), cfg, applied.data()));
+    return applied;
+}
+// DEVICE frames, slabs, sel and applied (either may be null; dst null: in place), enqueued on the detector's stream; async: no
+// host synchronisation.  The tracker's flags array is a ready `sel`.
+inline void redact_faces_device(RetinaFaceDetection &det, const std::vector<rfd_image> &imgs, const rfd_image *dst, const rfd_dets &dets,
+                                const uint32_t *sel, const rfd_redact_config *cfg, int32_t *applied = nullptr, bool async = false)
+{
+    check(rfd_redact_faces_device(det.raw(), imgs.data(), dst, (int)imgs.size(), &dets, sel, cfg, applied, async ? 1 : 0));
+}
+
 } // namespace rfd
 #endif

@@ -164,6 +164,12 @@ class rfd_shot_quality_config(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+class rfd_redact_config(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("shape", C.c_int32), ("cell", C.c_int32), ("fill", C.c_uint8 * 4), ("margin_x", C.c_float),
+                ("margin_top", C.c_float), ("margin_bottom", C.c_float), ("sel_mask", C.c_uint32), ("sel_value", C.c_uint32),
+                ("reserved", C.c_int32 * 6)]
+
+
 class rfd_frame(C.Structure):
     _fields_ = [("plane", C.c_void_p * 3), ("stride", C.c_ssize_t * 3), ("width", C.c_int32), ("height", C.c_int32),
                 ("format", C.c_int32), ("color", C.c_int32), ("reserved", C.c_int32 * 4)]
@@ -238,6 +244,7 @@ API_SYMBOLS = [
     "rfd_frame_layout_of", "rfd_convert_frames_device", "rfd_upload_frames_device", "rfd_convert_frames",
     "rfd_jpeg_encode_config_default", "rfd_jpeg_encode_bound", "rfd_jpeg_encode_header", "rfd_encode_jpeg_batch_device", "rfd_encode_jpeg_batch",
     "rfd_debug_jpeg_encode_blocks", "rfd_debug_jpeg_encode_coefficients",
+    "rfd_redact_config_default", "rfd_redact_faces_device", "rfd_redact_faces",
 ]
 
 _lib = None
@@ -427,6 +434,10 @@ def load_library(path=None):
     L.rfd_encode_jpeg_batch.argtypes = [vp, C.POINTER(rfd_image), ci, ecfg, vp, C.c_size_t, vp]
     L.rfd_debug_jpeg_encode_blocks.argtypes = [vp, C.POINTER(rfd_image), ecfg, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rfd_debug_jpeg_encode_coefficients.argtypes = [vp, vp, C.c_size_t, ci, ci, ecfg, vp, C.c_size_t, C.POINTER(C.c_int32)]
+    rcfg = C.POINTER(rfd_redact_config)
+    L.rfd_redact_config_default.argtypes = [rcfg]
+    L.rfd_redact_faces_device.argtypes = [vp, C.POINTER(rfd_image), C.POINTER(rfd_image), ci, C.POINTER(rfd_dets), vp, rcfg, vp, ci]
+    L.rfd_redact_faces.argtypes = [vp, C.POINTER(rfd_image), C.POINTER(rfd_image), ci, C.POINTER(rfd_dets), vp, rcfg, vp]
     if path is None:
         _lib = L
     return L
@@ -1102,6 +1113,25 @@ def shot_quality_config(**fields):
     return c
 
 
+REDACT_FILL, REDACT_PIXELATE = 0, 1   # RFD_REDACT_*: rfd_redact_config.mode
+REDACT_RECT, REDACT_ELLIPSE = 0, 1    # rfd_redact_config.shape
+REDACT_MAX_SIDE = 32768               # RFD_REDACT_MAX_SIDE
+
+
+def redact_config(**fields):
+    """rfd_redact_config: the default (PIXELATE, ELLIPSE, cell 16, fill 0 0 0, margins 0.1 / 0.2 / 0.1, sel_mask 0, sel_value 0
+    -- chosen values, not tuned on data) with the given fields replaced; fill = (B, G, R)"""
+    c = rfd_redact_config()
+    _check(load_library().rfd_redact_config_default(C.byref(c)))
+    for k, v in fields.items():
+        if k not in dict(rfd_redact_config._fields_) or k == "reserved":
+            raise TypeError("rfd_redact_config has no field %r" % k)
+        if k == "fill":
+            v = (C.c_uint8 * 4)(*(list(v) + [0] * (4 - len(v))))
+        setattr(c, k, v)
+    return c
+
+
 # rfd_pixel_format and rfd_color (rfd.h, "frames in camera and decoder formats")
 PIXEL_BGR, PIXEL_RGB, PIXEL_BGRA, PIXEL_RGBA, PIXEL_GRAY, PIXEL_NV12, PIXEL_NV21, PIXEL_I420, PIXEL_YUYV, PIXEL_UYVY = range(10)
 COLOR_BT601_LIMITED, COLOR_BT601_FULL, COLOR_BT709_LIMITED, COLOR_BT709_FULL = range(4)
@@ -1719,6 +1749,43 @@ class RetinaFaceDetection:
         ptr = lambda a: None if a is None else a.ctypes.data
         _check(self._L.rfd_shot_quality(self._ctx, arr, n, C.byref(d), cp, ptr(q), ptr(parts), ptr(status)))
         return q, parts, status
+
+    # ---- redaction: pixelate or fill the faces of detection rows in frames (rfd.h, "redaction") ----
+    def redact_faces(self, frames, dets, sel=None, cfg=None, device=False, dst=None, applied=None, async_=False):
+        """rfd_redact_faces / rfd_redact_faces_device; cfg: an rfd_redact_config (redact_config()), None = the default.
+        device=False: frames = HxWx3 u8 BGR arrays (any row stride, unit pixel stride), dets = (boxes [n, max_det, 5], count [n]),
+        sel = u32 [n, max_det] or None; dst = arrays of the frames' shapes to write into, None = in place (the frames
+        themselves are painted) -> (the painted arrays, applied [n] i32).
+        device=True: frames and dst = [(device address, height, width[, stride])], dets = (boxes, count) device addresses, sel and
+        applied = device addresses or None; enqueued on the context's stream, with no host synchronisation when async_ is set."""
+        n, md = len(frames), self.max_det
+        cp = None if cfg is None else C.byref(cfg)
+        if device:
+            def descs(fr):
+                arr = (rfd_image * max(n, 1))()
+                for i, f in enumerate(fr):
+                    arr[i].data, arr[i].height, arr[i].width = f[0], f[1], f[2]
+                    arr[i].stride = f[3] if len(f) > 3 else f[2] * 3
+                return arr
+            d = rfd_dets(dets[0], None, dets[1], None)
+            _check(self._L.rfd_redact_faces_device(self._ctx, descs(frames), None if dst is None else descs(dst), n, C.byref(d), sel, cp,
+                                                   applied, int(async_)))
+            return dst, applied
+        for f in list(frames) + list(dst or []):
+            if not (isinstance(f, np.ndarray) and f.dtype == np.uint8 and f.ndim == 3 and f.shape[2] == 3 and f.strides[1:] == (3, 1)):
+                raise RfdError(RFD_ERR_INVALID_ARG, "frames must be HxWx3 uint8 arrays (BGR) with contiguous rows: they are written in place")
+        arr, keep = self._images(frames) if n else ((rfd_image * 1)(), [])
+        darr = None
+        if dst is not None:
+            darr, keep_dst = self._images(dst) if n else ((rfd_image * 1)(), [])
+        b = np.ascontiguousarray(dets[0], np.float32).reshape(n, md, 5)
+        c = np.ascontiguousarray(dets[1], np.int32).reshape(n)
+        s = None if sel is None else np.ascontiguousarray(sel, np.uint32).reshape(n, md)
+        if applied is None:
+            applied = np.zeros(n, np.int32)
+        d = rfd_dets(b.ctypes.data, None, c.ctypes.data, None)
+        _check(self._L.rfd_redact_faces(self._ctx, arr, darr, n, C.byref(d), None if s is None else s.ctypes.data, cp, applied.ctypes.data))
+        return (list(frames) if dst is None else list(dst)), applied
 
     # ---- frames in camera and decoder formats (rfd.h): NV12, I420, YUYV, BGRA ... -> the BGR frames every other call reads ----
     def convert_frames(self, frames):
