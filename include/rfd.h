@@ -1447,7 +1447,9 @@ RFD_API int rfd_get_op_profile(rfd_ctx *ctx, float *ms, int cap);
 
 /* ---- test hooks (not part of the drop-in surface): raw access to a network tensor (device layout:
  *      NHWC, bf16 or f32 as rfd_tensor_desc says; n * C*H*W elements) and partial execution of the
- *      op list [first_op, last_op] (last_op < 0: to the end), so every op can be checked in isolation. */
+ *      op list [first_op, last_op] (last_op < 0: to the end), so every op can be checked in isolation.
+ *      In the f32 parity mode (RFD_PRECISION_F32) every tensor but the network input is f32: rfd_debug_tensor_io then moves
+ *      n * C*H*W * 4 bytes of an intermediate tensor, the n images contiguous at the tensor's own size. */
 RFD_API int rfd_debug_tensor_io(rfd_ctx *ctx, int tensor_id, int n, void *host, int write);
 RFD_API int rfd_debug_run_ops(rfd_ctx *ctx, int n, int first_op, int last_op);
 /* rfd_debug_run_ops as a chain of a split pass runs the range: on images [batch_off, batch_off + n) of the workspace

@@ -1018,14 +1018,18 @@ int rfd_debug_tensor_io(rfd_ctx *c, int tensor_id, int n, void *host, int write)
     RFD_TRY(c->ensure_network());
     RFD_CHECK_ARG(tensor_id >= 0 && tensor_id < (int)c->net.g.tensors.size(), "tensor id out of range");
     RFD_CHECK_ARG(n >= 1 && n <= c->cfg.max_batch_size, "batch out of range");
-    const size_t bytes = c->net.g.tensors[tensor_id].bytes_per_image() * (size_t)n;
+    const TensorDesc &td = c->net.g.tensors[tensor_id];
+    size_t bytes = td.bytes_per_image() * (size_t)n;
+    void *dev = c->net.tensor_ptr(tensor_id);
     c->ov_last_n = -1;
-    if (c->net.precision != 0 && !c->net.g.tensors[tensor_id].is_f32 && tensor_id != c->net.g.input) {
-        set_error("f32 parity mode: intermediate tensors are f32, not the bf16 layout this hook transfers");
-        return RFD_ERR_STATE;
+    if (c->net.precision != 0 && !td.is_f32 && tensor_id != c->net.g.input) {
+        // f32 parity mode: an intermediate tensor lives in the f32 workspace, n images of C*H*W floats, contiguous at the tensor's
+        // own size as the f32 kernels index them (Network::tensor_ptr32)
+        bytes = (size_t)n * td.C * td.H * td.W * sizeof(float);
+        dev = c->net.tensor_ptr32(tensor_id);
     }
-    if (write) RFD_HIP(hipMemcpyAsync(c->net.tensor_ptr(tensor_id), host, bytes, hipMemcpyHostToDevice, c->stream));
-    else RFD_HIP(hipMemcpyAsync(host, c->net.tensor_ptr(tensor_id), bytes, hipMemcpyDeviceToHost, c->stream));
+    if (write) RFD_HIP(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream));
+    else RFD_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
     RFD_HIP(hipStreamSynchronize(c->stream));
     return RFD_OK;
 }

@@ -6,9 +6,11 @@
 // This file is the mode in which north_star's "identical kept-box index sets, coordinates within 1e-4" can be shown END TO END
 // against an independent f32 evaluation: the same graph (same fusions, same folded parameters, same op list) with f32 weights,
 // f32 activations and -- since round 4 -- f64 ACCUMULATION with one rounding per convolution output: products of two f32 values are
-// exact in f64, so every conv output is the correctly rounded value of its exact sum (up to ~K * 2^-53, i.e. one output in ~10^5
-// lands on the other side of an f32 rounding boundary), whatever order the terms are added in.  Two f32 evaluations with
-// different summation orders differ by 1-3e-6 in the head tensors, which a 512-pixel anchor turns into 7e-4 px (round 3); two
+// exact in f64, so every conv output is the correctly rounded value of its exact sum, whatever order the terms are added in, up
+// to ~K * 2^-53 of the sum of the terms' magnitudes.  That worst-case bound leaves one output in 1.3 * 10^4 open between two
+// neighbouring floats; measured op by op, none of 4.1 * 10^7 outputs landed on another side of an f32 rounding boundary than the
+// CPU's f64 sum (tests/test_f32_exact_gpu.py holds every op to this per element; profiles/f32_exact_sweep.txt).  Two f32
+// evaluations with different summation orders differ by 1-3e-6 in the head tensors, which a 512-pixel anchor turns into 7e-4 px (round 3); two
 // f64-accumulating ones agree to the ulp, and north_star's 1e-4 becomes checkable end to end (tests/test_t2_gpu.py against
 // tests/torch_ref.py with acc64=True: f64 conv, .float() per layer).  Everything outside the sums is plain f32 in a fixed order.
 // It is a correctness mode, not a fast path: plain LDS-tiled FMA kernels (64 x 64 outputs per workgroup, K step 16), no MFMA,

@@ -2039,13 +2039,26 @@ class RetinaFaceDetection:
         return keep[:num.value].copy()
 
     # ---- test hooks ----
+    def debug_dtype(self, desc):
+        """element type of a network tensor on the device: the f32 parity mode keeps every tensor but the network input in f32"""
+        f32 = desc.is_f32 or (self.cfg.precision == PRECISION_F32 and not desc.is_input)
+        return np.float32 if f32 else np.uint16
+
     def debug_write(self, tensor_id, arr):
+        """arr: n images in device layout (NHWC), elements of the tensor's debug_dtype"""
         a = np.ascontiguousarray(arr)
+        if self.cfg.precision == PRECISION_F32:   # the library copies 4 bytes per element of an intermediate tensor: hold the array to that
+            if getattr(self, "_debug_graph", None) is None:
+                self._debug_graph = Graph(self.cfg.backbone, *self.image_size)
+            td = self._debug_graph.tensors[tensor_id]
+            want = (td.height, td.width, td.channels)
+            if a.ndim != 4 or a.shape[1:] != want or a.dtype != self.debug_dtype(td):
+                raise RfdError(RFD_ERR_INVALID_ARG, "debug_write: tensor %d takes [n, %d, %d, %d] %s in the f32 parity mode, got %s %s" % (
+                    (tensor_id,) + want + (np.dtype(self.debug_dtype(td)).name, list(a.shape), a.dtype.name)))
         _check(self._L.rfd_debug_tensor_io(self._ctx, tensor_id, a.shape[0], a.ctypes.data, 1))
 
     def debug_read(self, tensor_id, n, desc):
-        dt = np.float32 if desc.is_f32 else np.uint16
-        a = np.zeros((n, desc.height, desc.width, desc.channels), dt)
+        a = np.zeros((n, desc.height, desc.width, desc.channels), self.debug_dtype(desc))
         _check(self._L.rfd_debug_tensor_io(self._ctx, tensor_id, n, a.ctypes.data, 0))
         return a
 

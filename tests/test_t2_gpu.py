@@ -150,7 +150,8 @@ def test_t2_f32_parity_mode_meets_1e_4_against_the_f64_accumulating_walk(rfd, or
     device in its f32 parity mode (csrc/kernels_f32.hip) and torch-CPU through tests/torch_ref.py (acc64=True: F.conv2d in float64,
     `.float()` per layer, the elementwise steps in the device's order).  A product of two f32 values is exact in f64, so each side
     computes the correctly rounded value of the same exact sum; they differ only where ~K * 2^-53 of summation-order noise
-    straddles an f32 rounding boundary (about one output in 10^5), and such a one-ulp seed stays ~1e-7 relative downstream.
+    straddles an f32 rounding boundary (the worst-case bound allows it for one output in 1.3 * 10^4; per op, none of 4.1 * 10^7
+    did: tests/test_f32_exact_gpu.py, profiles/f32_exact_sweep.txt), and such a one-ulp seed stays ~1e-7 relative downstream.
     The heads are compared in ulps; the detections through the oracle's decode / NMS (face_detection.rs:319-493) of the torch
     heads against the device's rows.  Any residual above 1e-4 would be listed with its head-tensor ulp distance."""
     import torch

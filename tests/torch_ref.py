@@ -5,6 +5,8 @@ ops on the SAME weights read back from the device, rounding activations to bf16 
 HIP kernels do (every stored tensor except the f32 heads).  It is an independent implementation of
 the convolutions (torch/oneDNN), not the reference's network: the reference has none (the model
 lives on a Triton server that is not in the repo) -- CNN parity is "unpinned" (DESIGN.md)."""
+import contextlib
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -63,6 +65,18 @@ class TorchRef:
                 self.aff.append((torch.from_numpy(s), torch.from_numpy(t)))
             else:
                 self.aff.append(None)
+
+    @contextlib.contextmanager
+    def arithmetic(self):
+        """run_op() called on its own (not through forward()) evaluates with the roundings and the accumulation this object was
+        built for only inside this block: the switches are module state."""
+        saved = _ROUND[0], _ACC64[0]
+        _ROUND[0], _ACC64[0] = self.round_bf16, self.acc64
+        try:
+            with torch.no_grad():
+                yield self
+        finally:
+            _ROUND[0], _ACC64[0] = saved
 
     def run_op(self, i, tensors):
         """tensors: dict id -> NCHW f32 torch tensor (bf16-rounded values).  Evaluates op i."""
