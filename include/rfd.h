@@ -1143,6 +1143,136 @@ RFD_API int rfd_align_detections_device(rfd_ctx *ctx, const rfd_image *imgs, int
                                         const rfd_face_list_config *list_cfg, const rfd_alignment_config *align_cfg,
                                         const rfd_face_tensor_config *cfgs, int k, int cap, rfd_face_list *out, int async);
 
+/* ---- track identities: the gallery's answer brought back to the track, on the device.  No counterpart in the reference, which
+ *      sees one image.  The tracker hands out (stream, serial) and DUE; every due shot is embedded by the remote models and
+ *      searched in the gallery.  Without this section each shot is searched on its own, and a detection row can only be selected
+ *      "by person" after a host round trip that joins track, due_track and the search results by serial.  With it a track keeps
+ *        - a TEMPLATE: the weighted sum of the normalised embeddings of its shots, so the gallery is asked once per shot with
+ *          everything known about the track;
+ *        - a NAME: the identity the gallery gave the fused template, under a two-threshold rule;
+ *      and every detection row of every frame, the 24 of 25 per second that are not DUE included, gets an ANSWER in the shape
+ *      rfd_redact_faces_device takes as `sel`:
+ *        detect -> shot quality -> track -> align the due faces -> (models) -> fuse -> gallery search -> label -> who -> redact
+ *      is one stream order with no host wait.
+ *
+ *      State.  rfd_tracker_identity_enable allocates, once per tracker, [streams][max_tracks] entries {serial, identity, row,
+ *      score, named, shots, weight} and a template S[dim] f32 each, all zero.  Entry j of stream s belongs to the track in slot
+ *      j ONLY WHILE entry.serial == slot.serial.  Serials are not reused (tracker section), so an entry whose serial differs is
+ *      STALE: it belongs to a track that has ended, and it is cleared the first time the slot's new track is fused.  Hence the
+ *      tracker's update kernel, its slots, rfd_tracker_config, rfd_track_out and rfd_track are untouched by this section, and
+ *      rfd_tracker_reset needs no change either: the tracks it removes take their serials with them, and whatever is born in
+ *      their slots finds a stale entry.  A tracker that never enables identities launches and allocates what it always did.
+ *
+ *      The observations of a call (rfd_track_obs) are described the way the pipeline already holds them: the face list's total,
+ *      first and row, and the tracker's due_track as `serial`.  count = total ? min(max(total[0], 0), m) : m.  Frame b owns the
+ *      observations t in [max(first[b], 0), min(first[b + 1], count)); observation t of frame b is the track (stream[b],
+ *      serial[b][row[t]]).  The track is looked up by its serial among the stream's slots AT THE TIME THE KERNEL RUNS (the lowest
+ *      slot that holds it): the models are remote, so embeddings may arrive several updates late.  A track that has ended since,
+ *      a serial 0 or a row outside [0, max_det) is "no track": a status, not an error.  The observations of one stream are
+ *      processed in the call order of its frames and in ascending t within a frame; the face list is in (frame, row) order, so
+ *      that is ascending t and their order in time.  Streams are independent.  `stream` is a host array [n] that travels through
+ *      the tracker's ring of page-locked slots, so no call waits for the context's stream.
+ *
+ *      1. Fuse (rfd_tracker_fuse_device).  emb [m][dim] f32, the ID model's raw output; weight [m] f32 or NULL for 1.0f (the
+ *         natural source: the score array of rfd_quality_decide_device); query [m][dim] f32 and status [m] int32 are written.
+ *         For observation t, every operation f32 in the written order:
+ *         a. Normalise: e = emb[t] / |emb[t]| in the order of rfd_normalize_embeddings: lane l of 64 sums the squares of elements
+ *            l, l + 64, ... in ascending order starting from 0 (a lane that owns no element holds 0), the 64 partial sums meet
+ *            in the xor butterfly 32, 16, 8, 4, 2, 1 (s = s + partner's s), one sqrt, one division per element, every one an
+ *            IEEE operation rounded to nearest.  rfd_normalize_embeddings takes its square root with the hardware's
+ *            approximation, which is within one ulp; where that is the correctly rounded root, e has its bits.
+ *         b. Bad input: the norm is zero or not finite, or w is not (finite and > 0): status 2 (RFD_TRACK_FUSE_BAD_INPUT),
+ *            query[t] = e as computed, no state changes.
+ *         c. No track: status 1 (RFD_TRACK_FUSE_NO_TRACK), query[t] = e, no state changes.
+ *         d. Fuse: a stale entry is cleared first (S = 0, shots = 0, weight = 0, unnamed: identity -1, row -1, score -inf,
+ *            named 0; serial = the track's).  Then S[i] = S[i] + w * e[i]: one multiplication, one addition, no fma.  shots += 1,
+ *            weight = weight + w.  query[t] = S normalised by the rule of (a).  Status 0 (RFD_TRACK_FUSE_OK); when the norm of S
+ *            is not finite, status 3 (RFD_TRACK_FUSE_OVERFLOW): the state is kept as fused and query[t] is as computed.
+ *         query and status at or past the count stay as passed.  Splitting the observations of a stream over calls in any way
+ *         that keeps their order gives the same bits.
+ *      2. Label (rfd_tracker_label_device).  scores, rows, ids [m][k], k in 1..32, as rfd_gallery_search_identities_device (or
+ *         _filtered_device) wrote them for `query`; ids may be NULL (a plain search: every identity reads -1).  status_in is the
+ *         fuse call's status: observations with a non-zero status are skipped, and so are those whose track is "no track" or
+ *         whose entry is stale.  The same groups and order as the fuse call.  For observation t and its entry:
+ *           top = entry 0 of t; it is EMPTY when rows[t][0] == -1 or scores[t][0] is NaN.  The runner-up is entry 1 when k >= 2,
+ *           empty by the same rule.
+ *           A named entry (identity X, row R) KEEPS its name iff top is non-empty, names the same person (ids[t][0] == X when
+ *           X >= 0; rows[t][0] == R for an unlabelled gallery row, X = -1) and top.score >= release; then score = top.score and
+ *           row = rows[t][0].
+ *           Otherwise, and for an unnamed entry: the entry TAKES top as its name (named 1, identity, row, score of top) iff top
+ *           is non-empty, top.score >= accept, and there is no non-empty runner-up or top.score - runner.score >= margin (one
+ *           subtraction, one comparison).  If not, it is or becomes unnamed: named 0, identity -1, row -1, score -inf.
+ *         A later observation of the same track in the same call supersedes the earlier one: its query held more evidence.
+ *      3. Who (rfd_tracker_who_device), for every detection row of the n frames.  track [n][max_det] as rfd_track_out.track,
+ *         count [n].  Row i < min(max(count[b], 0), max_det) gets who[b][i] = (flags_in ? flags_in[b][i] : 0) | (named ?
+ *         RFD_TRACK_NAMED : 0), where "named" is: track[b][i] != 0, a slot of stream[b] holds that serial, its entry is not stale
+ *         and is named.  identity[b][i] and id_score[b][i] (each may be NULL) get the entry's values then, -1 and -inf otherwise.
+ *         who may be flags_in itself; no other overlap is allowed.  Rows at or past the count stay as passed.
+ *         "Redact everyone the gallery did not name" is rfd_redact_faces_device with sel = who, sel_mask = RFD_TRACK_NAMED,
+ *         sel_value = 0; "confirmed and unnamed" is sel_mask = RFD_TRACK_CONFIRMED | RFD_TRACK_NAMED, sel_value =
+ *         RFD_TRACK_CONFIRMED.  A watch-list deployment searches with rfd_gallery_search_filtered_device restricted to the
+ *         list's tag, so that "named" means "on the list".
+ *
+ *      The defaults (rfd_track_identity_config_default: dim 512, accept 0.5, release 0.4, margin 0.05) are CHOSEN values, not
+ *      tuned on data: this repository has no trained weights.
+ *      Errors: RFD_ERR_INVALID_ARG with the field named in rfd_last_error() for every bound in the config comments, for enabling
+ *      twice, a NULL required pointer, m < 0, k outside 1..32, a stream outside [0, streams), and for every call of this section
+ *      on a tracker without identities enabled; RFD_ERR_CAPACITY for a state above 1 GiB (streams * max_tracks * dim * 4) and
+ *      for n > max_batch_size.  n = 0 or m = 0 is a no-op; nothing is enqueued when a check fails.  Nothing here is atomic or
+ *      order-dependent: the same bits on every run.
+ *      Out of scope: the identity of tracks at the moment they end (the `ended` serials), saving the state to a file,
+ *      cross-camera linking, a decay of old shots, and any change to DUE. ---- */
+#define RFD_TRACK_NAMED 8u
+#define RFD_TRACK_FUSE_OK 0
+#define RFD_TRACK_FUSE_NO_TRACK 1
+#define RFD_TRACK_FUSE_BAD_INPUT 2
+#define RFD_TRACK_FUSE_OVERFLOW 3
+typedef struct rfd_track_identity_config {
+    int32_t dim;      /* the gallery's: a multiple of 32, 32..1024 */
+    float   accept;   /* an unnamed track takes a name when top score >= accept; finite */
+    float   release;  /* a named track keeps it while the same identity scores >= release; finite, release <= accept */
+    float   margin;   /* >= 0, finite: with k >= 2 and a non-empty runner-up, top - runner_up >= margin is also required to take a name */
+    int32_t reserved[4];
+} rfd_track_identity_config;   /* default: 512, 0.5, 0.4, 0.05 */
+typedef struct rfd_track_obs {
+    const int32_t *total;   /* [1] or NULL; observations t >= min(max(total[0],0), m) are skipped   (rfd_face_list.total) */
+    const int32_t *first;   /* [n+1]: frame b owns t in [first[b], first[b+1])                     (rfd_face_list.first) */
+    const int32_t *row;     /* [m]: row of t in its frame's slab                                   (rfd_face_list.row)   */
+    const int32_t *serial;  /* [n][max_det]: the track of each slab row                            (rfd_track_out.due_track) */
+} rfd_track_obs;
+typedef struct rfd_track_identity {
+    int32_t slot, serial;
+    int32_t identity, row;  /* of the gallery; -1, -1 while unnamed */
+    float   score;          /* -inf while unnamed */
+    int32_t named, shots;
+    float   weight;
+} rfd_track_identity;
+RFD_API int rfd_track_identity_config_default(rfd_track_identity_config *cfg);
+/* cfg NULL: the default.  Once per tracker; the fill of the state is enqueued in stream order. */
+RFD_API int rfd_tracker_identity_enable(rfd_tracker *t, const rfd_track_identity_config *cfg);
+/* stream: host [n]; every pointer of obs, emb, weight, query, status: DEVICE.  Enqueued on the context's stream with no host
+ * wait; async = 0 returns after the stream has drained, any other value at once. */
+RFD_API int rfd_tracker_fuse_device(rfd_tracker *t, const int32_t *stream, int n, const rfd_track_obs *obs, int m, const float *emb,
+                                    const float *weight, float *query, int32_t *status, int async);
+RFD_API int rfd_tracker_label_device(rfd_tracker *t, const int32_t *stream, int n, const rfd_track_obs *obs, int m, int k,
+                                     const float *scores, const int32_t *rows, const int32_t *ids, const int32_t *status_in, int async);
+RFD_API int rfd_tracker_who_device(rfd_tracker *t, const int32_t *stream, int n, const int32_t *track, const int32_t *count,
+                                   const uint32_t *flags_in, uint32_t *who, int32_t *identity, float *id_score, int async);
+/* Stage-level: the same with host pointers, through the same kernels; synchronous.  The output arrays travel to the device
+ * and back whole, so what they held past the counts comes back as it was. */
+RFD_API int rfd_tracker_fuse(rfd_tracker *t, const int32_t *stream, int n, const rfd_track_obs *obs, int m, const float *emb,
+                             const float *weight, float *query, int32_t *status);
+RFD_API int rfd_tracker_label(rfd_tracker *t, const int32_t *stream, int n, const rfd_track_obs *obs, int m, int k, const float *scores,
+                              const int32_t *rows, const int32_t *ids, const int32_t *status_in);
+RFD_API int rfd_tracker_who(rfd_tracker *t, const int32_t *stream, int n, const int32_t *track, const int32_t *count,
+                            const uint32_t *flags_in, uint32_t *who, int32_t *identity, float *id_score);
+/* The entries of the live slots of `stream` that are not stale, in ascending slot order: at most cap of them into out (may be
+ * NULL when cap is 0); *count = how many there are, also when that exceeds cap.  Waits for the stream. */
+RFD_API int rfd_tracker_get_identities(rfd_tracker *t, int stream, rfd_track_identity *out, int cap, int *count);
+/* The template S[dim] of the live track `serial` of `stream`; RFD_ERR_INVALID_ARG ("no such track") when no live slot holds
+ * that serial or its entry is stale.  Waits for the stream. */
+RFD_API int rfd_tracker_get_template(rfd_tracker *t, int stream, int32_t serial, float *out);
+
 /* ---- shot quality: a figure of merit in [0, 1] for every detection row, on the device, from the pixels under its box and its
  *      landmarks.  No counterpart in the reference.  It fills the quality[n][max_det] array that rfd_tracker_update_device reads,
  *      so that the tracker's DUE rule ("a better shot") compares sharpness, pose, exposure and size instead of the detector's

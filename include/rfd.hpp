@@ -801,10 +801,140 @@ class Tracker {
         return out;
     }
 
+    // ---- track identities (rfd.h, "track identities"): a template and a name per track, an answer per detection row ----
+    static rfd_track_identity_config default_identity_config()
+    {
+        rfd_track_identity_config c;
+        check(rfd_track_identity_config_default(&c));
+        return c;
+    }
+    // once per tracker
+    void enable_identities(const rfd_track_identity_config &cfg)
+    {
+        check(rfd_tracker_identity_enable(t_, &cfg));
+        id_cfg_ = cfg;
+    }
+    void enable_identities() { enable_identities(default_identity_config()); }
+    const rfd_track_identity_config &identity_config() const { return id_cfg_; }
+    // One observation of the host forms: the embedding (or gallery answer) of slab row `row` of frame `frame`, whose track is
+    // `serial`; observations in (frame, row) order.
+    struct Observation {
+        int32_t frame, row, serial;
+    };
+    struct Fused {
+        std::vector<float> query;     // [m][dim]: what to search the gallery with
+        std::vector<int32_t> status;  // [m]: RFD_TRACK_FUSE_*
+    };
+    // emb: [m][dim], the ID model's raw output; weight: [m] or empty for 1
+    Fused fuse(const std::vector<int32_t> &streams, const std::vector<Observation> &obs, const std::vector<float> &emb,
+               const std::vector<float> &weight = {})
+    {
+        const std::size_t m = obs.size(), dim = (std::size_t)id_cfg_.dim;
+        if (emb.size() != m * dim || (!weight.empty() && weight.size() != m)) throw Error(RFD_ERR_INVALID_ARG, "tracker - an embedding (and weight) per observation");
+        ObsArrays a = obs_arrays(streams, obs);
+        Fused out{std::vector<float>(m * dim), std::vector<int32_t>(m, RFD_TRACK_FUSE_NO_TRACK)};
+        const rfd_track_obs o{nullptr, a.first.data(), a.row.data(), a.serial.data()};
+        check(rfd_tracker_fuse(t_, streams.data(), (int)streams.size(), &o, (int)m, emb.data(), weight.empty() ? nullptr : weight.data(),
+                               out.query.data(), out.status.data()));
+        return out;
+    }
+    // scores, rows, ids: [m][k] as Gallery's identity search returned them for Fused::query; status: Fused::status
+    void label(const std::vector<int32_t> &streams, const std::vector<Observation> &obs, int k, const std::vector<float> &scores,
+               const std::vector<int32_t> &rows, const std::vector<int32_t> &ids, const std::vector<int32_t> &status)
+    {
+        const std::size_t m = obs.size(), mk = m * (std::size_t)(k > 0 ? k : 0);
+        if (scores.size() != mk || rows.size() != mk || (!ids.empty() && ids.size() != mk) || status.size() != m)
+            throw Error(RFD_ERR_INVALID_ARG, "tracker - k results and a status per observation");
+        ObsArrays a = obs_arrays(streams, obs);
+        const rfd_track_obs o{nullptr, a.first.data(), a.row.data(), a.serial.data()};
+        check(rfd_tracker_label(t_, streams.data(), (int)streams.size(), &o, (int)m, k, scores.data(), rows.data(), ids.empty() ? nullptr : ids.data(),
+                                status.data()));
+    }
+    // one frame's answer of who: per row the flags with RFD_TRACK_NAMED added, the identity (-1) and its score (-inf)
+    struct Who {
+        std::vector<uint32_t> who;
+        std::vector<int32_t> identity;
+        std::vector<float> score;
+    };
+    // frames: what update returned for the same streams; every row of every frame is answered
+    std::vector<Who> who(const std::vector<int32_t> &streams, const std::vector<Frame> &frames)
+    {
+        const std::size_t n = frames.size(), md = max_det_;
+        if (streams.size() != n) throw Error(RFD_ERR_INVALID_ARG, "tracker - one stream per frame");
+        std::vector<int32_t> track(n * md), count(n), identity(n * md);
+        std::vector<uint32_t> flags(n * md);
+        std::vector<float> score(n * md);
+        for (std::size_t i = 0; i < n; ++i) {
+            const std::size_t k = std::min(frames[i].track.size(), md);
+            std::copy(frames[i].track.begin(), frames[i].track.begin() + (std::ptrdiff_t)k, track.begin() + (std::ptrdiff_t)(i * md));
+            std::copy(frames[i].flags.begin(), frames[i].flags.begin() + (std::ptrdiff_t)k, flags.begin() + (std::ptrdiff_t)(i * md));
+            count[i] = (int32_t)k;
+        }
+        check(rfd_tracker_who(t_, streams.data(), (int)n, track.data(), count.data(), flags.data(), flags.data(), identity.data(), score.data()));
+        std::vector<Who> res(n);
+        for (std::size_t i = 0; i < n; ++i) {
+            const std::ptrdiff_t at = (std::ptrdiff_t)(i * md), k = (std::ptrdiff_t)count[i];
+            res[i].who.assign(flags.begin() + at, flags.begin() + at + k);
+            res[i].identity.assign(identity.begin() + at, identity.begin() + at + k);
+            res[i].score.assign(score.begin() + at, score.begin() + at + k);
+        }
+        return res;
+    }
+    // DEVICE pointers throughout (stream list: host), enqueued on the detector's stream; async: no host synchronisation
+    void fuse_device(const std::vector<int32_t> &streams, const rfd_track_obs &obs, int m, const float *emb, const float *weight, float *query,
+                     int32_t *status, bool async = false)
+    {
+        check(rfd_tracker_fuse_device(t_, streams.data(), (int)streams.size(), &obs, m, emb, weight, query, status, async ? 1 : 0));
+    }
+    void label_device(const std::vector<int32_t> &streams, const rfd_track_obs &obs, int m, int k, const float *scores, const int32_t *rows,
+                      const int32_t *ids, const int32_t *status, bool async = false)
+    {
+        check(rfd_tracker_label_device(t_, streams.data(), (int)streams.size(), &obs, m, k, scores, rows, ids, status, async ? 1 : 0));
+    }
+    void who_device(const std::vector<int32_t> &streams, const int32_t *track, const int32_t *count, const uint32_t *flags_in, uint32_t *who,
+                    int32_t *identity, float *id_score, bool async = false)
+    {
+        check(rfd_tracker_who_device(t_, streams.data(), (int)streams.size(), track, count, flags_in, who, identity, id_score, async ? 1 : 0));
+    }
+    // the entries of the live, fused tracks of a stream in ascending slot order (waits for the stream)
+    std::vector<rfd_track_identity> identities(int stream)
+    {
+        int n = 0;
+        check(rfd_tracker_get_identities(t_, stream, nullptr, 0, &n));
+        std::vector<rfd_track_identity> out((std::size_t)n);
+        check(rfd_tracker_get_identities(t_, stream, out.data(), n, &n));
+        return out;
+    }
+    // the template of a live, fused track; throws for "no such track"
+    std::vector<float> track_template(int stream, int32_t serial)
+    {
+        std::vector<float> out((std::size_t)id_cfg_.dim);
+        check(rfd_tracker_get_template(t_, stream, serial, out.data()));
+        return out;
+    }
+
   private:
+    struct ObsArrays {
+        std::vector<int32_t> first, row, serial;
+    };
+    ObsArrays obs_arrays(const std::vector<int32_t> &streams, const std::vector<Observation> &obs) const
+    {
+        const std::size_t n = streams.size(), md = max_det_;
+        ObsArrays a{std::vector<int32_t>(n + 1, 0), std::vector<int32_t>(obs.size()), std::vector<int32_t>(n * md, 0)};
+        for (std::size_t t = 0; t < obs.size(); ++t) {
+            const Observation &o = obs[t];
+            if (o.frame < 0 || (std::size_t)o.frame >= n || (t > 0 && o.frame < obs[t - 1].frame))
+                throw Error(RFD_ERR_INVALID_ARG, "tracker - observations in frame order, each of a frame of the call");
+            for (std::size_t b = (std::size_t)o.frame + 1; b <= n; ++b) ++a.first[b];
+            a.row[t] = o.row;
+            if (o.row >= 0 && (std::size_t)o.row < md) a.serial[(std::size_t)o.frame * md + (std::size_t)o.row] = o.serial;
+        }
+        return a;
+    }
     rfd_tracker *t_ = nullptr;
     std::size_t max_det_ = 0;
     rfd_tracker_config cfg_{};
+    rfd_track_identity_config id_cfg_{};
 };
 
 // The device-resident form of the face list over caller-made DEVICE slabs (rfd_align_detections_device): with a tracker's

@@ -28,3 +28,6 @@ echo "built $OBJ/gallery_identity_demo"
 # the tracker through include/rfd.hpp (tests/test_tracker_cpp_gpu.py)
 g++ -std=c++17 -O2 -Wall -I"$HERE/../include" "$HERE/../tests/cpp/tracker_demo.cpp" -o "$OBJ/tracker_demo" -L"$HERE" -lrfd_hip -Wl,-rpath,'$ORIGIN/..' -Wl,-rpath,"$HERE" -Wl,-rpath,/opt/rocm/lib
 echo "built $OBJ/tracker_demo"
+# the track identities through include/rfd.hpp (tests/test_track_identity_cpp_gpu.py)
+g++ -std=c++17 -O2 -Wall -I"$HERE/../include" "$HERE/../tests/cpp/track_identity_demo.cpp" -o "$OBJ/track_identity_demo" -L"$HERE" -lrfd_hip -Wl,-rpath,'$ORIGIN/..' -Wl,-rpath,"$HERE" -Wl,-rpath,/opt/rocm/lib
+echo "built $OBJ/track_identity_demo"

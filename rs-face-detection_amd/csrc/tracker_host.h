@@ -4,6 +4,7 @@
 #include "ctx_access.h" // what a tracker needs of its context: ctx_stream, ctx_device
 #include "host_resources.h"
 #include "track_plan.h"
+#include "track_identity_host.h" // TrackIdentityState: empty unless identities are enabled
 
 namespace rfd {
 
@@ -61,4 +62,6 @@ struct rfd_tracker {
     // host form, allocated by its first call: the device twins of the caller's arrays
     rfd::DevBuf h_boxes, h_lmk, h_count, h_quality, h_track, h_flags, h_stats, h_ended, h_due_boxes, h_due_lmk, h_due_count,
         h_due_total, h_due_track;
+    // the track identities (track_identity_host.hip): nothing is allocated before rfd_tracker_identity_enable
+    rfd::TrackIdentityState ident;
 };

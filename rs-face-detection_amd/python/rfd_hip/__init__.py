@@ -158,6 +158,19 @@ class rfd_track(C.Structure):
                 ("shot_q", C.c_float)]
 
 
+class rfd_track_identity_config(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("accept", C.c_float), ("release", C.c_float), ("margin", C.c_float), ("reserved", C.c_int32 * 4)]
+
+
+class rfd_track_obs(C.Structure):
+    _fields_ = [("total", C.c_void_p), ("first", C.c_void_p), ("row", C.c_void_p), ("serial", C.c_void_p)]
+
+
+class rfd_track_identity(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("serial", C.c_int32), ("identity", C.c_int32), ("row", C.c_int32), ("score", C.c_float),
+                ("named", C.c_int32), ("shots", C.c_int32), ("weight", C.c_float)]
+
+
 class rfd_shot_quality_config(C.Structure):
     _fields_ = [("dark", C.c_int32), ("bright", C.c_int32), ("pitch0", C.c_float), ("w_yaw", C.c_float), ("w_roll", C.c_float),
                 ("w_pitch", C.c_float), ("sharp_ref", C.c_float), ("size_ref", C.c_float), ("times_score", C.c_int32),
@@ -240,6 +253,9 @@ API_SYMBOLS = [
     "rfd_view_config_default", "rfd_view_plan", "rfd_detect_views_batch_device", "rfd_detect_views_batch", "rfd_decode_nms_views",
     "rfd_tracker_config_default", "rfd_tracker_create", "rfd_tracker_destroy", "rfd_tracker_update_device", "rfd_tracker_update",
     "rfd_tracker_reset", "rfd_tracker_get_tracks", "rfd_align_detections_device",
+    "rfd_track_identity_config_default", "rfd_tracker_identity_enable", "rfd_tracker_fuse_device", "rfd_tracker_label_device",
+    "rfd_tracker_who_device", "rfd_tracker_fuse", "rfd_tracker_label", "rfd_tracker_who", "rfd_tracker_get_identities",
+    "rfd_tracker_get_template",
     "rfd_shot_quality_config_default", "rfd_shot_quality_device", "rfd_shot_quality",
     "rfd_frame_layout_of", "rfd_convert_frames_device", "rfd_upload_frames_device", "rfd_convert_frames",
     "rfd_jpeg_encode_config_default", "rfd_jpeg_encode_bound", "rfd_jpeg_encode_header", "rfd_encode_jpeg_batch_device", "rfd_encode_jpeg_batch",
@@ -418,6 +434,16 @@ def load_library(path=None):
     L.rfd_tracker_update.argtypes = [vp, vp, C.POINTER(rfd_dets), vp, ci, C.POINTER(rfd_track_out)]
     L.rfd_tracker_reset.argtypes = [vp, ci]
     L.rfd_tracker_get_tracks.argtypes = [vp, ci, C.POINTER(rfd_track), ci, C.POINTER(ci)]
+    L.rfd_track_identity_config_default.argtypes = [C.POINTER(rfd_track_identity_config)]
+    L.rfd_tracker_identity_enable.argtypes = [vp, C.POINTER(rfd_track_identity_config)]
+    L.rfd_tracker_fuse_device.argtypes = [vp, vp, ci, C.POINTER(rfd_track_obs), ci, vp, vp, vp, vp, ci]
+    L.rfd_tracker_label_device.argtypes = [vp, vp, ci, C.POINTER(rfd_track_obs), ci, ci, vp, vp, vp, vp, ci]
+    L.rfd_tracker_who_device.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, ci]
+    L.rfd_tracker_fuse.argtypes = [vp, vp, ci, C.POINTER(rfd_track_obs), ci, vp, vp, vp, vp]
+    L.rfd_tracker_label.argtypes = [vp, vp, ci, C.POINTER(rfd_track_obs), ci, ci, vp, vp, vp, vp]
+    L.rfd_tracker_who.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp]
+    L.rfd_tracker_get_identities.argtypes = [vp, ci, C.POINTER(rfd_track_identity), ci, C.POINTER(ci)]
+    L.rfd_tracker_get_template.argtypes = [vp, ci, C.c_int32, vp]
     L.rfd_align_detections_device.argtypes = [vp, C.POINTER(rfd_image), ci, C.POINTER(rfd_dets), vp, vp, vp, ci, ci, C.POINTER(rfd_face_list), ci]
     L.rfd_shot_quality_config_default.argtypes = [C.POINTER(rfd_shot_quality_config)]
     L.rfd_shot_quality_device.argtypes = [vp, C.POINTER(rfd_image), ci, C.POINTER(rfd_dets), C.POINTER(rfd_shot_quality_config), vp, vp, vp, ci]
@@ -1096,8 +1122,123 @@ class Tracker:
         _check(self._L.rfd_tracker_get_tracks(self._t, int(stream), arr, n.value, C.byref(n)))
         return list(arr[:n.value])
 
+    # ---- track identities (rfd.h, "track identities") ----
+    def enable_identities(self, cfg=None, **fields):
+        """rfd_tracker_identity_enable, once per tracker: cfg, or the default (dim 512, accept 0.5, release 0.4, margin 0.05 --
+        chosen values, not tuned on data) with `fields` replaced"""
+        self.identity_cfg = cfg if cfg is not None else track_identity_config(**fields)
+        _check(self._L.rfd_tracker_identity_enable(self._t, C.byref(self.identity_cfg)))
+        return self.identity_cfg
 
-SHOT_QUALITY_PARTS = 8            # RFD_SHOT_QUALITY_PARTS: sharp, mean, expo, yaw, roll, pitch, pose, size
+    def _obs(self, n, first, row, serial, total):
+        """the host arrays of an rfd_track_obs (kept alive by the caller of this) and the struct over them"""
+        f = np.ascontiguousarray(first, np.int32).reshape(n + 1)
+        r = np.ascontiguousarray(row, np.int32).reshape(-1)
+        s = np.ascontiguousarray(serial, np.int32).reshape(n, self._det.max_det)
+        t = None if total is None else np.ascontiguousarray(total, np.int32).reshape(1)
+        return (f, r, s, t), rfd_track_obs(None if t is None else t.ctypes.data, f.ctypes.data, r.ctypes.data, s.ctypes.data), len(r)
+
+    def fuse(self, streams, first, row, serial, emb, weight=None, total=None, query=None, status=None):
+        """the host form of rfd_tracker_fuse: streams [n]; first [n + 1], row [m], total (an int or None) as a FaceList holds them,
+        serial [n, max_det] as TrackOut.due_track; emb [m, dim]; weight [m] or None -> (query [m, dim] f32, status [m] int32).
+        query / status: caller-made arrays to write into (rows at or past the count keep what they hold)"""
+        s = self._streams(streams)
+        keep, obs, m = self._obs(len(s), first, row, serial, total)
+        dim = self.identity_cfg.dim
+        e = np.ascontiguousarray(emb, np.float32).reshape(m, dim)
+        w = None if weight is None else np.ascontiguousarray(weight, np.float32).reshape(m)
+        query = np.zeros((m, dim), np.float32) if query is None else query
+        status = np.zeros(m, np.int32) if status is None else status
+        assert query.dtype == np.float32 and query.shape == (m, dim) and query.flags.c_contiguous
+        assert status.dtype == np.int32 and status.shape == (m,) and status.flags.c_contiguous
+        _check(self._L.rfd_tracker_fuse(self._t, s.ctypes.data, len(s), C.byref(obs), m, e.ctypes.data, None if w is None else w.ctypes.data,
+                                        query.ctypes.data, status.ctypes.data))
+        return query, status
+
+    def fuse_device(self, streams, obs, m, emb_ptr, query_ptr, status_ptr, weight_ptr=None, async_=False):
+        """the same from raw device addresses; obs: an rfd_track_obs of device addresses.  Enqueued on the detector's stream, with
+        no host synchronisation when async_ is set"""
+        s = self._streams(streams)
+        _check(self._L.rfd_tracker_fuse_device(self._t, s.ctypes.data, len(s), C.byref(obs), int(m), emb_ptr, weight_ptr, query_ptr, status_ptr,
+                                               int(async_)))
+
+    def label(self, streams, first, row, serial, scores, rows, ids, status, total=None):
+        """the host form of rfd_tracker_label: the observations as in fuse; scores / rows / ids [m, k] as the gallery's identity
+        search wrote them for fuse's query (ids may be None); status: fuse's"""
+        s = self._streams(streams)
+        keep, obs, m = self._obs(len(s), first, row, serial, total)
+        sc = np.ascontiguousarray(scores, np.float32)
+        assert sc.ndim == 2 and sc.shape[0] == m, "scores is [m, k]"
+        k = sc.shape[1]
+        rw = np.ascontiguousarray(rows, np.int32).reshape(m, k)
+        idn = None if ids is None else np.ascontiguousarray(ids, np.int32).reshape(m, k)
+        st = np.ascontiguousarray(status, np.int32).reshape(m)
+        _check(self._L.rfd_tracker_label(self._t, s.ctypes.data, len(s), C.byref(obs), m, k, sc.ctypes.data, rw.ctypes.data,
+                                         None if idn is None else idn.ctypes.data, st.ctypes.data))
+
+    def label_device(self, streams, obs, m, k, scores_ptr, rows_ptr, ids_ptr, status_ptr, async_=False):
+        """the same from raw device addresses, by the conventions of fuse_device"""
+        s = self._streams(streams)
+        _check(self._L.rfd_tracker_label_device(self._t, s.ctypes.data, len(s), C.byref(obs), int(m), int(k), scores_ptr, rows_ptr, ids_ptr,
+                                                status_ptr, int(async_)))
+
+    def who(self, streams, track, count, flags=None, who=None, identity=None, id_score=None):
+        """the host form of rfd_tracker_who: track [n, max_det] and count [n] as TrackOut holds them; flags [n, max_det] uint32 or
+        None -> (who, identity, id_score), each [n, max_det].  who / identity / id_score: caller-made arrays to write into (rows at
+        or past a frame's count keep what they hold); who may be `flags` itself"""
+        s = self._streams(streams)
+        n, md = len(s), self._det.max_det
+        tr = np.ascontiguousarray(track, np.int32).reshape(n, md)
+        c = np.ascontiguousarray(count, np.int32).reshape(n)
+        who = np.zeros((n, md), np.uint32) if who is None else who
+        identity = np.zeros((n, md), np.int32) if identity is None else identity
+        id_score = np.zeros((n, md), np.float32) if id_score is None else id_score
+        fl = None if flags is None else (flags if flags is who else np.ascontiguousarray(flags, np.uint32).reshape(n, md))
+        for a, dt in ((who, np.uint32), (identity, np.int32), (id_score, np.float32)):
+            assert a.dtype == dt and a.shape == (n, md) and a.flags.c_contiguous
+        _check(self._L.rfd_tracker_who(self._t, s.ctypes.data, n, tr.ctypes.data, c.ctypes.data, None if fl is None else fl.ctypes.data,
+                                       who.ctypes.data, identity.ctypes.data, id_score.ctypes.data))
+        return who, identity, id_score
+
+    def who_device(self, streams, track_ptr, count_ptr, who_ptr, flags_ptr=None, identity_ptr=None, id_score_ptr=None, async_=False):
+        """the same from raw device addresses; who_ptr may equal flags_ptr"""
+        s = self._streams(streams)
+        _check(self._L.rfd_tracker_who_device(self._t, s.ctypes.data, len(s), track_ptr, count_ptr, flags_ptr, who_ptr, identity_ptr,
+                                              id_score_ptr, int(async_)))
+
+    def identities(self, stream):
+        """the entries of the live, fused tracks of a stream in ascending slot order, as rfd_track_identity structures (waits for
+        the stream)"""
+        n = C.c_int(0)
+        _check(self._L.rfd_tracker_get_identities(self._t, int(stream), None, 0, C.byref(n)))
+        arr = (rfd_track_identity * max(n.value, 1))()
+        _check(self._L.rfd_tracker_get_identities(self._t, int(stream), arr, n.value, C.byref(n)))
+        return list(arr[:n.value])
+
+    def template(self, stream, serial):
+        """the template S [dim] f32 of a live, fused track (waits for the stream); an unknown serial raises"""
+        out = np.zeros(self.identity_cfg.dim, np.float32)
+        _check(self._L.rfd_tracker_get_template(self._t, int(stream), int(serial), out.ctypes.data))
+        return out
+
+
+TRACK_NAMED = 8                                   # RFD_TRACK_NAMED: the bit rfd_tracker_who adds to a row's flags
+TRACK_FUSE_OK, TRACK_FUSE_NO_TRACK, TRACK_FUSE_BAD_INPUT, TRACK_FUSE_OVERFLOW = 0, 1, 2, 3   # RFD_TRACK_FUSE_*: fuse's status
+
+
+def track_identity_config(**fields):
+    """rfd_track_identity_config: the default (dim 512, accept 0.5, release 0.4, margin 0.05 -- chosen values, not tuned on
+    data) with the given fields replaced"""
+    c = rfd_track_identity_config()
+    _check(load_library().rfd_track_identity_config_default(C.byref(c)))
+    for k, v in fields.items():
+        if k not in dict(rfd_track_identity_config._fields_) or k == "reserved":
+            raise TypeError("rfd_track_identity_config has no field %r" % k)
+        setattr(c, k, v)
+    return c
+
+
+SHOT_QUALITY_PARTS = 8           # RFD_SHOT_QUALITY_PARTS: sharp, mean, expo, yaw, roll, pitch, pose, size
 SHOT_QUALITY_MAX_SIDE = 32768     # RFD_SHOT_QUALITY_MAX_SIDE
 
 
