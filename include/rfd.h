@@ -1179,8 +1179,7 @@ RFD_API int rfd_align_detections_device(rfd_ctx *ctx, const rfd_image *imgs, int
  *         a. Normalise: e = emb[t] / |emb[t]| in the order of rfd_normalize_embeddings: lane l of 64 sums the squares of elements
  *            l, l + 64, ... in ascending order starting from 0 (a lane that owns no element holds 0), the 64 partial sums meet
  *            in the xor butterfly 32, 16, 8, 4, 2, 1 (s = s + partner's s), one sqrt, one division per element, every one an
- *            IEEE operation rounded to nearest.  rfd_normalize_embeddings takes its square root with the hardware's
- *            approximation, which is within one ulp; where that is the correctly rounded root, e has its bits.
+ *            IEEE operation rounded to nearest: e has the bits of rfd_normalize_embeddings.
  *         b. Bad input: the norm is zero or not finite, or w is not (finite and > 0): status 2 (RFD_TRACK_FUSE_BAD_INPUT),
  *            query[t] = e as computed, no state changes.
  *         c. No track: status 1 (RFD_TRACK_FUSE_NO_TRACK), query[t] = e, no state changes.

@@ -499,7 +499,9 @@ int launch_quality_decide(const float *logits, int n, int classes, float thresho
 
 // normalize_outputs, utils.rs:148-154: array / array.norm_l2().  One wave64 per row: lane l sums the squares of elements l,
 // l + 64, ... in ascending order, the 64 partial sums meet in a fixed xor butterfly (every lane ends with the same bits: IEEE
-// addition commutes), then one correctly rounded square root and one correctly rounded division per element.
+// addition commutes), then one correctly rounded square root and one correctly rounded division per element.  The square
+// root is the compiler's expansion around the hardware's approximation (__builtin_sqrtf): __fsqrt_rn is the bare hardware
+// instruction on this toolchain, one ulp off for some inputs (a subnormal sum of squares among them).
 __global__ void __launch_bounds__(256) l2_normalize_kernel(const float *emb, int n, int dim, float *out) // out may be emb
 {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -509,7 +511,7 @@ __global__ void __launch_bounds__(256) l2_normalize_kernel(const float *emb, int
     for (int i = lane; i < dim; i += 64) s = __fadd_rn(s, __fmul_rn(x[i], x[i]));
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) s = __fadd_rn(s, __shfl_xor(s, off, 64));
-    const float norm = __fsqrt_rn(s);
+    const float norm = __builtin_sqrtf(s);
     float *o = out + (size_t)row * dim;
     for (int i = lane; i < dim; i += 64) o[i] = __fdiv_rn(x[i], norm);
 }

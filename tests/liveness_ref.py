@@ -43,30 +43,35 @@ def f32_min(a, b):
     return a if a < b else b
 
 
-def scale_image_box(box):
-    """_get_scale_image :249-262 -> Rect (x, y, w, h)"""
+def scale_image_box(box, cast=as_i32, wrap=wrap_i32, trace=None):
+    """_get_scale_image :249-262 -> Rect (x, y, w, h).  cast / wrap: the two integer rules, replaceable by the mutation guards of
+    tests/liveness_cases.py; trace: a dict that receives the four f32 values in front of the casts"""
     with np.errstate(**_ERR):
         xmin, ymin, xmax, ymax = (f32(v) for v in box[:4])
         det_height = ymax - ymin
         c_x = (xmin + xmax) / f32(2.0)
-        left = as_i32(c_x - f32(0.47) * det_height)
-        right = as_i32(c_x + f32(0.47) * det_height)
-        return left, as_i32(ymin), wrap_i32(right - left + 1), as_i32(ymax - ymin + f32(1.0))
+        pre = (c_x - f32(0.47) * det_height, c_x + f32(0.47) * det_height, ymin, ymax - ymin + f32(1.0))
+        if trace is not None:
+            trace["crop"] = pre
+        left, right = cast(pre[0]), cast(pre[1])
+        return left, cast(pre[2]), wrap(right - left + 1), cast(pre[3])
 
 
-def new_box(src_w, src_h, bbox, scale_ori):
-    """_get_new_box :342-385 -> (ltx, lty, rbx, rby, weight, shifts); shifts names the `if`s that fired (for the tests)"""
+def new_box(src_w, src_h, bbox, scale_ori, cast=as_i32, trace=None):
+    """_get_new_box :342-385 -> (ltx, lty, rbx, rby, weight, shifts); shifts names the `if`s that fired (for the tests);
+    trace: a dict that receives the ratios, the scale and the corners before the shifts and in front of the casts"""
     x, y, box_w, box_h = bbox
     scale_ori = f32(scale_ori)
     with np.errstate(**_ERR):
         w1, h1 = i32_as_f32(src_w) - f32(1.0), i32_as_f32(src_h) - f32(1.0)
-        scale = f32_min(h1 / i32_as_f32(box_h), f32_min(w1 / i32_as_f32(box_w), scale_ori))
+        ratio_h, ratio_w = h1 / i32_as_f32(box_h), w1 / i32_as_f32(box_w)
+        scale = f32_min(ratio_h, f32_min(ratio_w, scale_ori))
         new_width, new_height = i32_as_f32(box_w) * scale, i32_as_f32(box_h) * scale
         center_x = i32_as_f32(box_w) / f32(2.0) + i32_as_f32(x)
         center_y = i32_as_f32(box_h) / f32(2.0) + i32_as_f32(y)
         ltx, lty = center_x - new_width / f32(2.0), center_y - new_height / f32(2.0)
         rbx, rby = center_x + new_width / f32(2.0), center_y + new_height / f32(2.0)
-        shifts = []
+        shifts, first = [], (ltx, lty, rbx, rby)
         if ltx < f32(0.0):
             rbx = rbx - ltx
             ltx = f32(0.0)
@@ -83,11 +88,13 @@ def new_box(src_w, src_h, bbox, scale_ori):
             lty = lty - (rby - i32_as_f32(src_h) + f32(1.0))
             rby = h1
             shifts.append("bottom")
-        return as_i32(ltx), as_i32(lty), as_i32(rbx), as_i32(rby), f32(scale / scale_ori), shifts
+        if trace is not None:
+            trace.update(ratio_h=ratio_h, ratio_w=ratio_w, scale=scale, w1=w1, h1=h1, first=first, corners=(ltx, lty, rbx, rby))
+        return cast(ltx), cast(lty), cast(rbx), cast(rby), f32(scale / scale_ori), shifts
 
 
-def roi_rect(ltx, lty, rbx, rby):
-    return ltx, lty, wrap_i32(rbx - ltx + 1), wrap_i32(rby - lty + 1)   # :323
+def roi_rect(ltx, lty, rbx, rby, wrap=wrap_i32):
+    return ltx, lty, wrap(rbx - ltx + 1), wrap(rby - lty + 1)   # :323
 
 
 def roi_ok(rect, src_w, src_h):
@@ -96,9 +103,9 @@ def roi_ok(rect, src_w, src_h):
     return x >= 0 and y >= 0 and w > 0 and h > 0 and x + w <= src_w and y + h <= src_h
 
 
-def face(frame, box, found, scales=DEFAULT_SCALES, sizes=DEFAULT_SIZES, oracle=None):
+def face(frame, box, found, scales=DEFAULT_SCALES, sizes=DEFAULT_SIZES, oracle=None, cast=as_i32, wrap=wrap_i32, traces=None):
     """One face = a single-image call of the reference.  -> dict(tensors [k] of [3, out_h, out_w] f32 (or None without an
-    oracle), weights [k] f32, rois [k, 4] i32, status, shifts [k] lists)"""
+    oracle), weights [k] f32, rois [k, 4] i32, status, shifts [k] lists).  traces: a list that receives one dict per model"""
     k = len(scales)
     src_h, src_w = frame.shape[:2]
     rois, weights, shifts = np.zeros((k, 4), np.int32), np.zeros(k, np.float32), [[] for _ in range(k)]
@@ -106,12 +113,17 @@ def face(frame, box, found, scales=DEFAULT_SCALES, sizes=DEFAULT_SIZES, oracle=N
     if not (int(found) & 1):
         status = -2
     else:
-        bbox = scale_image_box(box)
+        crop = {}
+        bbox = scale_image_box(box, cast, wrap, crop)
         for j in range(k):
-            ltx, lty, rbx, rby, weights[j], shifts[j] = new_box(src_w, src_h, bbox, scales[j])
-            rois[j] = ltx, lty, rbx, rby
-            if not roi_ok(roi_rect(ltx, lty, rbx, rby), src_w, src_h):
+            tr = dict(crop, bbox=bbox)
+            ltx, lty, rbx, rby, weights[j], shifts[j] = new_box(src_w, src_h, bbox, scales[j], cast, tr)
+            rois[j] = wrap_i32(ltx), wrap_i32(lty), wrap_i32(rbx), wrap_i32(rby)   # (only a mutated cast leaves the i32 range)
+            tr["rect"] = roi_rect(ltx, lty, rbx, rby, wrap)
+            if not roi_ok(tr["rect"], src_w, src_h):
                 status = -3   # the reference returns Err for the whole face (:324-337)
+            if traces is not None:
+                traces.append(tr)
     tensors = None
     if oracle is not None:
         tensors = []
