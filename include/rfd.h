@@ -1219,8 +1219,8 @@ RFD_API int rfd_align_detections_device(rfd_ctx *ctx, const rfd_image *imgs, int
  *      on a tracker without identities enabled; RFD_ERR_CAPACITY for a state above 1 GiB (streams * max_tracks * dim * 4) and
  *      for n > max_batch_size.  n = 0 or m = 0 is a no-op; nothing is enqueued when a check fails.  Nothing here is atomic or
  *      order-dependent: the same bits on every run.
- *      Out of scope: the identity of tracks at the moment they end (the `ended` serials), saving the state to a file,
- *      cross-camera linking, a decay of old shots, and any change to DUE. ---- */
+ *      Out of scope: saving the state to a file, cross-camera linking, a decay of old shots, and any change to DUE.  (The
+ *      identity of a track at the moment it ends is in its record: "track shots" below.) ---- */
 #define RFD_TRACK_NAMED 8u
 #define RFD_TRACK_FUSE_OK 0
 #define RFD_TRACK_FUSE_NO_TRACK 1
@@ -1271,6 +1271,131 @@ RFD_API int rfd_tracker_get_identities(rfd_tracker *t, int stream, rfd_track_ide
 /* The template S[dim] of the live track `serial` of `stream`; RFD_ERR_INVALID_ARG ("no such track") when no live slot holds
  * that serial or its entry is stale.  Waits for the stream. */
 RFD_API int rfd_tracker_get_template(rfd_tracker *t, int stream, int32_t serial, float *out);
+
+/* ---- track shots: the best aligned crop of every track kept on the device, and ended tracks listed as records.  No counterpart
+ *      in the reference, which sees one image.  The product of a door camera is one record per visit: who it was, when, and the
+ *      best picture as a JPEG file.  The aligned crop of a due face lives in rfd_face_list.crops for one call, and a track that
+ *      ends leaves only its serial in `ended`; without this section a caller copies every due crop to the host on every call and
+ *      joins crops, due_track and ended by (stream, serial) there.  With it
+ *        detect -> shot quality -> track -> COLLECT -> align the due faces -> KEEP -> (models) -> fuse -> search -> label -> who
+ *        -> redact -> rfd_encode_jpeg_batch_device of the records' crops
+ *      is one stream order with a single wait at the end: rfd_track_records.crops is laid out as the encoder's crops are and
+ *      rfd_track_records.total is a ready count_dev.
+ *
+ *      State.  rfd_tracker_shots_enable allocates, once per tracker, [streams][max_tracks] heads {serial, shots, kept, q,
+ *      first_stamp, best_stamp} (32 bytes, all zero) and one crop of crop_w * crop_h * 3 bytes beside each.  Entry j of stream s
+ *      belongs to the track in slot j ONLY WHILE head.serial == slot.serial; otherwise it is STALE, exactly as for the track
+ *      identities, and it is cleared the first time a shot of the slot's new track is kept.  Hence the tracker's update kernel,
+ *      its slots, rfd_tracker_config, rfd_track_out and rfd_track are untouched by this section, and rfd_tracker_reset needs no
+ *      change either: the tracks it removes take their serials with them (and get no record: they have no `ended` entry).  A
+ *      tracker that never enables shots launches and allocates what it always did.  `stream` and `stamp` are host arrays [n]
+ *      that travel through a ring of page-locked slots owned by this state, so the tracker's own ring stays as it is and no call
+ *      waits for the context's stream.  stamp[b] is the caller's time of frame b, any int64 (NULL: 0 for every frame); it is
+ *      stored and handed back, never interpreted.
+ *
+ *      1. Keep (rfd_tracker_keep_shots_device).  The observations are rfd_track_obs, and the count, the ownership of
+ *         observations by frames, the lookup of the track, the groups and the order are the fuse call's, word for word: count =
+ *         total ? min(max(total[0], 0), m) : m; frame b owns t in [max(first[b], 0), min(first[b + 1], count)); observation t of
+ *         frame b is the track (stream[b], serial[b][row[t]]), found by its serial among the stream's slots AT THE TIME THE
+ *         KERNEL RUNS, at the lowest slot that holds it.  A track that has ended, serial 0 or a row outside [0, max_det) is "no
+ *         track".  The observations of one stream are processed in the call order of its frames and in ascending t within a
+ *         frame; streams are independent.  crops [m][crop_h][crop_w][3] u8 (rfd_face_list.crops, any byte address);
+ *         face_status [m] int32 or NULL (rfd_face_list.status); q [m] f32 or NULL; status [m] int32 is written.  The natural
+ *         sources of q: the score array of rfd_quality_decide_device (the remote quality model), as for `weight` in fuse; or
+ *         NULL, since by the tracker's DUE rule every later due shot already beat the last one by `improve`.
+ *         For observation t of frame b:
+ *         a. face_status given and face_status[t] < 0 (the alignment zero-filled the crop), or q given and q[t] is NaN: status 2
+ *            (RFD_TRACK_SHOT_BAD_INPUT), nothing changes.
+ *         b. No track: status 1 (RFD_TRACK_SHOT_NO_TRACK), nothing changes.
+ *         c. A stale entry is cleared first: serial = the track's, shots 0, kept 0, q -inf, first_stamp = stamp[b], best_stamp 0.
+ *         d. shots += 1.  The shot is KEPT if and only if kept == 0, or q is NULL, or q[t] > head.q (one f32 comparison: an equal
+ *            q keeps the earlier shot).  If kept: crop t becomes the entry's crop, head.q = q ? q[t] : 0.0f, best_stamp =
+ *            stamp[b], kept += 1, status 0 (RFD_TRACK_SHOT_KEPT).  Otherwise status 3 (RFD_TRACK_SHOT_PASSED).
+ *         A later kept observation of the same track in the same call supersedes the earlier one; both get status 0.  Splitting
+ *         the observations of a stream over calls in any way that keeps their order gives the same state, byte for byte.  status
+ *         at or past the count stays as passed.
+ *      2. Collect (rfd_tracker_collect_ended_device).  stats [n][4] and ended [n][max_tracks] as rfd_track_out holds them.  For
+ *         frame b in the call order of frames, then entries e = 0 .. min(max(stats[b][2], 0), max_tracks) - 1 of ended[b] in
+ *         order: the serial ended[b][e] is looked up among the HEADS of stream[b] (the lowest j with head.serial == serial; serial
+ *         0 never matches) -- the slot no longer holds the track, so the lookup cannot go through the slots.  If found it is a
+ *         record; if not, the entry is skipped and no record is written (the track never had a kept shot, or its entry was
+ *         already taken by a later track because the call came too late).  c[b] is the number of records of frame b; first[b] =
+ *         c[0] + .. + c[b-1], first[n] = total[0], both untruncated, as in the face list.  Records r >= cap are dropped.  EVERY
+ *         rec AND crops ROW AT OR PAST min(total, cap) IS LEFT EXACTLY AS PASSED.  Record r holds the head's fields (serial,
+ *         shots, kept, q, first_stamp, best_stamp), stream = stream[b], frame = b, end_stamp = stamp[b], reserved = 0, and the
+ *         stored crop in crops[r] (unless crops is NULL).  If identities are enabled and a head of the identity state of
+ *         stream[b] holds the same serial (the lowest such j), the record has that head's identity, row, score, named, shots and
+ *         weight as identity, row, id_score, named, id_shots, id_weight; otherwise -1, -1, -inf, 0, 0, 0.  Collect reads the
+ *         state and changes nothing in it.
+ *         WHERE THE CALL BELONGS: directly behind the rfd_tracker_update_device whose `ended` it reads, BEFORE that call's align
+ *         -> keep -> fuse.  Two consequences: a slot reborn in the same frame still yields its old track's record (the new
+ *         track's first keep, which clears the entry, comes later); and a track whose only due shot arrives after it ended has
+ *         none (that keep is "no track").
+ *      3. Readers, both waiting for the stream: rfd_tracker_get_shots lists the entries of the live slots that are not stale;
+ *         rfd_tracker_get_shot_crop copies the stored crop of a live track.
+ *
+ *      Errors: RFD_ERR_INVALID_ARG with the field named in rfd_last_error() for every bound in the config comments, a non-zero
+ *      reserved, enabling twice, a NULL required pointer, m < 0, cap < 1, a stream outside [0, streams), and for every call of
+ *      this section on a tracker without shots enabled; RFD_ERR_CAPACITY for a bank above 1 GiB (streams * max_tracks * crop_w
+ *      * crop_h * 3) and for n > max_batch_size.  n = 0 is a no-op, and so is m = 0 for keep; nothing is enqueued when a check
+ *      fails.  Nothing here is atomic or order-dependent: the same bytes on every run.
+ *      Out of scope: any change to the tracker's update or to DUE, saving the bank to a file, a device-side peek at the crops
+ *      of live tracks (the two readers wait for the stream), source-frame context around the face (encode a rectangle of the
+ *      frame for that), and cross-camera linking. ---- */
+#define RFD_TRACK_SHOT_KEPT 0      /* the crop is now the track's stored shot */
+#define RFD_TRACK_SHOT_NO_TRACK 1
+#define RFD_TRACK_SHOT_BAD_INPUT 2
+#define RFD_TRACK_SHOT_PASSED 3    /* a valid shot, not better than the stored one */
+typedef struct rfd_track_shot_config {
+    int32_t crop_w, crop_h;   /* 1..1024 each: rfd_alignment_config.out_w / out_h of the crops that will be kept */
+    int32_t reserved[6];      /* 0 */
+} rfd_track_shot_config;      /* 32 bytes; default 112, 112 */
+typedef struct rfd_track_shot {      /* 40 bytes */
+    int32_t slot, serial;
+    int32_t shots, kept;             /* valid observations seen; times the stored crop was replaced */
+    float   q;
+    int32_t reserved;
+    int64_t first_stamp, best_stamp;
+} rfd_track_shot;
+typedef struct rfd_track_record {    /* 80 bytes */
+    int32_t stream, serial, frame;   /* frame: index b of the call's frame whose update ended the track */
+    int32_t shots, kept;
+    float   q;
+    int64_t first_stamp, best_stamp, end_stamp;
+    int32_t identity, row;
+    float   id_score;
+    int32_t named, id_shots;
+    float   id_weight;
+    int32_t reserved[2];             /* written as 0 */
+} rfd_track_record;
+typedef struct rfd_track_records {
+    int32_t *total;          /* [1]   untruncated number of records */
+    int32_t *first;          /* [n+1] records of frame b are [first[b], first[b+1]) */
+    rfd_track_record *rec;   /* [cap] */
+    uint8_t *crops;          /* [cap][crop_h][crop_w][3], may be NULL */
+} rfd_track_records;
+RFD_API int rfd_track_shot_config_default(rfd_track_shot_config *cfg);
+/* cfg NULL: the default.  Once per tracker; the fill of the heads is enqueued in stream order. */
+RFD_API int rfd_tracker_shots_enable(rfd_tracker *t, const rfd_track_shot_config *cfg);
+/* stream: host [n]; stamp: host int64 [n] or NULL; every pointer of obs, crops, face_status, q, status: DEVICE.  Enqueued on the
+ * context's stream with no host wait; async = 0 returns after the stream has drained, any other value at once. */
+RFD_API int rfd_tracker_keep_shots_device(rfd_tracker *t, const int32_t *stream, const int64_t *stamp, int n, const rfd_track_obs *obs, int m,
+                                          const uint8_t *crops, const int32_t *face_status, const float *q, int32_t *status, int async);
+/* stats, ended and every pointer of out: DEVICE; total, first and rec are required. */
+RFD_API int rfd_tracker_collect_ended_device(rfd_tracker *t, const int32_t *stream, const int64_t *stamp, int n, const int32_t *stats,
+                                             const int32_t *ended, int cap, const rfd_track_records *out, int async);
+/* Stage-level: the same with host pointers, through the same kernels; synchronous.  The output arrays travel to the device
+ * and back whole, so what they held past the counts comes back as it was. */
+RFD_API int rfd_tracker_keep_shots(rfd_tracker *t, const int32_t *stream, const int64_t *stamp, int n, const rfd_track_obs *obs, int m,
+                                   const uint8_t *crops, const int32_t *face_status, const float *q, int32_t *status);
+RFD_API int rfd_tracker_collect_ended(rfd_tracker *t, const int32_t *stream, const int64_t *stamp, int n, const int32_t *stats,
+                                      const int32_t *ended, int cap, const rfd_track_records *out);
+/* The entries of the live slots of `stream` that are not stale, in ascending slot order: at most cap of them into out (may be
+ * NULL when cap is 0); *count = how many there are, also when that exceeds cap.  Waits for the stream. */
+RFD_API int rfd_tracker_get_shots(rfd_tracker *t, int stream, rfd_track_shot *out, int cap, int *count);
+/* The stored crop [crop_h][crop_w][3] of the live track `serial` of `stream`; RFD_ERR_INVALID_ARG ("no such track") when no live
+ * slot holds that serial or its entry is stale.  Waits for the stream. */
+RFD_API int rfd_tracker_get_shot_crop(rfd_tracker *t, int stream, int32_t serial, uint8_t *out);
 
 /* ---- shot quality: a figure of merit in [0, 1] for every detection row, on the device, from the pixels under its box and its
  *      landmarks.  No counterpart in the reference.  It fills the quality[n][max_det] array that rfd_tracker_update_device reads,

@@ -913,6 +913,97 @@ class Tracker {
         return out;
     }
 
+    // ---- track shots (rfd.h, "track shots"): the best aligned crop of every track, ended tracks as records ----
+    static rfd_track_shot_config default_shot_config()
+    {
+        rfd_track_shot_config c;
+        check(rfd_track_shot_config_default(&c));
+        return c;
+    }
+    // once per tracker
+    void enable_shots(const rfd_track_shot_config &cfg)
+    {
+        check(rfd_tracker_shots_enable(t_, &cfg));
+        shot_cfg_ = cfg;
+    }
+    void enable_shots() { enable_shots(default_shot_config()); }
+    const rfd_track_shot_config &shot_config() const { return shot_cfg_; }
+    std::size_t shot_bytes() const { return (std::size_t)shot_cfg_.crop_w * (std::size_t)shot_cfg_.crop_h * 3; }
+    // crops: [m][crop_h][crop_w][3], the aligned crop of each observation; face_status: [m] or empty; q: [m] or empty (every
+    // valid shot is kept); stamps: one per frame or empty for 0 -> [m] RFD_TRACK_SHOT_*
+    std::vector<int32_t> keep_shots(const std::vector<int32_t> &streams, const std::vector<Observation> &obs, const std::vector<uint8_t> &crops,
+                                    const std::vector<float> &q = {}, const std::vector<int32_t> &face_status = {},
+                                    const std::vector<int64_t> &stamps = {})
+    {
+        const std::size_t m = obs.size();
+        if (crops.size() != m * shot_bytes() || (!q.empty() && q.size() != m) || (!face_status.empty() && face_status.size() != m) ||
+            (!stamps.empty() && stamps.size() != streams.size()))
+            throw Error(RFD_ERR_INVALID_ARG, "tracker - a crop (and q, face status) per observation, a stamp per frame");
+        ObsArrays a = obs_arrays(streams, obs);
+        std::vector<int32_t> status(m, RFD_TRACK_SHOT_NO_TRACK);
+        const rfd_track_obs o{nullptr, a.first.data(), a.row.data(), a.serial.data()};
+        check(rfd_tracker_keep_shots(t_, streams.data(), stamps.empty() ? nullptr : stamps.data(), (int)streams.size(), &o, (int)m, crops.data(),
+                                     face_status.empty() ? nullptr : face_status.data(), q.empty() ? nullptr : q.data(), status.data()));
+        return status;
+    }
+    // the records of the tracks that `frames` (what update returned for the same streams) ended, with their crops
+    struct Records {
+        int total = 0;                       // untruncated
+        std::vector<int32_t> first;          // [n + 1]
+        std::vector<rfd_track_record> rec;   // [min(total, cap)]
+        std::vector<uint8_t> crops;          // [min(total, cap)][crop_h][crop_w][3]
+    };
+    Records collect_ended(const std::vector<int32_t> &streams, const std::vector<Frame> &frames, int cap, const std::vector<int64_t> &stamps = {})
+    {
+        const std::size_t n = frames.size(), mt = (std::size_t)cfg_.max_tracks;
+        if (streams.size() != n || (!stamps.empty() && stamps.size() != n) || cap < 1) throw Error(RFD_ERR_INVALID_ARG, "tracker - one stream (and stamp) per frame, cap >= 1");
+        std::vector<int32_t> stats(n * 4, 0), ended(n * mt, 0);
+        for (std::size_t i = 0; i < n; ++i) {
+            const std::size_t k = std::min(frames[i].ended.size(), mt);
+            stats[i * 4 + 2] = (int32_t)k;
+            std::copy(frames[i].ended.begin(), frames[i].ended.begin() + (std::ptrdiff_t)k, ended.begin() + (std::ptrdiff_t)(i * mt));
+        }
+        Records out;
+        out.first.assign(n + 1, 0);
+        out.rec.resize((std::size_t)cap);
+        out.crops.resize((std::size_t)cap * shot_bytes());
+        int32_t total = 0;
+        const rfd_track_records r{&total, out.first.data(), out.rec.data(), out.crops.data()};
+        check(rfd_tracker_collect_ended(t_, streams.data(), stamps.empty() ? nullptr : stamps.data(), (int)n, stats.data(), ended.data(), cap, &r));
+        out.total = total;
+        const std::size_t have = (std::size_t)std::min(std::max(total, 0), cap);
+        out.rec.resize(have);
+        out.crops.resize(have * shot_bytes());
+        return out;
+    }
+    // DEVICE pointers throughout (stream list and stamps: host), enqueued on the detector's stream; async: no host synchronisation
+    void keep_shots_device(const std::vector<int32_t> &streams, const int64_t *stamps, const rfd_track_obs &obs, int m, const uint8_t *crops,
+                           const int32_t *face_status, const float *q, int32_t *status, bool async = false)
+    {
+        check(rfd_tracker_keep_shots_device(t_, streams.data(), stamps, (int)streams.size(), &obs, m, crops, face_status, q, status, async ? 1 : 0));
+    }
+    void collect_ended_device(const std::vector<int32_t> &streams, const int64_t *stamps, const int32_t *stats, const int32_t *ended, int cap,
+                              const rfd_track_records &out, bool async = false)
+    {
+        check(rfd_tracker_collect_ended_device(t_, streams.data(), stamps, (int)streams.size(), stats, ended, cap, &out, async ? 1 : 0));
+    }
+    // the entries of the live tracks of a stream that have a kept shot, in ascending slot order (waits for the stream)
+    std::vector<rfd_track_shot> shots(int stream)
+    {
+        int n = 0;
+        check(rfd_tracker_get_shots(t_, stream, nullptr, 0, &n));
+        std::vector<rfd_track_shot> out((std::size_t)n);
+        check(rfd_tracker_get_shots(t_, stream, out.data(), n, &n));
+        return out;
+    }
+    // the stored crop of a live track; throws for "no such track"
+    std::vector<uint8_t> shot_crop(int stream, int32_t serial)
+    {
+        std::vector<uint8_t> out(shot_bytes());
+        check(rfd_tracker_get_shot_crop(t_, stream, serial, out.data()));
+        return out;
+    }
+
   private:
     struct ObsArrays {
         std::vector<int32_t> first, row, serial;
@@ -935,6 +1026,7 @@ class Tracker {
     std::size_t max_det_ = 0;
     rfd_tracker_config cfg_{};
     rfd_track_identity_config id_cfg_{};
+    rfd_track_shot_config shot_cfg_{};
 };
 
 // The device-resident form of the face list over caller-made DEVICE slabs (rfd_align_detections_device): with a tracker's

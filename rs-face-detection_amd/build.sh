@@ -31,3 +31,6 @@ echo "built $OBJ/tracker_demo"
 # the track identities through include/rfd.hpp (tests/test_track_identity_cpp_gpu.py)
 g++ -std=c++17 -O2 -Wall -I"$HERE/../include" "$HERE/../tests/cpp/track_identity_demo.cpp" -o "$OBJ/track_identity_demo" -L"$HERE" -lrfd_hip -Wl,-rpath,'$ORIGIN/..' -Wl,-rpath,"$HERE" -Wl,-rpath,/opt/rocm/lib
 echo "built $OBJ/track_identity_demo"
+# the track shots through include/rfd.hpp (tests/test_track_shots_cpp_gpu.py)
+g++ -std=c++17 -O2 -Wall -I"$HERE/../include" "$HERE/../tests/cpp/track_shots_demo.cpp" -o "$OBJ/track_shots_demo" -L"$HERE" -lrfd_hip -Wl,-rpath,'$ORIGIN/..' -Wl,-rpath,"$HERE" -Wl,-rpath,/opt/rocm/lib
+echo "built $OBJ/track_shots_demo"

@@ -5,6 +5,7 @@
 #include "host_resources.h"
 #include "track_plan.h"
 #include "track_identity_host.h" // TrackIdentityState: empty unless identities are enabled
+#include "track_shots_host.h"    // TrackShotState: empty unless shots are enabled
 
 namespace rfd {
 
@@ -64,4 +65,6 @@ struct rfd_tracker {
         h_due_total, h_due_track;
     // the track identities (track_identity_host.hip): nothing is allocated before rfd_tracker_identity_enable
     rfd::TrackIdentityState ident;
+    // the track shots (track_shots_host.hip): nothing is allocated before rfd_tracker_shots_enable
+    rfd::TrackShotState shots;
 };

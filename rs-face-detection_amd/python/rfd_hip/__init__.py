@@ -171,6 +171,26 @@ class rfd_track_identity(C.Structure):
                 ("named", C.c_int32), ("shots", C.c_int32), ("weight", C.c_float)]
 
 
+class rfd_track_shot_config(C.Structure):
+    _fields_ = [("crop_w", C.c_int32), ("crop_h", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class rfd_track_shot(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("serial", C.c_int32), ("shots", C.c_int32), ("kept", C.c_int32), ("q", C.c_float),
+                ("reserved", C.c_int32), ("first_stamp", C.c_int64), ("best_stamp", C.c_int64)]
+
+
+class rfd_track_record(C.Structure):
+    _fields_ = [("stream", C.c_int32), ("serial", C.c_int32), ("frame", C.c_int32), ("shots", C.c_int32), ("kept", C.c_int32),
+                ("q", C.c_float), ("first_stamp", C.c_int64), ("best_stamp", C.c_int64), ("end_stamp", C.c_int64),
+                ("identity", C.c_int32), ("row", C.c_int32), ("id_score", C.c_float), ("named", C.c_int32), ("id_shots", C.c_int32),
+                ("id_weight", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+class rfd_track_records(C.Structure):
+    _fields_ = [("total", C.c_void_p), ("first", C.c_void_p), ("rec", C.c_void_p), ("crops", C.c_void_p)]
+
+
 class rfd_shot_quality_config(C.Structure):
     _fields_ = [("dark", C.c_int32), ("bright", C.c_int32), ("pitch0", C.c_float), ("w_yaw", C.c_float), ("w_roll", C.c_float),
                 ("w_pitch", C.c_float), ("sharp_ref", C.c_float), ("size_ref", C.c_float), ("times_score", C.c_int32),
@@ -256,6 +276,8 @@ API_SYMBOLS = [
     "rfd_track_identity_config_default", "rfd_tracker_identity_enable", "rfd_tracker_fuse_device", "rfd_tracker_label_device",
     "rfd_tracker_who_device", "rfd_tracker_fuse", "rfd_tracker_label", "rfd_tracker_who", "rfd_tracker_get_identities",
     "rfd_tracker_get_template",
+    "rfd_track_shot_config_default", "rfd_tracker_shots_enable", "rfd_tracker_keep_shots_device", "rfd_tracker_collect_ended_device",
+    "rfd_tracker_keep_shots", "rfd_tracker_collect_ended", "rfd_tracker_get_shots", "rfd_tracker_get_shot_crop",
     "rfd_shot_quality_config_default", "rfd_shot_quality_device", "rfd_shot_quality",
     "rfd_frame_layout_of", "rfd_convert_frames_device", "rfd_upload_frames_device", "rfd_convert_frames",
     "rfd_jpeg_encode_config_default", "rfd_jpeg_encode_bound", "rfd_jpeg_encode_header", "rfd_encode_jpeg_batch_device", "rfd_encode_jpeg_batch",
@@ -444,6 +466,14 @@ def load_library(path=None):
     L.rfd_tracker_who.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp]
     L.rfd_tracker_get_identities.argtypes = [vp, ci, C.POINTER(rfd_track_identity), ci, C.POINTER(ci)]
     L.rfd_tracker_get_template.argtypes = [vp, ci, C.c_int32, vp]
+    L.rfd_track_shot_config_default.argtypes = [C.POINTER(rfd_track_shot_config)]
+    L.rfd_tracker_shots_enable.argtypes = [vp, C.POINTER(rfd_track_shot_config)]
+    L.rfd_tracker_keep_shots_device.argtypes = [vp, vp, vp, ci, C.POINTER(rfd_track_obs), ci, vp, vp, vp, vp, ci]
+    L.rfd_tracker_collect_ended_device.argtypes = [vp, vp, vp, ci, vp, vp, ci, C.POINTER(rfd_track_records), ci]
+    L.rfd_tracker_keep_shots.argtypes = [vp, vp, vp, ci, C.POINTER(rfd_track_obs), ci, vp, vp, vp, vp]
+    L.rfd_tracker_collect_ended.argtypes = [vp, vp, vp, ci, vp, vp, ci, C.POINTER(rfd_track_records)]
+    L.rfd_tracker_get_shots.argtypes = [vp, ci, C.POINTER(rfd_track_shot), ci, C.POINTER(ci)]
+    L.rfd_tracker_get_shot_crop.argtypes = [vp, ci, C.c_int32, vp]
     L.rfd_align_detections_device.argtypes = [vp, C.POINTER(rfd_image), ci, C.POINTER(rfd_dets), vp, vp, vp, ci, ci, C.POINTER(rfd_face_list), ci]
     L.rfd_shot_quality_config_default.argtypes = [C.POINTER(rfd_shot_quality_config)]
     L.rfd_shot_quality_device.argtypes = [vp, C.POINTER(rfd_image), ci, C.POINTER(rfd_dets), C.POINTER(rfd_shot_quality_config), vp, vp, vp, ci]
@@ -1220,6 +1250,101 @@ class Tracker:
         out = np.zeros(self.identity_cfg.dim, np.float32)
         _check(self._L.rfd_tracker_get_template(self._t, int(stream), int(serial), out.ctypes.data))
         return out
+
+
+    # ---- track shots (rfd.h, "track shots") ----
+    def enable_shots(self, cfg=None, **fields):
+        """rfd_tracker_shots_enable, once per tracker: cfg, or the default (112 x 112 crops) with `fields` replaced"""
+        self.shot_cfg = cfg if cfg is not None else track_shot_config(**fields)
+        _check(self._L.rfd_tracker_shots_enable(self._t, C.byref(self.shot_cfg)))
+        return self.shot_cfg
+
+    @staticmethod
+    def _stamps(stamp, n):
+        return None if stamp is None else np.ascontiguousarray(stamp, np.int64).reshape(n)
+
+    def keep_shots(self, streams, first, row, serial, crops, stamp=None, face_status=None, q=None, total=None, status=None):
+        """the host form of rfd_tracker_keep_shots: streams [n]; stamp [n] int64 or None; first [n + 1], row [m], total (an int or
+        None) as a FaceList holds them, serial [n, max_det] as TrackOut.due_track; crops [m, crop_h, crop_w, 3] uint8; face_status
+        [m] int32 or None; q [m] f32 or None -> status [m] int32.  status: a caller-made array to write into (rows at or past the
+        count keep what they hold)"""
+        s = self._streams(streams)
+        keep, obs, m = self._obs(len(s), first, row, serial, total)
+        st = self._stamps(stamp, len(s))
+        c = np.ascontiguousarray(crops, np.uint8).reshape(m, self.shot_cfg.crop_h, self.shot_cfg.crop_w, 3)
+        fs = None if face_status is None else np.ascontiguousarray(face_status, np.int32).reshape(m)
+        qq = None if q is None else np.ascontiguousarray(q, np.float32).reshape(m)
+        status = np.zeros(m, np.int32) if status is None else status
+        assert status.dtype == np.int32 and status.shape == (m,) and status.flags.c_contiguous
+        p = lambda a: None if a is None else a.ctypes.data
+        _check(self._L.rfd_tracker_keep_shots(self._t, s.ctypes.data, p(st), len(s), C.byref(obs), m, c.ctypes.data, p(fs), p(qq),
+                                              status.ctypes.data))
+        return status
+
+    def keep_shots_device(self, streams, obs, m, crops_ptr, status_ptr, stamp=None, face_status_ptr=None, q_ptr=None, async_=False):
+        """the same from raw device addresses; obs: an rfd_track_obs of device addresses.  Enqueued on the detector's stream, with
+        no host synchronisation when async_ is set"""
+        s = self._streams(streams)
+        st = self._stamps(stamp, len(s))
+        _check(self._L.rfd_tracker_keep_shots_device(self._t, s.ctypes.data, None if st is None else st.ctypes.data, len(s), C.byref(obs),
+                                                     int(m), crops_ptr, face_status_ptr, q_ptr, status_ptr, int(async_)))
+
+    def collect_ended(self, streams, stats, ended, cap, stamp=None, total=None, first=None, rec=None, crops=None, with_crops=True):
+        """the host form of rfd_tracker_collect_ended: stats [n, 4] and ended [n, max_tracks] as TrackOut holds them -> (total [1]
+        int32, first [n + 1] int32, rec: a ctypes array of cap rfd_track_record, crops [cap, crop_h, crop_w, 3] uint8 or None).
+        total / first / rec / crops: caller-made ones to write into (rows at or past min(total, cap) keep what they hold); rec may
+        also be a numpy array of cap 80-byte items"""
+        s = self._streams(streams)
+        n, cap = len(s), int(cap)
+        st = self._stamps(stamp, n)
+        sa = np.ascontiguousarray(stats, np.int32).reshape(n, 4)
+        en = np.ascontiguousarray(ended, np.int32).reshape(n, self.cfg.max_tracks)
+        total = np.zeros(1, np.int32) if total is None else total
+        first = np.zeros(n + 1, np.int32) if first is None else first
+        rec = (rfd_track_record * max(cap, 1))() if rec is None else rec
+        if crops is None and with_crops:
+            crops = np.zeros((max(cap, 1), self.shot_cfg.crop_h, self.shot_cfg.crop_w, 3), np.uint8)
+        rec_ptr = rec.ctypes.data if isinstance(rec, np.ndarray) else C.addressof(rec)
+        out = rfd_track_records(total.ctypes.data, first.ctypes.data, rec_ptr, None if crops is None else crops.ctypes.data)
+        _check(self._L.rfd_tracker_collect_ended(self._t, s.ctypes.data, None if st is None else st.ctypes.data, n, sa.ctypes.data,
+                                                 en.ctypes.data, cap, C.byref(out)))
+        return total, first, rec, crops
+
+    def collect_ended_device(self, streams, stats_ptr, ended_ptr, cap, out, stamp=None, async_=False):
+        """the same from raw device addresses; out: an rfd_track_records of device addresses"""
+        s = self._streams(streams)
+        st = self._stamps(stamp, len(s))
+        _check(self._L.rfd_tracker_collect_ended_device(self._t, s.ctypes.data, None if st is None else st.ctypes.data, len(s), stats_ptr,
+                                                        ended_ptr, int(cap), C.byref(out), int(async_)))
+
+    def shots(self, stream):
+        """the entries of the live tracks of a stream that have a kept shot, in ascending slot order, as rfd_track_shot structures
+        (waits for the stream)"""
+        n = C.c_int(0)
+        _check(self._L.rfd_tracker_get_shots(self._t, int(stream), None, 0, C.byref(n)))
+        arr = (rfd_track_shot * max(n.value, 1))()
+        _check(self._L.rfd_tracker_get_shots(self._t, int(stream), arr, n.value, C.byref(n)))
+        return list(arr[:n.value])
+
+    def shot_crop(self, stream, serial):
+        """the stored crop [crop_h, crop_w, 3] uint8 of a live track (waits for the stream); an unknown serial raises"""
+        out = np.zeros((self.shot_cfg.crop_h, self.shot_cfg.crop_w, 3), np.uint8)
+        _check(self._L.rfd_tracker_get_shot_crop(self._t, int(stream), int(serial), out.ctypes.data))
+        return out
+
+
+TRACK_SHOT_KEPT, TRACK_SHOT_NO_TRACK, TRACK_SHOT_BAD_INPUT, TRACK_SHOT_PASSED = 0, 1, 2, 3   # RFD_TRACK_SHOT_*: keep's status
+
+
+def track_shot_config(**fields):
+    """rfd_track_shot_config: the default (112 x 112 crops) with the given fields replaced"""
+    c = rfd_track_shot_config()
+    _check(load_library().rfd_track_shot_config_default(C.byref(c)))
+    for k, v in fields.items():
+        if k not in dict(rfd_track_shot_config._fields_) or k == "reserved":
+            raise TypeError("rfd_track_shot_config has no field %r" % k)
+        setattr(c, k, v)
+    return c
 
 
 TRACK_NAMED = 8                                   # RFD_TRACK_NAMED: the bit rfd_tracker_who adds to a row's flags
