@@ -1646,7 +1646,7 @@ RFD_API int rfd_debug_jpeg_encode_coefficients(rfd_ctx *ctx, const int16_t *coef
  *                non-skipped rows of frame b, written for every b < n.
  *
  *      Limits.  One cell size per call (no per-face cells), no Gaussian or box blur (a blur needs a halo and an out-of-place
- *      source), no outlines or landmarks drawn, and sel is the caller's: the library does not derive it from gallery results.
+ *      source), no outlines or landmarks drawn (that is "annotation" below), and sel is the caller's: the library does not derive it from gallery results.
  *      PIXELATION WITH A FIXED CELL IS WEAK ON VERY LARGE FACES (a 400-pixel face at cell 16 keeps 25 x 25 samples); FILL is the mode
  *      that guarantees removal.  The defaults (rfd_redact_config_default) are CHOSEN values, not tuned on data.
  *      Errors, all with nothing enqueued: RFD_ERR_INVALID_ARG with the field named in rfd_last_error() for every bound in the
@@ -1684,6 +1684,89 @@ RFD_API int rfd_redact_faces_device(rfd_ctx *ctx, const rfd_image *imgs, const r
  * imgs[i] when dst is NULL, written through the same const cast) come back with one 2-D copy of 3 * W bytes per row. */
 RFD_API int rfd_redact_faces(rfd_ctx *ctx, const rfd_image *imgs, const rfd_image *dst, int n, const rfd_dets *dets, const uint32_t *sel,
                              const rfd_redact_config *cfg, int32_t *applied);
+
+/* ---- annotation: box outlines, the five landmarks and a text label ("17 83%") drawn into BGR frames on the device, so a frame
+ *      can SHOW what the pipeline decided without a round trip through the host.  No counterpart in the reference.  detect -> ...
+ *      -> who -> redact (out of place) -> annotate (in place on that dst) -> rfd_encode_jpeg_batch_device is one stream order with
+ *      no host wait.  sel is the tracker's flags or `who`, label is `identity` (or a serial's low bits), value is `id_score` or a
+ *      quality figure; the library derives none of them.
+ *
+ *      The rule, for frame b (H x W, BGR u8, byte stride).  Every step is an integer, or one IEEE f32 operation in the written order
+ *      with no contraction; as_i32 is the redaction's (toward zero, saturating, NaN -> 0).
+ *      Rows and styles.  Row i < min(max(count[b], 0), max_det).  Word s = sel ? sel[b][i] : 0.  The row takes the FIRST style k <
+ *                n_styles with (s & mask_k) == value_k; a row that matches none is not drawn.  Its colour C_row is that style's.
+ *      Box.      bw, bh, xa, xb, ya, yb exactly as the redaction's Region line, and so are the skip conditions (a non-finite
+ *                coordinate, !(bw >= 0), !(bh >= 0), a NaN among the four).  XA = as_i32(xa), XB = as_i32(xb), YA = as_i32(ya),
+ *                YB = as_i32(yb), NOT clipped to the frame: a box leaving the frame draws no line along the frame's edge.  The row
+ *                is also skipped if XB < XA or YB < YA.  All comparisons below are in int64.
+ *      Layer 1, outline (t = thickness > 0).  Pixel (x, y) is on the outline iff XA <= x <= XB and YA <= y <= YB, and
+ *                x < XA + t or x > XB - t or y < YA + t or y > YB - t.
+ *      Layer 2, marks (r = mark_radius > 0).  For each of the five landmarks with both coordinates finite, cx = as_i32(lx) and
+ *                cy = as_i32(ly); the pixel is marked iff (x - cx)^2 + (y - cy)^2 <= r^2.
+ *      Text.     At most 15 glyphs from the set 0-9 - ? % space, with indices 0 .. 13.  label_source = ARRAY: "?" if label[b][i] < 0,
+ *                else its decimal digits.  value_source != NONE: v is value[b][i] or the score boxes[b][i][4]; "--" if v is not
+ *                finite or !(v >= 0), else the decimal digits of min(as_i32(v * 100.0f + 0.5f), 999); then "%".  If both parts are
+ *                present, one space separates them.  len = 0 means no layers 3 and 4.
+ *      Layer 3, plate.  With s = text_scale: PW = s * (6 * len + 1), PH = 9 * s, PX = XA, PY = YA - PH if YA - PH >= 0, else YA
+ *                (above the box when there is room above, inside its top otherwise).  The plate is [PX, PX + PW) x [PY, PY + PH).
+ *      Layer 4, text.  For a plate pixel, fx = (x - PX) div s and fy = (y - PY) div s.  It is a text pixel iff fx >= 1 and fy >= 1,
+ *                k = (fx - 1) div 6 < len, u = (fx - 1) mod 6 < 5, v = fy - 1 < 7, and bit 4 - u of row v of glyph text[k] is set.
+ *                The font is a 5 x 7 bitmap of 14 glyphs; the library holds the only copy (rfd_debug_annotate_glyph reads it).
+ *      Winner.   Among the drawn, non-skipped rows that cover a pixel with any layer, the LOWEST row index wins (row 0 is the best
+ *                score and ends on top); within that row the highest layer wins.  C = text_colour on layer 4, otherwise C_row.
+ *      Output.   A covered pixel with source value P gets, per channel, C if alpha == 256, otherwise (alpha * C + (256 - alpha) * P
+ *                + 128) >> 8; every other pixel its source value.  The result is a pure function of (source frame, rows).
+ *                In place (dst == NULL): no byte of a non-covered pixel and no stride padding is ever written.  Out of place:
+ *                dst[b] has the size of imgs[b] and a stride >= 3 * width, overlaps no source frame, receives all 3 * W bytes of
+ *                every row (its padding is untouched), and the source is untouched.  applied[b] = the number of drawn,
+ *                non-skipped rows of frame b (a row wholly outside the frame counts), written for every b < n.
+ *
+ *      Limits.  One thickness, radius and scale per call; no anti-aliased or vector text and no glyph beyond the 14; no corner
+ *      brackets, trails or legends.  The defaults (rfd_annotate_config_default) are CHOSEN values, not tuned on data.
+ *      Errors, all with nothing enqueued: RFD_ERR_INVALID_ARG with the field named in rfd_last_error() for every bound in the
+ *      config comments, a non-zero reserved word, colour[3] or text_colour[3], a non-zero style at or past n_styles, label_source =
+ *      ARRAY with `label` NULL, value_source = ARRAY with `value` NULL, mark_radius > 0 with dets->landmarks NULL, a NULL required
+ *      pointer (ctx, imgs, dets and its boxes / count), and the redaction's frame and dst checks; RFD_ERR_CAPACITY for n >
+ *      max_batch_size; n = 0 is a no-op.  The context is checked last. ---- */
+#define RFD_ANNOTATE_NONE   0
+#define RFD_ANNOTATE_ARRAY  1
+#define RFD_ANNOTATE_SCORE  2            /* value_source only: the detection's own score, boxes[..][4] */
+#define RFD_ANNOTATE_MAX_STYLES 4
+typedef struct rfd_annotate_style {
+    uint32_t sel_mask, sel_value;
+    uint8_t  colour[4];                  /* B G R 0 */
+} rfd_annotate_style;                    /* 12 bytes */
+typedef struct rfd_annotate_config {
+    int32_t n_styles;                    /* 1 .. 4 */
+    rfd_annotate_style style[RFD_ANNOTATE_MAX_STYLES]; /* entries >= n_styles all zero */
+    int32_t thickness;                   /* 0 .. 16, 0: no outline */
+    int32_t mark_radius;                 /* 0 .. 8, 0: no landmarks; > 0 needs dets->landmarks */
+    int32_t label_source;                /* RFD_ANNOTATE_NONE | RFD_ANNOTATE_ARRAY (needs `label`) */
+    int32_t value_source;                /* RFD_ANNOTATE_NONE | RFD_ANNOTATE_ARRAY (needs `value`) | RFD_ANNOTATE_SCORE */
+    int32_t text_scale;                  /* 1 .. 4 */
+    uint8_t text_colour[4];              /* B G R 0 */
+    int32_t alpha;                       /* 1 .. 256; 256 = opaque */
+    float   margin_x, margin_top, margin_bottom; /* finite, 0 .. 4: the redaction's, so an outline can frame a redacted region */
+    int32_t reserved[4];                 /* 0 */
+} rfd_annotate_config;                   /* 108 bytes */
+/* one style {0, 0, (0, 255, 0)} = every row green; thickness 2, mark_radius 2, label NONE, value SCORE, text_scale 2, text
+ * (0, 0, 0), alpha 256, margins 0: "box, landmarks, score %" */
+RFD_API int rfd_annotate_config_default(rfd_annotate_config *cfg);
+/* Host and device memory as rfd_redact_faces_device: imgs[], dst[] and cfg are host memory; every imgs[i].data and dst[i].data,
+ * the pointers of `dets` (boxes, count, and landmarks when mark_radius > 0), sel, label, value and applied are DEVICE memory.
+ * The call WRITES through dst[i].data -- through imgs[i].data when dst is NULL -- by the same const cast.  Enqueued on the context's
+ * stream, ONE launch whatever the number, sizes and alignment of the frames, no host wait, no global atomics, the same bits on
+ * every run; async = 0 returns after the stream has drained, any other value at once.  The frames of a call may differ in size;
+ * any byte alignment of data and any stride >= 3 * width are legal. */
+RFD_API int rfd_annotate_faces_device(rfd_ctx *ctx, const rfd_image *imgs, const rfd_image *dst /* NULL: in place */, int n,
+                                      const rfd_dets *dets, const uint32_t *sel /* [n][max_det] or NULL */,
+                                      const int32_t *label /* [n][max_det] or NULL */, const float *value /* [n][max_det] or NULL */,
+                                      const rfd_annotate_config *cfg /* NULL: the default */, int32_t *applied /* [n] or NULL */, int async);
+/* Stage-level: the same with host pointers (frames included), through the same kernel; synchronous. */
+RFD_API int rfd_annotate_faces(rfd_ctx *ctx, const rfd_image *imgs, const rfd_image *dst, int n, const rfd_dets *dets, const uint32_t *sel,
+                               const int32_t *label, const float *value, const rfd_annotate_config *cfg, int32_t *applied);
+/* Test hook: the seven rows (top first, bit 4 = the left column) of glyph 0 .. 13 of the font the library was built with. */
+RFD_API int rfd_debug_annotate_glyph(int glyph, uint8_t rows[7]);
 
 /* ---- introspection ---- */
 RFD_API int rfd_get_stats(rfd_ctx *ctx, rfd_stats *stats);

@@ -1125,5 +1125,59 @@ inline void redact_faces_device(RetinaFaceDetection &det, const std::vector<rfd_
     check(rfd_redact_faces_device(det.raw(), imgs.data(), dst, (int)imgs.size(), &dets, sel, cfg, applied, async ? 1 : 0));
 }
 
+// ---- annotation (rfd.h, "annotation"): box outlines, landmarks and text labels drawn into frames ----
+inline rfd_annotate_config annotate_default_config()
+{
+    rfd_annotate_config c;
+    check(rfd_annotate_config_default(&c));
+    return c;
+}
+// The seven rows of glyph 0 .. 13 of the library's font (0-9 - ? % space), top first, bit 4 the left column.
+inline std::array<uint8_t, 7> annotate_glyph(int glyph)
+{
+    std::array<uint8_t, 7> rows{};
+    check(rfd_debug_annotate_glyph(glyph, rows.data()));
+    return rows;
+}
+// Host frames[i] with their detections dets[i] as call_batch returns them (boxes, landmarks, scores), drawn into dst[i] (frames
+// of the same sizes), or in place when dst is empty: the frames' data is then written through.  sel, label, value: empty, or one
+// entry per frame and row (rfd.h); cfg = nullptr: the default.  -> applied per frame.
+inline std::vector<int32_t> annotate_faces(RetinaFaceDetection &det, const std::vector<rfd_image> &frames, const std::vector<rfd_image> &dst,
+                                           const std::vector<Detections> &dets, const std::vector<std::vector<uint32_t>> &sel = {},
+                                           const std::vector<std::vector<int32_t>> &label = {}, const std::vector<std::vector<float>> &value = {},
+                                           const rfd_annotate_config *cfg = nullptr)
+{
+    const std::size_t n = frames.size(), md = det.max_det();
+    if (dets.size() != n) throw Error(RFD_ERR_INVALID_ARG, "annotate faces - one detection list per frame");
+    if (!dst.empty() && dst.size() != n) throw Error(RFD_ERR_INVALID_ARG, "annotate faces - one dst per frame, or none");
+    if ((!sel.empty() && sel.size() != n) || (!label.empty() && label.size() != n) || (!value.empty() && value.size() != n))
+        throw Error(RFD_ERR_INVALID_ARG, "annotate faces - one sel, label and value list per frame, or none");
+    std::vector<float> boxes(n * md * 5), lmk(n * md * 10), values(value.empty() ? 0 : n * md);
+    std::vector<int32_t> count(n), applied(n), labels(label.empty() ? 0 : n * md);
+    std::vector<uint32_t> words(sel.empty() ? 0 : n * md);
+    for (std::size_t i = 0; i < n; ++i) {
+        const std::size_t k = std::min(dets[i].k, md);
+        std::copy(dets[i].det.begin(), dets[i].det.begin() + (std::ptrdiff_t)(k * 5), boxes.begin() + (std::ptrdiff_t)(i * md * 5));
+        std::copy(dets[i].kps.begin(), dets[i].kps.begin() + (std::ptrdiff_t)(k * 10), lmk.begin() + (std::ptrdiff_t)(i * md * 10));
+        count[i] = (int32_t)k;
+        if (!sel.empty()) std::copy_n(sel[i].begin(), std::min(sel[i].size(), md), words.begin() + (std::ptrdiff_t)(i * md));
+        if (!label.empty()) std::copy_n(label[i].begin(), std::min(label[i].size(), md), labels.begin() + (std::ptrdiff_t)(i * md));
+        if (!value.empty()) std::copy_n(value[i].begin(), std::min(value[i].size(), md), values.begin() + (std::ptrdiff_t)(i * md));
+    }
+    const rfd_dets d{boxes.data(), lmk.data(), count.data(), nullptr};
+    check(rfd_annotate_faces(det.raw(), frames.data(), dst.empty() ? nullptr : dst.data(), (int)n, &d, sel.empty() ? nullptr : words.data(),
+                             label.empty() ? nullptr : labels.data(), value.empty() ? nullptr : values.data(), cfg, applied.data()));
+    return applied;
+}
+// DEVICE frames, slabs, sel, label, value and applied (each may be null where rfd.h lets it; dst null: in place), enqueued on the
+// detector's stream; async: no host synchronisation.  The tracker's flags or `who` array is a ready `sel`, `identity` a ready
+// `label`, `id_score` a ready `value`.
+inline void annotate_faces_device(RetinaFaceDetection &det, const std::vector<rfd_image> &imgs, const rfd_image *dst, const rfd_dets &dets,
+                                  const uint32_t *sel, const int32_t *label, const float *value, const rfd_annotate_config *cfg,
+                                  int32_t *applied = nullptr, bool async = false)
+{
+    check(rfd_annotate_faces_device(det.raw(), imgs.data(), dst, (int)imgs.size(), &dets, sel, label, value, cfg, applied, async ? 1 : 0));
+}
+
 } // namespace rfd
 #endif

@@ -34,3 +34,6 @@ echo "built $OBJ/track_identity_demo"
 # the track shots through include/rfd.hpp (tests/test_track_shots_cpp_gpu.py)
 g++ -std=c++17 -O2 -Wall -I"$HERE/../include" "$HERE/../tests/cpp/track_shots_demo.cpp" -o "$OBJ/track_shots_demo" -L"$HERE" -lrfd_hip -Wl,-rpath,'$ORIGIN/..' -Wl,-rpath,"$HERE" -Wl,-rpath,/opt/rocm/lib
 echo "built $OBJ/track_shots_demo"
+# the annotation through include/rfd.hpp (tests/test_annotate_cpp_gpu.py)
+g++ -std=c++17 -O2 -Wall -I"$HERE/../include" "$HERE/../tests/cpp/annotate_demo.cpp" -o "$OBJ/annotate_demo" -L"$HERE" -lrfd_hip -Wl,-rpath,'$ORIGIN/..' -Wl,-rpath,"$HERE" -Wl,-rpath,/opt/rocm/lib
+echo "built $OBJ/annotate_demo"

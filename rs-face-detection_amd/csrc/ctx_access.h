@@ -1,5 +1,5 @@
 // ctx_access.h -- what a layer next to detector.hip may ask of its context.  rfd_ctx stays private to detector.hip, which
-// defines all of these; the layers (gallery, tracker, shot quality, frame conversion, face stage, JPEG encode, redaction) see it through them alone.
+// defines all of these; the layers (gallery, tracker, shot quality, frame conversion, face stage, JPEG encode, redaction, annotation) see it through them alone.
 #pragma once
 #include "host_resources.h"
 
@@ -11,6 +11,7 @@ struct FrameConvert;
 struct FaceStage;
 struct JpegEncoder;
 struct Redact;
+struct Annotate;
 
 // The stream a layer's commands go on (the caller's after rfd_set_stream, so it is asked for at every call), and the device.
 hipStream_t ctx_stream(const rfd_ctx *c);
@@ -24,6 +25,7 @@ FrameConvert &ctx_frame_convert(rfd_ctx *c);
 FaceStage &ctx_face_stage(rfd_ctx *c);
 JpegEncoder &ctx_jpeg_encoder(rfd_ctx *c);
 Redact &ctx_redact(rfd_ctx *c);
+Annotate &ctx_annotate(rfd_ctx *c);
 
 // n images fit the context; the error names them as "<what> n<unit>".  ctx_check_images: n valid 3-channel frames that fit.
 int ctx_check_batch(const rfd_ctx *c, int n, const char *what, const char *unit = "");

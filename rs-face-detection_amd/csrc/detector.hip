@@ -5,7 +5,7 @@
 // This file is the context (rfd_ctx, private to it) and the detection alone: frames in, network, decode / sort / NMS, the
 // views, the pipelined and multi-GPU entries, weights, and the test hooks of those.  Every other stateful layer of the ABI has a
 // file of its own and sees the context through ctx_access.h: the face stage behind the detection (face_host.hip), the JPEG decode
-// (jpeg_host.hip), the JPEG encode (jpeg_encode_host.hip), the frame conversion (frame_host.hip), the shot quality (shot_quality_host.hip), the redaction (redact_host.hip), the face gallery
+// (jpeg_host.hip), the JPEG encode (jpeg_encode_host.hip), the frame conversion (frame_host.hip), the shot quality (shot_quality_host.hip), the redaction (redact_host.hip), the annotation (annotate_host.hip), the face gallery
 // (gallery_host.hip) and the tracker (tracker_host.hip).
 #include <dlfcn.h>
 #include <stdarg.h>
@@ -17,6 +17,7 @@
 #include <mutex>
 #include <vector>
 
+#include "annotate_host.h"
 #include "ctx_access.h"
 #include "face_host.h"
 #include "frame_host.h"
@@ -206,6 +207,7 @@ struct rfd_ctx {
     FrameConvert frames; // frames in camera and decoder formats (rfd.h): frame_host.h
     JpegEncoder encoder; // JPEG encode (rfd.h, "JPEG encode"): jpeg_encode_host.h
     Redact redact; // redaction (rfd.h, "redaction"): redact_host.h
+    Annotate annotate; // annotation (rfd.h, "annotation"): annotate_host.h
     // pipelined host entry (rfd_submit_batch / rfd_collect_batch): two slots, H2D on its own stream
     struct PipeSlot {
         DevBuf frames, imgs, scale, ob, ol, oc, ot;
@@ -758,6 +760,7 @@ ShotQuality &rfd::ctx_shot_quality(rfd_ctx *c) { return c->shot; }
 FrameConvert &rfd::ctx_frame_convert(rfd_ctx *c) { return c->frames; }
 JpegEncoder &rfd::ctx_jpeg_encoder(rfd_ctx *c) { return c->encoder; }
 Redact &rfd::ctx_redact(rfd_ctx *c) { return c->redact; }
+Annotate &rfd::ctx_annotate(rfd_ctx *c) { return c->annotate; }
 FaceStage &rfd::ctx_face_stage(rfd_ctx *c) { return c->face; }
 int rfd::ctx_check_batch(const rfd_ctx *c, int n, const char *what, const char *unit) { return check_batch(c, n, what, unit); }
 int rfd::ctx_check_images(const rfd_ctx *c, const rfd_image *imgs, int n) { return check_images(c, imgs, n); }

@@ -203,6 +203,17 @@ class rfd_redact_config(C.Structure):
                 ("reserved", C.c_int32 * 6)]
 
 
+class rfd_annotate_style(C.Structure):
+    _fields_ = [("sel_mask", C.c_uint32), ("sel_value", C.c_uint32), ("colour", C.c_uint8 * 4)]
+
+
+class rfd_annotate_config(C.Structure):
+    _fields_ = [("n_styles", C.c_int32), ("style", rfd_annotate_style * 4), ("thickness", C.c_int32), ("mark_radius", C.c_int32),
+                ("label_source", C.c_int32), ("value_source", C.c_int32), ("text_scale", C.c_int32), ("text_colour", C.c_uint8 * 4),
+                ("alpha", C.c_int32), ("margin_x", C.c_float), ("margin_top", C.c_float), ("margin_bottom", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
 class rfd_frame(C.Structure):
     _fields_ = [("plane", C.c_void_p * 3), ("stride", C.c_ssize_t * 3), ("width", C.c_int32), ("height", C.c_int32),
                 ("format", C.c_int32), ("color", C.c_int32), ("reserved", C.c_int32 * 4)]
@@ -283,6 +294,7 @@ API_SYMBOLS = [
     "rfd_jpeg_encode_config_default", "rfd_jpeg_encode_bound", "rfd_jpeg_encode_header", "rfd_encode_jpeg_batch_device", "rfd_encode_jpeg_batch",
     "rfd_debug_jpeg_encode_blocks", "rfd_debug_jpeg_encode_coefficients",
     "rfd_redact_config_default", "rfd_redact_faces_device", "rfd_redact_faces",
+    "rfd_annotate_config_default", "rfd_annotate_faces_device", "rfd_annotate_faces", "rfd_debug_annotate_glyph",
 ]
 
 _lib = None
@@ -494,6 +506,11 @@ def load_library(path=None):
     L.rfd_redact_config_default.argtypes = [rcfg]
     L.rfd_redact_faces_device.argtypes = [vp, C.POINTER(rfd_image), C.POINTER(rfd_image), ci, C.POINTER(rfd_dets), vp, rcfg, vp, ci]
     L.rfd_redact_faces.argtypes = [vp, C.POINTER(rfd_image), C.POINTER(rfd_image), ci, C.POINTER(rfd_dets), vp, rcfg, vp]
+    acfg = C.POINTER(rfd_annotate_config)
+    L.rfd_annotate_config_default.argtypes = [acfg]
+    L.rfd_annotate_faces_device.argtypes = [vp, C.POINTER(rfd_image), C.POINTER(rfd_image), ci, C.POINTER(rfd_dets), vp, vp, vp, acfg, vp, ci]
+    L.rfd_annotate_faces.argtypes = [vp, C.POINTER(rfd_image), C.POINTER(rfd_image), ci, C.POINTER(rfd_dets), vp, vp, vp, acfg, vp]
+    L.rfd_debug_annotate_glyph.argtypes = [ci, C.POINTER(C.c_uint8 * 7)]
     if path is None:
         _lib = L
     return L
@@ -1398,6 +1415,40 @@ def redact_config(**fields):
     return c
 
 
+ANNOTATE_NONE, ANNOTATE_ARRAY, ANNOTATE_SCORE = 0, 1, 2   # RFD_ANNOTATE_*: rfd_annotate_config.label_source / value_source
+ANNOTATE_MAX_STYLES = 4                                   # RFD_ANNOTATE_MAX_STYLES
+
+
+def annotate_config(**fields):
+    """rfd_annotate_config: the default (one style: every row green; thickness 2, mark_radius 2, label NONE, value SCORE,
+    text_scale 2, text black, alpha 256, margins 0 -- chosen values, not tuned on data) with the given fields replaced.
+    styles = [(sel_mask, sel_value, (B, G, R)), ...] sets n_styles and style[]; text_colour = (B, G, R)"""
+    c = rfd_annotate_config()
+    _check(load_library().rfd_annotate_config_default(C.byref(c)))
+    for k, v in fields.items():
+        if k == "styles":
+            if len(v) > ANNOTATE_MAX_STYLES:
+                raise TypeError("rfd_annotate_config holds at most %d styles" % ANNOTATE_MAX_STYLES)
+            c.n_styles = len(v)
+            for i in range(ANNOTATE_MAX_STYLES):
+                m, w, col = v[i] if i < len(v) else (0, 0, ())
+                c.style[i] = rfd_annotate_style(m, w, (C.c_uint8 * 4)(*(list(col) + [0] * (4 - len(col)))))
+            continue
+        if k not in dict(rfd_annotate_config._fields_) or k in ("reserved", "style"):
+            raise TypeError("rfd_annotate_config has no field %r" % k)
+        if k == "text_colour":
+            v = (C.c_uint8 * 4)(*(list(v) + [0] * (4 - len(v))))
+        setattr(c, k, v)
+    return c
+
+
+def annotate_glyph(glyph):
+    """rfd_debug_annotate_glyph: the seven rows (top first, bit 4 = the left column) of glyph 0 .. 13 of the library's font"""
+    rows = (C.c_uint8 * 7)()
+    _check(load_library().rfd_debug_annotate_glyph(int(glyph), C.byref(rows)))
+    return list(rows)
+
+
 # rfd_pixel_format and rfd_color (rfd.h, "frames in camera and decoder formats")
 PIXEL_BGR, PIXEL_RGB, PIXEL_BGRA, PIXEL_RGBA, PIXEL_GRAY, PIXEL_NV12, PIXEL_NV21, PIXEL_I420, PIXEL_YUYV, PIXEL_UYVY = range(10)
 COLOR_BT601_LIMITED, COLOR_BT601_FULL, COLOR_BT709_LIMITED, COLOR_BT709_FULL = range(4)
@@ -2051,6 +2102,45 @@ class RetinaFaceDetection:
             applied = np.zeros(n, np.int32)
         d = rfd_dets(b.ctypes.data, None, c.ctypes.data, None)
         _check(self._L.rfd_redact_faces(self._ctx, arr, darr, n, C.byref(d), None if s is None else s.ctypes.data, cp, applied.ctypes.data))
+        return (list(frames) if dst is None else list(dst)), applied
+
+    # ---- annotation: box outlines, landmarks and text labels drawn into frames (rfd.h, "annotation") ----
+    def annotate_faces(self, frames, dets, sel=None, label=None, value=None, cfg=None, device=False, dst=None, applied=None, async_=False):
+        """rfd_annotate_faces / rfd_annotate_faces_device; cfg: an rfd_annotate_config (annotate_config()), None = the default.
+        device=False: frames = HxWx3 u8 BGR arrays (any row stride, unit pixel stride), dets = (boxes [n, max_det, 5], landmarks
+        [n, max_det, 10] or None, count [n]), sel = u32, label = i32, value = f32 [n, max_det] or None; dst = arrays of the frames'
+        shapes to write into, None = in place (the frames themselves are painted) -> (the painted arrays, applied [n] i32).
+        device=True: frames and dst = [(device address, height, width[, stride])], dets = (boxes, landmarks, count) device
+        addresses, sel, label, value and applied = device addresses or None; enqueued on the context's stream, with no host
+        synchronisation when async_ is set."""
+        n, md = len(frames), self.max_det
+        cp = None if cfg is None else C.byref(cfg)
+        if device:
+            def descs(fr):
+                arr = (rfd_image * max(n, 1))()
+                for i, f in enumerate(fr):
+                    arr[i].data, arr[i].height, arr[i].width = f[0], f[1], f[2]
+                    arr[i].stride = f[3] if len(f) > 3 else f[2] * 3
+                return arr
+            d = rfd_dets(dets[0], dets[1], dets[2], None)
+            _check(self._L.rfd_annotate_faces_device(self._ctx, descs(frames), None if dst is None else descs(dst), n, C.byref(d), sel, label,
+                                                     value, cp, applied, int(async_)))
+            return dst, applied
+        for f in list(frames) + list(dst or []):
+            if not (isinstance(f, np.ndarray) and f.dtype == np.uint8 and f.ndim == 3 and f.shape[2] == 3 and f.strides[1:] == (3, 1)):
+                raise RfdError(RFD_ERR_INVALID_ARG, "frames must be HxWx3 uint8 arrays (BGR) with contiguous rows: they are written in place")
+        arr, keep = self._images(frames) if n else ((rfd_image * 1)(), [])
+        darr = None
+        if dst is not None:
+            darr, keep_dst = self._images(dst) if n else ((rfd_image * 1)(), [])
+        whole = lambda a, t, *shape: None if a is None else np.ascontiguousarray(a, t).reshape(n, *shape)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        b, lm, c = whole(dets[0], np.float32, md, 5), whole(dets[1], np.float32, md, 10), whole(dets[2], np.int32)
+        s, lb, va = whole(sel, np.uint32, md), whole(label, np.int32, md), whole(value, np.float32, md)
+        if applied is None:
+            applied = np.zeros(n, np.int32)
+        d = rfd_dets(ptr(b), ptr(lm), ptr(c), None)
+        _check(self._L.rfd_annotate_faces(self._ctx, arr, darr, n, C.byref(d), ptr(s), ptr(lb), ptr(va), cp, applied.ctypes.data))
         return (list(frames) if dst is None else list(dst)), applied
 
     # ---- frames in camera and decoder formats (rfd.h): NV12, I420, YUYV, BGRA ... -> the BGR frames every other call reads ----
